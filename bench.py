@@ -1,7 +1,12 @@
 #!/usr/bin/env python3
 """bench.py — MegaGTA hot path on MI355X: SdBG build (Gk-mer/s) + A* expansions/s + reads->contigs wall.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--reads R] [--k 45]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--reads R] [--k 45] [--dump-outputs DIR] [--full]
+
+A plain run does what the headline figure needs and nothing else: it generates the reads, runs W warm-up steps and K timed steps,
+writes the last timed step's outputs when --dump-outputs is given, and prints the line (metric / value / unit / ms_per_step, the build's
+own roofline from the timed steps' kernel times).  --full adds every other leg described below (search, findstart, denovo, e2e,
+parity_1M, cpu_baseline); without it the options of those legs are ignored.
 
 N = 1 workload = BASELINE.json configs[2], the configuration the metric is quoted on: rplB + nirK, 100 M x 150 bp synthetic reads,
 CLI k = 45 (graph k = 44); `--reads 10000000` is configs[1].  The reads are generated and packed ON the device (seeded; every rank
@@ -13,12 +18,17 @@ so every rank ends with the whole stream.  Work is fixed as N g
 
 One JSON line on rank 0: metric / value / unit per BASELINE.json;
   `roofline`     the dominant kernel of the build (algorithmic bytes / HIP-event duration measured inside the library on its own stream);
+with --full also
   `search`       the A* leg on the graph of that build (graph + HMMs replicated; seeds shard by gene, then round-robin; one all-gather
                  of contigs): expansions/s, achieved bytes/s against the random-line peak the library's own HIP probe measures in the same run;
   `e2e`          reads.fa -> contigs through the driver (`megagta.py -k 30,36,45`, rplB + nirK) on a bounded sample (2 M reads), next to the
                  reference binary behind the same driver on the SAME files (`speedup_same_sample`);
   `parity_1M`    the device's edge stream of the CPU-baseline sample against the reference binary's .sdbg files of it (bit-exact or not);
   `cpu_baseline` the reference `buildgraph` (kind "reference") or the oracle port on this box's host cores, bounded sample.
+
+--dump-outputs DIR: what the last timed step handed back, as .npy files (float64 / float32, ~25 MB; see dump_outputs): the build's counts
+and the edge records it left on the device, summed up whole (value histogram, block sums) and as a fixed, seeded sample.  The same
+arguments give the same inputs in every run, so two builds of the project can be compared output for output.
 """
 from __future__ import annotations
 
@@ -512,6 +522,54 @@ def random_line_probe(ctx, table_bytes: int = 8 << 30) -> dict:
             "idle_dependent_ns": rdep[0]["ns_per_step"]}
 
 
+DUMP_COUNTS = ("n_reads", "n_kmers", "n_items", "n_edges", "n_tips", "n_large", "n_passes")
+DUMP_SAMPLE = 1 << 21                   # records sampled by --dump-outputs (one per stratum of the stream, seeded)
+DUMP_BLOCKS = 4096                      # contiguous blocks of the stream whose record values are summed
+DUMP_CHUNK = 1 << 24                    # records per device pass of the summaries (bounds their temporaries at ~0.5 GB)
+
+
+def dump_outputs(d: str, stats: dict, pieces) -> dict:
+    """--dump-outputs: what the last timed step handed back.  `stats` = its build counts; `pieces` = the edge records it left on the device
+    (uint16 records as uint8 CUDA tensors, in stream order): the resident stream of the build's last pass with one rank, the gathered
+    whole stream with N.  Every value is exact in its dtype (record values < 2^16 in float32, counts and positions < 2^53 in float64).
+      build_counts.npy           float64 [7]      DUMP_COUNTS of the step
+      records_histogram.npy      float64 [65536]  how many records hold each 16-bit value (every record)
+      records_block_sums.npy     float64 [4096]   sum of the record values of each of DUMP_BLOCKS equal contiguous blocks (every record)
+      records_sample.npy         float32 [<=2^21] record values at the positions below
+      records_sample_index.npy   float64 [<=2^21] positions: one per equal stratum of the stream, drawn from a fixed seed"""
+    import torch
+    os.makedirs(d, exist_ok=True)
+    recs = [p.view(torch.int16) for p in pieces if p.numel()]
+    n = sum(int(r.numel()) for r in recs)
+    dev = recs[0].device if recs else torch.device("cuda")
+    hist = torch.zeros(65536, dtype=torch.int64, device=dev)
+    blocks = torch.zeros(DUMP_BLOCKS, dtype=torch.int64, device=dev)
+    m = min(n, DUMP_SAMPLE)
+    lo = np.arange(m, dtype=np.int64) * n // max(1, m)
+    hi = np.arange(1, m + 1, dtype=np.int64) * n // max(1, m)
+    pos = lo + (np.random.default_rng(20240601).random(m) * (hi - lo)).astype(np.int64)      # sorted, distinct, each < n
+    sample = np.zeros(m, dtype=np.float32)
+    base = 0
+    for r in recs:
+        for s in range(0, r.numel(), DUMP_CHUNK):
+            v = r[s:s + DUMP_CHUNK].to(torch.int64) & 0xFFFF
+            hist += torch.bincount(v, minlength=65536)
+            blk = torch.arange(base + s, base + s + v.numel(), dtype=torch.int64, device=dev) * DUMP_BLOCKS // n
+            blocks.index_add_(0, blk, v)
+            del v, blk
+        a, b = np.searchsorted(pos, [base, base + r.numel()])
+        if b > a:
+            idx = torch.from_numpy(pos[a:b] - base).to(dev)
+            sample[a:b] = (r.index_select(0, idx).to(torch.int64) & 0xFFFF).cpu().numpy().astype(np.float32)
+        base += r.numel()
+    out = {"build_counts": np.array([float(stats[c]) for c in DUMP_COUNTS], dtype=np.float64),
+           "records_histogram": hist.cpu().numpy().astype(np.float64), "records_block_sums": blocks.cpu().numpy().astype(np.float64),
+           "records_sample": sample, "records_sample_index": pos.astype(np.float64)}
+    for name, a in out.items():
+        np.save(os.path.join(d, name + ".npy"), a)
+    return {"dir": d, "records": n, "files": sorted(out), "bytes": int(sum(a.nbytes for a in out.values()))}
+
+
 _T0 = time.time()
 
 
@@ -539,7 +597,11 @@ def main():
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--check-stream", action="store_true", help="md5 of the edge records every rank holds after the timed steps (the gathered stream with "
                                                                 "--gpus N, the resident one with one rank) goes into the line: tests compare the two")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None, help="write what the last timed step computed to DIR/<name>.npy (see dump_outputs)")
+    ap.add_argument("--full", action="store_true", help="also run the legs beyond the headline figure: search, findstart, denovo, e2e, CPU baselines, parity")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be at least 1 and --warmup at least 0")
 
     rank = int(os.environ.get("RANK", "0"))
     local_rank = int(os.environ.get("LOCAL_RANK", "0"))
@@ -567,7 +629,7 @@ def main():
     gene_specs = tuple((g.split(":")[0], int(g.split(":")[1])) for g in args.genes.split(","))
     # identical synthetic read set on every rank (seeded), generated and packed on the device
     t0 = time.time()
-    host_sample = max(args.cpu_sample, 1) if rank == 0 and world == 1 else 1      # (the CPU baseline's sample; also the reads the product-mode seeds come from)
+    host_sample = max(args.cpu_sample, 1) if args.full and rank == 0 and world == 1 else 1      # (the CPU baseline's sample; also the reads the product-mode seeds come from)
     mg = synth.make_metagenome_device(args.reads, L, gene_specs, seed=1, device=f"cuda:{local_rank}", host_sample=host_sample)
     t_gen = time.time() - t0
     note(f"{args.reads} reads generated and packed on the device in {t_gen:.1f} s")
@@ -578,7 +640,7 @@ def main():
 
     last_whole = [None]
 
-    def step():
+    def step(last=False):
         g = ctx.build_sdbg(rd, k, collect=False, bucket_range=(b0, b1))
         if args.check_stream and world == 1:
             last_whole[0] = [api.export_records_to_torch(ctx)]
@@ -589,7 +651,7 @@ def main():
             torch.cuda.current_stream().synchronize()
             shard = api.export_records_to_torch(ctx)
             whole = mdist.all_gather_bytes(shard, piece=256 << 20)   # (torch.cat of the pieces = the stream; the graph loader takes them as they are)
-            last_whole[0] = whole if args.check_stream else None
+            last_whole[0] = whole if args.check_stream or (last and args.dump_outputs) else None
             del whole
         return g.stats
 
@@ -607,11 +669,18 @@ def main():
     note("warm-up done")
     t = time.time()
     stats = []
-    for _ in range(args.steps):
-        stats.append(step())
+    for i in range(args.steps):
+        stats.append(step(last=i == args.steps - 1))
     fence()
     dt = time.time() - t
     note(f"{args.steps} build steps: {dt / args.steps * 1e3:.1f} ms each, {stats[-1]['n_passes']} pass(es)")
+    dumped = None
+    if args.dump_outputs and rank == 0:                      # (outside the timed region) the records the last step left: resident / gathered
+        dumped = dump_outputs(args.dump_outputs, stats[-1], last_whole[0] if world > 1 else [api.export_records_to_torch(ctx)])
+        note(f"outputs of the last step: {dumped}")
+    if args.dump_outputs and not args.check_stream:
+        last_whole[0] = None
+        torch.cuda.empty_cache()
     stream_md5 = None
     if args.check_stream and last_whole[0] is not None:      # (outside the timed region) what this rank holds after the exchange, rank by rank in bucket order
         hsh = hashlib.md5()
@@ -629,7 +698,7 @@ def main():
     search = None
     findstart_leg = None
     denovo_leg = None
-    if args.seeds > 0:
+    if args.full and args.seeds > 0:
         from megagta_amd import hmm as hmmlib
         from megagta_amd import findstart as fsm
         ctx.keep_stream(True)
@@ -888,7 +957,9 @@ def main():
             out["findstart"] = findstart_leg
             if denovo_leg is not None:
                 out["denovo"] = denovo_leg
-        if world == 1:
+        if dumped is not None:
+            out["outputs"] = dumped
+        if world == 1 and args.full:
             # free the device before the child processes of the e2e leg ask for it
             rd.free()
             rd._keep = None

@@ -6,7 +6,7 @@ O=$R/gpurun_out/prof_r03
 mkdir -p $O
 export TMPDIR=/tmp
 cd $R
-B="python3 bench.py --no-cpu-baseline --e2e-reads 0"
+B="python3 bench.py --full --no-cpu-baseline --e2e-reads 0"
 echo "== kernel stats"; rocprofv3 --kernel-trace --stats --output-format csv -d $O/stats -o bench -- $B --steps 5 --warmup 1 > $O/stats_line.json 2> $O/stats.err; tail -2 $O/stats.err
 echo "== FETCH_SIZE"; rocprofv3 --pmc FETCH_SIZE --kernel-trace --output-format csv -d $O/fetch -o p -- $B --seeds 0 --steps 2 --warmup 1 > /dev/null 2> $O/fetch.err; tail -1 $O/fetch.err
 echo "== WRITE_SIZE"; rocprofv3 --pmc WRITE_SIZE --kernel-trace --output-format csv -d $O/write -o p -- $B --seeds 0 --steps 2 --warmup 1 > /dev/null 2> $O/write.err; tail -1 $O/write.err

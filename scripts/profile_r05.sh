@@ -10,7 +10,7 @@ O=$R/gpurun_out/prof_r05
 mkdir -p $O
 export TMPDIR=/tmp
 cd $R
-B="python3 bench.py --no-cpu-baseline --e2e-reads 0"
+B="python3 bench.py --full --no-cpu-baseline --e2e-reads 0"
 if [ "$what" = "build" ] || [ "$what" = "all" ]; then
   echo "== kernel stats (build only)"; rocprofv3 --kernel-trace --stats --output-format csv -d $O/stats -o bench -- $B --seeds 0 --steps 5 --warmup 1 > $O/stats_line.json 2> $O/stats.err; tail -2 $O/stats.err
   echo "== FETCH_SIZE"; rocprofv3 --pmc FETCH_SIZE --kernel-trace --output-format csv -d $O/fetch -o p -- $B --seeds 0 --steps 2 --warmup 1 > /dev/null 2> $O/fetch.err; tail -1 $O/fetch.err
@@ -57,7 +57,7 @@ t = out["astar_tcc"]
 if t["expansions_of_all_astar_dispatches"]:
     latest = {"reads": 100000000, "graph_k": 44, "lanes_per_search": 8, "TCC_MISS_sum": t["counters_sum_over_astar_dispatches"].get("TCC_MISS_sum"),
               "TCC_HIT_sum": t["counters_sum_over_astar_dispatches"].get("TCC_HIT_sum"), "expansions": t["expansions_of_all_astar_dispatches"],
-              "command": "rocprofv3 --pmc TCC_HIT_sum TCC_MISS_sum TCP_TCC_READ_REQ_sum TCP_TCC_WRITE_REQ_sum --kernel-trace -- python3 bench.py --no-cpu-baseline --e2e-reads 0 --seeds 60000 --product-seeds 0 --steps 1 --warmup 0",
+              "command": "rocprofv3 --pmc TCC_HIT_sum TCC_MISS_sum TCP_TCC_READ_REQ_sum TCP_TCC_WRITE_REQ_sum --kernel-trace -- python3 bench.py --full --no-cpu-baseline --e2e-reads 0 --seeds 60000 --product-seeds 0 --steps 1 --warmup 0",
               "source_signature": bench.source_signature(*bench.ASTAR_SOURCES), "collected": time.strftime("%Y-%m-%d %H:%M UTC", time.gmtime()), "commit": os.environ.get("MGTA_COMMIT", "?")}
     json.dump(latest, open(f"{O}/astar_counters_latest.json", "w"), indent=1)
 print(json.dumps(out, indent=1)[:1800])

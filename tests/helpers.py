@@ -84,6 +84,22 @@ def parse_probe_astar(lines):
     return res
 
 
+def write_filter_input(path: str) -> None:
+    """seeded contigs for `megagta filterbylen` / `translate`: multi-line records, CRLF, comments, records shorter than 450, lengths not
+    divisible by three, N, no newline at the end"""
+    rng = np.random.default_rng(4)
+    parts = []
+    for i in range(400):
+        L = int(rng.integers(1, 1400))
+        s = "".join("acgtACGTn"[c] for c in rng.integers(0, 9 if i % 17 == 0 else 4, L))
+        head = f">g_contig_{2 * i}_contig_{2 * i + 1}" + (" some comment" if i % 5 == 0 else "")
+        eol = "\r\n" if i % 7 == 0 else "\n"
+        body = eol.join(s[j:j + 70] for j in range(0, L, 70)) if i % 3 == 0 else s
+        parts.append(head + eol + body + eol)
+    text = "".join(parts)
+    open(path, "w", newline="").write(text[:-1])                         # no newline at the end
+
+
 def write_buildlib_inputs(d: str) -> str:
     """seeded read files for `megagta buildlib` (multi-line FASTA with empty reads / N / lower case, gzip'ed paired FASTQ,
     interleaved FASTQ whose quality lines start with '@' and '>'); returns the path of the read_lib file"""

@@ -121,3 +121,32 @@ elif a[0] == "search":
     assert sb["cores"] == 32 and sb["seconds"] == 1.0 and set(sb["seconds_by_threads"]) == {12, 32}
     assert list(sb["crashed_by_threads"]) == [16] and "signal 11" in sb["crashed_by_threads"][16]
     assert sb["expansions"] == 150 + 2 * 10 and sb["value"] == 170.0
+
+
+def test_dump_outputs_summarises_every_record_and_samples_the_same_positions(monkeypatch, tmp_path):
+    """--dump-outputs: the histogram and block sums cover every record of the stream, wherever it is cut into pieces and chunks; the sample
+    is the records at its own (sorted, distinct, seeded) positions; every file is float32 / float64 and the same stream gives the same files"""
+    import torch
+    import bench
+    monkeypatch.setattr(bench, "DUMP_CHUNK", 1000)
+    monkeypatch.setattr(bench, "DUMP_SAMPLE", 500)
+    rng = np.random.default_rng(3)
+    recs = rng.integers(0, 1 << 16, size=12345, dtype=np.uint16)
+    recs[:7] = [0, 1, 0x7FFF, 0x8000, 0xFFFF, 0xFFFF, 2]                  # (the top bit of a record is no sign)
+    stats = {c: i + 1 for i, c in enumerate(bench.DUMP_COUNTS)}
+    raw = torch.from_numpy(recs.view(np.uint8).copy())
+    cuts = [0, 2 * 4000, 2 * 4001, 2 * 4001, 2 * 12345]                   # (an empty piece and a one-record piece among them)
+    info = bench.dump_outputs(str(tmp_path / "a"), stats, [raw[a:b] for a, b in zip(cuts, cuts[1:])])
+    bench.dump_outputs(str(tmp_path / "b"), stats, [raw])
+    out = {n: np.load(tmp_path / "a" / f"{n}.npy") for n in info["files"]}
+    assert info["records"] == recs.size and info["bytes"] == sum(a.nbytes for a in out.values())
+    assert all(a.dtype in (np.float32, np.float64) for a in out.values())
+    for n in info["files"]:
+        assert np.array_equal(out[n], np.load(tmp_path / "b" / f"{n}.npy")), n
+    assert out["build_counts"].tolist() == [float(i + 1) for i in range(len(bench.DUMP_COUNTS))]
+    assert np.array_equal(out["records_histogram"], np.bincount(recs, minlength=65536).astype(np.float64))
+    blk = np.arange(recs.size) * bench.DUMP_BLOCKS // recs.size
+    assert np.array_equal(out["records_block_sums"], np.bincount(blk, weights=recs.astype(np.float64), minlength=bench.DUMP_BLOCKS))
+    pos = out["records_sample_index"].astype(np.int64)
+    assert pos.size == 500 and np.all(np.diff(pos) > 0) and pos[0] >= 0 and pos[-1] < recs.size
+    assert np.array_equal(out["records_sample"], recs[pos].astype(np.float32))

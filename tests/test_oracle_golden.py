@@ -195,19 +195,31 @@ def test_astar_models_beyond_the_lds(oracle, golden_dir, tmp_path, case, mode):
 def test_oracle_sdbg_reader_pinned_by_fresh_reference_files(oracle, golden_dir, tmp_path, case, k, threads):
     """the golden stream MD5s are computed by the oracle's own `.sdbg` reader: pin that reader directly.  A raw-file MD5 cannot serve
     (the reference spreads the buckets over its `.sdbg.N` files by thread timing: two runs of the same command write different bytes),
-    so the reference binary is run HERE, with another thread count than the generator used, and the oracle's decoding of the files it
-    has just written must be the stream the fixture describes; the decoded file set is checked to hold every bucket exactly once."""
+    so the reference binary's files of a run with another thread count than the generator used are decoded, and the oracle's decoding
+    must be the stream the fixture describes; the decoded file set is checked to hold every bucket exactly once.  One such file set is
+    stored under tests/golden/<case>/ref_sdbg/ (make_golden_reference_files.py); when the reference binary is built it also writes a fresh
+    one HERE."""
     import glob
+    import gzip
+    import shutil
     import subprocess
     ref = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "oracle", "_ref", "megagta")
-    if not os.path.exists(ref):
-        pytest.skip("oracle/_ref/megagta (the prebuilt reference) is not present")
     fx = H.load_streams(os.path.join(golden_dir, case, "sdbg_streams.json"))[str(k)]
-    prefix = str(tmp_path / "g")
-    subprocess.run([ref, "buildgraph", "-k", str(k), "-m", "1", "--host_mem", "2000000000", "--mem_flag", "1", "--gpu_mem", "0", "--output_prefix",
-                    prefix, "--num_cpu_threads", str(threads), "--num_output_threads", "1", "--read_lib_file", os.path.join(golden_dir, case, "reads.lib")],
-                   check=True, capture_output=True)
-    assert len(glob.glob(prefix + ".sdbg.*")) >= 1
-    e = oracle.Stream.read(prefix).edges()
-    _stream_matches(e, fx)
-    assert int(e.bucket_items.sum()) == fx["num_edges"]
+    stored = sorted(glob.glob(os.path.join(golden_dir, case, "ref_sdbg", f"k{k}_t{threads}", "g.sdbg*.gz")))
+    assert len(stored) >= 3, "the stored file set: g.sdbg_info + at least two g.sdbg.N"
+    os.makedirs(tmp_path / "stored")
+    for p in stored:
+        with gzip.open(p, "rb") as fi, open(tmp_path / "stored" / os.path.basename(p)[:-3], "wb") as fo:
+            shutil.copyfileobj(fi, fo)
+    prefixes = [str(tmp_path / "stored" / "g")]
+    if os.path.exists(ref):
+        prefix = str(tmp_path / "g")
+        subprocess.run([ref, "buildgraph", "-k", str(k), "-m", "1", "--host_mem", "2000000000", "--mem_flag", "1", "--gpu_mem", "0", "--output_prefix",
+                        prefix, "--num_cpu_threads", str(threads), "--num_output_threads", "1", "--read_lib_file", os.path.join(golden_dir, case, "reads.lib")],
+                       check=True, capture_output=True)
+        prefixes.append(prefix)
+    for prefix in prefixes:
+        assert len(glob.glob(prefix + ".sdbg.*")) >= 1
+        e = oracle.Stream.read(prefix).edges()
+        _stream_matches(e, fx)
+        assert int(e.bucket_items.sum()) == fx["num_edges"]
