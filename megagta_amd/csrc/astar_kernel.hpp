@@ -20,20 +20,13 @@
 
 namespace mgta {
 
-#ifndef MGTA_ASTAR_WAVES
-#define MGTA_ASTAR_WAVES 8
-#endif
-constexpr int kAstarWaves = MGTA_ASTAR_WAVES;                 // waves per workgroup (one workgroup per CU: the HMM tables take most of the LDS)
+constexpr int kAstarWaves = 8;                                // waves per workgroup (one workgroup per CU: the HMM tables take most of the LDS)
 constexpr int kAstarThreads = kAstarWaves * 64;
 constexpr uint32_t kNone = 0x7FFFFFFFu;
 constexpr int kMaxKmer = 160;
 // heap slots of a search kept in LDS: the root block and its eight child blocks (six tree levels); with 8 lanes per search (twice the
 // searches per workgroup) the root block and four child blocks, so that the HMM tables of a 360-column model still fit beside them
-#ifdef MGTA_ASTAR_LDS_HEAP
-constexpr uint32_t lds_heap_slots(int G) { return MGTA_ASTAR_LDS_HEAP; }
-#else
 constexpr uint32_t lds_heap_slots(int G) { return G >= 16 ? 72u : 40u; }
-#endif
 constexpr int kUnitLog = 12;                   // pool offsets are kept in 4 KB units
 constexpr int kNumClasses = 28;                // chunk size classes: 4 KB << c
 constexpr uint32_t kNoChunk = 0xFFFFFFFFu;
@@ -108,9 +101,7 @@ struct PoolDev {
     unsigned int *lock, *cnt;     // [kNumClasses] spin lock and number of free chunks per class
     unsigned int *stack;          // free chunks (4 KB units) of class c at stack[meta[c] .. meta[c] + meta[kNumClasses + c])
     const unsigned int *meta;
-    unsigned long long *stat;     // [0] chunks served by the free lists, [1] failed allocations, [2] re-hashes, [3] searches that grew,
-                                  // [4] bytes handed out and not yet returned, [5] its high-water mark (sampled when a search starts),
-                                  // [6] searches that gave their memory back and started again in place (ordered launches only)
+    unsigned long long *stat;     // [kNumStats], see PoolStat
     unsigned long long soft_limit;   // no new search starts while more than this is in use: the ones that run keep room to grow
     // The RESERVE: the last reserve_bytes of the pool, behind `bytes`, with a bump pointer of its own and no free lists.  Only the LOWEST
     // running search of an ordered launch takes chunks from it, and only when the lists and the bump pointer above have nothing for it
@@ -119,7 +110,58 @@ struct PoolDev {
     // directions take their seeds from two queues, so a search can be the lowest running one for a while and then see a lower one
     // start); the owner resets the bump pointer when it ends or yields; chunks of the reserve never enter a free list.
     unsigned long long reserve_off, reserve_bytes;
-    unsigned long long *rbump;    // [0] next never-used byte of the reserve, [1] its high-water mark over the launch, [2] owner (search id + 1, 0 = free)
+    unsigned long long *rbump;    // [3] ReserveWord (the host points it at AstarArgs::start_limit + kCtlReserve)
+};
+// the words of PoolDev::stat
+enum PoolStat : int {
+    kStatRecycled = 0,            // chunks served by the free lists
+    kStatRefused = 1,             // failed allocations (requests refused)
+    kStatRehash = 2,              // re-hashes (hash table bucket splits)
+    kStatGrown = 3,               // searches that grew beyond their base arena
+    kStatInUse = 4,               // bytes handed out and not yet returned
+    kStatInUseHigh = 5,           // its high-water mark (sampled when a search starts)
+    kStatRestarts = 6,            // searches that gave their memory back and started again in place (ordered launches only)
+    kNumStats = 7
+};
+// the words of PoolDev::rbump
+enum ReserveWord : int {
+    kReserveBump = 0,             // next never-used byte of the reserve
+    kReserveHigh = 1,             // its high-water mark over the launch
+    kReserveOwner = 2             // owner (search id + 1, 0 = free)
+};
+// The pool's metadata block on the device, in 32-bit words: [bump u64][stat u64 x kNumStats][lock NC][cnt NC][meta 2 NC][stacks].
+// The host fills it before a launch and reads its head (PoolHead) back after one.
+struct PoolHead {
+    unsigned long long bump;      // PoolDev::bump
+    unsigned long long stat[kNumStats];
+};
+constexpr size_t kMetaBump = 0, kMetaStat = 2, kMetaLock = kMetaStat + 2 * kNumStats, kMetaCnt = kMetaLock + kNumClasses,
+                 kMetaMeta = kMetaCnt + kNumClasses, kMetaStack = kMetaMeta + 2 * kNumClasses;
+static_assert(sizeof(PoolHead) == kMetaLock * 4, "pool metadata layout");
+
+// AstarArgs::status: how one side of a seed (search 2 * seed + direction) ended
+enum SearchStatus : int32_t {
+    kSearchPending = 0,           // not ended (yet): never started, or cut off by a pass that gave up
+    kSearchDone = 1,
+    kSearchStarved = 2,           // the pool ran dry for it (or its result outgrew out_cap): run again
+    kSearchBadSeed = 3,           // k-mer / model position outside the model
+    kSearchGateTimeout = 4,       // waited at the ordered-commit gate beyond its bound
+    kSearchOverLimit = 5          // one array of the search reached kMaxPages pages (2 GB beyond the base arena: ~33 M nodes): the
+                                  // library's limit, not the device's
+};
+// AstarArgs::start_limit: the control words of an ordered / shared-cache launch (agent-scope atomics; zeroed by the host before each pass)
+enum CtlWord : int {
+    kCtlLimit = 0,                // [0..1] per direction: highest seed index known to be allowed to start (monotone cache of the gate)
+    kCtlScanTime = 2,             // [2..3] per direction: time of the last refresh of that limit by a waiting wave
+    kCtlQuit = 4,                 // the pass has given up: no further seed is taken
+    kCtlMemCall = 5,              // the call for memory (call_for_memory)
+    kCtlEnded = 6,                // [6..7] per direction: searches ended in this pass (slow start)
+    kCtlReserve = 8,              // [8..10] the reserve's words (PoolDev::rbump, ReserveWord)
+    kCtlCaller = 11,              // the lowest search that has called for memory in this episode, + 1
+    kCtlCallerSeen = 12,          // when that caller last called
+    kCtlCacheDrops = 13,          // shared-cache inserts that found no room
+    kCtlUnordered = 14,           // the batch has given up its order (AstarArgs::auto_unorder)
+    kCtlWords = 16
 };
 
 struct AstarArgs {
@@ -143,8 +185,7 @@ struct AstarArgs {
     int log_b0;                   // base arena = 1 << log_b0 nodes, 2 << log_b0 heap slots and 2 << log_b0 hash entries
     mgta_astar_side *sides;       // [2n]
     char *out_seq; uint32_t out_cap; uint32_t *out_len;   // [2n]
-    int32_t *status;              // [2n] 0 = pending, 1 = done, 2 = pool exhausted, 3 = bad seed, 4 = gate timeout, 5 = one array of the search reached
-                                  // kMaxPages pages (2 GB beyond the base arena: ~33 M nodes): the library's limit, not the device's
+    int32_t *status;              // [2n] SearchStatus
     // shared term_nodes caches (search.cpp:182), one per direction.  window = 0: off (cold).  window = B >= 1: the path found by
     // seed j (c_j expansions) is seen by exactly the seeds >= j + B + c_j / cost_rate (cost_rate = 0: no cost term; B = 1 then is
     // the reference's sequential run).  The cost term lets later seeds start while a long search is still running: it cannot
@@ -167,9 +208,7 @@ struct AstarArgs {
     uint32_t cache_probe_limit;   // an insert gives up after this many probes (a missed entry is always correct)
     long long *run_seed;          // [slots] seed a search slot is working on (a lower bound while it is taking one from the queue), -1 = none
     unsigned long long *run_progress;   // [slots] expansions of that search so far (lags; only ever too small)
-    unsigned long long *start_limit;    // [0..1] highest seed index known to be allowed to start (monotone cache of the gate), [2..3] time of the last
-                                        // refresh by a waiting wave, [4] the pass has given up (no further seed is taken), [5] the call
-                                        // for memory (call_for_memory)
+    unsigned long long *start_limit;    // [kCtlWords] the launch's control words, see CtlWord
     uint32_t n_slots;
     uint32_t blocks_dir0;         // workgroups [0, blocks_dir0) search direction 0 (the k-mer, forward model), the rest direction 1: split by the work the
                                   // seeds' model positions promise (a forward search covers M - s columns, a reverse one s), not in halves
@@ -178,7 +217,7 @@ struct AstarArgs {
                                   // first slot of the direction that found its queue empty (from then on the launch only finishes what is in flight: the tail)
     uint32_t ramp_base;           // ordered launches: searches in flight per direction before any has ended (slow start)
     int auto_unorder;             // ordered launches, OPT-IN (MEGAGTA_SEARCH_ALLOW_UNORDERED=1): when the searches in flight have outgrown the pool (thousands of refused requests) the
-                                  // batch gives up the ORDER, not the searches: start_limit[14] is set, from then on every path is visible
+                                  // batch gives up the ORDER, not the searches: start_limit[kCtlUnordered] is set, from then on every path is visible
                                   // to every search as soon as it is inserted and no seed waits at the gate -- the reference's multi-thread
                                   // behaviour (search.cpp:182-189).  Holding the order there means thousands of long searches waiting for
                                   // each other's memory while the seeds behind them wait for their progress (50 M reads, nirK on the multi-k
@@ -258,7 +297,7 @@ __device__ __forceinline__ uint32_t pool_pop(const PoolDev &P, int c) {
 }
 __device__ __forceinline__ uint32_t pool_alloc_one(const PoolDev &P, int c) {
     uint32_t res = pool_pop(P, c);
-    if (res != kNoChunk) __hip_atomic_fetch_add(&P.stat[0], 1ull, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    if (res != kNoChunk) __hip_atomic_fetch_add(&P.stat[kStatRecycled], 1ull, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
     if (res == kNoChunk) {
         const unsigned long long size = 1ull << (c + kUnitLog);
         unsigned long long old = ld_agent(P.bump);
@@ -275,7 +314,7 @@ __device__ __forceinline__ uint32_t pool_alloc_one(const PoolDev &P, int c) {
         res = pool_pop(P, c + e);
         if (res != kNoChunk) res |= (uint32_t)e << kBorrowShift;
     }
-    if (res == kNoChunk) __hip_atomic_fetch_add(&P.stat[1], 1ull, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    if (res == kNoChunk) __hip_atomic_fetch_add(&P.stat[kStatRefused], 1ull, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
     return res;
 }
 __device__ __forceinline__ uint32_t pool_alloc(const PoolDev &P, int c) {
@@ -292,7 +331,7 @@ __device__ __forceinline__ uint32_t pool_alloc(const PoolDev &P, int c) {
     // thousand starved searches asking every iteration (50 M reads, nirK: the one search that could run did 1 500 expansions a second)
     if (__ballot(res != kNoChunk) != 0ull) __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");
     if (res != kNoChunk)                                                  // bytes in use
-        __hip_atomic_fetch_add(&P.stat[4], 1ull << (c + (int)((res >> kBorrowShift) & 3u) + kUnitLog), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        __hip_atomic_fetch_add(&P.stat[kStatInUse], 1ull << (c + (int)((res >> kBorrowShift) & 3u) + kUnitLog), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
     return res;
 }
 // The caller has issued pool_release_fence() since its last store into the chunk.
@@ -301,7 +340,7 @@ __device__ __forceinline__ void pool_free(const PoolDev &P, int c, uint32_t unit
     c += (int)((unit >> kBorrowShift) & 3u);                          // a borrowed chunk goes back to its own list
     unit &= kUnitMask;
     if (P.reserve_bytes != 0ull && ((unsigned long long)unit << kUnitLog) >= P.reserve_off) return;   // the reserve is reset as a whole by its owner
-    __hip_atomic_fetch_sub(&P.stat[4], 1ull << (c + kUnitLog), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    __hip_atomic_fetch_sub(&P.stat[kStatInUse], 1ull << (c + kUnitLog), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
     uint64_t turn = __ballot(true);
     while (turn) {
         const int l = __builtin_ctzll(turn);
@@ -333,12 +372,12 @@ __device__ __forceinline__ void pool_release_fence() {
 // A chunk of the reserve (see PoolDev): called by lane 0 of the one search that owns it.
 __device__ __forceinline__ uint32_t reserve_alloc(const PoolDev &P, int c) {
     const unsigned long long size = 1ull << (c + kUnitLog);
-    const unsigned long long old = __hip_atomic_fetch_add(&P.rbump[0], size, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    const unsigned long long old = __hip_atomic_fetch_add(&P.rbump[kReserveBump], size, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
     if (old + size > P.reserve_bytes) {
-        __hip_atomic_fetch_sub(&P.rbump[0], size, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        __hip_atomic_fetch_sub(&P.rbump[kReserveBump], size, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
         return kNoChunk;
     }
-    __hip_atomic_fetch_max(&P.rbump[1], old + size, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    __hip_atomic_fetch_max(&P.rbump[kReserveHigh], old + size, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
     __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");                // an earlier owner ran on another CU
     return (uint32_t)((P.reserve_off + old) >> kUnitLog);
 }
@@ -346,12 +385,12 @@ __device__ __forceinline__ uint32_t reserve_alloc(const PoolDev &P, int c) {
 // lane 0 of a search that has found itself the lowest running one: claim the reserve (false: an earlier lowest search still holds it)
 __device__ __forceinline__ bool reserve_claim(const PoolDev &P, long long sid) {
     unsigned long long expect = 0ull;
-    return __hip_atomic_compare_exchange_strong(&P.rbump[2], &expect, (unsigned long long)sid + 1ull, __ATOMIC_RELAXED, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    return __hip_atomic_compare_exchange_strong(&P.rbump[kReserveOwner], &expect, (unsigned long long)sid + 1ull, __ATOMIC_RELAXED, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
 }
 // the owner ends or yields (after pool_release_fence(): its dirty lines are written back): everything in the reserve is free again
 __device__ __forceinline__ void reserve_release(const PoolDev &P) {
-    st_agent(&P.rbump[0], 0ull);
-    st_agent(&P.rbump[2], 0ull);
+    st_agent(&P.rbump[kReserveBump], 0ull);
+    st_agent(&P.rbump[kReserveOwner], 0ull);
 }
 
 // One piece of the pool for lane 0 of a search: from the lists / the bump pointer, else (the lowest running search) from the reserve.
@@ -615,7 +654,7 @@ __device__ __forceinline__ void cache_insert(const AstarArgs &a, int dir, uint64
         }
         i = (i + 1) & cmask;
     }
-    __hip_atomic_fetch_add(&a.start_limit[13], 1ull, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);   // no room: counted, reported by the host
+    __hip_atomic_fetch_add(&a.start_limit[kCtlCacheDrops], 1ull, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);   // no room: counted, reported by the host
 }
 
 // the cost term of the sharing rule: c expansions delay a path's visibility by c / rate seeds (rate > 0) or c * |rate| seeds (rate < 0)
@@ -667,34 +706,34 @@ __device__ __forceinline__ long long start_bound(const AstarArgs &a, int dir, in
             }
     }
     bound = wave_min_ll(bound);
-    if (lane == 0 && bound > 0) __hip_atomic_fetch_max(&a.start_limit[dir], (unsigned long long)bound, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    if (lane == 0 && bound > 0) __hip_atomic_fetch_max(&a.start_limit[kCtlLimit + dir], (unsigned long long)bound, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
     return bound;
 }
 
-// start_limit[5]: the call for memory of a search nobody may overtake (the lowest running one when it starves, or one that waits to start
+// start_limit[kCtlMemCall]: the call for memory of a search nobody may overtake (the lowest running one when it starves, or one that waits to start
 // again): first28 << 28 | last28, times in units of 1024 ticks of the 100 MHz clock (~10 us) of the first and the latest call of the
 // episode (calls less than 50 ms apart).  The LEVEL of the call is its age in 10 ms steps: starved searches with fewer than
 // 256 << 2 level expansions give their memory back, so the ones with the least work to lose go first and everybody after 100 ms.
-// start_limit[11]: the lowest search (2 * seed + direction, + 1) that has called in this episode.  Any search that has waited for memory
+// start_limit[kCtlCaller]: the lowest search (2 * seed + direction, + 1) that has called in this episode.  Any search that has waited for memory
 // beyond its patience calls; a starved search ABOVE the caller gives its memory back (by the level rule above), the caller and
 // everything below it keep theirs: the lowest starved search is always served, so a pool that the searches in flight have outgrown
 // together drains from the top instead of standing still.
 __device__ __forceinline__ void call_for_memory(const AstarArgs &a, long long sid) {
-    const unsigned long long now = (__builtin_amdgcn_s_memrealtime() >> 10) & 0xFFFFFFFull, word = ld_agent(&a.start_limit[5]);
+    const unsigned long long now = (__builtin_amdgcn_s_memrealtime() >> 10) & 0xFFFFFFFull, word = ld_agent(&a.start_limit[kCtlMemCall]);
     const unsigned long long last = word & 0xFFFFFFFull, first = (word >> 28) & 0xFFFFFFFull;
     const bool going = word != 0ull && ((now - last) & 0xFFFFFFFull) < 5000ull;
-    // the caller's seat ([11] id + 1, [12] when its holder last called): taken by a lower search, refreshed by its holder, and free again
+    // the caller's seat (kCtlCaller: id + 1, kCtlCallerSeen: when its holder last called): taken by a lower search, refreshed by its holder, and free again
     // 20 ms after the holder's last call (it was served, or it ended)
-    const unsigned long long cur = ld_agent(&a.start_limit[11]), seen = ld_agent(&a.start_limit[12]);
+    const unsigned long long cur = ld_agent(&a.start_limit[kCtlCaller]), seen = ld_agent(&a.start_limit[kCtlCallerSeen]);
     if (!going || cur == 0ull || ((now - seen) & 0xFFFFFFFull) > 2000ull || (unsigned long long)sid + 1ull <= cur) {
-        st_agent(&a.start_limit[11], (unsigned long long)sid + 1ull);
-        st_agent(&a.start_limit[12], now);
+        st_agent(&a.start_limit[kCtlCaller], (unsigned long long)sid + 1ull);
+        st_agent(&a.start_limit[kCtlCallerSeen], now);
     }
-    st_agent(&a.start_limit[5], ((going ? first : now) << 28) | now);
+    st_agent(&a.start_limit[kCtlMemCall], ((going ? first : now) << 28) | now);
 }
-__device__ __forceinline__ long long memory_caller(const AstarArgs &a) { return (long long)ld_agent(&a.start_limit[11]) - 1ll; }
+__device__ __forceinline__ long long memory_caller(const AstarArgs &a) { return (long long)ld_agent(&a.start_limit[kCtlCaller]) - 1ll; }
 __device__ __forceinline__ int memory_call_level(const AstarArgs &a) {          // -1: nobody is calling
-    const unsigned long long now = (__builtin_amdgcn_s_memrealtime() >> 10) & 0xFFFFFFFull, word = ld_agent(&a.start_limit[5]);
+    const unsigned long long now = (__builtin_amdgcn_s_memrealtime() >> 10) & 0xFFFFFFFull, word = ld_agent(&a.start_limit[kCtlMemCall]);
     const unsigned long long last = word & 0xFFFFFFFull, first = (word >> 28) & 0xFFFFFFFull;
     if (word == 0ull || ((now - last) & 0xFFFFFFFull) >= 5000ull) return -1;
     const unsigned long long age = ((last - first) & 0xFFFFFFFull) / 1000ull;
@@ -830,12 +869,12 @@ __global__ __launch_bounds__(kAstarThreads) void astar_kernel(AstarArgs a) {
     uint32_t hp_pages = 0, hp = 0;
     int hL = 0;
     uint32_t n_closed = 0, n_expanded = 0, n_opened = 0;     // (a search of 2^32 expansions would run for a day)
-    int status = 1, partial = 0, ok = 0;
+    int status = kSearchDone, partial = 0, ok = 0;
     uint32_t starved = 0;                                             // iterations this search has waited for memory
     bool yield_check = false;                                         // ordered launch: starved for long -- give the memory back unless this is the lowest running seed
     bool lowest_check = false;                                        // ordered launch: waiting for memory -- is this the lowest running search (the reserve's owner)?
     bool use_reserve = false;                                         // this IS the lowest running search: what the pool cannot give it comes from the reserve
-    bool order_off = a.free_share != 0;                               // paths are shared without an order (asked for, or the batch gave its order up: start_limit[14])
+    bool order_off = a.free_share != 0;                               // paths are shared without an order (asked for, or the batch gave its order up: start_limit[kCtlUnordered])
     uint32_t prog_floor = 0;                                          // expansions already announced for this seed before it started again in place
     bool have_curr = false;                                           // the node to expand is already popped (the search was waiting for memory)
     int32_t goal = -1, inter = 0, cur = 0;
@@ -917,10 +956,10 @@ __global__ __launch_bounds__(kAstarThreads) void astar_kernel(AstarArgs a) {
         if (st == S_IDLE && lslot >= a.active_slots) st = S_EXIT;
         if (st == S_BACKOFF) {    // a search that gave its memory back: it starts again (same seed, same place in the order) once there is room
             unsigned long long used = 0, quit = 0;
-            if (gl == 0) { used = ld_agent(&a.pool.stat[4]); quit = ld_agent(&a.start_limit[4]); }
+            if (gl == 0) { used = ld_agent(&a.pool.stat[kStatInUse]); quit = ld_agent(&a.start_limit[kCtlQuit]); }
             used = GX::bcast(used, 0, gbase);
             quit = GX::bcast(quit, 0, gbase);
-            if (quit) { if (gl == 0) st_agent(&a.run_seed[slot], -1ll); st = S_EXIT; }       // (status stays 0: the pass is run again)
+            if (quit) { if (gl == 0) st_agent(&a.run_seed[slot], -1ll); st = S_EXIT; }       // (status stays kSearchPending: the pass is run again)
             else if (used <= a.pool.soft_limit) { st = S_START; starved = 0; }
             else if ((++starved & 255u) == 0u && gl == 0) call_for_memory(a, sid);   // waiting for room is calling for room too (this may be the
                                                                                       // lowest search of all: the running ones must not sit on what it waits for)
@@ -933,8 +972,8 @@ __global__ __launch_bounds__(kAstarThreads) void astar_kernel(AstarArgs a) {
         unsigned long long used = 0;
         if (st == S_IDLE) {       // admission: searches in flight are bounded by the memory they hold, not only by the number of slots
             if (gl == 0) {
-                used = ld_agent(&a.pool.stat[4]);
-                if (used > ld_agent(&a.pool.stat[5])) __hip_atomic_fetch_max(&a.pool.stat[5], used, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+                used = ld_agent(&a.pool.stat[kStatInUse]);
+                if (used > ld_agent(&a.pool.stat[kStatInUseHigh])) __hip_atomic_fetch_max(&a.pool.stat[kStatInUseHigh], used, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
             }
             used = GX::bcast(used, 0, gbase);
             admit = used <= a.pool.soft_limit;
@@ -942,7 +981,7 @@ __global__ __launch_bounds__(kAstarThreads) void astar_kernel(AstarArgs a) {
         if (st == S_IDLE && admit) {
             long long qi = 0;
             if (gl == 0) {
-                if (a.gate && ld_agent(&a.start_limit[4]) != 0ull) {
+                if (a.gate && ld_agent(&a.start_limit[kCtlQuit]) != 0ull) {
                     qi = n_todo;                                                       // the pass has given up (a search that fits nowhere): take nothing more
                 } else if (a.gate) {
                     // announce a lower bound of the seed about to be taken BEFORE taking it: whoever sees the queue beyond a seed also
@@ -954,7 +993,7 @@ __global__ __launch_bounds__(kAstarThreads) void astar_kernel(AstarArgs a) {
                     // 8192 of them outgrew a 140 GB pool together within ten seconds and the batch stood still).  The searches in
                     // flight per direction start at ramp_base and grow by one with every search that ends, so the memory in use is
                     // known (and the admission rule above works) before every slot is busy.
-                    const unsigned long long done = ld_agent(&a.start_limit[6 + dir]);
+                    const unsigned long long done = ld_agent(&a.start_limit[kCtlEnded + dir]);
                     qi = -1;
                     for (int tries = 0; tries < 4; ++tries) {
                         if (t >= (unsigned long long)n_todo) { qi = (long long)t; break; }   // nothing left to take: the slot retires
@@ -1004,8 +1043,8 @@ __global__ __launch_bounds__(kAstarThreads) void astar_kernel(AstarArgs a) {
                 if (!scan) {
                     long long lim = 0, quit = 0;
                     if (lane == 0) {
-                        lim = (long long)ld_agent(&a.start_limit[dir]); quit = (long long)ld_agent(&a.start_limit[4]);
-                        if (a.auto_unorder && ld_agent(&a.start_limit[14]) != 0ull) lim = 0x7FFFFFFFFFFFFFFFll;   // the order is off: nobody waits
+                        lim = (long long)ld_agent(&a.start_limit[kCtlLimit + dir]); quit = (long long)ld_agent(&a.start_limit[kCtlQuit]);
+                        if (a.auto_unorder && ld_agent(&a.start_limit[kCtlUnordered]) != 0ull) lim = 0x7FFFFFFFFFFFFFFFll;   // the order is off: nobody waits
                     }
                     lim = __shfl(lim, 0, 64);
                     quit = __shfl(quit, 0, 64);
@@ -1016,9 +1055,9 @@ __global__ __launch_bounds__(kAstarThreads) void astar_kernel(AstarArgs a) {
                         int refresh = 0;
                         if (lane == 0) {
                             const unsigned long long now = __builtin_amdgcn_s_memrealtime();     // 100 MHz
-                            unsigned long long last = ld_agent(&a.start_limit[2 + dir]);
+                            unsigned long long last = ld_agent(&a.start_limit[kCtlScanTime + dir]);
                             if (now - last > 5000ull)
-                                refresh = __hip_atomic_compare_exchange_strong(&a.start_limit[2 + dir], &last, now, __ATOMIC_RELAXED, __ATOMIC_RELAXED,
+                                refresh = __hip_atomic_compare_exchange_strong(&a.start_limit[kCtlScanTime + dir], &last, now, __ATOMIC_RELAXED, __ATOMIC_RELAXED,
                                                                                __HIP_MEMORY_SCOPE_AGENT);
                         }
                         scan = __shfl(refresh, 0, 64) != 0;
@@ -1030,7 +1069,7 @@ __global__ __launch_bounds__(kAstarThreads) void astar_kernel(AstarArgs a) {
                     need_scan = false;
                 }
                 if (st == S_WAIT && ++spins > (1u << 22)) {          // bounded wait (counted while the limit stands still): the host reports the seed
-                    if (gl == 0) { a.status[sid] = 4; st_agent(&a.run_seed[slot], -1ll); }
+                    if (gl == 0) { a.status[sid] = kSearchGateTimeout; st_agent(&a.run_seed[slot], -1ll); }
                     st = S_EXIT;
                 }
                 if (__ballot(st == S_START || st == S_RUN) == 0ull) {  // nothing to do in this wave but wait
@@ -1071,14 +1110,14 @@ __global__ __launch_bounds__(kAstarThreads) void astar_kernel(AstarArgs a) {
                     // everything that is handed out cannot be helped by waiting)
                     const unsigned long long own = (unsigned long long)(np_nodes + np_heap + hp_pages) << kPageLog;
                     unsigned long long used = 0;
-                    if (gl == 0) used = ld_agent(&a.pool.stat[4]);
+                    if (gl == 0) used = ld_agent(&a.pool.stat[kStatInUse]);
                     used = GX::bcast(used, 0, gbase);
                     int got = 0;
                     if (!use_reserve && a.pool.reserve_bytes != 0ull && gl == 0) got = reserve_claim(a.pool, sid) ? 1 : 0;
                     if (GX::bcast(got, 0, gbase)) { use_reserve = true; starved = 0; }
                     else if (used <= own || starved > (1u << 18)) {                  // (the second: a backstop -- no room for ten seconds of calling)
-                        status = 2; st = S_DONE;
-                        if (gl == 0) st_agent(&a.start_limit[4], 1ull);                // no further seed is taken: the pass is going to be run again
+                        status = kSearchStarved; st = S_DONE;
+                        if (gl == 0) st_agent(&a.start_limit[kCtlQuit], 1ull);                // no further seed is taken: the pass is going to be run again
                     }
                 } else if (level >= 0 && (uint64_t)n_expanded < (256ull << (2 * level))) {
                     release_all();
@@ -1086,7 +1125,7 @@ __global__ __launch_bounds__(kAstarThreads) void astar_kernel(AstarArgs a) {
                         if (gl == 0) reserve_release(a.pool);
                         use_reserve = false;
                     }
-                    if (gl == 0) __hip_atomic_fetch_add(&a.pool.stat[6], 1ull, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+                    if (gl == 0) __hip_atomic_fetch_add(&a.pool.stat[kStatRestarts], 1ull, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
                     prog_floor = n_expanded > prog_floor ? n_expanded : prog_floor;
                     starved = 0; have_curr = false;
                     st = S_BACKOFF;
@@ -1100,12 +1139,12 @@ __global__ __launch_bounds__(kAstarThreads) void astar_kernel(AstarArgs a) {
             n_nodes = 0; n_heap = 0; n_keys = 0;
             np_nodes = 0; np_heap = 0; hp_pages = 0; hp = 0; hL = 0;
             n_closed = 0; n_expanded = 0; n_opened = 0;
-            status = 1; partial = 0; ok = 0; goal = -1; inter = 0; cur = 0; first = true; starved = 0; have_curr = false;
+            status = kSearchDone; partial = 0; ok = 0; goal = -1; inter = 0; cur = 0; first = true; starved = 0; have_curr = false;
             use_reserve = false; lowest_check = false; yield_check = false;
             if (gl == 0) gt_words[3] = kNoChunk;
             if (a.auto_unorder && !order_off) {
                 int off = 0;
-                if (gl == 0) off = ld_agent(&a.start_limit[14]) != 0ull;
+                if (gl == 0) off = ld_agent(&a.start_limit[kCtlUnordered]) != 0ull;
                 order_off = GX::bcast(off, 0, gbase) != 0;
             }
             for (uint32_t i = (uint32_t)gl; i <= hmask0; i += G) hash_put(base_hash, i, 0ull, 0u);
@@ -1131,7 +1170,7 @@ __global__ __launch_bounds__(kAstarThreads) void astar_kernel(AstarArgs a) {
                 }
             }
             st = S_RUN;
-            if (bad) { status = 3; st = S_DONE; }
+            if (bad) { status = kSearchBadSeed; st = S_DONE; }
             else {
                 curr.parent = -1; curr.state_no = (int16_t)(sstate + n_aa); curr.em_state = (uint16_t)(ST_M << 9); curr.length = (int16_t)n_aa;
                 curr.fval = 0; curr.score = sc; curr.real_score = rs; curr.max_score = 0; curr.negative_count = 0;
@@ -1219,31 +1258,31 @@ __global__ __launch_bounds__(kAstarThreads) void astar_kernel(AstarArgs a) {
             PROF(3)
             // room for this expansion's children: the arena grows in place, the table is re-hashed when half full.  When the pool has
             // nothing to give, the search keeps its popped node and asks again in the next iteration: memory comes back as other
-            // searches end (bounded: after kStarveLimit iterations it gives up with status 2 and is run again by the host)
+            // searches end (bounded: after kStarveLimit iterations it gives up with kSearchStarved and is run again by the host)
             bool wait_mem = false;
             // (a search that is waiting asks again every 8th, later every 64th iteration: thousands of waiting searches asking every
             // iteration keep the allocator's words -- and the memory channels they live in -- busy for everybody)
             const bool ask = starved == 0u || (starved & (starved < 1024u ? 7u : 63u)) == 0u;
             if (!stop && !ask) wait_mem = true;
             if (!stop && !wait_mem && n_nodes + kMaxNew > cap_nodes) {                 // one more page of nodes
-                if ((np_nodes | np_heap | hp_pages) == 0u && gl == 0) __hip_atomic_fetch_add(&a.pool.stat[3], 1ull, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+                if ((np_nodes | np_heap | hp_pages) == 0u && gl == 0) __hip_atomic_fetch_add(&a.pool.stat[kStatGrown], 1ull, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
                 int got = 0;
                 if (gl == 0) got = take_page(pt_nodes, gt_words, np_nodes);
                 got = GX::bcast(got, 0, gbase);
                 tables_written(np_nodes);
                 if (got > 0) ++np_nodes;
-                else if (got < 0) { status = 5; stop = true; }                         // (its own status: not a starvation, nothing to wait for or to resume)
+                else if (got < 0) { status = kSearchOverLimit; stop = true; }          // (its own status: not a starvation, nothing to wait for or to resume)
                 else wait_mem = true;
             }
             if (!stop && !wait_mem && heap_slots_needed(n_heap + kMaxNew) > cap_heap) {    // pages of heap slots (a new block level can ask for several)
                 const uint32_t need = heap_slots_needed(n_heap + kMaxNew);
-                if ((np_nodes | np_heap | hp_pages) == 0u && gl == 0) __hip_atomic_fetch_add(&a.pool.stat[3], 1ull, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+                if ((np_nodes | np_heap | hp_pages) == 0u && gl == 0) __hip_atomic_fetch_add(&a.pool.stat[kStatGrown], 1ull, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
                 while (need > cap_heap) {                                              // (what was obtained is kept: the next attempt goes on from there)
                     int got = 0;
                     if (gl == 0) got = take_page(pt_heap, gt_words + 1, np_heap);
                     got = GX::bcast(got, 0, gbase);
                     tables_written(np_heap);
-                    if (got < 0) { status = 5; stop = true; break; }
+                    if (got < 0) { status = kSearchOverLimit; stop = true; break; }
                     if (!got) { wait_mem = true; break; }
                     ++np_heap;
                 }
@@ -1252,10 +1291,10 @@ __global__ __launch_bounds__(kAstarThreads) void astar_kernel(AstarArgs a) {
             // split in the current round hold up to twice the average): one bucket is split per step
             while (!stop && !wait_mem && (hp_pages == 0u ? (uint64_t)(n_keys + kMaxNew) * 2 > (uint64_t)hmask0 + 1
                                                          : (uint64_t)(n_keys + kMaxNew) * 3 > (uint64_t)hp_pages * kHashPerPage)) {
-                if ((np_nodes | np_heap | hp_pages) == 0u && gl == 0) __hip_atomic_fetch_add(&a.pool.stat[3], 1ull, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+                if ((np_nodes | np_heap | hp_pages) == 0u && gl == 0) __hip_atomic_fetch_add(&a.pool.stat[kStatGrown], 1ull, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
                 const bool first_bucket = hp_pages == 0u;
                 const uint32_t b_old = hp, b_new = hp_pages;                           // the bucket that is split, the bucket it splits into
-                if (b_new >= (uint32_t)kMaxPages) { status = 5; stop = true; break; }  // the table is at its limit
+                if (b_new >= (uint32_t)kMaxPages) { status = kSearchOverLimit; stop = true; break; }   // the table is at its limit
                 // lane 0: the new page(s).  uA takes the place of the split bucket (or is the first bucket), uB is the new bucket
                 uint32_t uA = kNoChunk, uB = kNoChunk, tnew = kNoChunk;
                 if (gl == 0 && b_new < (uint32_t)kMaxPages) {
@@ -1324,7 +1363,7 @@ __global__ __launch_bounds__(kAstarThreads) void astar_kernel(AstarArgs a) {
                         if (!in_pool(u_old) && gt_words[3] == kNoChunk) gt_words[3] = u_old;   // (a page of the reserve: kept for the owner's next split)
                         else pool_free(a.pool, kPageClass, u_old);
                     }
-                    __hip_atomic_fetch_add(&a.pool.stat[2], 1ull, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+                    __hip_atomic_fetch_add(&a.pool.stat[kStatRehash], 1ull, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
                 }
                 tables_written(b_new);
                 if (first_bucket) { hp_pages = 1; hL = 0; hp = 0; }
@@ -1339,8 +1378,8 @@ __global__ __launch_bounds__(kAstarThreads) void astar_kernel(AstarArgs a) {
                 if (a.auto_unorder && !order_off && (starved & 63u) == 1u) {
                     int off = 0;
                     if (gl == 0) {
-                        off = ld_agent(&a.start_limit[14]) != 0ull;
-                        if (!off && ld_agent(&a.pool.stat[1]) > 4096ull) { st_agent(&a.start_limit[14], 1ull); off = 1; }
+                        off = ld_agent(&a.start_limit[kCtlUnordered]) != 0ull;
+                        if (!off && ld_agent(&a.pool.stat[kStatRefused]) > 4096ull) { st_agent(&a.start_limit[kCtlUnordered], 1ull); off = 1; }
                     }
                     order_off = GX::bcast(off, 0, gbase) != 0;
                 }
@@ -1352,7 +1391,7 @@ __global__ __launch_bounds__(kAstarThreads) void astar_kernel(AstarArgs a) {
                 if (++starved > patience) {
                     if (a.gate) {                                                      // ordered launch: yield in place (above), never a host re-run
                         if (((starved - patience) & 255u) == 1u) yield_check = true;
-                    } else { status = 2; stop = true; }
+                    } else { status = kSearchStarved; stop = true; }
                 }
             } else {
                 starved = 0;
@@ -1374,7 +1413,7 @@ __global__ __launch_bounds__(kAstarThreads) void astar_kernel(AstarArgs a) {
                     __hip_atomic_store(&a.run_progress[slot], (unsigned long long)n_expanded, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
                 if (a.auto_unorder && !order_off && (n_expanded & 255u) == 0u) {
                     int off = 0;
-                    if (gl == 0) off = ld_agent(&a.start_limit[14]) != 0ull;
+                    if (gl == 0) off = ld_agent(&a.start_limit[kCtlUnordered]) != 0ull;
                     order_off = GX::bcast(off, 0, gbase) != 0;
                 }
 
@@ -1714,7 +1753,7 @@ __global__ __launch_bounds__(kAstarThreads) void astar_kernel(AstarArgs a) {
             r.fval = 0; r.length = 0; r.state_no = -1; r.state = '-'; r.node_id = -1; r.real_score = 0; r.score = 0;
             uint32_t len = 0;
             char *dst = a.out_seq + (size_t)sid * a.out_cap;
-            if (status == 1 && ok && goal >= 0) {
+            if (status == kSearchDone && ok && goal >= 0) {
                 int32_t best = goal;
                 ANode nd = load_node(node_at((uint32_t)goal));
                 double best_rs = nd.real_score;
@@ -1731,7 +1770,7 @@ __global__ __launch_bounds__(kAstarThreads) void astar_kernel(AstarArgs a) {
                 nd = gn;
                 while (nd.parent >= 0) {
                     if ((nd.em_state >> 9) != ST_D) {
-                        if (len + 3 > a.out_cap) { status = 2; break; }
+                        if (len + 3 > a.out_cap) { status = kSearchStarved; break; }
                         if (gl == 0)
                             for (int t = 0; t < 3; ++t) dst[len + t] = "acgt-"[(nd.em_state >> (3 * t)) & 7];
                         len += 3;
@@ -1761,7 +1800,7 @@ __global__ __launch_bounds__(kAstarThreads) void astar_kernel(AstarArgs a) {
             if (a.gate && gl == 0) {     // the paths are in the cache (atomics, all performed): this search no longer holds anybody back
                 asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
                 st_agent(&a.run_seed[slot], -1ll);
-                __hip_atomic_fetch_add(&a.start_limit[6 + dir], 1ull, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);   // (slow start: one more search may be in flight)
+                __hip_atomic_fetch_add(&a.start_limit[kCtlEnded + dir], 1ull, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);   // (slow start: one more search may be in flight)
             }
             st = S_IDLE;
         }
