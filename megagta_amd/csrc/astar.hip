@@ -716,12 +716,6 @@ int astar_batch_impl(mgta_ctx *ctx, mgta_sdbg *g, const mgta_hmm *fwd, const mgt
         return rc;
     } catch (const HipError &e) { return e.code; }
 }
-// no exception crosses the C boundary: a host allocation that fails inside is an error code like any other
-template <class F> int guarded(const char *who, F &&f) {
-    try { return f(); }
-    catch (const std::bad_alloc &) { set_error("%s: out of host memory", who); return MGTA_ENOMEM; }
-    catch (const std::exception &e) { set_error("%s: %s", who, e.what()); return MGTA_EHIP; }
-}
 }  // namespace
 
 extern "C" {

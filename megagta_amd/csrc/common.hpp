@@ -6,6 +6,8 @@
 #include <cstdint>
 #include <cstdio>
 #include <cstring>
+#include <exception>
+#include <new>
 #include <string>
 #include <vector>
 
@@ -56,6 +58,18 @@ struct DevBuf {
     template <class T> T *as() const { return reinterpret_cast<T *>(p); }
 };
 
+// no exception crosses the C boundary: a device error or a host allocation that fails inside is an error code like any other
+template <class F> int guarded(const char *who, F &&f) {
+    try { return f(); }
+    catch (const HipError &e) { return e.code; }
+    catch (const std::bad_alloc &) { set_error("%s: out of host memory", who); return MGTA_ENOMEM; }
+    catch (const std::exception &e) { set_error("%s: %s", who, e.what()); return MGTA_EHIP; }
+}
+
+// slots of mgta_ctx::pool, the graph build's grow-only device buffers; between builds others may borrow its key buffers S_KEYS_A / S_KEYS_B
+enum Slot { S_BLOCK_COUNT, S_BLOCK_BASE, S_SCAN_TMP, S_SMALL, S_KEYS_A, S_KEYS_B, S_HIST, S_TILE_HEADS, S_TILE_BASE, S_CNT, S_BASE,
+            S_FIRST, S_OUT_REC, S_OUT_LARGE, S_OUT_TIPS, S_PLAN, S_BIG, S_LSD, S_MULTI_COUNT, S_POS2ID, S_SOLID, S_MERCY, S_EDGE_COUNT, S_SIDE, S_NUM };
+
 }  // namespace mgta
 
 namespace mgta {
@@ -103,6 +117,10 @@ struct mgta_ctx {
 namespace mgta {
 inline void ctx_retain(mgta_ctx *c) { __atomic_add_fetch(&c->refs, 1, __ATOMIC_RELAXED); }
 void ctx_release(mgta_ctx *c);    // frees the context when the last reference goes (ctx.hip)
+// the context no longer names the output of its last build (its buffers went, or now belong to something else)
+inline void forget_last_build(mgta_ctx *c) {
+    c->last_rec = nullptr; c->last_tips = nullptr; c->last_first = nullptr; c->last_n_rec = 0; c->last_n_tips = 0; c->last_k = 0;
+}
 }  // namespace mgta
 
 struct mgta_reads {

@@ -78,7 +78,7 @@ int mgta_ctx_keep_stream(mgta_ctx *ctx, int on) {
     ctx->keep_stream = on == 2 ? 2 : on ? 1 : 0;
     if (!on) {
         // after a keep-stream build last_rec / last_tips point INTO the stream buffers: they go with them
-        if (ctx->acc_valid) { ctx->last_rec = nullptr; ctx->last_tips = nullptr; ctx->last_first = nullptr; ctx->last_n_rec = 0; ctx->last_n_tips = 0; ctx->last_k = 0; }
+        if (ctx->acc_valid) mgta::forget_last_build(ctx);
         ctx->acc_rec.release(); ctx->acc_tips.release(); ctx->acc_valid = false;
     }
     return MGTA_OK;
@@ -91,7 +91,7 @@ int mgta_ctx_release_scratch(mgta_ctx *ctx) {
     const bool in_pool = ctx->last_rec && !ctx->acc_valid;      // the last pass's stream lives in the pool: it goes with it
     ctx->pool.clear();
     ctx->astar.pool.release(); ctx->astar.meta.release();
-    if (in_pool) { ctx->last_rec = nullptr; ctx->last_tips = nullptr; ctx->last_first = nullptr; ctx->last_n_rec = 0; ctx->last_n_tips = 0; ctx->last_k = 0; }
+    if (in_pool) mgta::forget_last_build(ctx);
     return MGTA_OK;
 }
 

@@ -983,7 +983,8 @@ static uint64_t pop_bubbles(Work &w, int64_t &n_rounds, int64_t &n_candidates) {
                                                                              std::min<uint64_t>((nb + 63) / 64 * 64 + 64, kBubbleWindowMax) * (uint64_t)b.per * 8));
     scratch_budget = std::min(scratch_budget, need);
     int64_t *scratch_p = nullptr;
-    for (size_t slot = 4; slot <= 5 && slot < w.ctx->pool.size(); ++slot) {      // S_KEYS_A / S_KEYS_B of sdbg_build.hip
+    for (const int slot : {S_KEYS_A, S_KEYS_B}) {
+        if ((size_t)slot >= w.ctx->pool.size()) break;
         DevBuf &kb = w.ctx->pool[slot];
         if (kb.p && kb.bytes >= scratch_budget / 4 && kb.bytes >= (256ull << 20) && (!scratch_p || kb.bytes > b.scratch_bytes)) {
             scratch_p = kb.as<int64_t>(); b.scratch_bytes = kb.bytes;

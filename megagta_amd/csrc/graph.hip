@@ -501,7 +501,7 @@ int mgta_sdbg_stream_detach(mgta_ctx *ctx, mgta_stream **out) {
         st->n_rec = ctx->acc_n_rec; st->n_tip_words = ctx->acc_n_tips * (uint64_t)ctx->last_words_per_tip;
         st->rec = std::move(ctx->acc_rec); st->tips = std::move(ctx->acc_tips);
         ctx->acc_valid = false;
-        ctx->last_rec = nullptr; ctx->last_tips = nullptr; ctx->last_first = nullptr; ctx->last_n_rec = 0; ctx->last_n_tips = 0; ctx->last_k = 0;
+        forget_last_build(ctx);
         ctx_retain(ctx);
         *out = st.release();
         return MGTA_OK;
@@ -592,7 +592,7 @@ int mgta_sdbg_load_resident(mgta_ctx *ctx, mgta_sdbg **out) {
                 // go on naming it (a failure frees it with B; a retry or an export would read freed memory)
                 auto forget_stream = [&]() {
                     ctx->acc_tips.release(); ctx->acc_valid = false;
-                    ctx->last_rec = nullptr; ctx->last_tips = nullptr; ctx->last_first = nullptr; ctx->last_n_rec = 0; ctx->last_n_tips = 0; ctx->last_k = 0;
+                    forget_last_build(ctx);
                 };
                 try {
                     graph_pack(B, B.g->lines.as<uint16_t>(), 0, 0, B.n_lines);
@@ -600,7 +600,7 @@ int mgta_sdbg_load_resident(mgta_ctx *ctx, mgta_sdbg **out) {
                     MGTA_HIP_CHECK(hipStreamSynchronize(ctx->stream));
                     forget_stream();                               // the stream is gone: it IS the graph now
                     return graph_finish(B, out);
-                } catch (const HipError &) { forget_stream(); throw; }
+                } catch (...) { forget_stream(); throw; }
             }
         }
         if (ctx->acc_valid)      // a multi-pass build that kept its whole stream (mgta_ctx_keep_stream): records per bucket are on the host

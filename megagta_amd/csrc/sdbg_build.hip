@@ -9,7 +9,7 @@
 // with a device-resident design (no differential offset lists, no per-bucket CPU threads):
 //
 //   pass over a bucket range [b_lo,b_hi) that fits the memory budget (the analogue of CX1's lv1 loop)
-//     1. items per workgroup: closed form when k+1 is odd and every bucket is wanted (2 (len - k) + 4 per read), else
+//     1. items per workgroup: closed form when every bucket is wanted (2 (len - k) + 4 per read), else
 //        item_scan<count>: one wave per read, one lane per (k+1)-mer position: funnel-shift the edge out of the 2-bit read
 //        array, reverse-complement it in registers, count the <= 6 sort items of the position whose first 8 characters fall
 //        into the range (one scan counts every range that is still ahead)
@@ -502,12 +502,9 @@ __device__ __forceinline__ void get_digits(const Key<W> (&key)[N], Digit d, uint
     for (int i = 0; i < N; ++i) dg[i] = __builtin_amdgcn_alignbit(hi[i], lo[i], (uint32_t)off) & mask;
 }
 
-// tile of workgroup b of n when workgroup b runs on XCD b % 8 (MGTA_XCD_TILES: 1 = contiguous eighths per XCD, 0 = tile b)
-#ifndef MGTA_XCD_TILES
-#define MGTA_XCD_TILES 1
-#endif
+// tile of workgroup b of n when workgroup b runs on XCD b % 8: contiguous eighths of the tiles per XCD
 __device__ __forceinline__ uint32_t xcd_tile(uint32_t b, uint32_t n) {
-    if (!MGTA_XCD_TILES || n < 64) return b;
+    if (n < 64) return b;
     const uint32_t x = b & 7u, idx = b >> 3, q = n >> 3, r = n & 7u;
     return x * q + (x < r ? x : r) + idx;
 }
@@ -693,11 +690,8 @@ __global__ __launch_bounds__(1024) void radix_rowscan_kernel(uint64_t *hist, uin
 
 // keys staged in LDS per round of the scatter: 4096, or 2048 for the 10- and 11-word records of stage 1 at k > 110 (a 4096-key stage
 // of those would not fit the 160 KB); a tile stays 32768 keys either way (census and scatter agree on that)
-#ifndef MGTA_SCATTER_IPT_NARROW
-#define MGTA_SCATTER_IPT_NARROW kItemsPerThread                  // (experiment builds: keys per thread of the staged sub-tile for W <= 3)
-#endif
 template <int W> struct ScatterCfg {
-    static constexpr int kIpt = W >= 10 ? 2 : (W <= 3 ? MGTA_SCATTER_IPT_NARROW : kItemsPerThread);
+    static constexpr int kIpt = W >= 10 ? 2 : kItemsPerThread;
     static constexpr int kSub = kSortThreads * kIpt;
     static constexpr int kChunk = kSub / kSortWaves;
 };
@@ -1721,25 +1715,24 @@ namespace mgta {
 // ---------------------------------------------------------------------------------------------
 // host orchestration
 // ---------------------------------------------------------------------------------------------
-struct Timer {
-    hipEvent_t a, b;
+struct Timer {                   // owns its two events
+    hipEvent_t a = nullptr, b = nullptr;
     hipStream_t st;
     explicit Timer(hipStream_t s) : st(s) { MGTA_HIP_CHECK(hipEventCreate(&a)); MGTA_HIP_CHECK(hipEventCreate(&b)); }
-    ~Timer() { (void)hipEventDestroy(a); (void)hipEventDestroy(b); }
+    Timer(Timer &&o) noexcept : a(o.a), b(o.b), st(o.st) { o.a = o.b = nullptr; }
+    ~Timer() { if (a) (void)hipEventDestroy(a); if (b) (void)hipEventDestroy(b); }
     void start() { MGTA_HIP_CHECK(hipEventRecord(a, st)); }
+    void end() { MGTA_HIP_CHECK(hipEventRecord(b, st)); }        // without waiting: ms() once the stream is past it
+    float ms() const { float t = 0; MGTA_HIP_CHECK(hipEventElapsedTime(&t, a, b)); return t; }
     double stop() {   // milliseconds, synchronises; a launch the runtime rejected inside the phase (grid or LDS limits) surfaces here
         MGTA_HIP_CHECK(hipGetLastError());
-        MGTA_HIP_CHECK(hipEventRecord(b, st));
+        end();
         MGTA_HIP_CHECK(hipEventSynchronize(b));
         MGTA_HIP_CHECK(hipGetLastError());
-        float ms = 0;
-        MGTA_HIP_CHECK(hipEventElapsedTime(&ms, a, b));
-        return ms;
+        return ms();
     }
 };
 
-// most significant digits first: digit i = key bits [32W - 8(i+1), 32W - 8i)
-static Digit top_digit(int W, int i) { return Digit{32 * W - 8 * (i + 1), 8}; }
 // digits of the bits below 32W - T (T = prefix bits the global passes sorted on), least significant first (flags, then characters; the zero pad is skipped)
 static std::vector<Digit> low_digit_plan(int k, int W, int T) {
     std::vector<Digit> plan;
@@ -1749,11 +1742,7 @@ static std::vector<Digit> low_digit_plan(int k, int W, int T) {
     return plan;
 }
 
-// grow-only device buffers kept in the context between calls (multi-k builds, repeated steps):
-// hipMalloc/hipFree of multi-GB buffers costs far more than the kernels that use them.
-enum Slot { S_BLOCK_COUNT, S_BLOCK_BASE, S_SCAN_TMP, S_SMALL, S_KEYS_A, S_KEYS_B, S_HIST, S_TILE_HEADS, S_TILE_BASE, S_CNT, S_BASE,
-            S_FIRST, S_OUT_REC, S_OUT_LARGE, S_OUT_TIPS, S_PLAN, S_BIG, S_LSD, S_MULTI_COUNT, S_POS2ID, S_SOLID, S_MERCY, S_EDGE_COUNT, S_SIDE, S_NUM };
-
+// hipMalloc/hipFree of multi-GB buffers costs far more than the kernels that use them: the pool slots (enum Slot) only grow
 template <class T>
 static T *pool_get(mgta_ctx *ctx, int slot, uint64_t bytes) {
     if ((int)ctx->pool.size() < S_NUM) ctx->pool.resize(S_NUM);
@@ -1772,12 +1761,20 @@ static uint64_t pool_bytes(const mgta_ctx *ctx) {
     return t;
 }
 
-// Sort n keys of WT words ascending on the digits that matter: `max_top` leading bytes may be used for global passes;
-// low_plan_for(P) lists the remaining significant digits (least significant first).  Returns the buffer (a or b) that
-// holds the result, nullptr on an unsupported input (error set).
-// P: smallest number of leading bytes that leaves segments of <= 256 keys on average — up to 1024 rather than a fourth
-// global pass: a 4096-key tile still holds several such segments, and the comparison route needs key bits left in word 0.
-// prefix_frac: share of the leading-byte values the keys can take (a pass over a bucket sub-range only holds that share of
+// MGTA_SORT_BIAS: 0 never, 1 (default) when it saves a pass and leaves short segments, 2 whenever valid (tests) -- see choose_top_plan.
+// MGTA_SORT_SIDE: side digits (see SortJob::uses_side) 0 off, 1 (default) on, 2 on and every side census checked against the census
+// of the keys (tests).  Read once per build and never cached: tests and scripts flip them between builds.
+struct SortModes {
+    int bias = 1, side = 1;
+    static SortModes from_env() {
+        const char *bias = getenv("MGTA_SORT_BIAS"), *side = getenv("MGTA_SORT_SIDE");
+        return SortModes{bias ? atoi(bias) : 1, side ? atoi(side) : 1};
+    }
+};
+
+// The global passes sort on P leading bytes of the keys: the smallest P that leaves segments of <= 256 keys on average -- up to 1024
+// rather than a fourth global pass: a 4096-key tile still holds several such segments, and the comparison route needs key bits left in
+// word 0.  prefix_frac: share of the leading-byte values the keys can take (a pass over a bucket sub-range only holds that share of
 // the prefixes, so its segments are as long as those of the whole key set)
 static double avg_segment_len(uint64_t n_items, int p, double prefix_frac) { return (double)n_items / std::max(1.0, std::pow(256.0, p) * prefix_frac); }
 // The global passes of a build over the buckets [b_lo, b_hi) need not spend digit values on prefixes no key has: word 0 minus
@@ -1789,20 +1786,16 @@ struct TopPlan {
     uint32_t bias = 0;
     double frac = 1.0;           // share of the 2^T prefix values the keys can take
     int T() const { return 8 * P + skip; }
+    // digit of global pass i, most significant first (i = 0: the 8 key bits right below the `skip` bits every key shares, after the bias)
+    Digit pass_digit(int W, int i) const { return Digit{32 * W - 8 * (i + 1) - skip, 8, bias}; }
 };
-static TopPlan choose_top_plan(const mgta_ctx *ctx, uint64_t n_items, int max_top, double prefix_frac, uint32_t b_lo = 0, uint32_t b_hi = 0) {
+// mode: SortModes::bias
+static TopPlan choose_top_plan(const mgta_ctx *ctx, uint64_t n_items, int max_top, double prefix_frac, uint32_t b_lo = 0, uint32_t b_hi = 0,
+                               int mode = 0) {
     TopPlan plain;
     plain.frac = prefix_frac;
     if (ctx && ctx->force_full_lsd) return plain;
-    auto passes = [&](double frac_of, int p_min) {
-        int P = p_min;
-        while (P < max_top && avg_segment_len(n_items, P, frac_of) > (P >= 3 ? 700.0 : 256.0)) ++P;
-        return P;
-    };
-    plain.P = passes(prefix_frac, 0);
-    // 0 never, 1 (default) when it saves a pass and leaves short segments, 2 whenever valid (tests); read per call: scripts flip it between builds
-    const char *mode_env = getenv("MGTA_SORT_BIAS");
-    const int mode = mode_env ? atoi(mode_env) : 1;
+    while (plain.P < max_top && avg_segment_len(n_items, plain.P, prefix_frac) > (plain.P >= 3 ? 700.0 : 256.0)) ++plain.P;
     if (mode == 0 || b_hi <= b_lo || (b_lo == 0 && b_hi >= (uint32_t)MGTA_NUM_BUCKETS)) return plain;
     const uint32_t span = ((b_hi - b_lo) << 16) - 1u;                  // largest biased word 0
     const int skip_full = __builtin_clz(span | 1u);
@@ -1815,109 +1808,101 @@ static TopPlan choose_top_plan(const mgta_ctx *ctx, uint64_t n_items, int max_to
         // only worth skipping when the segments stay short (<= 400 keys).
         const double limit = mode >= 2 ? (P >= 3 ? 700.0 : 256.0) : (P >= 3 ? 400.0 : 256.0);
         if (P < max_top && avg_segment_len(n_items, P, frac) > limit) continue;
-        if (P < plain.P || (mode >= 2 && P <= plain.P)) {
-            TopPlan b;
-            b.P = P; b.skip = skip; b.bias = b_lo << 16; b.frac = frac;
-            return b;
-        }
+        if (P < plain.P || (mode >= 2 && P <= plain.P)) return TopPlan{P, skip, b_lo << 16, frac};
         break;
     }
     return plain;
 }
 
-// first_census_done: the census of the first global pass (digit top_digit(WT, P-1), tiles of kBlockTile keys of `a`) is already in
-// the S_HIST buffer (item_write_tiled_kernel counted while it wrote the keys)
-template <int WT, class LowPlanFn>
-static Key<WT> *device_sort(mgta_ctx *ctx, hipStream_t stream, Key<WT> *a, Key<WT> *b, uint64_t n_items, int max_top, LowPlanFn low_plan_for,
-                            std::vector<std::pair<hipEvent_t, hipEvent_t>> *scatter_ev, mgta_build_stats *S, double prefix_frac = 1.0,
-                            uint32_t mask_last2 = ~0u, uint32_t mask_last = ~0u, bool first_census_done = false, uint32_t b_lo = 0, uint32_t b_hi = 0,
-                            bool first_side_done = false) {
-    const uint64_t n_tiles = (n_items + kBlockTile - 1) / kBlockTile;
-    uint64_t *d_hist = pool_get<uint64_t>(ctx, S_HIST, std::max<uint64_t>(1, n_tiles) * 256 * 8);
+// One sort: n keys of WT words in `a` (`b` is the other buffer of the ping-pong) ascending on the digits that matter: top.P global LSD
+// passes on the leading bytes, then every segment of equal prefix finished inside LDS on the `low` digits.  The key writer of a build
+// pass reads the same object (fused census, side digits), so the writer and the sort cannot disagree on the plan.
+template <int WT>
+struct SortJob {
+    Key<WT> *a = nullptr, *b = nullptr;
+    uint64_t n = 0;
+    TopPlan top;
+    std::vector<Digit> low;                   // the significant digits below the leading top.T() bits, least significant first
+    uint32_t mask_last2 = ~0u, mask_last = ~0u;   // significant bits of the last two key words (LocalPlan)
+    int side_mode = 1;                        // SortModes::side
+    bool census_done = false;                 // the first global pass's census (tiles of kBlockTile keys of a) is already in S_HIST
+    bool side_done = false;                   // S_SIDE already holds the first global pass's digit of every key
+    // side digits: the scatter of a pass leaves the NEXT pass's digit of every key in a byte array (S_SIDE), and that pass's census
+    // reads the bytes instead of the keys
+    bool uses_side() const { return side_mode > 0 && top.P >= 2 && kSideFits<WT>; }
+};
+struct SortLog {                              // what the stats of a build take from its sorts
+    mgta_build_stats *S = nullptr;
+    std::vector<Timer> scatter;               // one per global scatter, read when the build is done (ms_sort_scatter)
+};
+
+// the top.P global passes, least significant digit first; returns the buffer that holds their result, nullptr on an error (set)
+template <int WT>
+static Key<WT> *global_passes(mgta_ctx *ctx, const SortJob<WT> &job, SortLog *log) {
+    hipStream_t stream = ctx->stream;
+    const uint64_t n = job.n, tiles = (n + kBlockTile - 1) / kBlockTile;
+    uint64_t *d_hist = pool_get<uint64_t>(ctx, S_HIST, std::max<uint64_t>(1, tiles) * 256 * 8);
     uint64_t *d_totals = pool_get<uint64_t>(ctx, S_SMALL, 4096) + 8;
-    Key<WT> *src = a, *dst = b;
-    bool side_failed = false;
-    // side digits (MGTA_SORT_SIDE=0 switches them off; 2 checks every side census against the census of the keys): the scatter of
-    // a pass leaves the NEXT pass's digit of every key in a byte array, and that pass's census reads the bytes instead of the keys
-    const char *side_env = getenv("MGTA_SORT_SIDE");
-    const int side_mode = side_env ? atoi(side_env) : 1;
-    const TopPlan tp = choose_top_plan(ctx, n_items, max_top, prefix_frac, b_lo, b_hi);
-    const int P = tp.P, T = tp.T();
-    uint8_t *d_side = side_mode > 0 && P >= 2 && kSideFits<WT> ? pool_get<uint8_t>(ctx, S_SIDE, n_items + 64) : nullptr;
-    bool side_valid = first_side_done && d_side;                        // d_side holds the digits of the pass about to run
-    static const bool unstable_first = !(getenv("MGTA_SORT_UNSTABLE_FIRST") && atoi(getenv("MGTA_SORT_UNSTABLE_FIRST")) == 0);   // (measurements)
-    auto global_pass = [&](Key<WT> *from, Key<WT> *to, uint64_t cnt, const Digit &dg, bool have_census, const Digit *dg_next, bool unstable_ok) {
-        uint64_t tiles = (cnt + kBlockTile - 1) / kBlockTile;
-        if (!have_census) {
+    uint8_t *d_side = job.uses_side() ? pool_get<uint8_t>(ctx, S_SIDE, n + 64) : nullptr;
+    bool side_valid = job.side_done && d_side;                          // d_side holds the digits of the pass about to run
+    const dim3 grid((unsigned)tiles), block(kSortThreads);
+    Key<WT> *src = job.a, *dst = job.b;
+    for (int i = job.top.P - 1; i >= 0; --i) {
+        const bool first = i == job.top.P - 1;
+        const Digit dg = job.top.pass_digit(WT, i), dn = i > 0 ? job.top.pass_digit(WT, i - 1) : Digit{0, 0, 0};
+        if (!(first && job.census_done)) {
             if (side_valid) {
-                hipLaunchKernelGGL(radix_census_side_kernel, dim3((unsigned)tiles), dim3(kSortThreads), 0, stream, d_side, cnt, tiles, d_hist);
-                if (side_mode >= 2) {                                   // (test aid) the same census from the keys must agree
+                hipLaunchKernelGGL(radix_census_side_kernel, grid, block, 0, stream, d_side, n, tiles, d_hist);
+                if (job.side_mode >= 2) {                               // (test aid) the same census from the keys must agree
                     std::vector<uint64_t> h_side(tiles * 256), h_keys(tiles * 256);
                     MGTA_HIP_CHECK(hipStreamSynchronize(stream));
                     MGTA_HIP_CHECK(hipMemcpy(h_side.data(), d_hist, tiles * 256 * 8, hipMemcpyDeviceToHost));
-                    hipLaunchKernelGGL((radix_census_kernel<WT>), dim3((unsigned)tiles), dim3(kSortThreads), 0, stream, from, cnt, dg, tiles, d_hist);
+                    hipLaunchKernelGGL((radix_census_kernel<WT>), grid, block, 0, stream, src, n, dg, tiles, d_hist);
                     MGTA_HIP_CHECK(hipStreamSynchronize(stream));
                     MGTA_HIP_CHECK(hipMemcpy(h_keys.data(), d_hist, tiles * 256 * 8, hipMemcpyDeviceToHost));
-                    if (h_side != h_keys) { set_error("internal: side-digit census differs from the census of the keys"); side_failed = true; }
+                    if (h_side != h_keys) { set_error("internal: side-digit census differs from the census of the keys"); return nullptr; }
                 }
             } else
-                hipLaunchKernelGGL((radix_census_kernel<WT>), dim3((unsigned)tiles), dim3(kSortThreads), 0, stream, from, cnt, dg, tiles, d_hist);
+                hipLaunchKernelGGL((radix_census_kernel<WT>), grid, block, 0, stream, src, n, dg, tiles, d_hist);
         }
         hipLaunchKernelGGL(radix_rowscan_kernel, dim3(256), dim3(1024), 0, stream, d_hist, tiles, d_totals);
-        hipEvent_t e0 = nullptr, e1 = nullptr;
-        if (scatter_ev) {
-            MGTA_HIP_CHECK(hipEventCreate(&e0));
-            MGTA_HIP_CHECK(hipEventCreate(&e1));
-            MGTA_HIP_CHECK(hipEventRecord(e0, stream));
-        }
-        const bool write_side = d_side && dg_next;
-        const Digit dn = dg_next ? *dg_next : Digit{0, 0, 0};
-        const dim3 grid((unsigned)tiles), block(kSortThreads);
+        if (log) log->scatter.emplace_back(stream).start();
+        const bool write_side = d_side && i > 0;
         // (the first pass of the sort orders nothing that was ordered before: its ranks need not be stable)
         auto launch = [&](auto biased, auto side, auto stable) {
-            hipLaunchKernelGGL((radix_scatter_kernel<WT, decltype(biased)::value, decltype(side)::value, decltype(stable)::value>), grid, block, 0, stream, from, to, cnt,
+            hipLaunchKernelGGL((radix_scatter_kernel<WT, decltype(biased)::value, decltype(side)::value, decltype(stable)::value>), grid, block, 0, stream, src, dst, n,
                                dg, tiles, d_hist, d_totals, decltype(side)::value ? d_side : nullptr, dn);
         };
-        auto pick_stable = [&](auto biased, auto side) {
-            if (unstable_ok) launch(biased, side, std::false_type{});
-            else launch(biased, side, std::true_type{});
-        };
+        auto pick_stable = [&](auto biased, auto side) { first ? launch(biased, side, std::false_type{}) : launch(biased, side, std::true_type{}); };
         auto pick_side = [&](auto biased) {
             if constexpr (kSideFits<WT>) {
                 if (write_side) { pick_stable(biased, std::true_type{}); return; }
             }
             pick_stable(biased, std::false_type{});
         };
-        if (dg.bias) pick_side(std::true_type{});
-        else pick_side(std::false_type{});
+        dg.bias ? pick_side(std::true_type{}) : pick_side(std::false_type{});
         side_valid = write_side;
-        if (scatter_ev) {
-            MGTA_HIP_CHECK(hipEventRecord(e1, stream));
-            scatter_ev->emplace_back(e0, e1);
-            if (S) S->n_sort_launches++;
-        }
-        return 0;
-    };
-    auto pass_digit = [&](int i) {
-        Digit dg = top_digit(WT, i);
-        dg.pos -= tp.skip;
-        dg.bias = tp.bias;
-        return dg;
-    };
-    for (int i = P - 1; i >= 0; --i) {
-        const Digit dg = pass_digit(i), dn = i > 0 ? pass_digit(i - 1) : Digit{0, 0, 0};
-        if (global_pass(src, dst, n_items, dg, first_census_done && i == P - 1, i > 0 ? &dn : nullptr, unstable_first && i == P - 1)) return nullptr;
-        if (side_failed) return nullptr;
+        if (log) { log->scatter.back().end(); log->S->n_sort_launches++; }
         std::swap(src, dst);
     }
-    const std::vector<Digit> low = low_plan_for(T);
+    return src;
+}
+
+// every segment of equal leading top.T() bits finished inside LDS (local_sort_kernel, local_lsd_kernel), segments that did not fit a
+// tile on their own (segment_lds_kernel, segment_sort_kernel).  `src` holds the keys, `dst` is scratch.  Returns src, nullptr on an
+// error (set).
+template <int WT>
+static Key<WT> *lds_finish(mgta_ctx *ctx, const SortJob<WT> &job, Key<WT> *src, Key<WT> *dst, SortLog *log) {
+    hipStream_t stream = ctx->stream;
+    const uint64_t n_items = job.n;
+    const int T = job.top.T();
+    const std::vector<Digit> &low = job.low;
     if (low.size() > 64) { set_error("too many sort digits"); return nullptr; }
     Digit *d_plan = pool_get<Digit>(ctx, S_PLAN, 64 * sizeof(Digit));
     MGTA_HIP_CHECK(hipMemcpyAsync(d_plan, low.data(), low.size() * sizeof(Digit), hipMemcpyHostToDevice, stream));
     // room behind the stride for the last segment of a tile: ~2.5 average segments, an eighth of the tile at least, half at most
-    const double avg_seg = avg_segment_len(n_items, P, tp.frac);
-    static const double margin_factor = getenv("MGTA_SORT_MARGIN") ? atof(getenv("MGTA_SORT_MARGIN")) : 2.5;      // (measurement knob)
-    uint32_t margin = (uint32_t)std::min<double>(LocalCfg<WT>::kTile / 2, std::max<double>(LocalCfg<WT>::kTile / 8, margin_factor * avg_seg));
+    const double avg_seg = avg_segment_len(n_items, job.top.P, job.top.frac);
+    uint32_t margin = (uint32_t)std::min<double>(LocalCfg<WT>::kTile / 2, std::max<double>(LocalCfg<WT>::kTile / 8, 2.5 * avg_seg));
     margin = (margin + 63u) & ~63u;
     const uint32_t stride = (uint32_t)LocalCfg<WT>::kTile - margin;
     const uint64_t l_blocks = (n_items + stride - 1) / stride;
@@ -1927,25 +1912,17 @@ static Key<WT> *device_sort(mgta_ctx *ctx, hipStream_t stream, Key<WT> *a, Key<W
     uint32_t *d_big_count = reinterpret_cast<uint32_t *>(d_big + 2 * (uint64_t)big_cap);
     MGTA_HIP_CHECK(hipMemsetAsync(d_big_count, 0, 8, stream));
     uint64_t *d_lsd = pool_get<uint64_t>(ctx, S_LSD, 2 * l_blocks * 8);
-    hipEvent_t le0, le1;
-    MGTA_HIP_CHECK(hipEventCreate(&le0));
-    MGTA_HIP_CHECK(hipEventCreate(&le1));
-    MGTA_HIP_CHECK(hipEventRecord(le0, stream));
-    LocalPlan lp;
-    lp.low_plan = d_plan;
-    lp.n_low = (int)low.size();
-    lp.T = T;
+    Timer t(stream);
+    t.start();
     // the comparison route is skipped for a few sorts after one that found mostly long runs (highly redundant input)
     const bool skip_a = ctx->lsd_skip_left > 0;
     if (skip_a) --ctx->lsd_skip_left;
     const int ub = ((ctx->force_lsd_tiles & 1) || skip_a) ? 0 : std::max(0, std::min(8, (WT > 1 ? 40 : 32) - T));
+    LocalPlan lp;
+    lp.low_plan = d_plan; lp.n_low = (int)low.size(); lp.T = T;
     lp.upper = Digit{32 * WT - T - ub, ub};
-    lp.mask_last2 = mask_last2;
-    lp.mask_last = mask_last;
-    lp.stride = stride;
-    lp.lsd_list = d_lsd;
-    lp.lsd_count = d_big_count + 1;
-    lp.lsd_cap = (uint32_t)l_blocks;
+    lp.mask_last2 = job.mask_last2; lp.mask_last = job.mask_last; lp.stride = stride;
+    lp.lsd_list = d_lsd; lp.lsd_count = d_big_count + 1; lp.lsd_cap = (uint32_t)l_blocks;
     lp.debug = ctx->force_lsd_tiles >> 1;
     if (ub > 0)
         hipLaunchKernelGGL((local_sort_kernel<WT, true>), dim3((unsigned)l_blocks), dim3(kSortThreads), 0, stream, src, n_items, lp, d_big, d_big_count,
@@ -1953,61 +1930,46 @@ static Key<WT> *device_sort(mgta_ctx *ctx, hipStream_t stream, Key<WT> *a, Key<W
     else
         hipLaunchKernelGGL((local_sort_kernel<WT, false>), dim3((unsigned)l_blocks), dim3(kSortThreads), 0, stream, src, n_items, lp, d_big, d_big_count,
                            big_cap);
-    MGTA_HIP_CHECK(hipEventRecord(le1, stream));
+    t.end();
     uint32_t n_big = 0, n_lsd_tiles = 0;
     MGTA_HIP_CHECK(hipMemcpyAsync(&n_lsd_tiles, d_big_count + 1, 4, hipMemcpyDeviceToHost, stream));
     MGTA_HIP_CHECK(hipMemcpyAsync(&n_big, d_big_count, 4, hipMemcpyDeviceToHost, stream));
     MGTA_HIP_CHECK(hipStreamSynchronize(stream));
-    float ms_local = 0;
-    MGTA_HIP_CHECK(hipEventElapsedTime(&ms_local, le0, le1));
+    const float ms_local = t.ms();
     if (n_big > big_cap) { set_error("more than %u oversized key segments in one pass", big_cap); return nullptr; }
     if (n_lsd_tiles > lp.lsd_cap) { set_error("internal: tile list overflow"); return nullptr; }
     if (ub > 0 && l_blocks >= 64 && 2 * (uint64_t)n_lsd_tiles > l_blocks) ctx->lsd_skip_left = 7;   // then look again
-    MGTA_HIP_CHECK(hipEventRecord(le0, stream));
+    t.start();
     if (n_lsd_tiles > 0 && !(lp.debug & 2))
         hipLaunchKernelGGL((local_lsd_kernel<WT>), dim3(n_lsd_tiles), dim3(kSortThreads), 0, stream, src, d_lsd, d_lsd + 1, 2, lp);
     if (n_big > 0) {
         // segments that did not fit a tile next to their neighbours: alone in LDS if they fit, else (hot k-mers, or the whole array
         // when it is tiny) one workgroup each with global ping-pong passes
         hipLaunchKernelGGL((segment_end_kernel<WT>), dim3(n_big), dim3(256), 0, stream, src, n_items, T, d_big, d_big + big_cap);
-        if (getenv("MGTA_SORT_DIAG")) {                               // (measurement aid) sizes of the deferred segments of this sort
-            std::vector<uint64_t> s(n_big), e(n_big);
-            MGTA_HIP_CHECK(hipStreamSynchronize(stream));
-            MGTA_HIP_CHECK(hipMemcpy(s.data(), d_big, n_big * 8ull, hipMemcpyDeviceToHost));
-            MGTA_HIP_CHECK(hipMemcpy(e.data(), d_big + big_cap, n_big * 8ull, hipMemcpyDeviceToHost));
-            uint64_t hist[40] = {}, keys[40] = {}, mx = 0;
-            for (uint32_t i = 0; i < n_big; ++i) {
-                const uint64_t c = e[i] - s[i];
-                const int b = c ? 64 - __builtin_clzll(c) : 0;
-                hist[b]++; keys[b] += c; mx = std::max(mx, c);
-            }
-            fprintf(stderr, "[sort diag] %u deferred segments of %llu keys, longest %llu:", n_big, (unsigned long long)n_items, (unsigned long long)mx);
-            for (int b = 0; b < 40; ++b)
-                if (hist[b]) fprintf(stderr, " <2^%d: %llu (%llu keys)", b, (unsigned long long)hist[b], (unsigned long long)keys[b]);
-            fprintf(stderr, "\n");
-        }
         hipLaunchKernelGGL((local_lsd_kernel<WT>), dim3(n_big), dim3(kSortThreads), 0, stream, src, d_big, d_big + big_cap, 1, lp);
-        static const bool big_tile = !getenv("MGTA_SORT_NO_BIG_TILE");  // (measurement knob)
-        const bool use_big = BigCfg<WT>::kTile > 0 && big_tile && !low.empty();
+        const bool use_big = BigCfg<WT>::kTile > 0 && !low.empty();
         if (use_big) hipLaunchKernelGGL((segment_lds_kernel<WT>), dim3(n_big), dim3(kSortThreads), 0, stream, src, d_big, d_big + big_cap, lp);
         hipLaunchKernelGGL((segment_sort_kernel<WT>), dim3(n_big), dim3(kSortThreads), 0, stream, src, dst, d_big, d_big + big_cap, d_plan,
                            (int)low.size(), (uint32_t)(use_big ? BigCfg<WT>::kTile : LocalCfg<WT>::kTile));
     }
-    MGTA_HIP_CHECK(hipEventRecord(le1, stream));
-    MGTA_HIP_CHECK(hipEventSynchronize(le1));
-    {
-        float ms = 0;
-        MGTA_HIP_CHECK(hipEventElapsedTime(&ms, le0, le1));
-        if (S) { S->ms_local_sort += ms_local + ms; S->n_lsd_tiles += n_lsd_tiles; S->n_big_segments += n_big; }
-        (void)hipEventDestroy(le0); (void)hipEventDestroy(le1);
-    }
+    t.end();
+    MGTA_HIP_CHECK(hipEventSynchronize(t.b));
+    const float ms = t.ms();
+    if (log) { log->S->ms_local_sort += ms_local + ms; log->S->n_lsd_tiles += n_lsd_tiles; log->S->n_big_segments += n_big; }
     return src;
+}
+
+// Sort job.n keys (see SortJob).  Returns the buffer (a or b) that holds the result, nullptr on an unsupported input (error set).
+template <int WT>
+static Key<WT> *device_sort(mgta_ctx *ctx, const SortJob<WT> &job, SortLog *log = nullptr) {
+    Key<WT> *src = global_passes(ctx, job, log);
+    return src ? lds_finish(ctx, job, src, src == job.a ? job.b : job.a, log) : nullptr;
 }
 
 // ---- stage 1 (min_count >= 2): fills the is_solid bit-vector (+ mercy edges) that stage 2 then honours -------------
 template <int W>
 static int run_stage1(mgta_ctx *ctx, const mgta_reads *rd, uint64_t n_short, int k, int min_count, int need_mercy, uint64_t budget,
-                      unsigned long long **is_solid_out, int *num_k1_out, mgta_build_stats *S) {
+                      int side_mode, unsigned long long **is_solid_out, int *num_k1_out) {
     constexpr int WT = W + 2;                                          // key words (= words_per_substring of s1, s1.cpp:248) + 64-bit payload
     hipStream_t stream = ctx->stream;
     const uint64_t n_reads = rd->n_reads;
@@ -2088,7 +2050,9 @@ static int run_stage1(mgta_ctx *ctx, const mgta_reads *rd, uint64_t n_short, int
                 return plan;
             };
             const int max_top = std::min(4, std::max(0, (2 * (k - 1)) / 8));
-            Key<WT> *sorted = device_sort<WT>(ctx, stream, d_a, d_b, n_items, max_top, low_plan, nullptr, nullptr, (double)(b_hi - b_lo) / MGTA_NUM_BUCKETS, 0u, 0x3Fu);
+            SortJob<WT> job{d_a, d_b, n_items, choose_top_plan(ctx, n_items, max_top, (double)(b_hi - b_lo) / MGTA_NUM_BUCKETS)};
+            job.low = low_plan(job.top.T()); job.mask_last2 = 0u; job.mask_last = 0x3Fu; job.side_mode = side_mode;
+            Key<WT> *sorted = device_sort(ctx, job);
             if (!sorted) return MGTA_EUNSUPPORTED;
             char *scratch = reinterpret_cast<char *>(sorted == d_a ? d_b : d_a);
             uint64_t e_tiles = (n_items + kEmitTile - 1) / kEmitTile;
@@ -2128,7 +2092,9 @@ static int run_stage1(mgta_ctx *ctx, const mgta_reads *rd, uint64_t n_short, int
                 for (int pos = 0; pos < 64 - T; pos += 8) plan.push_back(Digit{pos, std::min(8, 64 - T - pos)});
                 return plan;
             };
-            Key<2> *cs = device_sort<2>(ctx, stream, d_mercy, d_tmp, n_cand, 4, low64, nullptr, nullptr);
+            SortJob<2> job{d_mercy, d_tmp, n_cand, choose_top_plan(ctx, n_cand, 4, 1.0)};
+            job.low = low64(job.top.T()); job.side_mode = side_mode;
+            Key<2> *cs = device_sort(ctx, job);
             if (!cs) return MGTA_EUNSUPPORTED;
             if ((int)max_len <= kMercyMaxLen) {
                 hipLaunchKernelGGL(mercy_kernel<false>, dim3((unsigned)((n_cand + 255) / 256)), dim3(256), 0, stream, cs, n_cand, rd->d_start, n_reads, k,
@@ -2147,111 +2113,148 @@ static int run_stage1(mgta_ctx *ctx, const mgta_reads *rd, uint64_t n_short, int
             }
         }
     }
-    (void)S;
     *is_solid_out = d_solid;
     *num_k1_out = num_k1;
     return MGTA_OK;
 }
 
+// ---- stage 2: a loop over bucket ranges (passes) that fit the memory budget; a pass counts its sort items, writes the keys, sorts
+// them and emits the edges of its buckets
+struct Pass {                                  // one bucket range [b_lo, b_hi) and what the stages make of it
+    uint32_t b_lo = 0, b_hi = 0, width = 0;
+    bool closed_form = false;                  // every bucket, no stage-1 verdicts: items and keys by the closed-form layout
+    uint64_t n_items = 0, n_tiles = 0, key_b = 0;   // sort items, tiles of the global sort passes, bytes of each key buffer
+    uint64_t n_edges = 0, n_large = 0, n_tips = 0;
+    uint16_t *rec = nullptr, *large = nullptr; // the pass's output in the pool
+    uint32_t *tips = nullptr;
+    int64_t *first = nullptr;
+    uint32_t nb() const { return b_hi - b_lo; }
+};
+
 template <int W>
-static int build_impl(mgta_ctx *ctx, const mgta_reads *rd, uint64_t n_short, int k, int min_count, int need_mercy, uint32_t bucket_begin,
-                      uint32_t bucket_end, mgta_edge_sink sink, void *user, mgta_build_stats *st) {
+struct Build {                                 // a build of keys of W words: what its stages share, and the stages
+    mgta_ctx *ctx;
     hipStream_t stream = ctx->stream;
-    MGTA_HIP_CHECK(hipSetDevice(ctx->device));
-    const int words_per_tip = (2 * k + 31) / 32;                       // sdbg_multi_io.h:63
-    const uint64_t n_reads = rd->n_reads;
-    const uint64_t n_blocks = (n_reads + kReadsPerBlock - 1) / kReadsPerBlock;
-    // the scan kernels run one workgroup of kScanBlock threads per kReadsPerBlock reads: a dispatch holds fewer than 2^32 work-items
-    if (n_blocks * (uint64_t)kScanBlock >= (1ull << 32)) { set_error("too many reads for one launch (%llu)", (unsigned long long)n_reads); return MGTA_EUNSUPPORTED; }
-    mgta_build_stats S;
-    memset(&S, 0, sizeof(S));
-    S.k = k; S.words_per_key = W; S.words_per_tip = words_per_tip; S.n_reads = (int64_t)n_reads;
-    ctx->peak_bytes = ctx->live_bytes;
-
-    size_t free_b = 0, total_b = 0;
-    MGTA_HIP_CHECK(hipMemGetInfo(&free_b, &total_b));
-    // what the build may hold: the explicit limit, else 90 % of (free + what our pool already holds)
-    uint64_t avail = (uint64_t)free_b + pool_bytes(ctx);
-    uint64_t budget = ctx->mem_limit ? std::min<uint64_t>(ctx->mem_limit, avail) : (uint64_t)(avail * 0.9);
-
-    // whole-stream hand-off of a multi-pass build (mgta_ctx_keep_stream)
-    const bool acc = ctx->keep_stream != 0;           // (of a bucket sub-range too: the shard a rank hands to the all-gather)
-    const double range_frac = (double)(bucket_end - bucket_begin) / (double)MGTA_NUM_BUCKETS;
-    ctx->acc_valid = false;
-    ctx->acc_n_rec = 0; ctx->acc_n_tips = 0;
-    if (acc) ctx->acc_items.assign(MGTA_NUM_BUCKETS, 0);
-    std::vector<int64_t> acc_first;
-
-    Timer t_all(stream), t_ph(stream);
-    std::vector<std::pair<hipEvent_t, hipEvent_t>> scatter_ev;
-    uint32_t *d_block_count = pool_get<uint32_t>(ctx, S_BLOCK_COUNT, std::max<uint64_t>(1, n_blocks) * 4);
-    uint64_t *d_block_base = pool_get<uint64_t>(ctx, S_BLOCK_BASE, std::max<uint64_t>(1, n_blocks) * 8);
-    uint64_t *d_small = pool_get<uint64_t>(ctx, S_SMALL, 4096);       // [0] total, [1] kmers, [2..4] emit totals, [5] sentinels, [8..263] digit totals
-    uint64_t *d_total = d_small, *d_kmers = d_small + 1, *d_tot3 = d_small + 2, *d_sentinel = d_small + 5;
-
-    ScanArgs sa;
-    sa.packed = rd->d_packed; sa.n_words = rd->n_words; sa.start = rd->d_start; sa.n_reads = n_reads; sa.k = k;
-    sa.block_count = d_block_count; sa.block_base = d_block_base; sa.out = nullptr;
-    sa.n_kmers = (unsigned long long *)d_kmers;
-    sa.n_sentinel = (unsigned long long *)d_sentinel;
-    sa.is_solid = nullptr; sa.num_k1_per_read = 0; sa.n_short = n_short;
-    sa.side = nullptr; sa.side_shift = 0; sa.side_bias = 0;
-    if (min_count > 1) {
-        unsigned long long *sol = nullptr;
-        int nk1 = 0;
-        int rc1 = MGTA_EUNSUPPORTED;
-        Timer t_s1(stream);
-        t_s1.start();
-        if constexpr (W <= 9) rc1 = run_stage1<W>(ctx, rd, n_short, k, min_count, need_mercy, budget, &sol, &nk1, &S);
-        else set_error("min_count > 1: a key of %d words is not supported", W);
-        if (rc1 != MGTA_OK) return rc1;
-        S.ms_stage1 = t_s1.stop();
-        sa.is_solid = sol; sa.num_k1_per_read = nk1;
-        // run_stage1 may have re-grown pool slots: refresh the small pointers
-        d_block_count = pool_get<uint32_t>(ctx, S_BLOCK_COUNT, std::max<uint64_t>(1, n_blocks) * 4);
-        d_block_base = pool_get<uint64_t>(ctx, S_BLOCK_BASE, std::max<uint64_t>(1, n_blocks) * 8);
-        sa.block_count = d_block_count; sa.block_base = d_block_base;
-    }
-
-    t_all.start();
-    int n_pass = 1;
-    uint32_t b_lo = bucket_begin;
-    const uint32_t span = bucket_end - bucket_begin;
-    bool first_pass = true;
-    std::vector<int64_t> h_first;
+    const mgta_reads *rd = nullptr;
+    uint64_t n_short = 0, n_blocks = 0;        // n_blocks: workgroups of the read scans (kReadsPerBlock reads each)
+    int k = 0, words_per_tip = 0, min_count = 1, need_mercy = 0;
+    uint32_t bucket_begin = 0, bucket_end = 0;
+    mgta_edge_sink sink = nullptr; void *user = nullptr;
+    SortModes modes;
+    uint64_t budget = 0;                       // device bytes the build may hold
+    bool acc = false;                          // mgta_ctx_keep_stream: the whole stream of every pass stays on the device
+    ScanArgs sa{};
+    uint64_t *d_block_base = nullptr, *d_total = nullptr, *d_kmers = nullptr, *d_tot3 = nullptr, *d_sentinel = nullptr;
+    uint32_t multi_n = 0, multi_width = 0, multi_lo = 0;   // ranges counted ahead by one scan (rows of d_multi_count)
+    uint32_t *d_multi_count = nullptr;
+    mgta_build_stats S{};
+    Timer t_all{stream}, t_ph{stream};
+    SortLog log{&S, {}};
+    std::vector<int64_t> h_first, h_items;    // host staging of a pass
     std::vector<uint16_t> h_rec, h_large;
     std::vector<uint32_t> h_tips;
-    std::vector<int64_t> h_items;
+    explicit Build(mgta_ctx *c) : ctx(c) {}
 
-    uint32_t multi_n = 0, multi_width = 0, multi_lo = 0;             // ranges counted ahead by one scan (d_multi_count rows)
-    uint32_t *d_multi_count = nullptr;
-    while (b_lo < bucket_end) {
-        uint32_t width = (span + n_pass - 1) / n_pass;
-        uint32_t b_hi = std::min<uint32_t>(bucket_end, b_lo + width);
-        // ---- 1. count
+    int run() {
+        int rc = start();
+        if (rc == MGTA_OK) rc = solid_from_stage1();
+        if (rc != MGTA_OK) return rc;
+        t_all.start();
+        int n_pass = 1;
+        for (uint32_t b_lo = bucket_begin; b_lo < bucket_end;) {
+            Pass p;
+            p.width = (bucket_end - bucket_begin + n_pass - 1) / n_pass;
+            p.b_lo = b_lo; p.b_hi = std::min<uint32_t>(bucket_end, b_lo + p.width);
+            count_pass(p);
+            if (const int more = admit_pass(p, n_pass)) { n_pass = more; continue; }
+            S.n_items += (int64_t)p.n_items;
+            S.n_passes++;
+            if (p.n_items > 0) {
+                Key<W> *a = pool_get<Key<W>>(ctx, S_KEYS_A, p.key_b), *b = pool_get<Key<W>>(ctx, S_KEYS_B, p.key_b);
+                const SortJob<W> job = plan_sort(p, a, b);
+                write_keys(p, job);
+                Key<W> *sorted = sort_keys(job);
+                if (!sorted) return MGTA_EUNSUPPORTED;
+                if ((rc = drop_sentinels(p)) != MGTA_OK || (rc = emit(p, sorted, sorted == a ? b : a)) != MGTA_OK) return rc;
+            }
+            publish_last(p.b_lo, p.b_hi, p.rec, p.n_edges, p.tips, p.n_tips, p.first);   // (an empty range names no records)
+            if (acc && p.n_items > 0) append_to_stream(p);
+            S.n_edges += (int64_t)p.n_edges; S.n_large += (int64_t)p.n_large; S.n_tips += (int64_t)p.n_tips;
+            if ((rc = deliver_pass(p)) != MGTA_OK) return rc;
+            b_lo = p.b_hi;
+        }
+        if (acc) publish_last(bucket_begin, bucket_end, ctx->acc_rec.p, ctx->acc_n_rec, ctx->acc_tips.p, ctx->acc_n_tips, nullptr);
+        ctx->acc_valid = acc;
+        S.ms_total = t_all.stop();
+        for (const Timer &t : log.scatter) S.ms_sort_scatter += t.ms();
+        S.bytes_peak = ctx->peak_bytes;
+        return MGTA_OK;
+    }
+
+    // stats, memory budget, the whole-stream hand-off and the scan's fixed arguments
+    int start() {
+        words_per_tip = (2 * k + 31) / 32;                             // sdbg_multi_io.h:63
+        n_blocks = (rd->n_reads + kReadsPerBlock - 1) / kReadsPerBlock;
+        // the scan kernels run one workgroup of kScanBlock threads per kReadsPerBlock reads: a dispatch holds fewer than 2^32 work-items
+        if (n_blocks * (uint64_t)kScanBlock >= (1ull << 32)) { set_error("too many reads for one launch (%llu)", (unsigned long long)rd->n_reads); return MGTA_EUNSUPPORTED; }
+        S.k = k; S.words_per_key = W; S.words_per_tip = words_per_tip; S.n_reads = (int64_t)rd->n_reads;
+        ctx->peak_bytes = ctx->live_bytes;
+        size_t free_b = 0, total_b = 0;
+        MGTA_HIP_CHECK(hipMemGetInfo(&free_b, &total_b));
+        // what the build may hold: the explicit limit, else 90 % of (free + what our pool already holds)
+        const uint64_t avail = (uint64_t)free_b + pool_bytes(ctx);
+        budget = ctx->mem_limit ? std::min<uint64_t>(ctx->mem_limit, avail) : (uint64_t)(avail * 0.9);
+        acc = ctx->keep_stream != 0;           // (of a bucket sub-range too: the shard a rank hands to the all-gather)
+        ctx->acc_valid = false; ctx->acc_n_rec = 0; ctx->acc_n_tips = 0;
+        if (acc) ctx->acc_items.assign(MGTA_NUM_BUCKETS, 0);
+        point_scans_at_pool();
+        uint64_t *d_small = pool_get<uint64_t>(ctx, S_SMALL, 4096);   // [0] total, [1] kmers, [2..4] emit totals, [5] sentinels, [8..263] digit totals
+        d_total = d_small; d_kmers = d_small + 1; d_tot3 = d_small + 2; d_sentinel = d_small + 5;
+        sa.packed = rd->d_packed; sa.n_words = rd->n_words; sa.start = rd->d_start; sa.n_reads = rd->n_reads; sa.k = k; sa.n_short = n_short;
+        sa.n_kmers = (unsigned long long *)d_kmers; sa.n_sentinel = (unsigned long long *)d_sentinel;
+        return MGTA_OK;
+    }
+    void point_scans_at_pool() {               // the scans' per-workgroup counts and offsets
+        sa.block_count = pool_get<uint32_t>(ctx, S_BLOCK_COUNT, std::max<uint64_t>(1, n_blocks) * 4);
+        sa.block_base = d_block_base = pool_get<uint64_t>(ctx, S_BLOCK_BASE, std::max<uint64_t>(1, n_blocks) * 8);
+    }
+
+    // min_count >= 2: the stage-1 verdicts the scans honour
+    int solid_from_stage1() {
+        if (min_count <= 1) return MGTA_OK;
+        unsigned long long *sol = nullptr;
+        int nk1 = 0;
         t_ph.start();
-        sa.b_lo = b_lo; sa.b_hi = b_hi;
+        const int rc = run_stage1<W>(ctx, rd, n_short, k, min_count, need_mercy, budget, modes.side, &sol, &nk1);
+        if (rc != MGTA_OK) return rc;
+        S.ms_stage1 = t_ph.stop();
+        sa.is_solid = sol; sa.num_k1_per_read = nk1;
+        point_scans_at_pool();                 // run_stage1 may have re-grown pool slots
+        return MGTA_OK;
+    }
+
+    // ---- 1./2. items per workgroup and their prefix sum: the closed form, the counting scan, or the row of a scan that counted
+    // every range ahead; the first pass also totals the (k+1)-mers
+    void count_pass(Pass &p) {
+        const bool first_pass = S.n_passes == 0;
+        t_ph.start();
+        sa.b_lo = p.b_lo; sa.b_hi = p.b_hi;
         sa.n_kmers = first_pass ? (unsigned long long *)d_kmers : nullptr;
         if (first_pass) MGTA_HIP_CHECK(hipMemsetAsync(d_kmers, 0, 8, stream));
         uint64_t *d_scan_tmp = pool_get<uint64_t>(ctx, S_SCAN_TMP, scan_tmp_elems(std::max<uint64_t>(n_blocks, 1024)) * 8);
         static_assert(kReadsPerBlock == 64, "item_count_closed_kernel: one lane per read of a workgroup");
-        static const bool closed_even = !(getenv("MGTA_CLOSED_EVEN") && atoi(getenv("MGTA_CLOSED_EVEN")) == 0);   // 0: k+1 even takes the scans
-        const bool closed_form = (((k + 1) & 1) || closed_even) && !sa.is_solid && b_lo == 0 && b_hi == (uint32_t)MGTA_NUM_BUCKETS && !ctx->force_full_lsd;
-        const uint32_t *counts = d_block_count;
+        p.closed_form = !sa.is_solid && p.b_lo == 0 && p.b_hi == (uint32_t)MGTA_NUM_BUCKETS && !ctx->force_full_lsd;
+        const uint32_t *counts = sa.block_count;
         sa.multi_n = 0; sa.multi_width = 0; sa.multi_magic = 0;
-        if (n_blocks && closed_form)
+        // the k-mer total of the first pass comes from the read lengths alone, for the scans too: one atomic per wave of the scan on
+        // ONE address (6.25 M of them at 100 M reads) kept the count scan at 80 ms where the write scan, which does more, takes 52
+        if (n_blocks && (p.closed_form || sa.n_kmers))
             hipLaunchKernelGGL(item_count_closed_kernel, dim3((unsigned)((n_blocks + 63) / 64)), dim3(256), 0, stream, sa.start, sa.n_reads, n_blocks, k,
-                               sa.block_count, sa.n_kmers);
-        else if (n_blocks) {
-            // the k-mer total of the first pass from the read lengths alone: one atomic per wave of the scan on ONE address (6.25 M of
-            // them at 100 M reads) kept the count scan at 80 ms where the write scan, which does more, takes 52
-            if (sa.n_kmers) {
-                hipLaunchKernelGGL(item_count_closed_kernel, dim3((unsigned)((n_blocks + 63) / 64)), dim3(256), 0, stream, sa.start, sa.n_reads, n_blocks, k,
-                                   (uint32_t *)nullptr, sa.n_kmers);
-                sa.n_kmers = nullptr;
-            }
+                               p.closed_form ? sa.block_count : nullptr, sa.n_kmers);
+        if (n_blocks && !p.closed_form) {
+            sa.n_kmers = nullptr;
             // several equally wide ranges ahead (memory-bound passes): one scan counts them all
-            const uint32_t ranges_left = (bucket_end - b_lo + width - 1) / width;
+            const uint32_t width = p.width, b_lo = p.b_lo, ranges_left = (bucket_end - b_lo + width - 1) / width;
             if (multi_n && (width != multi_width || b_lo < multi_lo || (b_lo - multi_lo) % width != 0 || (b_lo - multi_lo) / width >= multi_n)) multi_n = 0;
             if (!multi_n && ranges_left > 1 && ranges_left <= (uint32_t)kMaxCountRanges) {
                 d_multi_count = pool_get<uint32_t>(ctx, S_MULTI_COUNT, (uint64_t)ranges_left * n_blocks * 4);
@@ -2264,228 +2267,227 @@ static int build_impl(mgta_ctx *ctx, const mgta_reads *rd, uint64_t n_short, int
             else hipLaunchKernelGGL((item_scan_kernel<W, false>), dim3((unsigned)n_blocks), dim3(kScanBlock), 0, stream, sa);
         }
         exclusive_scan_u32(stream, counts, n_blocks, d_block_base, d_scan_tmp, d_total);
-        uint64_t n_items = 0;
-        MGTA_HIP_CHECK(hipMemcpyAsync(&n_items, d_total, 8, hipMemcpyDeviceToHost, stream));
+        MGTA_HIP_CHECK(hipMemcpyAsync(&p.n_items, d_total, 8, hipMemcpyDeviceToHost, stream));
         S.ms_count += t_ph.stop();
         if (first_pass) {
             unsigned long long km = 0;
             MGTA_HIP_CHECK(hipMemcpy(&km, d_kmers, 8, hipMemcpyDeviceToHost));
             S.n_kmers = (int64_t)km;
         }
-        // does the pass fit?  two key buffers (the second doubles as emit scratch) + census + outputs (estimate)
-        uint64_t n_tiles = (n_items + kBlockTile - 1) / kBlockTile;
+    }
+
+    // Does the pass fit?  Two key buffers (the second doubles as emit scratch) + census + outputs (estimate).  0: it does, else the
+    // number of passes to split the buckets into instead (narrower bucket ranges: CX1's lv1 loop, cx1.h:494)
+    int admit_pass(Pass &p, int n_pass) {
+        p.n_tiles = (p.n_items + kBlockTile - 1) / kBlockTile;
         // either key buffer may end up as the emitter's scratch (11 bytes per key: run start u64, record u16, info u8), whichever
         // the last sort pass leaves idle: both hold >= 12 bytes per key
-        uint64_t key_b = std::max<uint64_t>(n_items * sizeof(Key<W>), n_items * 12) + 4096;
-        uint64_t need = 2 * key_b + n_tiles * 256 * 8 + n_items * 2 + n_items /* side digits */ + (8u << 20);
+        p.key_b = std::max<uint64_t>(p.n_items * sizeof(Key<W>), p.n_items * 12) + 4096;
+        const uint64_t need = 2 * p.key_b + p.n_tiles * 256 * 8 + p.n_items * 2 + p.n_items /* side digits */ + (8u << 20);
         uint64_t other = ctx->live_bytes - pool_bytes(ctx);
         if (acc) {     // room for the stream the passes leave behind: ~0.6 edges of 2 bytes per (k+1)-mer, tips, slack
+            const double range_frac = (double)(bucket_end - bucket_begin) / (double)MGTA_NUM_BUCKETS;
             const uint64_t est = (uint64_t)((double)S.n_kmers * 1.5 * range_frac) + (64ull << 20);
             const uint64_t have = ctx->acc_rec.bytes + ctx->acc_tips.bytes;
             other += est > have ? est - have : 0;
         }
         const uint64_t avail = budget - std::min<uint64_t>(budget, other);
-        if (need + need / 8 > avail && width > 1) {                   // narrower bucket ranges (CX1's lv1 loop, cx1.h:494)
-            const double ratio = (double)(need + need / 8) / (double)std::max<uint64_t>(avail, 1) * 1.03;
-            n_pass = std::max(n_pass + 1, (int)std::ceil((double)n_pass * ratio));
-            continue;
+        if (need + need / 8 <= avail || p.width <= 1) return 0;
+        const double ratio = (double)(need + need / 8) / (double)std::max<uint64_t>(avail, 1) * 1.03;
+        return std::max(n_pass + 1, (int)std::ceil((double)n_pass * ratio));
+    }
+
+    // the one plan of the pass's sort, for the key writer and the sort
+    SortJob<W> plan_sort(const Pass &p, Key<W> *a, Key<W> *b) const {
+        const int max_top = (2 * k + 4 + 7) / 8 > 1 ? std::min(4, (32 * W - 8) / 8) : 0;
+        SortJob<W> job{a, b, p.n_items, choose_top_plan(ctx, p.n_items, max_top, (double)p.nb() / MGTA_NUM_BUCKETS, p.b_lo, p.b_hi, modes.bias)};
+        job.low = low_digit_plan(k, W, job.top.T());
+        job.side_mode = modes.side;
+        // closed form + at least one global sort pass: the key writer works tile by tile of that pass and leaves its census behind;
+        // the general writer leaves that pass's digit of every key in the side array instead
+        job.census_done = p.closed_form && job.top.P >= 1 && p.n_tiles <= 0x7FFFFFFFull;
+        job.side_done = !p.closed_form && job.uses_side();
+        return job;
+    }
+
+    // ---- 3. the keys, into job.a
+    void write_keys(const Pass &p, const SortJob<W> &job) {
+        t_ph.start();
+        sa.out = job.a;
+        if (p.closed_form) MGTA_HIP_CHECK(hipMemsetAsync(d_sentinel, 0, 8, stream));
+        const int shift = 32 - job.top.T();    // of the first global pass's digit in key word 0
+        if (job.census_done) {
+            uint64_t *d_hist = pool_get<uint64_t>(ctx, S_HIST, std::max<uint64_t>(1, p.n_tiles) * 256 * 8);   // the buffer the sort uses
+            hipLaunchKernelGGL((item_write_tiled_kernel<W>), dim3((unsigned)p.n_tiles), dim3(kScanBlock), 0, stream, sa, n_blocks, p.n_items,
+                               shift, p.n_tiles, d_hist);
+        } else if (p.closed_form)
+            hipLaunchKernelGGL((item_write_closed_kernel<W>), dim3((unsigned)n_blocks), dim3(kScanBlock), 0, stream, sa);
+        else {
+            if (job.side_done) {
+                sa.side = pool_get<uint8_t>(ctx, S_SIDE, p.n_items + 64);
+                sa.side_shift = shift;
+                sa.side_bias = job.top.bias;
+            }
+            hipLaunchKernelGGL((item_scan_kernel<W, true>), dim3((unsigned)n_blocks), dim3(kScanBlock), 0, stream, sa);
+            sa.side = nullptr;
         }
-        first_pass = false;
-        S.n_items += (int64_t)n_items;
-        S.n_passes++;
-        const uint32_t nb = b_hi - b_lo;
-        h_items.assign((size_t)nb * 3, 0);
-        uint64_t n_edges = 0, n_large = 0, n_tips = 0;
-        if (n_items > 0) {
-            Key<W> *d_a = pool_get<Key<W>>(ctx, S_KEYS_A, key_b);
-            Key<W> *d_b = pool_get<Key<W>>(ctx, S_KEYS_B, key_b);
-            // ---- 3. write keys
-            t_ph.start();
-            sa.out = d_a;
-            const int max_top = (2 * k + 4 + 7) / 8 > 1 ? std::min(4, (32 * W - 8) / 8) : 0;
-            const double prefix_frac = (double)(b_hi - b_lo) / MGTA_NUM_BUCKETS;
-            // closed form + at least one global sort pass: the key writer works tile by tile of that pass and leaves its census behind
-            const int P_top = choose_top_plan(ctx, n_items, max_top, prefix_frac).P;
-            static const bool tiled_keygen = !(getenv("MGTA_KEYGEN_TILED") && atoi(getenv("MGTA_KEYGEN_TILED")) == 0);
-            const bool fused_census = closed_form && P_top >= 1 && tiled_keygen && n_tiles <= 0x7FFFFFFFull;
-            bool first_side = false;
-            if (closed_form) MGTA_HIP_CHECK(hipMemsetAsync(d_sentinel, 0, 8, stream));
-            if (fused_census) {
-                uint64_t *d_hist = pool_get<uint64_t>(ctx, S_HIST, std::max<uint64_t>(1, n_tiles) * 256 * 8);   // the buffer device_sort uses
-                hipLaunchKernelGGL((item_write_tiled_kernel<W>), dim3((unsigned)n_tiles), dim3(kScanBlock), 0, stream, sa, n_blocks, n_items,
-                                   32 - 8 * P_top, n_tiles, d_hist);
-            } else if (closed_form)
-                hipLaunchKernelGGL((item_write_closed_kernel<W>), dim3((unsigned)n_blocks), dim3(kScanBlock), 0, stream, sa);
-            else {
-                // the general writer leaves the first global pass's digit of every key in the side array (see device_sort): that pass's
-                // census then reads one byte per key.  The plan is the one device_sort is about to choose (same arguments).
-                const TopPlan tp = choose_top_plan(ctx, n_items, max_top, prefix_frac, b_lo, b_hi);
-                const char *side_env = getenv("MGTA_SORT_SIDE");
-                if (tp.P >= 2 && kSideFits<W> && (!side_env || atoi(side_env) > 0)) {
-                    sa.side = pool_get<uint8_t>(ctx, S_SIDE, n_items + 64);
-                    sa.side_shift = 32 - 8 * tp.P - tp.skip;
-                    sa.side_bias = tp.bias;
-                    first_side = true;
-                }
-                hipLaunchKernelGGL((item_scan_kernel<W, true>), dim3((unsigned)n_blocks), dim3(kScanBlock), 0, stream, sa);
-                sa.side = nullptr;
-            }
-            S.ms_gen += t_ph.stop();
-            // ---- 4. sort: P global passes on the most significant bytes, then the segment-local finish in LDS
-            t_ph.start();
-            Key<W> *src = device_sort<W>(ctx, stream, d_a, d_b, n_items, max_top, [&](int T) { return low_digit_plan(k, W, T); }, &scatter_ev, &S,
-                                           prefix_frac, ~0u, ~0u, fused_census, b_lo, b_hi, first_side);
-            if (!src) return MGTA_EUNSUPPORTED;
-            Key<W> *dst = src == d_a ? d_b : d_a;
-            S.ms_sort += t_ph.stop();
-            if (closed_form && !((k + 1) & 1)) {
-                // sentinel keys (rc slots of palindromic (k+1)-mers) sorted behind every real key: the emitter stops before them
-                unsigned long long n_sent = 0;
-                MGTA_HIP_CHECK(hipMemcpy(&n_sent, d_sentinel, 8, hipMemcpyDeviceToHost));
-                if (n_sent >= n_items) { set_error("internal: %llu sentinel keys among %llu items", n_sent, (unsigned long long)n_items); return MGTA_EINTERNAL; }
-                n_items -= n_sent;
-                S.n_items -= (int64_t)n_sent;
-            }
-            // ---- 5. emit.  `src` holds the sorted keys; the other buffer is scratch.
-            t_ph.start();
-            const Key<W> *sorted = src;
-            char *scratch = reinterpret_cast<char *>(dst);
-            uint64_t e_tiles = (n_items + kEmitTile - 1) / kEmitTile;
-            d_scan_tmp = pool_get<uint64_t>(ctx, S_SCAN_TMP, scan_tmp_elems(std::max<uint64_t>(std::max(n_blocks, e_tiles), n_items / kDecideTile + 1)) * 8);
-            // run descriptors, compacted in key order in one read of the keys (chained scan over the tiles).  Scratch layout for up to
-            // n_items runs (<= 7.01 bytes per key of a >= 12-byte-per-key buffer): start u32 | rec u16 | info u8 | full start u64 per 1024 runs
-            if (e_tiles > 0xFFFFFFFFull) { set_error("too many emit tiles"); return MGTA_EUNSUPPORTED; }
-            unsigned long long *d_chain = pool_get<unsigned long long>(ctx, S_TILE_BASE, (e_tiles + 4) * 8);
-            EmitChain chain;
-            chain.state = d_chain;
-            chain.total = d_chain + e_tiles;
-            chain.ticket = reinterpret_cast<uint32_t *>(d_chain + e_tiles + 1);
-            chain.error = reinterpret_cast<uint32_t *>(d_chain + e_tiles + 2);
-            RunStarts sub_start;
-            sub_start.lo = reinterpret_cast<uint32_t *>(scratch);
-            uint16_t *rec = reinterpret_cast<uint16_t *>(scratch + n_items * 4);
-            uint8_t *info = reinterpret_cast<uint8_t *>(scratch + n_items * 6);
-            sub_start.base = reinterpret_cast<uint64_t *>(scratch + ((n_items * 7 + 7) & ~7ull));
-            unsigned long long chain_out[3] = {0, 0, 0};                   // total, ticket, error
-            for (int attempt = 0; attempt < 2; ++attempt) {
-                MGTA_HIP_CHECK(hipMemsetAsync(d_chain, 0, (e_tiles + 4) * 8, stream));
-                if (attempt == 0 && !ctx->force_full_lsd)
-                    hipLaunchKernelGGL((emit_compact_kernel<W, false>), dim3((unsigned)e_tiles), dim3(kEmitThreads), 0, stream, sorted, n_items, k, chain,
-                                       (uint32_t)e_tiles, sub_start, info);
-                else
-                    hipLaunchKernelGGL((emit_compact_kernel<W, true>), dim3((unsigned)e_tiles), dim3(kEmitThreads), 0, stream, sorted, n_items, k, chain,
-                                       (uint32_t)e_tiles, sub_start, info);
-                MGTA_HIP_CHECK(hipMemcpyAsync(chain_out, d_chain + e_tiles, 24, hipMemcpyDeviceToHost, stream));
-                MGTA_HIP_CHECK(hipStreamSynchronize(stream));
-                if ((uint32_t)chain_out[2] == 0) break;
-            }
-            if ((uint32_t)chain_out[2] != 0) { set_error("internal: chained scan of the emitter timed out"); return MGTA_EINTERNAL; }
-            const uint64_t m = chain_out[0];
-            uint64_t d_tiles = (m + kDecideTile - 1) / kDecideTile;
-            uint32_t *ce = pool_get<uint32_t>(ctx, S_CNT, d_tiles * 4 * 3), *cl = ce + d_tiles, *ct = cl + d_tiles;
-            uint64_t *be = pool_get<uint64_t>(ctx, S_BASE, d_tiles * 8 * 3), *bl = be + d_tiles, *bt = bl + d_tiles;
-            int64_t *d_first = pool_get<int64_t>(ctx, S_FIRST, (uint64_t)MGTA_NUM_BUCKETS * 3 * 8);
-            MGTA_HIP_CHECK(hipMemsetAsync(d_first, 0xFF, (uint64_t)nb * 3 * 8, stream));
-            hipLaunchKernelGGL(emit_decide_kernel, dim3((unsigned)d_tiles), dim3(kDecideThreads), 0, stream, sub_start, info, m, n_items,
-                               rec, ce, cl, ct);
-            exclusive_scan_u32(stream, ce, d_tiles, be, d_scan_tmp, d_tot3);
-            exclusive_scan_u32(stream, cl, d_tiles, bl, d_scan_tmp, d_tot3 + 1);
-            exclusive_scan_u32(stream, ct, d_tiles, bt, d_scan_tmp, d_tot3 + 2);
-            uint64_t tot3[3];
-            MGTA_HIP_CHECK(hipMemcpyAsync(tot3, d_tot3, 24, hipMemcpyDeviceToHost, stream));
+        S.ms_gen += t_ph.stop();
+    }
+
+    // ---- 4. sort: P global passes on the most significant bytes, then the segment-local finish in LDS
+    Key<W> *sort_keys(const SortJob<W> &job) {
+        t_ph.start();
+        Key<W> *sorted = device_sort(ctx, job, &log);
+        if (sorted) S.ms_sort += t_ph.stop();
+        return sorted;
+    }
+
+    // sentinel keys (rc slots of palindromic (k+1)-mers of a closed-form pass, k+1 even) sort behind every real key: the emitter stops before them
+    int drop_sentinels(Pass &p) {
+        if (!p.closed_form || ((k + 1) & 1)) return MGTA_OK;
+        unsigned long long n_sent = 0;
+        MGTA_HIP_CHECK(hipMemcpy(&n_sent, d_sentinel, 8, hipMemcpyDeviceToHost));
+        if (n_sent >= p.n_items) { set_error("internal: %llu sentinel keys among %llu items", n_sent, (unsigned long long)p.n_items); return MGTA_EINTERNAL; }
+        p.n_items -= n_sent;
+        S.n_items -= (int64_t)n_sent;
+        return MGTA_OK;
+    }
+
+    // ---- 5. the edges of the `sorted` keys; the other key buffer is scratch
+    int emit(Pass &p, const Key<W> *sorted, Key<W> *scratch_keys) {
+        const uint64_t n_items = p.n_items;
+        t_ph.start();
+        char *scratch = reinterpret_cast<char *>(scratch_keys);
+        uint64_t e_tiles = (n_items + kEmitTile - 1) / kEmitTile;
+        uint64_t *d_scan_tmp = pool_get<uint64_t>(ctx, S_SCAN_TMP, scan_tmp_elems(std::max<uint64_t>(std::max(n_blocks, e_tiles), n_items / kDecideTile + 1)) * 8);
+        // run descriptors, compacted in key order in one read of the keys (chained scan over the tiles).  Scratch layout for up to
+        // n_items runs (<= 7.01 bytes per key of a >= 12-byte-per-key buffer): start u32 | rec u16 | info u8 | full start u64 per 1024 runs
+        if (e_tiles > 0xFFFFFFFFull) { set_error("too many emit tiles"); return MGTA_EUNSUPPORTED; }
+        unsigned long long *d_chain = pool_get<unsigned long long>(ctx, S_TILE_BASE, (e_tiles + 4) * 8);
+        EmitChain chain;
+        chain.state = d_chain; chain.total = d_chain + e_tiles;
+        chain.ticket = reinterpret_cast<uint32_t *>(d_chain + e_tiles + 1); chain.error = reinterpret_cast<uint32_t *>(d_chain + e_tiles + 2);
+        RunStarts sub_start;
+        sub_start.lo = reinterpret_cast<uint32_t *>(scratch);
+        uint16_t *rec = reinterpret_cast<uint16_t *>(scratch + n_items * 4);
+        uint8_t *info = reinterpret_cast<uint8_t *>(scratch + n_items * 6);
+        sub_start.base = reinterpret_cast<uint64_t *>(scratch + ((n_items * 7 + 7) & ~7ull));
+        unsigned long long chain_out[3] = {0, 0, 0};               // total, ticket, error
+        for (int attempt = 0; attempt < 2; ++attempt) {
+            MGTA_HIP_CHECK(hipMemsetAsync(d_chain, 0, (e_tiles + 4) * 8, stream));
+            if (attempt == 0 && !ctx->force_full_lsd)
+                hipLaunchKernelGGL((emit_compact_kernel<W, false>), dim3((unsigned)e_tiles), dim3(kEmitThreads), 0, stream, sorted, n_items, k, chain,
+                                   (uint32_t)e_tiles, sub_start, info);
+            else
+                hipLaunchKernelGGL((emit_compact_kernel<W, true>), dim3((unsigned)e_tiles), dim3(kEmitThreads), 0, stream, sorted, n_items, k, chain,
+                                   (uint32_t)e_tiles, sub_start, info);
+            MGTA_HIP_CHECK(hipMemcpyAsync(chain_out, d_chain + e_tiles, 24, hipMemcpyDeviceToHost, stream));
             MGTA_HIP_CHECK(hipStreamSynchronize(stream));
-            n_edges = tot3[0]; n_large = tot3[1]; n_tips = tot3[2];
-            uint16_t *d_out_rec = pool_get<uint16_t>(ctx, S_OUT_REC, n_edges * 2);
-            uint16_t *d_out_large = pool_get<uint16_t>(ctx, S_OUT_LARGE, n_large * 2);
-            uint32_t *d_out_tips = pool_get<uint32_t>(ctx, S_OUT_TIPS, n_tips * words_per_tip * 4);
-            hipLaunchKernelGGL((emit_write_kernel<W>), dim3((unsigned)d_tiles), dim3(kDecideThreads), 0, stream, sorted, sub_start, info, rec, m,
-                               n_items, be, bl, bt, words_per_tip, b_lo, d_out_rec, d_out_large, d_out_tips, d_first);
-            S.ms_emit += t_ph.stop();
-            ctx->last_rec = d_out_rec; ctx->last_n_rec = n_edges; ctx->last_bucket_lo = b_lo; ctx->last_bucket_hi = b_hi;
-            ctx->last_tips = d_out_tips; ctx->last_n_tips = n_tips; ctx->last_first = d_first; ctx->last_k = k; ctx->last_words_per_tip = words_per_tip;
-            if (acc) {
-                // append this pass to the whole-stream buffers (device to device); capacity from the share of the buckets done so far
-                auto ensure = [&](DevBuf &buf, uint64_t used, uint64_t add) {
-                    if (used + add <= buf.bytes) return;
-                    const double done = (double)(b_hi - bucket_begin) / (double)(bucket_end - bucket_begin);
-                    uint64_t want = (uint64_t)((double)(used + add) / std::max(done, 1e-3) * 1.1) + (1u << 20);
-                    want = std::max<uint64_t>(want, used + add);
-                    DevBuf bigger;
-                    bigger.alloc(want, &ctx->live_bytes, &ctx->peak_bytes);
-                    if (used) MGTA_HIP_CHECK(hipMemcpyAsync(bigger.p, buf.p, used, hipMemcpyDeviceToDevice, stream));
-                    MGTA_HIP_CHECK(hipStreamSynchronize(stream));
-                    buf = std::move(bigger);
-                };
-                ensure(ctx->acc_rec, ctx->acc_n_rec * 2, n_edges * 2);
-                ensure(ctx->acc_tips, ctx->acc_n_tips * words_per_tip * 4, n_tips * words_per_tip * 4);
-                if (n_edges) MGTA_HIP_CHECK(hipMemcpyAsync(ctx->acc_rec.as<char>() + ctx->acc_n_rec * 2, d_out_rec, n_edges * 2, hipMemcpyDeviceToDevice, stream));
-                if (n_tips) MGTA_HIP_CHECK(hipMemcpyAsync(ctx->acc_tips.as<char>() + ctx->acc_n_tips * words_per_tip * 4, d_out_tips,
-                                                          n_tips * words_per_tip * 4, hipMemcpyDeviceToDevice, stream));
-                acc_first.resize((size_t)nb * 3);
-                MGTA_HIP_CHECK(hipMemcpyAsync(acc_first.data(), d_first, (size_t)nb * 3 * 8, hipMemcpyDeviceToHost, stream));
-                MGTA_HIP_CHECK(hipStreamSynchronize(stream));
-                int64_t nxt = (int64_t)n_edges;
-                for (int64_t b = (int64_t)nb - 1; b >= 0; --b) {
-                    int64_t f = acc_first[(size_t)b * 3];
-                    if (f < 0) f = nxt;
-                    ctx->acc_items[(size_t)b_lo + (size_t)b] = nxt - f;
-                    nxt = f;
+            if ((uint32_t)chain_out[2] == 0) break;
+        }
+        if ((uint32_t)chain_out[2] != 0) { set_error("internal: chained scan of the emitter timed out"); return MGTA_EINTERNAL; }
+        const uint64_t m = chain_out[0];
+        uint64_t d_tiles = (m + kDecideTile - 1) / kDecideTile;
+        uint32_t *ce = pool_get<uint32_t>(ctx, S_CNT, d_tiles * 4 * 3), *cl = ce + d_tiles, *ct = cl + d_tiles;
+        uint64_t *be = pool_get<uint64_t>(ctx, S_BASE, d_tiles * 8 * 3), *bl = be + d_tiles, *bt = bl + d_tiles;
+        p.first = pool_get<int64_t>(ctx, S_FIRST, (uint64_t)MGTA_NUM_BUCKETS * 3 * 8);
+        MGTA_HIP_CHECK(hipMemsetAsync(p.first, 0xFF, (uint64_t)p.nb() * 3 * 8, stream));
+        hipLaunchKernelGGL(emit_decide_kernel, dim3((unsigned)d_tiles), dim3(kDecideThreads), 0, stream, sub_start, info, m, n_items,
+                           rec, ce, cl, ct);
+        exclusive_scan_u32(stream, ce, d_tiles, be, d_scan_tmp, d_tot3);
+        exclusive_scan_u32(stream, cl, d_tiles, bl, d_scan_tmp, d_tot3 + 1);
+        exclusive_scan_u32(stream, ct, d_tiles, bt, d_scan_tmp, d_tot3 + 2);
+        uint64_t tot3[3];
+        MGTA_HIP_CHECK(hipMemcpyAsync(tot3, d_tot3, 24, hipMemcpyDeviceToHost, stream));
+        MGTA_HIP_CHECK(hipStreamSynchronize(stream));
+        p.n_edges = tot3[0]; p.n_large = tot3[1]; p.n_tips = tot3[2];
+        p.rec = pool_get<uint16_t>(ctx, S_OUT_REC, p.n_edges * 2);
+        p.large = pool_get<uint16_t>(ctx, S_OUT_LARGE, p.n_large * 2);
+        p.tips = pool_get<uint32_t>(ctx, S_OUT_TIPS, p.n_tips * words_per_tip * 4);
+        hipLaunchKernelGGL((emit_write_kernel<W>), dim3((unsigned)d_tiles), dim3(kDecideThreads), 0, stream, sorted, sub_start, info, rec, m,
+                           n_items, be, bl, bt, words_per_tip, p.b_lo, p.rec, p.large, p.tips, p.first);
+        S.ms_emit += t_ph.stop();
+        return MGTA_OK;
+    }
+
+    // what mgta_sdbg_load_resident / mgta_sdbg_export_records_device find of the build on the context
+    void publish_last(uint32_t lo, uint32_t hi, const void *rec, uint64_t n_rec, const void *tips, uint64_t n_tips, const void *first) {
+        ctx->last_rec = rec; ctx->last_n_rec = n_rec; ctx->last_bucket_lo = lo; ctx->last_bucket_hi = hi;
+        ctx->last_tips = tips; ctx->last_n_tips = n_tips; ctx->last_first = first; ctx->last_k = k; ctx->last_words_per_tip = words_per_tip;
+    }
+
+    // the pass appended to the whole-stream buffers (device to device); capacity from the share of the buckets done so far
+    void append_to_stream(const Pass &p) {
+        const uint64_t tip_b = words_per_tip * 4;
+        auto ensure = [&](DevBuf &buf, uint64_t used, uint64_t add) {
+            if (used + add <= buf.bytes) return;
+            const double done = (double)(p.b_hi - bucket_begin) / (double)(bucket_end - bucket_begin);
+            uint64_t want = (uint64_t)((double)(used + add) / std::max(done, 1e-3) * 1.1) + (1u << 20);
+            want = std::max<uint64_t>(want, used + add);
+            DevBuf bigger;
+            bigger.alloc(want, &ctx->live_bytes, &ctx->peak_bytes);
+            if (used) MGTA_HIP_CHECK(hipMemcpyAsync(bigger.p, buf.p, used, hipMemcpyDeviceToDevice, stream));
+            MGTA_HIP_CHECK(hipStreamSynchronize(stream));
+            buf = std::move(bigger);
+        };
+        ensure(ctx->acc_rec, ctx->acc_n_rec * 2, p.n_edges * 2);
+        ensure(ctx->acc_tips, ctx->acc_n_tips * tip_b, p.n_tips * tip_b);
+        if (p.n_edges) MGTA_HIP_CHECK(hipMemcpyAsync(ctx->acc_rec.as<char>() + ctx->acc_n_rec * 2, p.rec, p.n_edges * 2, hipMemcpyDeviceToDevice, stream));
+        if (p.n_tips) MGTA_HIP_CHECK(hipMemcpyAsync(ctx->acc_tips.as<char>() + ctx->acc_n_tips * tip_b, p.tips, p.n_tips * tip_b, hipMemcpyDeviceToDevice, stream));
+        h_first.resize((size_t)p.nb() * 3);
+        MGTA_HIP_CHECK(hipMemcpyAsync(h_first.data(), p.first, (size_t)p.nb() * 3 * 8, hipMemcpyDeviceToHost, stream));
+        MGTA_HIP_CHECK(hipStreamSynchronize(stream));
+        int64_t nxt = (int64_t)p.n_edges;
+        for (int64_t b = (int64_t)p.nb() - 1; b >= 0; --b) {
+            int64_t f = h_first[(size_t)b * 3];
+            if (f < 0) f = nxt;
+            ctx->acc_items[(size_t)p.b_lo + (size_t)b] = nxt - f;
+            nxt = f;
+        }
+        ctx->acc_n_rec += p.n_edges; ctx->acc_n_tips += p.n_tips;
+    }
+
+    // ---- device -> host and the sink.  keep_stream 2: records and tip labels stay on the device only (the caller takes the whole
+    // stream afterwards, mgta_sdbg_stream_detach / mgta_stream_download); the sink still gets the counts and the large multiplicities
+    int deliver_pass(const Pass &p) {
+        if (!sink) return MGTA_OK;
+        const bool to_host = ctx->keep_stream != 2;
+        const uint64_t n_tip_words = p.n_tips * words_per_tip;
+        h_items.assign((size_t)p.nb() * 3, 0);
+        if (p.n_items > 0) {
+            t_ph.start();
+            h_rec.resize(to_host ? p.n_edges : 0); h_large.resize(p.n_large); h_tips.resize(to_host ? n_tip_words : 0);
+            h_first.resize((size_t)p.nb() * 3);
+            if (p.n_edges && to_host) MGTA_HIP_CHECK(hipMemcpyAsync(h_rec.data(), p.rec, p.n_edges * 2, hipMemcpyDeviceToHost, stream));
+            if (p.n_large) MGTA_HIP_CHECK(hipMemcpyAsync(h_large.data(), p.large, p.n_large * 2, hipMemcpyDeviceToHost, stream));
+            if (p.n_tips && to_host) MGTA_HIP_CHECK(hipMemcpyAsync(h_tips.data(), p.tips, n_tip_words * 4, hipMemcpyDeviceToHost, stream));
+            MGTA_HIP_CHECK(hipMemcpyAsync(h_first.data(), p.first, (size_t)p.nb() * 3 * 8, hipMemcpyDeviceToHost, stream));
+            S.ms_d2h += t_ph.stop();
+            // bucket boundaries -> counts; untouched entries (-1) are empty buckets
+            int64_t nxt[3] = {(int64_t)p.n_edges, (int64_t)p.n_large, (int64_t)p.n_tips};
+            for (int64_t b = (int64_t)p.nb() - 1; b >= 0; --b)
+                for (int c = 0; c < 3; ++c) {
+                    int64_t f = h_first[(size_t)b * 3 + c];
+                    if (f < 0) f = nxt[c];
+                    h_items[(size_t)b * 3 + c] = nxt[c] - f;
+                    nxt[c] = f;
                 }
-                ctx->acc_n_rec += n_edges; ctx->acc_n_tips += n_tips;
-            }
-            // ---- device -> host
-            if (sink) {
-                t_ph.start();
-                // keep_stream 2: records and tip labels stay on the device only (the caller takes the whole stream afterwards,
-                // mgta_sdbg_stream_detach / mgta_stream_download); the sink still gets the counts and the large multiplicities
-                const bool to_host = ctx->keep_stream != 2;
-                h_rec.resize(to_host ? n_edges : 0); h_large.resize(n_large); h_tips.resize(to_host ? n_tips * words_per_tip : 0);
-                h_first.resize((size_t)nb * 3);
-                if (n_edges && to_host) MGTA_HIP_CHECK(hipMemcpyAsync(h_rec.data(), d_out_rec, n_edges * 2, hipMemcpyDeviceToHost, stream));
-                if (n_large) MGTA_HIP_CHECK(hipMemcpyAsync(h_large.data(), d_out_large, n_large * 2, hipMemcpyDeviceToHost, stream));
-                if (n_tips && to_host) MGTA_HIP_CHECK(hipMemcpyAsync(h_tips.data(), d_out_tips, n_tips * words_per_tip * 4, hipMemcpyDeviceToHost, stream));
-                MGTA_HIP_CHECK(hipMemcpyAsync(h_first.data(), d_first, (size_t)nb * 3 * 8, hipMemcpyDeviceToHost, stream));
-                S.ms_d2h += t_ph.stop();
-                // bucket boundaries -> counts; untouched entries (-1) are empty buckets
-                int64_t nxt[3] = {(int64_t)n_edges, (int64_t)n_large, (int64_t)n_tips};
-                for (int64_t b = (int64_t)nb - 1; b >= 0; --b)
-                    for (int c = 0; c < 3; ++c) {
-                        int64_t f = h_first[(size_t)b * 3 + c];
-                        if (f < 0) f = nxt[c];
-                        h_items[(size_t)b * 3 + c] = nxt[c] - f;
-                        nxt[c] = f;
-                    }
-            }
-        } else {
-            h_rec.clear(); h_large.clear(); h_tips.clear();
-            ctx->last_rec = nullptr; ctx->last_n_rec = 0; ctx->last_bucket_lo = b_lo; ctx->last_bucket_hi = b_hi;
-            ctx->last_tips = nullptr; ctx->last_n_tips = 0; ctx->last_first = nullptr; ctx->last_k = k; ctx->last_words_per_tip = words_per_tip;
-        }
-        S.n_edges += (int64_t)n_edges; S.n_large += (int64_t)n_large; S.n_tips += (int64_t)n_tips;
-        if (sink) {
-            const bool to_host = ctx->keep_stream != 2;
-            int rc = sink(user, (int32_t)b_lo, (int32_t)b_hi, h_items.data(), to_host ? h_rec.data() : nullptr, (int64_t)n_edges, h_large.data(),
-                          (int64_t)n_large, to_host ? h_tips.data() : nullptr, (int64_t)(n_tips * words_per_tip));
-            if (rc != 0) { set_error("edge sink returned %d", rc); return MGTA_ESINK; }
-        }
-        b_lo = b_hi;
+        } else { h_rec.clear(); h_large.clear(); h_tips.clear(); }
+        const int rc = sink(user, (int32_t)p.b_lo, (int32_t)p.b_hi, h_items.data(), to_host ? h_rec.data() : nullptr, (int64_t)p.n_edges,
+                            h_large.data(), (int64_t)p.n_large, to_host ? h_tips.data() : nullptr, (int64_t)n_tip_words);
+        if (rc != 0) { set_error("edge sink returned %d", rc); return MGTA_ESINK; }
+        return MGTA_OK;
     }
-    if (acc) {
-        ctx->last_rec = ctx->acc_rec.p; ctx->last_n_rec = ctx->acc_n_rec; ctx->last_bucket_lo = bucket_begin; ctx->last_bucket_hi = bucket_end;
-        ctx->last_tips = ctx->acc_tips.p; ctx->last_n_tips = ctx->acc_n_tips; ctx->last_first = nullptr; ctx->last_k = k;
-        ctx->last_words_per_tip = words_per_tip;
-        ctx->acc_valid = true;
-    }
-    S.ms_total = t_all.stop();
-    for (auto &ev : scatter_ev) {
-        float ms = 0;
-        MGTA_HIP_CHECK(hipEventElapsedTime(&ms, ev.first, ev.second));
-        S.ms_sort_scatter += ms;
-        (void)hipEventDestroy(ev.first); (void)hipEventDestroy(ev.second);
-    }
-    S.bytes_peak = ctx->peak_bytes;
-    if (st) *st = S;
-    return MGTA_OK;
+};
+
+// f(std::integral_constant<int, W>{}) for the key width W = 1 .. 9 words
+template <int W = 1, class F>
+static int with_key_words(int words, F &&f) {
+    if constexpr (W < 9) {
+        if (words == W) return f(std::integral_constant<int, W>{});
+        return with_key_words<W + 1>(words, f);
+    } else
+        return f(std::integral_constant<int, W>{});
 }
 
 }  // namespace mgta
@@ -2497,7 +2499,7 @@ extern "C" {
 int mgta_reads_upload(mgta_ctx *ctx, const uint32_t *packed, uint64_t n_words, const uint64_t *start_idx, uint64_t n_reads,
                       mgta_reads **out) {
     if (!ctx || !packed || !start_idx || !out) { set_error("mgta_reads_upload: null argument"); return MGTA_EINVAL; }
-    try {
+    return guarded("mgta_reads_upload", [&] {
         MGTA_HIP_CHECK(hipSetDevice(ctx->device));
         auto r = std::make_unique<mgta_reads>();
         r->ctx = ctx; r->n_words = n_words; r->n_reads = n_reads;
@@ -2512,17 +2514,19 @@ int mgta_reads_upload(mgta_ctx *ctx, const uint32_t *packed, uint64_t n_words, c
         ctx_retain(ctx);
         *out = r.release();
         return MGTA_OK;
-    } catch (const HipError &e) { return e.code; }
+    });
 }
 
 int mgta_reads_adopt_device(mgta_ctx *ctx, const uint32_t *d_packed, uint64_t n_words, const uint64_t *d_start, uint64_t n_reads,
                             mgta_reads **out) {
     if (!ctx || !d_packed || !d_start || !out) { set_error("mgta_reads_adopt_device: null argument"); return MGTA_EINVAL; }
-    auto *r = new mgta_reads;
-    r->ctx = ctx; r->d_packed = d_packed; r->d_start = d_start; r->n_words = n_words; r->n_reads = n_reads;
-    ctx_retain(ctx);
-    *out = r;
-    return MGTA_OK;
+    return guarded("mgta_reads_adopt_device", [&] {
+        auto *r = new mgta_reads;
+        r->ctx = ctx; r->d_packed = d_packed; r->d_start = d_start; r->n_words = n_words; r->n_reads = n_reads;
+        ctx_retain(ctx);
+        *out = r;
+        return MGTA_OK;
+    });
 }
 
 void mgta_reads_free(mgta_reads *r) {
@@ -2541,23 +2545,19 @@ int mgta_sdbg_build_resident(mgta_ctx *ctx, const mgta_reads *rd, uint64_t n_sho
         return MGTA_EINVAL;
     }
     if (min_count < 1) { set_error("min_count must be >= 1"); return MGTA_EINVAL; }
-    if (min_count > 1 && (bucket_begin != 0 || bucket_end != MGTA_NUM_BUCKETS) ) {
-        // stage 1 always covers every bucket (its verdicts feed every stage-2 bucket); a stage-2 shard is fine
-    }
-    try {
-        int W = (2 * k + 4 + 31) / 32;                                 // words_per_substring, s2.cpp:331
-        switch (W) {
-        case 1: return build_impl<1>(ctx, rd, n_short_reads, k, min_count, need_mercy, (uint32_t)bucket_begin, (uint32_t)bucket_end, sink, user, stats);
-        case 2: return build_impl<2>(ctx, rd, n_short_reads, k, min_count, need_mercy, (uint32_t)bucket_begin, (uint32_t)bucket_end, sink, user, stats);
-        case 3: return build_impl<3>(ctx, rd, n_short_reads, k, min_count, need_mercy, (uint32_t)bucket_begin, (uint32_t)bucket_end, sink, user, stats);
-        case 4: return build_impl<4>(ctx, rd, n_short_reads, k, min_count, need_mercy, (uint32_t)bucket_begin, (uint32_t)bucket_end, sink, user, stats);
-        case 5: return build_impl<5>(ctx, rd, n_short_reads, k, min_count, need_mercy, (uint32_t)bucket_begin, (uint32_t)bucket_end, sink, user, stats);
-        case 6: return build_impl<6>(ctx, rd, n_short_reads, k, min_count, need_mercy, (uint32_t)bucket_begin, (uint32_t)bucket_end, sink, user, stats);
-        case 7: return build_impl<7>(ctx, rd, n_short_reads, k, min_count, need_mercy, (uint32_t)bucket_begin, (uint32_t)bucket_end, sink, user, stats);
-        case 8: return build_impl<8>(ctx, rd, n_short_reads, k, min_count, need_mercy, (uint32_t)bucket_begin, (uint32_t)bucket_end, sink, user, stats);
-        default: return build_impl<9>(ctx, rd, n_short_reads, k, min_count, need_mercy, (uint32_t)bucket_begin, (uint32_t)bucket_end, sink, user, stats);
-        }
-    } catch (const HipError &e) { return e.code; }
+    // (stage 1 always covers every bucket: its verdicts feed every stage-2 bucket; a stage-2 shard is fine)
+    return guarded("mgta_sdbg_build", [&] {
+        MGTA_HIP_CHECK(hipSetDevice(ctx->device));
+        return with_key_words((2 * k + 4 + 31) / 32, [&](auto w) {   // words_per_substring, s2.cpp:331
+            Build<decltype(w)::value> B(ctx);
+            B.rd = rd; B.n_short = n_short_reads; B.k = k; B.min_count = min_count; B.need_mercy = need_mercy;
+            B.bucket_begin = (uint32_t)bucket_begin; B.bucket_end = (uint32_t)bucket_end; B.sink = sink; B.user = user;
+            B.modes = SortModes::from_env();
+            const int rc = B.run();
+            if (rc == MGTA_OK && stats) *stats = B.S;
+            return rc;
+        });
+    });
 }
 
 int mgta_sdbg_last_counting(mgta_ctx *ctx, int64_t *hist) {
@@ -2573,7 +2573,7 @@ int mgta_sort_plan(uint64_t n_items, int words_per_key, uint32_t bucket_begin, u
         return MGTA_EINVAL;
     }
     const TopPlan tp = choose_top_plan(nullptr, n_items, std::min(4, (32 * words_per_key - 8) / 8), (double)(bucket_end - bucket_begin) / MGTA_NUM_BUCKETS,
-                                       bucket_begin, bucket_end);
+                                       bucket_begin, bucket_end, SortModes::from_env().bias);
     *n_passes = tp.P;
     *skip_bits = tp.skip;
     return MGTA_OK;
@@ -2585,12 +2585,12 @@ int mgta_sdbg_export_records_device(mgta_ctx *ctx, void *d_dst, uint64_t capacit
     if (ctx->last_k == 0 || (!ctx->last_rec && ctx->last_n_rec)) { set_error("no device-resident build output"); return MGTA_EINVAL; }
     if (!d_dst) return MGTA_OK;                                    // size query
     if (capacity_bytes < ctx->last_n_rec * 2) { set_error("destination too small"); return MGTA_EINVAL; }
-    try {
+    return guarded("mgta_sdbg_export_records_device", [&] {
         MGTA_HIP_CHECK(hipSetDevice(ctx->device));
         if (ctx->last_n_rec) MGTA_HIP_CHECK(hipMemcpyAsync(d_dst, ctx->last_rec, ctx->last_n_rec * 2, hipMemcpyDeviceToDevice, ctx->stream));
         MGTA_HIP_CHECK(hipStreamSynchronize(ctx->stream));
         return MGTA_OK;
-    } catch (const HipError &e) { return e.code; }
+    });
 }
 
 int mgta_sdbg_build(mgta_ctx *ctx, const uint32_t *packed, uint64_t n_words, const uint64_t *start_idx, uint64_t n_reads,
