@@ -102,6 +102,10 @@ int mgta_ctx_set_search_cost_curve(mgta_ctx *, int expansions_per_seed, uint64_t
  * caches stay) with a larger share in the reserve: 1/2, then 7/8, then one search at a time (mgta_astar_stats.n_resumes, a note on
  * stderr).  Small values exercise these paths on small inputs (tests). */
 int mgta_ctx_set_search_arena(mgta_ctx *, int log2_base_nodes, uint64_t pool_bytes);
+/* Pages of 2 MB that one array of a search (its nodes, its heap, its hash table) may hold beyond its base arena: 1 .. 1024, 0 = the
+ * library's 1024 (the default; ~33 M nodes).  A search that needs one more page ends as a failed side (mgta_astar_stats.n_over_limit).
+ * Small values exercise that limit on small inputs (tests); the limit belongs to the context and holds until it is set again. */
+int mgta_ctx_set_search_page_limit(mgta_ctx *, int pages);
 
 /* ------------------------------------------------------------------------------------------------
  * Read ingestion (`megagta buildlib`: SequenceManager::ReadShortReads + WriteBinarySequences, sequence_manager.cpp:109-216,375-410;
@@ -281,8 +285,10 @@ typedef struct mgta_astar_stats {
                                                            * > 0: later seeds may have searched where they could have followed a cached path) */
     int64_t hmm_in_lds;                                   /* 1: the HMM tables were staged in LDS; 0: (M + 1)(A + 11) * 8 B beside the heap tops
                                                            * exceed the CU's 160 KB (models longer than ~400 columns): read from device memory */
-    int64_t n_over_limit;                                 /* search sides that outgrew the library's page tables (2 GB per array, ~33 M nodes) and are
-                                                           * reported as failed searches (ok = 0, no extension); named on stderr.  0 in every measured run */
+    int64_t n_over_limit;                                 /* search sides that outgrew the page limit (2 GB per array, ~33 M nodes, unless
+                                                           * mgta_ctx_set_search_page_limit set another) and are reported as failed searches
+                                                           * (ok = 0, no extension); each is named on stderr, and the count is on the per-gene "Done"
+                                                           * line of `megagta search` and of search_dist.py (rank 0's).  0 in every measured run */
     double ms_queue_drained;                              /* first pass: milliseconds from the kernel's start to the moment the last seed of the batch was
                                                            * TAKEN by a search slot; ms_kernel - ms_queue_drained = the tail in which the launch only finishes
                                                            * the searches in flight (a batch cannot end before its longest search does) */

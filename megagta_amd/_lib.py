@@ -97,6 +97,7 @@ SYMBOLS = {
     "mgta_ctx_set_search_cost_rate": (C.c_int, [C.c_void_p, C.c_int]),
     "mgta_ctx_set_search_cost_curve": (C.c_int, [C.c_void_p, C.c_int, C.c_uint64, C.c_int]),
     "mgta_ctx_set_search_arena": (C.c_int, [C.c_void_p, C.c_int, C.c_uint64]),
+    "mgta_ctx_set_search_page_limit": (C.c_int, [C.c_void_p, C.c_int]),
     "mgta_ctx_device_memory": (C.c_int, [C.c_void_p, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]),
     "mgta_ctx_keep_stream": (C.c_int, [C.c_void_p, C.c_int]),
     "mgta_sdbg_stream_detach": (C.c_int, [C.c_void_p, C.POINTER(C.c_void_p)]),

@@ -110,6 +110,11 @@ class Context:
         grow into (0 = auto).  Small values exercise the in-place growth on small inputs."""
         check(self._L.mgta_ctx_set_search_arena(self.h, int(log2_base_nodes), int(pool_bytes)), "mgta_ctx_set_search_arena")
 
+    def set_search_page_limit(self, pages: int = 0):
+        """pages of 2 MB one array of a search (nodes, heap, hash table) may hold beyond its base arena before the search ends as a failed
+        side (mgta_astar_stats.n_over_limit): 1 .. 1024, 0 = the library's 1024.  Small values exercise that limit on small inputs."""
+        check(self._L.mgta_ctx_set_search_page_limit(self.h, int(pages)), "mgta_ctx_set_search_page_limit")
+
     # ---- SdBG build ---------------------------------------------------------------------------
     def upload_reads(self, packed: np.ndarray, start_idx: np.ndarray) -> "Reads":
         packed = np.ascontiguousarray(packed, dtype=np.uint32)

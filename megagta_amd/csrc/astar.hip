@@ -122,6 +122,12 @@ int mgta_ctx_set_search_arena(mgta_ctx *ctx, int log2_base_nodes, uint64_t pool_
     return MGTA_OK;
 }
 
+int mgta_ctx_set_search_page_limit(mgta_ctx *ctx, int pages) {
+    if (!ctx || pages < 0 || pages > kMaxPages) { set_error("mgta_ctx_set_search_page_limit: 0 <= pages <= %d", kMaxPages); return MGTA_EINVAL; }
+    ctx->search_page_limit = pages;
+    return MGTA_OK;
+}
+
 int mgta_ctx_set_search_share(mgta_ctx *ctx, int num, int den) {
     if (!ctx || num < 1 || den < num) { set_error("mgta_ctx_set_search_share: 1 <= num <= den"); return MGTA_EINVAL; }
     ctx->search_share_num = num; ctx->search_share_den = den;
@@ -231,6 +237,7 @@ void upload_batch(Batch &b, const std::vector<int64_t> &start_node, int prune_le
     a.base_off = 0; a.log_b0 = ctx->astar_log_b0 ? ctx->astar_log_b0 : 13;
     b.slot_bytes = 128ull << a.log_b0;                                         // per node of the base arena: 64 B + 2 heap slots + 2 hash entries of 16 B
     a.slot_bytes = b.slot_bytes; a.gate = b.gated; a.free_share = b.free_share;
+    a.page_limit = (uint32_t)(ctx->search_page_limit ? ctx->search_page_limit : kMaxPages);
     // The order is HELD by default, whatever it costs (advisor r4: giving it up silently made the contigs of large inputs depend on timing and
     // on the rank count).  MEGAGTA_SEARCH_ALLOW_UNORDERED=1 opts into the last resort: a batch whose searches in flight have outgrown the
     // pool (thousands of refused requests) goes on WITHOUT the order, says so on stderr and in mgta_astar_stats.order_abandoned.
@@ -516,9 +523,10 @@ int account_pass(Batch &b, int attempt, const PassPlan &p, const PassOut &o, mgt
         if (b.h_status[(size_t)s] == kSearchOverLimit && !b.over_limit_seen[(size_t)s]) {
             b.over_limit_seen[(size_t)s] = 1;
             char msg[384];
-            snprintf(msg, sizeof(msg), "search %lld (seed %lld, %s) outgrew the library's limit of %d pages of %d KB per array (~%lld M nodes): the reference's pool has no "
-                     "bound (pool_st.h:43), this build's page tables do", (long long)s, (long long)(s / 2), (s & 1) ? "left" : "right", kMaxPages,
-                     1 << (kPageLog - 10), (long long)(((uint64_t)kMaxPages << (kPageLog - 6)) >> 20));
+            snprintf(msg, sizeof(msg), "search %lld (seed %lld, %s) outgrew the %s limit of %u pages of %d KB per array (~%.2f M nodes): the reference's pool has no "
+                     "bound (pool_st.h:43), this build's page tables do", (long long)s, (long long)(s / 2), (s & 1) ? "left" : "right",
+                     b.ctx->search_page_limit ? "context's" : "library's", b.a.page_limit, 1 << (kPageLog - 10),
+                     (double)((uint64_t)b.a.page_limit << (kPageLog - 6)) / (1 << 20));
             const char *strict = getenv("MEGAGTA_SEARCH_STRICT_LIMIT");
             if (strict && atoi(strict) != 0) { set_error("%s", msg); return MGTA_EOVERFLOW; }
             fprintf(stderr, "[megagta_amd] search: %s -- this side of the seed is reported as a failed search, the batch goes on\n", msg);

@@ -42,7 +42,7 @@ constexpr uint32_t kNoChunk = 0xFFFFFFFFu;
 constexpr int kPageClass = 9;                  // 4 KB << 9 = 2 MB
 constexpr int kPageLog = kPageClass + kUnitLog;
 constexpr int kLdsPages = 16;                  // pages of an array named in LDS (32 MB); beyond: a 4 KB table chunk (1024 pages = 2 GB per array)
-constexpr int kMaxPages = 1024;
+constexpr int kMaxPages = 1024;                // the table chunk's size and the ceiling of AstarArgs::page_limit
 constexpr int kPtWords = 3 * kLdsPages + 4;    // LDS words per search: three page tables + the three table chunks' units (+ 1 spare)
 constexpr uint32_t kStage = 8;                 // open-list entries of one walk pass staged in LDS in commit order (more than these: the lane-by-lane loop)
 constexpr uint32_t kStarveLimit = 1u << 15;    // iterations a search waits for memory before it gives up (about a second)
@@ -146,8 +146,8 @@ enum SearchStatus : int32_t {
     kSearchStarved = 2,           // the pool ran dry for it (or its result outgrew out_cap): run again
     kSearchBadSeed = 3,           // k-mer / model position outside the model
     kSearchGateTimeout = 4,       // waited at the ordered-commit gate beyond its bound
-    kSearchOverLimit = 5          // one array of the search reached kMaxPages pages (2 GB beyond the base arena: ~33 M nodes): the
-                                  // library's limit, not the device's
+    kSearchOverLimit = 5          // one array of the search reached AstarArgs::page_limit pages (kMaxPages by default: 2 GB beyond the base
+                                  // arena, ~33 M nodes): the library's limit, not the device's
 };
 // AstarArgs::start_limit: the control words of an ordered / shared-cache launch (agent-scope atomics; zeroed by the host before each pass)
 enum CtlWord : int {
@@ -224,6 +224,8 @@ struct AstarArgs {
                                   // graph: 79 000 of 300 000 seeds taken after 150 s; without the order the 300 000 end in 94 s).
     uint32_t active_slots;        // search slots per workgroup that take seeds (all of them; 1 in the last-resort pass: one search per
                                   // direction at a time, with the whole pool to itself)
+    uint32_t page_limit;          // pages one array of a search may hold, 1 .. kMaxPages (mgta_ctx_set_search_page_limit): a search that needs
+                                  // page `page_limit` of its node array, heap or hash table ends with kSearchOverLimit
 };
 
 __device__ __forceinline__ int to_fval(double x) {   // (int)x as x86-64 cvttsd2si does it (INT_MIN when out of range / NaN)
@@ -912,9 +914,9 @@ __global__ __launch_bounds__(kAstarThreads) void astar_kernel(AstarArgs a) {
     // lane 0: page g of an array (named in LDS below kLdsPages, else in the array's table chunk, obtained with the first such page)
     auto in_pool = [&](uint32_t u) { return a.pool.reserve_bytes == 0ull || ((unsigned long long)(u & kUnitMask) << kUnitLog) < a.pool.reserve_off; };
     // lane 0: page g of an array (named in LDS below kLdsPages, else in the array's table chunk, obtained with the first such page).
-    // 0 = no memory now, 1 = a page of the reserve, 2 = a page of the pool, -1 = the array is at its limit (kMaxPages pages: no memory ever helps)
+    // 0 = no memory now, 1 = a page of the reserve, 2 = a page of the pool, -1 = the array is at its limit (a.page_limit pages: no memory ever helps)
     auto take_page = [&](uint32_t *pt, uint32_t *gtw, uint32_t g) -> int {
-        if (g >= (uint32_t)kMaxPages) return -1;
+        if (g >= a.page_limit) return -1;
         if (g == (uint32_t)kLdsPages) {                                // the table chunk first
             const uint32_t t = chunk_alloc(a.pool, 0, use_reserve);
             if (t == kNoChunk) return 0;
@@ -1294,10 +1296,10 @@ __global__ __launch_bounds__(kAstarThreads) void astar_kernel(AstarArgs a) {
                 if ((np_nodes | np_heap | hp_pages) == 0u && gl == 0) __hip_atomic_fetch_add(&a.pool.stat[kStatGrown], 1ull, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
                 const bool first_bucket = hp_pages == 0u;
                 const uint32_t b_old = hp, b_new = hp_pages;                           // the bucket that is split, the bucket it splits into
-                if (b_new >= (uint32_t)kMaxPages) { status = kSearchOverLimit; stop = true; break; }   // the table is at its limit
+                if (b_new >= a.page_limit) { status = kSearchOverLimit; stop = true; break; }   // the table is at its limit
                 // lane 0: the new page(s).  uA takes the place of the split bucket (or is the first bucket), uB is the new bucket
                 uint32_t uA = kNoChunk, uB = kNoChunk, tnew = kNoChunk;
-                if (gl == 0 && b_new < (uint32_t)kMaxPages) {
+                if (gl == 0 && b_new < a.page_limit) {
                     bool ok_t = true;
                     if (b_new == (uint32_t)kLdsPages) { tnew = chunk_alloc(a.pool, 0, use_reserve); ok_t = tnew != kNoChunk; }
                     if (ok_t) {

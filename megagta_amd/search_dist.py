@@ -152,13 +152,13 @@ def main(argv: list[str]) -> int:
         kmers, states = seeds[gi]
         mine = share[gi]
         tg = time.time()
-        contigs, offsets, nexp = np.zeros(0, np.uint8), np.zeros(1, np.int64), 0
+        contigs, offsets, nexp, nover = np.zeros(0, np.uint8), np.zeros(1, np.int64), 0, 0
         if mine.size:
             fw, rv = api.DeviceHmm(ctx, hmmlib.parse_hmm(fwd)), api.DeviceHmm(ctx, hmmlib.parse_hmm(rev))
             window, rate = window_and_rate(int(mine.size))            # per rank: over its own sub-sequence of the seeds
             contigs, offsets, st = api.astar_search_packed(graph, fw, rv, [kmers[i] for i in mine], [states[i] for i in mine], prune, pen,
                                                            cache_mode=window, cost_rate=rate)
-            nexp = st["n_expansions"]
+            nexp, nover = st["n_expansions"], st["n_over_limit"]
             fw.free(); rv.free()
         if world == 1:                                                # one rank: a gene's file is written as soon as the gene is searched
             write_fasta(f"{out_prefix}_raw_contigs_{name}.fasta", name, contigs, offsets)
@@ -166,8 +166,9 @@ def main(argv: list[str]) -> int:
         else:
             results.append((name, len(kmers), mine, contigs, offsets))
         if rank == 0:
+            # (rank 0's own searches only: the other ranks name their over-limit sides on their own stderr)
             print(f"    [megagta_amd] Done {name}: {len(kmers)} seeds over {world} rank(s), rank 0: {mine.size} seeds, {nexp} expansions, "
-                  f"{time.time() - tg:.2f} s", file=sys.stderr, flush=True)
+                  f"{nover} sides over the page limit, {time.time() - tg:.2f} s", file=sys.stderr, flush=True)
     tg = time.time()
     # the searches are over: the graph and the searches' pool (sized to most of the free memory) go BEFORE the exchange, which then has the
     # device to itself -- its staging is (world + 1) pieces of 64 MB, the contigs themselves stay on the host (advisor r4: the gather used to

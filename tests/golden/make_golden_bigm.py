@@ -25,6 +25,8 @@ from tests.golden.make_golden import run, gz_write, buildgraph, REF, GOLD   # no
 
 from tests.helpers import BIGM_CASES as CASES, bigm_inputs   # noqa: E402  (the tests regenerate the same inputs)
 
+BIG_SEED = {"m1200": "atatggaaagaagactttgccggatgggacgagcaaaagcatgga"}   # model position 698
+
 
 def star_hmm_text() -> str:
     """a 12-column model with `*` match emissions and `*` transitions, a non-uniform COMPO line and a lower-case alphabet letter"""
@@ -75,6 +77,7 @@ def main():
         buildgraph(f"{d}/reads.lib", f"{d}/k44/44", 44)
         seeds = run([f"{REF}/megagta", "findstart", f"{gdir}/ref_aligned.faa", f"{d}/reads.lib.bin", "45", "1"]).stdout.splitlines()
         seeds = sorted(seeds)                              # (the reference shuffles its lines: fast_kmer_filter.cpp:183)
+        all_seeds = seeds
         step = max(1, len(seeds) // c["n_seeds"])
         seeds = seeds[::step][:c["n_seeds"]]
         open(f"{out}/{case}_starting_kmers.txt", "wb").write(b"\n".join(seeds) + b"\n")
@@ -82,6 +85,15 @@ def main():
             res = run([f"{REF}/probe", "astar", f"{d}/k44/44", f"{gdir}/for_enone.hmm", f"{gdir}/rev_enone.hmm",
                        f"{out}/{case}_starting_kmers.txt", "20", "0.5", mode]).stdout
             gz_write(f"{out}/{case}_astar_{mode}.txt.gz", res)
+        if case in BIG_SEED:
+            # one search past the 16 pages an array names in LDS: the findstart seed BIG_SEED[case], cold, prune 0 (its right side opens
+            # ~0.7 M nodes, its left side a few thousand)
+            big = [s for s in all_seeds if s.split()[3].decode().lower() == BIG_SEED[case]]
+            assert len(big) == 1, big
+            open(f"{out}/{case}_big_starting_kmers.txt", "wb").write(big[0] + b"\n")
+            res = run([f"{REF}/probe", "astar", f"{d}/k44/44", f"{gdir}/for_enone.hmm", f"{gdir}/rev_enone.hmm",
+                       f"{out}/{case}_big_starting_kmers.txt", "0", "0.5", "cold"]).stdout
+            gz_write(f"{out}/{case}_big_astar_cold.txt.gz", res)
         meta[case] = dict(c, n_seeds_found=len(seeds),
                           md5={n: hashlib.md5(open(p, "rb").read()).hexdigest()
                                for n, p in (("reads", f"{d}/reads.lib.bin"), ("for", f"{gdir}/for_enone.hmm"), ("rev", f"{gdir}/rev_enone.hmm"))})

@@ -2,6 +2,7 @@
 Bar: contig strings exact; path log-probabilities (real_score, score) within 1e-4 relative -- in fact bit-equal;
 closed-node counts equal (path-identical search)."""
 import os
+import tempfile
 
 import numpy as np
 import pytest
@@ -136,6 +137,17 @@ def test_models_beyond_the_lds_vs_reference(ctx, golden_dir, tmp_path, case, sea
             _check_side(r.left_side, ref["L"])
             assert r.contig(ref["kmer"]) == ref["contig"]
     assert st["max_search_expansions"] > 10000                        # (these searches are long ones: ~10^5 expansions per seed)
+    if (case, request_id(search_mode)) == ("m1200", "g16-grow"):
+        # the page tables in device memory: the goldens above need at most 11 pages per array; one more seed, at prune 0, opens ~0.7 M
+        # nodes -- more than its base arena and 16 pages of 32768 hold -- so pages 17 and up of its node array are named in a table chunk
+        # (take_page, g == kLdsPages).  Its result is the reference's bit for bit.
+        res, st, big = _m1200_big(ctx, golden_dir, g, fw, rv)
+        for r, ref in zip(res, big):
+            _check_side(r.right_side, ref["R"])
+            _check_side(r.left_side, ref["L"])
+            assert r.contig(ref["kmer"]) == ref["contig"]
+        assert st["max_search_nodes"] > (1 << search_mode[1]) + 16 * 32768, st["max_search_nodes"]
+        assert _need(res[0].right_side, 1 << search_mode[1])[0] > 16
 
 
 def test_giving_up_the_order_is_opt_in_and_says_so(ctx, oracle, monkeypatch, meta20k):
@@ -402,3 +414,301 @@ def test_fuzz_genes_k_and_search_options_vs_oracle(ctx, oracle, tmp_path, M, k1,
                    (ref.ok, ref.n_closed, ref.n_expanded, ref.partial, ref.n_opened)
             if ref.ok:
                 assert got["real_score"] == ref.real_score and got["score"] == ref.score and got["fval"] == ref.fval
+
+
+# ---- the page limit (mgta_ctx_set_search_page_limit): a side whose node array, heap or hash table needs page `P` of its own ends at once as a
+# failed side (kSearchOverLimit: ok = 0, no extension, counted in n_over_limit), the batch goes on.  What one side holds follows from its
+# counts (astar_kernel.hpp): n_nodes = n_opened + c1 (c1 = the first expansion's children, 1 .. 129: its delete child always, they are not
+# counted in n_opened); an expansion is preceded by the growth checks with the node count it starts from, which lies in
+# [n_nodes - 129, n_nodes] for the last one; heap entries and hash keys are at most n_nodes - 1 (the start node is neither pushed nor keyed).
+NODES_PER_PAGE, SLOTS_PER_PAGE, MAX_NEW = 1 << 15, 1 << 17, 132         # 2 MB of 64-B nodes / of 16-B heap slots and hash entries; kMaxNew
+
+
+def _heap_slots(n):
+    """heap_slots_needed: the slots a block-stored heap of n entries occupies (its deepest block level complete)"""
+    l = (n | 1).bit_length() - 1
+    b = (l * 11) >> 5
+    r, lvl = l - 3 * b, 1 << (3 * b)
+    return 8 * ((lvl - 1) // 7 + (n - lvl + 1 if r == 0 else lvl))
+
+
+def _pages(n, b0):
+    """pages of (nodes, heap, hash table) a search holds when it expands with n nodes, n heap entries and n hash keys"""
+    nodes = max(0, -(-(n + MAX_NEW - b0) // NODES_PER_PAGE))
+    heap = max(0, -(-(_heap_slots(n + MAX_NEW) - 2 * b0) // SLOTS_PER_PAGE))
+    hash_ = 0 if (n + MAX_NEW) * 2 <= 2 * b0 else max(1, -(-(n + MAX_NEW) * 3 // SLOTS_PER_PAGE))
+    return nodes, heap, hash_
+
+
+def _need(side, b0):
+    """(fewest, most) pages one array of a side with these counts asked for: the node array's least, any array's most"""
+    n = side["n_opened"]
+    return _pages(max(0, n - 128), b0)[0], max(_pages(n + 129, b0))
+
+
+def _over(side):
+    """a side cut off by the page limit: ok = 0 with more than its start node (the other failed searches -- a seed k-mer that is not in
+    the graph -- end before their first expansion, with n_opened = 1)"""
+    return side["ok"] == 0 and side["n_opened"] > 1
+
+
+def _check_over_limit_seed(r, km, sides, P, b0):
+    """the rules for a seed one or both of whose sides hit the limit: a side over it has no extension and was at the limit when it stopped;
+    the contig is the other side's extension around the lower-cased k-mer"""
+    for s, ext in zip(sides, (r.right, r.left)):
+        if _over(s):
+            assert ext == "" and s["partial"] == 0 and s["real_score"] == 0 and s["fval"] == 0, (km, s)
+            assert _need(s, b0)[1] > P, (km, s, P)                  # (it asked for page P of some array)
+        else:
+            assert _need(s, b0)[0] <= P, (km, s, P)                 # (a side that ended on its own never held more than P pages)
+    assert r.contig(km) == r.left + km.lower() + r.right
+
+
+@pytest.fixture
+def limits(ctx, monkeypatch):
+    """a test that sets the context's page limit or base arena: both go back to the library's defaults when it ends"""
+    monkeypatch.delenv("MEGAGTA_SEARCH_STRICT_LIMIT", raising=False)
+    yield ctx
+    ctx.set_search_page_limit(0)
+    ctx.set_search_arena(0, 0)
+
+
+def _choose_limit(sides, b0):
+    """the smallest P at which some sides must hit the limit, at least one side needs exactly P pages of its node array and cannot hit it
+    (an off-by-one in the limit check fails that side), and three quarters of the sides cannot hit it -> (P, must, band, cannot)"""
+    need = [_need(s, b0) for s in sides]
+    for P in range(1, 1025):
+        must = [i for i, (lo, hi) in enumerate(need) if lo > P]
+        cannot = [i for i, (lo, hi) in enumerate(need) if hi <= P]
+        band = [i for i in cannot if need[i][0] == P]
+        if must and band and len(cannot) >= 0.75 * len(sides):
+            return P, must, band, cannot
+    raise AssertionError("no page limit splits these searches")
+
+
+_room = {}
+
+
+def _cold_room_and_limit(ctx, meta20k, G):
+    """meta20k, prune 0, cold, G lanes per search, 128-node base arenas: the run with all the room there is, the limit chosen from it, and
+    the run under that limit (once per module and lane width)"""
+    from megagta_amd import api
+    if G not in _room:
+        g, fw, rv, kmers, states = meta20k.g, meta20k.fw, meta20k.rv, meta20k.kmers, meta20k.states
+        os.environ["MGTA_ASTAR_GROUP"] = str(G)
+        try:
+            ctx.set_search_arena(7, 0)
+            want, st0 = api.astar_search(g, fw, rv, kmers, states, 0, 0.5)
+            sides0 = [s for r in want for s in (r.right_side, r.left_side)]
+            P, must, band, cannot = _choose_limit(sides0, 128)
+            ctx.set_search_page_limit(P)
+            got, st = api.astar_search(g, fw, rv, kmers, states, 0, 0.5)
+        finally:
+            os.environ.pop("MGTA_ASTAR_GROUP", None)
+            ctx.set_search_page_limit(0)
+            ctx.set_search_arena(0, 0)
+        _room[G] = (want, st0, P, must, band, cannot, got, st)
+    return _room[G]
+
+
+@pytest.mark.parametrize("G", [8, 16, 64])
+def test_page_limit_cold_every_lane_width(ctx, meta20k, limits, G):
+    """cold searches under a page limit chosen from the roomy run of the same 400 seeds: the sides that cannot reach it are that run's bit for
+    bit, the ones that must reach it are failed sides without an extension, a side that needs exactly P pages still ends on its own (an
+    off-by-one in the limit fails it), and n_over_limit counts the sides that hit it.  Every lane width: the lanes of a search stop together
+    (with 8 lanes the edge pairs are walked in two passes)"""
+    want, st0, P, must, band, cannot, got, st = _cold_room_and_limit(ctx, meta20k, G)
+    print(f"G {G}: page limit {P}; {len(must)} sides must hit it, {len(band)} need exactly {P} pages and cannot, {len(cannot)} of "
+          f"{2 * len(want)} cannot; {st['n_over_limit']} hit it; largest search {st0['max_search_nodes']} nodes")
+    assert st0["n_over_limit"] == 0 and st0["n_retries"] == 0 and st0["n_grown"] > 300
+    sides0 = [s for r in want for s in (r.right_side, r.left_side)]
+    sides = [s for r in got for s in (r.right_side, r.left_side)]
+    assert not any(_over(s) for s in sides0)
+    for i in cannot:                                                     # (bit-identical: contig, scores, fval, counts)
+        assert sides[i] == sides0[i], (i, P)
+        assert (got[i // 2].right, got[i // 2].left)[i % 2] == (want[i // 2].right, want[i // 2].left)[i % 2]
+    for i in must:
+        assert _over(sides[i]), (i, P)
+    # a side that needs exactly P + 1 pages hits the limit (a check that let page P through would miss it), as the band above pins P
+    assert any(_need(sides0[i], 128)[0] == P + 1 for i in must)
+    hit = [i for i, s in enumerate(sides) if _over(s)]
+    assert set(must) <= set(hit) and not set(hit) & set(cannot)
+    assert st["n_over_limit"] == len(hit) > 0
+    for i in hit:                                                        # (stopped before the expansion that needed the page)
+        assert sides[i]["n_expanded"] < sides0[i]["n_expanded"], i
+    for i in set(range(len(sides))) - set(hit):                          # (a side in between that did not hit it ran to its end)
+        assert sides[i] == sides0[i], (i, P)
+    for r, km in zip(got, meta20k.kmers):
+        _check_over_limit_seed(r, km, (r.right_side, r.left_side), P, 128)
+    for i in hit:                                                        # a seed with one side over the limit: the other side's extension
+        r, w = got[i // 2], want[i // 2]
+        other = (r.left, r.right)[i % 2]
+        assert other == ("" if _over(sides[i ^ 1]) else (w.left, w.right)[i % 2])
+
+
+def test_page_limit_packed_entry_agrees(ctx, meta20k, limits):
+    """mgta_astar_batch_packed (what search_dist runs) under the same limit: the same sides, contigs and n_over_limit as mgta_astar_batch"""
+    from megagta_amd import api
+    want, st0, P, must, band, cannot, got, st = _cold_room_and_limit(ctx, meta20k, 16)
+    os.environ["MGTA_ASTAR_GROUP"] = "16"
+    try:
+        ctx.set_search_arena(7, 0)
+        ctx.set_search_page_limit(P)
+        contigs, offsets, stp, sides = api.astar_search_packed(meta20k.g, meta20k.fw, meta20k.rv, meta20k.kmers, meta20k.states, 0, 0.5, want_sides=True)
+    finally:
+        os.environ.pop("MGTA_ASTAR_GROUP", None)
+    assert stp["n_over_limit"] == st["n_over_limit"] > 0
+    from megagta_amd import _lib
+    fields = [f for f, _ in _lib.AstarSide._fields_]
+    for i, (r, km) in enumerate(zip(got, meta20k.kmers)):
+        assert bytes(contigs[offsets[i]:offsets[i + 1]]).decode() == r.contig(km)
+        for s, d in ((sides[2 * i], r.right_side), (sides[2 * i + 1], r.left_side)):
+            assert {f: getattr(s, f) for f in fields if f != "state"} == {f: d[f] for f in fields if f != "state"} and chr(s.state) == d["state"]
+
+
+_big = {}
+
+
+def _m1200_big(ctx, golden_dir, g=None, fw=None, rv=None):
+    """the m1200 seed of tests/golden/bigm/m1200_big_*, cold, prune 0, 16 lanes per search, 128-node base arenas: its right side opens ~0.7 M
+    nodes.  -> (results, stats, goldens), run once per module (on the graph and models of the caller, or its own)"""
+    from megagta_amd import api
+    if not _big:
+        if g is None:
+            tmp = tempfile.mkdtemp(prefix="m1200_big_")
+            packed, start, gdir, _, _ = H.bigm_case(golden_dir, "m1200", tmp)
+            g = api.Graph(ctx, ctx.build_sdbg(ctx.upload_reads(packed, start), 44))
+            fw = api.DeviceHmm(ctx, hmmlib.parse_hmm(os.path.join(gdir, "for_enone.hmm")))
+            rv = api.DeviceHmm(ctx, hmmlib.parse_hmm(os.path.join(gdir, "rev_enone.hmm")))
+        big = H.parse_probe_astar(H.gz_lines(os.path.join(golden_dir, "bigm", "m1200_big_astar_cold.txt.gz")))
+        os.environ["MGTA_ASTAR_GROUP"] = "16"
+        try:
+            ctx.set_search_arena(7, 0)
+            res, st = api.astar_search(g, fw, rv, [r["kmer"] for r in big], [r["start_state"] for r in big], 0, 0.5)
+        finally:
+            os.environ.pop("MGTA_ASTAR_GROUP", None)
+        _big.update(g=g, fw=fw, rv=rv, res=res, st=st, gold=big)
+    return _big["res"], _big["st"], _big["gold"]
+
+
+def test_page_limit_beyond_the_lds_page_tables_vs_reference(ctx, golden_dir, limits):
+    """a limit beyond the 16 pages an array names in LDS, reached in the table chunk: the m1200 search of ~0.7 M nodes (prune 0, the HMM tables
+    in device memory) under a limit one page below what its node array needs.  That side fails by the rules above; the other side equals
+    the reference's golden bit for bit (the reference has no limit)"""
+    from megagta_amd import api
+    want, st0, big = _m1200_big(ctx, golden_dir)
+    sides0 = [s for r in want for s in (r.right_side, r.left_side)]
+    P = max(_need(s, 128)[0] for s in sides0) - 1                      # (the largest side needs exactly P + 1 pages of nodes)
+    assert P >= 17 and st0["n_over_limit"] == 0
+    must = [i for i, s in enumerate(sides0) if _need(s, 128)[0] > P]
+    cannot = [i for i, s in enumerate(sides0) if _need(s, 128)[1] <= P]
+    assert must and len(must) + len(cannot) == len(sides0)
+    os.environ["MGTA_ASTAR_GROUP"] = "16"
+    try:
+        ctx.set_search_arena(7, 0)
+        ctx.set_search_page_limit(P)
+        res, st = api.astar_search(_big["g"], _big["fw"], _big["rv"], [r["kmer"] for r in big], [r["start_state"] for r in big], 0, 0.5)
+    finally:
+        os.environ.pop("MGTA_ASTAR_GROUP", None)
+    assert st["hmm_in_lds"] == 0
+    sides = [s for r in res for s in (r.right_side, r.left_side)]
+    print(f"m1200 prune 0: page limit {P}; sides {[s['n_opened'] for s in sides0]} nodes in the roomy run; {st['n_over_limit']} over the limit")
+    for i in must:
+        assert _over(sides[i]) and sides[i]["n_expanded"] < sides0[i]["n_expanded"], i
+    for i in cannot:
+        assert sides[i] == sides0[i]
+    for r, ref in zip(res, big):
+        for got, gold in ((r.right_side, ref["R"]), (r.left_side, ref["L"])):
+            if not _over(got):
+                _check_side(got, gold)
+        _check_over_limit_seed(r, ref["kmer"], (r.right_side, r.left_side), P, 128)
+        if not _over(r.left_side):
+            assert ref["contig"].startswith(r.left)
+        if not _over(r.right_side):
+            assert ref["contig"].endswith(r.right)
+    assert st["n_over_limit"] == len(must) == sum(_over(s) for s in sides)
+
+
+def test_page_limit_ordered_window(ctx, meta20k, limits):
+    """the ordered-commit window (B = 8) under a page limit: the batch ends, n_over_limit counts the failed sides, every seed before the first
+    one with a side over the limit is the roomy run's (the later ones may see other paths: a failed side commits none), and two runs under
+    the same limit agree.  (The seeds whose cold searches must reach the limit go to places 4 .. 7 of the order: the first eight seeds see no
+    path of another, so they search as cold ones do and reach it here too)"""
+    from megagta_amd import api
+    _, _, P, must, _, _, _, _ = _cold_room_and_limit(ctx, meta20k, 16)
+    big = sorted({i // 2 for i in must})
+    assert 0 < len(big) <= 4
+    order = [i for i in range(len(meta20k.kmers)) if i not in big]
+    order = order[:4] + big + order[4:]
+    g, fw, rv = meta20k.g, meta20k.fw, meta20k.rv
+    kmers, states = [meta20k.kmers[i] for i in order], [meta20k.states[i] for i in order]
+    ctx.set_search_arena(7, 0)
+    want, st0 = api.astar_search(g, fw, rv, kmers, states, 0, 0.5, cache_mode=8)
+    ctx.set_search_page_limit(P)
+    runs = [api.astar_search(g, fw, rv, kmers, states, 0, 0.5, cache_mode=8) for _ in range(2)]
+    got, st = runs[0]
+    hit = [i for i, r in enumerate(got) if _over(r.right_side) or _over(r.left_side)]
+    print(f"ordered: page limit {P}; {st['n_over_limit']} sides over it, at seeds {hit}")
+    assert st0["n_over_limit"] == 0 and not any(_over(r.right_side) or _over(r.left_side) for r in want)
+    assert st["n_over_limit"] == sum(_over(r.right_side) + _over(r.left_side) for r in got) > 0
+    assert hit[0] == 4 and set(range(4, 4 + len(big))) <= set(hit)
+    for a, b, km in zip(got[:hit[0]], want, kmers):
+        assert a.contig(km) == b.contig(km) and a.right_side == b.right_side and a.left_side == b.left_side
+    for r, km in zip(got, kmers):
+        _check_over_limit_seed(r, km, (r.right_side, r.left_side), P, 128)
+    again, st2 = runs[1]
+    assert st2["n_over_limit"] == st["n_over_limit"] and st2["n_expansions"] == st["n_expansions"]
+    for a, b, km in zip(again, got, kmers):
+        assert a.contig(km) == b.contig(km) and a.right_side == b.right_side and a.left_side == b.left_side
+
+
+def test_page_limit_strict_fails_the_batch_and_leaves_the_context_clean(ctx, toy, meta20k, limits, monkeypatch):
+    """MEGAGTA_SEARCH_STRICT_LIMIT=1: a side over the limit fails the whole batch with MGTA_EOVERFLOW (-6), through either entry, and the
+    message names the seed and the side (the lowest side over the limit).  The same context then gives the reference's cold results:
+    nothing of the pool, the page tables or the statuses is left behind by the pass that returned early"""
+    from megagta_amd import api
+    want, st0, P, must, band, cannot, got, st = _cold_room_and_limit(ctx, meta20k, 16)
+    first = min(i for i, s in enumerate(s for r in got for s in (r.right_side, r.left_side)) if _over(s))     # (search id 2 seed + direction)
+    monkeypatch.setenv("MGTA_ASTAR_GROUP", "16")
+    monkeypatch.setenv("MEGAGTA_SEARCH_STRICT_LIMIT", "1")
+    ctx.set_search_arena(7, 0)
+    ctx.set_search_page_limit(P)
+    for call in (api.astar_search, api.astar_search_packed):
+        with pytest.raises(api.MegaGtaError) as e:
+            call(meta20k.g, meta20k.fw, meta20k.rv, meta20k.kmers, meta20k.states, 0, 0.5)
+        assert "(-6)" in str(e.value) and f"seed {first // 2}, {('right', 'left')[first % 2]})" in str(e.value), str(e.value)
+    monkeypatch.delenv("MEGAGTA_SEARCH_STRICT_LIMIT")
+    monkeypatch.delenv("MGTA_ASTAR_GROUP")
+    ctx.set_search_page_limit(0)
+    g, fw, rv, d = toy
+    gold = H.parse_probe_astar(H.gz_lines(os.path.join(d, "astar_cold_prune0.txt.gz")))
+    res, st = api.astar_search(g, fw, rv, [r["kmer"] for r in gold], [r["start_state"] for r in gold], 0, 0.5)
+    assert st["n_grown"] > 0 and st["n_over_limit"] == 0 and st["n_retries"] == 0
+    for r, ref in zip(res, gold):
+        _check_side(r.right_side, ref["R"])
+        _check_side(r.left_side, ref["L"])
+        assert r.contig(ref["kmer"]) == ref["contig"]
+
+
+def test_page_limit_arguments(ctx, meta20k, limits, monkeypatch):
+    """1 .. 1024 pages; anything else is refused and leaves the limit as it was; 0 restores the library's 1024"""
+    from megagta_amd import api
+    want, st0, P, must, band, cannot, got, st = _cold_room_and_limit(ctx, meta20k, 16)
+    for bad in (-1, 1025, 1 << 20):
+        with pytest.raises(api.MegaGtaError):
+            ctx.set_search_page_limit(bad)
+    for ok in (1, 1024):
+        ctx.set_search_page_limit(ok)
+    monkeypatch.setenv("MGTA_ASTAR_GROUP", "16")
+    ctx.set_search_arena(7, 0)
+    ctx.set_search_page_limit(P)
+    with pytest.raises(api.MegaGtaError):
+        ctx.set_search_page_limit(1025)
+    res, st1 = api.astar_search(meta20k.g, meta20k.fw, meta20k.rv, meta20k.kmers, meta20k.states, 0, 0.5)
+    assert st1["n_over_limit"] == st["n_over_limit"] > 0                # (the refused value left the limit at P pages)
+    assert [(r.right_side, r.left_side) for r in res] == [(r.right_side, r.left_side) for r in got]
+    ctx.set_search_page_limit(0)
+    res, st2 = api.astar_search(meta20k.g, meta20k.fw, meta20k.rv, meta20k.kmers, meta20k.states, 0, 0.5)
+    assert st2["n_over_limit"] == 0
+    for a, b, km in zip(res, want, meta20k.kmers):
+        assert a.contig(km) == b.contig(km) and a.right_side == b.right_side and a.left_side == b.left_side

@@ -1,6 +1,7 @@
 """The process-level drop-in boundary: `megagta buildgraph` / `megagta search` (C++ host + libmegagta_hip.so)
 driven by the Python-3 driver, next to the stock reference binary for the steps outside the path."""
 import os
+import re
 import subprocess
 import sys
 
@@ -63,6 +64,8 @@ def test_single_k_pipeline_matches_reference_artifacts(toy_inputs, oracle, golde
     assert (out / "opts.txt").exists() and (out / "contigs" / "rplB" / "nucl_merged.fasta").exists()
     done = [l.split() for l in (out / "tmp" / "cp.txt").read_text().splitlines()]
     assert [int(a[0]) for a in done] == list(range(len(done))) and all(a[1] == "done" for a in done)
+    # `megagta search` reports the sides over the page limit on its per-gene "Done" line (its stderr goes to the driver's log)
+    assert re.search(r"\[megagta_amd\] Done rplB: .*, 0 sides over the page limit[;)]", (out / "log").read_text())
 
 
 def test_assist_seq_graph_matches_reference(toy_inputs, oracle):
@@ -266,6 +269,8 @@ def test_sharded_search_one_and_two_ranks_vs_megagta_search(two_gene_inputs):
     assert r.returncode == 0, r.stderr[-2000:]
     for gene in ("rplB", "nirK"):
         assert (d / f"sd_w1_raw_contigs_{gene}.fasta").read_bytes() == (d / f"sd_ref_raw_contigs_{gene}.fasta").read_bytes()
+        # the per-gene "Done" line reports rank 0's sides over the page limit
+        assert re.search(rf"\[megagta_amd\] Done {gene}: .*, 0 sides over the page limit, ", r.stderr), r.stderr[-2000:]
 
     def two_ranks(gene_list, tag):
         import socket
