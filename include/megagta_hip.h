@@ -106,6 +106,15 @@ int mgta_ctx_set_search_arena(mgta_ctx *, int log2_base_nodes, uint64_t pool_byt
  * library's 1024 (the default; ~33 M nodes).  A search that needs one more page ends as a failed side (mgta_astar_stats.n_over_limit).
  * Small values exercise that limit on small inputs (tests); the limit belongs to the context and holds until it is set again. */
 int mgta_ctx_set_search_page_limit(mgta_ctx *, int pages);
+/* on: the graphs this context loads FROM NOW ON also hold the full multiplicity of every edge (SuccinctDBG::EdgeMultiplicity,
+ * succinct_dbg.h:133-147; LoadFromMultiFile(..., need_multiplicity = true), succinct_dbg.cpp:618-694): one byte per edge, min(mult, 255),
+ * and for the edges stored as 255 their 16-bit counts in edge order, found by a rank over the 255s (8 bytes per 64 edges) -- the
+ * reference's edge_multi_ + large_multi_h_ without the hash table.  What mgta_sdbg_edge_multiplicity and mgta_contig_coverage need.
+ * off (default): a load allocates, packs and holds exactly what it did before the switch existed; it is never implied (1 byte per
+ * edge is 6.3 GB on the graph of 100 M reads).  A build that runs while the switch is on also keeps the large multiplicities of a
+ * kept multi-pass stream (mgta_ctx_keep_stream) beside its records.  A load that cannot keep the counts (mgta_sdbg_load of a stream
+ * with records of 255: it is not given the large words; a kept stream built while the switch was off) fails with MGTA_EUNSUPPORTED. */
+int mgta_ctx_keep_multiplicity(mgta_ctx *, int on);
 
 /* ------------------------------------------------------------------------------------------------
  * Read ingestion (`megagta buildlib`: SequenceManager::ReadShortReads + WriteBinarySequences, sequence_manager.cpp:109-216,375-410;
@@ -188,6 +197,11 @@ int mgta_sdbg_load(mgta_ctx *, int k, const uint16_t *recs, int64_t size, const 
  * mgta_sdbg_build* call of this context left on the device (one pass over all 65536 buckets), read where it lies — the records
  * never visit the host.  MGTA_EINVAL when there is no such stream (no build yet, a bucket sub-range, several passes). */
 int mgta_sdbg_load_resident(mgta_ctx *, mgta_sdbg **out);
+/* mgta_sdbg_load with the stream's large multiplicities (the sink's `large`: one word per record of 255, in stream order), for a
+ * context that keeps multiplicities (mgta_ctx_keep_multiplicity; without the switch the words are ignored).  MGTA_EINVAL when n_large
+ * is not the number of records stored as 255. */
+int mgta_sdbg_load_large(mgta_ctx *, int k, const uint16_t *recs, int64_t size, const int64_t *bucket_items, const uint32_t *tips,
+                         int64_t n_tip_words, int words_per_tip, const uint16_t *large, int64_t n_large, mgta_sdbg **out);
 /* The same load from the files `buildgraph` wrote: PREFIX.sdbg_info + PREFIX.sdbg.0 .. N-1 (SdbgReader + LoadFromMultiFile,
  * sdbg_multi_io.h:201-417, succinct_dbg.cpp:595-723).  The host maps the files and copies them to the device; the variable-length records
  * are parsed there, one bucket per lane.  What every rank of a multi-GPU search and every one-shot `megagta denovo|search` calls.
@@ -207,6 +221,45 @@ int mgta_sdbg_outgoing(mgta_sdbg *, const int64_t *edges, int64_t n, int64_t *ou
  * Set for tips and $ edges after a load, and for everything `mgta_denovo` removed. */
 int mgta_sdbg_invalid_bits(mgta_sdbg *, uint64_t *words);
 int mgta_sdbg_index_edges(mgta_sdbg *, const uint8_t *seqs /* n x (k+1) */, int64_t n, int64_t *edge_ids);
+
+/* batched EdgeMultiplicity (succinct_dbg.h:133-147): the full count of the (k+1)-mer of each edge, as the stream gave it (tips and $
+ * edges have one too).  MGTA_EINVAL for a graph loaded without mgta_ctx_keep_multiplicity and for an id outside [0, size). */
+int mgta_sdbg_edge_multiplicity(mgta_sdbg *, const int64_t *edge_ids, int64_t n, uint16_t *mult);
+
+/* ------------------------------------------------------------------------------------------------
+ * Per-contig k-mer coverage and abundance (the `kmer_coverage` step at the end of the reference's bin/post_proc.sh:113-118, which
+ * recounts from the reads what the graph already holds).  Contig i = seqs[offsets[i] .. offsets[i + 1]), letters in any case.  A
+ * WINDOW is a (k+1)-mer of the contig at offset p = 0 .. len - k - 1; its coverage is the multiplicity of the edge
+ * IndexBinarySearchEdge (succinct_dbg.cpp:530-549) finds for it, and 0 when there is none or when the window holds a letter other
+ * than A, C, G, T (no N -> G folding: an N was never counted).  Only the string as given is looked up (the graph holds both strands
+ * with equal counts).  per_contig[i]: see the struct; median = the LOWER median over all windows, zeros included (element
+ * (n_windows - 1) / 2 of the ascending order); the mean is sum / n_windows, formed by the caller.  per_window (may be NULL): the
+ * coverages back to back, contig by contig (prefix sums of n_windows index it).  abundance (may be NULL) [65536]: abundance[m] =
+ * number of DISTINCT edges of multiplicity m that the windows of THIS CALL found (an edge reached from three contigs counts once;
+ * index 65535 = that or more).  One call = one set of contigs: the marks live for one call, so a gene's contigs go in one call (the
+ * library cuts its own work into batches that fit the per-window scratch and keeps the marks across them;
+ * mgta_ctx_set_coverage_batch sets the windows per batch, 0 = the library's 2^29: small values exercise that on small inputs).
+ * Every output is a function of (graph, contigs) only.  MGTA_EINVAL for a graph loaded without mgta_ctx_keep_multiplicity.
+ * ------------------------------------------------------------------------------------------------ */
+typedef struct mgta_contig_cov {
+    uint64_t sum;                    /* sum of the window coverages */
+    uint32_t len, n_windows;         /* n_windows = max(0, len - k); 0 -> every other field but len is 0 */
+    uint32_t n_covered;              /* windows with coverage > 0 */
+    uint32_t min, max, median;
+} mgta_contig_cov;
+typedef struct mgta_coverage_stats {
+    int64_t n_contigs, n_windows;
+    int64_t n_walked;                /* windows whose edge was found by one forward step from the window before */
+    int64_t n_index_searches;        /* windows that needed IndexBinarySearchEdge: the first of a contig, and the first after the contig left the graph */
+    int64_t n_batches;
+    int64_t groups_per_cu;           /* lane groups of 8 (one contig, one dependent line in flight each) a CU holds at once in the walk
+                                      * kernel: 32 per workgroup x the workgroups its registers allow (asked of the runtime) */
+    double ms_kernel;                /* walk + statistics kernels (HIP events) */
+    double ms_walk;                  /* the walk kernel alone */
+} mgta_coverage_stats;
+int mgta_ctx_set_coverage_batch(mgta_ctx *, uint64_t windows);
+int mgta_contig_coverage(mgta_sdbg *, const char *seqs, const uint64_t *offsets /* [n + 1] */, int64_t n, mgta_contig_cov *per_contig,
+                         uint16_t *per_window /* optional */, int64_t *abundance /* optional, [65536] */, mgta_coverage_stats *stats /* optional */);
 
 /* ------------------------------------------------------------------------------------------------
  * Seed finder (replaces the read scan of `megagta findstart`, fast_kmer_filter.cpp:108-176,193-215):

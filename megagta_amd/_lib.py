@@ -67,6 +67,19 @@ class LineProbe(C.Structure):
         return {n: getattr(self, n) for n, _ in self._fields_ if n != "pad_"}
 
 
+class ContigCov(C.Structure):
+    _fields_ = [("sum", C.c_uint64), ("len", C.c_uint32), ("n_windows", C.c_uint32), ("n_covered", C.c_uint32), ("min", C.c_uint32),
+                ("max", C.c_uint32), ("median", C.c_uint32)]
+
+
+class CoverageStats(C.Structure):
+    _fields_ = [("n_contigs", C.c_int64), ("n_windows", C.c_int64), ("n_walked", C.c_int64), ("n_index_searches", C.c_int64),
+                ("n_batches", C.c_int64), ("groups_per_cu", C.c_int64), ("ms_kernel", C.c_double), ("ms_walk", C.c_double)]
+
+    def as_dict(self):
+        return {n: getattr(self, n) for n, _ in self._fields_}
+
+
 EDGE_SINK = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_int32, C.c_int32, C.POINTER(C.c_int64), C.POINTER(C.c_uint16), C.c_int64,
                         C.POINTER(C.c_uint16), C.c_int64, C.POINTER(C.c_uint32), C.c_int64)
 CONTIG_SINK = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_void_p, C.c_int64,
@@ -116,6 +129,12 @@ SYMBOLS = {
     "mgta_host_free": (None, [C.c_void_p]),
     "mgta_sdbg_load": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_int64, C.c_int,
                                 C.POINTER(C.c_void_p)]),
+    "mgta_ctx_keep_multiplicity": (C.c_int, [C.c_void_p, C.c_int]),
+    "mgta_ctx_set_coverage_batch": (C.c_int, [C.c_void_p, C.c_uint64]),
+    "mgta_sdbg_load_large": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_int64, C.c_int, C.c_void_p, C.c_int64,
+                                      C.POINTER(C.c_void_p)]),
+    "mgta_sdbg_edge_multiplicity": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p]),
+    "mgta_contig_coverage": (C.c_int, [C.c_void_p, C.c_char_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "mgta_sdbg_free": (None, [C.c_void_p]),
     "mgta_sdbg_size": (C.c_int64, [C.c_void_p]),
     "mgta_sdbg_outgoing": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p]),

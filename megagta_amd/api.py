@@ -101,6 +101,17 @@ class Context:
             self._L.mgta_stream_free(h)
         return recs, tips
 
+    def keep_multiplicity(self, on=True):
+        """graphs loaded from now on also hold the full multiplicity of every edge (1 byte per edge + the counts above 254): what
+        Graph.edge_multiplicity / Graph.contig_coverage need.  Off by default; never implied."""
+        check(self._L.mgta_ctx_keep_multiplicity(self.h, int(bool(on))), "mgta_ctx_keep_multiplicity")
+        self._keep_multiplicity = bool(on)
+
+    def set_coverage_batch(self, windows: int = 0):
+        """windows one batch of Graph.contig_coverage holds in its per-window scratch (0 = the library's 2^29); small values exercise
+        the batching on small inputs.  The result does not depend on it."""
+        check(self._L.mgta_ctx_set_coverage_batch(self.h, int(windows)), "mgta_ctx_set_coverage_batch")
+
     def release_scratch(self):
         """free the work memory kept between calls (build pool, search pool)"""
         check(self._L.mgta_ctx_release_scratch(self.h), "mgta_ctx_release_scratch")
@@ -170,35 +181,71 @@ def export_records_to_torch(ctx: "Context"):
     return t[: n.value * 2]
 
 
+# mgta_contig_cov
+COV_DTYPE = np.dtype([("sum", "<u8"), ("len", "<u4"), ("n_windows", "<u4"), ("n_covered", "<u4"), ("min", "<u4"), ("max", "<u4"), ("median", "<u4")])
+
+
+class _multiplicity:
+    """the context's keep-multiplicity switch set for one load and put back afterwards; .on = what holds during the load"""
+
+    def __init__(self, ctx: "Context", on: bool):
+        self.ctx, self.was = ctx, getattr(ctx, "_keep_multiplicity", False)
+        self.on = bool(on) or self.was
+
+    def __enter__(self):
+        if self.on != self.was:
+            self.ctx.keep_multiplicity(self.on)
+        return self
+
+    def __exit__(self, *exc):
+        if self.on != self.was:
+            self.ctx.keep_multiplicity(self.was)
+        return False
+
+
 class Graph:
     """Device-resident succinct de Bruijn graph (mgta_sdbg) <-> SuccinctDBG (succinct_dbg.h:32-247)."""
 
-    def __init__(self, ctx: Context, stream: "EdgeStream | None", k: int = 0):
-        """stream = None: the edge stream the last build of `ctx` left on the device (mgta_sdbg_load_resident; k = that build's k)"""
+    def __init__(self, ctx: Context, stream: "EdgeStream | None", k: int = 0, keep_multiplicity: bool = False):
+        """stream = None: the edge stream the last build of `ctx` left on the device (mgta_sdbg_load_resident; k = that build's k).
+        keep_multiplicity: this load keeps the full edge multiplicities (the context's switch is set for the load and put back; for a
+        resident stream of several passes it must also have been on during the build, Context.keep_multiplicity)."""
         if stream is None:
             self.ctx, self.k = ctx, k
             out = C.c_void_p()
-            check(ctx._L.mgta_sdbg_load_resident(ctx.h, C.byref(out)), "mgta_sdbg_load_resident")
+            with _multiplicity(ctx, keep_multiplicity) as sw:
+                self.keep_multiplicity = sw.on
+                check(ctx._L.mgta_sdbg_load_resident(ctx.h, C.byref(out)), "mgta_sdbg_load_resident")
             self.h = out
             self.size = ctx._L.mgta_sdbg_size(self.h)
+            self.k = ctx._L.mgta_sdbg_k(self.h)                 # (the build's k, whatever the caller passed)
             return
         self.ctx, self.k = ctx, stream.k
         recs = np.ascontiguousarray(stream.records, dtype=np.uint16)
         bi = np.ascontiguousarray(stream.bucket_items, dtype=np.int64)
         tips = np.ascontiguousarray(stream.tips, dtype=np.uint32)
         out = C.c_void_p()
-        check(ctx._L.mgta_sdbg_load(ctx.h, stream.k, recs.ctypes.data, recs.size, bi.ctypes.data, tips.ctypes.data, tips.size,
-                                    stream.words_per_tip, C.byref(out)), "mgta_sdbg_load")
+        with _multiplicity(ctx, keep_multiplicity) as sw:
+            self.keep_multiplicity = sw.on
+            if sw.on:
+                large = np.ascontiguousarray(stream.large, dtype=np.uint16)
+                check(ctx._L.mgta_sdbg_load_large(ctx.h, stream.k, recs.ctypes.data, recs.size, bi.ctypes.data, tips.ctypes.data, tips.size,
+                                                  stream.words_per_tip, large.ctypes.data, large.size, C.byref(out)), "mgta_sdbg_load_large")
+            else:
+                check(ctx._L.mgta_sdbg_load(ctx.h, stream.k, recs.ctypes.data, recs.size, bi.ctypes.data, tips.ctypes.data, tips.size,
+                                            stream.words_per_tip, C.byref(out)), "mgta_sdbg_load")
         self.h = out
         self.size = ctx._L.mgta_sdbg_size(self.h)
 
     @classmethod
-    def from_files(cls, ctx: Context, prefix: str) -> "Graph":
+    def from_files(cls, ctx: Context, prefix: str, keep_multiplicity: bool = False) -> "Graph":
         """PREFIX.sdbg_info + PREFIX.sdbg.* -> graph on the device (mgta_sdbg_load_files: the records are parsed on the device)"""
         self = cls.__new__(cls)
         self.ctx = ctx
         out = C.c_void_p()
-        check(ctx._L.mgta_sdbg_load_files(ctx.h, os.fsencode(prefix), C.byref(out)), "mgta_sdbg_load_files")
+        with _multiplicity(ctx, keep_multiplicity) as sw:
+            self.keep_multiplicity = sw.on
+            check(ctx._L.mgta_sdbg_load_files(ctx.h, os.fsencode(prefix), C.byref(out)), "mgta_sdbg_load_files")
         self.h = out
         self.size = ctx._L.mgta_sdbg_size(self.h)
         self.k = ctx._L.mgta_sdbg_k(self.h)
@@ -224,6 +271,40 @@ class Graph:
         """the validity bits as they are now (bit e of word e // 64 set = edge e is not part of the graph)"""
         out = np.zeros((self.size + 63) // 64, dtype=np.uint64)
         check(self.ctx._L.mgta_sdbg_invalid_bits(self.h, out.ctypes.data), "mgta_sdbg_invalid_bits")
+        return out
+
+    def edge_multiplicity(self, ids) -> np.ndarray:
+        """EdgeMultiplicity (succinct_dbg.h:133-147) for a batch of edge ids -> uint16[n]; needs keep_multiplicity=True at the load"""
+        e = np.ascontiguousarray(ids, dtype=np.int64)
+        out = np.empty(e.size, dtype=np.uint16)
+        check(self.ctx._L.mgta_sdbg_edge_multiplicity(self.h, e.ctypes.data, e.size, out.ctypes.data), "mgta_sdbg_edge_multiplicity")
+        return out
+
+    def contig_coverage(self, seqs, per_window: bool = False, abundance: bool = True) -> dict:
+        """mgta_contig_coverage for a list of contigs (str or bytes, any case): the coverage of a window = the multiplicity of its
+        (k+1)-mer's edge, 0 when absent or not ACGT.  -> dict(contigs = structured array (sum, len, n_windows, n_covered, min, max,
+        median: the lower median over all windows), abundance = int64[65536] distinct edges per multiplicity over THIS call,
+        stats, and with per_window=True per_window = uint16 coverages back to back + window_offsets int64[n + 1]).
+        One call = one set of contigs (abundance marks live for one call): pass a gene's contigs together."""
+        raw = [s if isinstance(s, (bytes, bytearray)) else str(s).encode() for s in seqs]
+        n = len(raw)
+        offsets = np.zeros(n + 1, dtype=np.uint64)
+        if n:
+            np.cumsum([len(s) for s in raw], out=offsets[1:])
+        buf = b"".join(raw)
+        cov = np.zeros(n, dtype=COV_DTYPE)
+        nw = np.maximum(0, np.diff(offsets.astype(np.int64)) - self.ctx._L.mgta_sdbg_k(self.h))      # (the graph's own k sizes the buffer)
+        woff = np.zeros(n + 1, dtype=np.int64)
+        np.cumsum(nw, out=woff[1:])
+        pw = np.zeros(int(woff[-1]), dtype=np.uint16) if per_window else None
+        ab = np.zeros(65536, dtype=np.int64) if abundance else None
+        st = _lib.CoverageStats()
+        check(self.ctx._L.mgta_contig_coverage(self.h, buf, offsets.ctypes.data, n, cov.ctypes.data if n else None,
+                                               pw.ctypes.data if per_window and pw.size else None, ab.ctypes.data if abundance else None,
+                                               C.byref(st)), "mgta_contig_coverage")
+        out = dict(contigs=cov, abundance=ab, stats=st.as_dict())
+        if per_window:
+            out["per_window"], out["window_offsets"] = pw, woff
         return out
 
     def denovo(self, max_tip_len: int = 150, no_bubble: bool = False, min_contig: int = 0) -> tuple[str, dict]:

@@ -113,6 +113,15 @@ struct mgta_ctx {
     mgta::DevBuf acc_rec, acc_tips;
     uint64_t acc_n_rec = 0, acc_n_tips = 0;
     std::vector<int64_t> acc_items;
+    // mgta_ctx_keep_multiplicity: loads keep the full edge multiplicities.  The large words (records stored as 255) of the last pass
+    // are in the pool; a kept multi-pass stream accumulates them here when the build ran with the switch on (acc_has_large)
+    int keep_multiplicity = 0;
+    uint64_t coverage_batch_windows = 0;   // mgta_ctx_set_coverage_batch (0 = the library's default)
+    const void *last_large = nullptr;
+    uint64_t last_n_large = 0;
+    mgta::DevBuf acc_large;
+    uint64_t acc_n_large = 0;
+    bool acc_has_large = false;
 };
 
 namespace mgta {
@@ -121,6 +130,7 @@ void ctx_release(mgta_ctx *c);    // frees the context when the last reference g
 // the context no longer names the output of its last build (its buffers went, or now belong to something else)
 inline void forget_last_build(mgta_ctx *c) {
     c->last_rec = nullptr; c->last_tips = nullptr; c->last_first = nullptr; c->last_n_rec = 0; c->last_n_tips = 0; c->last_k = 0;
+    c->last_large = nullptr; c->last_n_large = 0;
 }
 }  // namespace mgta
 

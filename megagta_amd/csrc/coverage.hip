@@ -1,0 +1,397 @@
+// coverage.hip — per-contig k-mer coverage and abundance from the resident graph, and the batched EdgeMultiplicity query.
+//
+// The reference's last post-processing step (`kmer_coverage`, bin/post_proc.sh:113-118) counts the (k+1)-mers of the contigs in a
+// second pass over all reads.  That count is the multiplicity the edge stream already carries (sdbg_multi_io.h:83-112) and a graph
+// loaded under mgta_ctx_keep_multiplicity still holds (SuccinctDBG::EdgeMultiplicity, succinct_dbg.h:133-147): the coverage of a
+// contig is one walk along it.
+//
+// A window's edge is what IndexBinarySearchEdge (succinct_dbg.cpp:530-549) finds for its k + 1 letters.  Only the first window of a
+// contig is found that way; the edge of the next window is the edge of the node Forward(e) points to whose label is the next base:
+// ONE dependent graph line per window.  That is a pointer chase (0.5-0.65 us per dependent line), so the parallelism is
+// across contigs: a group of 8 lanes owns a contig and reads a line with one request (16 bytes per lane, the shape of probe.hip),
+// 32 groups per workgroup, as many workgroups per CU as the kernel's registers allow (asked of the runtime at the launch and
+// reported in mgta_coverage_stats.groups_per_cu).  As compiled for gfx950 the walk takes 111 VGPRs = 4 waves per SIMD = 4 workgroups
+// = 128 groups = 128 independent lines in flight per CU, half of the 256 DESIGN 5 names for the full random-line rate: asking the
+// compiler for 8 waves per SIMD (64 VGPRs) spills 72 VGPRs to scratch memory (its resource report), so it is not asked.  Contigs are
+// handed out longest first from one atomic head, a few at a time.
+#include <algorithm>
+#include <numeric>
+#include <vector>
+
+#include "common.hpp"
+#include "device_utils.hpp"
+#include "graph.hpp"
+
+namespace mgta {
+namespace {
+
+constexpr int kCovThreads = 256;          // 4 waves = 32 groups of 8 lanes
+constexpr int kCovLowBins = 256;          // abundance bins counted in LDS per workgroup (where nearly all edges are); the rest go straight to device memory
+
+struct CovJob {                           // one contig of a batch
+    uint64_t off;                         // its first letter in the batch's symbols
+    uint64_t win_base;                    // its first window in the batch's per-window scratch
+    uint32_t len, idx;                    // letters; contig number inside the batch
+};
+
+// letters -> symbols 1..4 (A C G T in either case), 0 for anything else (an N is NOT folded to G: it was never counted); in place
+__global__ __launch_bounds__(256) void cov_symbols_kernel(uint8_t *s, uint64_t n) {
+    const uint64_t stride = (uint64_t)gridDim.x * 256;
+    for (uint64_t i = (uint64_t)blockIdx.x * 256 + threadIdx.x; i < n; i += stride) {
+        const uint32_t c = s[i] & 0xDFu;
+        s[i] = (uint8_t)(c == 'A' ? 1 : c == 'C' ? 2 : c == 'G' ? 3 : c == 'T' ? 4 : 0);
+    }
+}
+
+// A group of 8 lanes fetches line li with one request, 16 bytes per lane, and hands every lane the whole line (sub = lane & 7).
+// All 8 lanes of a group run the same control flow on the same values, so the shuffles always find their source lane active.
+__device__ __forceinline__ LineR grp_load_line(const GraphDev &g, uint64_t li, int sub) {
+    const uint4 v = reinterpret_cast<const uint4 *>(g.lines + li)[sub];
+    const uint64_t lo = (uint64_t)v.x | ((uint64_t)v.y << 32), hi = (uint64_t)v.z | ((uint64_t)v.w << 32);
+    LineR L;
+    L.w0 = __shfl(lo, 0, 8); L.w1 = __shfl(hi, 0, 8); L.w2 = __shfl(lo, 1, 8); L.w3 = __shfl(hi, 1, 8);
+    L.last = __shfl(lo, 2, 8); L.tip = __shfl(hi, 2, 8); L.invalid = __shfl(lo, 3, 8); L.multi1 = 0;
+    L.rank_last = __shfl(lo, 4, 8);
+    L.rw0 = __shfl(lo, 5, 8); L.rw1 = __shfl(hi, 5, 8); L.rw2 = __shfl(lo, 6, 8); L.rw3 = __shfl(hi, 6, 8);
+    L.h01 = __shfl(lo, 7, 8); L.h23 = __shfl(hi, 7, 8);
+    return L;
+}
+
+// One forward step of the walk.  In: e = the edge of the window before, L = its line (e >> 6), c = the next base (1..4).
+// Out: the edge of the next window, i.e. the edge of the node Forward(e) points to (succinct_dbg.h:155-164) whose label is c or c + 4,
+// with L = its line; -1 when that node has no such edge.
+//
+// This is NOT g_outgoing / g_outgoing_line: those answer -1 for a start edge whose `invalid` bit is set and skip invalid target edges
+// (tips and $ edges after a load, everything `denovo` removed), while IndexBinarySearchEdge -- the contract of a window -- does not look
+// at that bit, and such an edge has a multiplicity in the stream like any other.  So the step forwards from any edge and scans the
+// target node exactly as IndexBinarySearchEdge scans the node it found: from the node's `last` edge downwards to the next last | tip bit.
+__device__ __forceinline__ int64_t cov_step(const GraphDev &g, LineR &L, int64_t e, int c, int sub) {
+    int a = l_W(L, e);
+    if (a > 4) a -= 4;
+    if (a == 0) return -1;
+    int64_t cnt;                                                          // Rank(a, e) from the registers (rank_and_select.h:153)
+    if (e >= g.size - 1) cnt = a == 1 ? g.total_w[1] : a == 2 ? g.total_w[2] : a == 3 ? g.total_w[3] : g.total_w[4];
+    else {
+        const int j = (int)(e & 63), fw = j >> 4;
+        const int nb = (j & 15) + 1;
+        const uint64_t m = nb == 16 ? ~0ull : ((1ull << (4 * nb)) - 1);
+        cnt = (int64_t)sel4(L.rw0, L.rw1, L.rw2, L.rw3, a - 1);
+        const uint64_t e0 = nib_eq(L.w0, a), e1 = nib_eq(L.w1, a), e2 = nib_eq(L.w2, a), e3 = nib_eq(L.w3, a);
+        cnt += __popcll(fw > 0 ? e0 : (e0 & m));
+        if (fw >= 1) cnt += __popcll(fw > 1 ? e1 : (e1 & m));
+        if (fw >= 2) cnt += __popcll(fw > 2 ? e2 : (e2 & m));
+        if (fw >= 3) cnt += __popcll(e3 & m);
+    }
+    const int64_t rf = a == 1 ? g.rank_f[1] : a == 2 ? g.rank_f[2] : a == 3 ? g.rank_f[3] : g.rank_f[4];
+    const int64_t r = rf + cnt - 1;
+    if (r >= g.total_last || r < 0) return -1;
+    const uint64_t hh = (a <= 2) ? L.h01 : L.h23;
+    uint64_t li = (a & 1) ? (hh & 0xFFFFFFFFull) : (hh >> 32);           // fwd_hint[a - 1]
+    LineR A = grp_load_line(g, li, sub);                                  // the one dependent line of this window
+    uint64_t next_rank = A.rank_last + (uint64_t)__popcll(A.last);
+    while (li + 1 < g.n_lines && (int64_t)next_rank <= r) {               // rare: the target is a line further
+        ++li;
+        A = grp_load_line(g, li, sub);
+        next_rank = A.rank_last + (uint64_t)__popcll(A.last);
+    }
+    int64_t x = (int64_t)(li << 6) + select64(A.last, (int)(r - (int64_t)A.rank_last));
+    do {                                                                  // succinct_dbg.cpp:540-548
+        const bool in = (uint64_t)(x >> 6) == li;                         // almost always: the node's edges sit in the target line
+        const int lab = in ? l_W(A, x) : g_W(g, x);
+        if (lab == c || lab - 4 == c) {
+            L = in ? A : grp_load_line(g, (uint64_t)x >> 6, sub);
+            return x;
+        }
+        --x;
+    } while (x >= 0 && !(((uint64_t)(x >> 6) == li) ? g_bit(A.last | A.tip, x) : (int)g_last_or_tip(g, x)));
+    return -1;
+}
+
+// counters: [0] queue head, [1] windows found by a step, [2] index searches
+__global__ __launch_bounds__(kCovThreads) void cov_walk_kernel(GraphDev g, MultDev m, const uint8_t *sym, const CovJob *jobs, uint32_t n_jobs, uint32_t chunk,
+                                                               uint16_t *pw, uint32_t *marks, unsigned long long *abund, unsigned long long *counters) {
+    __shared__ uint32_t s_hist[kCovLowBins];
+    for (int i = threadIdx.x; i < kCovLowBins; i += kCovThreads) s_hist[i] = 0;
+    __syncthreads();
+    const int sub = threadIdx.x & 7;
+    const int k = g.k;
+    uint32_t walked = 0, searched = 0;
+    for (;;) {
+        unsigned long long first = 0;
+        if (sub == 0) first = atomicAdd(&counters[0], (unsigned long long)chunk);
+        first = __shfl(first, 0, 8);
+        if (first >= n_jobs) break;
+        const uint32_t j_end = (uint32_t)min((unsigned long long)n_jobs, first + chunk);
+        for (uint32_t j = (uint32_t)first; j < j_end; ++j) {
+            const CovJob job = jobs[j];
+            const uint8_t *s = sym + job.off;
+            const uint32_t n_win = job.len > (uint32_t)k ? job.len - (uint32_t)k : 0;
+            uint16_t *out = pw + job.win_base;
+            int run = 0;                                                  // A C G T letters in a row, up to the window's last letter
+            for (int i = 0; i < k && (uint32_t)i < job.len; ++i) run = s[i] ? run + 1 : 0;
+            int64_t e = -1;                                               // the edge of the window before, -1 = the walk has to start again
+            LineR L{};
+            uint32_t mine = 0;
+            for (uint32_t p = 0; p < n_win; ++p) {
+                const int c = s[p + k];
+                run = c ? run + 1 : 0;
+                uint32_t cov = 0;
+                if (run > k) {
+                    if (e >= 0) {
+                        e = cov_step(g, L, e, c, sub);
+                        if (e >= 0) ++walked;
+                    } else {
+                        e = g_index_edge(g, s + p);
+                        ++searched;
+                        if (e >= 0) L = grp_load_line(g, (uint64_t)e >> 6, sub);
+                    }
+                    if (e >= 0) {
+                        cov = g_edge_mult(m, e);
+                        if (marks && sub == 0) {                          // abundance: the lane that turns the edge's bit on counts the edge
+                            const uint32_t bit = 1u << (e & 31);
+                            if (!(atomicOr(&marks[e >> 5], bit) & bit)) {
+                                if (cov < (uint32_t)kCovLowBins) atomicAdd(&s_hist[cov], 1u);
+                                else atomicAdd(&abund[cov], 1ull);
+                            }
+                        }
+                    }
+                } else e = -1;
+                // eight windows leave as one 16-byte store of the group
+                if ((int)(p & 7) == sub) mine = cov;
+                if ((p & 7) == 7 || p + 1 == n_win) {
+                    const uint32_t q = (p & ~7u) + (uint32_t)sub;
+                    if (q <= p) out[q] = (uint16_t)mine;
+                }
+            }
+        }
+    }
+    __syncthreads();
+    if (marks)
+        for (int i = threadIdx.x; i < kCovLowBins; i += kCovThreads)
+            if (s_hist[i]) atomicAdd(&abund[i], (unsigned long long)s_hist[i]);
+    const uint32_t w = wave_sum(sub == 0 ? walked : 0u), sc = wave_sum(sub == 0 ? searched : 0u);
+    if (lane_id() == 0) {
+        if (w) atomicAdd(&counters[1], (unsigned long long)w);
+        if (sc) atomicAdd(&counters[2], (unsigned long long)sc);
+    }
+}
+
+// the bin of `h` (256 bins, 4 per lane) that holds the r-th element (0-based) of what was counted; rem = its rank inside the bin
+__device__ __forceinline__ uint32_t cov_select_bin(const uint32_t *h, uint32_t r, uint32_t &rem) {
+    const int lane = lane_id();
+    const uint32_t c0 = h[lane * 4], c1 = h[lane * 4 + 1], c2 = h[lane * 4 + 2], c3 = h[lane * 4 + 3];
+    const uint32_t tot = c0 + c1 + c2 + c3, incl = wave_incl_scan(tot), excl = incl - tot;
+    const bool here = excl <= r && r < incl;
+    uint32_t bin = 0, left = 0;
+    if (here) {
+        uint32_t q = r - excl;
+        if (q < c0) bin = lane * 4;
+        else if ((q -= c0) < c1) bin = lane * 4 + 1;
+        else if ((q -= c1) < c2) bin = lane * 4 + 2;
+        else { q -= c2; bin = lane * 4 + 3; }
+        left = q;
+    }
+    const uint64_t who = __ballot(here);
+    const int src = who ? __ffsll((long long)who) - 1 : 0;
+    rem = __shfl(left, src, 64);
+    return __shfl(bin, src, 64);
+}
+
+// One wave per contig over its per-window slice.  The median (lower median, zeros included) by a counting select over the 16-bit
+// value range: the high byte, then the low byte among the values of that high byte -- no sort.
+__global__ __launch_bounds__(256) void cov_stats_kernel(const CovJob *jobs, uint32_t n_jobs, int k, const uint16_t *pw, mgta_contig_cov *out) {
+    __shared__ uint32_t s_h[4][256];
+    const int w = wave_id(), lane = lane_id();
+    const uint32_t j = blockIdx.x * 4 + (uint32_t)w;
+    if (j >= n_jobs) return;                                              // (whole waves leave; the rest use wave-level ordering only)
+    const CovJob job = jobs[j];
+    const uint32_t n_win = job.len > (uint32_t)k ? job.len - (uint32_t)k : 0;
+    const uint16_t *v = pw + job.win_base;
+    mgta_contig_cov res;
+    res.sum = 0; res.len = job.len; res.n_windows = n_win; res.n_covered = 0; res.min = 0; res.max = 0; res.median = 0;
+    if (n_win) {
+        uint64_t sum = 0;
+        uint32_t mn = 0xFFFFFFFFu, mx = 0, nc = 0;
+        uint32_t *h = s_h[w];
+        for (int i = 0; i < 4; ++i) h[lane * 4 + i] = 0;
+        wave_lds_fence();
+        for (uint32_t i = lane; i < n_win; i += 64) {
+            const uint32_t x = v[i];
+            sum += x; mn = min(mn, x); mx = max(mx, x); nc += x != 0;
+            atomicAdd(&h[x >> 8], 1u);
+        }
+        wave_lds_fence();
+        uint32_t rem = 0;
+        const uint32_t hi = cov_select_bin(h, (n_win - 1) / 2, rem);
+        wave_lds_fence();
+        for (int i = 0; i < 4; ++i) h[lane * 4 + i] = 0;
+        wave_lds_fence();
+        for (uint32_t i = lane; i < n_win; i += 64) {
+            const uint32_t x = v[i];
+            if ((x >> 8) == hi) atomicAdd(&h[x & 255u], 1u);
+        }
+        wave_lds_fence();
+        uint32_t rem2 = 0;
+        const uint32_t lo = cov_select_bin(h, rem, rem2);
+        res.sum = wave_sum64(sum); res.min = wave_min(mn); res.max = wave_max(mx); res.n_covered = wave_sum(nc);
+        res.median = (hi << 8) | lo;
+    }
+    if (lane == 0) out[job.idx] = res;
+}
+
+__global__ __launch_bounds__(256) void edge_mult_kernel(MultDev m, const int64_t *ids, int64_t n, uint16_t *out) {
+    const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (i < n) out[i] = (uint16_t)g_edge_mult(m, ids[i]);
+}
+
+// the per-window scratch: a key buffer of the build pool when it is large enough (it sits idle between the steps), grown otherwise
+uint16_t *window_scratch(mgta_ctx *ctx, uint64_t bytes) {
+    if ((int)ctx->pool.size() < S_NUM) ctx->pool.resize(S_NUM);
+    DevBuf &b = ctx->pool[S_KEYS_A];
+    if (!b.p || b.bytes < bytes) {
+        b.release();
+        b.alloc(bytes, &ctx->live_bytes, &ctx->peak_bytes);
+    }
+    return b.as<uint16_t>();
+}
+
+float elapsed_ms(hipEvent_t a, hipEvent_t b) {
+    float ms = 0;
+    MGTA_HIP_CHECK(hipEventSynchronize(b));
+    MGTA_HIP_CHECK(hipEventElapsedTime(&ms, a, b));
+    return ms;
+}
+
+}  // namespace
+}  // namespace mgta
+
+using namespace mgta;
+
+extern "C" {
+
+int mgta_sdbg_edge_multiplicity(mgta_sdbg *g, const int64_t *edge_ids, int64_t n, uint16_t *mult) {
+    if (!g || n < 0 || (n > 0 && (!edge_ids || !mult))) { set_error("mgta_sdbg_edge_multiplicity: bad argument"); return MGTA_EINVAL; }
+    if (!g->has_mult) { set_error("mgta_sdbg_edge_multiplicity: the graph was loaded without multiplicities (mgta_ctx_keep_multiplicity)"); return MGTA_EINVAL; }
+    for (int64_t i = 0; i < n; ++i)
+        if (edge_ids[i] < 0 || edge_ids[i] >= g->dev.size) { set_error("mgta_sdbg_edge_multiplicity: edge id %lld out of range", (long long)edge_ids[i]); return MGTA_EINVAL; }
+    if (n == 0) return MGTA_OK;
+    return guarded("mgta_sdbg_edge_multiplicity", [&]() {
+        mgta_ctx *ctx = g->ctx;
+        MGTA_HIP_CHECK(hipSetDevice(ctx->device));
+        DevBuf d_e, d_m;
+        d_e.alloc((size_t)n * 8); d_m.alloc((size_t)n * 2);
+        MGTA_HIP_CHECK(hipMemcpyAsync(d_e.p, edge_ids, (size_t)n * 8, hipMemcpyHostToDevice, ctx->stream));
+        hipLaunchKernelGGL(edge_mult_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, ctx->stream, g->mult, d_e.as<int64_t>(), n, d_m.as<uint16_t>());
+        MGTA_HIP_CHECK(hipGetLastError());
+        MGTA_HIP_CHECK(hipMemcpyAsync(mult, d_m.p, (size_t)n * 2, hipMemcpyDeviceToHost, ctx->stream));
+        MGTA_HIP_CHECK(hipStreamSynchronize(ctx->stream));
+        return MGTA_OK;
+    });
+}
+
+int mgta_contig_coverage(mgta_sdbg *g, const char *seqs, const uint64_t *offsets, int64_t n, mgta_contig_cov *per_contig, uint16_t *per_window,
+                         int64_t *abundance, mgta_coverage_stats *stats) {
+    if (!g || n < 0 || n > 0xFFFFFFF0ll || (n > 0 && (!offsets || !per_contig))) { set_error("mgta_contig_coverage: bad argument"); return MGTA_EINVAL; }
+    if (!g->has_mult) { set_error("mgta_contig_coverage: the graph was loaded without multiplicities (mgta_ctx_keep_multiplicity)"); return MGTA_EINVAL; }
+    for (int64_t i = 0; i < n; ++i)
+        if (offsets[i + 1] < offsets[i] || offsets[i + 1] - offsets[i] > 0xFFFFFFF0ull || (offsets[i + 1] > offsets[i] && !seqs)) {
+            set_error("mgta_contig_coverage: contig %lld: offsets must ascend, a contig holds < 2^32 letters", (long long)i);
+            return MGTA_EINVAL;
+        }
+    if (stats) memset(stats, 0, sizeof(*stats));
+    if (abundance) memset(abundance, 0, 65536 * sizeof(int64_t));
+    if (n == 0) return MGTA_OK;
+    hipEvent_t ev[3] = {nullptr, nullptr, nullptr};
+    const int rc = guarded("mgta_contig_coverage", [&]() {
+        mgta_ctx *ctx = g->ctx;
+        MGTA_HIP_CHECK(hipSetDevice(ctx->device));
+        hipStream_t st = ctx->stream;
+        const uint64_t k = (uint64_t)g->dev.k;
+        for (auto &e : ev) MGTA_HIP_CHECK(hipEventCreate(&e));
+        const uint64_t cap = ctx->coverage_batch_windows ? ctx->coverage_batch_windows : 1ull << 29;   // windows per batch: 1 GB of per-window scratch
+        // workgroups of the walk a CU holds at once: what its registers allow (never assumed)
+        int blocks_per_cu = 0;
+        MGTA_HIP_CHECK(hipOccupancyMaxActiveBlocksPerMultiprocessor(&blocks_per_cu, cov_walk_kernel, kCovThreads, 0));
+        blocks_per_cu = std::max(1, blocks_per_cu);
+        DevBuf d_cnt, d_abund, d_sym, d_jobs, d_out;
+        d_cnt.alloc(64);
+        MGTA_HIP_CHECK(hipMemsetAsync(d_cnt.p, 0, 64, st));
+        uint32_t *d_marks = nullptr;
+        if (abundance) {                                                  // one mark bit per edge, zeroed per call = per set of contigs
+            const size_t mark_b = ((size_t)g->dev.size / 32 + 2) * 4;
+            if (g->marks.bytes < mark_b) g->marks.alloc(mark_b, &ctx->live_bytes, &ctx->peak_bytes);
+            MGTA_HIP_CHECK(hipMemsetAsync(g->marks.p, 0, mark_b, st));
+            d_marks = g->marks.as<uint32_t>();
+            d_abund.alloc(65536 * 8);
+            MGTA_HIP_CHECK(hipMemsetAsync(d_abund.p, 0, 65536 * 8, st));
+        }
+        std::vector<CovJob> jobs;
+        uint64_t win_done = 0;
+        double ms_walk = 0, ms_stats = 0;
+        int64_t n_batches = 0;
+        for (int64_t c0 = 0; c0 < n;) {
+            // the contigs [c0, c1) of this batch: as many as fit the scratch (one at least)
+            int64_t c1 = c0;
+            uint64_t n_win = 0;
+            jobs.clear();
+            while (c1 < n) {
+                const uint64_t len = offsets[c1 + 1] - offsets[c1], wn = len > k ? len - k : 0;
+                if (c1 > c0 && n_win + wn > cap) break;
+                jobs.push_back(CovJob{offsets[c1] - offsets[c0], n_win, (uint32_t)len, (uint32_t)(c1 - c0)});
+                n_win += wn;
+                ++c1;
+            }
+            const uint32_t nj = (uint32_t)jobs.size();
+            // longest first, so that no group starts a long contig when the others are about to finish (ties by number: the order is fixed)
+            std::sort(jobs.begin(), jobs.end(), [](const CovJob &a, const CovJob &b) { return a.len != b.len ? a.len > b.len : a.idx < b.idx; });
+            const uint64_t n_bytes = offsets[c1] - offsets[c0];
+            if (d_sym.bytes < n_bytes + 16) d_sym.alloc(n_bytes + 16, &ctx->live_bytes, &ctx->peak_bytes);
+            if (d_jobs.bytes < (size_t)nj * sizeof(CovJob)) d_jobs.alloc((size_t)nj * sizeof(CovJob), &ctx->live_bytes, &ctx->peak_bytes);
+            if (d_out.bytes < (size_t)nj * sizeof(mgta_contig_cov)) d_out.alloc((size_t)nj * sizeof(mgta_contig_cov), &ctx->live_bytes, &ctx->peak_bytes);
+            uint16_t *d_pw = window_scratch(ctx, n_win * 2 + 64);
+            if (n_bytes) MGTA_HIP_CHECK(hipMemcpyAsync(d_sym.p, seqs + offsets[c0], n_bytes, hipMemcpyHostToDevice, st));
+            MGTA_HIP_CHECK(hipMemcpyAsync(d_jobs.p, jobs.data(), (size_t)nj * sizeof(CovJob), hipMemcpyHostToDevice, st));
+            MGTA_HIP_CHECK(hipMemsetAsync(d_cnt.p, 0, 8, st));            // the queue head
+            if (n_bytes)
+                hipLaunchKernelGGL(cov_symbols_kernel, dim3((unsigned)std::min<uint64_t>((n_bytes + 255) / 256, (uint64_t)ctx->num_cus * 16)), dim3(256), 0, st,
+                                   d_sym.as<uint8_t>(), n_bytes);
+            // a group takes `chunk` contigs per visit to the queue head (one word saturates near 88 dequeues per microsecond)
+            const uint64_t groups = (uint64_t)ctx->num_cus * (uint64_t)blocks_per_cu * (kCovThreads / 8);
+            const uint32_t chunk = nj >= groups * 64 ? 4u : 1u;
+            const unsigned blocks = (unsigned)std::min<uint64_t>((uint64_t)ctx->num_cus * (uint64_t)blocks_per_cu, ((uint64_t)nj + kCovThreads / 8 - 1) / (kCovThreads / 8));
+            MGTA_HIP_CHECK(hipEventRecord(ev[0], st));
+            if (g->dev.size > 0)
+                hipLaunchKernelGGL(cov_walk_kernel, dim3(blocks), dim3(kCovThreads), 0, st, g->dev, g->mult, d_sym.as<uint8_t>(), d_jobs.as<CovJob>(), nj, chunk, d_pw,
+                                   d_marks, d_abund.as<unsigned long long>(), d_cnt.as<unsigned long long>());
+            else
+                MGTA_HIP_CHECK(hipMemsetAsync(d_pw, 0, n_win * 2 + 64, st));
+            MGTA_HIP_CHECK(hipGetLastError());
+            MGTA_HIP_CHECK(hipEventRecord(ev[1], st));
+            hipLaunchKernelGGL(cov_stats_kernel, dim3((nj + 3) / 4), dim3(256), 0, st, d_jobs.as<CovJob>(), nj, (int)k, d_pw, d_out.as<mgta_contig_cov>());
+            MGTA_HIP_CHECK(hipGetLastError());
+            MGTA_HIP_CHECK(hipEventRecord(ev[2], st));
+            MGTA_HIP_CHECK(hipMemcpyAsync(per_contig + c0, d_out.p, (size_t)nj * sizeof(mgta_contig_cov), hipMemcpyDeviceToHost, st));
+            if (per_window && n_win) MGTA_HIP_CHECK(hipMemcpyAsync(per_window + win_done, d_pw, n_win * 2, hipMemcpyDeviceToHost, st));
+            MGTA_HIP_CHECK(hipStreamSynchronize(st));                     // (jobs and the device buffers serve the next batch)
+            ms_walk += elapsed_ms(ev[0], ev[1]);
+            ms_stats += elapsed_ms(ev[1], ev[2]);
+            win_done += n_win;
+            ++n_batches;
+            c0 = c1;
+        }
+        unsigned long long cnt[3] = {0, 0, 0};
+        MGTA_HIP_CHECK(hipMemcpyAsync(cnt, d_cnt.p, 24, hipMemcpyDeviceToHost, st));
+        if (abundance) MGTA_HIP_CHECK(hipMemcpyAsync(abundance, d_abund.p, 65536 * 8, hipMemcpyDeviceToHost, st));
+        MGTA_HIP_CHECK(hipStreamSynchronize(st));
+        if (stats) {
+            stats->n_contigs = n; stats->n_windows = (int64_t)win_done; stats->n_walked = (int64_t)cnt[1]; stats->n_index_searches = (int64_t)cnt[2];
+            stats->groups_per_cu = (int64_t)blocks_per_cu * (kCovThreads / 8);
+            stats->n_batches = n_batches; stats->ms_walk = ms_walk; stats->ms_kernel = ms_walk + ms_stats;
+        }
+        return MGTA_OK;
+    });
+    for (auto &e : ev) if (e) (void)hipEventDestroy(e);
+    return rc;
+}
+
+}  // extern "C"

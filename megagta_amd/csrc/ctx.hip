@@ -79,8 +79,20 @@ int mgta_ctx_keep_stream(mgta_ctx *ctx, int on) {
     if (!on) {
         // after a keep-stream build last_rec / last_tips point INTO the stream buffers: they go with them
         if (ctx->acc_valid) mgta::forget_last_build(ctx);
-        ctx->acc_rec.release(); ctx->acc_tips.release(); ctx->acc_valid = false;
+        ctx->acc_rec.release(); ctx->acc_tips.release(); ctx->acc_large.release(); ctx->acc_valid = false;
     }
+    return MGTA_OK;
+}
+
+int mgta_ctx_set_coverage_batch(mgta_ctx *ctx, uint64_t windows) {
+    if (!ctx) return MGTA_EINVAL;
+    ctx->coverage_batch_windows = windows;
+    return MGTA_OK;
+}
+
+int mgta_ctx_keep_multiplicity(mgta_ctx *ctx, int on) {
+    if (!ctx) return MGTA_EINVAL;
+    ctx->keep_multiplicity = on ? 1 : 0;
     return MGTA_OK;
 }
 

@@ -24,7 +24,7 @@ namespace mgta {
 // (the lines [line_lo, line_hi) from the records recs[0 ...) = records rec_base ...: a graph too large to hold its records AND its lines at once
 // is packed range by range, mgta_sdbg_load_files)
 __global__ __launch_bounds__(256) void graph_pack_kernel(const uint16_t *recs, int64_t rec_base, int64_t size, GLine *lines, uint64_t n_lines,
-                                                         uint64_t line_lo, uint64_t line_hi, uint32_t *cnt) {
+                                                         uint64_t line_lo, uint64_t line_hi, uint32_t *cnt, uint8_t *m8, uint32_t *cnt255) {
     // one wave per line, one lane per edge; the grid is capped (a dispatch holds < 2^32 work-items: 6.3 G edges do not fit one lane each)
     const int lane = lane_id();
     for (uint64_t li = line_lo + (uint64_t)blockIdx.x * 4 + wave_id(); li < line_hi; li += (uint64_t)gridDim.x * 4) {
@@ -36,6 +36,11 @@ __global__ __launch_bounds__(256) void graph_pack_kernel(const uint16_t *recs, i
     uint64_t b_tip = __ballot(in && ((it >> 5) & 1));
     uint64_t b_inv = __ballot(in && (((it >> 5) & 1) || w == 0));
     uint64_t b_m1 = __ballot(in && ((it >> 8) <= 1));
+    if (m8) {                                                             // keep_multiplicity: the stored count, and how many of the line say "see large"
+        const uint64_t b_255 = __ballot(in && (it >> 8) == 255u);
+        if (in) m8[e] = (uint8_t)(it >> 8);
+        if (lane == 0) cnt255[li] = (uint32_t)__popcll(b_255);
+    }
     uint64_t sym[4];
 #pragma unroll
     for (int a = 1; a <= 4; ++a) sym[a - 1] = __ballot(in && w == (uint32_t)a);
@@ -110,21 +115,30 @@ struct BucketSrc {
     uint64_t src;        // byte offset of the bucket inside `bytes` (even)
     uint64_t n_bytes;    // 2 items + 2 large + 4 words_per_tip tips
     int64_t items, rec_out, tip_out;   // records, index of its first record, index of its first tip
+    int64_t large_out, large_n;        // index of its first large multiplicity and their number (kept only under mgta_ctx_keep_multiplicity)
 };
 __global__ __launch_bounds__(64) void sdbg_decode_kernel(const uint16_t *bytes, const BucketSrc *buckets, uint32_t n, int words_per_tip, uint16_t *recs,
-                                                         uint32_t *tips, uint32_t *bad) {
+                                                         uint32_t *tips, uint16_t *large, uint32_t *bad) {
     const uint32_t i = blockIdx.x * 64 + threadIdx.x;
     if (i >= n) return;
     const BucketSrc b = buckets[i];
     const uint16_t *p = bytes + (b.src >> 1), *end = p + (b.n_bytes >> 1);
     uint16_t *out = recs + b.rec_out;
     uint32_t *tp = tips + b.tip_out * words_per_tip;
+    uint16_t *lg = large ? large + b.large_out : nullptr;
+    int64_t n_lg = 0;
     bool ok = true;
     for (int64_t r = 0; r < b.items; ++r) {
         if (p >= end) { ok = false; break; }
         const uint32_t it = *p++;
         out[r] = (uint16_t)it;
-        if ((it >> 8) == 255u) ++p;                                      // the full multiplicity: not part of the graph (need_multiplicity = false)
+        if ((it >> 8) == 255u) {                                         // the full multiplicity: kept only when the graph keeps counts (need_multiplicity)
+            if (lg) {
+                if (p >= end || n_lg >= b.large_n) { ok = false; break; }   // (never past the bucket's share of the table, whatever the file says)
+                lg[n_lg++] = *p;
+            }
+            ++p;
+        }
         if ((it >> 5) & 1u) {
             if (p + 2 * words_per_tip > end) { ok = false; break; }
             for (int w = 0; w < words_per_tip; ++w) { *tp++ = (uint32_t)p[0] | ((uint32_t)p[1] << 16); p += 2; }
@@ -170,15 +184,17 @@ extern "C" {
 // from records on the device, graph_finish() builds the rank / select tables.  (succinct_dbg.cpp:595-723, rank_and_select.h:80,430)
 struct GraphBuild {
     std::unique_ptr<mgta_sdbg> g;
-    DevBuf d_cnt;
+    DevBuf d_cnt, d_cnt255;
     uint64_t n_lines = 0;
     int64_t size = 0;
 };
 // tips: the labels (host or device memory, `tips_on_device`), or null = the caller fills g->tips itself before graph_finish()
 // adopt_lines: a device buffer that holds the RECORDS and is large enough for the lines: the lines are then packed IN PLACE (a GLine is exactly
 // as large as the 64 two-byte records it is made of, and a wavefront reads its 64 records before it stores its line)
+// n_large: large multiplicities the stream holds; under mgta_ctx_keep_multiplicity the graph gets room for them (the caller fills
+// g->large before graph_finish()), the per-edge bytes and the per-line counts of 255s
 static int graph_begin(mgta_ctx *ctx, int k, int64_t size, const int64_t *bucket_items, const uint32_t *tips, int64_t n_tip_words, int words_per_tip,
-                       bool tips_on_device, GraphBuild &B, DevBuf *adopt_lines = nullptr) {
+                       bool tips_on_device, GraphBuild &B, DevBuf *adopt_lines = nullptr, int64_t n_large = 0) {
     MGTA_HIP_CHECK(hipSetDevice(ctx->device));
     hipStream_t st = ctx->stream;
     B.g = std::make_unique<mgta_sdbg>();
@@ -203,6 +219,16 @@ static int graph_begin(mgta_ctx *ctx, int k, int64_t size, const int64_t *bucket
     if (n_tip_words && tips)
         MGTA_HIP_CHECK(hipMemcpyAsync(g->tips.p, tips, (size_t)n_tip_words * 4, tips_on_device ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice, st));
     if (size > 0) B.d_cnt.alloc(n_lines * 6 * 4, &ctx->live_bytes, &ctx->peak_bytes);
+    if (ctx->keep_multiplicity) {
+        g->has_mult = true; g->n_large = n_large;
+        g->m8.alloc(n_lines * 64 + 64, &ctx->live_bytes, &ctx->peak_bytes);
+        MGTA_HIP_CHECK(hipMemsetAsync(g->m8.p, 0, n_lines * 64 + 64, st));
+        g->large.alloc((size_t)n_large * 2 + 16, &ctx->live_bytes, &ctx->peak_bytes);
+        g->rank255.alloc((n_lines + 1) * 8, &ctx->live_bytes, &ctx->peak_bytes);
+        MGTA_HIP_CHECK(hipMemsetAsync(g->rank255.p, 0, (n_lines + 1) * 8, st));
+        if (size > 0) B.d_cnt255.alloc(n_lines * 4, &ctx->live_bytes, &ctx->peak_bytes);
+        g->mult = MultDev{g->m8.as<uint8_t>(), g->rank255.as<uint64_t>(), g->large.as<uint16_t>()};
+    }
     // the caller's buffer changes hands only once nothing in here can fail any more: an allocation that throws above leaves the stream where
     // it was, still valid (advisor r5)
     if (adopt_lines) g->lines = std::move(*adopt_lines);
@@ -214,7 +240,8 @@ static void graph_pack(GraphBuild &B, const uint16_t *dev_recs, int64_t rec_base
     if (line_hi <= line_lo) return;
     mgta_ctx *ctx = B.g->ctx;
     hipLaunchKernelGGL(graph_pack_kernel, dim3((unsigned)std::min<uint64_t>((line_hi - line_lo + 3) / 4, 1u << 22)), dim3(256), 0, ctx->stream, dev_recs, rec_base,
-                       B.size, B.g->lines.as<GLine>(), B.n_lines, line_lo, line_hi, B.d_cnt.as<uint32_t>());
+                       B.size, B.g->lines.as<GLine>(), B.n_lines, line_lo, line_hi, B.d_cnt.as<uint32_t>(),
+                       B.g->has_mult ? B.g->m8.as<uint8_t>() : nullptr, B.d_cnt255.as<uint32_t>());
     MGTA_HIP_CHECK(hipGetLastError());
 }
 static int graph_finish(GraphBuild &B, mgta_sdbg **out) {
@@ -251,8 +278,19 @@ static int graph_finish(GraphBuild &B, mgta_sdbg **out) {
         hipLaunchKernelGGL(graph_hint_kernel, dim3((unsigned)((n_lines + 255) / 256)), dim3(256), 0, st, d, g->lines.as<GLine>());
         MGTA_HIP_CHECK(hipGetLastError());
         MGTA_HIP_CHECK(hipStreamSynchronize(st));
+        if (g->has_mult) {                                               // rank of the 255s; their number must be the number of large words
+            uint64_t n255 = 0;
+            exclusive_scan_u32(st, B.d_cnt255.as<uint32_t>(), n_lines, g->rank255.as<uint64_t>(), d_tmp.as<uint64_t>(), d_tot.as<uint64_t>() + 6);
+            MGTA_HIP_CHECK(hipMemcpyAsync(&n255, d_tot.as<uint64_t>() + 6, 8, hipMemcpyDeviceToHost, st));
+            MGTA_HIP_CHECK(hipStreamSynchronize(st));
+            if ((int64_t)n255 != g->n_large) {
+                set_error("the stream holds %llu records with multiplicity 255 but %lld large multiplicities", (unsigned long long)n255, (long long)g->n_large);
+                return MGTA_EINVAL;
+            }
+        }
     }
-    B.d_cnt.release();
+    else if (g->has_mult && g->n_large != 0) { set_error("an empty stream with %lld large multiplicities", (long long)g->n_large); return MGTA_EINVAL; }
+    B.d_cnt.release(); B.d_cnt255.release();
     ctx_retain(ctx);
     *out = g.release();
     return MGTA_OK;
@@ -262,12 +300,15 @@ static int graph_finish(GraphBuild &B, mgta_sdbg **out) {
 // (`recs_owner`: a device buffer of the caller that holds `recs` and nothing else -- released as soon as the lines are packed, before
 // the rank tables are built: at 2 bytes per edge it is as large as the graph itself)
 static int load_graph(mgta_ctx *ctx, int k, const uint16_t *recs, int64_t size, const int64_t *bucket_items, const uint32_t *tips,
-                      int64_t n_tip_words, int words_per_tip, bool resident, mgta_sdbg **out, DevBuf *recs_owner = nullptr) {
+                      int64_t n_tip_words, int words_per_tip, bool resident, mgta_sdbg **out, DevBuf *recs_owner = nullptr,
+                      const uint16_t *large = nullptr, int64_t n_large = 0) {
     try {
         GraphBuild B;
-        const int rc = graph_begin(ctx, k, size, bucket_items, tips, n_tip_words, words_per_tip, resident, B);
+        const int rc = graph_begin(ctx, k, size, bucket_items, tips, n_tip_words, words_per_tip, resident, B, nullptr, n_large);
         if (rc != MGTA_OK) return rc;
         hipStream_t st = ctx->stream;
+        if (B.g->has_mult && n_large)                                    // (`large` lives where the records live)
+            MGTA_HIP_CHECK(hipMemcpyAsync(B.g->large.p, large, (size_t)n_large * 2, resident ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice, st));
         if (size > 0) {
             DevBuf d_recs;
             const uint16_t *dev_recs = recs;
@@ -290,7 +331,22 @@ static int load_graph(mgta_ctx *ctx, int k, const uint16_t *recs, int64_t size, 
 int mgta_sdbg_load(mgta_ctx *ctx, int k, const uint16_t *recs, int64_t size, const int64_t *bucket_items, const uint32_t *tips,
                    int64_t n_tip_words, int words_per_tip, mgta_sdbg **out) {
     if (!ctx || !out || size < 0 || (size > 0 && !recs) || !bucket_items) { set_error("mgta_sdbg_load: bad argument"); return MGTA_EINVAL; }
+    if (ctx->keep_multiplicity)      // this entry point is not given the large words: a stream that has any cannot keep its counts
+        for (int64_t i = 0; i < size; ++i)
+            if ((recs[i] >> 8) == 255) {
+                set_error("mgta_sdbg_load: the context keeps multiplicities and the stream has records of 255: pass their large words to mgta_sdbg_load_large");
+                return MGTA_EUNSUPPORTED;
+            }
     return load_graph(ctx, k, recs, size, bucket_items, tips, n_tip_words, words_per_tip, false, out);
+}
+
+int mgta_sdbg_load_large(mgta_ctx *ctx, int k, const uint16_t *recs, int64_t size, const int64_t *bucket_items, const uint32_t *tips,
+                         int64_t n_tip_words, int words_per_tip, const uint16_t *large, int64_t n_large, mgta_sdbg **out) {
+    if (!ctx || !out || size < 0 || (size > 0 && !recs) || !bucket_items || n_large < 0 || (n_large > 0 && !large)) {
+        set_error("mgta_sdbg_load_large: bad argument");
+        return MGTA_EINVAL;
+    }
+    return load_graph(ctx, k, recs, size, bucket_items, tips, n_tip_words, words_per_tip, false, out, nullptr, large, n_large);
 }
 
 // SuccinctDBG::LoadFromMultiFile (succinct_dbg.cpp:595-723) from the files themselves: the host reads the index, maps the record files
@@ -339,20 +395,20 @@ int mgta_sdbg_load_files(mgta_ctx *ctx, const char *prefix_c, mgta_sdbg **out) {
             }
         }
         // where every bucket's records and tips go, and the pieces to copy: the buckets of a file in offset order, cut every ~512 MB
-        std::vector<int64_t> items(MGTA_NUM_BUCKETS), rec_out(MGTA_NUM_BUCKETS), tip_out(MGTA_NUM_BUCKETS);
-        long long acc_r = 0, acc_t = 0;
+        std::vector<int64_t> items(MGTA_NUM_BUCKETS), rec_out(MGTA_NUM_BUCKETS), tip_out(MGTA_NUM_BUCKETS), large_out(MGTA_NUM_BUCKETS);
+        long long acc_r = 0, acc_t = 0, acc_l = 0;
         std::vector<std::vector<int>> of_file(nf);
         for (int b = 0; b < nb; ++b) {
             const bool has = bl[b].tid >= 0 && bl[b].items > 0;
             items[b] = has ? bl[b].items : 0;
-            rec_out[b] = acc_r; tip_out[b] = acc_t;
+            rec_out[b] = acc_r; tip_out[b] = acc_t; large_out[b] = acc_l;
             if (!has) continue;
             const unsigned long long nbytes = 2ull * bl[b].items + 2ull * bl[b].large + 4ull * wpt * bl[b].tips;
             if ((unsigned long long)bl[b].off + nbytes > files[bl[b].tid].size || bl[b].tips > bl[b].items || bl[b].large > bl[b].items) {
                 set_error("%s.sdbg_info: bucket %d does not fit %s.sdbg.%d", prefix.c_str(), b, prefix.c_str(), bl[b].tid);
                 return MGTA_EINVAL;
             }
-            acc_r += bl[b].items; acc_t += bl[b].tips;
+            acc_r += bl[b].items; acc_t += bl[b].tips; acc_l += bl[b].large;
             of_file[bl[b].tid].push_back(b);
         }
         if (acc_r != total || acc_t != ntips) { set_error("%s.sdbg_info: the bucket lines hold %lld records / %lld tips, the header says %lld / %lld",
@@ -366,7 +422,7 @@ int mgta_sdbg_load_files(mgta_ctx *ctx, const char *prefix_c, mgta_sdbg **out) {
         // with the second: its first records are carried over to the front of the buffer.
         GraphBuild B;
         {
-            const int rc = graph_begin(ctx, k, (int64_t)total, items.data(), nullptr, (int64_t)ntips * wpt, wpt, true, B);
+            const int rc = graph_begin(ctx, k, (int64_t)total, items.data(), nullptr, (int64_t)ntips * wpt, wpt, true, B, nullptr, (int64_t)acc_l);
             if (rc != MGTA_OK) return rc;
         }
         uint64_t range = 1ull << 32;
@@ -430,7 +486,7 @@ int mgta_sdbg_load_files(mgta_ctx *ctx, const char *prefix_c, mgta_sdbg **out) {
                         const unsigned long long nbytes = 2ull * L.items + 2ull * L.large + 4ull * wpt * L.tips;
                         if (j > i && (unsigned long long)L.off + nbytes - lo > kPiece) break;
                         hi = std::max(hi, (unsigned long long)L.off + nbytes);
-                        desc.push_back(BucketSrc{(uint64_t)L.off - lo, nbytes, L.items, rec_out[bs[j]] - rec_base, tip_out[bs[j]]});
+                        desc.push_back(BucketSrc{(uint64_t)L.off - lo, nbytes, L.items, rec_out[bs[j]] - rec_base, tip_out[bs[j]], large_out[bs[j]], L.large});
                     }
                     // (the piece buffers alternate: the kernel of one piece runs while the next is being staged; a buffer is re-used two
                     // pieces later, behind that kernel in stream order)
@@ -440,7 +496,8 @@ int mgta_sdbg_load_files(mgta_ctx *ctx, const char *prefix_c, mgta_sdbg **out) {
                     MGTA_HIP_CHECK(hipMemcpyAsync(d_desc[pc].p, desc.data(), desc.size() * sizeof(BucketSrc), hipMemcpyHostToDevice, st));
                     MGTA_HIP_CHECK(hipStreamSynchronize(st));                             // (desc is re-used by the host; pieces are hundreds of MB)
                     hipLaunchKernelGGL(sdbg_decode_kernel, dim3((unsigned)((desc.size() + 63) / 64)), dim3(64), 0, st, d_piece[pc].as<uint16_t>(),
-                                       d_desc[pc].as<BucketSrc>(), (uint32_t)desc.size(), wpt, d_range.as<uint16_t>(), B.g->tips.as<uint32_t>(), d_bad.as<uint32_t>());
+                                       d_desc[pc].as<BucketSrc>(), (uint32_t)desc.size(), wpt, d_range.as<uint16_t>(), B.g->tips.as<uint32_t>(),
+                                       B.g->has_mult ? B.g->large.as<uint16_t>() : nullptr, d_bad.as<uint32_t>());
                     MGTA_HIP_CHECK(hipGetLastError());
                     pc ^= 1;
                     i = j;
@@ -500,6 +557,7 @@ int mgta_sdbg_stream_detach(mgta_ctx *ctx, mgta_stream **out) {
         st->ctx = ctx; st->device = ctx->device; st->k = ctx->last_k; st->words_per_tip = ctx->last_words_per_tip;
         st->n_rec = ctx->acc_n_rec; st->n_tip_words = ctx->acc_n_tips * (uint64_t)ctx->last_words_per_tip;
         st->rec = std::move(ctx->acc_rec); st->tips = std::move(ctx->acc_tips);
+        ctx->acc_large.release();
         ctx->acc_valid = false;
         forget_last_build(ctx);
         ctx_retain(ctx);
@@ -564,6 +622,13 @@ int mgta_sdbg_load_resident(mgta_ctx *ctx, mgta_sdbg **out) {
                   "(none yet, a bucket sub-range, or several memory-bound passes)");
         return MGTA_EINVAL;
     }
+    const uint16_t *d_large = static_cast<const uint16_t *>(ctx->last_large);
+    const int64_t n_large = ctx->keep_multiplicity ? (int64_t)ctx->last_n_large : 0;
+    if (ctx->keep_multiplicity && ctx->acc_valid && !ctx->acc_has_large) {
+        set_error("mgta_sdbg_load_resident: the kept stream was built while mgta_ctx_keep_multiplicity was off: its large multiplicities are gone "
+                  "(set the switch before the build, or load the graph from its files)");
+        return MGTA_EUNSUPPORTED;
+    }
     try {
         MGTA_HIP_CHECK(hipSetDevice(ctx->device));
         if (ctx->acc_valid) {    // the build's key buffers (grow-only pool) are scratch; a graph of tens of billions of edges needs their room
@@ -586,12 +651,13 @@ int mgta_sdbg_load_resident(mgta_ctx *ctx, mgta_sdbg **out) {
             if (want && size > 0 && ctx->acc_rec.p == ctx->last_rec && ctx->acc_rec.bytes >= (n_lines + 1) * sizeof(GLine)) {
                 GraphBuild B;
                 const int rc = graph_begin(ctx, ctx->last_k, size, ctx->acc_items.data(), static_cast<const uint32_t *>(ctx->last_tips),
-                                           (int64_t)ctx->last_n_tips * ctx->last_words_per_tip, ctx->last_words_per_tip, true, B, &ctx->acc_rec);
+                                           (int64_t)ctx->last_n_tips * ctx->last_words_per_tip, ctx->last_words_per_tip, true, B, &ctx->acc_rec, n_large);
                 if (rc != MGTA_OK) return rc;
+                if (B.g->has_mult && n_large) MGTA_HIP_CHECK(hipMemcpyAsync(B.g->large.p, d_large, (size_t)n_large * 2, hipMemcpyDeviceToDevice, ctx->stream));
                 // from here on the stream's buffer belongs to the graph under construction: whatever happens below, the context must not
                 // go on naming it (a failure frees it with B; a retry or an export would read freed memory)
                 auto forget_stream = [&]() {
-                    ctx->acc_tips.release(); ctx->acc_valid = false;
+                    ctx->acc_tips.release(); ctx->acc_large.release(); ctx->acc_valid = false;
                     forget_last_build(ctx);
                 };
                 try {
@@ -606,7 +672,7 @@ int mgta_sdbg_load_resident(mgta_ctx *ctx, mgta_sdbg **out) {
         if (ctx->acc_valid)      // a multi-pass build that kept its whole stream (mgta_ctx_keep_stream): records per bucket are on the host
             return load_graph(ctx, ctx->last_k, static_cast<const uint16_t *>(ctx->last_rec), (int64_t)ctx->last_n_rec, ctx->acc_items.data(),
                               static_cast<const uint32_t *>(ctx->last_tips), (int64_t)ctx->last_n_tips * ctx->last_words_per_tip,
-                              ctx->last_words_per_tip, true, out);
+                              ctx->last_words_per_tip, true, out, nullptr, d_large, n_large);
         // records before every bucket (-1 = empty bucket) -> records per bucket
         std::vector<int64_t> first((size_t)MGTA_NUM_BUCKETS * 3), items(MGTA_NUM_BUCKETS);
         if (ctx->last_n_rec) {
@@ -624,7 +690,7 @@ int mgta_sdbg_load_resident(mgta_ctx *ctx, mgta_sdbg **out) {
         }
         return load_graph(ctx, ctx->last_k, static_cast<const uint16_t *>(ctx->last_rec), (int64_t)ctx->last_n_rec, items.data(),
                           static_cast<const uint32_t *>(ctx->last_tips), (int64_t)ctx->last_n_tips * ctx->last_words_per_tip,
-                          ctx->last_words_per_tip, true, out);
+                          ctx->last_words_per_tip, true, out, nullptr, d_large, n_large);
     } catch (const HipError &e) { return e.code; }
 }
 

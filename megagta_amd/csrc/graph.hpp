@@ -563,10 +563,38 @@ __device__ inline int64_t g_index_edge(const GraphDev &g, const uint8_t *seq) {
     return -1;
 }
 
+// ---- edge multiplicities (mgta_ctx_keep_multiplicity; SuccinctDBG::EdgeMultiplicity, succinct_dbg.h:133-147) ------------------------
+// Not part of GraphDev: the search kernels never see them, and a graph loaded without the switch is what it always was.
+struct MultDev {
+    const uint8_t *m8;         // min(mult, 255) per edge (edge_multi_)
+    const uint64_t *rank255;   // per line of 64 edges: edges stored as 255 before it
+    const uint16_t *large;     // the full counts of the edges stored as 255, in edge order (the stream's `large` words)
+};
+// bytes of `x` equal to 0xFF -> bit 7 of each such byte
+__device__ __forceinline__ uint64_t bytes_ff(uint64_t x) {
+    return (((x & 0x7F7F7F7F7F7F7F7Full) + 0x0101010101010101ull) & x) & 0x8080808080808080ull;
+}
+__device__ __forceinline__ uint32_t g_edge_mult(const MultDev &m, int64_t e) {
+    const uint32_t v = m.m8[e];
+    if (v != 255u) return v;
+    // rank of e among the 255s: those before its line + those before it inside the line (8 aligned words of 8 edges)
+    const uint64_t *w = reinterpret_cast<const uint64_t *>(m.m8 + (e & ~63ll));
+    const int j = (int)(e & 63);
+    uint64_t idx = m.rank255[e >> 6];
+    for (int q = 0; q < (j >> 3); ++q) idx += (uint64_t)__popcll(bytes_ff(w[q]));
+    if (j & 7) idx += (uint64_t)__popcll(bytes_ff(w[j >> 3]) & ((1ull << (8 * (j & 7))) - 1ull));
+    return m.large[idx];
+}
+
 }  // namespace mgta
 
 struct mgta_sdbg {
     mgta_ctx *ctx = nullptr;
     mgta::GraphDev dev;                       // host copy of the descriptor (pointers are device pointers)
     mgta::DevBuf lines, sel_last, sel_w[5], tips;
+    bool has_mult = false;                    // loaded under mgta_ctx_keep_multiplicity
+    mgta::MultDev mult{nullptr, nullptr, nullptr};
+    int64_t n_large = 0;
+    mgta::DevBuf m8, rank255, large;
+    mgta::DevBuf marks;                       // mgta_contig_coverage: one bit per edge, allocated by the first call that counts abundance
 };

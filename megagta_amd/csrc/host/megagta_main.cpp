@@ -57,6 +57,8 @@ struct Session {
     mgta_ctx *ctx2 = nullptr;     // second context of the device: the other lane of a two-gene search
     mgta_sdbg *graph = nullptr;   // graph of the last buildgraph, not used yet
     std::string graph_prefix;
+    mgta_sdbg *cov_graph = nullptr;   // graph loaded WITH its multiplicities by the last `coverage`: serves the coverage of the next gene
+    std::string cov_key;          // the graph files it came from (index path | size | mtime)
     std::thread writer;           // PREFIX.sdbg.* of the last buildgraph being written while the next step already runs on the resident graph
     std::string writer_error;     // why that thread failed (set by the thread, read after the join)
     mgta_stream *stream = nullptr;   // the edge stream that thread downloads from the device (freed on this thread once it has joined)
@@ -166,6 +168,7 @@ static PackedReads &lib_get(const std::string &bin_path, const std::string &lib_
 }
 static void graph_drop() {
     if (g_sess.graph) { mgta_sdbg_free(g_sess.graph); g_sess.graph = nullptr; g_sess.graph_prefix.clear(); }
+    if (g_sess.cov_graph) { mgta_sdbg_free(g_sess.cov_graph); g_sess.cov_graph = nullptr; g_sess.cov_key.clear(); }
 }
 // the graph PREFIX names: the one the last buildgraph of this process left on the device, else read from the files
 static mgta_sdbg *graph_get(mgta_ctx *ctx, const std::string &prefix, int *k_out, size_t *n_edges) {
@@ -779,6 +782,90 @@ static int main_denovo(int argc, char **argv) {
     return 0;
 }
 
+// ---- coverage: per-contig k-mer coverage and abundance from the graph's own multiplicities (the reference's last post-processing step,
+// `kmer_coverage` in bin/post_proc.sh:113-118, recounts them from the reads).  The file formats are this project's own: INTEGRATION.md.
+static int main_coverage(int argc, char **argv) {
+    if (argc != 4) { fprintf(stderr, "Usage: megagta coverage <sdbg_prefix> <contigs.fasta> <out_prefix>\n"); return 1; }
+    RssLine rss;
+    const std::string prefix = argv[1], fasta = argv[2], out_prefix = argv[3];
+    // the records of the FASTA in file order: name = the header up to the first blank, sequence = its lines joined
+    std::vector<std::string> names;
+    std::string seqs;
+    std::vector<uint64_t> offsets{0};
+    {
+        FILE *f = fopen(fasta.c_str(), "r");
+        if (!f) die("cannot open %s", fasta.c_str());
+        char *line = nullptr;
+        size_t cap = 0;
+        ssize_t n;
+        bool open_rec = false;
+        while ((n = getline(&line, &cap, f)) >= 0) {
+            while (n > 0 && (line[n - 1] == '\n' || line[n - 1] == '\r' || line[n - 1] == ' ' || line[n - 1] == '\t')) line[--n] = 0;
+            if (n > 0 && line[0] == '>') {
+                if (open_rec) offsets.push_back(seqs.size());
+                size_t e = 1;
+                while (e < (size_t)n && line[e] != ' ' && line[e] != '\t') ++e;
+                names.emplace_back(line + 1, e - 1);
+                open_rec = true;
+            } else if (open_rec) {
+                const char *b = line;
+                while (*b == ' ' || *b == '\t') ++b;
+                seqs.append(b);
+            }
+        }
+        if (open_rec) offsets.push_back(seqs.size());
+        free(line);
+        fclose(f);
+    }
+    const int64_t n = (int64_t)names.size();
+    double t0 = now_s();
+    mgta_ctx *ctx = ctx_get();
+    // The graph with its counts.  A worker keeps the one the coverage of the gene before loaded (the same files: one load for all
+    // genes of a run).  The graph a worker's buildgraph hands over has no counts (1 byte per edge more is never implied) and the search
+    // that ran since has used it up, so the first request loads the files -- which are complete first -- with the switch on.
+    if (writer_join() != 0) die("the graph files of %s are incomplete", prefix.c_str());
+    const std::string key = file_key(prefix + ".sdbg_info");
+    mgta_sdbg *g = nullptr;
+    if (g_sess.active && g_sess.cov_graph && g_sess.cov_key == key) {
+        g = g_sess.cov_graph;
+        logf("graph %s with multiplicities: still on the device", prefix.c_str());
+    } else {
+        graph_drop();
+        mgta_ctx_keep_multiplicity(ctx, 1);
+        const int lrc = mgta_sdbg_load_files(ctx, prefix.c_str(), &g);
+        mgta_ctx_keep_multiplicity(ctx, 0);
+        if (lrc != MGTA_OK) die("mgta_sdbg_load_files: %s", mgta_last_error());
+        if (g_sess.active) { g_sess.cov_graph = g; g_sess.cov_key = key; }
+    }
+    logf("Number of Edges: %lld; K value: %d (load with multiplicities %.3f s)", (long long)mgta_sdbg_size(g), mgta_sdbg_k(g), now_s() - t0);
+    std::vector<mgta_contig_cov> cov((size_t)n);
+    std::vector<int64_t> abund(65536);
+    mgta_coverage_stats st;
+    t0 = now_s();
+    // all records in ONE call: the abundance counts an edge once for the file
+    if (mgta_contig_coverage(g, seqs.data(), offsets.data(), n, cov.data(), nullptr, abund.data(), &st) != MGTA_OK) die("mgta_contig_coverage: %s", mgta_last_error());
+    logf("coverage of %lld contigs: %lld windows, %lld by the walk, %lld index searches, %lld batch%s; kernels %.1f ms (walk %.1f ms), wall %.3f s", (long long)n,
+         (long long)st.n_windows, (long long)st.n_walked, (long long)st.n_index_searches, (long long)st.n_batches, st.n_batches == 1 ? "" : "es", st.ms_kernel,
+         st.ms_walk, now_s() - t0);
+    FILE *cf = fopen((out_prefix + "_coverage.txt").c_str(), "w");
+    if (!cf) die("cannot write %s_coverage.txt", out_prefix.c_str());
+    fprintf(cf, "#contig\tlen\twindows\tcovered\tmean\tmedian\tmin\tmax\n");
+    for (int64_t i = 0; i < n; ++i) {
+        const mgta_contig_cov &c = cov[(size_t)i];
+        fprintf(cf, "%s\t%u\t%u\t%u\t%.4f\t%u\t%u\t%u\n", names[(size_t)i].c_str(), c.len, c.n_windows, c.n_covered,
+                c.n_windows ? (double)c.sum / (double)c.n_windows : 0.0, c.median, c.min, c.max);
+    }
+    if (fclose(cf) != 0) die("short write to %s_coverage.txt", out_prefix.c_str());
+    FILE *af = fopen((out_prefix + "_abundance.txt").c_str(), "w");
+    if (!af) die("cannot write %s_abundance.txt", out_prefix.c_str());
+    for (int m = 0; m < 65536; ++m)
+        if (abund[(size_t)m]) fprintf(af, "%d\t%lld\n", m, (long long)abund[(size_t)m]);
+    if (fclose(af) != 0) die("short write to %s_abundance.txt", out_prefix.c_str());
+    if (!g_sess.active) mgta_sdbg_free(g);
+    ctx_put(ctx);
+    return 0;
+}
+
 static int dispatch(int argc, char **argv);
 
 // megagta serve: requests on stdin, one per line: the sub-command's argv, tab separated; a field "<PATH" / ">PATH" redirects the
@@ -866,7 +953,7 @@ int main(int argc, char **argv) {
 static int dispatch(int argc, char **argv) {
     if (argc < 2) {
         fprintf(stderr, "Usage: %s <sub_program> [sub options]\n    sub-programs on the MI355X hot path:\n        buildgraph    build succinct de Bruijn graph\n"
-                        "        denovo        tips, bubbles, contigs of an intermediate k\n        search        HMM-guided search of gene contigs\n        findstart     find starting kmers of the search\n        dumpversion   dump version\n", argv[0]);
+                        "        denovo        tips, bubbles, contigs of an intermediate k\n        search        HMM-guided search of gene contigs\n        findstart     find starting kmers of the search\n        coverage      per-contig k-mer coverage and abundance from the graph\n        dumpversion   dump version\n", argv[0]);
         return 1;
     }
     std::string sub = argv[1];
@@ -874,6 +961,7 @@ static int dispatch(int argc, char **argv) {
     if (sub == "search") return main_search(argc - 1, argv + 1);
     if (sub == "findstart") return main_findstart(argc - 1, argv + 1);
     if (sub == "denovo") return main_denovo(argc - 1, argv + 1);
+    if (sub == "coverage") return main_coverage(argc - 1, argv + 1);
     if (sub == "filterbylen") return main_filterbylen(argc - 1, argv + 1);
     if (sub == "translate") return main_translate(argc - 1, argv + 1);
     if (sub == "buildlib") {                                             // build_read_lib.cpp:8-20 (host only: file formats, no kernel)
@@ -976,6 +1064,6 @@ static int dispatch(int argc, char **argv) {
         return 0;
     }
     if (sub == "dumpversion") { printf("%s\n", mgta_version()); return 0; }
-    fprintf(stderr, "sub-command '%s' is not built here (buildlib, buildgraph, denovo, findstart, search, filterbylen, translate are): run it with the reference's megagta binary\n", sub.c_str());
+    fprintf(stderr, "sub-command '%s' is not built here (buildlib, buildgraph, denovo, findstart, search, coverage, filterbylen, translate are): run it with the reference's megagta binary\n", sub.c_str());
     return 1;
 }

@@ -2177,13 +2177,14 @@ struct Build {                                 // a build of keys of W words: wh
                 if (!sorted) return MGTA_EUNSUPPORTED;
                 if ((rc = drop_sentinels(p)) != MGTA_OK || (rc = emit(p, sorted, sorted == a ? b : a)) != MGTA_OK) return rc;
             }
-            publish_last(p.b_lo, p.b_hi, p.rec, p.n_edges, p.tips, p.n_tips, p.first);   // (an empty range names no records)
+            publish_last(p.b_lo, p.b_hi, p.rec, p.n_edges, p.tips, p.n_tips, p.first, p.large, p.n_large);   // (an empty range names no records)
             if (acc && p.n_items > 0) append_to_stream(p);
             S.n_edges += (int64_t)p.n_edges; S.n_large += (int64_t)p.n_large; S.n_tips += (int64_t)p.n_tips;
             if ((rc = deliver_pass(p)) != MGTA_OK) return rc;
             b_lo = p.b_hi;
         }
-        if (acc) publish_last(bucket_begin, bucket_end, ctx->acc_rec.p, ctx->acc_n_rec, ctx->acc_tips.p, ctx->acc_n_tips, nullptr);
+        if (acc) publish_last(bucket_begin, bucket_end, ctx->acc_rec.p, ctx->acc_n_rec, ctx->acc_tips.p, ctx->acc_n_tips, nullptr,
+                              ctx->acc_has_large ? ctx->acc_large.p : nullptr, ctx->acc_n_large);
         ctx->acc_valid = acc;
         S.ms_total = t_all.stop();
         for (const Timer &t : log.scatter) S.ms_sort_scatter += t.ms();
@@ -2206,6 +2207,7 @@ struct Build {                                 // a build of keys of W words: wh
         budget = ctx->mem_limit ? std::min<uint64_t>(ctx->mem_limit, avail) : (uint64_t)(avail * 0.9);
         acc = ctx->keep_stream != 0;           // (of a bucket sub-range too: the shard a rank hands to the all-gather)
         ctx->acc_valid = false; ctx->acc_n_rec = 0; ctx->acc_n_tips = 0;
+        ctx->acc_n_large = 0; ctx->acc_has_large = acc && ctx->keep_multiplicity;   // (the large words stay with a kept stream only on request)
         if (acc) ctx->acc_items.assign(MGTA_NUM_BUCKETS, 0);
         point_scans_at_pool();
         uint64_t *d_small = pool_get<uint64_t>(ctx, S_SMALL, 4096);   // [0] total, [1] kmers, [2..4] emit totals, [5] sentinels, [8..263] digit totals
@@ -2411,7 +2413,9 @@ struct Build {                                 // a build of keys of W words: wh
     }
 
     // what mgta_sdbg_load_resident / mgta_sdbg_export_records_device find of the build on the context
-    void publish_last(uint32_t lo, uint32_t hi, const void *rec, uint64_t n_rec, const void *tips, uint64_t n_tips, const void *first) {
+    void publish_last(uint32_t lo, uint32_t hi, const void *rec, uint64_t n_rec, const void *tips, uint64_t n_tips, const void *first,
+                      const void *large, uint64_t n_large) {
+        ctx->last_large = large; ctx->last_n_large = n_large;
         ctx->last_rec = rec; ctx->last_n_rec = n_rec; ctx->last_bucket_lo = lo; ctx->last_bucket_hi = hi;
         ctx->last_tips = tips; ctx->last_n_tips = n_tips; ctx->last_first = first; ctx->last_k = k; ctx->last_words_per_tip = words_per_tip;
     }
@@ -2432,6 +2436,10 @@ struct Build {                                 // a build of keys of W words: wh
         };
         ensure(ctx->acc_rec, ctx->acc_n_rec * 2, p.n_edges * 2);
         ensure(ctx->acc_tips, ctx->acc_n_tips * tip_b, p.n_tips * tip_b);
+        if (ctx->acc_has_large) {
+            ensure(ctx->acc_large, ctx->acc_n_large * 2, p.n_large * 2);
+            if (p.n_large) MGTA_HIP_CHECK(hipMemcpyAsync(ctx->acc_large.as<char>() + ctx->acc_n_large * 2, p.large, p.n_large * 2, hipMemcpyDeviceToDevice, stream));
+        }
         if (p.n_edges) MGTA_HIP_CHECK(hipMemcpyAsync(ctx->acc_rec.as<char>() + ctx->acc_n_rec * 2, p.rec, p.n_edges * 2, hipMemcpyDeviceToDevice, stream));
         if (p.n_tips) MGTA_HIP_CHECK(hipMemcpyAsync(ctx->acc_tips.as<char>() + ctx->acc_n_tips * tip_b, p.tips, p.n_tips * tip_b, hipMemcpyDeviceToDevice, stream));
         h_first.resize((size_t)p.nb() * 3);
@@ -2444,7 +2452,7 @@ struct Build {                                 // a build of keys of W words: wh
             ctx->acc_items[(size_t)p.b_lo + (size_t)b] = nxt - f;
             nxt = f;
         }
-        ctx->acc_n_rec += p.n_edges; ctx->acc_n_tips += p.n_tips;
+        ctx->acc_n_rec += p.n_edges; ctx->acc_n_tips += p.n_tips; ctx->acc_n_large += p.n_large;
     }
 
     // ---- device -> host and the sink.  keep_stream 2: records and tip labels stay on the device only (the caller takes the whole

@@ -36,7 +36,9 @@ USAGE = """Usage:
                      all-gather of contigs (megagta_amd/search_dist.py).  `buildgraph`: one process per GPU, each builds its share of the
                      65536 prefix buckets and writes it as <prefix>.sdbg.<rank> (no exchange at all).  denovo / findstart run on GPU 0
     --one-process-per-step   start every step as its own process, as the reference driver does (default: one worker process,
-                     `megagta serve`, runs all steps and keeps the device context, the read library and the last graph between them)"""
+                     `megagta serve`, runs all steps and keeps the device context, the read library and the last graph between them)
+    --coverage       after the last k: per gene contigs/<gene>/nucl_merged_coverage.txt and nucl_merged_abundance.txt, the k-mer coverage
+                     of every contig and the abundance histogram of the edges they touch, from the graph's own multiplicities (GPU 0)"""
 
 
 class Usage(Exception):
@@ -67,6 +69,7 @@ class Opt:
         self.bin = os.path.join(os.path.dirname(os.path.abspath(__file__)), "bin", "megagta")
         self.one_process_per_step = False
         self.gpus = 1
+        self.coverage = False
 
 
 opt = Opt()
@@ -74,7 +77,7 @@ cp = 0
 
 LONG = ["help", "read=", "12=", "out-dir=", "memory=", "gpu-mem=", "min-contig-len=", "num-cpu-threads=", "kmin-1pass", "k-list=",
         "min-count=", "max-tip-len=", "no-mercy", "keep-tmp-files", "mem-flag=", "version", "verbose", "continue", "gene-list=",
-        "prune-len=", "low-cov-penalty=", "bin=", "one-process-per-step", "gpus="]
+        "prune-len=", "low-cov-penalty=", "bin=", "one-process-per-step", "gpus=", "coverage"]
 
 
 def parse_opt(argv):
@@ -120,6 +123,7 @@ def parse_opt(argv):
         elif o == "--bin": opt.bin = v
         elif o == "--one-process-per-step": opt.one_process_per_step = True
         elif o == "--gpus": opt.gpus = int(v)
+        elif o == "--coverage": opt.coverage = True
         else:
             raise Usage("Invalid option " + o)
     opt.temp_dir = opt.out_dir + "tmp/"
@@ -548,6 +552,18 @@ def search_contigs(k):
     write_cp()
 
 
+def contig_coverage(k):
+    """--coverage: per gene contigs/<gene>/nucl_merged_coverage.txt and _abundance.txt from the multiplicities of the last k's graph
+    (`megagta coverage`: the graph files are loaded with their counts on GPU 0; one call per gene, so a gene's abundance counts an edge
+    once).  Its checkpoints come after every checkpoint of a run without the flag, so `--continue` works under both."""
+    for gene in opt.gene_info:
+        d = opt.out_dir + "contigs/" + gene
+        if should_run():
+            run_step([opt.bin, "coverage", graph_prefix(k), d + "/nucl_merged.fasta", d + "/nucl_merged"],
+                     "Computing k-mer coverage of the contigs of %s" % gene)
+        write_cp()
+
+
 def main(argv=None):
     argv = sys.argv if argv is None else argv
     try:
@@ -586,6 +602,8 @@ def main(argv=None):
                         worker.close()
                     return 0
                 search_contigs(k)
+                if opt.coverage:
+                    contig_coverage(k)
         flush_deferred_cp()
         if worker is not None:
             worker.close()
