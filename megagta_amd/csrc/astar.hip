@@ -75,7 +75,7 @@ int mgta_hmm_load(mgta_ctx *ctx, int M, int A, const double *msc, const double *
         set_error("mgta_hmm_load: bad argument");
         return MGTA_EINVAL;
     }
-    try {
+    return guarded("mgta_hmm_load", [&]() -> int {
         MGTA_HIP_CHECK(hipSetDevice(ctx->device));
         auto hm = std::make_unique<mgta_hmm>();
         hm->ctx = ctx; hm->M = M; hm->A = A;
@@ -104,7 +104,7 @@ int mgta_hmm_load(mgta_ctx *ctx, int M, int A, const double *msc, const double *
         ctx_retain(ctx);
         *out = hm.release();
         return MGTA_OK;
-    } catch (const HipError &e) { return e.code; }
+    });
 }
 
 void mgta_hmm_free(mgta_hmm *h) {
@@ -673,56 +673,54 @@ int astar_batch_impl(mgta_ctx *ctx, mgta_sdbg *g, const mgta_hmm *fwd, const mgt
     if (ctx->device != g->ctx->device) { set_error("mgta_astar_batch_on: the context and the graph live on different devices"); return MGTA_EINVAL; }
     const int klen = g->dev.k + 1;
     if (klen > kMaxKmer) { set_error("k too large"); return MGTA_EINVAL; }
-    try {
-        MGTA_HIP_CHECK(hipSetDevice(ctx->device));
-        mgta_astar_stats ST{};
-        ST.n_seeds = n;
-        Batch b{ctx, g, ctx->stream, {fwd, rev}, kmers, start_state, n, klen, cache_mode, free_share, cache_mode > 0 && !free_share};
-        if (n == 0) {                                                          // (nothing runs; a packed call still gets its empty buffer)
-            const int rc = deliver(b, Results{}, packed, sink, user);
-            if (rc == MGTA_OK && stats) *stats = ST;
-            return rc;
-        }
-        Events ev;
-        MGTA_HIP_CHECK(hipEventRecord(ev.e[0], b.st));
-        std::vector<int64_t> start_node;
-        int rc = encode_start_edges(g, kmers, n, klen, start_node);
-        if (rc != MGTA_OK) return rc;
-        b.G = lanes_per_search(b); b.spb = (int64_t)kAstarWaves * (64 / b.G);
-        upload_batch(b, start_node, prune_len, low_cov_penalty, ST);
-        for (int d = 0; d < 2; ++d) { b.todo[d].resize(n); for (int64_t s = 0; s < n; ++s) b.todo[d][s] = s; }
-        longest_first(b);
-        b.h_status.resize((size_t)n * 2); b.over_limit_seen.resize((size_t)n * 2);
-        size_t free_b = 0, total_b = 0;
-        MGTA_HIP_CHECK(hipMemGetInfo(&free_b, &total_b));
-        if (cache_mode > 0) alloc_caches(b, free_b);
-        for (int attempt = 0; attempt < 4 && (!b.todo[0].empty() || !b.todo[1].empty()); ++attempt) {
-            const PassPlan p = plan_pass(b, attempt, b.todo, free_b, ctx->astar.pool);
-            upload_pool(b, p);
-            const PassOut o = run_pass(b, p, ST.order_abandoned != 0, ev);
-            rc = account_pass(b, attempt, p, o, ST);
-            if (rc != MGTA_OK) return rc;
-            MGTA_HIP_CHECK(hipMemGetInfo(&free_b, &total_b));
-        }
-        if (!b.todo[0].empty() || !b.todo[1].empty()) {
-            set_error("%zu searches do not fit the device memory left for them (pool of %llu bytes)", b.todo[0].size() + b.todo[1].size(),
-                      (unsigned long long)ST.pool_bytes);
-            return MGTA_EOVERFLOW;
-        }
-        for (int64_t s = 0; s < n * 2; ++s)
-            if (b.h_status[(size_t)s] == kSearchGateTimeout || b.h_status[(size_t)s] == kSearchPending) {
-                set_error("search %lld did not run (ordered-commit gate timed out)", (long long)s);
-                return MGTA_EHIP;
-            }
-#ifdef MGTA_ASTAR_PROFILE
-        profile_report(b);
-#endif
-        Results r;
-        rc = collect_results(b, ev, r, ST);
-        if (rc == MGTA_OK) rc = deliver(b, r, packed, sink, user);
+    MGTA_HIP_CHECK(hipSetDevice(ctx->device));                                 // (throws from here on: both entry points below call this under guarded())
+    mgta_astar_stats ST{};
+    ST.n_seeds = n;
+    Batch b{ctx, g, ctx->stream, {fwd, rev}, kmers, start_state, n, klen, cache_mode, free_share, cache_mode > 0 && !free_share};
+    if (n == 0) {                                                          // (nothing runs; a packed call still gets its empty buffer)
+        const int rc = deliver(b, Results{}, packed, sink, user);
         if (rc == MGTA_OK && stats) *stats = ST;
         return rc;
-    } catch (const HipError &e) { return e.code; }
+    }
+    Events ev;
+    MGTA_HIP_CHECK(hipEventRecord(ev.e[0], b.st));
+    std::vector<int64_t> start_node;
+    int rc = encode_start_edges(g, kmers, n, klen, start_node);
+    if (rc != MGTA_OK) return rc;
+    b.G = lanes_per_search(b); b.spb = (int64_t)kAstarWaves * (64 / b.G);
+    upload_batch(b, start_node, prune_len, low_cov_penalty, ST);
+    for (int d = 0; d < 2; ++d) { b.todo[d].resize(n); for (int64_t s = 0; s < n; ++s) b.todo[d][s] = s; }
+    longest_first(b);
+    b.h_status.resize((size_t)n * 2); b.over_limit_seen.resize((size_t)n * 2);
+    size_t free_b = 0, total_b = 0;
+    MGTA_HIP_CHECK(hipMemGetInfo(&free_b, &total_b));
+    if (cache_mode > 0) alloc_caches(b, free_b);
+    for (int attempt = 0; attempt < 4 && (!b.todo[0].empty() || !b.todo[1].empty()); ++attempt) {
+        const PassPlan p = plan_pass(b, attempt, b.todo, free_b, ctx->astar.pool);
+        upload_pool(b, p);
+        const PassOut o = run_pass(b, p, ST.order_abandoned != 0, ev);
+        rc = account_pass(b, attempt, p, o, ST);
+        if (rc != MGTA_OK) return rc;
+        MGTA_HIP_CHECK(hipMemGetInfo(&free_b, &total_b));
+    }
+    if (!b.todo[0].empty() || !b.todo[1].empty()) {
+        set_error("%zu searches do not fit the device memory left for them (pool of %llu bytes)", b.todo[0].size() + b.todo[1].size(),
+                  (unsigned long long)ST.pool_bytes);
+        return MGTA_EOVERFLOW;
+    }
+    for (int64_t s = 0; s < n * 2; ++s)
+        if (b.h_status[(size_t)s] == kSearchGateTimeout || b.h_status[(size_t)s] == kSearchPending) {
+            set_error("search %lld did not run (ordered-commit gate timed out)", (long long)s);
+            return MGTA_EHIP;
+        }
+#ifdef MGTA_ASTAR_PROFILE
+    profile_report(b);
+#endif
+    Results r;
+    rc = collect_results(b, ev, r, ST);
+    if (rc == MGTA_OK) rc = deliver(b, r, packed, sink, user);
+    if (rc == MGTA_OK && stats) *stats = ST;
+    return rc;
 }
 }  // namespace
 

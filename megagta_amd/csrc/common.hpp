@@ -66,6 +66,24 @@ template <class F> int guarded(const char *who, F &&f) {
     catch (const std::exception &e) { set_error("%s: %s", who, e.what()); return MGTA_EHIP; }
 }
 
+struct Timer {                   // owns its two events
+    hipEvent_t a = nullptr, b = nullptr;
+    hipStream_t st;
+    explicit Timer(hipStream_t s) : st(s) { MGTA_HIP_CHECK(hipEventCreate(&a)); MGTA_HIP_CHECK(hipEventCreate(&b)); }
+    Timer(Timer &&o) noexcept : a(o.a), b(o.b), st(o.st) { o.a = o.b = nullptr; }
+    ~Timer() { if (a) (void)hipEventDestroy(a); if (b) (void)hipEventDestroy(b); }
+    void start() { MGTA_HIP_CHECK(hipEventRecord(a, st)); }
+    void end() { MGTA_HIP_CHECK(hipEventRecord(b, st)); }        // without waiting: ms() once the stream is past it
+    float ms() const { float t = 0; MGTA_HIP_CHECK(hipEventElapsedTime(&t, a, b)); return t; }
+    double stop() {   // milliseconds, synchronises; a launch the runtime rejected inside the phase (grid or LDS limits) surfaces here
+        MGTA_HIP_CHECK(hipGetLastError());
+        end();
+        MGTA_HIP_CHECK(hipEventSynchronize(b));
+        MGTA_HIP_CHECK(hipGetLastError());
+        return ms();
+    }
+};
+
 // slots of mgta_ctx::pool, the graph build's grow-only device buffers; between builds others may borrow its key buffers S_KEYS_A / S_KEYS_B
 enum Slot { S_BLOCK_COUNT, S_BLOCK_BASE, S_SCAN_TMP, S_SMALL, S_KEYS_A, S_KEYS_B, S_HIST, S_TILE_HEADS, S_TILE_BASE, S_CNT, S_BASE,
             S_FIRST, S_OUT_REC, S_OUT_LARGE, S_OUT_TIPS, S_PLAN, S_BIG, S_LSD, S_MULTI_COUNT, S_POS2ID, S_SOLID, S_MERCY, S_EDGE_COUNT, S_SIDE, S_NUM };

@@ -255,13 +255,6 @@ uint16_t *window_scratch(mgta_ctx *ctx, uint64_t bytes) {
     return b.as<uint16_t>();
 }
 
-float elapsed_ms(hipEvent_t a, hipEvent_t b) {
-    float ms = 0;
-    MGTA_HIP_CHECK(hipEventSynchronize(b));
-    MGTA_HIP_CHECK(hipEventElapsedTime(&ms, a, b));
-    return ms;
-}
-
 }  // namespace
 }  // namespace mgta
 
@@ -301,13 +294,12 @@ int mgta_contig_coverage(mgta_sdbg *g, const char *seqs, const uint64_t *offsets
     if (stats) memset(stats, 0, sizeof(*stats));
     if (abundance) memset(abundance, 0, 65536 * sizeof(int64_t));
     if (n == 0) return MGTA_OK;
-    hipEvent_t ev[3] = {nullptr, nullptr, nullptr};
-    const int rc = guarded("mgta_contig_coverage", [&]() {
+    return guarded("mgta_contig_coverage", [&]() {
         mgta_ctx *ctx = g->ctx;
         MGTA_HIP_CHECK(hipSetDevice(ctx->device));
         hipStream_t st = ctx->stream;
         const uint64_t k = (uint64_t)g->dev.k;
-        for (auto &e : ev) MGTA_HIP_CHECK(hipEventCreate(&e));
+        Timer t_walk(st), t_stats(st);
         const uint64_t cap = ctx->coverage_batch_windows ? ctx->coverage_batch_windows : 1ull << 29;   // windows per batch: 1 GB of per-window scratch
         // workgroups of the walk a CU holds at once: what its registers allow (never assumed)
         int blocks_per_cu = 0;
@@ -359,22 +351,23 @@ int mgta_contig_coverage(mgta_sdbg *g, const char *seqs, const uint64_t *offsets
             const uint64_t groups = (uint64_t)ctx->num_cus * (uint64_t)blocks_per_cu * (kCovThreads / 8);
             const uint32_t chunk = nj >= groups * 64 ? 4u : 1u;
             const unsigned blocks = (unsigned)std::min<uint64_t>((uint64_t)ctx->num_cus * (uint64_t)blocks_per_cu, ((uint64_t)nj + kCovThreads / 8 - 1) / (kCovThreads / 8));
-            MGTA_HIP_CHECK(hipEventRecord(ev[0], st));
+            t_walk.start();
             if (g->dev.size > 0)
                 hipLaunchKernelGGL(cov_walk_kernel, dim3(blocks), dim3(kCovThreads), 0, st, g->dev, g->mult, d_sym.as<uint8_t>(), d_jobs.as<CovJob>(), nj, chunk, d_pw,
                                    d_marks, d_abund.as<unsigned long long>(), d_cnt.as<unsigned long long>());
             else
                 MGTA_HIP_CHECK(hipMemsetAsync(d_pw, 0, n_win * 2 + 64, st));
             MGTA_HIP_CHECK(hipGetLastError());
-            MGTA_HIP_CHECK(hipEventRecord(ev[1], st));
+            t_walk.end();
+            t_stats.start();
             hipLaunchKernelGGL(cov_stats_kernel, dim3((nj + 3) / 4), dim3(256), 0, st, d_jobs.as<CovJob>(), nj, (int)k, d_pw, d_out.as<mgta_contig_cov>());
             MGTA_HIP_CHECK(hipGetLastError());
-            MGTA_HIP_CHECK(hipEventRecord(ev[2], st));
+            t_stats.end();
             MGTA_HIP_CHECK(hipMemcpyAsync(per_contig + c0, d_out.p, (size_t)nj * sizeof(mgta_contig_cov), hipMemcpyDeviceToHost, st));
             if (per_window && n_win) MGTA_HIP_CHECK(hipMemcpyAsync(per_window + win_done, d_pw, n_win * 2, hipMemcpyDeviceToHost, st));
             MGTA_HIP_CHECK(hipStreamSynchronize(st));                     // (jobs and the device buffers serve the next batch)
-            ms_walk += elapsed_ms(ev[0], ev[1]);
-            ms_stats += elapsed_ms(ev[1], ev[2]);
+            ms_walk += t_walk.ms();
+            ms_stats += t_stats.ms();
             win_done += n_win;
             ++n_batches;
             c0 = c1;
@@ -390,8 +383,6 @@ int mgta_contig_coverage(mgta_sdbg *g, const char *seqs, const uint64_t *offsets
         }
         return MGTA_OK;
     });
-    for (auto &e : ev) if (e) (void)hipEventDestroy(e);
-    return rc;
 }
 
 }  // extern "C"

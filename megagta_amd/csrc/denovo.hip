@@ -290,6 +290,45 @@ struct StampTab {
     }
 };
 
+// The edges one reach walk has seen so far: open addressing in the candidate's own scratch.  Entries carry the round in their top 24
+// bits: whatever an earlier round or a search left in the scratch reads as empty (edge ids stay below 2^40), so nothing is cleared.
+// tag_flag sets the wide walk's entries apart: what the narrow walk of the same round left reads as stale.
+struct ReachSet {
+    unsigned long long *hash;
+    unsigned long long tag;
+    __device__ ReachSet(int64_t *scratch, unsigned long long round, unsigned long long tag_flag)
+        : hash(reinterpret_cast<unsigned long long *>(scratch)), tag((((round & 0x3FFFFFull) + 1) << 40) | tag_flag) {}
+    __device__ __forceinline__ bool insert(int64_t e) const {        // true = new; slots are claimed at the L2 (other lanes insert at the same time)
+        uint32_t h = (uint32_t)(((uint64_t)e * 0x9E3779B97F4A7C15ull) >> 49) & (kReachHash - 1);
+        const unsigned long long mine = tag | (unsigned long long)e;
+        for (;;) {
+            unsigned long long v = __hip_atomic_load(&hash[h], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+            if (v == mine) return false;
+            if ((v & ~0xFFFFFFFFFFull) != tag) {
+                if (__hip_atomic_compare_exchange_strong(&hash[h], &v, mine, __ATOMIC_RELAXED, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)) return true;
+                if (v == mine) return false;
+                continue;                            // another lane took the slot for another edge: look at it again
+            }
+            h = (h + 1) & (kReachHash - 1);
+        }
+    }
+};
+// a reach walk's counters (LDS, shared by the lanes that walk one candidate)
+enum { C_NEXT /* edges of the next level */, C_SEEN /* edges seen */, C_STOP, C_OVER /* the REGION is over the limit (not the table) */, C_NUM };
+// An out-edge a reach walk sees for the first time: counted, given a place in the next level's frontier, stamped together with the
+// edges into it.  The walk stops when the region is over `limit` or a stamp did not fit (the stamp table is crowded: treated like a
+// region that does not fit).
+__device__ __forceinline__ void reach_new_edge(const GraphDev &g, int64_t e, int *cnt, int64_t *nxt, int limit, const StampTab &owner, unsigned long long key) {
+    const int seen = atomicAdd(&cnt[C_SEEN], 1) + 1, at = atomicAdd(&cnt[C_NEXT], 1);
+    if (seen > limit || at >= kReachFrontier) { cnt[C_STOP] = 1; cnt[C_OVER] = 1; return; }
+    __hip_atomic_store(&nxt[at], e, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    bool fits = owner.stamp(e, key);
+    int64_t in[8];
+    const int id = d_incoming(g, e, in);
+    for (int y = 0; y < id; ++y) fits = owner.stamp(in[y], key) && fits;
+    if (!fits) cnt[C_STOP] = 1;
+}
+
 struct SinkNone { __device__ void operator()(int64_t) {} __device__ bool stop() const { return false; } };
 struct SinkStamp {
     StampTab tab;
@@ -406,34 +445,16 @@ __global__ __launch_bounds__(64) void bubble_find_kernel(GraphDev g, const int64
 // otherwise keep one lane busy for milliseconds while the round waits for it).  Which edges end up stamped, and whether the region
 // fits, depends on the region alone (counts per level and in all), not on the order the lanes find them in.
 __device__ bool bubble_reach_stamp(const GraphDev &g, int64_t begin, int max_len, int64_t *scratch, const StampTab &owner, unsigned long long key,
-                                   unsigned long long round, int reach_max, int *s_cnt /* LDS: [0] edges of the next level, [1] edges seen, [2] overflow */,
-                                   unsigned long long tag_flag) {
+                                   unsigned long long round, int reach_max, int *s_cnt /* LDS: C_NUM counters */, unsigned long long tag_flag) {
     if (!g_valid(g, begin)) return true;
     const int lane = threadIdx.x;
-    unsigned long long *hash = reinterpret_cast<unsigned long long *>(scratch);
     int64_t *cur = scratch + kReachHash, *nxt = cur + kReachFrontier;
-    // hash entries carry the round in their top 24 bits: whatever an earlier round or a search left in the scratch reads as empty
-    // (edge ids stay below 2^40), so nothing is cleared
-    const unsigned long long tag = (((round & 0x3FFFFFull) + 1) << 40) | tag_flag;     // (tag_flag: what the narrow walk of the same round left reads as stale)
-    auto insert = [&](int64_t e) -> bool {           // true = new; slots are claimed at the L2 (other lanes insert at the same time)
-        uint32_t h = (uint32_t)(((uint64_t)e * 0x9E3779B97F4A7C15ull) >> 49) & (kReachHash - 1);
-        const unsigned long long mine = tag | (unsigned long long)e;
-        for (;;) {
-            unsigned long long v = __hip_atomic_load(&hash[h], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-            if (v == mine) return false;
-            if ((v & ~0xFFFFFFFFFFull) != tag) {
-                if (__hip_atomic_compare_exchange_strong(&hash[h], &v, mine, __ATOMIC_RELAXED, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)) return true;
-                if (v == mine) return false;
-                continue;                            // another lane took the slot for another edge: look at it again
-            }
-            h = (h + 1) & (kReachHash - 1);
-        }
-    };
+    const ReachSet set(scratch, round, tag_flag);
     if (lane == 0) {
-        s_cnt[0] = 0; s_cnt[1] = 1; s_cnt[2] = 0; s_cnt[3] = 0;
-        insert(begin);
+        s_cnt[C_NEXT] = 0; s_cnt[C_SEEN] = 1; s_cnt[C_STOP] = 0; s_cnt[C_OVER] = 0;
+        set.insert(begin);
         __hip_atomic_store(&cur[0], begin, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        if (!owner.stamp(begin, key)) s_cnt[2] = 1;
+        if (!owner.stamp(begin, key)) s_cnt[C_STOP] = 1;
     }
     __syncthreads();
     int n_cur = 1;
@@ -443,29 +464,29 @@ __device__ bool bubble_reach_stamp(const GraphDev &g, int64_t begin, int max_len
             if (i < n_cur) {
                 int64_t out[8];
                 const int od = d_outgoing(g, __hip_atomic_load(&cur[i], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT), out);
-                for (int x = 0; x < od; ++x) {
-                    if (!insert(out[x])) continue;
-                    const int seen = atomicAdd(&s_cnt[1], 1) + 1, at = atomicAdd(&s_cnt[0], 1);
-                    if (seen > reach_max || at >= kReachFrontier) { s_cnt[2] = 1; s_cnt[3] = 1; continue; }   // [3]: the REGION is too large (not the table)
-                    __hip_atomic_store(&nxt[at], out[x], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-                    bool fits = owner.stamp(out[x], key);
-                    int64_t in[8];
-                    const int id = d_incoming(g, out[x], in);
-                    for (int y = 0; y < id; ++y) fits = owner.stamp(in[y], key) && fits;
-                    if (!fits) s_cnt[2] = 1;                            // the stamp table is crowded: treated like a region that does not fit
-                }
+                for (int x = 0; x < od; ++x)
+                    if (set.insert(out[x])) reach_new_edge(g, out[x], s_cnt, nxt, reach_max, owner, key);
             }
         }
         __syncthreads();
-        if (s_cnt[2]) return false;
-        n_cur = s_cnt[0];
+        if (s_cnt[C_STOP]) return false;
+        n_cur = s_cnt[C_NEXT];
         __syncthreads();
-        if (lane == 0) s_cnt[0] = 0;
+        if (lane == 0) s_cnt[C_NEXT] = 0;
         __syncthreads();
         int64_t *t = cur; cur = nxt; nxt = t;
     }
     return true;
 }
+
+// One round's counters, shared by its kernels and the host (set before the round, read back after it)
+struct RoundCounters {
+    uint32_t barrier;      // lowest position whose candidate's check failed with its reach unknown: nobody above it commits
+    uint32_t n_done;       // candidates that committed
+    uint32_t n_crowded;    // candidates that could not stamp even what they read: the host shrinks the next window
+    uint32_t n_wide;       // length of the list of candidates left to the wide walk
+};
+static_assert(sizeof(RoundCounters) == 16, "round counters");
 
 constexpr unsigned long long kKnownBig = 1ull << 63;   // in a window's position word: the candidate's region did not fit the scratch in an earlier round
 constexpr unsigned long long kKnownWide = 1ull << 62;  // ... its region has more than kNarrowMax edges: walked by a whole wave from the start
@@ -479,12 +500,12 @@ constexpr int kNarrowLanes = 8, kNarrowMax = 512;
 // write at its turn is open) does it become the round's barrier: nobody above it commits.  Round 3 raised the barrier at every such
 // candidate, whatever its check said: every region that did not fit cost a round (100 M reads, k = 29: thousands of rounds).
 __device__ void bubble_reach_failed(const GraphDev &g, const int64_t *cand, uint32_t i, int max_len, int64_t *scratch, size_t per, const StampTab &owner,
-                                    unsigned long long key, uint32_t *barrier, uint32_t *unknown) {
+                                    unsigned long long key, RoundCounters *rc, uint32_t *unknown) {
     unknown[i] = 1u;
     int mult[kMaxBranches], nb = 0, len = 0;
     SinkStamp s{owner, key, true};
     bubble_search(g, cand[i], max_len, scratch + (size_t)i * per, mult, nb, len, s);
-    if (!s.ok) atomicAdd(barrier + 2, 1u);                             // not even that fitted the table: the host shrinks the next window
+    if (!s.ok) atomicAdd(&rc->n_crowded, 1u);                          // not even that fitted the table
 }
 
 // Most regions are a few dozen edges in levels of one to three: a wave per candidate keeps 60 lanes idle through ~60 levels of dependent
@@ -492,10 +513,10 @@ __device__ void bubble_reach_failed(const GraphDev &g, const int64_t *cand, uint
 // (same stamps, same verdict) with eight times the candidates in flight.  A region of more than kNarrowMax edges is left to the wave-wide
 // walk below (list), now and in later rounds (kKnownWide); what this walk stamped of it is a subset of what that one stamps.
 __global__ __launch_bounds__(64) void bubble_reach_narrow_kernel(GraphDev g, const int64_t *cand, uint64_t *pos, uint32_t n, int max_len, int64_t *scratch, size_t per,
-                                                                 StampTab owner, unsigned long long round, int reach_max, int narrow_max, uint32_t *barrier,
-                                                                 uint32_t *wide_list, uint32_t *wide_count, uint32_t *unknown) {
+                                                                 StampTab owner, unsigned long long round, int reach_max, int narrow_max, RoundCounters *rc,
+                                                                 uint32_t *wide_list, uint32_t *unknown) {
     constexpr int G = kNarrowLanes, NG = 64 / G;
-    __shared__ int s_cnt[NG][4];                                       // per candidate: [0] edges of the next level, [1] edges seen, [2] stop, [3] the region is over the limit
+    __shared__ int s_cnt[NG][C_NUM];                                   // per candidate
     const int lane = threadIdx.x, grp = lane / G, gl = lane % G;
     const uint32_t i = blockIdx.x * NG + grp;
     const bool have = i < n;
@@ -507,29 +528,14 @@ __global__ __launch_bounds__(64) void bubble_reach_narrow_kernel(GraphDev g, con
     enum { WALK, FITS, FAILED, WIDE };
     int state = !have ? FITS : known_big ? FAILED : known_wide ? WIDE : !g_valid(g, begin) ? FITS : WALK;
     int64_t *mine = scratch + (size_t)(have ? i : 0) * per;
-    unsigned long long *hash = reinterpret_cast<unsigned long long *>(mine);
     int64_t *cur = mine + kReachHash, *nxt = cur + kReachFrontier;
-    const unsigned long long tag = ((round & 0x3FFFFFull) + 1) << 40;
-    auto insert = [&](int64_t e) -> bool {           // as in bubble_reach_stamp
-        uint32_t h = (uint32_t)(((uint64_t)e * 0x9E3779B97F4A7C15ull) >> 49) & (kReachHash - 1);
-        const unsigned long long me = tag | (unsigned long long)e;
-        for (;;) {
-            unsigned long long v = __hip_atomic_load(&hash[h], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-            if (v == me) return false;
-            if ((v & ~0xFFFFFFFFFFull) != tag) {
-                if (__hip_atomic_compare_exchange_strong(&hash[h], &v, me, __ATOMIC_RELAXED, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)) return true;
-                if (v == me) return false;
-                continue;
-            }
-            h = (h + 1) & (kReachHash - 1);
-        }
-    };
+    const ReachSet set(mine, round, 0ull);
     if (gl == 0) {
-        s_cnt[grp][0] = 0; s_cnt[grp][1] = 1; s_cnt[grp][2] = 0; s_cnt[grp][3] = 0;
+        s_cnt[grp][C_NEXT] = 0; s_cnt[grp][C_SEEN] = 1; s_cnt[grp][C_STOP] = 0; s_cnt[grp][C_OVER] = 0;
         if (state == WALK) {
-            insert(begin);
+            set.insert(begin);
             __hip_atomic_store(&cur[0], begin, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-            if (!owner.stamp(begin, key)) s_cnt[grp][2] = 1;
+            if (!owner.stamp(begin, key)) s_cnt[grp][C_STOP] = 1;
         }
     }
     __syncthreads();
@@ -542,54 +548,45 @@ __global__ __launch_bounds__(64) void bubble_reach_narrow_kernel(GraphDev g, con
             if (walking && idx < n_cur) {
                 int64_t out[8];
                 const int od = d_outgoing(g, __hip_atomic_load(&cur[idx], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT), out);
-                for (int x = 0; x < od; ++x) {
-                    if (!insert(out[x])) continue;
-                    const int seen = atomicAdd(&s_cnt[grp][1], 1) + 1, at = atomicAdd(&s_cnt[grp][0], 1);
-                    if (seen > limit || at >= kReachFrontier) { s_cnt[grp][2] = 1; s_cnt[grp][3] = 1; continue; }
-                    __hip_atomic_store(&nxt[at], out[x], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-                    bool fits = owner.stamp(out[x], key);
-                    int64_t in[8];
-                    const int id = d_incoming(g, out[x], in);
-                    for (int y = 0; y < id; ++y) fits = owner.stamp(in[y], key) && fits;
-                    if (!fits) s_cnt[grp][2] = 1;
-                }
+                for (int x = 0; x < od; ++x)
+                    if (set.insert(out[x])) reach_new_edge(g, out[x], s_cnt[grp], nxt, limit, owner, key);
             }
         }
         __syncthreads();
         if (walking) {
-            if (s_cnt[grp][2]) state = !s_cnt[grp][3] ? FAILED : (reach_max <= narrow_max ? FAILED : WIDE);
-            else n_cur = s_cnt[grp][0];
+            if (s_cnt[grp][C_STOP]) state = !s_cnt[grp][C_OVER] ? FAILED : (reach_max <= narrow_max ? FAILED : WIDE);
+            else n_cur = s_cnt[grp][C_NEXT];
         }
         __syncthreads();
-        if (gl == 0) s_cnt[grp][0] = 0;
+        if (gl == 0) s_cnt[grp][C_NEXT] = 0;
         __syncthreads();
         int64_t *t = cur; cur = nxt; nxt = t;
     }
     if (gl != 0 || !have || state == WALK || state == FITS) return;
     if (state == WIDE) {
         if (!known_wide) pos[i] = pw | kKnownWide;
-        wide_list[atomicAdd(wide_count, 1u)] = i;
+        wide_list[atomicAdd(&rc->n_wide, 1u)] = i;
         return;
     }
-    if (!known_big && s_cnt[grp][3]) pos[i] = pw | kKnownBig;          // (only with reach_max <= narrow_max: the region is too large for any walk)
-    bubble_reach_failed(g, cand, i, max_len, scratch, per, owner, key, barrier, unknown);
+    if (!known_big && s_cnt[grp][C_OVER]) pos[i] = pw | kKnownBig;          // (only with reach_max <= narrow_max: the region is too large for any walk)
+    bubble_reach_failed(g, cand, i, max_len, scratch, per, owner, key, rc, unknown);
 }
 // the listed candidates (regions of more than kNarrowMax edges), one workgroup of four waves each: the lanes take the edges of a level
 // side by side (a region of thousands of edges in a repeat would otherwise keep one lane busy for milliseconds while the round waits)
 constexpr int kWideThreads = 256;
 __global__ __launch_bounds__(kWideThreads) void bubble_reach_kernel(GraphDev g, const int64_t *cand, uint64_t *pos, int max_len, int64_t *scratch, size_t per,
-                                                          StampTab owner, unsigned long long round, int reach_max, uint32_t *barrier, const uint32_t *wide_list,
-                                                          const uint32_t *wide_count, uint32_t *unknown) {
-    __shared__ int s_cnt[4];
-    const uint32_t n_wide = *wide_count;
+                                                          StampTab owner, unsigned long long round, int reach_max, RoundCounters *rc, const uint32_t *wide_list,
+                                                          uint32_t *unknown) {
+    __shared__ int s_cnt[C_NUM];
+    const uint32_t n_wide = rc->n_wide;
     for (uint32_t b = blockIdx.x; b < n_wide; b += gridDim.x) {
         const uint32_t i = wide_list[b];
         const unsigned long long key = (round << 32) | (0xFFFFFFFFull - i);
         __syncthreads();                                                // the previous candidate's counters are no longer read
         if (bubble_reach_stamp(g, cand[i], max_len, scratch + (size_t)i * per, owner, key, round, reach_max, s_cnt, 1ull << 63)) continue;
         if (threadIdx.x != 0) continue;
-        if (s_cnt[3]) pos[i] |= kKnownBig;
-        bubble_reach_failed(g, cand, i, max_len, scratch, per, owner, key, barrier, unknown);
+        if (s_cnt[C_OVER]) pos[i] |= kKnownBig;
+        bubble_reach_failed(g, cand, i, max_len, scratch, per, owner, key, rc, unknown);
     }
 }
 // (the search's results: behind the reach walk's hash table and frontiers -- the packed multiplicities can have bits 40 and above set,
@@ -810,6 +807,16 @@ struct Work {
     hipStream_t st;
     Dn d;
     DevBuf mask, count, base, tmp, total;
+    explicit Work(mgta_sdbg *graph) : ctx(graph->ctx), st(graph->ctx->stream) {
+        d.g = graph->dev;
+        d.rw = graph->lines.as<GLine>();
+        const uint64_t n_lines = d.g.n_lines;
+        mask.alloc((n_lines + 1) * 8, live(), peak());
+        count.alloc((n_lines + 1) * 4, live(), peak());
+        base.alloc((n_lines + 1) * 8, live(), peak());
+        tmp.alloc(scan_tmp_elems(n_lines) * 8, live(), peak());
+        total.alloc(64, live(), peak());
+    }
     uint64_t *live() { return &ctx->live_bytes; }
     uint64_t *peak() { return &ctx->peak_bytes; }
 };
@@ -890,165 +897,202 @@ static uint64_t remove_tips(Work &w, int max_tip_len) {   // assembly_algorithms
     return read_u64(w, counter.p);
 }
 
-struct BubbleWork {
-    DevBuf scratch, stamp_key, stamp_val, marked, status, win[2], pos[2], ok, keep, base, tmp, small, unknown;
-    int64_t *scratch_p = nullptr;   // the per-candidate scratch: `scratch`, or a buffer of the context's pool that nobody uses during a denovo
-    uint64_t scratch_bytes = 0;
-    uint64_t stamp_mask = 0;
-    int64_t n_crowded = 0;   // rounds in which the stamp table turned a candidate away
-    size_t per = 0;          // int64 of scratch per candidate
-    uint32_t window = 0;
-    int reach_max = kReachMax;
-    int narrow_max = kNarrowMax;
-    uint64_t round = 0;
+// int64 of scratch per candidate: reach hash (the search's branches overlay it: edge ids read as stale entries) | frontiers | results
+constexpr size_t kCandWords = kResOffset + 1 + kMaxBranches / 2;
+static_assert((size_t)kMaxBranches * (2 * kMaxK + 4) <= (size_t)kReachHash, "the branches of a search fit the hash region");
+
+struct BubblePlan {
+    int borrow_slot = -1;        // slot of the context's pool whose buffer is the scratch (nobody uses it during a denovo); -1 = an allocation of its own
+    uint64_t scratch_bytes = 0;  // of that allocation
+    uint32_t window = 0;         // candidates per round at most
+    int reach_max = kReachMax, narrow_max = kNarrowMax;
+    int stamp_log = 22;          // log2 of the stamp table's slots
+    uint64_t find_threads = 0;   // of bubble_find_kernel
 };
 
-// the ordered loop `for each candidate: Search, then Pop` (assembly_algorithms.cpp:266-279 and :283-292)
-static void pop_in_order(Work &w, BubbleWork &b, const DevBuf &cand, uint64_t n, int max_len, int64_t &n_rounds) {
-    const GraphDev &g = w.d.g;
-    uint64_t p = 0;           // next candidate of the list not yet in a window
-    uint32_t carry = 0;       // pending candidates kept from the previous window (front of win[cur])
-    int cur = 0;
-    uint32_t want = std::min<uint32_t>(4096, b.window);
-    uint32_t *barrier = b.small.as<uint32_t>(), *n_done = b.small.as<uint32_t>() + 1;
-    uint32_t cap = b.window;      // windows shrink while the stamp table overflows (a crowded table holds back what it could not stamp)
-    while (carry > 0 || p < n) {
-        // (a carry larger than the round is cut: the candidates beyond it stay pending, in order.  A round that committed little is followed
-        // by a small one whatever is pending: behind a region that does not fit its scratch only the lowest candidates can commit, and a
-        // round costs what its window costs -- 500 M reads spent 19 727 rounds of 40-86 k candidates committing a few hundred each)
-        const uint32_t m = (uint32_t)std::min<uint64_t>(std::max<uint32_t>(1u, std::min<uint32_t>(want, std::max(cap, 1u))), carry + (n - p));
-        const uint32_t take = m > carry ? m - carry : 0, shed = carry > m ? carry - m : 0;
-        if (take) hipLaunchKernelGGL(window_fill_kernel, dim3((take + 255) / 256), dim3(256), 0, w.st, cand.as<int64_t>(), p, take, carry, b.win[cur].as<int64_t>(),
-                                     b.pos[cur].as<uint64_t>());
-        p += take;
-        ++b.round; ++n_rounds;
-        if (b.round >= 0xFFFFFEull) { set_error("mgta_denovo: more than 2^24 bubble rounds"); throw HipError{MGTA_EUNSUPPORTED}; }
-        const int64_t *c = b.win[cur].as<int64_t>();
-        const uint32_t init[4] = {0xFFFFFFFFu, 0u, 0u, 0u};
-        MGTA_HIP_CHECK(hipMemcpyAsync(b.small.p, init, 16, hipMemcpyHostToDevice, w.st));
-        MGTA_HIP_CHECK(hipMemsetAsync(b.unknown.p, 0, (size_t)m * 4, w.st));
-        const StampTab tab{b.stamp_key.as<unsigned long long>(), b.stamp_val.as<unsigned long long>(), b.stamp_mask, (unsigned long long)(b.round + 1) << 40};
-        // (the list of the wide candidates lives in `ok` until the check kernel writes that; its length in the fourth counter)
-        hipLaunchKernelGGL(bubble_reach_narrow_kernel, dim3((m + 64 / kNarrowLanes - 1) / (64 / kNarrowLanes)), dim3(64), 0, w.st, g, c, b.pos[cur].as<uint64_t>(), m, max_len,
-                           b.scratch_p, b.per, tab, (unsigned long long)b.round, b.reach_max, b.narrow_max, barrier, b.ok.as<uint32_t>(), barrier + 3, b.unknown.as<uint32_t>());
-        hipLaunchKernelGGL(bubble_reach_kernel, dim3(std::min<uint32_t>(m, 8192u)), dim3(kWideThreads), 0, w.st, g, c, b.pos[cur].as<uint64_t>(), max_len, b.scratch_p, b.per,
-                           tab, (unsigned long long)b.round, b.reach_max, barrier, b.ok.as<uint32_t>(), barrier + 3, b.unknown.as<uint32_t>());
-        hipLaunchKernelGGL(bubble_check_kernel, dim3((m + 63) / 64), dim3(64), 0, w.st, g, c, m, max_len, b.scratch_p, b.per, tab,
-                           (unsigned long long)b.round, b.ok.as<uint32_t>(), barrier, b.unknown.as<uint32_t>());
-        hipLaunchKernelGGL(bubble_commit_kernel, dim3((m + 63) / 64), dim3(64), 0, w.st, w.d, c, b.pos[cur].as<uint64_t>(), m, max_len, b.scratch_p, b.per,
-                           b.ok.as<uint32_t>(), barrier, b.marked.as<unsigned long long>(), b.status.as<uint32_t>(), b.keep.as<uint32_t>(), n_done);
-        if (shed) {      // the candidates beyond the cut stay pending, behind the ones this round keeps
-            hipLaunchKernelGGL(fill_u32_kernel, dim3((shed + 255) / 256), dim3(256), 0, w.st, b.keep.as<uint32_t>() + m, shed, 1u);
-        }
-        const uint32_t mm = m + shed;
-        exclusive_scan_u32(w.st, b.keep.as<uint32_t>(), mm, b.base.as<uint64_t>(), b.tmp.as<uint64_t>(), w.total.as<uint64_t>());
-        hipLaunchKernelGGL(window_keep_kernel, dim3((mm + 255) / 256), dim3(256), 0, w.st, c, b.pos[cur].as<uint64_t>(), b.keep.as<uint32_t>(), b.base.as<uint64_t>(), mm,
-                           b.win[cur ^ 1].as<int64_t>(), b.pos[cur ^ 1].as<uint64_t>());
-        uint32_t flags[4];
-        MGTA_HIP_CHECK(hipMemcpyAsync(flags, b.small.p, 16, hipMemcpyDeviceToHost, w.st));
-        carry = (uint32_t)read_u64(w, w.total.p);
-        cur ^= 1;
-        const uint32_t done = mm - carry;
-        if (flags[2]) { cap = std::max<uint32_t>(1, m / 2); ++b.n_crowded; }   // some candidate could not stamp even what it reads: fewer candidates share the table next time
-        else if (cap < b.window) cap = std::min<uint32_t>(b.window, cap * 2);
-        if (done == 0 && !(flags[2] && m > 1)) { set_error("mgta_denovo: a bubble round committed nothing"); throw HipError{MGTA_EINTERNAL}; }   // the lowest always commits
-        want = std::min<uint32_t>(b.window, std::max<uint32_t>(std::min<uint32_t>(4096, b.window), 4 * std::max(done, 1u)));
-        if ((n_rounds & 15) == 1) note(w, "bubble round %lld: window %u, committed %u, %llu of %llu taken", (long long)n_rounds, m, done, (unsigned long long)p, (unsigned long long)n);     // a round that commits few (a region that does not fit the reach scratch) shrinks the next
-    }
-}
-
-static uint64_t pop_bubbles(Work &w, int64_t &n_rounds, int64_t &n_candidates) {   // assembly_algorithms.cpp:245-301
-    const GraphDev &g = w.d.g;
-    const int max_len = g.k * 2 + 4;
-    BubbleWork b;
-    DevBuf branching, found, cand, flag, again, counter;
-    uint64_t nb = edges_where(w, PredBranching{}, branching);
-    b.per = kResOffset + 1 + kMaxBranches / 2;                         // reach hash (the search's branches overlay it: edge ids read as stale entries) | frontiers | results
-    static_assert((size_t)kMaxBranches * (2 * kMaxK + 4) <= (size_t)kReachHash, "the branches of a search fit the hash region");
+// Host arithmetic only.  keys_bytes: the sizes of the pool's S_KEYS_A / S_KEYS_B (0 = not there).
+static BubblePlan plan_bubble_scratch(uint64_t free_b, const uint64_t (&keys_bytes)[2], uint64_t n_branching, uint64_t n_edges, int max_len) {
+    BubblePlan p;
     // candidates per round: as many as an eighth of the free device memory (2 .. 32 GB) holds scratch for -- a round costs ~24 ms of
     // launches and look-ups whatever it commits, 100 M reads took 513 rounds with 8 GB
-    size_t free_b = 0, total_b = 0;
-    MGTA_HIP_CHECK(hipMemGetInfo(&free_b, &total_b));
-    uint64_t scratch_cap = 32ull << 30, borrow_cap = 128ull << 30;
-    if (const char *e = getenv("MGTA_DENOVO_SCRATCH_GB")) scratch_cap = borrow_cap = (uint64_t)std::max(1, atoi(e)) << 30;   // (measurements)
-    uint64_t scratch_budget = std::min<uint64_t>(scratch_cap, std::max<uint64_t>(2ull << 30, (uint64_t)free_b / 8));
+    uint64_t budget = std::min<uint64_t>(32ull << 30, std::max<uint64_t>(2ull << 30, free_b / 8));
     // ... but never more than the branching edges can use (a window slot per candidate, a read-only search per branching edge for as many
     // threads as the device holds at once), and obtained ONCE: 2 M reads: 32 GB of scratch for 263 k candidates cost 1.0-1.8 s of
     // hipMalloc per `denovo`, five to nine times the rounds themselves.  The build's key buffers sit idle in the context's pool while a
     // denovo runs (the worker keeps them between the steps): the larger of the two is borrowed when it holds at least a quarter of that --
     // and then ALL of it may be used (up to 128 GB): it costs nothing to obtain.  100 M reads, k = 29 / 35: windows of 228 k instead of
     // 61 k candidates, 130 / 88 rounds instead of 319 / 271, 7.6 / 6.8 s instead of 8.5 / 8.4 s (a round costs mostly what its window costs).
-    const uint64_t per_find_b = (uint64_t)kMaxBranches * (uint64_t)max_len * 8;
-    const uint64_t need = std::max<uint64_t>(256ull << 20, std::max<uint64_t>(std::min<uint64_t>((nb + 63) / 64 * 64, 1ull << 20) * per_find_b,
-                                                                             std::min<uint64_t>((nb + 63) / 64 * 64 + 64, kBubbleWindowMax) * (uint64_t)b.per * 8));
-    scratch_budget = std::min(scratch_budget, need);
-    int64_t *scratch_p = nullptr;
-    for (const int slot : {S_KEYS_A, S_KEYS_B}) {
-        if ((size_t)slot >= w.ctx->pool.size()) break;
-        DevBuf &kb = w.ctx->pool[slot];
-        if (kb.p && kb.bytes >= scratch_budget / 4 && kb.bytes >= (256ull << 20) && (!scratch_p || kb.bytes > b.scratch_bytes)) {
-            scratch_p = kb.as<int64_t>(); b.scratch_bytes = kb.bytes;
-        }
-    }
-    if (getenv("MGTA_DENOVO_OWN_SCRATCH")) scratch_p = nullptr;          // (measurements)
-    if (scratch_p) scratch_budget = std::min<uint64_t>(std::min<uint64_t>(borrow_cap, need), b.scratch_bytes);
-    b.window = (uint32_t)std::min<uint64_t>(kBubbleWindowMax, std::max<uint64_t>(4096, scratch_budget / (b.per * 8)));
+    const uint64_t nb64 = (n_branching + 63) / 64 * 64, per_find = (uint64_t)kMaxBranches * (uint64_t)max_len;
+    const uint64_t need = std::max<uint64_t>(256ull << 20, std::max<uint64_t>(std::min<uint64_t>(nb64, 1ull << 20) * per_find * 8,
+                                                                             std::min<uint64_t>(nb64 + 64, kBubbleWindowMax) * (uint64_t)kCandWords * 8));
+    budget = std::min(budget, need);
+    uint64_t borrowed = 0;
+    for (int i = 0; i < 2; ++i)
+        if (keys_bytes[i] >= budget / 4 && keys_bytes[i] >= (256ull << 20) && keys_bytes[i] > borrowed) { p.borrow_slot = i == 0 ? S_KEYS_A : S_KEYS_B; borrowed = keys_bytes[i]; }
+    if (borrowed) budget = std::min<uint64_t>(std::min<uint64_t>(128ull << 30, need), borrowed);
+    p.window = (uint32_t)std::min<uint64_t>(kBubbleWindowMax, std::max<uint64_t>(4096, budget / (kCandWords * 8)));
     // test knobs: tiny windows exercise the carry of pending candidates, a tiny reach limit the hold-back of a region that does not fit
-    if (const char *e = getenv("MGTA_DENOVO_WINDOW")) b.window = (uint32_t)std::max(64, atoi(e)) & ~63u;
-    if (const char *e = getenv("MGTA_DENOVO_REACH_MAX")) b.reach_max = std::min(kReachMax, std::max(1, atoi(e)));
-    if (const char *e = getenv("MGTA_DENOVO_NARROW_MAX")) b.narrow_max = std::min(kReachFrontier, std::max(1, atoi(e)));   // (tiny: every region takes the wave-wide walk)
-    if (scratch_p && (uint64_t)b.window * b.per * 8 <= b.scratch_bytes) b.scratch_p = scratch_p;
-    else { b.scratch.alloc((size_t)b.window * b.per * 8, w.live(), w.peak()); b.scratch_p = b.scratch.as<int64_t>(); }
-    found.alloc(nb * 4 + 64, w.live(), w.peak());
-    if (nb) {
-        // the read-only searches need kMaxBranches * max_len words each, not a reach table: as many threads as the scratch holds of those
-        // (10 M reads: 8.5 M branching edges took 1 s with one thread per window slot)
-        const size_t per_find = (size_t)kMaxBranches * max_len;
-        const uint64_t threads = std::min<uint64_t>((nb + 63) / 64 * 64, ((uint64_t)b.window * b.per / per_find) / 64 * 64);
-        hipLaunchKernelGGL(bubble_find_kernel, dim3((unsigned)(threads / 64)), dim3(64), 0, w.st, g, branching.as<int64_t>(), nb, max_len, b.scratch_p,
-                           per_find, found.as<uint32_t>());
-    }
-    const uint64_t nc = compact_list(w, branching, found, nb, cand);
-    n_candidates = (int64_t)nc;
-    note(w, "bubbles: %llu branching edges, %llu candidates, window %u", (unsigned long long)nb, (unsigned long long)nc, b.window);
-    if (nc == 0) return 0;
+    if (const char *e = getenv("MGTA_DENOVO_WINDOW")) p.window = (uint32_t)std::max(64, atoi(e)) & ~63u;
+    if (const char *e = getenv("MGTA_DENOVO_REACH_MAX")) p.reach_max = std::min(kReachMax, std::max(1, atoi(e)));
+    if (const char *e = getenv("MGTA_DENOVO_NARROW_MAX")) p.narrow_max = std::min(kReachFrontier, std::max(1, atoi(e)));   // (tiny: every region takes the wave-wide walk)
+    if ((uint64_t)p.window * kCandWords * 8 > borrowed) { p.borrow_slot = -1; p.scratch_bytes = (uint64_t)p.window * kCandWords * 8; }
+    // the read-only searches need kMaxBranches * max_len words each, not a reach table: as many threads as the scratch holds of those
+    // (10 M reads: 8.5 M branching edges took 1 s with one thread per window slot)
+    p.find_threads = std::min<uint64_t>(nb64, ((uint64_t)p.window * kCandWords / per_find) / 64 * 64);
     // the stamp table: one slot of 16 bytes per edge up to 2^29 slots (8 GB, whatever the size of the graph beyond that) -- a window of
     // 29 k candidates stamps up to 16 k edges each, a few hundred as a rule; what does not fit is held back and the next window is
     // smaller.  MGTA_DENOVO_STAMP_LOG2 (tests): a tiny table exercises that path.
-    int stamp_log = 22;
-    while (stamp_log < 29 && (1ull << stamp_log) < (uint64_t)g.size) ++stamp_log;
-    if (const char *e = getenv("MGTA_DENOVO_STAMP_LOG2")) stamp_log = std::min(30, std::max(8, atoi(e)));
-    b.stamp_mask = (1ull << stamp_log) - 1;
-    b.stamp_key.alloc((b.stamp_mask + 1) * 8, w.live(), w.peak());
-    b.stamp_val.alloc((b.stamp_mask + 1) * 8, w.live(), w.peak());
-    b.marked.alloc((g.n_lines + 1) * 8, w.live(), w.peak());
-    b.status.alloc(nc * 4 + 64, w.live(), w.peak());
-    for (int i = 0; i < 2; ++i) { b.win[i].alloc((size_t)b.window * 8, w.live(), w.peak()); b.pos[i].alloc((size_t)b.window * 8, w.live(), w.peak()); }
-    b.ok.alloc((size_t)b.window * 4, w.live(), w.peak());
-    b.keep.alloc((size_t)b.window * 4, w.live(), w.peak());
-    b.unknown.alloc((size_t)b.window * 4, w.live(), w.peak());
-    b.base.alloc((size_t)b.window * 8, w.live(), w.peak());
-    b.tmp.alloc(scan_tmp_elems(b.window) * 8, w.live(), w.peak());
-    b.small.alloc(64, w.live(), w.peak());
-    flag.alloc(nc * 4 + 64, w.live(), w.peak());
-    counter.alloc(64, w.live(), w.peak());
-    MGTA_HIP_CHECK(hipMemsetAsync(b.stamp_key.p, 0, (b.stamp_mask + 1) * 8, w.st));
-    MGTA_HIP_CHECK(hipMemsetAsync(b.stamp_val.p, 0, (b.stamp_mask + 1) * 8, w.st));
-    MGTA_HIP_CHECK(hipMemsetAsync(b.marked.p, 0, (g.n_lines + 1) * 8, w.st));
-    MGTA_HIP_CHECK(hipMemsetAsync(counter.p, 0, 64, w.st));
+    while (p.stamp_log < 29 && (1ull << p.stamp_log) < n_edges) ++p.stamp_log;
+    if (const char *e = getenv("MGTA_DENOVO_STAMP_LOG2")) p.stamp_log = std::min(30, std::max(8, atoi(e)));
+    return p;
+}
+
+struct BubbleWork {
+    BubblePlan plan;
+    DevBuf scratch, stamp_key, stamp_val, marked, status, win[2], pos[2], keep, unknown, base, tmp, counters, flag, popped;
+    DevBuf ok;                      // the check's verdicts; until the check kernel writes them, the list of the round's wide candidates (saves a window-sized buffer)
+    int64_t *scratch_p = nullptr;   // the per-candidate scratch: `scratch`, or the borrowed buffer
+    int64_t n_crowded = 0;          // rounds in which the stamp table turned a candidate away
+    uint64_t round = 0;
+};
+
+// the edges a search can succeed from (ascending).  Plans and obtains the scratch on the way: the read-only searches are its first users.
+static uint64_t find_candidates(Work &w, BubbleWork &b, int max_len, DevBuf &cand) {
+    const GraphDev &g = w.d.g;
+    DevBuf branching, found;
+    const uint64_t nb = edges_where(w, PredBranching{}, branching);
+    size_t free_b = 0, total_b = 0;
+    MGTA_HIP_CHECK(hipMemGetInfo(&free_b, &total_b));
+    uint64_t keys_bytes[2] = {0, 0};
+    const int key_slots[2] = {S_KEYS_A, S_KEYS_B};
+    for (int i = 0; i < 2; ++i)
+        if ((size_t)key_slots[i] < w.ctx->pool.size() && w.ctx->pool[key_slots[i]].p) keys_bytes[i] = w.ctx->pool[key_slots[i]].bytes;
+    b.plan = plan_bubble_scratch(free_b, keys_bytes, nb, (uint64_t)g.size, max_len);
+    if (b.plan.borrow_slot >= 0) b.scratch_p = w.ctx->pool[b.plan.borrow_slot].as<int64_t>();
+    else { b.scratch.alloc(b.plan.scratch_bytes, w.live(), w.peak()); b.scratch_p = b.scratch.as<int64_t>(); }
+    found.alloc(nb * 4 + 64, w.live(), w.peak());
+    if (nb)
+        hipLaunchKernelGGL(bubble_find_kernel, dim3((unsigned)(b.plan.find_threads / 64)), dim3(64), 0, w.st, g, branching.as<int64_t>(), nb, max_len, b.scratch_p,
+                           (size_t)kMaxBranches * max_len, found.as<uint32_t>());
+    const uint64_t nc = compact_list(w, branching, found, nb, cand);
+    note(w, "bubbles: %llu branching edges, %llu candidates, window %u", (unsigned long long)nb, (unsigned long long)nc, b.plan.window);
+    return nc;
+}
+
+static void alloc_bubble_work(Work &w, BubbleWork &b, uint64_t nc) {
+    const uint64_t n_lines = w.d.g.n_lines, slots = 1ull << b.plan.stamp_log, window = b.plan.window;
+    for (DevBuf *x : {&b.stamp_key, &b.stamp_val}) x->alloc(slots * 8, w.live(), w.peak());
+    b.marked.alloc((n_lines + 1) * 8, w.live(), w.peak());
+    for (DevBuf *x : {&b.status, &b.flag}) x->alloc(nc * 4 + 64, w.live(), w.peak());
+    for (DevBuf *x : {&b.win[0], &b.win[1], &b.pos[0], &b.pos[1], &b.base}) x->alloc(window * 8, w.live(), w.peak());
+    for (DevBuf *x : {&b.ok, &b.keep, &b.unknown}) x->alloc(window * 4, w.live(), w.peak());
+    b.tmp.alloc(scan_tmp_elems(window) * 8, w.live(), w.peak());
+    for (DevBuf *x : {&b.counters, &b.popped}) x->alloc(64, w.live(), w.peak());
+    MGTA_HIP_CHECK(hipMemsetAsync(b.stamp_key.p, 0, slots * 8, w.st));
+    MGTA_HIP_CHECK(hipMemsetAsync(b.stamp_val.p, 0, slots * 8, w.st));
+    MGTA_HIP_CHECK(hipMemsetAsync(b.marked.p, 0, (n_lines + 1) * 8, w.st));
+    MGTA_HIP_CHECK(hipMemsetAsync(b.popped.p, 0, 64, w.st));
+}
+
+struct Rounds {               // where the ordered loop stands
+    uint64_t p = 0;           // next candidate of the list not yet in a window
+    uint32_t carry = 0;       // pending candidates kept from the previous window (front of win[cur])
+    int cur = 0;
+    uint32_t want, cap;       // candidates of the next round: what the last one's commits suggest, what the stamp table holds (next_window)
+};
+struct RoundResult { uint32_t window, committed, carried; bool crowded; };
+
+// One round: the window is filled up from the list, every candidate stamps its reach, checks its stamps and commits or stays pending;
+// the pending ones move to the front of the other window, in order.
+static RoundResult run_round(Work &w, BubbleWork &b, const DevBuf &cand, uint64_t n, int max_len, Rounds &r) {
+    const GraphDev &g = w.d.g;
+    const BubblePlan &pl = b.plan;
+    // (a carry larger than the round is cut: the candidates beyond it stay pending, in order)
+    const uint32_t m = (uint32_t)std::min<uint64_t>(std::max<uint32_t>(1u, std::min<uint32_t>(r.want, std::max(r.cap, 1u))), r.carry + (n - r.p));
+    const uint32_t take = m > r.carry ? m - r.carry : 0, shed = r.carry > m ? r.carry - m : 0, mm = m + shed;
+    const int64_t *c = b.win[r.cur].as<int64_t>();
+    uint64_t *pos = b.pos[r.cur].as<uint64_t>();
+    uint32_t *ok = b.ok.as<uint32_t>(), *keep = b.keep.as<uint32_t>(), *unknown = b.unknown.as<uint32_t>();
+    RoundCounters *rc = b.counters.as<RoundCounters>();
+    if (take) hipLaunchKernelGGL(window_fill_kernel, dim3((take + 255) / 256), dim3(256), 0, w.st, cand.as<int64_t>(), r.p, take, r.carry, b.win[r.cur].as<int64_t>(), pos);
+    r.p += take;
+    if (++b.round >= 0xFFFFFEull) { set_error("mgta_denovo: more than 2^24 bubble rounds"); throw HipError{MGTA_EUNSUPPORTED}; }
+    const RoundCounters init{0xFFFFFFFFu, 0u, 0u, 0u};
+    MGTA_HIP_CHECK(hipMemcpyAsync(rc, &init, sizeof init, hipMemcpyHostToDevice, w.st));
+    MGTA_HIP_CHECK(hipMemsetAsync(unknown, 0, (size_t)m * 4, w.st));
+    const StampTab tab{b.stamp_key.as<unsigned long long>(), b.stamp_val.as<unsigned long long>(), (1ull << pl.stamp_log) - 1, (unsigned long long)(b.round + 1) << 40};
+    hipLaunchKernelGGL(bubble_reach_narrow_kernel, dim3((m + 64 / kNarrowLanes - 1) / (64 / kNarrowLanes)), dim3(64), 0, w.st, g, c, pos, m, max_len, b.scratch_p, kCandWords, tab,
+                       (unsigned long long)b.round, pl.reach_max, pl.narrow_max, rc, ok, unknown);
+    hipLaunchKernelGGL(bubble_reach_kernel, dim3(std::min<uint32_t>(m, 8192u)), dim3(kWideThreads), 0, w.st, g, c, pos, max_len, b.scratch_p, kCandWords, tab,
+                       (unsigned long long)b.round, pl.reach_max, rc, ok, unknown);
+    hipLaunchKernelGGL(bubble_check_kernel, dim3((m + 63) / 64), dim3(64), 0, w.st, g, c, m, max_len, b.scratch_p, kCandWords, tab, (unsigned long long)b.round, ok,
+                       &rc->barrier, unknown);
+    hipLaunchKernelGGL(bubble_commit_kernel, dim3((m + 63) / 64), dim3(64), 0, w.st, w.d, c, pos, m, max_len, b.scratch_p, kCandWords, ok, &rc->barrier,
+                       b.marked.as<unsigned long long>(), b.status.as<uint32_t>(), keep, &rc->n_done);
+    // the candidates beyond the cut stay pending, behind the ones this round keeps
+    if (shed) hipLaunchKernelGGL(fill_u32_kernel, dim3((shed + 255) / 256), dim3(256), 0, w.st, keep + m, shed, 1u);
+    exclusive_scan_u32(w.st, keep, mm, b.base.as<uint64_t>(), b.tmp.as<uint64_t>(), w.total.as<uint64_t>());
+    hipLaunchKernelGGL(window_keep_kernel, dim3((mm + 255) / 256), dim3(256), 0, w.st, c, pos, keep, b.base.as<uint64_t>(), mm, b.win[r.cur ^ 1].as<int64_t>(),
+                       b.pos[r.cur ^ 1].as<uint64_t>());
+    RoundCounters got;
+    MGTA_HIP_CHECK(hipMemcpyAsync(&got, rc, sizeof got, hipMemcpyDeviceToHost, w.st));
+    const uint32_t carried = (uint32_t)read_u64(w, w.total.p);
+    r.cur ^= 1;
+    if (got.n_crowded) ++b.n_crowded;
+    return RoundResult{m, mm - carried, carried, got.n_crowded != 0};
+}
+
+// The next round's size.  Windows shrink while the stamp table overflows (a crowded table holds back what it could not stamp: fewer
+// candidates share it next time) and grow back afterwards.  A round that committed little is followed by a small one whatever is pending:
+// behind a region that does not fit its scratch only the lowest candidates can commit, and a round costs what its window costs -- 500 M
+// reads spent 19 727 rounds of 40-86 k candidates committing a few hundred each.
+static void next_window(const RoundResult &rr, uint32_t window, Rounds &r) {
+    r.carry = rr.carried;
+    if (rr.crowded) r.cap = std::max<uint32_t>(1, rr.window / 2);
+    else if (r.cap < window) r.cap = std::min<uint32_t>(window, r.cap * 2);
+    if (rr.committed == 0 && !(rr.crowded && rr.window > 1)) { set_error("mgta_denovo: a bubble round committed nothing"); throw HipError{MGTA_EINTERNAL}; }   // the lowest always commits
+    r.want = std::min<uint32_t>(window, std::max<uint32_t>(std::min<uint32_t>(4096, window), 4 * std::max(rr.committed, 1u)));
+}
+
+// the ordered loop `for each candidate: Search, then Pop` (assembly_algorithms.cpp:266-279 and :283-292)
+static void pop_in_order(Work &w, BubbleWork &b, const DevBuf &cand, uint64_t n, int max_len, int64_t &n_rounds) {
+    Rounds r;
+    r.want = std::min<uint32_t>(4096, b.plan.window);
+    r.cap = b.plan.window;
+    while (r.carry > 0 || r.p < n) {
+        const RoundResult rr = run_round(w, b, cand, n, max_len, r);
+        ++n_rounds;
+        next_window(rr, b.plan.window, r);
+        if ((n_rounds & 15) == 1) note(w, "bubble round %lld: window %u, committed %u, %llu of %llu taken", (long long)n_rounds, rr.window, rr.committed, (unsigned long long)r.p, (unsigned long long)n);
+    }
+}
+
+// After a pass over `list`: counts its popped candidates (status 1) and, if asked, collects the ones whose Pop undid itself (status 2,
+// assembly_algorithms.cpp:273-277) for a second pass.
+static uint64_t tally(Work &w, BubbleWork &b, const DevBuf &list, uint64_t n, DevBuf *again) {
+    const dim3 grid((unsigned)((n + 255) / 256));
+    hipLaunchKernelGGL(flag_equals_kernel, grid, dim3(256), 0, w.st, b.status.as<uint32_t>(), n, 1u, b.flag.as<uint32_t>(), b.popped.as<unsigned long long>());
+    if (!again) return 0;
+    hipLaunchKernelGGL(flag_equals_kernel, grid, dim3(256), 0, w.st, b.status.as<uint32_t>(), n, 2u, b.flag.as<uint32_t>(), (unsigned long long *)nullptr);
+    return compact_list(w, list, b.flag, n, *again);
+}
+
+static uint64_t pop_bubbles(Work &w, int64_t &n_rounds, int64_t &n_candidates) {   // assembly_algorithms.cpp:245-301
+    const int max_len = w.d.g.k * 2 + 4;
+    BubbleWork b;
+    DevBuf cand, again;
+    const uint64_t nc = find_candidates(w, b, max_len, cand);
+    n_candidates = (int64_t)nc;
+    if (nc == 0) return 0;
+    alloc_bubble_work(w, b, nc);
     pop_in_order(w, b, cand, nc, max_len, n_rounds);
-    hipLaunchKernelGGL(flag_equals_kernel, dim3((unsigned)((nc + 255) / 256)), dim3(256), 0, w.st, b.status.as<uint32_t>(), nc, 1u, flag.as<uint32_t>(),
-                       counter.as<unsigned long long>());
-    hipLaunchKernelGGL(flag_equals_kernel, dim3((unsigned)((nc + 255) / 256)), dim3(256), 0, w.st, b.status.as<uint32_t>(), nc, 2u, flag.as<uint32_t>(),
-                       (unsigned long long *)nullptr);
-    const uint64_t na = compact_list(w, cand, flag, nc, again);
+    const uint64_t na = tally(w, b, cand, nc, &again);
     if (na) {
         pop_in_order(w, b, again, na, max_len, n_rounds);
-        hipLaunchKernelGGL(flag_equals_kernel, dim3((unsigned)((na + 255) / 256)), dim3(256), 0, w.st, b.status.as<uint32_t>(), na, 1u, flag.as<uint32_t>(),
-                           counter.as<unsigned long long>());
+        tally(w, b, again, na, nullptr);
     }
-    note(w, "bubbles: %lld rounds, the stamp table (2^%d slots) was crowded in %lld of them", (long long)n_rounds, stamp_log, (long long)b.n_crowded);
-    return read_u64(w, counter.p);
+    note(w, "bubbles: %lld rounds, the stamp table (2^%d slots) was crowded in %lld of them", (long long)n_rounds, b.plan.stamp_log, (long long)b.n_crowded);
+    return read_u64(w, b.popped.p);
 }
 
 struct Contigs {
@@ -1089,19 +1133,6 @@ static void unitigs(Work &w, int min_contig, Contigs &out) {
     emit_len.alloc(n * 4, w.live(), w.peak());
     hipLaunchKernelGGL(unitig_decide_kernel, dim3(grid64), dim3(64), 0, w.st, g, ends.as<int64_t>(), rec.as<PathRec>(), head.as<int64_t>(), state.as<uint32_t>(), n, min_contig,
                        emit_len.as<uint32_t>());
-    if (getenv("MGTA_DENOVO_DEBUG")) {      // the path table, for comparing with the oracle's model of this step
-        std::vector<PathRec> h(n);
-        std::vector<uint32_t> hs(n), he(n);
-        std::vector<int64_t> hend(n);
-        MGTA_HIP_CHECK(hipMemcpy(h.data(), rec.p, n * sizeof(PathRec), hipMemcpyDeviceToHost));
-        MGTA_HIP_CHECK(hipMemcpy(hs.data(), state.p, n * 4, hipMemcpyDeviceToHost));
-        MGTA_HIP_CHECK(hipMemcpy(he.data(), emit_len.p, n * 4, hipMemcpyDeviceToHost));
-        MGTA_HIP_CHECK(hipMemcpy(hend.data(), ends.p, n * 8, hipMemcpyDeviceToHost));
-        fprintf(stderr, "device: %llu paths\n", (unsigned long long)n);
-        for (uint64_t i = 0; i < n; ++i)
-            fprintf(stderr, "device p=%llu end=%lld start=%lld len=%u rc=%lld target=%lld dist=%u state=%u emit=%u\n", (unsigned long long)i, (long long)hend[i],
-                    (long long)h[i].start, h[i].length, (long long)h[i].rc_start, (long long)h[i].target, h[i].dist, hs[i], he[i] ? 1u : 0u);
-    }
     MGTA_HIP_CHECK(hipStreamSynchronize(w.st));
     head.release(); state.release();                                   // (only the records, the end edges and the verdicts are needed from here on)
     // the contigs leave in pieces of 2^25 paths: offsets, characters and records of one piece at a time
@@ -1138,6 +1169,57 @@ static void unitigs(Work &w, int min_contig, Contigs &out) {
     note(w, "unitigs: %zu contigs, %zu characters written", out.meta.size(), out.text.size());
 }
 
+// WriteContig, unitig_graph.cpp:134-150: ">k{K}_{id} flag={f} multi={%.4lf} len={L}\n{seq}\n", ids in emission order.  The headers are
+// formatted by several host threads (57.8 M of them took 16 s on one), each into its own piece of the text.  The contigs' characters
+// are released on the way out: the pieces hold them now.
+static std::vector<std::string> format_fasta(Contigs &c, int k) {
+    const size_t nc = c.meta.size();
+    const unsigned nt = (unsigned)std::max<size_t>(1, std::min<size_t>({(size_t)std::thread::hardware_concurrency(), (size_t)16, nc / 4096 + 1}));
+    std::vector<std::string> piece(nt);
+    std::vector<std::thread> th;
+    auto fmt = [&](unsigned t) {
+        const size_t i0 = nc * t / nt, i1 = nc * (t + 1) / nt;
+        std::string &o = piece[t];
+        size_t chars = 0;
+        for (size_t i = i0; i < i1; ++i) chars += c.meta[i].len;
+        o.reserve(chars + (i1 - i0) * 56);
+        char head[160];
+        for (size_t i = i0; i < i1; ++i) {
+            const ContigMeta &m = c.meta[i];
+            const double multi = std::min(65535.0, (double)m.depth / (double)m.length);
+            const int hl = snprintf(head, sizeof head, ">k%d_%lld flag=%d multi=%.4lf len=%d\n", k, (long long)(i + 1), m.flag, multi, (int)m.len);
+            o.append(head, (size_t)hl);
+            o.append(c.text.data() + m.offset, m.len);
+            o.push_back('\n');
+        }
+    };
+    struct Joiner { std::vector<std::thread> &th; ~Joiner() { for (auto &x : th) if (x.joinable()) x.join(); } } joiner{th};   // (also when a later thread cannot start)
+    for (unsigned t = 1; t < nt; ++t) th.emplace_back(fmt, t);
+    fmt(0);
+    for (auto &x : th) x.join();
+    std::vector<char>().swap(c.text);
+    return piece;
+}
+
+// the caller's buffer (mgta_host_free) and stats
+static int deliver(std::vector<std::string> &piece, const Contigs &c, mgta_denovo_stats &s, char **fasta, uint64_t *fasta_len, mgta_denovo_stats *stats) {
+    s.n_paths = c.n_paths;
+    s.n_unitig_sweeps = c.n_sweeps;
+    s.n_contigs = (int64_t)c.meta.size();
+    for (const ContigMeta &m : c.meta) s.total_len += m.len;
+    size_t total = 0;
+    for (const std::string &o : piece) total += o.size();
+    char *buf = (char *)malloc(total + 1);
+    if (!buf) { set_error("mgta_denovo: out of host memory"); return MGTA_ENOMEM; }
+    size_t at = 0;
+    for (std::string &o : piece) { memcpy(buf + at, o.data(), o.size()); at += o.size(); std::string().swap(o); }
+    buf[total] = 0;
+    *fasta = buf;
+    *fasta_len = total;
+    if (stats) *stats = s;
+    return MGTA_OK;
+}
+
 }  // namespace
 }  // namespace mgta
 
@@ -1149,89 +1231,31 @@ int mgta_denovo(mgta_sdbg *graph, int max_tip_len, int no_bubble, int min_contig
     if (!graph || !fasta || !fasta_len) { set_error("mgta_denovo: bad argument"); return MGTA_EINVAL; }
     if (graph->dev.k > kMaxK) { set_error("mgta_denovo: k = %d > %d", graph->dev.k, kMaxK); return MGTA_EUNSUPPORTED; }
     *fasta = nullptr; *fasta_len = 0;
-    mgta_denovo_stats s;
-    memset(&s, 0, sizeof s);
-    try {
-        mgta_ctx *ctx = graph->ctx;
-        MGTA_HIP_CHECK(hipSetDevice(ctx->device));
-        Work w;
-        w.ctx = ctx; w.st = ctx->stream;
-        w.d.g = graph->dev;
-        w.d.rw = graph->lines.as<GLine>();
-        const GraphDev &g = w.d.g;
-        if (g.size > 0) {
-            w.mask.alloc((g.n_lines + 1) * 8, w.live(), w.peak());
-            w.count.alloc((g.n_lines + 1) * 4, w.live(), w.peak());
-            w.base.alloc((g.n_lines + 1) * 8, w.live(), w.peak());
-            w.tmp.alloc(scan_tmp_elems(g.n_lines) * 8, w.live(), w.peak());
-            w.total.alloc(64, w.live(), w.peak());
-            hipEvent_t ev[4];
-            for (auto &e : ev) MGTA_HIP_CHECK(hipEventCreate(&e));
-            MGTA_HIP_CHECK(hipEventRecord(ev[0], w.st));
-            if (max_tip_len == -1) max_tip_len = g.k * 2;                           // assembler.cpp:125-127
-            note(w, "%lld edges", (long long)g.size);
+    return guarded("mgta_denovo", [&]() -> int {
+        MGTA_HIP_CHECK(hipSetDevice(graph->ctx->device));
+        mgta_denovo_stats s;
+        memset(&s, 0, sizeof s);
+        Contigs c;
+        if (graph->dev.size > 0) {                                                  // (an empty graph: no contigs, delivered like any others)
+            Work w(graph);
+            Timer t_tips(w.st), t_bubbles(w.st), t_unitigs(w.st);
+            if (max_tip_len == -1) max_tip_len = w.d.g.k * 2;                       // assembler.cpp:125-127
+            note(w, "%lld edges", (long long)w.d.g.size);
+            t_tips.start();
             if (max_tip_len > 0) s.n_tips = (int64_t)remove_tips(w, max_tip_len);
-            MGTA_HIP_CHECK(hipEventRecord(ev[1], w.st));
+            t_tips.end();
+            t_bubbles.start();
             if (!no_bubble) s.n_bubbles = (int64_t)pop_bubbles(w, s.n_bubble_rounds, s.n_bubble_candidates);
-            MGTA_HIP_CHECK(hipEventRecord(ev[2], w.st));
-            Contigs c;
+            t_bubbles.end();
+            t_unitigs.start();
             unitigs(w, min_contig, c);
-            MGTA_HIP_CHECK(hipEventRecord(ev[3], w.st));
-            MGTA_HIP_CHECK(hipEventSynchronize(ev[3]));
-            MGTA_HIP_CHECK(hipEventElapsedTime(&s.ms_tips, ev[0], ev[1]));
-            MGTA_HIP_CHECK(hipEventElapsedTime(&s.ms_bubbles, ev[1], ev[2]));
-            MGTA_HIP_CHECK(hipEventElapsedTime(&s.ms_unitigs, ev[2], ev[3]));
-            for (auto &e : ev) (void)hipEventDestroy(e);
-            s.n_paths = c.n_paths;
-            s.n_unitig_sweeps = c.n_sweeps;
-            s.n_contigs = (int64_t)c.meta.size();
-            // WriteContig, unitig_graph.cpp:134-150: ">k{K}_{id} flag={f} multi={%.4lf} len={L}\n{seq}\n", ids in emission order.  The
-            // headers are formatted by several host threads (57.8 M of them took 16 s on one), each into its own piece of the text.
-            const size_t nc = c.meta.size();
-            const unsigned nt = (unsigned)std::max<size_t>(1, std::min<size_t>({(size_t)std::thread::hardware_concurrency(), (size_t)16, nc / 4096 + 1}));
-            std::vector<std::string> piece(nt);
-            std::vector<std::thread> th;
-            auto fmt = [&](unsigned t) {
-                const size_t i0 = nc * t / nt, i1 = nc * (t + 1) / nt;
-                std::string &o = piece[t];
-                size_t chars = 0;
-                for (size_t i = i0; i < i1; ++i) chars += c.meta[i].len;
-                o.reserve(chars + (i1 - i0) * 56);
-                char head[160];
-                for (size_t i = i0; i < i1; ++i) {
-                    const ContigMeta &m = c.meta[i];
-                    const double multi = std::min(65535.0, (double)m.depth / (double)m.length);
-                    const int hl = snprintf(head, sizeof head, ">k%d_%lld flag=%d multi=%.4lf len=%d\n", g.k, (long long)(i + 1), m.flag, multi, (int)m.len);
-                    o.append(head, (size_t)hl);
-                    o.append(c.text.data() + m.offset, m.len);
-                    o.push_back('\n');
-                }
-            };
-            for (unsigned t = 1; t < nt; ++t) th.emplace_back(fmt, t);
-            fmt(0);
-            for (auto &x : th) x.join();
-            for (const ContigMeta &m : c.meta) s.total_len += m.len;
-            std::vector<char>().swap(c.text);
-            size_t total = 0;
-            for (const std::string &o : piece) total += o.size();
-            char *buf = (char *)malloc(total + 1);
-            if (!buf) { set_error("mgta_denovo: out of host memory"); return MGTA_ENOMEM; }
-            size_t at = 0;
-            for (std::string &o : piece) { memcpy(buf + at, o.data(), o.size()); at += o.size(); std::string().swap(o); }
-            buf[total] = 0;
-            *fasta = buf;
-            *fasta_len = total;
-            if (stats) *stats = s;
-            return MGTA_OK;
+            t_unitigs.end();
+            MGTA_HIP_CHECK(hipEventSynchronize(t_unitigs.b));
+            s.ms_tips = t_tips.ms(); s.ms_bubbles = t_bubbles.ms(); s.ms_unitigs = t_unitigs.ms();
         }
-        char *buf = (char *)malloc(1);
-        if (!buf) { set_error("mgta_denovo: out of host memory"); return MGTA_ENOMEM; }
-        buf[0] = 0;
-        *fasta = buf;
-        *fasta_len = 0;
-        if (stats) *stats = s;
-        return MGTA_OK;
-    } catch (const HipError &e) { return e.code; }
+        std::vector<std::string> piece = format_fasta(c, graph->dev.k);
+        return deliver(piece, c, s, fasta, fasta_len, stats);
+    });
 }
 
 void mgta_host_free(void *p) { free(p); }

@@ -184,7 +184,7 @@ extern "C" int mgta_findstart(mgta_ctx *ctx, const mgta_reads *reads, int reads_
         set_error("mgta_findstart: k = %d (a multiple of 3 in [9, 72] is required: k/3 residues, at most 24)", k);
         return MGTA_EINVAL;
     }
-    try {
+    return guarded("mgta_findstart", [&]() -> int {
         MGTA_HIP_CHECK(hipSetDevice(ctx->device));
         hipStream_t st = ctx->stream;
         const int kaa = k / 3, n0 = kaa < 12 ? kaa : 12;
@@ -228,23 +228,18 @@ extern "C" int mgta_findstart(mgta_ctx *ctx, const mgta_reads *reads, int reads_
         a.tab = d_tab.as<unsigned long long>(); a.tab_ref = d_ref.as<int32_t>(); a.tab_mask = (uint32_t)(tcap - 1);
         a.filter = d_filter.as<uint32_t>();
         a.hits = d_hits.as<mgta_seed_hit>(); a.n_hits = d_cnt.as<unsigned long long>(); a.cap = (uint64_t)cap;
-        hipEvent_t e0, e1;
-        MGTA_HIP_CHECK(hipEventCreate(&e0));
-        MGTA_HIP_CHECK(hipEventCreate(&e1));
-        MGTA_HIP_CHECK(hipEventRecord(e0, st));
+        Timer t(st);
+        t.start();
         const uint64_t n_blocks = (reads->n_reads + kFsReadsPerBlock - 1) / kFsReadsPerBlock;
         if (n_blocks) hipLaunchKernelGGL(findstart_kernel, dim3((unsigned)n_blocks), dim3(kFsBlock), 0, st, a);
-        MGTA_HIP_CHECK(hipEventRecord(e1, st));
+        t.end();
         unsigned long long n = 0;
         MGTA_HIP_CHECK(hipMemcpyAsync(&n, d_cnt.p, 8, hipMemcpyDeviceToHost, st));
         MGTA_HIP_CHECK(hipStreamSynchronize(st));
-        float ms = 0;
-        MGTA_HIP_CHECK(hipEventElapsedTime(&ms, e0, e1));
-        (void)hipEventDestroy(e0); (void)hipEventDestroy(e1);
-        if (ms_kernel) *ms_kernel = ms;
+        if (ms_kernel) *ms_kernel = t.ms();
         *n_hits = (int64_t)n;
         const uint64_t got = std::min<uint64_t>(n, (uint64_t)cap);
         if (got) MGTA_HIP_CHECK(hipMemcpy(hits, d_hits.p, got * sizeof(mgta_seed_hit), hipMemcpyDeviceToHost));
         return MGTA_OK;
-    } catch (const HipError &e) { return e.code; }
+    });
 }

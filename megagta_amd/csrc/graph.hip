@@ -302,7 +302,7 @@ static int graph_finish(GraphBuild &B, mgta_sdbg **out) {
 static int load_graph(mgta_ctx *ctx, int k, const uint16_t *recs, int64_t size, const int64_t *bucket_items, const uint32_t *tips,
                       int64_t n_tip_words, int words_per_tip, bool resident, mgta_sdbg **out, DevBuf *recs_owner = nullptr,
                       const uint16_t *large = nullptr, int64_t n_large = 0) {
-    try {
+    return guarded("mgta_sdbg_load", [&]() -> int {
         GraphBuild B;
         const int rc = graph_begin(ctx, k, size, bucket_items, tips, n_tip_words, words_per_tip, resident, B, nullptr, n_large);
         if (rc != MGTA_OK) return rc;
@@ -325,7 +325,7 @@ static int load_graph(mgta_ctx *ctx, int k, const uint16_t *recs, int64_t size, 
             }
         }
         return graph_finish(B, out);
-    } catch (const HipError &e) { return e.code; }
+    });
 }
 
 int mgta_sdbg_load(mgta_ctx *ctx, int k, const uint16_t *recs, int64_t size, const int64_t *bucket_items, const uint32_t *tips,
@@ -362,7 +362,7 @@ int mgta_sdbg_load_files(mgta_ctx *ctx, const char *prefix_c, mgta_sdbg **out) {
                      for (void *q : pin) if (q) (void)hipHostFree(q);
                      for (hipEvent_t e : ev) if (e) (void)hipEventDestroy(e); }
     } cleanup{files};
-    try {
+    return guarded("mgta_sdbg_load_files", [&]() -> int {
         FILE *info = fopen((prefix + ".sdbg_info").c_str(), "r");
         if (!info) { set_error("cannot open %s.sdbg_info", prefix.c_str()); return MGTA_EINVAL; }
         int k = 0, wpt = 0, nb = 0, nf = 0;
@@ -534,7 +534,7 @@ int mgta_sdbg_load_files(mgta_ctx *ctx, const char *prefix_c, mgta_sdbg **out) {
         if (bad) { set_error("%s: %u buckets do not parse to the sizes the index gives", prefix.c_str(), bad); return MGTA_EINVAL; }
         if (getenv("MGTA_LOAD_VERBOSE")) fprintf(stderr, "[load] %lld records in %d range(s) of <= %llu\n", total, n_ranges, (unsigned long long)range);
         return graph_finish(B, out);
-    } catch (const HipError &e) { return e.code; }
+    });
 }
 
 // ---- the whole edge stream of a keep-stream build, taken out of the context: it stays in device memory until it is freed, and a host
@@ -550,7 +550,7 @@ struct mgta_stream {
 int mgta_sdbg_stream_detach(mgta_ctx *ctx, mgta_stream **out) {
     if (!ctx || !out) { set_error("mgta_sdbg_stream_detach: bad argument"); return MGTA_EINVAL; }
     if (!ctx->acc_valid) { set_error("mgta_sdbg_stream_detach: the last build did not keep its whole stream (mgta_ctx_keep_stream)"); return MGTA_EINVAL; }
-    try {
+    return guarded("mgta_sdbg_stream_detach", [&]() -> int {
         MGTA_HIP_CHECK(hipSetDevice(ctx->device));
         MGTA_HIP_CHECK(hipStreamSynchronize(ctx->stream));
         auto st = std::make_unique<mgta_stream>();
@@ -563,7 +563,7 @@ int mgta_sdbg_stream_detach(mgta_ctx *ctx, mgta_stream **out) {
         ctx_retain(ctx);
         *out = st.release();
         return MGTA_OK;
-    } catch (const HipError &e) { return e.code; }
+    });
 }
 
 int mgta_stream_sizes(const mgta_stream *s, uint64_t *n_recs, uint64_t *n_tip_words) {
@@ -579,8 +579,7 @@ int mgta_stream_download(mgta_stream *s, uint16_t *recs, uint32_t *tips) {
     hipStream_t st = nullptr;
     void *stage[2] = {nullptr, nullptr};
     hipEvent_t ev[2] = {nullptr, nullptr};
-    int rc = MGTA_OK;
-    try {
+    const int rc = guarded("mgta_stream_download", [&]() -> int {
         MGTA_HIP_CHECK(hipSetDevice(s->device));
         MGTA_HIP_CHECK(hipStreamCreateWithFlags(&st, hipStreamNonBlocking));
         const size_t piece = 128ull << 20;
@@ -601,7 +600,8 @@ int mgta_stream_download(mgta_stream *s, uint16_t *recs, uint32_t *tips) {
                 memcpy(pt.dst + i * piece, stage[i & 1], std::min(piece, pt.bytes - i * piece));
             }
         }
-    } catch (const HipError &e) { rc = e.code; }
+        return MGTA_OK;
+    });
     for (int i = 0; i < 2; ++i) { if (stage[i]) (void)hipHostFree(stage[i]); if (ev[i]) (void)hipEventDestroy(ev[i]); }
     if (st) (void)hipStreamDestroy(st);
     return rc;
@@ -629,7 +629,7 @@ int mgta_sdbg_load_resident(mgta_ctx *ctx, mgta_sdbg **out) {
                   "(set the switch before the build, or load the graph from its files)");
         return MGTA_EUNSUPPORTED;
     }
-    try {
+    return guarded("mgta_sdbg_load_resident", [&]() -> int {
         MGTA_HIP_CHECK(hipSetDevice(ctx->device));
         if (ctx->acc_valid) {    // the build's key buffers (grow-only pool) are scratch; a graph of tens of billions of edges needs their room
             size_t free_b = 0, total_b = 0;
@@ -691,7 +691,7 @@ int mgta_sdbg_load_resident(mgta_ctx *ctx, mgta_sdbg **out) {
         return load_graph(ctx, ctx->last_k, static_cast<const uint16_t *>(ctx->last_rec), (int64_t)ctx->last_n_rec, items.data(),
                           static_cast<const uint32_t *>(ctx->last_tips), (int64_t)ctx->last_n_tips * ctx->last_words_per_tip,
                           ctx->last_words_per_tip, true, out, nullptr, d_large, n_large);
-    } catch (const HipError &e) { return e.code; }
+    });
 }
 
 void mgta_sdbg_free(mgta_sdbg *g) {
@@ -708,7 +708,7 @@ int mgta_sdbg_outgoing(mgta_sdbg *g, const int64_t *edges, int64_t n, int64_t *o
     for (int64_t i = 0; i < n; ++i)
         if (edges[i] < 0 || edges[i] >= g->dev.size) { set_error("edge id %lld out of range", (long long)edges[i]); return MGTA_EINVAL; }
     if (n == 0) return MGTA_OK;
-    try {
+    return guarded("mgta_sdbg_outgoing", [&]() -> int {
         mgta_ctx *ctx = g->ctx;
         MGTA_HIP_CHECK(hipSetDevice(ctx->device));
         DevBuf d_e, d_o, d_d;
@@ -720,13 +720,13 @@ int mgta_sdbg_outgoing(mgta_sdbg *g, const int64_t *edges, int64_t n, int64_t *o
         MGTA_HIP_CHECK(hipMemcpyAsync(outdeg, d_d.p, n, hipMemcpyDeviceToHost, ctx->stream));
         MGTA_HIP_CHECK(hipStreamSynchronize(ctx->stream));
         return MGTA_OK;
-    } catch (const HipError &e) { return e.code; }
+    });
 }
 
 int mgta_sdbg_invalid_bits(mgta_sdbg *g, uint64_t *words) {
     if (!g || !words) { set_error("mgta_sdbg_invalid_bits: bad argument"); return MGTA_EINVAL; }
     if (g->dev.size == 0) return MGTA_OK;
-    try {
+    return guarded("mgta_sdbg_invalid_bits", [&]() -> int {
         mgta_ctx *ctx = g->ctx;
         MGTA_HIP_CHECK(hipSetDevice(ctx->device));
         const uint64_t n = g->dev.n_lines;
@@ -736,13 +736,13 @@ int mgta_sdbg_invalid_bits(mgta_sdbg *g, uint64_t *words) {
         MGTA_HIP_CHECK(hipMemcpyAsync(words, d.p, n * 8, hipMemcpyDeviceToHost, ctx->stream));
         MGTA_HIP_CHECK(hipStreamSynchronize(ctx->stream));
         return MGTA_OK;
-    } catch (const HipError &e) { return e.code; }
+    });
 }
 
 int mgta_sdbg_index_edges(mgta_sdbg *g, const uint8_t *seqs, int64_t n, int64_t *edge_ids) {
     if (!g || n < 0 || (n > 0 && (!seqs || !edge_ids))) { set_error("mgta_sdbg_index_edges: bad argument"); return MGTA_EINVAL; }
     if (n == 0) return MGTA_OK;
-    try {
+    return guarded("mgta_sdbg_index_edges", [&]() -> int {
         mgta_ctx *ctx = g->ctx;
         MGTA_HIP_CHECK(hipSetDevice(ctx->device));
         size_t sb = (size_t)n * (g->dev.k + 1);
@@ -757,7 +757,7 @@ int mgta_sdbg_index_edges(mgta_sdbg *g, const uint8_t *seqs, int64_t n, int64_t 
         MGTA_HIP_CHECK(hipMemcpyAsync(edge_ids, d_i.p, n * 8, hipMemcpyDeviceToHost, ctx->stream));
         MGTA_HIP_CHECK(hipStreamSynchronize(ctx->stream));
         return MGTA_OK;
-    } catch (const HipError &e) { return e.code; }
+    });
 }
 
 }  // extern "C"

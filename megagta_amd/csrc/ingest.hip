@@ -44,7 +44,7 @@ extern "C" int mgta_reads_pack_text(mgta_ctx *ctx, const char *text, uint64_t n_
                                     uint32_t *bin_words, uint64_t capacity_words, uint64_t *n_words_out) {
     if (!ctx || !offsets || !n_words_out || (n_bytes && !text) || (capacity_words && !bin_words)) { set_error("mgta_reads_pack_text: bad argument"); return MGTA_EINVAL; }
     if (offsets[0] != 0 || offsets[n_reads] != n_bytes) { set_error("mgta_reads_pack_text: offsets must run from 0 to n_bytes"); return MGTA_EINVAL; }
-    try {
+    return guarded("mgta_reads_pack_text", [&]() -> int {
         MGTA_HIP_CHECK(hipSetDevice(ctx->device));
         hipStream_t st = ctx->stream;
         std::vector<uint64_t> out_off(n_reads + 1);
@@ -73,5 +73,5 @@ extern "C" int mgta_reads_pack_text(mgta_ctx *ctx, const char *text, uint64_t n_
         MGTA_HIP_CHECK(hipMemcpyAsync(bin_words, d_out.p, acc * 4, hipMemcpyDeviceToHost, st));
         MGTA_HIP_CHECK(hipStreamSynchronize(st));
         return MGTA_OK;
-    } catch (const HipError &e) { return e.code; }
+    });
 }

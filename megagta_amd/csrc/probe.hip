@@ -86,7 +86,7 @@ extern "C" int mgta_probe_random_lines(mgta_ctx *ctx, uint64_t table_bytes, mgta
             return MGTA_EINVAL;
         }
     }
-    try {
+    return guarded("mgta_probe_random_lines", [&]() -> int {
         MGTA_HIP_CHECK(hipSetDevice(ctx->device));
         hipStream_t st = ctx->stream;
         const uint64_t n_lines = table_bytes / 128;
@@ -96,9 +96,8 @@ extern "C" int mgta_probe_random_lines(mgta_ctx *ctx, uint64_t table_bytes, mgta
         MGTA_HIP_CHECK(hipMemsetAsync(sink.p, 0, 8, st));
         hipLaunchKernelGGL(probe_fill_kernel, dim3(ctx->num_cus * 8), dim3(256), 0, st, tab.as<uint4>(), n_lines);
         MGTA_HIP_CHECK(hipGetLastError());
-        hipEvent_t e0, e1;
-        MGTA_HIP_CHECK(hipEventCreate(&e0));
-        MGTA_HIP_CHECK(hipEventCreate(&e1));
+        const Timer t(st);                                              // (its two events; recorded below without throwing: this call has an error text of its own)
+        const hipEvent_t e0 = t.a, e1 = t.b;
         int rc = MGTA_OK;
         for (int i = 0; i < n_cfg && rc == MGTA_OK; ++i) {
             mgta_line_probe &c = cfg[i];
@@ -123,7 +122,6 @@ extern "C" int mgta_probe_random_lines(mgta_ctx *ctx, uint64_t table_bytes, mgta
             c.gb_per_s = ms > 0 ? (double)c.lines * 128.0 / (ms * 1e6) : 0.0;
             c.ns_per_step = ms > 0 ? (double)ms * 1e6 / (double)c.steps : 0.0;
         }
-        (void)hipEventDestroy(e0); (void)hipEventDestroy(e1);
         return rc;
-    } catch (const HipError &e) { return e.code; }
+    });
 }

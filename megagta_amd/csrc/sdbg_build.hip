@@ -1715,24 +1715,6 @@ namespace mgta {
 // ---------------------------------------------------------------------------------------------
 // host orchestration
 // ---------------------------------------------------------------------------------------------
-struct Timer {                   // owns its two events
-    hipEvent_t a = nullptr, b = nullptr;
-    hipStream_t st;
-    explicit Timer(hipStream_t s) : st(s) { MGTA_HIP_CHECK(hipEventCreate(&a)); MGTA_HIP_CHECK(hipEventCreate(&b)); }
-    Timer(Timer &&o) noexcept : a(o.a), b(o.b), st(o.st) { o.a = o.b = nullptr; }
-    ~Timer() { if (a) (void)hipEventDestroy(a); if (b) (void)hipEventDestroy(b); }
-    void start() { MGTA_HIP_CHECK(hipEventRecord(a, st)); }
-    void end() { MGTA_HIP_CHECK(hipEventRecord(b, st)); }        // without waiting: ms() once the stream is past it
-    float ms() const { float t = 0; MGTA_HIP_CHECK(hipEventElapsedTime(&t, a, b)); return t; }
-    double stop() {   // milliseconds, synchronises; a launch the runtime rejected inside the phase (grid or LDS limits) surfaces here
-        MGTA_HIP_CHECK(hipGetLastError());
-        end();
-        MGTA_HIP_CHECK(hipEventSynchronize(b));
-        MGTA_HIP_CHECK(hipGetLastError());
-        return ms();
-    }
-};
-
 // digits of the bits below 32W - T (T = prefix bits the global passes sorted on), least significant first (flags, then characters; the zero pad is skipped)
 static std::vector<Digit> low_digit_plan(int k, int W, int T) {
     std::vector<Digit> plan;

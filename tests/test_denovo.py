@@ -98,13 +98,19 @@ def test_device_vs_oracle_seeded(ctx, oracle, seed):
         assert (gst["n_tips"], gst["n_bubbles"], gst["n_contigs"], gst["total_len"]) == (wst["n_tips"], wst["n_bubbles"], wst["n_contigs"], wst["total_len"])
 
 
+@pytest.fixture(scope="module")
+def dense_snp_stream(oracle):
+    """variants closer than k (the input of the ordered-rounds tests), built once"""
+    reads = synth.make_strain_mix(77, n_genomes=6, genome_len=4000, snp_every=18, cov=30)
+    return _oracle_stream(oracle, reads, 21, 2)
+
+
 @pytest.mark.gpu
-def test_device_ordered_rounds(ctx, oracle):
+def test_device_ordered_rounds(ctx, oracle, dense_snp_stream):
     """variants closer than k: bubble candidates whose searches read each other's edges, so the window is cut at the first one that lost a
     stamp and popping takes several ordered rounds; the result is still the sequential loop's"""
     from megagta_amd import api
-    reads = synth.make_strain_mix(77, n_genomes=6, genome_len=4000, snp_every=18, cov=30)
-    st = _oracle_stream(oracle, reads, 21, 2)
+    st = dense_snp_stream
     want, wst = oracle.Graph(st).denovo(150, False, 0)
     got, gst = api.Graph(ctx, st.edges()).denovo(150, False, 0)
     assert got == want and gst["n_bubbles"] == wst["n_bubbles"] > 50
@@ -129,6 +135,32 @@ def test_device_ordered_rounds(ctx, oracle):
         finally:
             del os.environ["MGTA_DENOVO_NARROW_MAX"]
         assert got3 == want and gst3["n_bubbles"] == wst["n_bubbles"] and gst3["n_bubble_rounds"] == gst["n_bubble_rounds"], value
+
+
+ROUND_STATS = ("n_tips", "n_bubbles", "n_bubble_candidates", "n_bubble_rounds", "n_paths", "n_unitig_sweeps")
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("setting", ["default", "MGTA_DENOVO_WINDOW=64", "MGTA_DENOVO_REACH_MAX=8", "MGTA_DENOVO_NARROW_MAX=2", "MGTA_DENOVO_NARROW_MAX=24"])
+def test_device_round_stats_pinned(golden_dir, ctx, dense_snp_stream, setting):
+    """the window policy, which the contigs cannot show: candidates, rounds, paths and sweeps are the ones recorded in
+    tests/golden/denovo/round_stats.json (two runs of the commit before the host driver was split into stages agreed on every value; at
+    this size the window is the 4096 floor whatever memory is free).  The two MGTA_DENOVO_STAMP_LOG2 settings are left out: which
+    candidate a crowded table turns away depends on the order of racing inserts"""
+    from megagta_amd import api
+    with open(os.path.join(golden_dir, "denovo", "round_stats.json")) as f:
+        want = json.load(f)[setting]
+    knob, _, value = setting.partition("=")
+    if value:
+        os.environ[knob] = value
+    try:
+        _, gst = api.Graph(ctx, dense_snp_stream.edges()).denovo(150, False, 0)
+    finally:
+        if value:
+            del os.environ[knob]
+    got = {key: gst[key] for key in ROUND_STATS}
+    print(setting, got)
+    assert got == want
 
 
 @pytest.mark.gpu
