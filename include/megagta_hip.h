@@ -262,6 +262,36 @@ int mgta_contig_coverage(mgta_sdbg *, const char *seqs, const uint64_t *offsets 
                          uint16_t *per_window /* optional */, int64_t *abundance /* optional, [65536] */, mgta_coverage_stats *stats /* optional */);
 
 /* ------------------------------------------------------------------------------------------------
+ * Read recruitment (the `-m proc_match_reads.fa` output of the same `kmer_coverage` command line, bin/post_proc.sh:113-118): which reads
+ * of the library share a (k+1)-mer with a set of contigs.  Contigs as in mgta_contig_coverage; reads as uploaded for the build
+ * (reads_reversed as in mgta_findstart: one upload serves buildgraph, findstart and this).  Every WINDOW of a contig, as given AND
+ * reverse-complemented, marks the edge IndexBinarySearchEdge finds for it: nothing when there is none, nothing when it holds a letter
+ * other than A, C, G, T (no N -> G folding).  Window p of read r HITS iff the edge found for its k + 1 bases is marked (the validity
+ * bit is not looked at, as for the coverage windows).  hit_windows[r] (may be NULL) = the number of hitting windows; bit r of
+ * match_bits[r / 64] = at least one window of read r hits.  A read shorter than k + 1 has no windows.  Only the reads
+ * [0, n_short_reads) are scanned and have a bit (the rest are the assist sequences of a multi-k library).  On a `-m 1` graph of these
+ * very reads a hit is plain equality of (k+1)-mers on either strand.  With hit_windows = NULL the walk of a read ends at its first
+ * hit.  Works on any loaded graph (no multiplicities needed, none allocated); uses the graph's mark bits, cleared at the start of the
+ * call like mgta_contig_coverage's, so the two never see each other's marks.  One call = one set of contigs.  n = 0 or
+ * n_short_reads = 0: match_bits all zero, stats all zero.  Every output and every stats field but ms_* is a function of (graph,
+ * contigs, reads) only.  MGTA_EINVAL: NULL graph / reads / match_bits, n_short_reads > the reads uploaded, graph and reads of
+ * different contexts.
+ * ------------------------------------------------------------------------------------------------ */
+typedef struct mgta_match_stats {
+    int64_t n_contigs, n_contig_windows;   /* windows of the contigs as given (the reverse complements double the work, not this number) */
+    int64_t n_marked_edges;                /* distinct edges the contigs turned on, both strands together */
+    int64_t n_reads, n_read_windows;       /* sum max(0, len - k) over the reads scanned */
+    int64_t n_walked, n_index_searches;    /* read windows found by one forward step / by IndexBinarySearchEdge */
+    int64_t n_matched_reads;
+    int64_t groups_per_cu;                 /* as in mgta_coverage_stats, for the read walk */
+    double ms_mark, ms_walk;               /* HIP events */
+} mgta_match_stats;
+int mgta_reads_match_contigs(mgta_sdbg *, const mgta_reads *reads, int reads_reversed, uint64_t n_short_reads,
+                             const char *seqs, const uint64_t *offsets /* [n + 1] */, int64_t n,
+                             uint64_t *match_bits /* [ceil(n_short_reads / 64)], bit r of word r / 64 */,
+                             uint32_t *hit_windows /* optional [n_short_reads] */, mgta_match_stats *stats /* optional */);
+
+/* ------------------------------------------------------------------------------------------------
  * Seed finder (replaces the read scan of `megagta findstart`, fast_kmer_filter.cpp:108-176,193-215):
  * every window of k nucleotides (k a multiple of 3, k/3 <= 24) of every read, on both strands, whose translation is one of
  * the n_ref reference words.  A word = its residues in the code of prot_kmer.h:31-43 (ARNDCQEGHILKMFPSTWYV = 0..19, '*' = 20),

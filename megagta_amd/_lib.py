@@ -80,6 +80,15 @@ class CoverageStats(C.Structure):
         return {n: getattr(self, n) for n, _ in self._fields_}
 
 
+class MatchStats(C.Structure):
+    _fields_ = [("n_contigs", C.c_int64), ("n_contig_windows", C.c_int64), ("n_marked_edges", C.c_int64), ("n_reads", C.c_int64),
+                ("n_read_windows", C.c_int64), ("n_walked", C.c_int64), ("n_index_searches", C.c_int64), ("n_matched_reads", C.c_int64),
+                ("groups_per_cu", C.c_int64), ("ms_mark", C.c_double), ("ms_walk", C.c_double)]
+
+    def as_dict(self):
+        return {n: getattr(self, n) for n, _ in self._fields_}
+
+
 EDGE_SINK = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_int32, C.c_int32, C.POINTER(C.c_int64), C.POINTER(C.c_uint16), C.c_int64,
                         C.POINTER(C.c_uint16), C.c_int64, C.POINTER(C.c_uint32), C.c_int64)
 CONTIG_SINK = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_void_p, C.c_int64,
@@ -135,6 +144,8 @@ SYMBOLS = {
                                       C.POINTER(C.c_void_p)]),
     "mgta_sdbg_edge_multiplicity": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p]),
     "mgta_contig_coverage": (C.c_int, [C.c_void_p, C.c_char_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "mgta_reads_match_contigs": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_uint64, C.c_char_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p,
+                                          C.c_void_p]),
     "mgta_sdbg_free": (None, [C.c_void_p]),
     "mgta_sdbg_size": (C.c_int64, [C.c_void_p]),
     "mgta_sdbg_outgoing": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p]),

@@ -307,6 +307,25 @@ class Graph:
             out["per_window"], out["window_offsets"] = pw, woff
         return out
 
+    def match_reads(self, reads: "Reads", seqs, n_short_reads: int | None = None, counts: bool = False, reads_reversed: bool = True) -> dict:
+        """mgta_reads_match_contigs: which of the first n_short_reads reads (default: all of `reads`) share a (k+1)-mer with the contigs
+        `seqs` (str or bytes, any case), on either strand.  -> dict(bits = bool[n_short_reads], hit_windows = None, or with counts=True
+        uint32[n_short_reads] hitting windows per read, stats).  Without counts the walk of a read ends at its first hit.  Any loaded
+        graph will do (no multiplicities needed); one call = one set of contigs."""
+        raw = [s if isinstance(s, (bytes, bytearray)) else str(s).encode() for s in seqs]
+        n = len(raw)
+        offsets = np.zeros(n + 1, dtype=np.uint64)
+        if n:
+            np.cumsum([len(s) for s in raw], out=offsets[1:])
+        ns = reads.n_reads if n_short_reads is None else int(n_short_reads)
+        words = np.zeros(max(1, (ns + 63) // 64), dtype=np.uint64)          # (never an empty buffer: NULL is an error of its own)
+        hits = np.zeros(ns, dtype=np.uint32) if counts else None
+        st = _lib.MatchStats()
+        check(self.ctx._L.mgta_reads_match_contigs(self.h, reads.h, int(bool(reads_reversed)), ns, b"".join(raw), offsets.ctypes.data, n, words.ctypes.data,
+                                                   hits.ctypes.data if counts and ns else None, C.byref(st)), "mgta_reads_match_contigs")
+        bits = np.unpackbits(words.view(np.uint8), bitorder="little")[:ns].astype(bool)
+        return dict(bits=bits, hit_windows=hits, stats=st.as_dict())
+
     def denovo(self, max_tip_len: int = 150, no_bubble: bool = False, min_contig: int = 0) -> tuple[str, dict]:
         """`megagta denovo` (main_assemble, assembler.cpp:98-167): tips, bubbles, unitigs -> (text of PREFIX.contigs.fa, stats).
         The result is the reference's one-thread output.  CONSUMES the validity bits of this graph."""

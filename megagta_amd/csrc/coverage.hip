@@ -1,4 +1,5 @@
-// coverage.hip — per-contig k-mer coverage and abundance from the resident graph, and the batched EdgeMultiplicity query.
+// coverage.hip — per-contig k-mer coverage and abundance from the resident graph, the batched EdgeMultiplicity query, and read
+// recruitment (the reads that share a (k+1)-mer with a set of contigs: the same walk, over reads; further down).
 //
 // The reference's last post-processing step (`kmer_coverage`, bin/post_proc.sh:113-118) counts the (k+1)-mers of the contigs in a
 // second pass over all reads.  That count is the multiplicity the edge stream already carries (sdbg_multi_io.h:83-112) and a graph
@@ -255,6 +256,138 @@ uint16_t *window_scratch(mgta_ctx *ctx, uint64_t bytes) {
     return b.as<uint16_t>();
 }
 
+// ---- read recruitment (mgta_reads_match_contigs): which reads share a (k+1)-mer with a set of contigs ------------------------------
+// The contigs turn on the mark bit of every edge their windows find, as given and reverse-complemented; a read matches when the edge
+// of one of its windows is marked.  Both passes are the walk above -- one index search, then one dependent line per window -- without
+// multiplicities and without the per-window scratch.
+
+constexpr int kMatchMaxWindow = 128;      // k + 1 symbols of an index search, staged in LDS per group (32 groups: 4 KB per workgroup)
+
+struct MarkJob {                          // one strand of one contig
+    uint64_t off;                         // its first symbol
+    uint32_t len, pad_;
+};
+
+// the reverse complement of all n symbols behind them: s[n + i] = complement of s[n - 1 - i] (0 stays 0), so the reverse complement
+// of the contig at [a, b) lies at [2n - b, 2n - a)
+__global__ __launch_bounds__(256) void match_rc_symbols_kernel(uint8_t *s, uint64_t n) {
+    const uint64_t stride = (uint64_t)gridDim.x * 256;
+    for (uint64_t i = (uint64_t)blockIdx.x * 256 + threadIdx.x; i < n; i += stride) {
+        const uint32_t c = s[n - 1 - i];
+        s[n + i] = (uint8_t)(c ? 5u - c : 0u);
+    }
+}
+
+// counters: [0] queue head, [1] edges whose bit this launch turned on
+__global__ __launch_bounds__(kCovThreads) void match_mark_kernel(GraphDev g, const uint8_t *sym, const MarkJob *jobs, uint32_t n_jobs, uint32_t chunk, uint32_t *marks,
+                                                                 unsigned long long *counters) {
+    const int sub = threadIdx.x & 7;
+    const int k = g.k;
+    uint32_t marked = 0;
+    for (;;) {
+        unsigned long long first = 0;
+        if (sub == 0) first = atomicAdd(&counters[0], (unsigned long long)chunk);
+        first = __shfl(first, 0, 8);
+        if (first >= n_jobs) break;
+        const uint32_t j_end = (uint32_t)min((unsigned long long)n_jobs, first + chunk);
+        for (uint32_t j = (uint32_t)first; j < j_end; ++j) {
+            const MarkJob job = jobs[j];
+            const uint8_t *s = sym + job.off;
+            const uint32_t n_win = job.len > (uint32_t)k ? job.len - (uint32_t)k : 0;
+            int run = 0;                                                  // A C G T letters in a row, up to the window's last letter
+            for (int i = 0; i < k && (uint32_t)i < job.len; ++i) run = s[i] ? run + 1 : 0;
+            int64_t e = -1;                                               // the edge of the window before, -1 = the walk has to start again
+            LineR L{};
+            for (uint32_t p = 0; p < n_win; ++p) {
+                const int c = s[p + k];
+                run = c ? run + 1 : 0;
+                if (run <= k) { e = -1; continue; }
+                if (e >= 0) e = cov_step(g, L, e, c, sub);
+                else {
+                    e = g_index_edge(g, s + p);
+                    if (e >= 0) L = grp_load_line(g, (uint64_t)e >> 6, sub);
+                }
+                if (e >= 0 && sub == 0) {                                 // the lane that turns the edge's bit on counts the edge
+                    const uint32_t bit = 1u << (e & 31);
+                    if (!(atomicOr(&marks[e >> 5], bit) & bit)) ++marked;
+                }
+            }
+        }
+    }
+    const uint32_t m = wave_sum(marked);
+    if (lane_id() == 0 && m) atomicAdd(&counters[1], (unsigned long long)m);
+}
+
+// A group of 8 lanes owns a read.  Its bases come straight from the packed words (2 bits per base, base j of a word at bits 30 - 2j;
+// one 32-bit load per 16 bases, the same for all lanes of the group) in STORED order, words ascending.  Reads stored as sequenced are
+// walked as they are; reads stored reversed are walked with complemented bases, i.e. along their reverse complement: the marks hold
+// both strands of every contig window, so that walk hits exactly when the read does, window for window.  count_all = 0: the walk of
+// a read ends at its first hit.
+// counters: [0] queue head, [1] windows found by a step, [2] index searches, [3] matched reads, [4] read windows
+__global__ __launch_bounds__(kCovThreads) void match_walk_kernel(GraphDev g, const uint32_t *packed, const uint64_t *start, uint64_t n_reads, int reversed, uint32_t chunk,
+                                                                 const uint32_t *marks, uint32_t *bits, uint32_t *hit_windows, int count_all,
+                                                                 unsigned long long *counters) {
+    __shared__ uint8_t s_seq[kCovThreads / 8][kMatchMaxWindow];
+    const int sub = threadIdx.x & 7;
+    const int k = g.k;
+    uint8_t *seq = s_seq[threadIdx.x >> 3];
+    const uint32_t flip = reversed ? 3u : 0u;                             // base b -> symbol (b ^ flip) + 1: the complement when stored reversed
+    uint32_t walked = 0, searched = 0, matched = 0;
+    unsigned long long windows = 0;
+    for (;;) {
+        unsigned long long first = 0;
+        if (sub == 0) first = atomicAdd(&counters[0], (unsigned long long)chunk);
+        first = __shfl(first, 0, 8);
+        if (first >= n_reads) break;
+        const uint64_t r_end = min((unsigned long long)n_reads, first + chunk);
+        for (uint64_t r = first; r < r_end; ++r) {
+            const uint64_t s0 = start[r], len = start[r + 1] - s0;
+            const uint64_t n_win = len > (uint64_t)k ? len - (uint64_t)k : 0;
+            windows += n_win;
+            int64_t e = -1;                                               // the edge of the window before, -1 = the walk has to start again
+            LineR L{};
+            uint32_t hits = 0, w = 0;
+            for (uint64_t p = 0; p < n_win; ++p) {
+                const uint64_t q = s0 + p + (uint64_t)k;                  // the window's last base
+                if (p == 0 || (q & 15) == 0) w = packed[q >> 4];
+                const int c = (int)(((w >> (30 - 2 * (int)(q & 15))) & 3u) ^ flip) + 1;
+                if (e >= 0) {
+                    e = cov_step(g, L, e, c, sub);
+                    if (e >= 0) ++walked;
+                } else {
+                    // every lane writes all k + 1 symbols itself and reads back only what it wrote (the same values in every lane of the group)
+                    for (int i = 0; i <= k; ++i) {
+                        const uint64_t qi = s0 + p + (uint64_t)i;
+                        seq[i] = (uint8_t)((((packed[qi >> 4] >> (30 - 2 * (int)(qi & 15))) & 3u) ^ flip) + 1);
+                    }
+                    e = g_index_edge(g, seq);
+                    ++searched;
+                    if (e >= 0) L = grp_load_line(g, (uint64_t)e >> 6, sub);
+                }
+                if (e >= 0 && ((marks[e >> 5] >> (e & 31)) & 1u)) {
+                    ++hits;
+                    if (!count_all) break;
+                }
+            }
+            if (sub == 0) {
+                if (count_all) hit_windows[r] = hits;
+                if (hits) {
+                    atomicOr(&bits[r >> 5], 1u << (r & 31));
+                    ++matched;
+                }
+            }
+        }
+    }
+    const uint32_t wk = wave_sum(sub == 0 ? walked : 0u), sc = wave_sum(sub == 0 ? searched : 0u), mt = wave_sum(matched);
+    const uint64_t wn = wave_sum64(sub == 0 ? windows : 0ull);
+    if (lane_id() == 0) {
+        if (wk) atomicAdd(&counters[1], (unsigned long long)wk);
+        if (sc) atomicAdd(&counters[2], (unsigned long long)sc);
+        if (mt) atomicAdd(&counters[3], (unsigned long long)mt);
+        if (wn) atomicAdd(&counters[4], (unsigned long long)wn);
+    }
+}
+
 }  // namespace
 }  // namespace mgta
 
@@ -380,6 +513,110 @@ int mgta_contig_coverage(mgta_sdbg *g, const char *seqs, const uint64_t *offsets
             stats->n_contigs = n; stats->n_windows = (int64_t)win_done; stats->n_walked = (int64_t)cnt[1]; stats->n_index_searches = (int64_t)cnt[2];
             stats->groups_per_cu = (int64_t)blocks_per_cu * (kCovThreads / 8);
             stats->n_batches = n_batches; stats->ms_walk = ms_walk; stats->ms_kernel = ms_walk + ms_stats;
+        }
+        return MGTA_OK;
+    });
+}
+
+int mgta_reads_match_contigs(mgta_sdbg *g, const mgta_reads *reads, int reads_reversed, uint64_t n_short_reads, const char *seqs, const uint64_t *offsets, int64_t n,
+                             uint64_t *match_bits, uint32_t *hit_windows, mgta_match_stats *stats) {
+    if (!g || !reads) { set_error("mgta_reads_match_contigs: the graph and the reads must not be NULL"); return MGTA_EINVAL; }
+    if (g->ctx != reads->ctx) { set_error("mgta_reads_match_contigs: the graph and the reads belong to different contexts"); return MGTA_EINVAL; }
+    if (n_short_reads > reads->n_reads) {
+        set_error("mgta_reads_match_contigs: n_short_reads = %llu, the library holds %llu reads", (unsigned long long)n_short_reads, (unsigned long long)reads->n_reads);
+        return MGTA_EINVAL;
+    }
+    if (n_short_reads > 0 && !match_bits) { set_error("mgta_reads_match_contigs: match_bits must not be NULL"); return MGTA_EINVAL; }
+    if (n < 0 || n > 0x7FFFFFF0ll || (n > 0 && !offsets)) { set_error("mgta_reads_match_contigs: bad contig count or offsets"); return MGTA_EINVAL; }
+    for (int64_t i = 0; i < n; ++i)
+        if (offsets[i + 1] < offsets[i] || offsets[i + 1] - offsets[i] > 0xFFFFFFF0ull || (offsets[i + 1] > offsets[i] && !seqs)) {
+            set_error("mgta_reads_match_contigs: contig %lld: offsets must ascend, a contig holds < 2^32 letters", (long long)i);
+            return MGTA_EINVAL;
+        }
+    if (g->dev.k + 1 > kMatchMaxWindow) { set_error("mgta_reads_match_contigs: k = %d (k + 1 <= %d is supported)", g->dev.k, kMatchMaxWindow); return MGTA_EINVAL; }
+    const uint64_t n_bit_words = (n_short_reads + 63) / 64;
+    if (stats) memset(stats, 0, sizeof(*stats));
+    if (n_bit_words) memset(match_bits, 0, n_bit_words * 8);
+    if (hit_windows && n_short_reads) memset(hit_windows, 0, n_short_reads * 4);
+    if (n == 0 || n_short_reads == 0) return MGTA_OK;
+    return guarded("mgta_reads_match_contigs", [&]() {
+        mgta_ctx *ctx = g->ctx;
+        MGTA_HIP_CHECK(hipSetDevice(ctx->device));
+        hipStream_t st = ctx->stream;
+        const uint64_t k = (uint64_t)g->dev.k;
+        constexpr int kGroups = kCovThreads / 8;
+        // the two strands of every contig, longest first (ties by number: the order is fixed); the reverse complements lie mirrored behind the symbols
+        const uint64_t n_sym = offsets[n] - offsets[0];
+        std::vector<MarkJob> jobs;
+        jobs.reserve((size_t)n * 2);
+        uint64_t contig_windows = 0;
+        for (int64_t i = 0; i < n; ++i) {
+            const uint64_t a = offsets[i] - offsets[0], b = offsets[i + 1] - offsets[0];
+            contig_windows += b - a > k ? b - a - k : 0;
+            jobs.push_back(MarkJob{a, (uint32_t)(b - a), 0});
+            jobs.push_back(MarkJob{2 * n_sym - b, (uint32_t)(b - a), 0});
+        }
+        std::stable_sort(jobs.begin(), jobs.end(), [](const MarkJob &x, const MarkJob &y) { return x.len > y.len; });
+        const uint32_t nj = (uint32_t)jobs.size();
+        // workgroups a CU holds at once: what the kernels' registers allow (never assumed)
+        int mark_per_cu = 0, walk_per_cu = 0;
+        MGTA_HIP_CHECK(hipOccupancyMaxActiveBlocksPerMultiprocessor(&mark_per_cu, match_mark_kernel, kCovThreads, 0));
+        MGTA_HIP_CHECK(hipOccupancyMaxActiveBlocksPerMultiprocessor(&walk_per_cu, match_walk_kernel, kCovThreads, 0));
+        mark_per_cu = std::max(1, mark_per_cu);
+        walk_per_cu = std::max(1, walk_per_cu);
+        // one mark bit per edge, the graph's own, zeroed per call
+        const size_t mark_b = ((size_t)g->dev.size / 32 + 2) * 4;
+        if (g->marks.bytes < mark_b) g->marks.alloc(mark_b, &ctx->live_bytes, &ctx->peak_bytes);
+        MGTA_HIP_CHECK(hipMemsetAsync(g->marks.p, 0, mark_b, st));
+        DevBuf d_cnt, d_sym, d_jobs, d_bits, d_hits;
+        d_cnt.alloc(128);
+        d_sym.alloc(2 * n_sym + 16, &ctx->live_bytes, &ctx->peak_bytes);
+        d_jobs.alloc((size_t)nj * sizeof(MarkJob), &ctx->live_bytes, &ctx->peak_bytes);
+        d_bits.alloc(n_bit_words * 8, &ctx->live_bytes, &ctx->peak_bytes);
+        if (hit_windows) d_hits.alloc(n_short_reads * 4, &ctx->live_bytes, &ctx->peak_bytes);
+        MGTA_HIP_CHECK(hipMemsetAsync(d_cnt.p, 0, 128, st));
+        MGTA_HIP_CHECK(hipMemsetAsync(d_bits.p, 0, n_bit_words * 8, st));
+        if (n_sym) MGTA_HIP_CHECK(hipMemcpyAsync(d_sym.p, seqs + offsets[0], n_sym, hipMemcpyHostToDevice, st));
+        MGTA_HIP_CHECK(hipMemcpyAsync(d_jobs.p, jobs.data(), (size_t)nj * sizeof(MarkJob), hipMemcpyHostToDevice, st));
+        unsigned long long *cnt_mark = d_cnt.as<unsigned long long>(), *cnt_walk = cnt_mark + 8;
+        Timer t_mark(st), t_walk(st);
+        t_mark.start();
+        if (n_sym) {
+            const unsigned sym_blocks = (unsigned)std::min<uint64_t>((n_sym + 255) / 256, (uint64_t)ctx->num_cus * 16);
+            hipLaunchKernelGGL(cov_symbols_kernel, dim3(sym_blocks), dim3(256), 0, st, d_sym.as<uint8_t>(), n_sym);
+            hipLaunchKernelGGL(match_rc_symbols_kernel, dim3(sym_blocks), dim3(256), 0, st, d_sym.as<uint8_t>(), n_sym);
+        }
+        {
+            const uint64_t groups = (uint64_t)ctx->num_cus * (uint64_t)mark_per_cu * kGroups;
+            const uint32_t chunk = nj >= groups * 64 ? 4u : 1u;
+            const unsigned blocks = (unsigned)std::min<uint64_t>((uint64_t)ctx->num_cus * (uint64_t)mark_per_cu, ((uint64_t)nj + kGroups - 1) / kGroups);
+            hipLaunchKernelGGL(match_mark_kernel, dim3(blocks), dim3(kCovThreads), 0, st, g->dev, d_sym.as<uint8_t>(), d_jobs.as<MarkJob>(), nj, chunk,
+                               g->marks.as<uint32_t>(), cnt_mark);
+        }
+        MGTA_HIP_CHECK(hipGetLastError());
+        t_mark.end();
+        t_walk.start();
+        {
+            // a group takes `chunk` reads per visit to the queue head (one word saturates near 88 dequeues per microsecond)
+            const uint64_t groups = (uint64_t)ctx->num_cus * (uint64_t)walk_per_cu * kGroups;
+            const uint32_t chunk = n_short_reads >= groups * 256 ? 16u : 1u;
+            const unsigned blocks = (unsigned)std::min<uint64_t>((uint64_t)ctx->num_cus * (uint64_t)walk_per_cu, (n_short_reads + (uint64_t)kGroups * chunk - 1) / ((uint64_t)kGroups * chunk));
+            hipLaunchKernelGGL(match_walk_kernel, dim3(blocks), dim3(kCovThreads), 0, st, g->dev, reads->d_packed, reads->d_start, n_short_reads, reads_reversed ? 1 : 0, chunk,
+                               g->marks.as<uint32_t>(), d_bits.as<uint32_t>(), d_hits.as<uint32_t>(), hit_windows ? 1 : 0, cnt_walk);
+        }
+        MGTA_HIP_CHECK(hipGetLastError());
+        t_walk.end();
+        unsigned long long cnt[16] = {0};
+        MGTA_HIP_CHECK(hipMemcpyAsync(cnt, d_cnt.p, 128, hipMemcpyDeviceToHost, st));
+        MGTA_HIP_CHECK(hipMemcpyAsync(match_bits, d_bits.p, n_bit_words * 8, hipMemcpyDeviceToHost, st));
+        if (hit_windows) MGTA_HIP_CHECK(hipMemcpyAsync(hit_windows, d_hits.p, n_short_reads * 4, hipMemcpyDeviceToHost, st));
+        MGTA_HIP_CHECK(hipStreamSynchronize(st));
+        if (stats) {
+            stats->n_contigs = n; stats->n_contig_windows = (int64_t)contig_windows; stats->n_marked_edges = (int64_t)cnt[1];
+            stats->n_reads = (int64_t)n_short_reads; stats->n_read_windows = (int64_t)cnt[12];
+            stats->n_walked = (int64_t)cnt[9]; stats->n_index_searches = (int64_t)cnt[10]; stats->n_matched_reads = (int64_t)cnt[11];
+            stats->groups_per_cu = (int64_t)walk_per_cu * kGroups;
+            stats->ms_mark = t_mark.ms(); stats->ms_walk = t_walk.ms();
         }
         return MGTA_OK;
     });

@@ -59,6 +59,8 @@ struct Session {
     std::string graph_prefix;
     mgta_sdbg *cov_graph = nullptr;   // graph loaded WITH its multiplicities by the last `coverage`: serves the coverage of the next gene
     std::string cov_key;          // the graph files it came from (index path | size | mtime)
+    mgta_sdbg *match_graph = nullptr; // graph loaded WITHOUT multiplicities by the last `matchreads` that found no counted graph to use
+    std::string match_key;
     std::thread writer;           // PREFIX.sdbg.* of the last buildgraph being written while the next step already runs on the resident graph
     std::string writer_error;     // why that thread failed (set by the thread, read after the join)
     mgta_stream *stream = nullptr;   // the edge stream that thread downloads from the device (freed on this thread once it has joined)
@@ -169,6 +171,7 @@ static PackedReads &lib_get(const std::string &bin_path, const std::string &lib_
 static void graph_drop() {
     if (g_sess.graph) { mgta_sdbg_free(g_sess.graph); g_sess.graph = nullptr; g_sess.graph_prefix.clear(); }
     if (g_sess.cov_graph) { mgta_sdbg_free(g_sess.cov_graph); g_sess.cov_graph = nullptr; g_sess.cov_key.clear(); }
+    if (g_sess.match_graph) { mgta_sdbg_free(g_sess.match_graph); g_sess.match_graph = nullptr; g_sess.match_key.clear(); }
 }
 // the graph PREFIX names: the one the last buildgraph of this process left on the device, else read from the files
 static mgta_sdbg *graph_get(mgta_ctx *ctx, const std::string &prefix, int *k_out, size_t *n_edges) {
@@ -782,41 +785,44 @@ static int main_denovo(int argc, char **argv) {
     return 0;
 }
 
+// the records of a FASTA in file order: name = the header up to the first blank, sequence = its lines joined (offsets [n + 1] into seqs)
+static void read_fasta_records(const std::string &fasta, std::vector<std::string> &names, std::string &seqs, std::vector<uint64_t> &offsets) {
+    offsets.assign(1, 0);
+    FILE *f = fopen(fasta.c_str(), "r");
+    if (!f) die("cannot open %s", fasta.c_str());
+    char *line = nullptr;
+    size_t cap = 0;
+    ssize_t n;
+    bool open_rec = false;
+    while ((n = getline(&line, &cap, f)) >= 0) {
+        while (n > 0 && (line[n - 1] == '\n' || line[n - 1] == '\r' || line[n - 1] == ' ' || line[n - 1] == '\t')) line[--n] = 0;
+        if (n > 0 && line[0] == '>') {
+            if (open_rec) offsets.push_back(seqs.size());
+            size_t e = 1;
+            while (e < (size_t)n && line[e] != ' ' && line[e] != '\t') ++e;
+            names.emplace_back(line + 1, e - 1);
+            open_rec = true;
+        } else if (open_rec) {
+            const char *b = line;
+            while (*b == ' ' || *b == '\t') ++b;
+            seqs.append(b);
+        }
+    }
+    if (open_rec) offsets.push_back(seqs.size());
+    free(line);
+    fclose(f);
+}
+
 // ---- coverage: per-contig k-mer coverage and abundance from the graph's own multiplicities (the reference's last post-processing step,
 // `kmer_coverage` in bin/post_proc.sh:113-118, recounts them from the reads).  The file formats are this project's own: INTEGRATION.md.
 static int main_coverage(int argc, char **argv) {
     if (argc != 4) { fprintf(stderr, "Usage: megagta coverage <sdbg_prefix> <contigs.fasta> <out_prefix>\n"); return 1; }
     RssLine rss;
     const std::string prefix = argv[1], fasta = argv[2], out_prefix = argv[3];
-    // the records of the FASTA in file order: name = the header up to the first blank, sequence = its lines joined
     std::vector<std::string> names;
     std::string seqs;
-    std::vector<uint64_t> offsets{0};
-    {
-        FILE *f = fopen(fasta.c_str(), "r");
-        if (!f) die("cannot open %s", fasta.c_str());
-        char *line = nullptr;
-        size_t cap = 0;
-        ssize_t n;
-        bool open_rec = false;
-        while ((n = getline(&line, &cap, f)) >= 0) {
-            while (n > 0 && (line[n - 1] == '\n' || line[n - 1] == '\r' || line[n - 1] == ' ' || line[n - 1] == '\t')) line[--n] = 0;
-            if (n > 0 && line[0] == '>') {
-                if (open_rec) offsets.push_back(seqs.size());
-                size_t e = 1;
-                while (e < (size_t)n && line[e] != ' ' && line[e] != '\t') ++e;
-                names.emplace_back(line + 1, e - 1);
-                open_rec = true;
-            } else if (open_rec) {
-                const char *b = line;
-                while (*b == ' ' || *b == '\t') ++b;
-                seqs.append(b);
-            }
-        }
-        if (open_rec) offsets.push_back(seqs.size());
-        free(line);
-        fclose(f);
-    }
+    std::vector<uint64_t> offsets;
+    read_fasta_records(fasta, names, seqs, offsets);
     const int64_t n = (int64_t)names.size();
     double t0 = now_s();
     mgta_ctx *ctx = ctx_get();
@@ -861,6 +867,72 @@ static int main_coverage(int argc, char **argv) {
     for (int m = 0; m < 65536; ++m)
         if (abund[(size_t)m]) fprintf(af, "%d\t%lld\n", m, (long long)abund[(size_t)m]);
     if (fclose(af) != 0) die("short write to %s_abundance.txt", out_prefix.c_str());
+    if (!g_sess.active) mgta_sdbg_free(g);
+    ctx_put(ctx);
+    return 0;
+}
+
+// ---- matchreads: the reads of the library that share a (k+1)-mer with the contigs of a FASTA, on either strand (the `-m` output of the
+// reference's `kmer_coverage` step, bin/post_proc.sh:113-118).  The file format is this project's own: INTEGRATION.md 2h.
+static int main_matchreads(int argc, char **argv) {
+    if (argc != 5) { fprintf(stderr, "Usage: megagta matchreads <sdbg_prefix> <read.lib> <contigs.fasta> <out_prefix>\n"); return 1; }
+    RssLine rss;
+    const std::string prefix = argv[1], lib = argv[2], fasta = argv[3], out_prefix = argv[4];
+    std::vector<std::string> names;
+    std::string seqs;
+    std::vector<uint64_t> offsets;
+    read_fasta_records(fasta, names, seqs, offsets);
+    const int64_t n = (int64_t)names.size();
+    double t0 = now_s();
+    PackedReads local;
+    PackedReads::Mark mk;
+    PackedReads &pr = lib_get(lib + ".bin", lib, "", false, local, mk);  // reversed, as buildgraph uploads it: a worker that still holds it does not read it again
+    const uint64_t n_reads = pr.start.size() - 1;
+    logf("%llu reads, %llu total bases (load %.3f s)", (unsigned long long)n_reads, (unsigned long long)pr.start.back(), now_s() - t0);
+    t0 = now_s();
+    mgta_ctx *ctx = ctx_get();
+    // The graph: any load will do.  A worker uses the counted graph `coverage` has loaded from the same files, else the one the matchreads
+    // of the gene before loaded; the first request loads the files -- which are complete first -- without multiplicities.
+    if (writer_join() != 0) die("the graph files of %s are incomplete", prefix.c_str());
+    const std::string key = file_key(prefix + ".sdbg_info");
+    mgta_sdbg *g = nullptr;
+    if (g_sess.active && g_sess.cov_graph && g_sess.cov_key == key) g = g_sess.cov_graph;
+    else if (g_sess.active && g_sess.match_graph && g_sess.match_key == key) g = g_sess.match_graph;
+    if (g) logf("graph %s: still on the device", prefix.c_str());
+    else {
+        graph_drop();
+        if (mgta_sdbg_load_files(ctx, prefix.c_str(), &g) != MGTA_OK) die("mgta_sdbg_load_files: %s", mgta_last_error());
+        if (g_sess.active) { g_sess.match_graph = g; g_sess.match_key = key; }
+    }
+    logf("Number of Edges: %lld; K value: %d (load %.3f s)", (long long)mgta_sdbg_size(g), mgta_sdbg_k(g), now_s() - t0);
+    t0 = now_s();
+    mgta_reads *rd = nullptr;
+    if (mgta_reads_upload(ctx, pr.words.data(), pr.words.size(), pr.start.data(), n_reads, &rd) != MGTA_OK) die("mgta_reads_upload: %s", mgta_last_error());
+    std::vector<uint64_t> bits((size_t)((n_reads + 63) / 64) + 1);
+    mgta_match_stats st;
+    // all records in ONE call (the marks live for one call); bits only: the walk of a read ends at its first hit
+    if (mgta_reads_match_contigs(g, rd, 1, n_reads, seqs.data(), offsets.data(), n, bits.data(), nullptr, &st) != MGTA_OK) die("mgta_reads_match_contigs: %s", mgta_last_error());
+    mgta_reads_free(rd);
+    logf("matched reads of %lld contigs: %lld contig windows marked %lld edges (%.1f ms); %lld of %lld reads match, %lld read windows, %lld by the walk, %lld index "
+         "searches, %lld groups per CU (%.1f ms); wall %.3f s", (long long)n, (long long)st.n_contig_windows, (long long)st.n_marked_edges, st.ms_mark,
+         (long long)st.n_matched_reads, (long long)st.n_reads, (long long)st.n_read_windows, (long long)st.n_walked, (long long)st.n_index_searches,
+         (long long)st.groups_per_cu, st.ms_walk, now_s() - t0);
+    const std::string path = out_prefix + "_match_reads.fa";
+    FILE *f = fopen(path.c_str(), "w");
+    if (!f) die("cannot write %s", path.c_str());
+    std::string rec;
+    for (uint64_t r = 0; r < n_reads; ++r) {
+        if (!((bits[(size_t)(r >> 6)] >> (r & 63)) & 1)) continue;
+        const uint64_t s0 = pr.start[(size_t)r], len = pr.start[(size_t)r + 1] - s0;
+        rec = ">r" + std::to_string((unsigned long long)r) + "\n";
+        for (uint64_t j = 0; j < len; ++j) {                            // reversed storage -> the read as sequenced
+            const uint64_t q = s0 + (len - 1 - j);
+            rec.push_back("ACGT"[(pr.words[(size_t)(q >> 4)] >> (30 - 2 * (q & 15))) & 3]);
+        }
+        rec.push_back('\n');
+        if (fwrite(rec.data(), 1, rec.size(), f) != rec.size()) die("short write to %s", path.c_str());
+    }
+    if (fclose(f) != 0) die("short write to %s", path.c_str());
     if (!g_sess.active) mgta_sdbg_free(g);
     ctx_put(ctx);
     return 0;
@@ -953,7 +1025,7 @@ int main(int argc, char **argv) {
 static int dispatch(int argc, char **argv) {
     if (argc < 2) {
         fprintf(stderr, "Usage: %s <sub_program> [sub options]\n    sub-programs on the MI355X hot path:\n        buildgraph    build succinct de Bruijn graph\n"
-                        "        denovo        tips, bubbles, contigs of an intermediate k\n        search        HMM-guided search of gene contigs\n        findstart     find starting kmers of the search\n        coverage      per-contig k-mer coverage and abundance from the graph\n        dumpversion   dump version\n", argv[0]);
+                        "        denovo        tips, bubbles, contigs of an intermediate k\n        search        HMM-guided search of gene contigs\n        findstart     find starting kmers of the search\n        coverage      per-contig k-mer coverage and abundance from the graph\n        matchreads    the reads that share a (k+1)-mer with a set of contigs\n        dumpversion   dump version\n", argv[0]);
         return 1;
     }
     std::string sub = argv[1];
@@ -962,6 +1034,7 @@ static int dispatch(int argc, char **argv) {
     if (sub == "findstart") return main_findstart(argc - 1, argv + 1);
     if (sub == "denovo") return main_denovo(argc - 1, argv + 1);
     if (sub == "coverage") return main_coverage(argc - 1, argv + 1);
+    if (sub == "matchreads") return main_matchreads(argc - 1, argv + 1);
     if (sub == "filterbylen") return main_filterbylen(argc - 1, argv + 1);
     if (sub == "translate") return main_translate(argc - 1, argv + 1);
     if (sub == "buildlib") {                                             // build_read_lib.cpp:8-20 (host only: file formats, no kernel)
@@ -1064,6 +1137,6 @@ static int dispatch(int argc, char **argv) {
         return 0;
     }
     if (sub == "dumpversion") { printf("%s\n", mgta_version()); return 0; }
-    fprintf(stderr, "sub-command '%s' is not built here (buildlib, buildgraph, denovo, findstart, search, coverage, filterbylen, translate are): run it with the reference's megagta binary\n", sub.c_str());
+    fprintf(stderr, "sub-command '%s' is not built here (buildlib, buildgraph, denovo, findstart, search, coverage, matchreads, filterbylen, translate are): run it with the reference's megagta binary\n", sub.c_str());
     return 1;
 }

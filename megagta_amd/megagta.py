@@ -38,7 +38,9 @@ USAGE = """Usage:
     --one-process-per-step   start every step as its own process, as the reference driver does (default: one worker process,
                      `megagta serve`, runs all steps and keeps the device context, the read library and the last graph between them)
     --coverage       after the last k: per gene contigs/<gene>/nucl_merged_coverage.txt and nucl_merged_abundance.txt, the k-mer coverage
-                     of every contig and the abundance histogram of the edges they touch, from the graph's own multiplicities (GPU 0)"""
+                     of every contig and the abundance histogram of the edges they touch, from the graph's own multiplicities (GPU 0)
+    --match-reads    after the last k (and after --coverage): per gene contigs/<gene>/nucl_merged_match_reads.fa, the reads of the library
+                     that share a (k+1)-mer with the gene's contigs on either strand, as `>r<index in the library>` records (GPU 0)"""
 
 
 class Usage(Exception):
@@ -70,6 +72,7 @@ class Opt:
         self.one_process_per_step = False
         self.gpus = 1
         self.coverage = False
+        self.match_reads = False
 
 
 opt = Opt()
@@ -77,7 +80,7 @@ cp = 0
 
 LONG = ["help", "read=", "12=", "out-dir=", "memory=", "gpu-mem=", "min-contig-len=", "num-cpu-threads=", "kmin-1pass", "k-list=",
         "min-count=", "max-tip-len=", "no-mercy", "keep-tmp-files", "mem-flag=", "version", "verbose", "continue", "gene-list=",
-        "prune-len=", "low-cov-penalty=", "bin=", "one-process-per-step", "gpus=", "coverage"]
+        "prune-len=", "low-cov-penalty=", "bin=", "one-process-per-step", "gpus=", "coverage", "match-reads"]
 
 
 def parse_opt(argv):
@@ -124,6 +127,7 @@ def parse_opt(argv):
         elif o == "--one-process-per-step": opt.one_process_per_step = True
         elif o == "--gpus": opt.gpus = int(v)
         elif o == "--coverage": opt.coverage = True
+        elif o == "--match-reads": opt.match_reads = True
         else:
             raise Usage("Invalid option " + o)
     opt.temp_dir = opt.out_dir + "tmp/"
@@ -564,6 +568,26 @@ def contig_coverage(k):
         write_cp()
 
 
+def match_reads(k):
+    """--match-reads: per gene contigs/<gene>/nucl_merged_match_reads.fa, the reads of the run's library that share a (k+1)-mer with
+    the gene's contigs (`megagta matchreads` on the last k's graph, GPU 0; mates are not recruited).  Its checkpoints come after every
+    checkpoint of a run without the flag and after --coverage's, so `--continue` works under either."""
+    for gene in opt.gene_info:
+        d = opt.out_dir + "contigs/" + gene
+        if should_run():
+            run_step([opt.bin, "matchreads", graph_prefix(k), opt.lib, d + "/nucl_merged.fasta", d + "/nucl_merged"],
+                     "Recruiting the reads that match the contigs of %s" % gene)
+        write_cp()
+
+
+def after_search(k):
+    """the opt-in steps on the last k's graph, in a fixed order behind every checkpoint of a run without them"""
+    if opt.coverage:
+        contig_coverage(k)
+    if opt.match_reads:
+        match_reads(k)
+
+
 def main(argv=None):
     argv = sys.argv if argv is None else argv
     try:
@@ -602,8 +626,7 @@ def main(argv=None):
                         worker.close()
                     return 0
                 search_contigs(k)
-                if opt.coverage:
-                    contig_coverage(k)
+                after_search(k)
         flush_deferred_cp()
         if worker is not None:
             worker.close()
