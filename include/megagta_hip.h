@@ -292,6 +292,39 @@ int mgta_reads_match_contigs(mgta_sdbg *, const mgta_reads *reads, int reads_rev
                              uint32_t *hit_windows /* optional [n_short_reads] */, mgta_match_stats *stats /* optional */);
 
 /* ------------------------------------------------------------------------------------------------
+ * De-replication ("get the unique merged contigs", the first step of the reference's bin/post_proc.sh:50-55: `Clustering.jar derep`,
+ * then `ReadSeq.jar rm-dupseq -d`, both from a submodule the reference does not ship).  Needs no graph.  Sequence i =
+ * seqs[offsets[i] .. offsets[i + 1]), a byte string compared byte for byte: no case folding, no reverse complement (a gene's contigs
+ * all have the gene's orientation).  Every sequence gets
+ *   status 1 (duplicate): some j < i has s[j] == s[i]; rep[i] = the lowest such j, copies[i] = 0;
+ *   status 2 (contained): a first occurrence that is a substring of some LONGER sequence; rep[i] = -1, copies[i] = the number of
+ *                         inputs equal to s[i], itself included;
+ *   status 0 (kept):      every other first occurrence; rep[i] = i, copies as for contained.
+ * The empty sequence is contained as soon as a non-empty one exists.  The result is exactly this for any input: hashes only choose
+ * what is compared, every equality and containment that decides a status is confirmed on the letters.  status, rep, copies and every
+ * stats field but ms_* and n_compares are functions of the input only; n_compares depends on the order in which the device linked
+ * the window lists and may differ from call to call.  mgta_ctx_set_derep_hash_bits keeps only the low `bits` bits of both hashes
+ * (1 .. 64, default 64): with a few bits nearly every key collides and the outputs must not move -- a switch for tests, like
+ * mgta_ctx_set_coverage_batch.  Limits: n < 2^31 sequences and fewer than 2^32 letters in the first occurrences; beyond either the
+ * call returns MGTA_EINVAL and says which (nothing is truncated).  Device memory: about 9 bytes per letter of the first occurrences
+ * plus 16 bytes per slot of the window table (2 to 4 slots per window), accounted like every other buffer of the context; what does
+ * not fit is MGTA_ENOMEM.  MGTA_EINVAL: NULL context, n < 0, NULL outputs or offsets with n > 0, descending offsets (nothing is
+ * written).  n = 0: MGTA_OK, stats all zero.
+ * ------------------------------------------------------------------------------------------------ */
+typedef struct mgta_derep_stats {
+    int64_t n_seqs, n_letters;             /* the input */
+    int64_t n_first;                       /* first occurrences = n_contained + n_kept */
+    int64_t n_duplicates, n_contained, n_kept;
+    int64_t n_windows;                     /* anchor windows of the first occurrences in the table (0 when there is one first occurrence) */
+    int64_t anchor_len;                    /* min(16, shortest non-empty first occurrence); 0 when every sequence is empty */
+    int64_t n_compares;                    /* letter comparisons of a sequence against a candidate, both passes; depends on list order */
+    double ms_dups, ms_table, ms_verify;   /* HIP events: duplicate pass; packing + window table; anchor choice + list walks */
+} mgta_derep_stats;
+int mgta_seqs_derep(mgta_ctx *, const char *seqs, const uint64_t *offsets /* [n + 1] */, int64_t n,
+                    uint8_t *status, int64_t *rep, uint32_t *copies, mgta_derep_stats *stats /* may be NULL */);
+int mgta_ctx_set_derep_hash_bits(mgta_ctx *, int bits);   /* 1..64, default 64 */
+
+/* ------------------------------------------------------------------------------------------------
  * Seed finder (replaces the read scan of `megagta findstart`, fast_kmer_filter.cpp:108-176,193-215):
  * every window of k nucleotides (k a multiple of 3, k/3 <= 24) of every read, on both strands, whose translation is one of
  * the n_ref reference words.  A word = its residues in the code of prot_kmer.h:31-43 (ARNDCQEGHILKMFPSTWYV = 0..19, '*' = 20),

@@ -89,6 +89,15 @@ class MatchStats(C.Structure):
         return {n: getattr(self, n) for n, _ in self._fields_}
 
 
+class DerepStats(C.Structure):
+    _fields_ = [("n_seqs", C.c_int64), ("n_letters", C.c_int64), ("n_first", C.c_int64), ("n_duplicates", C.c_int64), ("n_contained", C.c_int64),
+                ("n_kept", C.c_int64), ("n_windows", C.c_int64), ("anchor_len", C.c_int64), ("n_compares", C.c_int64), ("ms_dups", C.c_double),
+                ("ms_table", C.c_double), ("ms_verify", C.c_double)]
+
+    def as_dict(self):
+        return {n: getattr(self, n) for n, _ in self._fields_}
+
+
 EDGE_SINK = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_int32, C.c_int32, C.POINTER(C.c_int64), C.POINTER(C.c_uint16), C.c_int64,
                         C.POINTER(C.c_uint16), C.c_int64, C.POINTER(C.c_uint32), C.c_int64)
 CONTIG_SINK = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_void_p, C.c_int64,
@@ -146,6 +155,8 @@ SYMBOLS = {
     "mgta_contig_coverage": (C.c_int, [C.c_void_p, C.c_char_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "mgta_reads_match_contigs": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_uint64, C.c_char_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p,
                                           C.c_void_p]),
+    "mgta_seqs_derep": (C.c_int, [C.c_void_p, C.c_char_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "mgta_ctx_set_derep_hash_bits": (C.c_int, [C.c_void_p, C.c_int]),
     "mgta_sdbg_free": (None, [C.c_void_p]),
     "mgta_sdbg_size": (C.c_int64, [C.c_void_p]),
     "mgta_sdbg_outgoing": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p]),

@@ -112,6 +112,27 @@ class Context:
         the batching on small inputs.  The result does not depend on it."""
         check(self._L.mgta_ctx_set_coverage_batch(self.h, int(windows)), "mgta_ctx_set_coverage_batch")
 
+    def set_derep_hash_bits(self, bits: int = 64):
+        """bits of both hashes `derep` keeps (1 .. 64, the default): with a few bits nearly every key collides.  The result does not
+        depend on it; only stats["n_compares"] does."""
+        check(self._L.mgta_ctx_set_derep_hash_bits(self.h, int(bits)), "mgta_ctx_set_derep_hash_bits")
+
+    def derep(self, seqs) -> dict:
+        """mgta_seqs_derep: the unique, non-contained sequences of `seqs` (str or bytes, compared byte for byte) -> dict(status =
+        uint8[n]: 0 kept, 1 duplicate of an earlier sequence, 2 contained in a longer one; rep = int64[n]: the first occurrence of a
+        duplicate, -1 for a contained sequence, itself for a kept one; copies = uint32[n]: inputs equal to a first occurrence, 0 for a
+        duplicate; stats).  Needs no graph."""
+        raw = [s if isinstance(s, (bytes, bytearray)) else str(s).encode() for s in seqs]
+        n = len(raw)
+        offsets = np.zeros(n + 1, dtype=np.uint64)
+        if n:
+            np.cumsum([len(s) for s in raw], out=offsets[1:])
+        status, rep, copies = np.zeros(max(1, n), dtype=np.uint8), np.zeros(max(1, n), dtype=np.int64), np.zeros(max(1, n), dtype=np.uint32)
+        st = _lib.DerepStats()
+        check(self._L.mgta_seqs_derep(self.h, b"".join(raw), offsets.ctypes.data, n, status.ctypes.data, rep.ctypes.data, copies.ctypes.data, C.byref(st)),
+              "mgta_seqs_derep")
+        return dict(status=status[:n], rep=rep[:n], copies=copies[:n], stats=st.as_dict())
+
     def release_scratch(self):
         """free the work memory kept between calls (build pool, search pool)"""
         check(self._L.mgta_ctx_release_scratch(self.h), "mgta_ctx_release_scratch")

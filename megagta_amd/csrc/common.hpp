@@ -135,6 +135,7 @@ struct mgta_ctx {
     // are in the pool; a kept multi-pass stream accumulates them here when the build ran with the switch on (acc_has_large)
     int keep_multiplicity = 0;
     uint64_t coverage_batch_windows = 0;   // mgta_ctx_set_coverage_batch (0 = the library's default)
+    int derep_hash_bits = 64;    // mgta_ctx_set_derep_hash_bits: bits of both hashes mgta_seqs_derep keeps (fewer = more collisions, same answers)
     const void *last_large = nullptr;
     uint64_t last_n_large = 0;
     mgta::DevBuf acc_large;

@@ -786,7 +786,9 @@ static int main_denovo(int argc, char **argv) {
 }
 
 // the records of a FASTA in file order: name = the header up to the first blank, sequence = its lines joined (offsets [n + 1] into seqs)
-static void read_fasta_records(const std::string &fasta, std::vector<std::string> &names, std::string &seqs, std::vector<uint64_t> &offsets) {
+// (headers, when asked for: every header line behind its '>' as it stands in the file, without the line end)
+static void read_fasta_records(const std::string &fasta, std::vector<std::string> &names, std::string &seqs, std::vector<uint64_t> &offsets,
+                               std::vector<std::string> *headers = nullptr) {
     offsets.assign(1, 0);
     FILE *f = fopen(fasta.c_str(), "r");
     if (!f) die("cannot open %s", fasta.c_str());
@@ -795,7 +797,9 @@ static void read_fasta_records(const std::string &fasta, std::vector<std::string
     ssize_t n;
     bool open_rec = false;
     while ((n = getline(&line, &cap, f)) >= 0) {
-        while (n > 0 && (line[n - 1] == '\n' || line[n - 1] == '\r' || line[n - 1] == ' ' || line[n - 1] == '\t')) line[--n] = 0;
+        while (n > 0 && (line[n - 1] == '\n' || line[n - 1] == '\r')) line[--n] = 0;
+        if (headers && n > 0 && line[0] == '>') headers->emplace_back(line + 1, (size_t)n - 1);
+        while (n > 0 && (line[n - 1] == ' ' || line[n - 1] == '\t')) line[--n] = 0;
         if (n > 0 && line[0] == '>') {
             if (open_rec) offsets.push_back(seqs.size());
             size_t e = 1;
@@ -938,6 +942,69 @@ static int main_matchreads(int argc, char **argv) {
     return 0;
 }
 
+// ---- derep: the unique, non-contained records of a gene's protein contigs, and the nucleotide records they select ("get the unique
+// merged contigs", bin/post_proc.sh:50-55,84-85).  Needs no graph and leaves a worker's resident graphs alone.  Formats: INTEGRATION.md 2i.
+static bool write_text_file(const std::string &path, const std::string &text) {
+    FILE *f = fopen(path.c_str(), "w");
+    if (!f) return false;
+    const bool ok = fwrite(text.data(), 1, text.size(), f) == text.size();
+    return (fclose(f) == 0) && ok;
+}
+static int main_derep(int argc, char **argv) {
+    if (argc != 3 && argc != 5) { fprintf(stderr, "Usage: megagta derep <prot.fasta> <out_prefix> [<nucl.fasta> <nucl_out_prefix>]\n"); return 1; }
+    RssLine rss;
+    const std::string fasta = argv[1], out_prefix = argv[2];
+    std::vector<std::string> names, headers, nnames, nheaders;
+    std::string seqs, nseqs;
+    std::vector<uint64_t> offsets, noffsets;
+    read_fasta_records(fasta, names, seqs, offsets, &headers);
+    const int64_t n = (int64_t)names.size();
+    if (argc == 5) {
+        // `translate` writes one protein record per nucleotide record, in order and under the same name: anything else is not this gene's pair
+        read_fasta_records(argv[3], nnames, nseqs, noffsets, &nheaders);
+        if (nnames.size() != names.size()) {
+            fprintf(stderr, "    [ERROR] derep: %s holds %zu records, %s holds %zu: nothing written\n", fasta.c_str(), names.size(), argv[3], nnames.size());
+            return 1;
+        }
+        for (int64_t i = 0; i < n; ++i)
+            if (nnames[(size_t)i] != names[(size_t)i]) {
+                fprintf(stderr, "    [ERROR] derep: record %lld is %s in %s and %s in %s: nothing written\n", (long long)i, names[(size_t)i].c_str(), fasta.c_str(),
+                        nnames[(size_t)i].c_str(), argv[3]);
+                return 1;
+            }
+    }
+    const double t0 = now_s();
+    mgta_ctx *ctx = ctx_get();
+    std::vector<uint8_t> status((size_t)n + 1);
+    std::vector<int64_t> rep((size_t)n + 1);
+    std::vector<uint32_t> copies((size_t)n + 1);
+    mgta_derep_stats st;
+    if (mgta_seqs_derep(ctx, seqs.data(), offsets.data(), n, status.data(), rep.data(), copies.data(), &st) != MGTA_OK) die("mgta_seqs_derep: %s", mgta_last_error());
+    logf("derep of %lld records, %lld letters: %lld kept, %lld duplicate, %lld contained; anchor %lld, %lld windows, %lld comparisons; duplicates %.1f ms, table %.1f ms, "
+         "walks %.1f ms; wall %.3f s", (long long)st.n_seqs, (long long)st.n_letters, (long long)st.n_kept, (long long)st.n_duplicates, (long long)st.n_contained,
+         (long long)st.anchor_len, (long long)st.n_windows, (long long)st.n_compares, st.ms_dups, st.ms_table, st.ms_verify, now_s() - t0);
+    static const char *kStatus[3] = {"kept", "duplicate", "contained"};
+    std::string kept, map, nkept;
+    for (int64_t i = 0; i < n; ++i) {
+        const size_t u = (size_t)i;
+        map += names[u] + "\t" + kStatus[status[u]] + "\t" + (status[u] == 2 ? std::string("-") : names[(size_t)rep[u]]) + "\t" + std::to_string(copies[u]) + "\n";
+        if (status[u] != 0) continue;
+        kept += ">" + headers[u] + "\n";
+        kept.append(seqs, (size_t)offsets[u], (size_t)(offsets[u + 1] - offsets[u]));
+        kept += "\n";
+        if (argc == 5) {
+            nkept += ">" + nheaders[u] + "\n";
+            nkept.append(nseqs, (size_t)noffsets[u], (size_t)(noffsets[u + 1] - noffsets[u]));
+            nkept += "\n";
+        }
+    }
+    if (!write_text_file(out_prefix + "_rmdup.fasta", kept)) die("cannot write %s_rmdup.fasta", out_prefix.c_str());
+    if (!write_text_file(out_prefix + "_rmdup_map.txt", map)) die("cannot write %s_rmdup_map.txt", out_prefix.c_str());
+    if (argc == 5 && !write_text_file(std::string(argv[4]) + "_rmdup.fasta", nkept)) die("cannot write %s_rmdup.fasta", argv[4]);
+    ctx_put(ctx);
+    return 0;
+}
+
 static int dispatch(int argc, char **argv);
 
 // megagta serve: requests on stdin, one per line: the sub-command's argv, tab separated; a field "<PATH" / ">PATH" redirects the
@@ -1025,7 +1092,7 @@ int main(int argc, char **argv) {
 static int dispatch(int argc, char **argv) {
     if (argc < 2) {
         fprintf(stderr, "Usage: %s <sub_program> [sub options]\n    sub-programs on the MI355X hot path:\n        buildgraph    build succinct de Bruijn graph\n"
-                        "        denovo        tips, bubbles, contigs of an intermediate k\n        search        HMM-guided search of gene contigs\n        findstart     find starting kmers of the search\n        coverage      per-contig k-mer coverage and abundance from the graph\n        matchreads    the reads that share a (k+1)-mer with a set of contigs\n        dumpversion   dump version\n", argv[0]);
+                        "        denovo        tips, bubbles, contigs of an intermediate k\n        search        HMM-guided search of gene contigs\n        findstart     find starting kmers of the search\n        coverage      per-contig k-mer coverage and abundance from the graph\n        matchreads    the reads that share a (k+1)-mer with a set of contigs\n        derep         the unique, non-contained records of a FASTA\n        dumpversion   dump version\n", argv[0]);
         return 1;
     }
     std::string sub = argv[1];
@@ -1035,6 +1102,7 @@ static int dispatch(int argc, char **argv) {
     if (sub == "denovo") return main_denovo(argc - 1, argv + 1);
     if (sub == "coverage") return main_coverage(argc - 1, argv + 1);
     if (sub == "matchreads") return main_matchreads(argc - 1, argv + 1);
+    if (sub == "derep") return main_derep(argc - 1, argv + 1);
     if (sub == "filterbylen") return main_filterbylen(argc - 1, argv + 1);
     if (sub == "translate") return main_translate(argc - 1, argv + 1);
     if (sub == "buildlib") {                                             // build_read_lib.cpp:8-20 (host only: file formats, no kernel)
@@ -1137,6 +1205,6 @@ static int dispatch(int argc, char **argv) {
         return 0;
     }
     if (sub == "dumpversion") { printf("%s\n", mgta_version()); return 0; }
-    fprintf(stderr, "sub-command '%s' is not built here (buildlib, buildgraph, denovo, findstart, search, coverage, matchreads, filterbylen, translate are): run it with the reference's megagta binary\n", sub.c_str());
+    fprintf(stderr, "sub-command '%s' is not built here (buildlib, buildgraph, denovo, findstart, search, coverage, matchreads, derep, filterbylen, translate are): run it with the reference's megagta binary\n", sub.c_str());
     return 1;
 }

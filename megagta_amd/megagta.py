@@ -40,7 +40,10 @@ USAGE = """Usage:
     --coverage       after the last k: per gene contigs/<gene>/nucl_merged_coverage.txt and nucl_merged_abundance.txt, the k-mer coverage
                      of every contig and the abundance histogram of the edges they touch, from the graph's own multiplicities (GPU 0)
     --match-reads    after the last k (and after --coverage): per gene contigs/<gene>/nucl_merged_match_reads.fa, the reads of the library
-                     that share a (k+1)-mer with the gene's contigs on either strand, as `>r<index in the library>` records (GPU 0)"""
+                     that share a (k+1)-mer with the gene's contigs on either strand, as `>r<index in the library>` records (GPU 0)
+    --derep          after the last k (and after --coverage and --match-reads): per gene contigs/<gene>/prot_merged_rmdup.fasta, the protein
+                     contigs that are neither a copy of an earlier one nor a piece of a longer one, nucl_merged_rmdup.fasta, their nucleotide
+                     records, and prot_merged_rmdup_map.txt, what became of every contig (GPU 0)"""
 
 
 class Usage(Exception):
@@ -73,6 +76,7 @@ class Opt:
         self.gpus = 1
         self.coverage = False
         self.match_reads = False
+        self.derep = False
 
 
 opt = Opt()
@@ -80,7 +84,7 @@ cp = 0
 
 LONG = ["help", "read=", "12=", "out-dir=", "memory=", "gpu-mem=", "min-contig-len=", "num-cpu-threads=", "kmin-1pass", "k-list=",
         "min-count=", "max-tip-len=", "no-mercy", "keep-tmp-files", "mem-flag=", "version", "verbose", "continue", "gene-list=",
-        "prune-len=", "low-cov-penalty=", "bin=", "one-process-per-step", "gpus=", "coverage", "match-reads"]
+        "prune-len=", "low-cov-penalty=", "bin=", "one-process-per-step", "gpus=", "coverage", "match-reads", "derep"]
 
 
 def parse_opt(argv):
@@ -128,6 +132,7 @@ def parse_opt(argv):
         elif o == "--gpus": opt.gpus = int(v)
         elif o == "--coverage": opt.coverage = True
         elif o == "--match-reads": opt.match_reads = True
+        elif o == "--derep": opt.derep = True
         else:
             raise Usage("Invalid option " + o)
     opt.temp_dir = opt.out_dir + "tmp/"
@@ -580,12 +585,26 @@ def match_reads(k):
         write_cp()
 
 
+def derep(k):
+    """--derep: per gene the unique, non-contained protein contigs and the nucleotide records they select (`megagta derep`, GPU 0; no
+    graph is needed, k only names the step).  Its checkpoints come after every checkpoint of a run without the flag and after those of
+    --coverage and --match-reads, so `--continue` works under any of them."""
+    for gene in opt.gene_info:
+        d = opt.out_dir + "contigs/" + gene
+        if should_run():
+            run_step([opt.bin, "derep", d + "/prot_merged.fasta", d + "/prot_merged", d + "/nucl_merged.fasta", d + "/nucl_merged"],
+                     "De-replicating the contigs of %s" % gene)
+        write_cp()
+
+
 def after_search(k):
     """the opt-in steps on the last k's graph, in a fixed order behind every checkpoint of a run without them"""
     if opt.coverage:
         contig_coverage(k)
     if opt.match_reads:
         match_reads(k)
+    if opt.derep:
+        derep(k)
 
 
 def main(argv=None):
