@@ -325,6 +325,57 @@ int mgta_seqs_derep(mgta_ctx *, const char *seqs, const uint64_t *offsets /* [n 
 int mgta_ctx_set_derep_hash_bits(mgta_ctx *, int bits);   /* 1..64, default 64 */
 
 /* ------------------------------------------------------------------------------------------------
+ * Alignment of protein sequences to a profile HMM (the place of `hmmalign` in the reference's bin/post_proc.sh:65; HMMER is not
+ * part of the reference and the rule below is this library's own, not hmmalign's).  Needs no graph.  Sequence i =
+ * seqs[offsets[i] .. offsets[i + 1]), L residues x_1 .. x_L; the model is the one mgta_hmm_load was given, M nodes.
+ *   Tables.    msc[j][a], j = 1 .. M: log-odds match score; tsc[X][j]: the transition OUT OF node j, X in MM, MI, MD, IM, II, DM, DD;
+ *              insert emissions are 0; node M has no insert state; node 0's transitions are not used.
+ *   Residues.  a = alpha[x_i]; a letter without a column (x, *, anything else; every byte >= 127) emits 0 in a match state:
+ *              e(j, x) = msc[j][alpha[x]] or 0.
+ *   Mode.      Global in the sequence, local in the model: every residue is emitted, the first one by some match state at no entry
+ *              cost, the last one by some match state, where the alignment ends.  No flanking states.
+ *   Recurrence (i = 1 .. L, j = 1 .. M; fp64, every + one IEEE add, no contraction; whatever is not defined is -inf):
+ *              VM[i][j] = max( 0 if i == 1 (B);  and for i > 1, j > 1:  VM[i-1][j-1] + tsc[MM][j-1] (M),  VI[i-1][j-1] + tsc[IM][j-1] (I),
+ *                              VD[i-1][j-1] + tsc[DM][j-1] (D) ) + e(j, x_i)             (the maximum first, then + e)
+ *              VI[i][j] = max( VM[i-1][j] + tsc[MI][j],   VI[i-1][j] + tsc[II][j] )       i > 1, j < M
+ *              VD[i][j] = max( VM[i][j-1] + tsc[MD][j-1], VD[i][j-1] + tsc[DD][j-1] )     i > 1, j > 1
+ *   Score.     score = max_j VM[L][j].  Ties matter for the traceback only: in every max the candidate written first wins on equality
+ *              (B, M, I, D), and the end column is the LOWEST j that reaches the score.
+ *   Unaligned. L == 0 or score == -inf: status 1, score -inf, every count 0, model_from = model_to = 0, a row of '-', an empty path.
+ *   No table entry may be +inf (-inf is legal), so no NaN arises.
+ * Outputs: recs[i]; cols[i*M .. (i+1)*M) when cols is given: one byte per model column, the residue UPPER-CASED where a match state
+ * emitted it, '-' for a delete state and for every column outside [model_from, model_to]; when path is given, the state path over
+ * 'M', 'I', 'D' in path order at path + offsets[i] + i*M (the caller's offsets as they are), L + n_delete <= L + M - 2 characters,
+ * not terminated, its length in path_len[i] (required with path).  Everything but stats.ms_* and the residency fields is a function
+ * of (tables, sequences); mgta_ctx_set_align_batch (cells = L * M of one batch; 0 = by the context's free memory; a batch always holds
+ * at least one sequence) is a switch for tests and moves no output.  Limits: L <= 4096 residues per sequence and n < 2^31; beyond,
+ * MGTA_EINVAL names the limit.  Device memory: the letters, one traceback byte per cell of a batch and the batch's outputs, accounted
+ * like every other buffer; what does not fit is MGTA_ENOMEM.  MGTA_EINVAL: NULL context / model / recs / offsets (n > 0) / path_len
+ * with path, n < 0, descending offsets, a model of another context (nothing is written).  n = 0: MGTA_OK, stats all zero.
+ * ------------------------------------------------------------------------------------------------ */
+typedef struct mgta_align_rec {
+    double score;                          /* -inf when unaligned */
+    int32_t status;                        /* 0 aligned, 1 unaligned */
+    int32_t model_from, model_to;          /* first and last match column, 1-based (0 when unaligned) */
+    int32_t n_match, n_insert, n_delete;
+} mgta_align_rec;
+typedef struct mgta_align_stats {
+    int64_t n_seqs, n_aligned, n_unaligned;
+    int64_t n_cells;                       /* sum of L * M */
+    int64_t n_batches;
+    int64_t blocks_per_cu;                 /* what the runtime answered for the fill kernel with its LDS (largest over the batches) */
+    int64_t waves_per_block;               /* sequences in flight per workgroup: 4, 2 or 1 by the longest sequence of the batch (smallest over the batches) */
+    int64_t grid_blocks;                   /* workgroups of the largest launch */
+    int64_t lds_bytes;                     /* LDS of a workgroup (largest over the batches) */
+    int64_t msc_in_lds;                    /* 1: every batch read the match scores from LDS; 0: some batch read them from device memory */
+    double ms_fill, ms_trace;              /* HIP events, summed over the batches */
+} mgta_align_stats;
+int mgta_seqs_align(mgta_ctx *, const mgta_hmm *, const char *seqs, const uint64_t *offsets /* [n + 1] */, int64_t n,
+                    mgta_align_rec *recs /* [n] */, uint8_t *cols /* [n * M] or NULL */, char *path /* [offsets[n] + n * M] or NULL */,
+                    int32_t *path_len /* [n] or NULL */, mgta_align_stats *stats /* may be NULL */);
+int mgta_ctx_set_align_batch(mgta_ctx *, int64_t cells);   /* 0 = by memory (default) */
+
+/* ------------------------------------------------------------------------------------------------
  * Seed finder (replaces the read scan of `megagta findstart`, fast_kmer_filter.cpp:108-176,193-215):
  * every window of k nucleotides (k a multiple of 3, k/3 <= 24) of every read, on both strands, whose translation is one of
  * the n_ref reference words.  A word = its residues in the code of prot_kmer.h:31-43 (ARNDCQEGHILKMFPSTWYV = 0..19, '*' = 20),

@@ -98,6 +98,20 @@ class DerepStats(C.Structure):
         return {n: getattr(self, n) for n, _ in self._fields_}
 
 
+class AlignRec(C.Structure):
+    _fields_ = [("score", C.c_double), ("status", C.c_int32), ("model_from", C.c_int32), ("model_to", C.c_int32), ("n_match", C.c_int32),
+                ("n_insert", C.c_int32), ("n_delete", C.c_int32)]
+
+
+class AlignStats(C.Structure):
+    _fields_ = [("n_seqs", C.c_int64), ("n_aligned", C.c_int64), ("n_unaligned", C.c_int64), ("n_cells", C.c_int64), ("n_batches", C.c_int64),
+                ("blocks_per_cu", C.c_int64), ("waves_per_block", C.c_int64), ("grid_blocks", C.c_int64), ("lds_bytes", C.c_int64),
+                ("msc_in_lds", C.c_int64), ("ms_fill", C.c_double), ("ms_trace", C.c_double)]
+
+    def as_dict(self):
+        return {n: getattr(self, n) for n, _ in self._fields_}
+
+
 EDGE_SINK = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_int32, C.c_int32, C.POINTER(C.c_int64), C.POINTER(C.c_uint16), C.c_int64,
                         C.POINTER(C.c_uint16), C.c_int64, C.POINTER(C.c_uint32), C.c_int64)
 CONTIG_SINK = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_void_p, C.c_int64,
@@ -157,6 +171,8 @@ SYMBOLS = {
                                           C.c_void_p]),
     "mgta_seqs_derep": (C.c_int, [C.c_void_p, C.c_char_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "mgta_ctx_set_derep_hash_bits": (C.c_int, [C.c_void_p, C.c_int]),
+    "mgta_seqs_align": (C.c_int, [C.c_void_p, C.c_void_p, C.c_char_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "mgta_ctx_set_align_batch": (C.c_int, [C.c_void_p, C.c_int64]),
     "mgta_sdbg_free": (None, [C.c_void_p]),
     "mgta_sdbg_size": (C.c_int64, [C.c_void_p]),
     "mgta_sdbg_outgoing": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p]),

@@ -133,6 +133,35 @@ class Context:
               "mgta_seqs_derep")
         return dict(status=status[:n], rep=rep[:n], copies=copies[:n], stats=st.as_dict())
 
+    def set_align_batch(self, cells: int = 0):
+        """cells (L * M) of one batch of `align` (0 = the default: by the context's free memory); a batch holds at least one sequence.
+        For tests: the result does not depend on it; only stats["n_batches"] does."""
+        check(self._L.mgta_ctx_set_align_batch(self.h, int(cells)), "mgta_ctx_set_align_batch")
+
+    def align(self, hmm: "DeviceHmm", seqs, cols: bool = True, paths: bool = False) -> dict:
+        """mgta_seqs_align: every sequence of `seqs` (str or bytes) placed on the columns of `hmm` (the rule: include/megagta_hip.h) ->
+        dict(recs = structured array [n] with score, status (0 aligned, 1 unaligned), model_from, model_to, n_match, n_insert, n_delete;
+        cols = uint8[n, M] when asked for: the upper-cased residue where a match state emitted it, `-` elsewhere; paths = list of str
+        over M / I / D when asked for; stats).  Needs no graph."""
+        raw = [s if isinstance(s, (bytes, bytearray)) else str(s).encode() for s in seqs]
+        n, M = len(raw), hmm.M
+        offsets = np.zeros(n + 1, dtype=np.uint64)
+        if n:
+            np.cumsum([len(s) for s in raw], out=offsets[1:])
+        recs = np.zeros(max(1, n), dtype=ALIGN_REC)
+        c = np.zeros((max(1, n), M), dtype=np.uint8) if cols else None
+        p = np.zeros(int(offsets[n]) + n * M + 1, dtype=np.uint8) if paths else None
+        plen = np.zeros(max(1, n), dtype=np.int32) if paths else None
+        st = _lib.AlignStats()
+        check(self._L.mgta_seqs_align(self.h, hmm.h, b"".join(raw), offsets.ctypes.data, n, recs.ctypes.data, c.ctypes.data if cols else None,
+                                      p.ctypes.data if paths else None, plen.ctypes.data if paths else None, C.byref(st)), "mgta_seqs_align")
+        out = dict(recs=recs[:n], stats=st.as_dict())
+        if cols:
+            out["cols"] = c[:n]
+        if paths:
+            out["paths"] = [p[int(offsets[i]) + i * M:int(offsets[i]) + i * M + int(plen[i])].tobytes().decode() for i in range(n)]
+        return out
+
     def release_scratch(self):
         """free the work memory kept between calls (build pool, search pool)"""
         check(self._L.mgta_ctx_release_scratch(self.h), "mgta_ctx_release_scratch")
@@ -365,6 +394,11 @@ class Graph:
             self.h = None
 
     __del__ = free
+
+
+# mgta_align_rec
+ALIGN_REC = np.dtype([("score", np.float64), ("status", np.int32), ("model_from", np.int32), ("model_to", np.int32), ("n_match", np.int32),
+                      ("n_insert", np.int32), ("n_delete", np.int32)], align=True)
 
 
 class DeviceHmm:

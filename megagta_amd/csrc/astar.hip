@@ -17,15 +17,6 @@
 #include "astar_kernel.hpp"
 #include "scan.hpp"
 
-struct mgta_hmm {
-    mgta_ctx *ctx = nullptr;
-    int M = 0, A = 0;
-    mgta::DevBuf tab;            // [msc (M+1)*A][tsc 7*(M+1)][maxm (M+1)][h 3*(M+1)]
-    int8_t col[2][64];           // codon (c1*16+c2*4+c3) -> emission column; [0] codonTable, [1] rc_codonTable; -1 = stop
-    mgta::DevBuf d_col;          // the same 128 bytes on the device
-    size_t n_doubles = 0;
-};
-
 using namespace mgta;
 
 static const char kCodonAA[65] = "KNKNTTTTRSRSIIMIQHQHPPPPRRRRLLLLEDEDAAAAGGGGVVVV*Y*YSSSS*CWCLFLF";   // codon.h:9-106
@@ -101,6 +92,9 @@ int mgta_hmm_load(mgta_ctx *ctx, int M, int A, const double *msc, const double *
         }
         hm->d_col.alloc(128, &ctx->live_bytes, &ctx->peak_bytes);
         MGTA_HIP_CHECK(hipMemcpy(hm->d_col.p, hm->col, 128, hipMemcpyHostToDevice));
+        for (int c = 0; c < 128; ++c) hm->alpha[c] = (int8_t)(c < 127 && alpha[c] >= 0 && alpha[c] < A ? alpha[c] : -1);
+        hm->d_alpha.alloc(128, &ctx->live_bytes, &ctx->peak_bytes);
+        MGTA_HIP_CHECK(hipMemcpy(hm->d_alpha.p, hm->alpha, 128, hipMemcpyHostToDevice));
         ctx_retain(ctx);
         *out = hm.release();
         return MGTA_OK;

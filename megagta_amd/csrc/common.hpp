@@ -135,6 +135,7 @@ struct mgta_ctx {
     // are in the pool; a kept multi-pass stream accumulates them here when the build ran with the switch on (acc_has_large)
     int keep_multiplicity = 0;
     uint64_t coverage_batch_windows = 0;   // mgta_ctx_set_coverage_batch (0 = the library's default)
+    uint64_t align_batch_cells = 0;        // mgta_ctx_set_align_batch: cells (L * M) of one batch of mgta_seqs_align (0 = by free memory)
     int derep_hash_bits = 64;    // mgta_ctx_set_derep_hash_bits: bits of both hashes mgta_seqs_derep keeps (fewer = more collisions, same answers)
     const void *last_large = nullptr;
     uint64_t last_n_large = 0;
@@ -152,6 +153,17 @@ inline void forget_last_build(mgta_ctx *c) {
     c->last_large = nullptr; c->last_n_large = 0;
 }
 }  // namespace mgta
+
+struct mgta_hmm {
+    mgta_ctx *ctx = nullptr;
+    int M = 0, A = 0;
+    mgta::DevBuf tab;            // [msc (M+1)*A][tsc 7*(M+1)][maxm (M+1)][h 3*(M+1)]
+    int8_t col[2][64];           // codon (c1*16+c2*4+c3) -> emission column; [0] codonTable, [1] rc_codonTable; -1 = stop
+    mgta::DevBuf d_col;          // the same 128 bytes on the device
+    int8_t alpha[128];           // residue letter -> emission column, -1 = unknown (and [127])
+    mgta::DevBuf d_alpha;        // the same 128 bytes on the device
+    size_t n_doubles = 0;
+};
 
 struct mgta_reads {
     mgta_ctx *ctx = nullptr;

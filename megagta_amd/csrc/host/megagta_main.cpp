@@ -1005,6 +1005,69 @@ static int main_derep(int argc, char **argv) {
     return 0;
 }
 
+// ---- align: the records of a gene's protein contigs placed on the columns of the gene's profile HMM (the place of `hmmalign` in
+// bin/post_proc.sh:65; the rule is mgta_seqs_align's own).  Needs no graph and leaves a worker's resident graphs alone.  Formats: INTEGRATION.md 2j.
+static int main_align(int argc, char **argv) {
+    if (argc != 4) { fprintf(stderr, "Usage: megagta align <model.hmm> <prot.fasta> <out_prefix>\n"); return 1; }
+    RssLine rss;
+    const std::string fasta = argv[2], out_prefix = argv[3];
+    std::vector<std::string> names, headers;
+    std::string seqs;
+    std::vector<uint64_t> offsets;
+    read_fasta_records(fasta, names, seqs, offsets, &headers);
+    const int64_t n = (int64_t)names.size();
+    const double t0 = now_s();
+    mgta_ctx *ctx = ctx_get();
+    ProfileHmm model;
+    if (!parse_hmm(argv[1], model)) die("cannot open HMM %s", argv[1]);
+    mgta_hmm *hm = nullptr;
+    if (mgta_hmm_load(ctx, model.M, model.A, model.msc.data(), model.tsc.data(), model.max_match.data(), model.h.data(), model.alpha, &hm) != MGTA_OK)
+        die("mgta_hmm_load(%s): %s", argv[1], mgta_last_error());
+    const size_t M = (size_t)model.M;
+    std::vector<mgta_align_rec> recs((size_t)n + 1);
+    std::vector<uint8_t> cols((size_t)n * M + 1);
+    std::vector<char> path(seqs.size() + (size_t)n * M + 1);
+    std::vector<int32_t> plen((size_t)n + 1);
+    mgta_align_stats st;
+    if (mgta_seqs_align(ctx, hm, seqs.data(), offsets.data(), n, recs.data(), cols.data(), path.data(), plen.data(), &st) != MGTA_OK)
+        die("mgta_seqs_align: %s", mgta_last_error());
+    logf("align of %lld records to %zu columns: %lld aligned, %lld unaligned; %lld cells in %lld batches, %lld workgroups of %lld waves, %lld per CU, %lld B of LDS, match "
+         "scores in %s; fill %.1f ms, trace %.1f ms; wall %.3f s", (long long)st.n_seqs, M, (long long)st.n_aligned, (long long)st.n_unaligned, (long long)st.n_cells,
+         (long long)st.n_batches, (long long)st.grid_blocks, (long long)st.waves_per_block, (long long)st.blocks_per_cu, (long long)st.lds_bytes,
+         st.msc_in_lds ? "LDS" : "device memory", st.ms_fill, st.ms_trace, now_s() - t0);
+    std::string fa, table = "#contig\tlen\tstatus\tscore\tmodel_from\tmodel_to\tmatch\tinsert\tdelete\n";
+    char num[64];
+    for (int64_t i = 0; i < n; ++i) {
+        const size_t u = (size_t)i;
+        const mgta_align_rec &r = recs[u];
+        const char *x = seqs.data() + offsets[u];
+        const uint8_t *row = cols.data() + u * M;
+        fa += ">" + headers[u] + "\n";
+        if (r.status != 0) fa.append(M, '-');
+        else {
+            const char *p = path.data() + offsets[u] + u * M;
+            size_t xi = 0, j = (size_t)r.model_from - 1;
+            fa.append((const char *)row, j);
+            for (int32_t s = 0; s < plen[u]; ++s) {
+                if (p[s] == 'I') { const char c = x[xi++]; fa += (c >= 'A' && c <= 'Z') ? (char)(c + 32) : c; }
+                else { fa += (char)row[j++]; xi += p[s] == 'M'; }
+            }
+            fa.append((const char *)row + j, M - j);
+        }
+        fa += "\n";
+        if (r.status != 0) snprintf(num, sizeof num, "-inf");
+        else snprintf(num, sizeof num, "%.4f", r.score);
+        table += names[u] + "\t" + std::to_string(offsets[u + 1] - offsets[u]) + "\t" + (r.status ? "unaligned" : "aligned") + "\t" + num + "\t" +
+                 std::to_string(r.model_from) + "\t" + std::to_string(r.model_to) + "\t" + std::to_string(r.n_match) + "\t" + std::to_string(r.n_insert) + "\t" +
+                 std::to_string(r.n_delete) + "\n";
+    }
+    mgta_hmm_free(hm);
+    if (!write_text_file(out_prefix + "_aligned.fasta", fa)) die("cannot write %s_aligned.fasta", out_prefix.c_str());
+    if (!write_text_file(out_prefix + "_aligned.txt", table)) die("cannot write %s_aligned.txt", out_prefix.c_str());
+    ctx_put(ctx);
+    return 0;
+}
+
 static int dispatch(int argc, char **argv);
 
 // megagta serve: requests on stdin, one per line: the sub-command's argv, tab separated; a field "<PATH" / ">PATH" redirects the
@@ -1092,7 +1155,7 @@ int main(int argc, char **argv) {
 static int dispatch(int argc, char **argv) {
     if (argc < 2) {
         fprintf(stderr, "Usage: %s <sub_program> [sub options]\n    sub-programs on the MI355X hot path:\n        buildgraph    build succinct de Bruijn graph\n"
-                        "        denovo        tips, bubbles, contigs of an intermediate k\n        search        HMM-guided search of gene contigs\n        findstart     find starting kmers of the search\n        coverage      per-contig k-mer coverage and abundance from the graph\n        matchreads    the reads that share a (k+1)-mer with a set of contigs\n        derep         the unique, non-contained records of a FASTA\n        dumpversion   dump version\n", argv[0]);
+                        "        denovo        tips, bubbles, contigs of an intermediate k\n        search        HMM-guided search of gene contigs\n        findstart     find starting kmers of the search\n        coverage      per-contig k-mer coverage and abundance from the graph\n        matchreads    the reads that share a (k+1)-mer with a set of contigs\n        derep         the unique, non-contained records of a FASTA\n        align         protein records placed on the columns of a profile HMM\n        dumpversion   dump version\n", argv[0]);
         return 1;
     }
     std::string sub = argv[1];
@@ -1103,6 +1166,7 @@ static int dispatch(int argc, char **argv) {
     if (sub == "coverage") return main_coverage(argc - 1, argv + 1);
     if (sub == "matchreads") return main_matchreads(argc - 1, argv + 1);
     if (sub == "derep") return main_derep(argc - 1, argv + 1);
+    if (sub == "align") return main_align(argc - 1, argv + 1);
     if (sub == "filterbylen") return main_filterbylen(argc - 1, argv + 1);
     if (sub == "translate") return main_translate(argc - 1, argv + 1);
     if (sub == "buildlib") {                                             // build_read_lib.cpp:8-20 (host only: file formats, no kernel)
@@ -1205,6 +1269,6 @@ static int dispatch(int argc, char **argv) {
         return 0;
     }
     if (sub == "dumpversion") { printf("%s\n", mgta_version()); return 0; }
-    fprintf(stderr, "sub-command '%s' is not built here (buildlib, buildgraph, denovo, findstart, search, coverage, matchreads, derep, filterbylen, translate are): run it with the reference's megagta binary\n", sub.c_str());
+    fprintf(stderr, "sub-command '%s' is not built here (buildlib, buildgraph, denovo, findstart, search, coverage, matchreads, derep, align, filterbylen, translate are): run it with the reference's megagta binary\n", sub.c_str());
     return 1;
 }

@@ -43,7 +43,11 @@ USAGE = """Usage:
                      that share a (k+1)-mer with the gene's contigs on either strand, as `>r<index in the library>` records (GPU 0)
     --derep          after the last k (and after --coverage and --match-reads): per gene contigs/<gene>/prot_merged_rmdup.fasta, the protein
                      contigs that are neither a copy of an earlier one nor a piece of a longer one, nucl_merged_rmdup.fasta, their nucleotide
-                     records, and prot_merged_rmdup_map.txt, what became of every contig (GPU 0)"""
+                     records, and prot_merged_rmdup_map.txt, what became of every contig (GPU 0)
+    --align          after the last k (and after --coverage, --match-reads and --derep): per gene the protein contigs placed on the columns
+                     of the gene's forward model: contigs/<gene>/prot_merged_aligned.fasta (A2M rows) and prot_merged_aligned.txt (score,
+                     columns and counts per contig); with --derep the input is prot_merged_rmdup.fasta and the files are
+                     prot_merged_rmdup_aligned.* (GPU 0)"""
 
 
 class Usage(Exception):
@@ -77,6 +81,7 @@ class Opt:
         self.coverage = False
         self.match_reads = False
         self.derep = False
+        self.align = False
 
 
 opt = Opt()
@@ -84,7 +89,7 @@ cp = 0
 
 LONG = ["help", "read=", "12=", "out-dir=", "memory=", "gpu-mem=", "min-contig-len=", "num-cpu-threads=", "kmin-1pass", "k-list=",
         "min-count=", "max-tip-len=", "no-mercy", "keep-tmp-files", "mem-flag=", "version", "verbose", "continue", "gene-list=",
-        "prune-len=", "low-cov-penalty=", "bin=", "one-process-per-step", "gpus=", "coverage", "match-reads", "derep"]
+        "prune-len=", "low-cov-penalty=", "bin=", "one-process-per-step", "gpus=", "coverage", "match-reads", "derep", "align"]
 
 
 def parse_opt(argv):
@@ -133,6 +138,7 @@ def parse_opt(argv):
         elif o == "--coverage": opt.coverage = True
         elif o == "--match-reads": opt.match_reads = True
         elif o == "--derep": opt.derep = True
+        elif o == "--align": opt.align = True
         else:
             raise Usage("Invalid option " + o)
     opt.temp_dir = opt.out_dir + "tmp/"
@@ -597,6 +603,17 @@ def derep(k):
         write_cp()
 
 
+def align(k):
+    """--align: per gene the protein contigs placed on the columns of the gene's forward model (`megagta align`, GPU 0; no graph is
+    needed, k only names the step).  The input is what --derep kept when that flag runs too.  Its checkpoints come after every other
+    checkpoint, those of --coverage, --match-reads and --derep included, so `--continue` works under any of them."""
+    for gene in opt.gene_info:
+        prefix = opt.out_dir + "contigs/" + gene + ("/prot_merged_rmdup" if opt.derep else "/prot_merged")
+        if should_run():
+            run_step([opt.bin, "align", opt.gene_info[gene][0], prefix + ".fasta", prefix], "Aligning the contigs of %s to its model" % gene)
+        write_cp()
+
+
 def after_search(k):
     """the opt-in steps on the last k's graph, in a fixed order behind every checkpoint of a run without them"""
     if opt.coverage:
@@ -605,6 +622,8 @@ def after_search(k):
         match_reads(k)
     if opt.derep:
         derep(k)
+    if opt.align:
+        align(k)
 
 
 def main(argv=None):
