@@ -376,6 +376,71 @@ int mgta_seqs_align(mgta_ctx *, const mgta_hmm *, const char *seqs, const uint64
 int mgta_ctx_set_align_batch(mgta_ctx *, int64_t cells);   /* 0 = by memory (default) */
 
 /* ------------------------------------------------------------------------------------------------
+ * Complete-linkage clusters of aligned rows ("cluster at 99% aa identity", the reference's bin/post_proc.sh:57-85: `Clustering.jar
+ * dmatrix -l 25`, `cluster`, `rep-seqs -l <cutoff>`, from a submodule the reference does not ship; the rule below is this library's
+ * own and is not checked against the jars).  Needs no graph.  Input: n rows of M bytes, row r = rows[r*M .. (r+1)*M), the `cols` rows
+ * of mgta_seqs_align: a byte is '-' or a residue; lens[n], the unaligned length of each record; min_overlap >= 1; cutoff, an fp64 in
+ * [0, 1].
+ *   Pair counts.  For i < j: n_overlap(i,j) = the number of columns where both rows hold a byte other than '-'; n_diff(i,j) = the
+ *                 number of those columns where the two bytes differ.  Bytes are compared byte for byte, no case folding; every value
+ *                 0 .. 255 other than '-' is a residue.  Inserted residues are not in the rows and do not count; a column where only
+ *                 one row has a residue does not count either way.
+ *   Kept pair.    n_overlap >= min_overlap and (double)n_diff <= cutoff * (double)n_overlap: one IEEE multiply and one compare, no
+ *                 contraction.  Every other pair is APART.
+ *   Clusters.     A row with no residue at all is UNALIGNED: in no cluster (cluster -1, rep -1).  Every other row starts as a cluster
+ *                 of its own.  Then, repeatedly: of every pair of clusters (A, B), min(A) < min(B), whose cross pairs are ALL kept,
+ *                 take the one with the smallest complete-linkage distance = the largest n_diff / n_overlap over its cross pairs
+ *                 (fractions compared exactly, by cross-multiplication in 64-bit integers, never in floating point; ties: the lower
+ *                 min(A), then the lower min(B)) and merge it; stop when no such pair exists.  This is complete linkage cut at
+ *                 `cutoff`.  Only kept pairs can ever decide a merge, so the sparse list of kept pairs is all the linkage needs.
+ *   Numbering.    Clusters are numbered 0, 1, .. by their lowest member.  A cluster's representative is the member with the largest
+ *                 lens, the lowest index on a tie (`rep-seqs -l`).
+ * mgta_rows_pairs gives the kept pairs sorted by (i, j).  At most `cap` pairs are stored: *n_pairs is the number found; when it
+ * exceeds cap NOTHING is stored (call again with a buffer that holds them; pairs = NULL with cap = 0 only counts).
+ * Both calls hold every kept pair on the host while they run, also when the count then exceeds cap: a caller that expects many pairs
+ * saves the second device pass by passing a generous buffer at once.
+ * mgta_rows_cluster runs the pairs on the device and the linkage on the host inside the library (connected components of the
+ * kept-pair graph first, then each component with a priority queue).  mgta_pairs_link is that linkage alone, host only, no context
+ * and no device: the kept pairs of n rows ascending by (i, j) as mgta_rows_pairs gives them, n_residues[i] = the residue columns of
+ * row i (0 = unaligned), lens; the same four outputs and the linkage's fields of stats.  MGTA_EINVAL: a pair outside 0 <= i < j < n,
+ * n_overlap = 0, n_diff > n_overlap, a row of a pair without residues, pairs not ascending, n_residues outside 0 .. 65535, NULLs.  cluster[i], rep[i]: the cluster's number and the representative's
+ * row; rep_diff[i], rep_overlap[i]: the counts of row i against its representative (every member of a cluster is a kept pair with
+ * every other): for the representative itself 0 and its own number of residue columns, for an unaligned row 0 and 0.
+ * Every output is a function of the inputs only, except stats.ms_*, the counters of work done (n_tiles, n_link_pops) and the
+ * residency fields.  mgta_ctx_set_cluster_tile sets the rows of one row block (0 = the default, 4096): the device works on one row
+ * block x row block tile at a time, so its memory is bounded whatever n is (4 bytes per pair of a tile, the tile's kept pairs, the
+ * rows once); a switch for tests, the outputs do not move.  Limits: n < 2^31 and 1 <= M < 65536 (both counts fit 16 bits); beyond
+ * either the call returns MGTA_EINVAL, names the limit and writes nothing.  The rows (1.125 bytes per input byte, laid out once) must fit
+ * the device memory the call may use, else MGTA_ENOMEM; the linkage holds fewer than 2^32 kept pairs, else MGTA_ENOMEM before it starts.  Kept pairs that do not fit the memory the call may use:
+ * MGTA_ENOMEM with the count in the message; nothing is truncated.  MGTA_EINVAL: NULL context, n < 0, NULL rows / lens / outputs /
+ * n_pairs with n > 0, NULL pairs with cap > 0, cap < 0, min_overlap < 1, cutoff outside [0, 1] or NaN (nothing is written).
+ * n = 0: MGTA_OK, stats all zero.
+ * ------------------------------------------------------------------------------------------------ */
+typedef struct mgta_row_pair { int32_t i, j; uint16_t n_diff, n_overlap; } mgta_row_pair;   /* i < j, kept pairs only */
+typedef struct mgta_cluster_stats {
+    int64_t n_rows, n_unaligned;
+    int64_t n_pairs_kept;
+    int64_t n_clusters, n_singletons, largest_cluster;   /* mgta_rows_cluster only */
+    int64_t n_components;                  /* connected components of the kept-pair graph over the aligned rows (mgta_rows_cluster only) */
+    int64_t n_tiles;                       /* row block x row block tiles the device worked on */
+    int64_t n_link_pops;                   /* entries the linkage took from its queues, stale ones included */
+    int64_t blocks_per_cu;                 /* what the runtime answered for the pairs kernel */
+    int64_t grid_blocks;                   /* workgroups of the largest pairs launch */
+    int64_t lds_bytes;                     /* LDS of a workgroup of the pairs kernel */
+    int64_t peak_bytes;                    /* most device memory the call held at once */
+    double ms_pairs, ms_link;              /* HIP events summed over the tiles (layout, pairs, count, scan, write); host clock of the linkage */
+} mgta_cluster_stats;
+int mgta_rows_pairs(mgta_ctx *, const uint8_t *rows /* [n * M] */, int64_t n, int64_t M, int64_t min_overlap, double cutoff,
+                    mgta_row_pair *pairs /* [cap] or NULL */, int64_t cap, int64_t *n_pairs, mgta_cluster_stats *stats /* may be NULL */);
+int mgta_rows_cluster(mgta_ctx *, const uint8_t *rows /* [n * M] */, const int64_t *lens /* [n] */, int64_t n, int64_t M, int64_t min_overlap,
+                      double cutoff, int32_t *cluster /* [n] */, int64_t *rep /* [n] */, uint16_t *rep_diff /* [n] */,
+                      uint16_t *rep_overlap /* [n] */, mgta_cluster_stats *stats /* may be NULL */);
+int mgta_pairs_link(const mgta_row_pair *pairs /* [n_pairs], ascending by (i, j) */, int64_t n_pairs, const int32_t *n_residues /* [n] */,
+                    const int64_t *lens /* [n] */, int64_t n, int32_t *cluster, int64_t *rep, uint16_t *rep_diff, uint16_t *rep_overlap,
+                    mgta_cluster_stats *stats /* may be NULL */);
+int mgta_ctx_set_cluster_tile(mgta_ctx *, int64_t rows_per_tile);   /* 0 = default */
+
+/* ------------------------------------------------------------------------------------------------
  * Seed finder (replaces the read scan of `megagta findstart`, fast_kmer_filter.cpp:108-176,193-215):
  * every window of k nucleotides (k a multiple of 3, k/3 <= 24) of every read, on both strands, whose translation is one of
  * the n_ref reference words.  A word = its residues in the code of prot_kmer.h:31-43 (ARNDCQEGHILKMFPSTWYV = 0..19, '*' = 20),

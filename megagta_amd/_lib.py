@@ -112,6 +112,20 @@ class AlignStats(C.Structure):
         return {n: getattr(self, n) for n, _ in self._fields_}
 
 
+class RowPair(C.Structure):
+    _fields_ = [("i", C.c_int32), ("j", C.c_int32), ("n_diff", C.c_uint16), ("n_overlap", C.c_uint16)]
+
+
+class ClusterStats(C.Structure):
+    _fields_ = [("n_rows", C.c_int64), ("n_unaligned", C.c_int64), ("n_pairs_kept", C.c_int64), ("n_clusters", C.c_int64), ("n_singletons", C.c_int64),
+                ("largest_cluster", C.c_int64), ("n_components", C.c_int64), ("n_tiles", C.c_int64), ("n_link_pops", C.c_int64),
+                ("blocks_per_cu", C.c_int64), ("grid_blocks", C.c_int64), ("lds_bytes", C.c_int64), ("peak_bytes", C.c_int64),
+                ("ms_pairs", C.c_double), ("ms_link", C.c_double)]
+
+    def as_dict(self):
+        return {n: getattr(self, n) for n, _ in self._fields_}
+
+
 EDGE_SINK = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_int32, C.c_int32, C.POINTER(C.c_int64), C.POINTER(C.c_uint16), C.c_int64,
                         C.POINTER(C.c_uint16), C.c_int64, C.POINTER(C.c_uint32), C.c_int64)
 CONTIG_SINK = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_void_p, C.c_int64,
@@ -173,6 +187,11 @@ SYMBOLS = {
     "mgta_ctx_set_derep_hash_bits": (C.c_int, [C.c_void_p, C.c_int]),
     "mgta_seqs_align": (C.c_int, [C.c_void_p, C.c_void_p, C.c_char_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "mgta_ctx_set_align_batch": (C.c_int, [C.c_void_p, C.c_int64]),
+    "mgta_rows_pairs": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_int64, C.c_int64, C.c_double, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p]),
+    "mgta_rows_cluster": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_int64, C.c_int64, C.c_double, C.c_void_p, C.c_void_p, C.c_void_p,
+                                    C.c_void_p, C.c_void_p]),
+    "mgta_pairs_link": (C.c_int, [C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "mgta_ctx_set_cluster_tile": (C.c_int, [C.c_void_p, C.c_int64]),
     "mgta_sdbg_free": (None, [C.c_void_p]),
     "mgta_sdbg_size": (C.c_int64, [C.c_void_p]),
     "mgta_sdbg_outgoing": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p]),

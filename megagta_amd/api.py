@@ -162,6 +162,59 @@ class Context:
             out["paths"] = [p[int(offsets[i]) + i * M:int(offsets[i]) + i * M + int(plen[i])].tobytes().decode() for i in range(n)]
         return out
 
+    def set_cluster_tile(self, rows: int = 0):
+        """rows of one row block of `row_pairs` / `cluster` (0 = the default): the device works on one row block x row block tile at a
+        time.  For tests: the result does not depend on it; only stats["n_tiles"] does."""
+        check(self._L.mgta_ctx_set_cluster_tile(self.h, int(rows)), "mgta_ctx_set_cluster_tile")
+
+    @staticmethod
+    def _rows(rows) -> np.ndarray:
+        """uint8[n, M] from an array, or from a list of equally long str / bytes"""
+        if isinstance(rows, np.ndarray):
+            r = np.ascontiguousarray(rows, dtype=np.uint8)
+        else:
+            raw = [s if isinstance(s, (bytes, bytearray)) else str(s).encode("latin-1") for s in rows]
+            if len({len(s) for s in raw}) > 1:
+                raise ValueError("rows must all have the same width")
+            r = np.frombuffer(b"".join(raw), dtype=np.uint8).reshape(len(raw), len(raw[0]) if raw else 0)
+        if r.ndim != 2:
+            raise ValueError("rows must be n x M")
+        return r
+
+    def row_pairs(self, rows, min_overlap: int, cutoff: float) -> dict:
+        """mgta_rows_pairs: the kept pairs of the aligned rows (the rule: include/megagta_hip.h) -> dict(pairs = structured array with
+        i, j, n_diff, n_overlap, sorted by (i, j); stats).  Needs no graph.  One call counts, a second one fills: the all-pairs pass runs
+        twice on the device, which is the price of an exactly sized buffer; a caller of the C entry that expects many pairs passes a
+        generous buffer at once (`cluster` runs the pass once)."""
+        r = self._rows(rows)
+        n, M = r.shape
+        cnt, st = C.c_int64(0), _lib.ClusterStats()
+        check(self._L.mgta_rows_pairs(self.h, r.ctypes.data, n, M, int(min_overlap), float(cutoff), None, 0, C.byref(cnt), C.byref(st)), "mgta_rows_pairs")
+        pairs = np.zeros(max(1, cnt.value), dtype=ROW_PAIR)
+        if cnt.value:
+            got = C.c_int64(0)
+            check(self._L.mgta_rows_pairs(self.h, r.ctypes.data, n, M, int(min_overlap), float(cutoff), pairs.ctypes.data, cnt.value, C.byref(got), C.byref(st)),
+                  "mgta_rows_pairs")
+            if got.value != cnt.value:
+                raise MegaGtaError(f"mgta_rows_pairs counted {cnt.value} pairs, then {got.value}")
+        return dict(pairs=pairs[:cnt.value], stats=st.as_dict())
+
+    def cluster(self, rows, lens, min_overlap: int, cutoff: float) -> dict:
+        """mgta_rows_cluster: complete-linkage clusters of the aligned rows cut at `cutoff` -> dict(cluster = int32[n], -1 for a row
+        without residues; rep = int64[n], the row of the cluster's representative (largest lens, lowest index); rep_diff, rep_overlap =
+        uint16[n], the counts of a row against its representative; stats).  Needs no graph."""
+        r = self._rows(rows)
+        n, M = r.shape
+        ln = np.ascontiguousarray(lens, dtype=np.int64)
+        if ln.shape != (n,):
+            raise ValueError("lens must hold one length per row")
+        cl, rep = np.zeros(max(1, n), dtype=np.int32), np.zeros(max(1, n), dtype=np.int64)
+        rd, ro = np.zeros(max(1, n), dtype=np.uint16), np.zeros(max(1, n), dtype=np.uint16)
+        st = _lib.ClusterStats()
+        check(self._L.mgta_rows_cluster(self.h, r.ctypes.data, ln.ctypes.data, n, M, int(min_overlap), float(cutoff), cl.ctypes.data, rep.ctypes.data,
+                                        rd.ctypes.data, ro.ctypes.data, C.byref(st)), "mgta_rows_cluster")
+        return dict(cluster=cl[:n], rep=rep[:n], rep_diff=rd[:n], rep_overlap=ro[:n], stats=st.as_dict())
+
     def release_scratch(self):
         """free the work memory kept between calls (build pool, search pool)"""
         check(self._L.mgta_ctx_release_scratch(self.h), "mgta_ctx_release_scratch")
@@ -399,6 +452,27 @@ class Graph:
 # mgta_align_rec
 ALIGN_REC = np.dtype([("score", np.float64), ("status", np.int32), ("model_from", np.int32), ("model_to", np.int32), ("n_match", np.int32),
                       ("n_insert", np.int32), ("n_delete", np.int32)], align=True)
+
+
+def link_pairs(pairs, n_residues, lens) -> dict:
+    """mgta_pairs_link: the linkage of `Context.cluster` alone, on the host, no context and no device: pairs = the kept pairs of n rows
+    ascending by (i, j) (a ROW_PAIR array, or tuples (i, j, n_diff, n_overlap)), n_residues = the residue columns of every row
+    (0 = unaligned), lens -> dict(cluster, rep, rep_diff, rep_overlap, stats)."""
+    p = np.ascontiguousarray(pairs, dtype=ROW_PAIR) if isinstance(pairs, np.ndarray) else np.array([tuple(x) for x in pairs], dtype=ROW_PAIR)
+    nr, ln = np.ascontiguousarray(n_residues, dtype=np.int32), np.ascontiguousarray(lens, dtype=np.int64)
+    n = nr.size
+    if ln.shape != (n,) or nr.ndim != 1:
+        raise ValueError("n_residues and lens must hold one value per row")
+    cl, rep = np.zeros(max(1, n), dtype=np.int32), np.zeros(max(1, n), dtype=np.int64)
+    rd, ro = np.zeros(max(1, n), dtype=np.uint16), np.zeros(max(1, n), dtype=np.uint16)
+    st = _lib.ClusterStats()
+    check(_lib.load().mgta_pairs_link(p.ctypes.data if p.size else None, p.size, nr.ctypes.data, ln.ctypes.data, n, cl.ctypes.data, rep.ctypes.data, rd.ctypes.data,
+                                      ro.ctypes.data, C.byref(st)), "mgta_pairs_link")
+    return dict(cluster=cl[:n], rep=rep[:n], rep_diff=rd[:n], rep_overlap=ro[:n], stats=st.as_dict())
+
+
+# mgta_row_pair
+ROW_PAIR = np.dtype([("i", np.int32), ("j", np.int32), ("n_diff", np.uint16), ("n_overlap", np.uint16)], align=True)
 
 
 class DeviceHmm:

@@ -1068,6 +1068,104 @@ static int main_align(int argc, char **argv) {
     return 0;
 }
 
+// ---- cluster: complete-linkage clusters of a gene's aligned protein contigs, their representatives and the nucleotide records those select
+// ("cluster at 99% aa identity", bin/post_proc.sh:57-85; the rule is mgta_rows_cluster's own).  Needs no graph and leaves a worker's resident
+// graphs alone.  Formats: INTEGRATION.md 2k.
+static int main_cluster(int argc, char **argv) {
+    if (argc != 5 && argc != 7) {
+        fprintf(stderr, "Usage: megagta cluster <aligned.fasta> <out_prefix> <dist_cutoff> <min_overlap> [<nucl.fasta> <nucl_out_prefix>]\n");
+        return 1;
+    }
+    RssLine rss;
+    const std::string fasta = argv[1], out_prefix = argv[2];
+    char *end = nullptr;
+    const double cutoff = strtod(argv[3], &end);
+    if (end == argv[3] || *end) { fprintf(stderr, "    [ERROR] cluster: dist_cutoff '%s' is not a number\n", argv[3]); return 1; }
+    const long long min_overlap = strtoll(argv[4], &end, 10);
+    if (end == argv[4] || *end) { fprintf(stderr, "    [ERROR] cluster: min_overlap '%s' is not an integer\n", argv[4]); return 1; }
+    std::vector<std::string> names, headers, nnames, nheaders;
+    std::string lines, nseqs;
+    std::vector<uint64_t> offsets, noffsets;
+    read_fasta_records(fasta, names, lines, offsets, &headers);
+    const int64_t n = (int64_t)names.size();
+    // the row of a record: its A2M line without the lower-case (inserted) residues; its length: the characters that are not '-'
+    std::string rows;
+    std::vector<int64_t> lens((size_t)n + 1);
+    size_t M = 1;
+    for (int64_t i = 0; i < n; ++i) {
+        const size_t before = rows.size();
+        int64_t len = 0;
+        for (uint64_t p = offsets[(size_t)i]; p < offsets[(size_t)i + 1]; ++p) {
+            const char c = lines[p];
+            len += c != '-';
+            if (!(c >= 'a' && c <= 'z')) rows += c;
+        }
+        lens[(size_t)i] = len;
+        if (i == 0) M = rows.size();
+        if (rows.size() - before != M || M == 0) {
+            fprintf(stderr, "    [ERROR] cluster: record %lld (%s) of %s has %zu columns, the first record has %zu: nothing written\n", (long long)i, names[(size_t)i].c_str(),
+                    fasta.c_str(), rows.size() - before, M);
+            return 1;
+        }
+    }
+    if (argc == 7) {
+        // `derep`'s check: one nucleotide record per protein record, in order and under the same name
+        read_fasta_records(argv[5], nnames, nseqs, noffsets, &nheaders);
+        if (nnames.size() != names.size()) {
+            fprintf(stderr, "    [ERROR] cluster: %s holds %zu records, %s holds %zu: nothing written\n", fasta.c_str(), names.size(), argv[5], nnames.size());
+            return 1;
+        }
+        for (int64_t i = 0; i < n; ++i)
+            if (nnames[(size_t)i] != names[(size_t)i]) {
+                fprintf(stderr, "    [ERROR] cluster: record %lld is %s in %s and %s in %s: nothing written\n", (long long)i, names[(size_t)i].c_str(), fasta.c_str(),
+                        nnames[(size_t)i].c_str(), argv[5]);
+                return 1;
+            }
+    }
+    const double t0 = now_s();
+    mgta_ctx *ctx = ctx_get();
+    std::vector<int32_t> cluster((size_t)n + 1);
+    std::vector<int64_t> rep((size_t)n + 1);
+    std::vector<uint16_t> rep_diff((size_t)n + 1), rep_overlap((size_t)n + 1);
+    mgta_cluster_stats st;
+    if (mgta_rows_cluster(ctx, (const uint8_t *)rows.data(), lens.data(), n, (int64_t)M, min_overlap, cutoff, cluster.data(), rep.data(), rep_diff.data(), rep_overlap.data(),
+                          &st) != MGTA_OK) {
+        fprintf(stderr, "    [ERROR] cluster: %s: nothing written\n", mgta_last_error());
+        ctx_put(ctx);
+        return 1;
+    }
+    logf("cluster of %lld rows of %zu columns at %g, overlap >= %lld: %lld unaligned, %lld kept pairs, %lld components, %lld clusters (%lld singletons, largest %lld); "
+         "%lld tiles, %lld workgroups at most, %lld per CU, %lld B of LDS, peak %lld B; pairs %.1f ms, linkage %.1f ms; wall %.3f s", (long long)st.n_rows, M, cutoff,
+         min_overlap, (long long)st.n_unaligned, (long long)st.n_pairs_kept, (long long)st.n_components, (long long)st.n_clusters, (long long)st.n_singletons,
+         (long long)st.largest_cluster, (long long)st.n_tiles, (long long)st.grid_blocks, (long long)st.blocks_per_cu, (long long)st.lds_bytes, (long long)st.peak_bytes,
+         st.ms_pairs, st.ms_link, now_s() - t0);
+    std::string table = "#contig\tstatus\tcluster\trep\tlen\tn_diff\tn_overlap\n", reps, nreps;
+    for (int64_t i = 0; i < n; ++i) {
+        const size_t u = (size_t)i;
+        const bool unaligned = cluster[u] < 0, is_rep = !unaligned && rep[u] == i;
+        table += names[u] + "\t" + (unaligned ? "unaligned" : is_rep ? "rep" : "member") + "\t" + (unaligned ? std::string("-") : std::to_string(cluster[u])) + "\t" +
+                 (unaligned ? std::string("-") : names[(size_t)rep[u]]) + "\t" + std::to_string(lens[u]) + "\t" + std::to_string(rep_diff[u]) + "\t" +
+                 std::to_string(rep_overlap[u]) + "\n";
+        if (!is_rep) continue;
+        reps += ">" + headers[u] + "\n";
+        for (uint64_t p = offsets[u]; p < offsets[u + 1]; ++p) {
+            const char c = lines[p];
+            if (c != '-') reps += (c >= 'a' && c <= 'z') ? (char)(c - 32) : c;
+        }
+        reps += "\n";
+        if (argc == 7) {
+            nreps += ">" + nheaders[u] + "\n";
+            nreps.append(nseqs, (size_t)noffsets[u], (size_t)(noffsets[u + 1] - noffsets[u]));
+            nreps += "\n";
+        }
+    }
+    if (!write_text_file(out_prefix + "_clust.txt", table)) die("cannot write %s_clust.txt", out_prefix.c_str());
+    if (!write_text_file(out_prefix + "_rep_seqs.fasta", reps)) die("cannot write %s_rep_seqs.fasta", out_prefix.c_str());
+    if (argc == 7 && !write_text_file(std::string(argv[6]) + "_rep_seqs.fasta", nreps)) die("cannot write %s_rep_seqs.fasta", argv[6]);
+    ctx_put(ctx);
+    return 0;
+}
+
 static int dispatch(int argc, char **argv);
 
 // megagta serve: requests on stdin, one per line: the sub-command's argv, tab separated; a field "<PATH" / ">PATH" redirects the
@@ -1155,7 +1253,7 @@ int main(int argc, char **argv) {
 static int dispatch(int argc, char **argv) {
     if (argc < 2) {
         fprintf(stderr, "Usage: %s <sub_program> [sub options]\n    sub-programs on the MI355X hot path:\n        buildgraph    build succinct de Bruijn graph\n"
-                        "        denovo        tips, bubbles, contigs of an intermediate k\n        search        HMM-guided search of gene contigs\n        findstart     find starting kmers of the search\n        coverage      per-contig k-mer coverage and abundance from the graph\n        matchreads    the reads that share a (k+1)-mer with a set of contigs\n        derep         the unique, non-contained records of a FASTA\n        align         protein records placed on the columns of a profile HMM\n        dumpversion   dump version\n", argv[0]);
+                        "        denovo        tips, bubbles, contigs of an intermediate k\n        search        HMM-guided search of gene contigs\n        findstart     find starting kmers of the search\n        coverage      per-contig k-mer coverage and abundance from the graph\n        matchreads    the reads that share a (k+1)-mer with a set of contigs\n        derep         the unique, non-contained records of a FASTA\n        align         protein records placed on the columns of a profile HMM\n        cluster       complete-linkage clusters of aligned protein records\n        dumpversion   dump version\n", argv[0]);
         return 1;
     }
     std::string sub = argv[1];
@@ -1167,6 +1265,7 @@ static int dispatch(int argc, char **argv) {
     if (sub == "matchreads") return main_matchreads(argc - 1, argv + 1);
     if (sub == "derep") return main_derep(argc - 1, argv + 1);
     if (sub == "align") return main_align(argc - 1, argv + 1);
+    if (sub == "cluster") return main_cluster(argc - 1, argv + 1);
     if (sub == "filterbylen") return main_filterbylen(argc - 1, argv + 1);
     if (sub == "translate") return main_translate(argc - 1, argv + 1);
     if (sub == "buildlib") {                                             // build_read_lib.cpp:8-20 (host only: file formats, no kernel)
@@ -1269,6 +1368,6 @@ static int dispatch(int argc, char **argv) {
         return 0;
     }
     if (sub == "dumpversion") { printf("%s\n", mgta_version()); return 0; }
-    fprintf(stderr, "sub-command '%s' is not built here (buildlib, buildgraph, denovo, findstart, search, coverage, matchreads, derep, align, filterbylen, translate are): run it with the reference's megagta binary\n", sub.c_str());
+    fprintf(stderr, "sub-command '%s' is not built here (buildlib, buildgraph, denovo, findstart, search, coverage, matchreads, derep, align, cluster, filterbylen, translate are): run it with the reference's megagta binary\n", sub.c_str());
     return 1;
 }

@@ -47,7 +47,12 @@ USAGE = """Usage:
     --align          after the last k (and after --coverage, --match-reads and --derep): per gene the protein contigs placed on the columns
                      of the gene's forward model: contigs/<gene>/prot_merged_aligned.fasta (A2M rows) and prot_merged_aligned.txt (score,
                      columns and counts per contig); with --derep the input is prot_merged_rmdup.fasta and the files are
-                     prot_merged_rmdup_aligned.* (GPU 0)"""
+                     prot_merged_rmdup_aligned.* (GPU 0)
+    --cluster        needs --align; after its steps: per gene the complete-linkage clusters of the aligned rows,
+                     contigs/<gene>/prot_merged[_rmdup]_clust.txt (what became of every contig), prot_merged[_rmdup]_rep_seqs.fasta and
+                     nucl_merged[_rmdup]_rep_seqs.fasta (one representative per cluster: the longest member) (GPU 0)
+    --cluster-dist D          largest share of differing columns inside a cluster [0.01: the reference's "99% aa identity"]
+    --cluster-min-overlap N   columns two contigs must share to be compared at all [25: the reference's `dmatrix -l 25`]"""
 
 
 class Usage(Exception):
@@ -82,6 +87,9 @@ class Opt:
         self.match_reads = False
         self.derep = False
         self.align = False
+        self.cluster = False
+        self.cluster_dist = 0.01
+        self.cluster_min_overlap = 25
 
 
 opt = Opt()
@@ -89,7 +97,8 @@ cp = 0
 
 LONG = ["help", "read=", "12=", "out-dir=", "memory=", "gpu-mem=", "min-contig-len=", "num-cpu-threads=", "kmin-1pass", "k-list=",
         "min-count=", "max-tip-len=", "no-mercy", "keep-tmp-files", "mem-flag=", "version", "verbose", "continue", "gene-list=",
-        "prune-len=", "low-cov-penalty=", "bin=", "one-process-per-step", "gpus=", "coverage", "match-reads", "derep", "align"]
+        "prune-len=", "low-cov-penalty=", "bin=", "one-process-per-step", "gpus=", "coverage", "match-reads", "derep", "align", "cluster",
+        "cluster-dist=", "cluster-min-overlap="]
 
 
 def parse_opt(argv):
@@ -139,6 +148,9 @@ def parse_opt(argv):
         elif o == "--match-reads": opt.match_reads = True
         elif o == "--derep": opt.derep = True
         elif o == "--align": opt.align = True
+        elif o == "--cluster": opt.cluster = True
+        elif o == "--cluster-dist": opt.cluster_dist = float(v)
+        elif o == "--cluster-min-overlap": opt.cluster_min_overlap = int(v)
         else:
             raise Usage("Invalid option " + o)
     opt.temp_dir = opt.out_dir + "tmp/"
@@ -188,6 +200,12 @@ def detect_available_mem():
 
 
 def check_opt():
+    if opt.cluster and not opt.align:
+        raise Usage("--cluster needs --align: it clusters the rows that step writes")
+    if not 0 <= opt.cluster_dist <= 1:
+        raise Usage("--cluster-dist should be between [0, 1]")
+    if opt.cluster_min_overlap < 1:
+        raise Usage("--cluster-min-overlap should be >= 1")
     if opt.host_mem <= 0:
         raise Usage("Please specify a positive number for -m flag.")
     if opt.host_mem < 1:
@@ -614,6 +632,20 @@ def align(k):
         write_cp()
 
 
+def cluster(k):
+    """--cluster: per gene the complete-linkage clusters of the rows --align wrote, one representative per cluster and the nucleotide
+    records of the representatives (`megagta cluster`, GPU 0; no graph is needed, k only names the step).  The files carry `_rmdup` when
+    --derep runs too.  Its checkpoints come after every other checkpoint, those of --align included, so `--continue` works under any
+    combination."""
+    stem = "_merged_rmdup" if opt.derep else "_merged"
+    for gene in opt.gene_info:
+        d = opt.out_dir + "contigs/" + gene
+        if should_run():
+            run_step([opt.bin, "cluster", d + "/prot" + stem + "_aligned.fasta", d + "/prot" + stem, repr(opt.cluster_dist), str(opt.cluster_min_overlap),
+                      d + "/nucl" + stem + ".fasta", d + "/nucl" + stem], "Clustering the aligned contigs of %s" % gene)
+        write_cp()
+
+
 def after_search(k):
     """the opt-in steps on the last k's graph, in a fixed order behind every checkpoint of a run without them"""
     if opt.coverage:
@@ -624,6 +656,8 @@ def after_search(k):
         derep(k)
     if opt.align:
         align(k)
+    if opt.cluster:
+        cluster(k)
 
 
 def main(argv=None):
