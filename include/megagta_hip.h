@@ -441,6 +441,69 @@ int mgta_pairs_link(const mgta_row_pair *pairs /* [n_pairs], ascending by (i, j)
 int mgta_ctx_set_cluster_tile(mgta_ctx *, int64_t rows_per_tile);   /* 0 = default */
 
 /* ------------------------------------------------------------------------------------------------
+ * The nearest reference protein of every contig (the place of FrameBot in the reference's bin/post_proc.sh:106-111, which names
+ * `AlignmentTool pairwise-knn` on the protein representatives as the alternative; neither tool nor a BLOSUM file is part of the
+ * reference, and the rule below is this library's own, not theirs).  Needs no graph.  Contig i = seqs[offsets[i] .. offsets[i + 1]),
+ * L residues x_1 .. x_L; reference r = refs[ref_offsets[r] .. ref_offsets[r + 1]), R residues y_1 .. y_R.
+ *   Residue class.  c(b) = 1 .. 26 for an ASCII letter (A / a = 1 .. Z / z = 26), c(b) = 0 for every other byte.
+ *   Scoring.    sub, int8[27][27], the caller's: s(i, j) = sub[c(x_i)][c(y_j)].  gap_open and gap_extend, integers with
+ *               0 <= gap_extend <= gap_open <= 1024; gap_open is the cost of a gap's FIRST residue, gap_extend of every further one.
+ *   Mode.       Global in the contig, local in the reference (the choice of mgta_seqs_align, for the same reason: a contig is a
+ *               piece of the gene): every contig residue is consumed, the first one is matched at no entry cost, the last one is
+ *               matched and the alignment ends there.
+ *   Recurrence  (i = 1 .. L, j = 1 .. R; int32 throughout; whatever is not defined below is undefined and is never a candidate):
+ *               M[i][j] = s(i,j) + max( 0 if i == 1 (B);  for i > 1, j > 1:  M[i-1][j-1] (M), X[i-1][j-1] (X), Y[i-1][j-1] (Y) )
+ *               X[i][j] = max( M[i-1][j] - gap_open, X[i-1][j] - gap_extend )      i > 1     (x_i against a gap: insert)
+ *               Y[i][j] = max( M[i][j-1] - gap_open, Y[i][j-1] - gap_extend )      j > 1     (y_j skipped: delete)
+ *   Score.      score(contig, ref) = max_j M[L][j]; no score when L = 0, R = 0 or no M[L][j] is defined (R = 1 < L is the smallest
+ *               such case).  Ties decide the traceback only: the candidate written first wins (B, M, X, Y; for X: M, X; for Y: M, Y),
+ *               and the end column is the LOWEST j that reaches the score.
+ *   Nearest.    The reference with the highest score; on a tie the lowest reference index.  A contig with no scored pair is
+ *               UNALIGNED: status 1, ref -1, every other field 0, an empty path.
+ *   Record.     From the traceback against the nearest reference only: ref, score; ref_from, ref_to: the first and the last matched
+ *               reference position, 1-based; n_match: match states; n_ident: match states with c(x_i) == c(y_j) != 0; n_insert,
+ *               n_delete; when path is given, the state path over 'M', 'I', 'D' in path order at path + offsets[i] + i*4096 (the
+ *               caller's offsets as they are), L + n_delete characters, not terminated, its length in path_len[i] (required with path).
+ *   Range.      Under the limits a defined value is at most 127 * 4096 + 1024 * 8192 < 2^24 in magnitude and never leaves int32.  The
+ *               kernels hold "undefined" as the sentinel -2^30; whatever derives from it stays within 9.6e6 of it (a monotone path of
+ *               at most 8191 + 128 steps, each worth between -1152 and +127), so it is below every defined value, below the floor
+ *               -2^29 under which nothing is reported, and above INT32_MIN: nothing wraps.
+ * scores, when given, takes score(i, r) of EVERY pair at scores[i * n_ref + r], INT32_MIN where the pair has no score (the tests'
+ * view; it costs 4 bytes of device memory per pair).  Two passes on the device: the score pass over all pairs, int32 without any
+ * traceback store, one wave per contig along the concatenation of the references; then the n (contig, nearest reference) pairs are
+ * filled again with one direction byte per cell, in batches, and one thread per pair walks the bytes back.  Every output is a
+ * function of the inputs only, except stats.ms_*, the counters of work done (n_batches, n_segments) and the residency fields;
+ * mgta_ctx_set_nearest_batch (cells = L * R of one trace batch; 0 = by the context's free memory; a batch always holds at least one
+ * pair) is a switch for tests and moves no output.  Limits: L <= 4096, R <= 4096, n < 2^31, n_ref < 2^31, and the references together
+ * hold fewer than 2^31 residues (a column of their concatenation is a 32-bit number); beyond any of them MGTA_EINVAL names the limit
+ * and nothing is written.  Device memory: the letters of both sides, 8 bytes per (contig, segment of references) of the score pass,
+ * one traceback byte per cell of a trace batch and the batch's outputs, accounted like every other buffer; what does not fit is
+ * MGTA_ENOMEM.  MGTA_EINVAL (nothing is written): NULL context; with n > 0 NULL offsets / recs / sub / ref_offsets (n_ref > 0) /
+ * seqs or refs with residues / path_len with path; n < 0, n_ref < 0, descending offsets on either side, gap parameters out of range.
+ * n = 0: MGTA_OK, stats all zero.  n_ref = 0: every contig unaligned.
+ * ------------------------------------------------------------------------------------------------ */
+typedef struct mgta_nearest_rec { int32_t status, ref, score, ref_from, ref_to, n_match, n_ident, n_insert, n_delete; } mgta_nearest_rec;
+typedef struct mgta_nearest_stats {
+    int64_t n_seqs, n_refs, n_pairs, n_unaligned;
+    int64_t n_cells;                       /* sum of L * R over all pairs (INT64_MAX when it does not fit) */
+    int64_t n_trace_cells;                 /* sum of L * R over the (contig, nearest reference) pairs */
+    int64_t n_batches;                     /* batches of the trace pass */
+    int64_t n_segments;                    /* runs of whole references the score pass cut the concatenation into (1 when the contigs fill the device) */
+    int64_t blocks_per_cu;                 /* what the runtime answered for the score kernel with its LDS */
+    int64_t waves_per_block;               /* contigs in flight per workgroup: 4, 2 or 1 by the longest contig */
+    int64_t grid_blocks;                   /* workgroups of the score pass */
+    int64_t lds_bytes;                     /* LDS of a workgroup */
+    int64_t peak_bytes;                    /* most device memory the call held at once */
+    double ms_score, ms_trace;             /* HIP events: the score pass; fill and walk of the trace pass, summed over the batches */
+} mgta_nearest_stats;
+int mgta_seqs_nearest(mgta_ctx *, const char *seqs, const uint64_t *offsets /* [n + 1] */, int64_t n,
+                      const char *refs, const uint64_t *ref_offsets /* [n_ref + 1] */, int64_t n_ref,
+                      const int8_t *sub /* [27 * 27] */, int32_t gap_open, int32_t gap_extend,
+                      mgta_nearest_rec *recs /* [n] */, int32_t *scores /* [n * n_ref] or NULL; INT32_MIN = no score */,
+                      char *path /* [offsets[n] + n * 4096] or NULL */, int32_t *path_len /* [n] or NULL */, mgta_nearest_stats *stats /* may be NULL */);
+int mgta_ctx_set_nearest_batch(mgta_ctx *, int64_t cells);   /* 0 = by memory (default); a switch for tests, the outputs do not move */
+
+/* ------------------------------------------------------------------------------------------------
  * Seed finder (replaces the read scan of `megagta findstart`, fast_kmer_filter.cpp:108-176,193-215):
  * every window of k nucleotides (k a multiple of 3, k/3 <= 24) of every read, on both strands, whose translation is one of
  * the n_ref reference words.  A word = its residues in the code of prot_kmer.h:31-43 (ARNDCQEGHILKMFPSTWYV = 0..19, '*' = 20),

@@ -126,6 +126,21 @@ class ClusterStats(C.Structure):
         return {n: getattr(self, n) for n, _ in self._fields_}
 
 
+class NearestRec(C.Structure):
+    _fields_ = [("status", C.c_int32), ("ref", C.c_int32), ("score", C.c_int32), ("ref_from", C.c_int32), ("ref_to", C.c_int32), ("n_match", C.c_int32),
+                ("n_ident", C.c_int32), ("n_insert", C.c_int32), ("n_delete", C.c_int32)]
+
+
+class NearestStats(C.Structure):
+    _fields_ = [("n_seqs", C.c_int64), ("n_refs", C.c_int64), ("n_pairs", C.c_int64), ("n_unaligned", C.c_int64), ("n_cells", C.c_int64),
+                ("n_trace_cells", C.c_int64), ("n_batches", C.c_int64), ("n_segments", C.c_int64), ("blocks_per_cu", C.c_int64),
+                ("waves_per_block", C.c_int64), ("grid_blocks", C.c_int64), ("lds_bytes", C.c_int64), ("peak_bytes", C.c_int64),
+                ("ms_score", C.c_double), ("ms_trace", C.c_double)]
+
+    def as_dict(self):
+        return {n: getattr(self, n) for n, _ in self._fields_}
+
+
 EDGE_SINK = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_int32, C.c_int32, C.POINTER(C.c_int64), C.POINTER(C.c_uint16), C.c_int64,
                         C.POINTER(C.c_uint16), C.c_int64, C.POINTER(C.c_uint32), C.c_int64)
 CONTIG_SINK = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_void_p, C.c_int64,
@@ -192,6 +207,9 @@ SYMBOLS = {
                                     C.c_void_p, C.c_void_p]),
     "mgta_pairs_link": (C.c_int, [C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "mgta_ctx_set_cluster_tile": (C.c_int, [C.c_void_p, C.c_int64]),
+    "mgta_seqs_nearest": (C.c_int, [C.c_void_p, C.c_char_p, C.c_void_p, C.c_int64, C.c_char_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_int32, C.c_int32,
+                                    C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "mgta_ctx_set_nearest_batch": (C.c_int, [C.c_void_p, C.c_int64]),
     "mgta_sdbg_free": (None, [C.c_void_p]),
     "mgta_sdbg_size": (C.c_int64, [C.c_void_p]),
     "mgta_sdbg_outgoing": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p]),

@@ -215,6 +215,43 @@ class Context:
                                         rd.ctypes.data, ro.ctypes.data, C.byref(st)), "mgta_rows_cluster")
         return dict(cluster=cl[:n], rep=rep[:n], rep_diff=rd[:n], rep_overlap=ro[:n], stats=st.as_dict())
 
+    def set_nearest_batch(self, cells: int = 0):
+        """cells (L * R) of one trace batch of `nearest` (0 = the default: by the context's free memory); a batch holds at least one
+        pair.  For tests: the result does not depend on it; only stats["n_batches"] does."""
+        check(self._L.mgta_ctx_set_nearest_batch(self.h, int(cells)), "mgta_ctx_set_nearest_batch")
+
+    def nearest(self, seqs, refs, sub, gap_open: int, gap_extend: int, scores: bool = False, paths: bool = False) -> dict:
+        """mgta_seqs_nearest: for every contig of `seqs` (str or bytes) the closest sequence of `refs` (the rule: include/megagta_hip.h);
+        sub = int8[27, 27] over the residue classes (0 = no letter, 1 .. 26 = A .. Z) -> dict(recs = structured array [n] with status
+        (0 aligned, 1 unaligned), ref (-1 unaligned), score, ref_from, ref_to, n_match, n_ident, n_insert, n_delete; scores =
+        int32[n, n_ref] of every pair when asked for, INT32_MIN where a pair has no score; paths = list of str over M / I / D when
+        asked for; stats).  Needs no graph."""
+        raw = [s if isinstance(s, (bytes, bytearray)) else str(s).encode("latin-1") for s in seqs]
+        rraw = [s if isinstance(s, (bytes, bytearray)) else str(s).encode("latin-1") for s in refs]
+        n, n_ref = len(raw), len(rraw)
+        table = np.ascontiguousarray(sub, dtype=np.int8)
+        if table.shape != (27, 27):
+            raise ValueError("sub must be int8[27, 27]")
+        offsets, roffsets = np.zeros(n + 1, dtype=np.uint64), np.zeros(n_ref + 1, dtype=np.uint64)
+        if n:
+            np.cumsum([len(s) for s in raw], out=offsets[1:])
+        if n_ref:
+            np.cumsum([len(s) for s in rraw], out=roffsets[1:])
+        recs = np.zeros(max(1, n), dtype=NEAREST_REC)
+        sc = np.zeros((n, n_ref), dtype=np.int32) if scores else None
+        p = np.zeros(int(offsets[n]) + n * 4096 + 1, dtype=np.uint8) if paths else None
+        plen = np.zeros(max(1, n), dtype=np.int32) if paths else None
+        st = _lib.NearestStats()
+        check(self._L.mgta_seqs_nearest(self.h, b"".join(raw), offsets.ctypes.data, n, b"".join(rraw), roffsets.ctypes.data, n_ref, table.ctypes.data,
+                                        int(gap_open), int(gap_extend), recs.ctypes.data, sc.ctypes.data if scores and sc.size else None,
+                                        p.ctypes.data if paths else None, plen.ctypes.data if paths else None, C.byref(st)), "mgta_seqs_nearest")
+        out = dict(recs=recs[:n], stats=st.as_dict())
+        if scores:
+            out["scores"] = sc
+        if paths:
+            out["paths"] = [p[int(offsets[i]) + i * 4096:int(offsets[i]) + i * 4096 + int(plen[i])].tobytes().decode() for i in range(n)]
+        return out
+
     def release_scratch(self):
         """free the work memory kept between calls (build pool, search pool)"""
         check(self._L.mgta_ctx_release_scratch(self.h), "mgta_ctx_release_scratch")
@@ -452,6 +489,11 @@ class Graph:
 # mgta_align_rec
 ALIGN_REC = np.dtype([("score", np.float64), ("status", np.int32), ("model_from", np.int32), ("model_to", np.int32), ("n_match", np.int32),
                       ("n_insert", np.int32), ("n_delete", np.int32)], align=True)
+
+
+# mgta_nearest_rec
+NEAREST_REC = np.dtype([("status", np.int32), ("ref", np.int32), ("score", np.int32), ("ref_from", np.int32), ("ref_to", np.int32), ("n_match", np.int32),
+                        ("n_ident", np.int32), ("n_insert", np.int32), ("n_delete", np.int32)], align=True)
 
 
 def link_pairs(pairs, n_residues, lens) -> dict:

@@ -1166,6 +1166,150 @@ static int main_cluster(int argc, char **argv) {
     return 0;
 }
 
+// ---- nearest: for every record of a gene's protein contigs the closest sequence of the gene's reference set and the identity to it (the
+// place of FrameBot / `AlignmentTool pairwise-knn`, bin/post_proc.sh:106-111; the rule is mgta_seqs_nearest's own).  Needs no graph and leaves
+// a worker's resident graphs alone.  Formats: INTEGRATION.md 2l.
+static int residue_class(unsigned char b) { return (b < 128 && (b | 32) >= 'a' && (b | 32) <= 'z') ? (b | 32) - 'a' + 1 : 0; }
+// `MATCH,MISMATCH`, or a matrix file in NCBI format (`#` comments, a header row of letters, rows `LETTER v v ...`; `*` is class 0; letters
+// the file does not have take its lowest value) -> sub[27 * 27]; an empty string when it is good, else what is wrong with it
+static std::string parse_scoring(const std::string &spec, int8_t *sub) {
+    {
+        long long a = 0, b = 0;
+        char *e1 = nullptr, *e2 = nullptr;
+        const size_t comma = spec.find(',');
+        if (comma != std::string::npos && spec.find(',', comma + 1) == std::string::npos) {
+            const std::string sa = spec.substr(0, comma), sb = spec.substr(comma + 1);
+            a = strtoll(sa.c_str(), &e1, 10); b = strtoll(sb.c_str(), &e2, 10);
+            if (!sa.empty() && !sb.empty() && !*e1 && !*e2) {
+                if (a < -128 || a > 127 || b < -128 || b > 127) return "a value of '" + spec + "' is outside int8";
+                for (int x = 0; x < 27; ++x)
+                    for (int y = 0; y < 27; ++y) sub[x * 27 + y] = (int8_t)((x == y && x != 0) ? a : b);
+                return "";
+            }
+        }
+    }
+    FILE *f = fopen(spec.c_str(), "r");
+    if (!f) return "'" + spec + "' is neither MATCH,MISMATCH nor a matrix file that can be read";
+    std::vector<int> cols;                                               // the class of every column, in file order
+    std::vector<std::vector<long long>> rows;
+    std::vector<int> row_cls;
+    std::string err;
+    char *line = nullptr;
+    size_t cap = 0;
+    ssize_t n;
+    bool have_header = false;
+    while (err.empty() && (n = getline(&line, &cap, f)) >= 0) {
+        if (char *h = strchr(line, '#')) *h = 0;
+        std::vector<std::string> fld;
+        for (char *tok = strtok(line, " \t\r\n"); tok; tok = strtok(nullptr, " \t\r\n")) fld.emplace_back(tok);
+        if (fld.empty()) continue;
+        auto cls_of = [](const std::string &t) { return t.size() != 1 ? -1 : t[0] == '*' ? 0 : (residue_class((unsigned char)t[0]) ? residue_class((unsigned char)t[0]) : -1); };
+        if (!have_header) {
+            have_header = true;
+            for (const std::string &t : fld) {
+                const int c = cls_of(t);
+                if (c < 0 || std::find(cols.begin(), cols.end(), c) != cols.end()) { err = "bad header row"; break; }
+                cols.push_back(c);
+            }
+            continue;
+        }
+        const int c = cls_of(fld[0]);
+        if (c < 0 || std::find(cols.begin(), cols.end(), c) == cols.end() || std::find(row_cls.begin(), row_cls.end(), c) != row_cls.end() ||
+            fld.size() != cols.size() + 1) { err = "bad row " + fld[0]; break; }
+        std::vector<long long> v;
+        for (size_t k = 1; k < fld.size() && err.empty(); ++k) {
+            char *e = nullptr;
+            const long long x = strtoll(fld[k].c_str(), &e, 10);
+            if (e == fld[k].c_str() || *e) err = "bad row " + fld[0];
+            else if (x < -128 || x > 127) err = "a value of row " + fld[0] + " is outside int8";
+            v.push_back(x);
+        }
+        row_cls.push_back(c); rows.push_back(v);
+    }
+    free(line);
+    fclose(f);
+    if (!err.empty()) return "matrix " + spec + ": " + err;
+    if (cols.empty() || rows.size() != cols.size()) return "matrix " + spec + ": a header row of letters and one row per letter of it";
+    long long lowest = 127;
+    for (const auto &v : rows) for (long long x : v) lowest = std::min(lowest, x);
+    for (int x = 0; x < 27 * 27; ++x) sub[x] = (int8_t)lowest;
+    for (size_t r = 0; r < rows.size(); ++r)
+        for (size_t k = 0; k < cols.size(); ++k) sub[row_cls[r] * 27 + cols[k]] = (int8_t)rows[r][k];
+    return "";
+}
+static int main_nearest(int argc, char **argv) {
+    if (argc != 7) { fprintf(stderr, "Usage: megagta nearest <ref.faa> <prot.fasta> <out_prefix> <gap_open> <gap_extend> <scoring>\n"); return 1; }
+    RssLine rss;
+    const std::string ref_fasta = argv[1], fasta = argv[2], out_prefix = argv[3];
+    char *end = nullptr;
+    const long long gap_open = strtoll(argv[4], &end, 10);
+    if (end == argv[4] || *end) { fprintf(stderr, "    [ERROR] nearest: gap_open '%s' is not an integer\n", argv[4]); return 1; }
+    const long long gap_extend = strtoll(argv[5], &end, 10);
+    if (end == argv[5] || *end) { fprintf(stderr, "    [ERROR] nearest: gap_extend '%s' is not an integer\n", argv[5]); return 1; }
+    if (gap_extend < 0 || gap_extend > gap_open || gap_open > 1024) {
+        fprintf(stderr, "    [ERROR] nearest: gap_open = %lld, gap_extend = %lld: 0 <= gap_extend <= gap_open <= 1024 is needed: nothing written\n", gap_open, gap_extend);
+        return 1;
+    }
+    int8_t sub[27 * 27];
+    const std::string bad = parse_scoring(argv[6], sub);
+    if (!bad.empty()) { fprintf(stderr, "    [ERROR] nearest: scoring: %s: nothing written\n", bad.c_str()); return 1; }
+    std::vector<std::string> names, headers, rnames;
+    std::string seqs, rraw, refs;
+    std::vector<uint64_t> offsets, rraw_off, roffsets(1, 0);
+    read_fasta_records(fasta, names, seqs, offsets, &headers);
+    read_fasta_records(ref_fasta, rnames, rraw, rraw_off);
+    const int64_t n = (int64_t)names.size(), n_ref = (int64_t)rnames.size();
+    // the residues of a reference: its ASCII letters, upper-cased; `-`, `.`, `*` and everything else go (the file may be an alignment)
+    for (int64_t r = 0; r < n_ref; ++r) {
+        for (uint64_t p = rraw_off[(size_t)r]; p < rraw_off[(size_t)r + 1]; ++p) {
+            const unsigned char c = (unsigned char)rraw[p];
+            if (residue_class(c)) refs += (char)(c >= 'a' ? c - 32 : c);
+        }
+        roffsets.push_back(refs.size());
+    }
+    const double t0 = now_s();
+    mgta_ctx *ctx = ctx_get();
+    std::vector<mgta_nearest_rec> recs((size_t)n + 1);
+    mgta_nearest_stats st;
+    if (mgta_seqs_nearest(ctx, seqs.data(), offsets.data(), n, refs.data(), roffsets.data(), n_ref, sub, (int32_t)gap_open, (int32_t)gap_extend, recs.data(), nullptr,
+                          nullptr, nullptr, &st) != MGTA_OK) {
+        fprintf(stderr, "    [ERROR] nearest: %s: nothing written\n", mgta_last_error());
+        ctx_put(ctx);
+        return 1;
+    }
+    logf("nearest of %lld records among %lld references: %lld unaligned; %lld cells in %lld segments, %lld workgroups of %lld waves, %lld per CU, %lld B of LDS; "
+         "%lld trace cells in %lld batches; peak %lld B; score %.1f ms, trace %.1f ms; wall %.3f s", (long long)st.n_seqs, (long long)st.n_refs, (long long)st.n_unaligned,
+         (long long)st.n_cells, (long long)st.n_segments, (long long)st.grid_blocks, (long long)st.waves_per_block, (long long)st.blocks_per_cu, (long long)st.lds_bytes,
+         (long long)st.n_trace_cells, (long long)st.n_batches, (long long)st.peak_bytes, st.ms_score, st.ms_trace, now_s() - t0);
+    std::string table = "#contig\tstatus\tref\tscore\tidentity\tlen\tref_len\tref_from\tref_to\tmatch\tident\tinsert\tdelete\n";
+    std::string rtable = "#ref\tref_len\tcontigs\tmean_identity\n";
+    std::vector<int64_t> count((size_t)n_ref + 1);
+    std::vector<double> total((size_t)n_ref + 1);
+    char num[64];
+    for (int64_t i = 0; i < n; ++i) {
+        const size_t u = (size_t)i;
+        const mgta_nearest_rec &r = recs[u];
+        const bool un = r.status != 0;
+        const int64_t cols = (int64_t)r.n_match + r.n_insert + r.n_delete;
+        const double idy = cols ? (double)r.n_ident / (double)cols : 0.0;
+        if (!un) { ++count[(size_t)r.ref]; total[(size_t)r.ref] += idy; }
+        snprintf(num, sizeof num, "%.4f", idy);
+        table += names[u] + "\t" + (un ? "unaligned" : "aligned") + "\t" + (un ? std::string("-") : rnames[(size_t)r.ref]) + "\t" + std::to_string(r.score) + "\t" + num +
+                 "\t" + std::to_string(offsets[u + 1] - offsets[u]) + "\t" + std::to_string(un ? 0 : roffsets[(size_t)r.ref + 1] - roffsets[(size_t)r.ref]) + "\t" +
+                 std::to_string(r.ref_from) + "\t" + std::to_string(r.ref_to) + "\t" + std::to_string(r.n_match) + "\t" + std::to_string(r.n_ident) + "\t" +
+                 std::to_string(r.n_insert) + "\t" + std::to_string(r.n_delete) + "\n";
+    }
+    for (int64_t r = 0; r < n_ref; ++r) {
+        const size_t u = (size_t)r;
+        snprintf(num, sizeof num, "%.4f", count[u] ? total[u] / (double)count[u] : 0.0);
+        rtable += rnames[u] + "\t" + std::to_string(roffsets[u + 1] - roffsets[u]) + "\t" + std::to_string(count[u]) + "\t" + num + "\n";
+    }
+    if (!write_text_file(out_prefix + "_nearest.txt", table)) die("cannot write %s_nearest.txt", out_prefix.c_str());
+    if (!write_text_file(out_prefix + "_nearest_refs.txt", rtable)) die("cannot write %s_nearest_refs.txt", out_prefix.c_str());
+    ctx_put(ctx);
+    return 0;
+}
+
 static int dispatch(int argc, char **argv);
 
 // megagta serve: requests on stdin, one per line: the sub-command's argv, tab separated; a field "<PATH" / ">PATH" redirects the
@@ -1253,7 +1397,7 @@ int main(int argc, char **argv) {
 static int dispatch(int argc, char **argv) {
     if (argc < 2) {
         fprintf(stderr, "Usage: %s <sub_program> [sub options]\n    sub-programs on the MI355X hot path:\n        buildgraph    build succinct de Bruijn graph\n"
-                        "        denovo        tips, bubbles, contigs of an intermediate k\n        search        HMM-guided search of gene contigs\n        findstart     find starting kmers of the search\n        coverage      per-contig k-mer coverage and abundance from the graph\n        matchreads    the reads that share a (k+1)-mer with a set of contigs\n        derep         the unique, non-contained records of a FASTA\n        align         protein records placed on the columns of a profile HMM\n        cluster       complete-linkage clusters of aligned protein records\n        dumpversion   dump version\n", argv[0]);
+                        "        denovo        tips, bubbles, contigs of an intermediate k\n        search        HMM-guided search of gene contigs\n        findstart     find starting kmers of the search\n        coverage      per-contig k-mer coverage and abundance from the graph\n        matchreads    the reads that share a (k+1)-mer with a set of contigs\n        derep         the unique, non-contained records of a FASTA\n        align         protein records placed on the columns of a profile HMM\n        cluster       complete-linkage clusters of aligned protein records\n        nearest       the closest reference protein of every protein record\n        dumpversion   dump version\n", argv[0]);
         return 1;
     }
     std::string sub = argv[1];
@@ -1266,6 +1410,7 @@ static int dispatch(int argc, char **argv) {
     if (sub == "derep") return main_derep(argc - 1, argv + 1);
     if (sub == "align") return main_align(argc - 1, argv + 1);
     if (sub == "cluster") return main_cluster(argc - 1, argv + 1);
+    if (sub == "nearest") return main_nearest(argc - 1, argv + 1);
     if (sub == "filterbylen") return main_filterbylen(argc - 1, argv + 1);
     if (sub == "translate") return main_translate(argc - 1, argv + 1);
     if (sub == "buildlib") {                                             // build_read_lib.cpp:8-20 (host only: file formats, no kernel)
@@ -1368,6 +1513,6 @@ static int dispatch(int argc, char **argv) {
         return 0;
     }
     if (sub == "dumpversion") { printf("%s\n", mgta_version()); return 0; }
-    fprintf(stderr, "sub-command '%s' is not built here (buildlib, buildgraph, denovo, findstart, search, coverage, matchreads, derep, align, cluster, filterbylen, translate are): run it with the reference's megagta binary\n", sub.c_str());
+    fprintf(stderr, "sub-command '%s' is not built here (buildlib, buildgraph, denovo, findstart, search, coverage, matchreads, derep, align, cluster, nearest, filterbylen, translate are): run it with the reference's megagta binary\n", sub.c_str());
     return 1;
 }

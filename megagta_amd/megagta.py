@@ -52,7 +52,14 @@ USAGE = """Usage:
                      contigs/<gene>/prot_merged[_rmdup]_clust.txt (what became of every contig), prot_merged[_rmdup]_rep_seqs.fasta and
                      nucl_merged[_rmdup]_rep_seqs.fasta (one representative per cluster: the longest member) (GPU 0)
     --cluster-dist D          largest share of differing columns inside a cluster [0.01: the reference's "99% aa identity"]
-    --cluster-min-overlap N   columns two contigs must share to be compared at all [25: the reference's `dmatrix -l 25`]"""
+    --cluster-min-overlap N   columns two contigs must share to be compared at all [25: the reference's `dmatrix -l 25`]
+    --nearest        after every other step: per gene the closest sequence of the gene's reference proteins (column 4 of the gene list)
+                     for every protein contig and the identity to it: contigs/<gene>/prot_merged[_rmdup]_nearest.txt and
+                     prot_merged[_rmdup]_nearest_refs.txt (per reference: its contigs and their mean identity); with --cluster the
+                     contigs are the representatives, prot_merged[_rmdup]_rep_seqs.fasta, and the files are ..._rep_seqs_nearest*.txt (GPU 0)
+    --nearest-scoring S       MATCH,MISMATCH or a substitution matrix file in NCBI format [5,-4: this driver's own default]
+    --nearest-gap-open N      cost of a gap's first residue [10: this driver's own default]
+    --nearest-gap-extend N    cost of every further residue of a gap [1: this driver's own default]"""
 
 
 class Usage(Exception):
@@ -90,6 +97,10 @@ class Opt:
         self.cluster = False
         self.cluster_dist = 0.01
         self.cluster_min_overlap = 25
+        self.nearest = False
+        self.nearest_scoring = "5,-4"
+        self.nearest_gap_open = 10
+        self.nearest_gap_extend = 1
 
 
 opt = Opt()
@@ -98,7 +109,7 @@ cp = 0
 LONG = ["help", "read=", "12=", "out-dir=", "memory=", "gpu-mem=", "min-contig-len=", "num-cpu-threads=", "kmin-1pass", "k-list=",
         "min-count=", "max-tip-len=", "no-mercy", "keep-tmp-files", "mem-flag=", "version", "verbose", "continue", "gene-list=",
         "prune-len=", "low-cov-penalty=", "bin=", "one-process-per-step", "gpus=", "coverage", "match-reads", "derep", "align", "cluster",
-        "cluster-dist=", "cluster-min-overlap="]
+        "cluster-dist=", "cluster-min-overlap=", "nearest", "nearest-scoring=", "nearest-gap-open=", "nearest-gap-extend="]
 
 
 def parse_opt(argv):
@@ -151,6 +162,10 @@ def parse_opt(argv):
         elif o == "--cluster": opt.cluster = True
         elif o == "--cluster-dist": opt.cluster_dist = float(v)
         elif o == "--cluster-min-overlap": opt.cluster_min_overlap = int(v)
+        elif o == "--nearest": opt.nearest = True
+        elif o == "--nearest-scoring": opt.nearest_scoring = v
+        elif o == "--nearest-gap-open": opt.nearest_gap_open = int(v)
+        elif o == "--nearest-gap-extend": opt.nearest_gap_extend = int(v)
         else:
             raise Usage("Invalid option " + o)
     opt.temp_dir = opt.out_dir + "tmp/"
@@ -206,6 +221,8 @@ def check_opt():
         raise Usage("--cluster-dist should be between [0, 1]")
     if opt.cluster_min_overlap < 1:
         raise Usage("--cluster-min-overlap should be >= 1")
+    if not 0 <= opt.nearest_gap_extend <= opt.nearest_gap_open <= 1024:
+        raise Usage("--nearest-gap-open and --nearest-gap-extend should satisfy 0 <= extend <= open <= 1024")
     if opt.host_mem <= 0:
         raise Usage("Please specify a positive number for -m flag.")
     if opt.host_mem < 1:
@@ -646,6 +663,20 @@ def cluster(k):
         write_cp()
 
 
+def nearest(k):
+    """--nearest: per gene the closest reference protein of every protein contig and the identity to it (`megagta nearest`, GPU 0; no
+    graph is needed, k only names the step).  The contigs are the representatives when --cluster runs too, else what --derep kept when
+    that flag runs, else all; the references are the gene's column-4 file.  Its checkpoints come after every other checkpoint, those of
+    --cluster included, so `--continue` works under any combination."""
+    stem = "/prot_merged" + ("_rmdup" if opt.derep else "") + ("_rep_seqs" if opt.cluster else "")
+    for gene in opt.gene_info:
+        prefix = opt.out_dir + "contigs/" + gene + stem
+        if should_run():
+            run_step([opt.bin, "nearest", opt.gene_info[gene][2], prefix + ".fasta", prefix, str(opt.nearest_gap_open), str(opt.nearest_gap_extend),
+                      opt.nearest_scoring], "Finding the nearest reference of the contigs of %s" % gene)
+        write_cp()
+
+
 def after_search(k):
     """the opt-in steps on the last k's graph, in a fixed order behind every checkpoint of a run without them"""
     if opt.coverage:
@@ -658,6 +689,8 @@ def after_search(k):
         align(k)
     if opt.cluster:
         cluster(k)
+    if opt.nearest:
+        nearest(k)
 
 
 def main(argv=None):
