@@ -504,6 +504,73 @@ int mgta_seqs_nearest(mgta_ctx *, const char *seqs, const uint64_t *offsets /* [
 int mgta_ctx_set_nearest_batch(mgta_ctx *, int64_t cells);   /* 0 = by memory (default); a switch for tests, the outputs do not move */
 
 /* ------------------------------------------------------------------------------------------------
+ * Contigs that two references explain better than one (the place of the chimera removal in the reference's bin/post_proc.sh:89-95,
+ * which runs `uchime` on the representatives; that tool is not part of the reference, and the rule below is this library's own: it is
+ * not uchime's and is not checked against it).  Needs no graph.  Contigs, references, residue classes, sub, gap_open and gap_extend
+ * are those of mgta_seqs_nearest, and score(x, y) is exactly its score: global in x, local in y, int32, or undefined.  Two more
+ * parameters: min_seg, 1 <= min_seg <= 4096, the fewest residues on either side of a break, and min_gain, 1 <= min_gain <= 2^20.
+ * For a contig x of L residues and a reference r:   P_r(b) = score(x[1..b], y_r),   S_r(b) = score(x[b..L], y_r).
+ * A breakpoint b means left = x[1..b], right = x[b+1..L]; b is in range when min_seg <= b <= L - min_seg.
+ *   1. Top two.  P1(b): the reference with the highest defined P_r(b), the lowest index on a tie; P2(b): the same choice among the
+ *                other references; S1(b), S2(b) likewise from S_r(b).  Any of the four may be absent.
+ *   2. The pair. If P1(b) and S1(b+1) name different references, the pair at b is (P1(b), S1(b+1)).  Otherwise the candidates are
+ *                (P1(b), S2(b+1)) and (P2(b), S1(b+1)), each only when both members exist; of two the larger sum wins, the first
+ *                on a tie; with no candidate there is no pair at b.  two(b) is the pair's sum.
+ *   3. The break. b* = the lowest b in range whose two(b) is the maximum; A and B are its left and right reference (A != B).
+ *   4. One parent. N = P1(L), the nearest reference.  one = max( P_N(L), max over r in {N, A, B} and over b in range with both terms
+ *                defined of P_r(b) + S_r(b+1) ): a single parent gets the free jump at the break that two parents get, so a contig
+ *                with a plain insertion or deletion against every reference does not gain its own gap cost.
+ *   5. Verdict.  gain = two(b*) - one.  status 1 (chimeric) when gain >= min_gain, else 0 (clean).  status 2 (unchecked) when no b in
+ *                range has a pair: L < 2 * min_seg, fewer than two references that score, an empty contig or reference set.  An
+ *                unchecked record keeps ref and score when N exists, else they are -1 and 0; its other fields are 0 and left_ref =
+ *                right_ref = -1.
+ *   Record.      status; ref, score: N and P_N(L) (-1, 0 without N); brk: b*; left_ref, left_score, right_ref, right_score: the
+ *                pair at b*; two, one, gain.
+ *   Range.       As for mgta_seqs_nearest a defined score is below 2^24 in size (127 * 4096 + 1024 * 8192); two and one are sums of
+ *                two such values and gain is their difference: all below 2^26, nothing leaves int32.  The kernels hold
+ *                "undefined" as that function's sentinel -2^30 with its floor -2^29; what derives from it stays within 9.7e6 of it.
+ * tops, when given, takes the top two of every row (the tests' view): for row b of contig c, at (offsets[c] + b - 1) * 8, P1.score,
+ * P1.ref, P2.score, P2.ref, S1.score, S1.ref, S2.score, S2.ref, the S entries for the suffix that STARTS at b; an absent entry is
+ * INT32_MIN, -1.  Two passes on the device, one kernel: the top-two pass, a lane per contig row, a wave along the concatenation of
+ * the references in both directions (the suffix pass runs over the reversed contig and the reversed references), the row's maximum
+ * over the current reference and its top two in registers; then the parents pass over N, A, B of every contig that has a pair, which
+ * writes the rows' maxima out.  Steps 2 to 5 are O(L) per contig and run on the host.  Every output is a function of the inputs only,
+ * except stats.ms_*, the counters of work done and the residency fields; mgta_ctx_set_chimera_segment (reference columns of one
+ * segment of the run, cut at reference boundaries; 0 = the library's choice) and mgta_ctx_set_chimera_groups (work items a (contig,
+ * direction) is cut into, each a run of consecutive segments, at most one per segment; 0 = by the number of contigs) are switches
+ * for tests and move no output.  Limits and
+ * errors are those of mgta_seqs_nearest: L <= 4096, R <= 4096, n < 2^31, n_ref < 2^31, fewer than 2^31 reference residues in all;
+ * beyond any of them, or with min_seg / min_gain / gap parameters out of range, MGTA_EINVAL names the limit and nothing is written.
+ * MGTA_EINVAL also: NULL context; with n > 0 NULL offsets / recs / sub / ref_offsets (n_ref > 0) / seqs or refs with residues; n < 0,
+ * n_ref < 0, descending offsets on either side.  n = 0: MGTA_OK, stats all zero.  Device memory: the letters of both sides twice, 16
+ * bytes per (row, direction, group of segments), 8 bytes per column of the longest segment for every resident wave (at most 4096 of them)
+ * when a contig has more than 64 residues, 24 bytes per row and 56 bytes per contig of the parents pass, which reads the references
+ * where they lie, accounted like every other buffer; what does not fit is MGTA_ENOMEM.
+ * ------------------------------------------------------------------------------------------------ */
+typedef struct mgta_chimera_rec { int32_t status, ref, score, brk, left_ref, left_score, right_ref, right_score, two, one, gain; } mgta_chimera_rec;
+typedef struct mgta_chimera_stats {
+    int64_t n_seqs, n_refs, n_clean, n_chimeric, n_unchecked;
+    int64_t n_cells;                       /* cells of the top-two pass: 2 * sum of L * R over all pairs (INT64_MAX when it does not fit) */
+    int64_t n_parent_cells;                /* cells of the parents pass */
+    int64_t n_items, n_parent_items;       /* work items (contig, direction, group of segments) of the two passes */
+    int64_t n_segments;                    /* runs of whole references the concatenation is cut into */
+    int64_t n_groups;                      /* groups of consecutive segments: 1 when the contigs fill the device */
+    int64_t grid_blocks;                   /* workgroups of the top-two pass */
+    int64_t waves_per_block;               /* items in flight per workgroup */
+    int64_t blocks_per_cu;                 /* what the runtime answered for the kernel, at most 4 */
+    int64_t lds_bytes;                     /* LDS of a workgroup: sub */
+    int64_t bound_bytes;                   /* the boundary buffers of all resident waves: 8 B per column of the longest segment each (0 when no contig has more than 64 residues) */
+    int64_t peak_bytes;                    /* most device memory the call held at once */
+    double ms_top, ms_parents;             /* HIP events: the top-two pass with its fold; the parents pass */
+} mgta_chimera_stats;
+int mgta_seqs_chimera(mgta_ctx *, const char *seqs, const uint64_t *offsets /* [n + 1] */, int64_t n,
+                      const char *refs, const uint64_t *ref_offsets /* [n_ref + 1] */, int64_t n_ref,
+                      const int8_t *sub /* [27 * 27] */, int32_t gap_open, int32_t gap_extend, int32_t min_seg, int32_t min_gain,
+                      mgta_chimera_rec *recs /* [n] */, int32_t *tops /* [offsets[n] * 8] or NULL */, mgta_chimera_stats *stats /* may be NULL */);
+int mgta_ctx_set_chimera_segment(mgta_ctx *, int64_t columns);   /* 0 = chosen by the library; a switch for tests, the outputs do not move */
+int mgta_ctx_set_chimera_groups(mgta_ctx *, int64_t groups);     /* 0 = by the number of contigs; a switch for tests, the outputs do not move */
+
+/* ------------------------------------------------------------------------------------------------
  * Seed finder (replaces the read scan of `megagta findstart`, fast_kmer_filter.cpp:108-176,193-215):
  * every window of k nucleotides (k a multiple of 3, k/3 <= 24) of every read, on both strands, whose translation is one of
  * the n_ref reference words.  A word = its residues in the code of prot_kmer.h:31-43 (ARNDCQEGHILKMFPSTWYV = 0..19, '*' = 20),

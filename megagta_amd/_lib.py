@@ -141,6 +141,21 @@ class NearestStats(C.Structure):
         return {n: getattr(self, n) for n, _ in self._fields_}
 
 
+class ChimeraRec(C.Structure):
+    _fields_ = [("status", C.c_int32), ("ref", C.c_int32), ("score", C.c_int32), ("brk", C.c_int32), ("left_ref", C.c_int32), ("left_score", C.c_int32),
+                ("right_ref", C.c_int32), ("right_score", C.c_int32), ("two", C.c_int32), ("one", C.c_int32), ("gain", C.c_int32)]
+
+
+class ChimeraStats(C.Structure):
+    _fields_ = [("n_seqs", C.c_int64), ("n_refs", C.c_int64), ("n_clean", C.c_int64), ("n_chimeric", C.c_int64), ("n_unchecked", C.c_int64),
+                ("n_cells", C.c_int64), ("n_parent_cells", C.c_int64), ("n_items", C.c_int64), ("n_parent_items", C.c_int64), ("n_segments", C.c_int64),
+                ("n_groups", C.c_int64), ("grid_blocks", C.c_int64), ("waves_per_block", C.c_int64), ("blocks_per_cu", C.c_int64), ("lds_bytes", C.c_int64),
+                ("bound_bytes", C.c_int64), ("peak_bytes", C.c_int64), ("ms_top", C.c_double), ("ms_parents", C.c_double)]
+
+    def as_dict(self):
+        return {n: getattr(self, n) for n, _ in self._fields_}
+
+
 EDGE_SINK = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_int32, C.c_int32, C.POINTER(C.c_int64), C.POINTER(C.c_uint16), C.c_int64,
                         C.POINTER(C.c_uint16), C.c_int64, C.POINTER(C.c_uint32), C.c_int64)
 CONTIG_SINK = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_void_p, C.c_int64,
@@ -210,6 +225,10 @@ SYMBOLS = {
     "mgta_seqs_nearest": (C.c_int, [C.c_void_p, C.c_char_p, C.c_void_p, C.c_int64, C.c_char_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_int32, C.c_int32,
                                     C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "mgta_ctx_set_nearest_batch": (C.c_int, [C.c_void_p, C.c_int64]),
+    "mgta_seqs_chimera": (C.c_int, [C.c_void_p, C.c_char_p, C.c_void_p, C.c_int64, C.c_char_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_int32, C.c_int32,
+                                    C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "mgta_ctx_set_chimera_segment": (C.c_int, [C.c_void_p, C.c_int64]),
+    "mgta_ctx_set_chimera_groups": (C.c_int, [C.c_void_p, C.c_int64]),
     "mgta_sdbg_free": (None, [C.c_void_p]),
     "mgta_sdbg_size": (C.c_int64, [C.c_void_p]),
     "mgta_sdbg_outgoing": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p]),

@@ -15,6 +15,7 @@ from dataclasses import dataclass, field
 import numpy as np
 
 from . import _lib
+from .chimera import REC as _chimera_rec
 from ._lib import MegaGtaError, check
 
 NUM_BUCKETS = 65536
@@ -250,6 +251,45 @@ class Context:
             out["scores"] = sc
         if paths:
             out["paths"] = [p[int(offsets[i]) + i * 4096:int(offsets[i]) + i * 4096 + int(plen[i])].tobytes().decode() for i in range(n)]
+        return out
+
+    def set_chimera_segment(self, columns: int = 0):
+        """reference columns of one segment of `chimera`'s run, cut at reference boundaries (0 = the library's choice; 1 = one reference
+        per segment).  For tests: the result does not depend on it; only stats["n_segments"] and stats["n_groups"] do."""
+        check(self._L.mgta_ctx_set_chimera_segment(self.h, int(columns)), "mgta_ctx_set_chimera_segment")
+
+    def set_chimera_groups(self, groups: int = 0):
+        """work items a (contig, direction) of `chimera` is cut into, each a run of consecutive segments, at most one per segment (0 =
+        the default: one unless the contigs are too few to fill the device).  For tests: the result does not depend on it; only
+        stats["n_groups"] and stats["n_items"] do."""
+        check(self._L.mgta_ctx_set_chimera_groups(self.h, int(groups)), "mgta_ctx_set_chimera_groups")
+
+    def chimera(self, seqs, refs, sub, gap_open: int, gap_extend: int, min_seg: int, min_gain: int, tops: bool = False) -> dict:
+        """mgta_seqs_chimera: for every contig of `seqs` (str or bytes) whether two sequences of `refs` explain it better than one (the
+        rule: include/megagta_hip.h); sub, gap_open, gap_extend as for `nearest` -> dict(recs = structured array [n] with status (0
+        clean, 1 chimeric, 2 unchecked), ref, score, brk, left_ref, left_score, right_ref, right_score, two, one, gain; tops = a list
+        of int32[L, 8] per contig when asked for: P1.score, P1.ref, P2.score, P2.ref, S1.score, S1.ref, S2.score, S2.ref of every row,
+        INT32_MIN, -1 where absent; stats).  Needs no graph."""
+        raw = [s if isinstance(s, (bytes, bytearray)) else str(s).encode("latin-1") for s in seqs]
+        rraw = [s if isinstance(s, (bytes, bytearray)) else str(s).encode("latin-1") for s in refs]
+        n, n_ref = len(raw), len(rraw)
+        table = np.ascontiguousarray(sub, dtype=np.int8)
+        if table.shape != (27, 27):
+            raise ValueError("sub must be int8[27, 27]")
+        offsets, roffsets = np.zeros(n + 1, dtype=np.uint64), np.zeros(n_ref + 1, dtype=np.uint64)
+        if n:
+            np.cumsum([len(s) for s in raw], out=offsets[1:])
+        if n_ref:
+            np.cumsum([len(s) for s in rraw], out=roffsets[1:])
+        recs = np.zeros(max(1, n), dtype=CHIMERA_REC)
+        tp = np.zeros((int(offsets[n]) + 1, 8), dtype=np.int32) if tops else None
+        st = _lib.ChimeraStats()
+        check(self._L.mgta_seqs_chimera(self.h, b"".join(raw), offsets.ctypes.data, n, b"".join(rraw), roffsets.ctypes.data, n_ref, table.ctypes.data,
+                                        int(gap_open), int(gap_extend), int(min_seg), int(min_gain), recs.ctypes.data, tp.ctypes.data if tops else None,
+                                        C.byref(st)), "mgta_seqs_chimera")
+        out = dict(recs=recs[:n], stats=st.as_dict())
+        if tops:
+            out["tops"] = [tp[int(offsets[i]):int(offsets[i + 1])] for i in range(n)]
         return out
 
     def release_scratch(self):
@@ -494,6 +534,10 @@ ALIGN_REC = np.dtype([("score", np.float64), ("status", np.int32), ("model_from"
 # mgta_nearest_rec
 NEAREST_REC = np.dtype([("status", np.int32), ("ref", np.int32), ("score", np.int32), ("ref_from", np.int32), ("ref_to", np.int32), ("n_match", np.int32),
                         ("n_ident", np.int32), ("n_insert", np.int32), ("n_delete", np.int32)], align=True)
+
+
+# mgta_chimera_rec (defined once, beside the readers of the step's files)
+CHIMERA_REC = _chimera_rec
 
 
 def link_pairs(pairs, n_residues, lens) -> dict:

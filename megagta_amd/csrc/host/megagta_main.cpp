@@ -1310,6 +1310,104 @@ static int main_nearest(int argc, char **argv) {
     return 0;
 }
 
+// ---- chimera: the records of a gene's protein contigs that two sequences of the gene's reference set explain better than one (the place
+// of `uchime`, bin/post_proc.sh:89-95; the rule is mgta_seqs_chimera's own).  Needs no graph and leaves a worker's resident graphs alone.
+// References and scoring are read as `nearest` reads them.  Formats: INTEGRATION.md 2m.
+static int main_chimera(int argc, char **argv) {
+    if (argc != 9 && argc != 11) {
+        fprintf(stderr, "Usage: megagta chimera <ref.faa> <prot.fasta> <out_prefix> <gap_open> <gap_extend> <scoring> <min_seg> <min_gain> [<nucl.fasta> <nucl_out_prefix>]\n");
+        return 1;
+    }
+    RssLine rss;
+    const std::string ref_fasta = argv[1], fasta = argv[2], out_prefix = argv[3];
+    long long par[4];
+    const char *par_name[4] = {"gap_open", "gap_extend", "min_seg", "min_gain"};
+    const int par_arg[4] = {4, 5, 7, 8};
+    for (int k = 0; k < 4; ++k) {
+        char *end = nullptr;
+        par[k] = strtoll(argv[par_arg[k]], &end, 10);
+        if (end == argv[par_arg[k]] || *end) { fprintf(stderr, "    [ERROR] chimera: %s '%s' is not an integer\n", par_name[k], argv[par_arg[k]]); return 1; }
+    }
+    const long long gap_open = par[0], gap_extend = par[1], min_seg = par[2], min_gain = par[3];
+    if (gap_extend < 0 || gap_extend > gap_open || gap_open > 1024) {
+        fprintf(stderr, "    [ERROR] chimera: gap_open = %lld, gap_extend = %lld: 0 <= gap_extend <= gap_open <= 1024 is needed: nothing written\n", gap_open, gap_extend);
+        return 1;
+    }
+    if (min_seg < 1 || min_seg > 4096) { fprintf(stderr, "    [ERROR] chimera: min_seg = %lld: 1 <= min_seg <= 4096 is needed: nothing written\n", min_seg); return 1; }
+    if (min_gain < 1 || min_gain > (1 << 20)) { fprintf(stderr, "    [ERROR] chimera: min_gain = %lld: 1 <= min_gain <= 2^20 is needed: nothing written\n", min_gain); return 1; }
+    int8_t sub[27 * 27];
+    const std::string bad = parse_scoring(argv[6], sub);
+    if (!bad.empty()) { fprintf(stderr, "    [ERROR] chimera: scoring: %s: nothing written\n", bad.c_str()); return 1; }
+    std::vector<std::string> names, headers, rnames, nnames, nheaders;
+    std::string seqs, rraw, refs, nseqs;
+    std::vector<uint64_t> offsets, rraw_off, roffsets(1, 0), noffsets;
+    read_fasta_records(fasta, names, seqs, offsets, &headers);
+    read_fasta_records(ref_fasta, rnames, rraw, rraw_off);
+    const int64_t n = (int64_t)names.size(), n_ref = (int64_t)rnames.size();
+    if (argc == 11) {
+        // `cluster`'s check: one nucleotide record per protein record, in order and under the same name
+        read_fasta_records(argv[9], nnames, nseqs, noffsets, &nheaders);
+        if (nnames.size() != names.size()) {
+            fprintf(stderr, "    [ERROR] chimera: %s holds %zu records, %s holds %zu: nothing written\n", fasta.c_str(), names.size(), argv[9], nnames.size());
+            return 1;
+        }
+        for (int64_t i = 0; i < n; ++i)
+            if (nnames[(size_t)i] != names[(size_t)i]) {
+                fprintf(stderr, "    [ERROR] chimera: record %lld is %s in %s and %s in %s: nothing written\n", (long long)i, names[(size_t)i].c_str(), fasta.c_str(),
+                        nnames[(size_t)i].c_str(), argv[9]);
+                return 1;
+            }
+    }
+    // the residues of a reference: its ASCII letters, upper-cased; `-`, `.`, `*` and everything else go (the file may be an alignment)
+    for (int64_t r = 0; r < n_ref; ++r) {
+        for (uint64_t p = rraw_off[(size_t)r]; p < rraw_off[(size_t)r + 1]; ++p) {
+            const unsigned char c = (unsigned char)rraw[p];
+            if (residue_class(c)) refs += (char)(c >= 'a' ? c - 32 : c);
+        }
+        roffsets.push_back(refs.size());
+    }
+    const double t0 = now_s();
+    mgta_ctx *ctx = ctx_get();
+    std::vector<mgta_chimera_rec> recs((size_t)n + 1);
+    mgta_chimera_stats st;
+    if (mgta_seqs_chimera(ctx, seqs.data(), offsets.data(), n, refs.data(), roffsets.data(), n_ref, sub, (int32_t)gap_open, (int32_t)gap_extend, (int32_t)min_seg,
+                          (int32_t)min_gain, recs.data(), nullptr, &st) != MGTA_OK) {
+        fprintf(stderr, "    [ERROR] chimera: %s: nothing written\n", mgta_last_error());
+        ctx_put(ctx);
+        return 1;
+    }
+    logf("chimera check of %lld records among %lld references, min_seg %lld, min_gain %lld: %lld chimeric, %lld clean, %lld unchecked; %lld cells in %lld items, "
+         "%lld segments in %lld groups, %lld workgroups of %lld waves, %lld per CU, %lld B of LDS, %lld B of boundary buffers; parents: %lld cells in %lld items; peak %lld B; "
+         "top two %.1f ms, parents %.1f ms; wall %.3f s", (long long)st.n_seqs, (long long)st.n_refs, min_seg, min_gain, (long long)st.n_chimeric, (long long)st.n_clean,
+         (long long)st.n_unchecked, (long long)st.n_cells, (long long)st.n_items, (long long)st.n_segments, (long long)st.n_groups, (long long)st.grid_blocks,
+         (long long)st.waves_per_block, (long long)st.blocks_per_cu, (long long)st.lds_bytes, (long long)st.bound_bytes, (long long)st.n_parent_cells,
+         (long long)st.n_parent_items, (long long)st.peak_bytes, st.ms_top, st.ms_parents, now_s() - t0);
+    std::string table = "#contig\tstatus\tref\tscore\tlen\tbreak\tleft_ref\tleft_score\tright_ref\tright_score\ttwo\tone\tgain\n", kept, nkept;
+    auto ref_name = [&](int32_t r) { return r < 0 ? std::string("-") : rnames[(size_t)r]; };
+    for (int64_t i = 0; i < n; ++i) {
+        const size_t u = (size_t)i;
+        const mgta_chimera_rec &r = recs[u];
+        table += names[u] + "\t" + (r.status == 0 ? "clean" : r.status == 1 ? "chimeric" : "unchecked") + "\t" + ref_name(r.ref) + "\t" + std::to_string(r.score) + "\t" +
+                 std::to_string(offsets[u + 1] - offsets[u]) + "\t" + std::to_string(r.brk) + "\t" + ref_name(r.left_ref) + "\t" + std::to_string(r.left_score) + "\t" +
+                 ref_name(r.right_ref) + "\t" + std::to_string(r.right_score) + "\t" + std::to_string(r.two) + "\t" + std::to_string(r.one) + "\t" +
+                 std::to_string(r.gain) + "\n";
+        if (r.status == 1) continue;
+        kept += ">" + headers[u] + "\n";
+        kept.append(seqs, (size_t)offsets[u], (size_t)(offsets[u + 1] - offsets[u]));
+        kept += "\n";
+        if (argc == 11) {
+            nkept += ">" + nheaders[u] + "\n";
+            nkept.append(nseqs, (size_t)noffsets[u], (size_t)(noffsets[u + 1] - noffsets[u]));
+            nkept += "\n";
+        }
+    }
+    if (!write_text_file(out_prefix + "_chimera.txt", table)) die("cannot write %s_chimera.txt", out_prefix.c_str());
+    if (!write_text_file(out_prefix + "_nochim.fasta", kept)) die("cannot write %s_nochim.fasta", out_prefix.c_str());
+    if (argc == 11 && !write_text_file(std::string(argv[10]) + "_nochim.fasta", nkept)) die("cannot write %s_nochim.fasta", argv[10]);
+    ctx_put(ctx);
+    return 0;
+}
+
 static int dispatch(int argc, char **argv);
 
 // megagta serve: requests on stdin, one per line: the sub-command's argv, tab separated; a field "<PATH" / ">PATH" redirects the
@@ -1397,7 +1495,7 @@ int main(int argc, char **argv) {
 static int dispatch(int argc, char **argv) {
     if (argc < 2) {
         fprintf(stderr, "Usage: %s <sub_program> [sub options]\n    sub-programs on the MI355X hot path:\n        buildgraph    build succinct de Bruijn graph\n"
-                        "        denovo        tips, bubbles, contigs of an intermediate k\n        search        HMM-guided search of gene contigs\n        findstart     find starting kmers of the search\n        coverage      per-contig k-mer coverage and abundance from the graph\n        matchreads    the reads that share a (k+1)-mer with a set of contigs\n        derep         the unique, non-contained records of a FASTA\n        align         protein records placed on the columns of a profile HMM\n        cluster       complete-linkage clusters of aligned protein records\n        nearest       the closest reference protein of every protein record\n        dumpversion   dump version\n", argv[0]);
+                        "        denovo        tips, bubbles, contigs of an intermediate k\n        search        HMM-guided search of gene contigs\n        findstart     find starting kmers of the search\n        coverage      per-contig k-mer coverage and abundance from the graph\n        matchreads    the reads that share a (k+1)-mer with a set of contigs\n        derep         the unique, non-contained records of a FASTA\n        align         protein records placed on the columns of a profile HMM\n        cluster       complete-linkage clusters of aligned protein records\n        nearest       the closest reference protein of every protein record\n        chimera       protein records that two references explain better than one\n        dumpversion   dump version\n", argv[0]);
         return 1;
     }
     std::string sub = argv[1];
@@ -1411,6 +1509,7 @@ static int dispatch(int argc, char **argv) {
     if (sub == "align") return main_align(argc - 1, argv + 1);
     if (sub == "cluster") return main_cluster(argc - 1, argv + 1);
     if (sub == "nearest") return main_nearest(argc - 1, argv + 1);
+    if (sub == "chimera") return main_chimera(argc - 1, argv + 1);
     if (sub == "filterbylen") return main_filterbylen(argc - 1, argv + 1);
     if (sub == "translate") return main_translate(argc - 1, argv + 1);
     if (sub == "buildlib") {                                             // build_read_lib.cpp:8-20 (host only: file formats, no kernel)
@@ -1513,6 +1612,6 @@ static int dispatch(int argc, char **argv) {
         return 0;
     }
     if (sub == "dumpversion") { printf("%s\n", mgta_version()); return 0; }
-    fprintf(stderr, "sub-command '%s' is not built here (buildlib, buildgraph, denovo, findstart, search, coverage, matchreads, derep, align, cluster, nearest, filterbylen, translate are): run it with the reference's megagta binary\n", sub.c_str());
+    fprintf(stderr, "sub-command '%s' is not built here (buildlib, buildgraph, denovo, findstart, search, coverage, matchreads, derep, align, cluster, nearest, chimera, filterbylen, translate are): run it with the reference's megagta binary\n", sub.c_str());
     return 1;
 }

@@ -59,7 +59,13 @@ USAGE = """Usage:
                      contigs are the representatives, prot_merged[_rmdup]_rep_seqs.fasta, and the files are ..._rep_seqs_nearest*.txt (GPU 0)
     --nearest-scoring S       MATCH,MISMATCH or a substitution matrix file in NCBI format [5,-4: this driver's own default]
     --nearest-gap-open N      cost of a gap's first residue [10: this driver's own default]
-    --nearest-gap-extend N    cost of every further residue of a gap [1: this driver's own default]"""
+    --nearest-gap-extend N    cost of every further residue of a gap [1: this driver's own default]
+    --chimera        after every other step: per gene the protein contigs that two of the gene's reference proteins (column 4 of the gene
+                     list) explain better than one: contigs/<gene>/prot_merged[_rmdup][_rep_seqs]_chimera.txt (every contig, its break and
+                     its two parents) and prot_..._nochim.fasta, nucl_..._nochim.fasta (the contigs that are not chimeric); scoring and gap
+                     costs are the --nearest-* options; the rule is this project's own, not uchime's (GPU 0)
+    --chimera-min-seg N       fewest residues on either side of a break [10: this driver's own default, from a CPU trial]
+    --chimera-min-gain N      what two parents must score above one for a contig to go [15: this driver's own default, from a CPU trial]"""
 
 
 class Usage(Exception):
@@ -101,6 +107,9 @@ class Opt:
         self.nearest_scoring = "5,-4"
         self.nearest_gap_open = 10
         self.nearest_gap_extend = 1
+        self.chimera = False
+        self.chimera_min_seg = 10
+        self.chimera_min_gain = 15
 
 
 opt = Opt()
@@ -109,7 +118,8 @@ cp = 0
 LONG = ["help", "read=", "12=", "out-dir=", "memory=", "gpu-mem=", "min-contig-len=", "num-cpu-threads=", "kmin-1pass", "k-list=",
         "min-count=", "max-tip-len=", "no-mercy", "keep-tmp-files", "mem-flag=", "version", "verbose", "continue", "gene-list=",
         "prune-len=", "low-cov-penalty=", "bin=", "one-process-per-step", "gpus=", "coverage", "match-reads", "derep", "align", "cluster",
-        "cluster-dist=", "cluster-min-overlap=", "nearest", "nearest-scoring=", "nearest-gap-open=", "nearest-gap-extend="]
+        "cluster-dist=", "cluster-min-overlap=", "nearest", "nearest-scoring=", "nearest-gap-open=", "nearest-gap-extend=",
+        "chimera", "chimera-min-seg=", "chimera-min-gain="]
 
 
 def parse_opt(argv):
@@ -166,6 +176,9 @@ def parse_opt(argv):
         elif o == "--nearest-scoring": opt.nearest_scoring = v
         elif o == "--nearest-gap-open": opt.nearest_gap_open = int(v)
         elif o == "--nearest-gap-extend": opt.nearest_gap_extend = int(v)
+        elif o == "--chimera": opt.chimera = True
+        elif o == "--chimera-min-seg": opt.chimera_min_seg = int(v)
+        elif o == "--chimera-min-gain": opt.chimera_min_gain = int(v)
         else:
             raise Usage("Invalid option " + o)
     opt.temp_dir = opt.out_dir + "tmp/"
@@ -223,6 +236,10 @@ def check_opt():
         raise Usage("--cluster-min-overlap should be >= 1")
     if not 0 <= opt.nearest_gap_extend <= opt.nearest_gap_open <= 1024:
         raise Usage("--nearest-gap-open and --nearest-gap-extend should satisfy 0 <= extend <= open <= 1024")
+    if not 1 <= opt.chimera_min_seg <= 4096:
+        raise Usage("--chimera-min-seg should be between [1, 4096]")
+    if not 1 <= opt.chimera_min_gain <= 1 << 20:
+        raise Usage("--chimera-min-gain should be between [1, 1048576]")
     if opt.host_mem <= 0:
         raise Usage("Please specify a positive number for -m flag.")
     if opt.host_mem < 1:
@@ -677,6 +694,21 @@ def nearest(k):
         write_cp()
 
 
+def chimera(k):
+    """--chimera: per gene the protein contigs that two reference proteins explain better than one, and the contigs without them
+    (`megagta chimera`, GPU 0; no graph is needed, k only names the step).  Contigs, references, scoring and gap costs are those of
+    --nearest, which need not run; the nucleotide companion is selected by name.  Its checkpoints come after every other checkpoint,
+    those of --nearest included, so `--continue` works under any combination."""
+    tail = "_merged" + ("_rmdup" if opt.derep else "") + ("_rep_seqs" if opt.cluster else "")
+    for gene in opt.gene_info:
+        d = opt.out_dir + "contigs/" + gene
+        if should_run():
+            run_step([opt.bin, "chimera", opt.gene_info[gene][2], d + "/prot" + tail + ".fasta", d + "/prot" + tail, str(opt.nearest_gap_open),
+                      str(opt.nearest_gap_extend), opt.nearest_scoring, str(opt.chimera_min_seg), str(opt.chimera_min_gain), d + "/nucl" + tail + ".fasta",
+                      d + "/nucl" + tail], "Checking the contigs of %s for chimeras" % gene)
+        write_cp()
+
+
 def after_search(k):
     """the opt-in steps on the last k's graph, in a fixed order behind every checkpoint of a run without them"""
     if opt.coverage:
@@ -691,6 +723,8 @@ def after_search(k):
         cluster(k)
     if opt.nearest:
         nearest(k)
+    if opt.chimera:
+        chimera(k)
 
 
 def main(argv=None):
