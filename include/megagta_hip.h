@@ -262,6 +262,59 @@ int mgta_contig_coverage(mgta_sdbg *, const char *seqs, const uint64_t *offsets 
                          uint16_t *per_window /* optional */, int64_t *abundance /* optional, [65536] */, mgta_coverage_stats *stats /* optional */);
 
 /* ------------------------------------------------------------------------------------------------
+ * Window-shared coverage: a coverage that ADDS UP over sets of contigs (what per-cluster and per-taxon abundance are summed from;
+ * mgta_contig_coverage credits an edge's full multiplicity to every contig that walks over it, so its numbers cannot be summed over
+ * redundant contigs).  Contigs, windows and the edge of a window are exactly those of mgta_contig_coverage: only the string as given
+ * is looked up, a window with a letter other than A, C, G, T has no edge, there is no N -> G folding.  With
+ *   edge(i, p)  the edge of window p of contig i, or none,
+ *   mult(e)     its multiplicity, capped at 65535,
+ *   share(e)    the number of windows OF THIS CALL whose edge is e (occurrences, not distinct contigs: a contig that holds the same
+ *               (k+1)-mer twice contributes 2, and both of its windows carry that share),
+ *   mass(i, p)  floor(mult(e) * 65536 / share(e)), an unsigned Q16 number; 0 for a window without an edge,
+ * per_contig[i].mass = the sum of mass(i, p) over its windows.  per_window_share (may be NULL): the shares back to back, contig by
+ * contig, as per_window of the coverage call, 0 = no edge; per_window (may be NULL): the multiplicities, laid out the same way.
+ * Each edge loses less than share(e) units to the floor, so with total_mult = the sum of mult over the DISTINCT edges of the call
+ *   65536 * total_mult - (covered windows of the call)  <=  sum of per_contig[i].mass  <=  65536 * total_mult.
+ * Every output and every stats field but ms_* and n_batches is a function of (graph, contigs) only; the order of the contigs in the
+ * call changes nothing but the order of the records.  One call = one set of contigs: shares are counted over the whole call,
+ * whatever the batches the library cuts its walk into (mgta_ctx_set_coverage_batch moves no output).  The counts live in a table
+ * keyed by the edge id and sized by the windows of the call, never by the graph; mgta_ctx_set_share_hash_bits keeps only the low
+ * `bits` bits of its hash (1 .. 64, default 64): with a few bits nearly every key collides and the outputs must not move -- a switch
+ * for tests, like mgta_ctx_set_derep_hash_bits.  Limits: n < 2^31 contigs and fewer than 2^32 windows in the call (a share fits 32
+ * bits); beyond either the call returns MGTA_EINVAL, says which, and writes nothing.  Device memory: 8 bytes per window of a batch,
+ * 4 bytes per window of the call and 16 bytes per table slot (2 to 4 slots per min(windows, edges of the graph)), accounted like
+ * every other buffer of the context; what does not fit is MGTA_ENOMEM, nothing is truncated.  MGTA_EINVAL for a graph loaded
+ * without mgta_ctx_keep_multiplicity.  n = 0: MGTA_OK, stats all zero.
+ * ------------------------------------------------------------------------------------------------ */
+typedef struct mgta_contig_share {
+    uint64_t mass;                   /* sum of the window masses, Q16 */
+    uint32_t len, n_windows;         /* as in mgta_contig_cov */
+    uint32_t n_covered;              /* windows with an edge of multiplicity > 0 */
+    uint32_t n_unique;               /* covered windows whose edge no other window of the call has (share 1) */
+    uint32_t max_share;              /* largest share over the covered windows; 0 when nothing is covered */
+    uint32_t reserved_;              /* 0 */
+} mgta_contig_share;
+typedef struct mgta_share_stats {
+    int64_t n_contigs, n_windows;
+    int64_t n_walked, n_index_searches;   /* as in mgta_coverage_stats, and equal to them on the same input: the walk is done once */
+    int64_t n_batches;
+    int64_t n_covered;               /* covered windows of the call */
+    int64_t n_distinct_edges;        /* distinct edges the windows of the call found */
+    uint64_t total_mult;             /* sum of mult over those distinct edges */
+    uint64_t total_mass;             /* sum of per_contig[i].mass */
+    uint64_t table_slots;            /* slots of the count table */
+    uint64_t table_bytes;            /* its bytes (key + count and multiplicity per slot) */
+    uint64_t window_bytes;           /* bytes kept per call beside it: the slot number of every window */
+    double ms_walk;                  /* the walk kernel (HIP events) */
+    double ms_count;                 /* edge ids -> table, batch by batch */
+    double ms_share;                 /* table -> masses and per-contig records */
+    double ms_total;                 /* the three together */
+} mgta_share_stats;
+int mgta_ctx_set_share_hash_bits(mgta_ctx *, int bits);   /* 1..64, default 64 */
+int mgta_contig_share_coverage(mgta_sdbg *, const char *seqs, const uint64_t *offsets /* [n + 1] */, int64_t n, mgta_contig_share *per_contig,
+                               uint32_t *per_window_share /* optional */, uint16_t *per_window /* optional */, mgta_share_stats *stats /* optional */);
+
+/* ------------------------------------------------------------------------------------------------
  * Read recruitment (the `-m proc_match_reads.fa` output of the same `kmer_coverage` command line, bin/post_proc.sh:113-118): which reads
  * of the library share a (k+1)-mer with a set of contigs.  Contigs as in mgta_contig_coverage; reads as uploaded for the build
  * (reads_reversed as in mgta_findstart: one upload serves buildgraph, findstart and this).  Every WINDOW of a contig, as given AND

@@ -80,6 +80,21 @@ class CoverageStats(C.Structure):
         return {n: getattr(self, n) for n, _ in self._fields_}
 
 
+class ContigShare(C.Structure):
+    _fields_ = [("mass", C.c_uint64), ("len", C.c_uint32), ("n_windows", C.c_uint32), ("n_covered", C.c_uint32), ("n_unique", C.c_uint32),
+                ("max_share", C.c_uint32), ("reserved_", C.c_uint32)]
+
+
+class ShareStats(C.Structure):
+    _fields_ = [("n_contigs", C.c_int64), ("n_windows", C.c_int64), ("n_walked", C.c_int64), ("n_index_searches", C.c_int64), ("n_batches", C.c_int64),
+                ("n_covered", C.c_int64), ("n_distinct_edges", C.c_int64), ("total_mult", C.c_uint64), ("total_mass", C.c_uint64),
+                ("table_slots", C.c_uint64), ("table_bytes", C.c_uint64), ("window_bytes", C.c_uint64), ("ms_walk", C.c_double), ("ms_count", C.c_double),
+                ("ms_share", C.c_double), ("ms_total", C.c_double)]
+
+    def as_dict(self):
+        return {n: getattr(self, n) for n, _ in self._fields_}
+
+
 class MatchStats(C.Structure):
     _fields_ = [("n_contigs", C.c_int64), ("n_contig_windows", C.c_int64), ("n_marked_edges", C.c_int64), ("n_reads", C.c_int64),
                 ("n_read_windows", C.c_int64), ("n_walked", C.c_int64), ("n_index_searches", C.c_int64), ("n_matched_reads", C.c_int64),
@@ -211,6 +226,8 @@ SYMBOLS = {
                                       C.POINTER(C.c_void_p)]),
     "mgta_sdbg_edge_multiplicity": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p]),
     "mgta_contig_coverage": (C.c_int, [C.c_void_p, C.c_char_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "mgta_contig_share_coverage": (C.c_int, [C.c_void_p, C.c_char_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "mgta_ctx_set_share_hash_bits": (C.c_int, [C.c_void_p, C.c_int]),
     "mgta_reads_match_contigs": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_uint64, C.c_char_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p,
                                           C.c_void_p]),
     "mgta_seqs_derep": (C.c_int, [C.c_void_p, C.c_char_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),

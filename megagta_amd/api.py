@@ -113,6 +113,11 @@ class Context:
         the batching on small inputs.  The result does not depend on it."""
         check(self._L.mgta_ctx_set_coverage_batch(self.h, int(windows)), "mgta_ctx_set_coverage_batch")
 
+    def set_share_hash_bits(self, bits: int = 64):
+        """bits of the hash the count table of Graph.contig_share_coverage keeps (1 .. 64, default 64); a few bits make nearly every key
+        collide and move no output -- a switch for tests"""
+        check(self._L.mgta_ctx_set_share_hash_bits(self.h, int(bits)), "mgta_ctx_set_share_hash_bits")
+
     def set_derep_hash_bits(self, bits: int = 64):
         """bits of both hashes `derep` keeps (1 .. 64, the default): with a few bits nearly every key collides.  The result does not
         depend on it; only stats["n_compares"] does."""
@@ -362,6 +367,8 @@ def export_records_to_torch(ctx: "Context"):
 
 
 # mgta_contig_cov
+SHARE_DTYPE = np.dtype([("mass", "<u8"), ("len", "<u4"), ("n_windows", "<u4"), ("n_covered", "<u4"), ("n_unique", "<u4"), ("max_share", "<u4"),
+                        ("reserved_", "<u4")])
 COV_DTYPE = np.dtype([("sum", "<u8"), ("len", "<u4"), ("n_windows", "<u4"), ("n_covered", "<u4"), ("min", "<u4"), ("max", "<u4"), ("median", "<u4")])
 
 
@@ -485,6 +492,31 @@ class Graph:
         out = dict(contigs=cov, abundance=ab, stats=st.as_dict())
         if per_window:
             out["per_window"], out["window_offsets"] = pw, woff
+        return out
+
+    def contig_share_coverage(self, seqs, per_window: bool = False) -> dict:
+        """mgta_contig_share_coverage for a list of contigs (str or bytes, any case): the multiplicity of every edge split among the windows
+        of THIS call that land on it, so that the masses add up over any set of contigs.  -> dict(contigs = structured array (mass: Q16,
+        len, n_windows, n_covered, n_unique, max_share), stats, and with per_window=True per_window_share = uint32 shares back to back
+        (0 = no edge), per_window = uint16 multiplicities + window_offsets int64[n + 1]).  One call = one set of contigs."""
+        raw = [s if isinstance(s, (bytes, bytearray)) else str(s).encode() for s in seqs]
+        n = len(raw)
+        offsets = np.zeros(n + 1, dtype=np.uint64)
+        if n:
+            np.cumsum([len(s) for s in raw], out=offsets[1:])
+        rec = np.zeros(n, dtype=SHARE_DTYPE)
+        nw = np.maximum(0, np.diff(offsets.astype(np.int64)) - self.ctx._L.mgta_sdbg_k(self.h))      # (the graph's own k sizes the buffers)
+        woff = np.zeros(n + 1, dtype=np.int64)
+        np.cumsum(nw, out=woff[1:])
+        pws = np.zeros(int(woff[-1]), dtype=np.uint32) if per_window else None
+        pw = np.zeros(int(woff[-1]), dtype=np.uint16) if per_window else None
+        st = _lib.ShareStats()
+        check(self.ctx._L.mgta_contig_share_coverage(self.h, b"".join(raw), offsets.ctypes.data, n, rec.ctypes.data if n else None,
+                                                     pws.ctypes.data if per_window and pws.size else None, pw.ctypes.data if per_window and pw.size else None,
+                                                     C.byref(st)), "mgta_contig_share_coverage")
+        out = dict(contigs=rec, stats=st.as_dict(), per_window_share=pws, per_window=pw)
+        if per_window:
+            out["window_offsets"] = woff
         return out
 
     def match_reads(self, reads: "Reads", seqs, n_short_reads: int | None = None, counts: bool = False, reads_reversed: bool = True) -> dict:

@@ -1,5 +1,7 @@
 // coverage.hip — per-contig k-mer coverage and abundance from the resident graph, the batched EdgeMultiplicity query, and read
-// recruitment (the reads that share a (k+1)-mer with a set of contigs: the same walk, over reads; further down).
+// recruitment (the reads that share a (k+1)-mer with a set of contigs: the same walk, over reads; further down), and the
+// window-shared coverage (every edge's multiplicity split among the windows of the call that land on it: the same walk, once, then
+// a count per distinct edge; at the end).
 //
 // The reference's last post-processing step (`kmer_coverage`, bin/post_proc.sh:113-118) counts the (k+1)-mers of the contigs in a
 // second pass over all reads.  That count is the multiplicity the edge stream already carries (sdbg_multi_io.h:83-112) and a graph
@@ -388,6 +390,189 @@ __global__ __launch_bounds__(kCovThreads) void match_walk_kernel(GraphDev g, con
     }
 }
 
+// ---- window-shared coverage (mgta_contig_share_coverage): every edge's multiplicity split among the windows of the call on it -------
+// Three phases.  (1) The walk above, once, leaving the edge id of every window of a batch (8 bytes, -1 = none) where the coverage
+// call leaves the multiplicity.  (2) The ids of the batch go into an open-addressing table keyed by the edge id (linear probing, 64-bit
+// compare-and-swap for the key, one 64-bit atomic add for the value: occurrences in the low word, the multiplicity -- added once, by the
+// lane that created the key -- in the high word) and every window keeps its slot number, 4 bytes, for the whole call.  (3) When all
+// batches are counted, one pass over the slot numbers: one 8-byte gather and one 32-bit division per window, one wave per contig.
+// Slot 0 is never used by a key and stands for "no edge": its value stays 0.
+//
+// Redundant contigs put thousands of windows on one edge, all on one address.  So equal ids are added up inside a wave before the
+// atomic: a wave of the count kernel owns 64 contigs that follow each other in the batch's job order (longest first, ties by number:
+// copies and contigs of one length sit side by side) and visits them position by position, lane l holding window p of its contig;
+// the lanes with equal ids elect the lowest one, which adds their number.  gfx950 has no match-any instruction: one ballot per
+// distinct id of the step, 1 when the 64 ids agree, 64 when they all differ.
+
+constexpr unsigned long long kShareEmpty = ~0ull;                         // (an edge id is < 2^63)
+
+// counters: [0] queue head, [1] windows found by a step, [2] index searches (cov_walk_kernel's; [3] .. [5] belong to share_count_kernel)
+__global__ __launch_bounds__(kCovThreads) void share_walk_kernel(GraphDev g, const uint8_t *sym, const CovJob *jobs, uint32_t n_jobs, uint32_t chunk, int64_t *ids,
+                                                                 unsigned long long *counters) {
+    const int sub = threadIdx.x & 7;
+    const int k = g.k;
+    uint32_t walked = 0, searched = 0;
+    for (;;) {
+        unsigned long long first = 0;
+        if (sub == 0) first = atomicAdd(&counters[0], (unsigned long long)chunk);
+        first = __shfl(first, 0, 8);
+        if (first >= n_jobs) break;
+        const uint32_t j_end = (uint32_t)min((unsigned long long)n_jobs, first + chunk);
+        for (uint32_t j = (uint32_t)first; j < j_end; ++j) {
+            const CovJob job = jobs[j];
+            const uint8_t *s = sym + job.off;
+            const uint32_t n_win = job.len > (uint32_t)k ? job.len - (uint32_t)k : 0;
+            int64_t *out = ids + job.win_base;
+            int run = 0;                                                  // A C G T letters in a row, up to the window's last letter
+            for (int i = 0; i < k && (uint32_t)i < job.len; ++i) run = s[i] ? run + 1 : 0;
+            int64_t e = -1;                                               // the edge of the window before, -1 = the walk has to start again
+            LineR L{};
+            int64_t mine = -1;
+            for (uint32_t p = 0; p < n_win; ++p) {
+                const int c = s[p + k];
+                run = c ? run + 1 : 0;
+                if (run > k) {
+                    if (e >= 0) {
+                        e = cov_step(g, L, e, c, sub);
+                        if (e >= 0) ++walked;
+                    } else {
+                        e = g_index_edge(g, s + p);
+                        ++searched;
+                        if (e >= 0) L = grp_load_line(g, (uint64_t)e >> 6, sub);
+                    }
+                } else e = -1;
+                // eight windows leave as one 64-byte store of the group
+                if ((int)(p & 7) == sub) mine = e;
+                if ((p & 7) == 7 || p + 1 == n_win) {
+                    const uint32_t q = (p & ~7u) + (uint32_t)sub;
+                    if (q <= p) out[q] = mine;
+                }
+            }
+        }
+    }
+    const uint32_t w = wave_sum(sub == 0 ? walked : 0u), sc = wave_sum(sub == 0 ? searched : 0u);
+    if (lane_id() == 0) {
+        if (w) atomicAdd(&counters[1], (unsigned long long)w);
+        if (sc) atomicAdd(&counters[2], (unsigned long long)sc);
+    }
+}
+
+// the value lane `src` (the same in every lane) holds
+__device__ __forceinline__ int64_t wave_read64(int64_t v, int src) {
+    const uint32_t lo = (uint32_t)__builtin_amdgcn_readlane((int)(uint32_t)v, src), hi = (uint32_t)__builtin_amdgcn_readlane((int)(uint32_t)((uint64_t)v >> 32), src);
+    return (int64_t)(((uint64_t)hi << 32) | lo);
+}
+
+__device__ __forceinline__ uint64_t mix64_share(uint64_t x) {             // the finaliser of splitmix64, as in derep.hip
+    x ^= x >> 30; x *= 0xBF58476D1CE4E5B9ull;
+    x ^= x >> 27; x *= 0x94D049BB133111EBull;
+    return x ^ (x >> 31);
+}
+
+// `times` occurrences of edge e -> its slot (1 .. n_slots - 1); 0 and *full = 1 when the table has no room (it is sized so that it has)
+__device__ __forceinline__ uint32_t share_table_add(const MultDev &m, unsigned long long *keys, unsigned long long *vals, uint64_t n_slots, uint64_t hmask, int64_t e,
+                                                    uint32_t times, uint32_t &n_new, uint64_t &sum_mult, unsigned long long *full) {
+    uint64_t slot = mix64_share((uint64_t)e) & hmask & (n_slots - 1);
+    if (slot == 0) slot = 1;
+    for (uint64_t tries = 0; tries < n_slots; ++tries) {
+        unsigned long long key = __hip_atomic_load(&keys[slot], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        if (key == kShareEmpty) {
+            key = atomicCAS(&keys[slot], kShareEmpty, (unsigned long long)e);
+            if (key == kShareEmpty) {                                     // this lane made the key: it brings the multiplicity, once
+                const uint32_t mult = g_edge_mult(m, e);
+                atomicAdd(&vals[slot], ((unsigned long long)mult << 32) | times);
+                ++n_new;
+                sum_mult += mult;
+                return (uint32_t)slot;
+            }
+        }
+        if (key == (unsigned long long)e) {
+            atomicAdd(&vals[slot], (unsigned long long)times);
+            return (uint32_t)slot;
+        }
+        slot = (slot + 1) & (n_slots - 1);
+        if (slot == 0) slot = 1;
+    }
+    atomicExch(full, 1ull);
+    return 0;
+}
+
+// counters: [3] keys made, [4] the sum of their multiplicities, [5] set when the table ran full
+__global__ __launch_bounds__(256) void share_count_kernel(MultDev m, const CovJob *jobs, uint32_t n_jobs, int k, const int64_t *ids, uint64_t win_done, uint32_t *slots,
+                                                          unsigned long long *keys, unsigned long long *vals, uint64_t n_slots, uint64_t hmask,
+                                                          unsigned long long *counters) {
+    const int lane = lane_id();
+    const uint32_t j = blockIdx.x * 64 + (uint32_t)lane;
+    uint32_t n_win = 0;
+    uint64_t base = 0;
+    if (j < n_jobs) {
+        const CovJob job = jobs[j];
+        n_win = job.len > (uint32_t)k ? job.len - (uint32_t)k : 0;
+        base = job.win_base;
+    }
+    const uint64_t longest = wave_max(n_win);
+    uint32_t n_new = 0;
+    uint64_t sum_mult = 0;
+    // the four waves of a workgroup take turns of 64 positions; every lane stays to the end (the shuffle below reads any lane)
+    for (uint64_t p0 = ((uint64_t)blockIdx.y * 4 + (uint64_t)wave_id()) * 64; p0 < longest; p0 += (uint64_t)gridDim.y * 256) {
+        const uint64_t p1 = min(longest, p0 + 64);
+        for (uint64_t p = p0; p < p1; ++p) {
+            const bool in = p < n_win;
+            const int64_t e = in ? ids[base + p] : -1;
+            int leader = lane;
+            uint32_t times = 1;
+            uint64_t todo = __ballot(e >= 0);
+            while (todo) {                                                // one turn per distinct id among the 64
+                const int src = __ffsll((long long)todo) - 1;
+                const int64_t e0 = wave_read64(e, src);
+                const uint64_t same = __ballot(e == e0);
+                if (e == e0) { leader = src; times = (uint32_t)__popcll(same); }
+                todo &= ~same;
+            }
+            uint32_t slot = 0;
+            if (e >= 0 && leader == lane) slot = share_table_add(m, keys, vals, n_slots, hmask, e, times, n_new, sum_mult, &counters[5]);
+            slot = __shfl(slot, leader, 64);
+            if (in) slots[win_done + base + p] = slot;
+        }
+    }
+    n_new = wave_sum(n_new);
+    sum_mult = wave_sum64(sum_mult);
+    if (lane == 0) {
+        if (n_new) atomicAdd(&counters[3], (unsigned long long)n_new);
+        if (sum_mult) atomicAdd(&counters[4], (unsigned long long)sum_mult);
+    }
+}
+
+// One wave per contig over the slot numbers of its windows, when every batch is counted: one 8-byte gather (occurrences low,
+// multiplicity high; slot 0 = no edge = 0) and ONE 32-bit division per window -- mult <= 65535, so mult << 16 fits 32 bits and
+// floor(mult * 65536 / share) is that quotient exactly.  The mass is an integer sum: no order matters.
+__global__ __launch_bounds__(256) void share_mass_kernel(const uint64_t *woff, const uint32_t *lens, uint32_t n, const uint32_t *slots, const unsigned long long *vals,
+                                                         mgta_contig_share *out, uint32_t *pw_share, uint16_t *pw_mult) {
+    const int lane = lane_id();
+    const uint32_t i = blockIdx.x * 4 + (uint32_t)wave_id();
+    if (i >= n) return;                                                   // (whole waves leave)
+    const uint64_t b = woff[i];
+    const uint32_t n_win = (uint32_t)(woff[i + 1] - b);
+    uint64_t mass = 0;
+    uint32_t nc = 0, nu = 0, mx = 0;
+    for (uint32_t q = lane; q < n_win; q += 64) {
+        const unsigned long long v = vals[slots[b + q]];
+        const uint32_t share = (uint32_t)v, mult = (uint32_t)(v >> 32);
+        if (mult) {
+            mass += (mult << 16) / share;
+            ++nc;
+            nu += share == 1u;
+            mx = max(mx, share);
+        }
+        if (pw_share) pw_share[b + q] = share;
+        if (pw_mult) pw_mult[b + q] = (uint16_t)mult;
+    }
+    mgta_contig_share res;
+    res.mass = wave_sum64(mass); res.len = lens[i]; res.n_windows = n_win; res.n_covered = wave_sum(nc); res.n_unique = wave_sum(nu);
+    res.max_share = wave_max(mx); res.reserved_ = 0;
+    if (lane == 0) out[i] = res;
+}
+
 }  // namespace
 }  // namespace mgta
 
@@ -617,6 +802,155 @@ int mgta_reads_match_contigs(mgta_sdbg *g, const mgta_reads *reads, int reads_re
             stats->n_walked = (int64_t)cnt[9]; stats->n_index_searches = (int64_t)cnt[10]; stats->n_matched_reads = (int64_t)cnt[11];
             stats->groups_per_cu = (int64_t)walk_per_cu * kGroups;
             stats->ms_mark = t_mark.ms(); stats->ms_walk = t_walk.ms();
+        }
+        return MGTA_OK;
+    });
+}
+
+int mgta_ctx_set_share_hash_bits(mgta_ctx *ctx, int bits) {
+    if (!ctx) { set_error("mgta_ctx_set_share_hash_bits: ctx must not be NULL"); return MGTA_EINVAL; }
+    if (bits < 1 || bits > 64) { set_error("mgta_ctx_set_share_hash_bits: bits = %d (1 .. 64)", bits); return MGTA_EINVAL; }
+    ctx->share_hash_bits = bits;
+    return MGTA_OK;
+}
+
+int mgta_contig_share_coverage(mgta_sdbg *g, const char *seqs, const uint64_t *offsets, int64_t n, mgta_contig_share *per_contig, uint32_t *per_window_share,
+                               uint16_t *per_window, mgta_share_stats *stats) {
+    if (!g || n < 0 || (n > 0 && (!offsets || !per_contig))) { set_error("mgta_contig_share_coverage: bad argument"); return MGTA_EINVAL; }
+    if (n > 0x7FFFFFFFll) { set_error("mgta_contig_share_coverage: %lld contigs (n < 2^31 is supported)", (long long)n); return MGTA_EINVAL; }
+    if (!g->has_mult) { set_error("mgta_contig_share_coverage: the graph was loaded without multiplicities (mgta_ctx_keep_multiplicity)"); return MGTA_EINVAL; }
+    const uint64_t k = (uint64_t)g->dev.k;
+    uint64_t total_win = 0, longest_win = 0;
+    for (int64_t i = 0; i < n; ++i) {
+        if (offsets[i + 1] < offsets[i] || offsets[i + 1] - offsets[i] > 0xFFFFFFF0ull || (offsets[i + 1] > offsets[i] && !seqs)) {
+            set_error("mgta_contig_share_coverage: contig %lld: offsets must ascend, a contig holds < 2^32 letters", (long long)i);
+            return MGTA_EINVAL;
+        }
+        const uint64_t len = offsets[i + 1] - offsets[i], wn = len > k ? len - k : 0;
+        total_win += wn;
+        longest_win = std::max(longest_win, wn);
+        if (total_win > 0xFFFFFFFFull) {
+            set_error("mgta_contig_share_coverage: more than 2^32 - 1 windows in the call (a share is a 32-bit count); contig %lld is the first beyond", (long long)i);
+            return MGTA_EINVAL;
+        }
+    }
+    if (stats) memset(stats, 0, sizeof(*stats));
+    if (n == 0) return MGTA_OK;
+    return guarded("mgta_contig_share_coverage", [&]() {
+        mgta_ctx *ctx = g->ctx;
+        MGTA_HIP_CHECK(hipSetDevice(ctx->device));
+        hipStream_t st = ctx->stream;
+        Timer t_walk(st), t_count(st), t_share(st);
+        const uint64_t cap = ctx->coverage_batch_windows ? ctx->coverage_batch_windows : 1ull << 29;   // windows per batch: 4 GB of edge ids
+        int blocks_per_cu = 0;
+        MGTA_HIP_CHECK(hipOccupancyMaxActiveBlocksPerMultiprocessor(&blocks_per_cu, share_walk_kernel, kCovThreads, 0));
+        blocks_per_cu = std::max(1, blocks_per_cu);
+        // the table: at most half full, never larger than 2^32 slots (a slot number is 32 bits; slot 0 is "no edge"), and sized by the
+        // windows of the call -- or by the graph where that has fewer edges than the call has windows
+        const uint64_t most_keys = std::min<uint64_t>(total_win, (uint64_t)std::max<int64_t>(g->dev.size, 0));
+        uint64_t n_slots = 1024;
+        while (n_slots < 2 * most_keys + 2 && n_slots < (1ull << 32)) n_slots <<= 1;
+        const uint64_t hmask = ctx->share_hash_bits >= 64 ? ~0ull : (1ull << ctx->share_hash_bits) - 1;
+        DevBuf d_cnt, d_sym, d_jobs, d_keys, d_vals, d_slots, d_woff, d_lens, d_out, d_pws, d_pwm;
+        d_cnt.alloc(64);
+        MGTA_HIP_CHECK(hipMemsetAsync(d_cnt.p, 0, 64, st));
+        d_keys.alloc(n_slots * 8, &ctx->live_bytes, &ctx->peak_bytes);
+        d_vals.alloc(n_slots * 8, &ctx->live_bytes, &ctx->peak_bytes);
+        d_slots.alloc(total_win * 4 + 16, &ctx->live_bytes, &ctx->peak_bytes);
+        MGTA_HIP_CHECK(hipMemsetAsync(d_keys.p, 0xFF, n_slots * 8, st));
+        MGTA_HIP_CHECK(hipMemsetAsync(d_vals.p, 0, n_slots * 8, st));
+        std::vector<CovJob> jobs;
+        uint64_t win_done = 0;
+        double ms_walk = 0, ms_count = 0;
+        int64_t n_batches = 0;
+        for (int64_t c0 = 0; c0 < n;) {
+            // the contigs [c0, c1) of this batch: as many as fit the scratch (one at least), exactly as mgta_contig_coverage cuts them
+            int64_t c1 = c0;
+            uint64_t n_win = 0;
+            jobs.clear();
+            while (c1 < n) {
+                const uint64_t len = offsets[c1 + 1] - offsets[c1], wn = len > k ? len - k : 0;
+                if (c1 > c0 && n_win + wn > cap) break;
+                jobs.push_back(CovJob{offsets[c1] - offsets[c0], n_win, (uint32_t)len, (uint32_t)(c1 - c0)});
+                n_win += wn;
+                ++c1;
+            }
+            const uint32_t nj = (uint32_t)jobs.size();
+            std::sort(jobs.begin(), jobs.end(), [](const CovJob &a, const CovJob &b) { return a.len != b.len ? a.len > b.len : a.idx < b.idx; });
+            const uint64_t batch_longest = jobs[0].len > k ? jobs[0].len - k : 0;
+            const uint64_t n_bytes = offsets[c1] - offsets[c0];
+            if (d_sym.bytes < n_bytes + 16) d_sym.alloc(n_bytes + 16, &ctx->live_bytes, &ctx->peak_bytes);
+            if (d_jobs.bytes < (size_t)nj * sizeof(CovJob)) d_jobs.alloc((size_t)nj * sizeof(CovJob), &ctx->live_bytes, &ctx->peak_bytes);
+            int64_t *d_ids = reinterpret_cast<int64_t *>(window_scratch(ctx, n_win * 8 + 64));
+            if (n_bytes) MGTA_HIP_CHECK(hipMemcpyAsync(d_sym.p, seqs + offsets[c0], n_bytes, hipMemcpyHostToDevice, st));
+            MGTA_HIP_CHECK(hipMemcpyAsync(d_jobs.p, jobs.data(), (size_t)nj * sizeof(CovJob), hipMemcpyHostToDevice, st));
+            MGTA_HIP_CHECK(hipMemsetAsync(d_cnt.p, 0, 8, st));            // the queue head
+            if (n_bytes)
+                hipLaunchKernelGGL(cov_symbols_kernel, dim3((unsigned)std::min<uint64_t>((n_bytes + 255) / 256, (uint64_t)ctx->num_cus * 16)), dim3(256), 0, st,
+                                   d_sym.as<uint8_t>(), n_bytes);
+            const uint64_t groups = (uint64_t)ctx->num_cus * (uint64_t)blocks_per_cu * (kCovThreads / 8);
+            const uint32_t chunk = nj >= groups * 64 ? 4u : 1u;
+            const unsigned blocks = (unsigned)std::min<uint64_t>((uint64_t)ctx->num_cus * (uint64_t)blocks_per_cu, ((uint64_t)nj + kCovThreads / 8 - 1) / (kCovThreads / 8));
+            t_walk.start();
+            if (g->dev.size > 0)
+                hipLaunchKernelGGL(share_walk_kernel, dim3(blocks), dim3(kCovThreads), 0, st, g->dev, d_sym.as<uint8_t>(), d_jobs.as<CovJob>(), nj, chunk, d_ids,
+                                   d_cnt.as<unsigned long long>());
+            else
+                MGTA_HIP_CHECK(hipMemsetAsync(d_ids, 0xFF, n_win * 8 + 64, st));   // no edge anywhere
+            MGTA_HIP_CHECK(hipGetLastError());
+            t_walk.end();
+            t_count.start();
+            if (batch_longest) {
+                const unsigned gy = (unsigned)std::min<uint64_t>((batch_longest + 255) / 256, 1024);
+                hipLaunchKernelGGL(share_count_kernel, dim3((nj + 63) / 64, gy), dim3(256), 0, st, g->mult, d_jobs.as<CovJob>(), nj, (int)k, d_ids, win_done,
+                                   d_slots.as<uint32_t>(), d_keys.as<unsigned long long>(), d_vals.as<unsigned long long>(), n_slots, hmask,
+                                   d_cnt.as<unsigned long long>());
+            }
+            MGTA_HIP_CHECK(hipGetLastError());
+            t_count.end();
+            MGTA_HIP_CHECK(hipStreamSynchronize(st));                     // (jobs and the device buffers serve the next batch)
+            ms_walk += t_walk.ms();
+            ms_count += t_count.ms();
+            win_done += n_win;
+            ++n_batches;
+            c0 = c1;
+        }
+        unsigned long long cnt[6] = {0, 0, 0, 0, 0, 0};
+        MGTA_HIP_CHECK(hipMemcpyAsync(cnt, d_cnt.p, 48, hipMemcpyDeviceToHost, st));
+        MGTA_HIP_CHECK(hipStreamSynchronize(st));
+        if (cnt[5]) { set_error("mgta_contig_share_coverage: the count table of %llu slots ran full", (unsigned long long)n_slots); return MGTA_EHIP; }
+        // every batch is counted: the shares are final.  The batch buffers make room for the outputs.
+        d_sym.release(); d_jobs.release();
+        std::vector<uint64_t> woff((size_t)n + 1, 0);
+        std::vector<uint32_t> lens((size_t)n);
+        for (int64_t i = 0; i < n; ++i) {
+            const uint64_t len = offsets[i + 1] - offsets[i];
+            lens[(size_t)i] = (uint32_t)len;
+            woff[(size_t)i + 1] = woff[(size_t)i] + (len > k ? len - k : 0);
+        }
+        d_woff.alloc(((size_t)n + 1) * 8, &ctx->live_bytes, &ctx->peak_bytes);
+        d_lens.alloc((size_t)n * 4, &ctx->live_bytes, &ctx->peak_bytes);
+        d_out.alloc((size_t)n * sizeof(mgta_contig_share), &ctx->live_bytes, &ctx->peak_bytes);
+        if (per_window_share && total_win) d_pws.alloc(total_win * 4, &ctx->live_bytes, &ctx->peak_bytes);
+        if (per_window && total_win) d_pwm.alloc(total_win * 2, &ctx->live_bytes, &ctx->peak_bytes);
+        MGTA_HIP_CHECK(hipMemcpyAsync(d_woff.p, woff.data(), ((size_t)n + 1) * 8, hipMemcpyHostToDevice, st));
+        MGTA_HIP_CHECK(hipMemcpyAsync(d_lens.p, lens.data(), (size_t)n * 4, hipMemcpyHostToDevice, st));
+        t_share.start();
+        hipLaunchKernelGGL(share_mass_kernel, dim3((unsigned)(((uint64_t)n + 3) / 4)), dim3(256), 0, st, d_woff.as<uint64_t>(), d_lens.as<uint32_t>(), (uint32_t)n,
+                           d_slots.as<uint32_t>(), d_vals.as<unsigned long long>(), d_out.as<mgta_contig_share>(), d_pws.as<uint32_t>(), d_pwm.as<uint16_t>());
+        MGTA_HIP_CHECK(hipGetLastError());
+        t_share.end();
+        MGTA_HIP_CHECK(hipMemcpyAsync(per_contig, d_out.p, (size_t)n * sizeof(mgta_contig_share), hipMemcpyDeviceToHost, st));
+        if (d_pws.p) MGTA_HIP_CHECK(hipMemcpyAsync(per_window_share, d_pws.p, total_win * 4, hipMemcpyDeviceToHost, st));
+        if (d_pwm.p) MGTA_HIP_CHECK(hipMemcpyAsync(per_window, d_pwm.p, total_win * 2, hipMemcpyDeviceToHost, st));
+        MGTA_HIP_CHECK(hipStreamSynchronize(st));
+        if (stats) {
+            uint64_t mass = 0, covered = 0;
+            for (int64_t i = 0; i < n; ++i) { mass += per_contig[i].mass; covered += per_contig[i].n_covered; }
+            stats->n_contigs = n; stats->n_windows = (int64_t)total_win; stats->n_walked = (int64_t)cnt[1]; stats->n_index_searches = (int64_t)cnt[2];
+            stats->n_batches = n_batches; stats->n_covered = (int64_t)covered; stats->n_distinct_edges = (int64_t)cnt[3]; stats->total_mult = cnt[4];
+            stats->total_mass = mass; stats->table_slots = n_slots; stats->table_bytes = n_slots * 16; stats->window_bytes = total_win * 4;
+            stats->ms_walk = ms_walk; stats->ms_count = ms_count; stats->ms_share = t_share.ms(); stats->ms_total = ms_walk + ms_count + stats->ms_share;
         }
         return MGTA_OK;
     });

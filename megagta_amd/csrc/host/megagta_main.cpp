@@ -817,22 +817,10 @@ static void read_fasta_records(const std::string &fasta, std::vector<std::string
     fclose(f);
 }
 
-// ---- coverage: per-contig k-mer coverage and abundance from the graph's own multiplicities (the reference's last post-processing step,
-// `kmer_coverage` in bin/post_proc.sh:113-118, recounts them from the reads).  The file formats are this project's own: INTEGRATION.md.
-static int main_coverage(int argc, char **argv) {
-    if (argc != 4) { fprintf(stderr, "Usage: megagta coverage <sdbg_prefix> <contigs.fasta> <out_prefix>\n"); return 1; }
-    RssLine rss;
-    const std::string prefix = argv[1], fasta = argv[2], out_prefix = argv[3];
-    std::vector<std::string> names;
-    std::string seqs;
-    std::vector<uint64_t> offsets;
-    read_fasta_records(fasta, names, seqs, offsets);
-    const int64_t n = (int64_t)names.size();
-    double t0 = now_s();
-    mgta_ctx *ctx = ctx_get();
-    // The graph with its counts.  A worker keeps the one the coverage of the gene before loaded (the same files: one load for all
-    // genes of a run).  The graph a worker's buildgraph hands over has no counts (1 byte per edge more is never implied) and the search
-    // that ran since has used it up, so the first request loads the files -- which are complete first -- with the switch on.
+// The graph of `prefix` with its counts, for `coverage` and `sharecov`.  A worker keeps the one the request before loaded (the same files:
+// one load for all genes of a run).  The graph a worker's buildgraph hands over has no counts (1 byte per edge more is never implied) and
+// the search that ran since has used it up, so the first request loads the files -- which are complete first -- with the switch on.
+static mgta_sdbg *counted_graph(mgta_ctx *ctx, const std::string &prefix, double t0) {
     if (writer_join() != 0) die("the graph files of %s are incomplete", prefix.c_str());
     const std::string key = file_key(prefix + ".sdbg_info");
     mgta_sdbg *g = nullptr;
@@ -848,6 +836,23 @@ static int main_coverage(int argc, char **argv) {
         if (g_sess.active) { g_sess.cov_graph = g; g_sess.cov_key = key; }
     }
     logf("Number of Edges: %lld; K value: %d (load with multiplicities %.3f s)", (long long)mgta_sdbg_size(g), mgta_sdbg_k(g), now_s() - t0);
+    return g;
+}
+
+// ---- coverage: per-contig k-mer coverage and abundance from the graph's own multiplicities (the reference's last post-processing step,
+// `kmer_coverage` in bin/post_proc.sh:113-118, recounts them from the reads).  The file formats are this project's own: INTEGRATION.md.
+static int main_coverage(int argc, char **argv) {
+    if (argc != 4) { fprintf(stderr, "Usage: megagta coverage <sdbg_prefix> <contigs.fasta> <out_prefix>\n"); return 1; }
+    RssLine rss;
+    const std::string prefix = argv[1], fasta = argv[2], out_prefix = argv[3];
+    std::vector<std::string> names;
+    std::string seqs;
+    std::vector<uint64_t> offsets;
+    read_fasta_records(fasta, names, seqs, offsets);
+    const int64_t n = (int64_t)names.size();
+    double t0 = now_s();
+    mgta_ctx *ctx = ctx_get();
+    mgta_sdbg *g = counted_graph(ctx, prefix, t0);
     std::vector<mgta_contig_cov> cov((size_t)n);
     std::vector<int64_t> abund(65536);
     mgta_coverage_stats st;
@@ -871,6 +876,50 @@ static int main_coverage(int argc, char **argv) {
     for (int m = 0; m < 65536; ++m)
         if (abund[(size_t)m]) fprintf(af, "%d\t%lld\n", m, (long long)abund[(size_t)m]);
     if (fclose(af) != 0) die("short write to %s_abundance.txt", out_prefix.c_str());
+    if (!g_sess.active) mgta_sdbg_free(g);
+    ctx_put(ctx);
+    return 0;
+}
+
+// ---- sharecov: the window-shared coverage of every record of a FASTA (mgta_contig_share_coverage): masses that add up over any set of
+// contigs, what `megagta.py --taxon-abund` sums per cluster and per reference.  The file format is this project's own: INTEGRATION.md 2n.
+// mass (Q16) is printed with four decimals by integers only, so that megagta_amd/taxonabund.py prints the same bytes at any size.
+static void print_q16(FILE *f, uint64_t mass) {
+    const unsigned __int128 q = ((unsigned __int128)mass * 10000u) >> 16;
+    fprintf(f, "%llu.%04llu", (unsigned long long)(q / 10000u), (unsigned long long)(q % 10000u));
+}
+
+static int main_sharecov(int argc, char **argv) {
+    if (argc != 4) { fprintf(stderr, "Usage: megagta sharecov <sdbg_prefix> <contigs.fasta> <out_prefix>\n"); return 1; }
+    RssLine rss;
+    const std::string prefix = argv[1], fasta = argv[2], out_prefix = argv[3];
+    std::vector<std::string> names;
+    std::string seqs;
+    std::vector<uint64_t> offsets;
+    read_fasta_records(fasta, names, seqs, offsets);
+    const int64_t n = (int64_t)names.size();
+    double t0 = now_s();
+    mgta_ctx *ctx = ctx_get();
+    mgta_sdbg *g = counted_graph(ctx, prefix, t0);
+    std::vector<mgta_contig_share> rec((size_t)n);
+    mgta_share_stats st;
+    t0 = now_s();
+    // all records in ONE call: the shares are counted over the file
+    if (mgta_contig_share_coverage(g, seqs.data(), offsets.data(), n, rec.data(), nullptr, nullptr, &st) != MGTA_OK)
+        die("mgta_contig_share_coverage: %s", mgta_last_error());
+    logf("shared coverage of %lld contigs: %lld windows, %lld covered, %lld distinct edges, %lld batch%s; walk %.1f ms, count %.1f ms, share %.1f ms, table %.1f MB, wall %.3f s",
+         (long long)n, (long long)st.n_windows, (long long)st.n_covered, (long long)st.n_distinct_edges, (long long)st.n_batches, st.n_batches == 1 ? "" : "es", st.ms_walk,
+         st.ms_count, st.ms_share, (double)st.table_bytes / 1e6, now_s() - t0);
+    FILE *sf = fopen((out_prefix + "_sharecov.txt").c_str(), "w");
+    if (!sf) die("cannot write %s_sharecov.txt", out_prefix.c_str());
+    fprintf(sf, "#contig\tlen\twindows\tcovered\tunique\tmax_share\tmass\n");
+    for (int64_t i = 0; i < n; ++i) {
+        const mgta_contig_share &c = rec[(size_t)i];
+        fprintf(sf, "%s\t%u\t%u\t%u\t%u\t%u\t", names[(size_t)i].c_str(), c.len, c.n_windows, c.n_covered, c.n_unique, c.max_share);
+        print_q16(sf, c.mass);
+        fputc('\n', sf);
+    }
+    if (fclose(sf) != 0) die("short write to %s_sharecov.txt", out_prefix.c_str());
     if (!g_sess.active) mgta_sdbg_free(g);
     ctx_put(ctx);
     return 0;
@@ -1495,7 +1544,7 @@ int main(int argc, char **argv) {
 static int dispatch(int argc, char **argv) {
     if (argc < 2) {
         fprintf(stderr, "Usage: %s <sub_program> [sub options]\n    sub-programs on the MI355X hot path:\n        buildgraph    build succinct de Bruijn graph\n"
-                        "        denovo        tips, bubbles, contigs of an intermediate k\n        search        HMM-guided search of gene contigs\n        findstart     find starting kmers of the search\n        coverage      per-contig k-mer coverage and abundance from the graph\n        matchreads    the reads that share a (k+1)-mer with a set of contigs\n        derep         the unique, non-contained records of a FASTA\n        align         protein records placed on the columns of a profile HMM\n        cluster       complete-linkage clusters of aligned protein records\n        nearest       the closest reference protein of every protein record\n        chimera       protein records that two references explain better than one\n        dumpversion   dump version\n", argv[0]);
+                        "        denovo        tips, bubbles, contigs of an intermediate k\n        search        HMM-guided search of gene contigs\n        findstart     find starting kmers of the search\n        coverage      per-contig k-mer coverage and abundance from the graph\n        sharecov      per-contig coverage shared among the windows of the file: masses that add up\n        matchreads    the reads that share a (k+1)-mer with a set of contigs\n        derep         the unique, non-contained records of a FASTA\n        align         protein records placed on the columns of a profile HMM\n        cluster       complete-linkage clusters of aligned protein records\n        nearest       the closest reference protein of every protein record\n        chimera       protein records that two references explain better than one\n        dumpversion   dump version\n", argv[0]);
         return 1;
     }
     std::string sub = argv[1];
@@ -1504,6 +1553,7 @@ static int dispatch(int argc, char **argv) {
     if (sub == "findstart") return main_findstart(argc - 1, argv + 1);
     if (sub == "denovo") return main_denovo(argc - 1, argv + 1);
     if (sub == "coverage") return main_coverage(argc - 1, argv + 1);
+    if (sub == "sharecov") return main_sharecov(argc - 1, argv + 1);
     if (sub == "matchreads") return main_matchreads(argc - 1, argv + 1);
     if (sub == "derep") return main_derep(argc - 1, argv + 1);
     if (sub == "align") return main_align(argc - 1, argv + 1);
@@ -1612,6 +1662,6 @@ static int dispatch(int argc, char **argv) {
         return 0;
     }
     if (sub == "dumpversion") { printf("%s\n", mgta_version()); return 0; }
-    fprintf(stderr, "sub-command '%s' is not built here (buildlib, buildgraph, denovo, findstart, search, coverage, matchreads, derep, align, cluster, nearest, chimera, filterbylen, translate are): run it with the reference's megagta binary\n", sub.c_str());
+    fprintf(stderr, "sub-command '%s' is not built here (buildlib, buildgraph, denovo, findstart, search, coverage, sharecov, matchreads, derep, align, cluster, nearest, chimera, filterbylen, translate are): run it with the reference's megagta binary\n", sub.c_str());
     return 1;
 }

@@ -65,7 +65,12 @@ USAGE = """Usage:
                      its two parents) and prot_..._nochim.fasta, nucl_..._nochim.fasta (the contigs that are not chimeric); scoring and gap
                      costs are the --nearest-* options; the rule is this project's own, not uchime's (GPU 0)
     --chimera-min-seg N       fewest residues on either side of a break [10: this driver's own default, from a CPU trial]
-    --chimera-min-gain N      what two parents must score above one for a contig to go [15: this driver's own default, from a CPU trial]"""
+    --chimera-min-gain N      what two parents must score above one for a contig to go [15: this driver's own default, from a CPU trial]
+    --taxon-abund    needs --align --cluster; after every other step: per gene contigs/<gene>/nucl_merged[_rmdup]_sharecov.txt (the k-mer
+                     coverage of every clustered contig with each edge's multiplicity split among the contig windows on it, so that it adds
+                     up), prot_merged[_rmdup]_otu_abund.txt (mass and ppm per cluster) and, with --nearest,
+                     prot_merged[_rmdup]_taxon_abund.txt (per reference protein and its lineage); --chimera's verdicts are used when that
+                     flag runs too (GPU 0)"""
 
 
 class Usage(Exception):
@@ -110,6 +115,7 @@ class Opt:
         self.chimera = False
         self.chimera_min_seg = 10
         self.chimera_min_gain = 15
+        self.taxon_abund = False
 
 
 opt = Opt()
@@ -119,7 +125,7 @@ LONG = ["help", "read=", "12=", "out-dir=", "memory=", "gpu-mem=", "min-contig-l
         "min-count=", "max-tip-len=", "no-mercy", "keep-tmp-files", "mem-flag=", "version", "verbose", "continue", "gene-list=",
         "prune-len=", "low-cov-penalty=", "bin=", "one-process-per-step", "gpus=", "coverage", "match-reads", "derep", "align", "cluster",
         "cluster-dist=", "cluster-min-overlap=", "nearest", "nearest-scoring=", "nearest-gap-open=", "nearest-gap-extend=",
-        "chimera", "chimera-min-seg=", "chimera-min-gain="]
+        "chimera", "chimera-min-seg=", "chimera-min-gain=", "taxon-abund"]
 
 
 def parse_opt(argv):
@@ -179,6 +185,7 @@ def parse_opt(argv):
         elif o == "--chimera": opt.chimera = True
         elif o == "--chimera-min-seg": opt.chimera_min_seg = int(v)
         elif o == "--chimera-min-gain": opt.chimera_min_gain = int(v)
+        elif o == "--taxon-abund": opt.taxon_abund = True
         else:
             raise Usage("Invalid option " + o)
     opt.temp_dir = opt.out_dir + "tmp/"
@@ -230,6 +237,8 @@ def detect_available_mem():
 def check_opt():
     if opt.cluster and not opt.align:
         raise Usage("--cluster needs --align: it clusters the rows that step writes")
+    if opt.taxon_abund and not (opt.align and opt.cluster):
+        raise Usage("--taxon-abund needs --align --cluster: it sums the coverage of the clusters those steps write")
     if not 0 <= opt.cluster_dist <= 1:
         raise Usage("--cluster-dist should be between [0, 1]")
     if opt.cluster_min_overlap < 1:
@@ -709,6 +718,35 @@ def chimera(k):
         write_cp()
 
 
+def taxon_abund(k):
+    """--taxon-abund: per gene the window-shared coverage of the clustered nucleotide contigs (`megagta sharecov` on the last k's graph,
+    loaded with its counts on GPU 0 exactly as for --coverage; one call per gene, so the shares are counted over the gene), then the join
+    with the tables of --cluster and, where they ran, --nearest and --chimera (megagta_amd/taxonabund.py, host only).  One checkpoint
+    per gene, after every other checkpoint, so `--continue` works under any combination."""
+    stem = "_merged_rmdup" if opt.derep else "_merged"
+    for gene in opt.gene_info:
+        d = opt.out_dir + "contigs/" + gene
+        if should_run():
+            run_step([opt.bin, "sharecov", graph_prefix(k), d + "/nucl" + stem + ".fasta", d + "/nucl" + stem],
+                     "Computing the shared k-mer coverage of the contigs of %s" % gene)
+            what = "Summing the abundance of the clusters of %s" % gene
+            logging.info("--- [%s] %s ---" % (datetime.now().strftime("%c"), what))
+            root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+            if root not in sys.path:
+                sys.path.insert(0, root)
+            from megagta_amd import taxonabund
+            rep = d + "/prot" + stem + "_rep_seqs"
+            try:
+                res = taxonabund.write_taxonabund(d + "/prot" + stem, d + "/nucl" + stem + "_sharecov.txt", d + "/prot" + stem + "_clust.txt",
+                                                  rep + "_nearest.txt" if opt.nearest else None, rep + "_chimera.txt" if opt.chimera else None,
+                                                  opt.gene_info[gene][2] if opt.nearest else None)
+            except (ValueError, OSError) as e:
+                logging.error(str(e))
+                fail_step("running \"%s\"" % what, 1)
+            logging.debug("%d clusters, total mass %s" % (sum(r["cluster"] is not None for r in res["otu"]), taxonabund.e4_text(res["total"])))
+        write_cp()
+
+
 def after_search(k):
     """the opt-in steps on the last k's graph, in a fixed order behind every checkpoint of a run without them"""
     if opt.coverage:
@@ -725,6 +763,8 @@ def after_search(k):
         nearest(k)
     if opt.chimera:
         chimera(k)
+    if opt.taxon_abund:
+        taxon_abund(k)
 
 
 def main(argv=None):
