@@ -156,6 +156,7 @@ typedef struct mgta_build_stats {
     int64_t n_lsd_tiles;             /* LDS tiles whose runs were too long to finish by comparison (LSD passes over every digit) */
     uint64_t bytes_peak;             /* device bytes allocated at the peak */
     double ms_stage1;                /* min_count >= 2: solid-edge counting + mercy edges, before (and not part of) ms_total */
+    int64_t n_fused_passes;          /* passes whose key writer placed the keys by the first global sort digit (no scatter launch for it) */
 } mgta_build_stats;
 
 /* a1: packed reads as `buildgraph` holds them — every read REVERSED (cx1_read2sdbg_s1.cpp:97,117),

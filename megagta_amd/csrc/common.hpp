@@ -84,9 +84,12 @@ struct Timer {                   // owns its two events
     }
 };
 
-// slots of mgta_ctx::pool, the graph build's grow-only device buffers; between builds others may borrow its key buffers S_KEYS_A / S_KEYS_B
+// slots of mgta_ctx::pool, the graph build's grow-only device buffers; between builds others may borrow its key buffers S_KEYS_A / S_KEYS_B.
+// S_FUSED_HIST (sdbg_build.hip, Build::count_pass): per-workgroup counts of the first sort digit of the ranges counted ahead -- gigabytes
+// at 10^8 reads, so unlike the other slots it is part of a pass's memory need, and Build::admit_pass lets it go where a pass only
+// fits without it
 enum Slot { S_BLOCK_COUNT, S_BLOCK_BASE, S_SCAN_TMP, S_SMALL, S_KEYS_A, S_KEYS_B, S_HIST, S_TILE_HEADS, S_TILE_BASE, S_CNT, S_BASE,
-            S_FIRST, S_OUT_REC, S_OUT_LARGE, S_OUT_TIPS, S_PLAN, S_BIG, S_LSD, S_MULTI_COUNT, S_POS2ID, S_SOLID, S_MERCY, S_EDGE_COUNT, S_SIDE, S_NUM };
+            S_FIRST, S_OUT_REC, S_OUT_LARGE, S_OUT_TIPS, S_PLAN, S_BIG, S_LSD, S_MULTI_COUNT, S_POS2ID, S_SOLID, S_MERCY, S_EDGE_COUNT, S_SIDE, S_FUSED_HIST, S_NUM };
 
 }  // namespace mgta
 

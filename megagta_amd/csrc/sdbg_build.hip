@@ -12,10 +12,13 @@
 //     1. items per workgroup: closed form when every bucket is wanted (2 (len - k) + 4 per read), else
 //        item_scan<count>: one wave per read, one lane per (k+1)-mer position: funnel-shift the edge out of the 2-bit read
 //        array, reverse-complement it in registers, count the <= 6 sort items of the position whose first 8 characters fall
-//        into the range (one scan counts every range that is still ahead)
+//        into the range (one scan counts every range that is still ahead -- and, for up to 8 ranges whose sort plan can be told from
+//        the attempt that was refused before, the digit of every item that the range's first global sort pass sorts on, per workgroup)
 //     2. prefix sum of the per-workgroup counts
 //     3. item_scan<write>   same scan, keys written (array-of-structs, W words) with wave-aggregated offsets, and next to every key
-//        the byte the first global sort pass sorts on (the SIDE array, W <= 7)
+//        the byte the first global sort pass sorts on (the SIDE array, W <= 7); or, where step 1 counted that pass's digits and the
+//        real plan is the one they were counted for, item_write_fused: the keys are ranked by the digit in LDS and leave as one run
+//        per digit value at the offsets the counts give, so that pass neither reads nor moves them again (MGTA_SORT_FUSED)
 //     4. sort: P <= 4 global LSD passes on the P leading key bytes (digit census per tile FROM THE SIDE BYTES, row scan, stable
 //        LDS-staged scatter with wave-level match ranking and coalesced run writes, which leaves the next pass's side bytes behind:
 //        the keys cross HBM once per pass for the scatter, not twice), then every segment of equal prefix is finished inside LDS:
@@ -122,8 +125,45 @@ struct ScanArgs {
     uint8_t *side;                         // write mode, optional: ((word 0 - side_bias) >> side_shift) & 255 of every key next to it (the
     int side_shift;                        // first global sort pass then counts these bytes instead of reading the keys back)
     uint32_t side_bias;
+    // fused first sort pass (item_scan_kernel<W, false, true> counts, item_write_fused_kernel places): digit of a key =
+    // ((word 0 - fz_bias) >> fz_shift) & 255, per range counted ahead in the count scan, entry 0 in the writer
+    uint64_t *fz_hist;                     // count scan: [range][digit value][workgroup]; writer: its range's slice after the row scan
+    const uint64_t *fz_totals;             // writer: keys of the pass per digit value
+    uint64_t fz_n;                         // writer: keys of the pass (no store goes past them)
+    uint32_t fz_bias[8];
+    uint32_t fz_shift[8];
 };
 constexpr int kMaxCountRanges = 64;
+constexpr int kMaxFusedRanges = 8;
+
+// tile of workgroup b of n when workgroup b runs on XCD b % 8: contiguous eighths of the tiles per XCD
+__device__ __forceinline__ uint32_t xcd_tile(uint32_t b, uint32_t n) {
+    if (n < 64) return b;
+    const uint32_t x = b & 7u, idx = b >> 3, q = n >> 3, r = n & 7u;
+    return x * q + (x < r ? x : r) + idx;
+}
+
+// LDS of the fused key writer: the keys of a batch as they are generated, their order by digit value, and per digit value the
+// row's place in the output.  The waves of a workgroup meet at a barrier every round and at six per batch, and only other
+// workgroups on the CU fill those gaps, so the stage is small: 26 KB per workgroup = six workgroups per CU = batches of 1536 keys at
+// W = 3.  Measured at 100 M reads, k = 44 (profiles/r07/build_fused/README.md; key generation of the three ranges per step): 52 KB 355 ms, 40 KB
+// 295 ms, 30 KB 265 ms, 26 KB 242 ms, 22 KB (seven workgroups, batches of 1152 keys: runs of 4-5 keys per digit value) 251 ms.
+constexpr int kFusedLdsKB = 26;
+template <int W> struct FusedCfg {
+    static constexpr int kWaveRound = 6 * 64;                                  // keys a round of one wave can yield at most
+    static constexpr int kFit = (kFusedLdsKB * 1024 - 5 * 1024) / (4 * W + 2) / 128 * 128;
+    static constexpr int kCap = kFit < kWaveRound ? kWaveRound : (kFit > 8192 ? 8192 : kFit);
+};
+template <int W> struct FusedShared {
+    Key<W> stage[FusedCfg<W>::kCap];
+    uint16_t perm[FusedCfg<W>::kCap];      // perm[i] = place in `stage` of the i-th key of the batch in digit order
+    uint32_t cnt[256];                     // keys of the batch per digit value (counted as they are staged), then the rank cursor
+    uint32_t pos[256];                     // first key of the digit value in the batch's digit order
+    uint64_t next[256];                    // place in the output of the row's next key of the digit value
+    uint32_t wave_tot[2][kScanBlock / 64]; // keys of the round per wave | "more rounds to come" << 31, double-buffered by round parity
+    uint32_t scr[kScanBlock / 64];
+    uint64_t s64[kScanBlock / 64 + 1];
+};
 
 // masks of the first n characters of a W-word string (keep_chars as W ANDs with wave-uniform operands)
 template <int W>
@@ -139,25 +179,50 @@ __device__ __forceinline__ void keep_masks(int n, uint32_t (&m)[W]) {
 // instruction takes four cycles of a 16-lane SIMD) and by load latency in count mode (117), so the write path keeps everything
 // wave-uniform out of the vector unit: character masks and the workgroup's slice of the output as scalars, no bounds checks on the read
 // words where the workgroup's reads end well inside the array, no staging array for the items of a position.
-template <int W, bool WRITE>
-__global__ __launch_bounds__(kScanBlock) void item_scan_kernel(ScanArgs a) {
+//
+// One body, three kernels.  CENSUS (count mode, <= 8 ranges ahead): every kept item also counts the digit its range's first global sort
+// pass will sort on, per workgroup (= row of that pass's offset table).  FUSED (write mode): the keys do not go out in scan order but
+// are ranked by that digit in LDS and leave as one run per digit value at the row's offsets (item_write_fused_kernel): the first
+// pass of the sort is done when the keys are written.  Both read groups of reads in xcd_tile order, so that the table entries of
+// neighbouring rows (one line per 16 rows of a digit value) are written and read through one L2.
+template <int W, bool WRITE, bool CENSUS, bool FUSED>
+__device__ __forceinline__ void item_scan_body(const ScanArgs &a) {
+    static_assert(!(CENSUS && WRITE) && !(FUSED && !WRITE), "the census belongs to the count scan, the placing to the writer");
+    static_assert(kScanBlock == 256, "fused writer: one thread per digit value");
     __shared__ uint32_t s_cursor;
     __shared__ uint32_t s_wave_cnt[kScanBlock / 64];
     __shared__ uint32_t s_range_cnt[kMaxCountRanges];
+    __shared__ uint32_t s_fz_hist[CENSUS ? kMaxFusedRanges * 256 : 1];
+    __shared__ uint32_t s_fz_bias[kMaxFusedRanges], s_fz_shift[kMaxFusedRanges];
+    __shared__ std::conditional_t<FUSED, FusedShared<W>, uint32_t> fs;   // (no LDS unless FUSED)
     const int k = a.k;
     const int lane = lane_id(), wv = wave_id();
     __shared__ uint64_t s_start[kReadsPerBlock + 1];                  // one coalesced load instead of two dependent ones per read
     const bool multi = !WRITE && a.multi_n > 0;
     const uint64_t multi_magic = a.multi_magic;                      // ceil(2^32 / multi_width): exact quotients for operands of at most 2^16
     const bool magic24 = multi_magic < (1u << 24);                   // (multi_width > 256: the product of a 16-bit and a 24-bit operand)
-    uint64_t r0 = (uint64_t)blockIdx.x * kReadsPerBlock;
+    const uint32_t blk = (CENSUS || FUSED) ? xcd_tile(blockIdx.x, gridDim.x) : blockIdx.x;   // group of 64 reads = row of the table
+    uint64_t r0 = (uint64_t)blk * kReadsPerBlock;
     uint64_t r1 = r0 + kReadsPerBlock < a.n_reads ? r0 + kReadsPerBlock : a.n_reads;
     if (threadIdx.x == 0) s_cursor = 0;
     if (!WRITE && threadIdx.x < kMaxCountRanges) s_range_cnt[threadIdx.x] = 0;
     if (threadIdx.x <= r1 - r0) s_start[threadIdx.x] = a.start[r0 + threadIdx.x];
+    if constexpr (CENSUS) {
+        for (int i = threadIdx.x; i < kMaxFusedRanges * 256; i += kScanBlock) s_fz_hist[i] = 0;
+        if (threadIdx.x < kMaxFusedRanges) { s_fz_bias[threadIdx.x] = a.fz_bias[threadIdx.x]; s_fz_shift[threadIdx.x] = a.fz_shift[threadIdx.x]; }
+    }
+    const uint32_t fz_bias = a.fz_bias[0], fz_shift = a.fz_shift[0];
+    uint32_t fz_fill = 0, fz_round = 0;                              // fused writer: keys staged, rounds done (workgroup-uniform)
+    if constexpr (FUSED) {
+        // place of the row's first key of every digit value: the keys of the smaller values + the keys of the value in earlier rows
+        const uint64_t t = a.fz_totals[threadIdx.x];
+        const uint64_t ex = block_excl_scan64<kScanBlock>(t, fs.s64, nullptr);
+        fs.next[threadIdx.x] = ex + a.fz_hist[(uint64_t)threadIdx.x * gridDim.x + blk];
+        fs.cnt[threadIdx.x] = 0;
+    }
     __syncthreads();
     Key<W> *out = reinterpret_cast<Key<W> *>(a.out);
-    uint64_t base = WRITE ? a.block_base[blockIdx.x] : 0;
+    uint64_t base = WRITE && !FUSED ? a.block_base[blockIdx.x] : 0;
     uint32_t my_count = 0;
     unsigned long long kmers = 0;
     const int pad_bits = 2 * (16 * W - (k + 1));   // 2..32
@@ -172,8 +237,44 @@ __global__ __launch_bounds__(kScanBlock) void item_scan_kernel(ScanArgs a) {
     // every word a lane of this workgroup can ask for lies inside the array (all but the workgroups of the array's last reads)
     const bool in_bounds = wave_uniform((s_start[r1 - r0] >> 4) + (uint64_t)(W + 1)) < a.n_words;
 
-    // one round of 64 positions: lane = position p of read r (s0 = its first character, npos = its positions); `active` lanes have one
-    auto positions = [&](bool active, uint64_t r, uint64_t s0, int p, int npos) {
+    // fused writer: the n staged keys leave in digit order, every digit value's keys as one run behind the row's earlier ones.  All
+    // threads call (six barriers); the stage is free again on return.
+    auto fz_digit = [&](uint32_t w0) { return ((w0 - fz_bias) >> fz_shift) & 255u; };
+    auto flush = [&](uint32_t n) {
+        if constexpr (FUSED) {
+            const uint32_t tid = threadIdx.x;
+            __syncthreads();                                           // the staged keys and their counts are in
+            const uint32_t c = fs.cnt[tid], inc = wave_incl_scan(c);
+            if (lane == 63) fs.scr[wv] = inc;
+            __syncthreads();
+            uint32_t ex = inc - c;
+            for (int w = 0; w < wv; ++w) ex += fs.scr[w];
+            fs.pos[tid] = ex;
+            fs.cnt[tid] = 0;
+            __syncthreads();
+            for (uint32_t j = tid; j < n; j += kScanBlock) {           // (any order inside a digit value: nothing is ordered before the first pass)
+                const uint32_t d = fz_digit(fs.stage[j].w[0]);
+                fs.perm[fs.pos[d] + atomicAdd(&fs.cnt[d], 1u)] = (uint16_t)j;
+            }
+            __syncthreads();
+            for (uint32_t i = tid; i < n; i += kScanBlock) {           // consecutive threads, consecutive places inside a run
+                const Key<W> key = fs.stage[fs.perm[i]];
+                const uint32_t d = fz_digit(key.w[0]);
+                const uint64_t to = fs.next[d] + (i - fs.pos[d]);
+                if (to < a.fz_n) {
+                    out[to] = key;
+                    if (a.side) a.side[to] = (uint8_t)((key.w[0] - a.side_bias) >> a.side_shift);
+                }
+            }
+            __syncthreads();
+            fs.next[tid] += c;
+            fs.cnt[tid] = 0;
+            __syncthreads();
+        }
+    };
+    // one round of 64 positions: lane = position p of read r (s0 = its first character, npos = its positions); `active` lanes have one.
+    // FUSED: every wave of the workgroup calls once per round, `more` = the wave has further rounds; returns whether any wave has
+    auto positions = [&](bool active, uint64_t r, uint64_t s0, int p, int npos, bool more = false) {
         bool run_first = p == 0, run_last = p == npos - 1;
         if (active && a.is_solid && r < a.n_short) {               // solid runs inside the read (s2.cpp:276,280,288)
             auto sol = [&](int pp) {
@@ -216,7 +317,7 @@ __global__ __launch_bounds__(kScanBlock) void item_scan_kernel(ScanArgs a) {
             }
             // the bucket (first 8 characters of the key, s2.cpp:832) is known before the key is built: most keys of a
             // narrow bucket range (memory-bound passes, multi-GPU shares) are dropped after three instructions
-            auto push = [&](int t, const uint32_t (&src)[W], int from) {
+            auto push = [&](int t, const uint32_t (&src)[W], int from, uint32_t keep0) {
                 const uint32_t b = ((src[0] << (2 * from)) >> 16);   // characters [from, from + 8), from <= 2
                 if (b < a.b_lo || b >= a.b_hi) return;
                 if (WRITE) mask |= 1u << t;
@@ -227,18 +328,23 @@ __global__ __launch_bounds__(kScanBlock) void item_scan_kernel(ScanArgs a) {
                     else range = (uint32_t)(((uint64_t)x * multi_magic) >> 32);
                     if (few) fields += 1u << (4 * range);
                     else atomicAdd(&s_range_cnt[range], 1u);
+                    if constexpr (CENSUS) {                         // key word 0 (W >= 2: no flags in it) without building the key
+                        const uint32_t w0 = (from ? ((src[0] << (2 * from)) | (src[W > 1 ? 1 : 0] >> (32 - 2 * from))) : src[0]) & keep0;
+                        if (range < (uint32_t)kMaxFusedRanges)
+                            atomicAdd(&s_fz_hist[range * 256u + (((w0 - s_fz_bias[range]) >> s_fz_shift[range]) & 255u)], 1u);
+                    }
                 }
                 ++cnt;
             };
             if (run_first) {                                       // left $  (s2.cpp:531-540)
-                push(0, e, 0);
-                if (!pal) push(1, rc, 2);
+                push(0, e, 0, m_k[0]);
+                if (!pal) push(1, rc, 2, m_k1[0]);
             }
-            push(2, e, 1);                                         // solid   (s2.cpp:543-550)
-            if (!pal) push(3, rc, 1);
+            push(2, e, 1, m_k[0]);                                 // solid   (s2.cpp:543-550)
+            if (!pal) push(3, rc, 1, m_k[0]);
             if (run_last) {                                        // right $ (s2.cpp:553-562)
-                push(4, e, 2);
-                if (!pal) push(5, rc, 0);
+                push(4, e, 2, m_k1[0]);
+                if (!pal) push(5, rc, 0, m_k[0]);
             }
         }
         if (!WRITE) {
@@ -251,13 +357,40 @@ __global__ __launch_bounds__(kScanBlock) void item_scan_kernel(ScanArgs a) {
         } else {
             const uint32_t inc = wave_incl_scan((uint32_t)cnt);
             const uint32_t tot = __shfl(inc, 63, 64);
+            uint32_t fz_before = 0, fz_tot[kScanBlock / 64] = {};
+            bool any_more = false;
+            if constexpr (FUSED) {
+                // the keys every wave brings this round, and whether any wave has rounds left
+                const uint32_t par = fz_round & 1u;
+                ++fz_round;
+                if (lane == 0) fs.wave_tot[par][wv] = tot | (more ? 0x80000000u : 0u);
+                __syncthreads();
+                for (int w = 0; w < kScanBlock / 64; ++w) fz_tot[w] = wave_uniform(fs.wave_tot[par][w]);
+            }
+            // FUSED: the waves take their places in the stage in turn; a wave whose keys do not fit behind the ones before flushes first
+            // (every wave decides the same from the same four totals, so all reach that flush, each between the same two waves' turns):
+            // the turns up to this wave's own before its keys are staged, the others after
+            auto take_turns = [&](int from, int to) {
+                if constexpr (FUSED) {
+#pragma unroll
+                    for (int turn = 0; turn < kScanBlock / 64; ++turn) {   // (constant bounds: fz_tot stays in registers)
+                        if (turn < from || turn >= to) continue;
+                        const uint32_t tw = fz_tot[turn] & 0x7FFFFFFFu;
+                        any_more = any_more || (fz_tot[turn] >> 31);
+                        if (fz_fill + tw > (uint32_t)FusedCfg<W>::kCap) { flush(fz_fill); fz_fill = 0; }
+                        fz_before = fz_fill;
+                        fz_fill += tw;
+                    }
+                }
+            };
+            take_turns(0, wv + 1);
             if (tot) {
                 uint32_t wbase = 0;
-                if (lane == 0) wbase = atomicAdd(&s_cursor, tot);
+                if (!FUSED && lane == 0) wbase = atomicAdd(&s_cursor, tot);
                 const uint64_t first = base + (uint64_t)wave_uniform(wbase);   // the wave's slots [first, first + tot): a scalar
                 char *const wave_out = reinterpret_cast<char *>(out + first);
-                uint8_t *const wave_side = a.side ? a.side + first : nullptr;
-                uint32_t slot = inc - (uint32_t)cnt;                    // < 6 * 64
+                uint8_t *const wave_side = !FUSED && a.side ? a.side + first : nullptr;
+                uint32_t slot = inc - (uint32_t)cnt + fz_before;        // < 6 * 64 (FUSED: place in the stage)
                 // every wanted item straight to its slot (no staging array: a lane-varying index into one costs a waterfall loop per store).
                 // key = characters [from, from + n) of src, flags in the low 4 bits: (n == k) << 3 | prev   [cx1_read2sdbg_s2.cpp:613-671]
                 auto put = [&](int t, const uint32_t (&src)[W], int from, const uint32_t (&keep)[W], uint32_t flags) {
@@ -269,8 +402,17 @@ __global__ __launch_bounds__(kScanBlock) void item_scan_kernel(ScanArgs a) {
                         key.w[j] = (from ? ((src[j] << (2 * from)) | (nx >> (32 - 2 * from))) : src[j]) & keep[j];
                     }
                     key.w[W - 1] |= flags;
-                    *reinterpret_cast<Key<W> *>(wave_out + slot * (uint32_t)sizeof(Key<W>)) = key;
-                    if (wave_side) wave_side[slot] = (uint8_t)((key.w[0] - a.side_bias) >> a.side_shift);
+                    if constexpr (FUSED) {
+                        // (a wave's keys of a round always fit an empty stage, kCap >= kWaveRound: the test only keeps a store
+                        // inside the array should that ever be broken; MGTA_SORT_FUSED=2 would then report the missing keys)
+                        if (slot < (uint32_t)FusedCfg<W>::kCap) {
+                            fs.stage[slot] = key;
+                            atomicAdd(&fs.cnt[fz_digit(key.w[0])], 1u);
+                        }
+                    } else {
+                        *reinterpret_cast<Key<W> *>(wave_out + slot * (uint32_t)sizeof(Key<W>)) = key;
+                        if (wave_side) wave_side[slot] = (uint8_t)((key.w[0] - a.side_bias) >> a.side_shift);
+                    }
                     ++slot;
                 };
                 const uint32_t e0 = e[0] >> 30, e1 = (e[0] >> 28) & 3u, r0c = rc[0] >> 30, r1c = (rc[0] >> 28) & 3u;
@@ -281,7 +423,13 @@ __global__ __launch_bounds__(kScanBlock) void item_scan_kernel(ScanArgs a) {
                 put(4, e, 2, m_k1, e1);
                 put(5, rc, 0, m_k, 8u | (uint32_t)kDollar);
             }
+            take_turns(wv + 1, kScanBlock / 64);
+            if constexpr (FUSED) {
+                if (!any_more) flush(fz_fill);                         // the last round of the workgroup
+                return any_more;
+            }
         }
+        return false;
     };
     // The reads of a wave all of one length (the common case) and no solid bits: their positions are numbered through, 64 per round --
     // reads of 150 bp at k = 44 have 106 positions: 26.5 rounds for the wave's 16 reads instead of 32 (the second round of a read of its
@@ -294,7 +442,51 @@ __global__ __launch_bounds__(kScanBlock) void item_scan_kernel(ScanArgs a) {
     const bool uniform = !a.is_solid && n_mine > 0 && len0 >= (uint32_t)(k + 1) && len0 - (uint32_t)k <= 4096u &&
                          __ballot((uint32_t)lane < n_mine && my_len != len0) == 0;
     static_assert(kReadsPerWave <= 64, "one lane per read of the wave");
-    if (uniform) {
+    if constexpr (FUSED) {
+        // the same rounds as below, but in step: every wave goes through a round's barrier until the last wave has had its last round
+        // (a wave that is through, or has no read at all, brings no positions)
+        uint32_t v = 0, total = 0, npos_u = 1, magic = 0;                     // numbered-through route
+        uint64_t rr = r0 + wv;                                                // read-at-a-time route: the read and the round inside it
+        int c0 = 0;
+        auto skip_short = [&]() {                                             // s2.cpp:262-264
+            while (rr < r1 && (int)(s_start[rr - r0 + 1] - s_start[rr - r0]) < k + 1) rr += kWaves;
+        };
+        if (uniform) {
+            npos_u = len0 - (uint32_t)k;
+            total = npos_u * n_mine;
+            magic = (uint32_t)(((1ull << 32) + npos_u - 1) / npos_u);
+        } else
+            skip_short();
+        struct Round { bool have, active; uint64_t r, s0; int p, npos; };
+        auto advance = [&]() {                                                // the wave's next round, if it has one
+            Round d{false, false, r0, 0, 0, 1};
+            if (uniform) {
+                if (v < total) {
+                    const uint32_t idx = v + (uint32_t)lane;
+                    d.have = true;
+                    d.active = idx < total;
+                    const uint32_t i = npos_u == 1 ? idx : __umulhi(idx, magic);
+                    const uint32_t slot = d.active ? wv + kWaves * i : wv;
+                    d.p = (int)(idx - i * npos_u); d.npos = (int)npos_u;
+                    d.r = r0 + slot; d.s0 = s_start[slot];
+                    v += 64;
+                }
+            } else if (rr < r1) {
+                d.have = true;
+                d.r = rr; d.s0 = s_start[rr - r0];
+                d.npos = (int)(s_start[rr - r0 + 1] - d.s0) - k;
+                d.p = c0 + lane;
+                d.active = d.p < d.npos;
+                c0 += 64;
+                if (c0 >= d.npos) { c0 = 0; rr += kWaves; skip_short(); }
+            }
+            return d;
+        };
+        for (;;) {
+            const Round cur = advance();
+            if (!positions(cur.active, cur.r, cur.s0, cur.p, cur.npos, uniform ? v < total : rr < r1)) break;
+        }
+    } else if (uniform) {
         const uint32_t npos = len0 - (uint32_t)k, total = npos * n_mine;     // <= 4096 * 16
         const uint32_t magic = (uint32_t)(((1ull << 32) + npos - 1) / npos);  // idx / npos for idx < 2^16 (npos = 1: magic wraps, handled)
         if (lane == 0) kmers += (unsigned long long)total;
@@ -333,8 +525,44 @@ __global__ __launch_bounds__(kScanBlock) void item_scan_kernel(ScanArgs a) {
             for (int w = 0; w < kScanBlock / 64; ++w) t += s_wave_cnt[w];
             a.block_count[blockIdx.x] = t;
         }
-        if (multi && threadIdx.x < a.multi_n) a.block_count[(uint64_t)threadIdx.x * gridDim.x + blockIdx.x] = s_range_cnt[threadIdx.x];
+        if (multi && threadIdx.x < a.multi_n) a.block_count[(uint64_t)threadIdx.x * gridDim.x + blk] = s_range_cnt[threadIdx.x];
         if (lane == 0 && kmers && a.n_kmers) atomicAdd(a.n_kmers, kmers);
+        if constexpr (CENSUS) {                                        // the workgroup's row of every range's table
+            const uint32_t n_rows = (a.multi_n < (uint32_t)kMaxFusedRanges ? a.multi_n : (uint32_t)kMaxFusedRanges) * 256u;
+            for (uint32_t i = threadIdx.x; i < n_rows; i += kScanBlock) a.fz_hist[(uint64_t)i * gridDim.x + blk] = s_fz_hist[i];
+        }
+    }
+}
+
+template <int W, bool WRITE, bool CENSUS = false>
+__global__ __launch_bounds__(kScanBlock) void item_scan_kernel(ScanArgs a) {
+    item_scan_body<W, WRITE, CENSUS, false>(a);
+}
+
+// The key writer of a pass whose first global sort pass was counted ahead by the count scan (item_scan_kernel<W, false, true>): the
+// same positions and keys as item_scan_kernel<W, true>, but every key goes where that sort pass would have moved it, so the pass
+// (a census and a scatter over every key) does not run.  The row of a workgroup in the table is its group of 64 reads.
+template <int W>
+__global__ __launch_bounds__(kScanBlock) void item_write_fused_kernel(ScanArgs a) {
+    item_scan_body<W, true, false, true>(a);
+}
+
+// MGTA_SORT_FUSED=2: every key of the fused writer's output lies in the slice of its digit value (bad[0] counts those that do not),
+// and the slices add up to the keys of the pass (bad[1])
+template <int W>
+__global__ __launch_bounds__(kScanBlock) void fused_check_kernel(const Key<W> *keys, uint64_t n, const uint64_t *totals, uint32_t bias, uint32_t shift,
+                                                                 uint32_t *bad) {
+    __shared__ uint64_t s_first[257];
+    __shared__ uint64_t s64[kScanBlock / 64 + 1];
+    const uint64_t t = totals[threadIdx.x];
+    const uint64_t ex = block_excl_scan64<kScanBlock>(t, s64, nullptr);
+    s_first[threadIdx.x] = ex;
+    if (threadIdx.x == kScanBlock - 1) s_first[256] = ex + t;
+    __syncthreads();
+    if (blockIdx.x == 0 && threadIdx.x == 0 && s_first[256] != n) atomicAdd(&bad[1], 1u);
+    for (uint64_t i = (uint64_t)blockIdx.x * kScanBlock + threadIdx.x; i < n; i += (uint64_t)gridDim.x * kScanBlock) {
+        const uint32_t d = ((keys[i].w[0] - bias) >> shift) & 255u;
+        if (i < s_first[d] || i >= s_first[d + 1]) atomicAdd(&bad[0], 1u);
     }
 }
 
@@ -500,13 +728,6 @@ __device__ __forceinline__ void get_digits(const Key<W> (&key)[N], Digit d, uint
     const uint32_t mask = (1u << d.bits) - 1u;
 #pragma unroll
     for (int i = 0; i < N; ++i) dg[i] = __builtin_amdgcn_alignbit(hi[i], lo[i], (uint32_t)off) & mask;
-}
-
-// tile of workgroup b of n when workgroup b runs on XCD b % 8: contiguous eighths of the tiles per XCD
-__device__ __forceinline__ uint32_t xcd_tile(uint32_t b, uint32_t n) {
-    if (n < 64) return b;
-    const uint32_t x = b & 7u, idx = b >> 3, q = n >> 3, r = n & 7u;
-    return x * q + (x < r ? x : r) + idx;
 }
 
 // census: hist[digit * n_tiles + tile]
@@ -1746,11 +1967,13 @@ static uint64_t pool_bytes(const mgta_ctx *ctx) {
 // MGTA_SORT_BIAS: 0 never, 1 (default) when it saves a pass and leaves short segments, 2 whenever valid (tests) -- see choose_top_plan.
 // MGTA_SORT_SIDE: side digits (see SortJob::uses_side) 0 off, 1 (default) on, 2 on and every side census checked against the census
 // of the keys (tests).  Read once per build and never cached: tests and scripts flip them between builds.
+// MGTA_SORT_FUSED: the key writer of a range pass does the first global sort pass (see Build::count_pass) 0 never, 1 (default) where
+// the plan of the pass was known when its items were counted, 2 the same and the writer's output checked on the device (tests).
 struct SortModes {
-    int bias = 1, side = 1;
+    int bias = 1, side = 1, fused = 1;
     static SortModes from_env() {
-        const char *bias = getenv("MGTA_SORT_BIAS"), *side = getenv("MGTA_SORT_SIDE");
-        return SortModes{bias ? atoi(bias) : 1, side ? atoi(side) : 1};
+        const char *bias = getenv("MGTA_SORT_BIAS"), *side = getenv("MGTA_SORT_SIDE"), *fused = getenv("MGTA_SORT_FUSED");
+        return SortModes{bias ? atoi(bias) : 1, side ? atoi(side) : 1, fused ? atoi(fused) : 1};
     }
 };
 
@@ -1808,7 +2031,8 @@ struct SortJob {
     uint32_t mask_last2 = ~0u, mask_last = ~0u;   // significant bits of the last two key words (LocalPlan)
     int side_mode = 1;                        // SortModes::side
     bool census_done = false;                 // the first global pass's census (tiles of kBlockTile keys of a) is already in S_HIST
-    bool side_done = false;                   // S_SIDE already holds the first global pass's digit of every key
+    bool side_done = false;                   // S_SIDE already holds the digit of every key that the first global pass to run sorts on
+    bool first_pass_done = false;             // the key writer placed the keys by the first global pass's digit: the passes start at the second
     // side digits: the scatter of a pass leaves the NEXT pass's digit of every key in a byte array (S_SIDE), and that pass's census
     // reads the bytes instead of the keys
     bool uses_side() const { return side_mode > 0 && top.P >= 2 && kSideFits<WT>; }
@@ -1829,7 +2053,7 @@ static Key<WT> *global_passes(mgta_ctx *ctx, const SortJob<WT> &job, SortLog *lo
     bool side_valid = job.side_done && d_side;                          // d_side holds the digits of the pass about to run
     const dim3 grid((unsigned)tiles), block(kSortThreads);
     Key<WT> *src = job.a, *dst = job.b;
-    for (int i = job.top.P - 1; i >= 0; --i) {
+    for (int i = job.top.P - 1 - (job.first_pass_done ? 1 : 0); i >= 0; --i) {
         const bool first = i == job.top.P - 1;
         const Digit dg = job.top.pass_digit(WT, i), dn = i > 0 ? job.top.pass_digit(WT, i - 1) : Digit{0, 0, 0};
         if (!(first && job.census_done)) {
@@ -2129,6 +2353,17 @@ struct Build {                                 // a build of keys of W words: wh
     uint64_t *d_block_base = nullptr, *d_total = nullptr, *d_kmers = nullptr, *d_tot3 = nullptr, *d_sentinel = nullptr;
     uint32_t multi_n = 0, multi_width = 0, multi_lo = 0;   // ranges counted ahead by one scan (rows of d_multi_count)
     uint32_t *d_multi_count = nullptr;
+    // Fused first sort pass.  The digit a range's first global pass sorts on depends on the plan of its sort, and that on its item
+    // count -- which the count scan is about to produce.  A scan of several ranges only runs after a wider attempt was refused, so
+    // every range's count is estimated from that attempt's (its share of the buckets), the plan chosen from the estimate, and the
+    // scan counts that plan's first digit per workgroup next to the items (fz_table: [range][digit value][workgroup]).  A pass
+    // whose real plan equals the estimated one takes the fused writer; any other the plain route, its histogram unused.
+    struct FusedAhead { bool on = false; int P = 0, skip = 0; uint32_t bias = 0; };
+    FusedAhead fz_plan[kMaxFusedRanges];
+    uint64_t *fz_table = nullptr;              // nullptr: the ranges ahead were counted without the digits
+    uint64_t wide_items = 0;                   // items and buckets of the last attempt admit_pass refused
+    uint32_t wide_nb = 0;
+    bool fz_check_failed = false;              // MGTA_SORT_FUSED=2: the fused writer's output failed its check
     mgta_build_stats S{};
     Timer t_all{stream}, t_ph{stream};
     SortLog log{&S, {}};
@@ -2148,13 +2383,14 @@ struct Build {                                 // a build of keys of W words: wh
             p.width = (bucket_end - bucket_begin + n_pass - 1) / n_pass;
             p.b_lo = b_lo; p.b_hi = std::min<uint32_t>(bucket_end, b_lo + p.width);
             count_pass(p);
-            if (const int more = admit_pass(p, n_pass)) { n_pass = more; continue; }
+            if (const int more = admit_pass(p, n_pass)) { n_pass = more; wide_items = p.n_items; wide_nb = p.nb(); continue; }
             S.n_items += (int64_t)p.n_items;
             S.n_passes++;
             if (p.n_items > 0) {
                 Key<W> *a = pool_get<Key<W>>(ctx, S_KEYS_A, p.key_b), *b = pool_get<Key<W>>(ctx, S_KEYS_B, p.key_b);
                 const SortJob<W> job = plan_sort(p, a, b);
                 write_keys(p, job);
+                if (fz_check_failed) { set_error("internal: the fused key writer left keys outside the slice of their first sort digit"); return MGTA_EINTERNAL; }
                 Key<W> *sorted = sort_keys(job);
                 if (!sorted) return MGTA_EUNSUPPORTED;
                 if ((rc = drop_sentinels(p)) != MGTA_OK || (rc = emit(p, sorted, sorted == a ? b : a)) != MGTA_OK) return rc;
@@ -2244,7 +2480,13 @@ struct Build {                                 // a build of keys of W words: wh
                 d_multi_count = pool_get<uint32_t>(ctx, S_MULTI_COUNT, (uint64_t)ranges_left * n_blocks * 4);
                 ScanArgs sm = sa;
                 sm.block_count = d_multi_count; sm.b_hi = bucket_end; sm.multi_width = width; sm.multi_n = ranges_left; sm.multi_magic = ((1ull << 32) + width - 1) / width;
-                hipLaunchKernelGGL((item_scan_kernel<W, false>), dim3((unsigned)n_blocks), dim3(kScanBlock), 0, stream, sm);
+                fz_table = nullptr;
+                if (plan_ahead(sm, b_lo, width, ranges_left)) {
+                    fz_table = sm.fz_hist = pool_get<uint64_t>(ctx, S_FUSED_HIST, fused_table_bytes(ranges_left));
+                    if constexpr (W >= 2)      // (plan_ahead refuses keys of one word: no such kernels are built)
+                        hipLaunchKernelGGL((item_scan_kernel<W, false, true>), dim3((unsigned)n_blocks), dim3(kScanBlock), 0, stream, sm);
+                } else
+                    hipLaunchKernelGGL((item_scan_kernel<W, false>), dim3((unsigned)n_blocks), dim3(kScanBlock), 0, stream, sm);
                 multi_n = ranges_left; multi_width = width; multi_lo = b_lo;
             }
             if (multi_n) counts = d_multi_count + (uint64_t)((b_lo - multi_lo) / width) * n_blocks;
@@ -2260,14 +2502,43 @@ struct Build {                                 // a build of keys of W words: wh
         }
     }
 
-    // Does the pass fit?  Two key buffers (the second doubles as emit scratch) + census + outputs (estimate).  0: it does, else the
-    // number of passes to split the buckets into instead (narrower bucket ranges: CX1's lv1 loop, cx1.h:494)
-    int admit_pass(Pass &p, int n_pass) {
-        p.n_tiles = (p.n_items + kBlockTile - 1) / kBlockTile;
+    int max_top() const { return (2 * k + 4 + 7) / 8 > 1 ? std::min(4, (32 * W - 8) / 8) : 0; }
+    uint64_t fused_table_bytes(uint32_t ranges) const { return (uint64_t)ranges * 256 * std::max<uint64_t>(1, n_blocks) * 8; }
+
+    // The plan of every range the count scan is about to count (see fz_plan), into the scan's arguments.  False: count without the
+    // digits -- no estimate (first attempt of the build), too many ranges, keys of one word (flags share word 0 with the digit), no
+    // range with a global pass, or a table that would not fit the budget next to a pass of the estimated size.
+    bool plan_ahead(ScanArgs &sm, uint32_t b_lo, uint32_t width, uint32_t ranges) {
+        for (FusedAhead &f : fz_plan) f = FusedAhead{};
+        if (modes.fused <= 0 || W < 2 || !wide_nb || ranges > (uint32_t)kMaxFusedRanges) return false;
+        bool any = false;
+        uint64_t est_max = 0;
+        for (uint32_t g = 0; g < ranges; ++g) {
+            const uint32_t lo = b_lo + g * width, hi = std::min<uint32_t>(bucket_end, lo + width);
+            const uint64_t est = (uint64_t)((double)wide_items * (double)(hi - lo) / (double)wide_nb);
+            const TopPlan tp = choose_top_plan(ctx, est, max_top(), (double)(hi - lo) / MGTA_NUM_BUCKETS, lo, hi, modes.bias);
+            est_max = std::max(est_max, est);
+            sm.fz_bias[g] = 0; sm.fz_shift[g] = 0;
+            if (tp.P < 1 || tp.T() > 32) continue;
+            fz_plan[g] = FusedAhead{true, tp.P, tp.skip, tp.bias};
+            sm.fz_bias[g] = tp.bias; sm.fz_shift[g] = (uint32_t)(32 - tp.T());
+            any = true;
+        }
+        if (!any) return false;
+        uint64_t key_b = 0;
+        const uint64_t need = pass_need(est_max, &key_b) + fused_table_bytes(ranges);
+        return need + need / 8 <= avail_bytes();
+    }
+
+    // device bytes of a pass of n_items (two key buffers, the second doubles as emit scratch, + census + outputs (estimate))
+    uint64_t pass_need(uint64_t n_items, uint64_t *key_b) const {
+        const uint64_t n_tiles = (n_items + kBlockTile - 1) / kBlockTile;
         // either key buffer may end up as the emitter's scratch (11 bytes per key: run start u64, record u16, info u8), whichever
         // the last sort pass leaves idle: both hold >= 12 bytes per key
-        p.key_b = std::max<uint64_t>(p.n_items * sizeof(Key<W>), p.n_items * 12) + 4096;
-        const uint64_t need = 2 * p.key_b + p.n_tiles * 256 * 8 + p.n_items * 2 + p.n_items /* side digits */ + (8u << 20);
+        *key_b = std::max<uint64_t>(n_items * sizeof(Key<W>), n_items * 12) + 4096;
+        return 2 * *key_b + n_tiles * 256 * 8 + n_items * 2 + n_items /* side digits */ + (8u << 20);
+    }
+    uint64_t avail_bytes() const {
         uint64_t other = ctx->live_bytes - pool_bytes(ctx);
         if (acc) {     // room for the stream the passes leave behind: ~0.6 edges of 2 bytes per (k+1)-mer, tips, slack
             const double range_frac = (double)(bucket_end - bucket_begin) / (double)MGTA_NUM_BUCKETS;
@@ -2275,7 +2546,21 @@ struct Build {                                 // a build of keys of W words: wh
             const uint64_t have = ctx->acc_rec.bytes + ctx->acc_tips.bytes;
             other += est > have ? est - have : 0;
         }
-        const uint64_t avail = budget - std::min<uint64_t>(budget, other);
+        return budget - std::min<uint64_t>(budget, other);
+    }
+
+    // Does the pass fit?  0: it does, else the number of passes to split the buckets into instead (narrower bucket ranges: CX1's
+    // lv1 loop, cx1.h:494).  The table of a fused first pass counts as long as the pool holds it; where the pass only fits without,
+    // the table goes and the ranges it covered take the plain route.
+    int admit_pass(Pass &p, int n_pass) {
+        p.n_tiles = (p.n_items + kBlockTile - 1) / kBlockTile;
+        uint64_t need = pass_need(p.n_items, &p.key_b);
+        const uint64_t avail = avail_bytes();
+        if ((int)ctx->pool.size() > S_FUSED_HIST && ctx->pool[S_FUSED_HIST].bytes) {
+            const uint64_t with = need + ctx->pool[S_FUSED_HIST].bytes;
+            if (with + with / 8 <= avail) need = with;
+            else if (need + need / 8 <= avail) { ctx->pool[S_FUSED_HIST].release(); fz_table = nullptr; }   // (else refused either way)
+        }
         if (need + need / 8 <= avail || p.width <= 1) return 0;
         const double ratio = (double)(need + need / 8) / (double)std::max<uint64_t>(avail, 1) * 1.03;
         return std::max(n_pass + 1, (int)std::ceil((double)n_pass * ratio));
@@ -2283,14 +2568,22 @@ struct Build {                                 // a build of keys of W words: wh
 
     // the one plan of the pass's sort, for the key writer and the sort
     SortJob<W> plan_sort(const Pass &p, Key<W> *a, Key<W> *b) const {
-        const int max_top = (2 * k + 4 + 7) / 8 > 1 ? std::min(4, (32 * W - 8) / 8) : 0;
-        SortJob<W> job{a, b, p.n_items, choose_top_plan(ctx, p.n_items, max_top, (double)p.nb() / MGTA_NUM_BUCKETS, p.b_lo, p.b_hi, modes.bias)};
+        SortJob<W> job{a, b, p.n_items, choose_top_plan(ctx, p.n_items, max_top(), (double)p.nb() / MGTA_NUM_BUCKETS, p.b_lo, p.b_hi, modes.bias)};
         job.low = low_digit_plan(k, W, job.top.T());
         job.side_mode = modes.side;
         // closed form + at least one global sort pass: the key writer works tile by tile of that pass and leaves its census behind;
         // the general writer leaves that pass's digit of every key in the side array instead
         job.census_done = p.closed_form && job.top.P >= 1 && p.n_tiles <= 0x7FFFFFFFull;
         job.side_done = !p.closed_form && job.uses_side();
+        // the count scan counted this range's first global pass ahead, and for the plan the real count gives: the writer does that pass
+        // (and leaves the side digits of the next one)
+        if (!p.closed_form && fz_table && multi_n && p.width == multi_width && p.b_lo >= multi_lo && (p.b_lo - multi_lo) % p.width == 0) {
+            const uint32_t g = (p.b_lo - multi_lo) / p.width;
+            if (g < multi_n && g < (uint32_t)kMaxFusedRanges) {
+                const FusedAhead &f = fz_plan[g];
+                job.first_pass_done = f.on && job.top.P >= 1 && f.P == job.top.P && f.skip == job.top.skip && f.bias == job.top.bias;
+            }
+        }
         return job;
     }
 
@@ -2306,7 +2599,33 @@ struct Build {                                 // a build of keys of W words: wh
                                shift, p.n_tiles, d_hist);
         } else if (p.closed_form)
             hipLaunchKernelGGL((item_write_closed_kernel<W>), dim3((unsigned)n_blocks), dim3(kScanBlock), 0, stream, sa);
-        else {
+        else if (job.first_pass_done) {
+            // the range's table -> row offsets and digit totals, as for a scatter whose tiles are the scan's workgroups
+            uint64_t *tab = fz_table + (uint64_t)((p.b_lo - multi_lo) / p.width) * 256 * n_blocks;
+            uint64_t *d_totals = pool_get<uint64_t>(ctx, S_SMALL, 4096) + 8;
+            hipLaunchKernelGGL(radix_rowscan_kernel, dim3(256), dim3(1024), 0, stream, tab, n_blocks, d_totals);
+            sa.fz_hist = tab; sa.fz_totals = d_totals; sa.fz_n = p.n_items;
+            sa.fz_bias[0] = job.top.bias; sa.fz_shift[0] = (uint32_t)shift;
+            if (job.side_done) {               // the digit of the pass that now runs first: the byte above
+                sa.side = pool_get<uint8_t>(ctx, S_SIDE, p.n_items + 64);
+                sa.side_shift = shift + 8;
+                sa.side_bias = job.top.bias;
+            }
+            if constexpr (W >= 2)
+                hipLaunchKernelGGL((item_write_fused_kernel<W>), dim3((unsigned)n_blocks), dim3(kScanBlock), 0, stream, sa);
+            sa.side = nullptr; sa.fz_hist = nullptr; sa.fz_totals = nullptr;
+            S.n_fused_passes++;
+            if (modes.fused >= 2) {            // (test aid)
+                uint32_t *d_bad = reinterpret_cast<uint32_t *>(pool_get<uint64_t>(ctx, S_SMALL, 4096) + 320);
+                uint32_t bad[2] = {0, 0};
+                MGTA_HIP_CHECK(hipMemsetAsync(d_bad, 0, 8, stream));
+                const unsigned grid = (unsigned)std::min<uint64_t>((p.n_items + kScanBlock - 1) / kScanBlock, (uint64_t)ctx->num_cus * 16);
+                hipLaunchKernelGGL((fused_check_kernel<W>), dim3(grid), dim3(kScanBlock), 0, stream, job.a, p.n_items, d_totals, job.top.bias, (uint32_t)shift, d_bad);
+                MGTA_HIP_CHECK(hipMemcpyAsync(bad, d_bad, 8, hipMemcpyDeviceToHost, stream));
+                MGTA_HIP_CHECK(hipStreamSynchronize(stream));
+                if (bad[0] || bad[1]) fz_check_failed = true;
+            }
+        } else {
             if (job.side_done) {
                 sa.side = pool_get<uint8_t>(ctx, S_SIDE, p.n_items + 64);
                 sa.side_shift = shift;
