@@ -75,6 +75,11 @@ int mgta_ctx_set_full_lsd(mgta_ctx *, int on);
  * once (bucket_begin << 16) is subtracted from key word 0 (0 for a whole-range build); the segment-local finish then sees segments of
  * equal leading 8 * n_passes + skip_bits bits.  Honours MGTA_SORT_BIAS. */
 int mgta_sort_plan(uint64_t n_items, int words_per_key, uint32_t bucket_begin, uint32_t bucket_end, int *n_passes, int *skip_bits);
+/* The plan the build really takes, wide digits included (MGTA_SORT_WIDE): widths[i] = bits of the i-th global pass to
+ * run, i < *n_passes <= 4 (the first 8, later ones 8 or 9); the segment-local finish sees segments of equal leading
+ * *skip_bits + sum(widths) bits.  Where wide digits save no pass this is mgta_sort_plan's answer with every width 8. */
+int mgta_sort_plan_wide(uint64_t n_items, int words_per_key, uint32_t bucket_begin, uint32_t bucket_end, int *n_passes, int *skip_bits,
+                        int *widths /* [4] */);
 /* Shared-cache searches (mgta_astar_batch with cache_mode = B >= 1): the path found by seed j after c_j node expansions is seen by
  * exactly the seeds >= j + B + c_j / expansions_per_seed.  0 (default) = no cost term: seed i sees the seeds <= i - B, and every
  * later seed waits for the longest unfinished search.  > 0: a search that has already run r expansions cannot become visible to the
@@ -157,6 +162,7 @@ typedef struct mgta_build_stats {
     uint64_t bytes_peak;             /* device bytes allocated at the peak */
     double ms_stage1;                /* min_count >= 2: solid-edge counting + mercy edges, before (and not part of) ms_total */
     int64_t n_fused_passes;          /* passes whose key writer placed the keys by the first global sort digit (no scatter launch for it) */
+    int64_t n_wide_passes;           /* radix scatter launches that sorted on a digit wider than 8 bits (MGTA_SORT_WIDE) */
 } mgta_build_stats;
 
 /* a1: packed reads as `buildgraph` holds them — every read REVERSED (cx1_read2sdbg_s1.cpp:97,117),

@@ -35,7 +35,8 @@ class BuildStats(C.Structure):
                 ("n_tips", C.c_int64), ("n_large", C.c_int64), ("n_sort_launches", C.c_int64), ("ms_total", C.c_double),
                 ("ms_count", C.c_double), ("ms_gen", C.c_double), ("ms_sort", C.c_double), ("ms_emit", C.c_double),
                 ("ms_d2h", C.c_double), ("ms_sort_scatter", C.c_double), ("ms_local_sort", C.c_double), ("n_big_segments", C.c_int64), ("n_lsd_tiles", C.c_int64),
-                ("bytes_peak", C.c_uint64), ("ms_stage1", C.c_double), ("n_fused_passes", C.c_int64)]
+                ("bytes_peak", C.c_uint64), ("ms_stage1", C.c_double), ("n_fused_passes", C.c_int64),
+                ("n_wide_passes", C.c_int64)]
 
     def as_dict(self):
         return {n: getattr(self, n) for n, _ in self._fields_}
@@ -185,6 +186,7 @@ SYMBOLS = {
     "mgta_ctx_set_mem_limit": (C.c_int, [C.c_void_p, C.c_uint64]),
     "mgta_ctx_set_full_lsd": (C.c_int, [C.c_void_p, C.c_int]),
     "mgta_sort_plan": (C.c_int, [C.c_uint64, C.c_int, C.c_uint32, C.c_uint32, C.POINTER(C.c_int), C.POINTER(C.c_int)]),
+    "mgta_sort_plan_wide": (C.c_int, [C.c_uint64, C.c_int, C.c_uint32, C.c_uint32, C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_int)]),
     "mgta_reads_upload": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint64, C.POINTER(C.c_void_p)]),
     "mgta_reads_adopt_device": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint64, C.POINTER(C.c_void_p)]),
     "mgta_reads_free": (None, [C.c_void_p]),

@@ -89,7 +89,8 @@ struct Timer {                   // owns its two events
 // at 10^8 reads, so unlike the other slots it is part of a pass's memory need, and Build::admit_pass lets it go where a pass only
 // fits without it
 enum Slot { S_BLOCK_COUNT, S_BLOCK_BASE, S_SCAN_TMP, S_SMALL, S_KEYS_A, S_KEYS_B, S_HIST, S_TILE_HEADS, S_TILE_BASE, S_CNT, S_BASE,
-            S_FIRST, S_OUT_REC, S_OUT_LARGE, S_OUT_TIPS, S_PLAN, S_BIG, S_LSD, S_MULTI_COUNT, S_POS2ID, S_SOLID, S_MERCY, S_EDGE_COUNT, S_SIDE, S_FUSED_HIST, S_NUM };
+            S_FIRST, S_OUT_REC, S_OUT_LARGE, S_OUT_TIPS, S_PLAN, S_BIG, S_LSD, S_MULTI_COUNT, S_POS2ID, S_SOLID, S_MERCY, S_EDGE_COUNT, S_SIDE, S_FUSED_HIST,
+            S_DIGIT_TOTALS /* keys per digit value of the global sort pass about to run: up to 1024 values */, S_NUM };
 
 }  // namespace mgta
 

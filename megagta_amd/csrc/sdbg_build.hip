@@ -125,6 +125,7 @@ struct ScanArgs {
     uint8_t *side;                         // write mode, optional: ((word 0 - side_bias) >> side_shift) & 255 of every key next to it (the
     int side_shift;                        // first global sort pass then counts these bytes instead of reading the keys back)
     uint32_t side_bias;
+    int side_bits;                         // fused writer: width of that digit; above 8 the entries are uint16_t (SideEntry)
     // fused first sort pass (item_scan_kernel<W, false, true> counts, item_write_fused_kernel places): digit of a key =
     // ((word 0 - fz_bias) >> fz_shift) & 255, per range counted ahead in the count scan, entry 0 in the writer
     uint64_t *fz_hist;                     // count scan: [range][digit value][workgroup]; writer: its range's slice after the row scan
@@ -263,7 +264,11 @@ __device__ __forceinline__ void item_scan_body(const ScanArgs &a) {
                 const uint64_t to = fs.next[d] + (i - fs.pos[d]);
                 if (to < a.fz_n) {
                     out[to] = key;
-                    if (a.side) a.side[to] = (uint8_t)((key.w[0] - a.side_bias) >> a.side_shift);
+                    if (a.side) {
+                        const uint32_t sd = (key.w[0] - a.side_bias) >> a.side_shift;
+                        if (a.side_bits > 8) reinterpret_cast<uint16_t *>(a.side)[to] = (uint16_t)(sd & ((1u << a.side_bits) - 1u));
+                        else a.side[to] = (uint8_t)sd;
+                    }
                 }
             }
             __syncthreads();
@@ -684,7 +689,7 @@ constexpr int kBlockTile = kSubTile * kSubTilesPerBlock;   // 32768 keys per wor
 
 struct Digit {
     int pos;     // bit position counted from the least significant bit of the whole key
-    int bits;    // <= 8
+    int bits;    // <= 8 (a global pass: the BITS of its kernels, 8 or 9)
     uint32_t bias;   // subtracted from key word 0 before the bits are taken (0 except for the global passes of a bucket sub-range build,
                      // where word 0 - (first bucket << 16) has leading zero bits that the digits skip)
 };
@@ -730,12 +735,30 @@ __device__ __forceinline__ void get_digits(const Key<W> (&key)[N], Digit d, uint
     for (int i = 0; i < N; ++i) dg[i] = __builtin_amdgcn_alignbit(hi[i], lo[i], (uint32_t)off) & mask;
 }
 
-// census: hist[digit * n_tiles + tile]
-template <int W>
+// wave_match (device_utils.hpp) for digits of a fixed width above 8 bits: one more ballot per bit
+template <int BITS>
+__device__ __forceinline__ void wave_match_wide(uint32_t dg, bool valid, uint32_t &rank, uint32_t &cnt) {
+    static_assert(BITS > 8 && BITS <= 16, "wave_match covers digits of up to 8 bits");
+    const uint64_t v = __ballot(valid);
+    uint32_t lo = (uint32_t)v, hi = (uint32_t)(v >> 32);
+#pragma unroll
+    for (int b = 0; b < BITS; ++b) {
+        const int sx = (int)(dg << (31 - b)) >> 31;
+        const uint64_t bal = __ballot(sx < 0);
+        lo &= ~((uint32_t)bal ^ (uint32_t)sx);
+        hi &= ~((uint32_t)(bal >> 32) ^ (uint32_t)sx);
+    }
+    rank = __builtin_amdgcn_mbcnt_hi(hi, __builtin_amdgcn_mbcnt_lo(lo, 0u));
+    cnt = (uint32_t)__popc(lo) + (uint32_t)__popc(hi);
+}
+
+// census: hist[digit * n_tiles + tile] (BITS: width of the digit's kernels, 1 << BITS values)
+template <int W, int BITS = 8>
 __global__ __launch_bounds__(kSortThreads) void radix_census_kernel(const Key<W> *keys, uint64_t n, Digit d, uint64_t n_tiles,
                                                                      uint64_t *hist) {
-    __shared__ uint32_t h[256];
-    for (int i = threadIdx.x; i < 256; i += kSortThreads) h[i] = 0;
+    constexpr int kVals = 1 << BITS;
+    __shared__ uint32_t h[kVals];
+    for (int i = threadIdx.x; i < kVals; i += kSortThreads) h[i] = 0;
     __syncthreads();
     const uint32_t tile = xcd_tile(blockIdx.x, (uint32_t)n_tiles);     // (neighbouring tiles' counters share lines: one L2 writes them)
     uint64_t base = (uint64_t)tile * kBlockTile;
@@ -751,37 +774,49 @@ __global__ __launch_bounds__(kSortThreads) void radix_census_kernel(const Key<W>
         }
     }
     __syncthreads();
-    for (int i = threadIdx.x; i < 256; i += kSortThreads) hist[(uint64_t)i * n_tiles + tile] = h[i];
+    for (int i = threadIdx.x; i < kVals; i += kSortThreads) hist[(uint64_t)i * n_tiles + tile] = h[i];
 }
 
 // The same census from the SIDE array of the previous scatter (one byte per key: the digit this pass sorts on, written next to the
 // key at its destination): 1 byte read per key instead of the whole key (W = 3: 7.2 GB instead of 86 GB per launch at 100 M reads).
-__global__ __launch_bounds__(kSortThreads) void radix_census_side_kernel(const uint8_t *side, uint64_t n, uint64_t n_tiles, uint64_t *hist) {
-    __shared__ uint32_t h[256];
-    for (int i = threadIdx.x; i < 256; i += kSortThreads) h[i] = 0;
+// A digit of more than 8 bits travels as uint16_t: 2 bytes per key, eight keys per 16-byte load.
+template <int BITS> using SideEntry = std::conditional_t<(BITS > 8), uint16_t, uint8_t>;
+
+template <int BITS = 8>
+__global__ __launch_bounds__(kSortThreads) void radix_census_side_kernel(const SideEntry<BITS> *side, uint64_t n, uint64_t n_tiles, uint64_t *hist) {
+    constexpr int kVals = 1 << BITS;
+    constexpr uint32_t kMask = kVals - 1;
+    __shared__ uint32_t h[kVals];
+    for (int i = threadIdx.x; i < kVals; i += kSortThreads) h[i] = 0;
     __syncthreads();
     const uint32_t tile = xcd_tile(blockIdx.x, (uint32_t)n_tiles);
     const uint64_t base = (uint64_t)tile * kBlockTile;                       // a multiple of 32768: 16-byte loads are aligned
-    constexpr int kPerThread = kBlockTile / kSortThreads;                    // 32 bytes = two 16-byte loads, consecutive threads consecutive
+    constexpr int kPerThread = kBlockTile / kSortThreads;                    // 32 entries = two (four) 16-byte loads, consecutive threads consecutive
+    constexpr int kPerLoad = 16 / (int)sizeof(SideEntry<BITS>);              // entries of a 16-byte load
 #pragma unroll
-    for (int half = 0; half < kPerThread / 16; ++half) {
-        const uint64_t idx = base + (uint64_t)half * (kSortThreads * 16) + (uint64_t)threadIdx.x * 16;
-        if (idx + 16 <= n) {
+    for (int half = 0; half < kPerThread / kPerLoad; ++half) {
+        const uint64_t idx = base + (uint64_t)half * (kSortThreads * kPerLoad) + (uint64_t)threadIdx.x * kPerLoad;
+        if (idx + kPerLoad <= n) {
             const uint4 v = *reinterpret_cast<const uint4 *>(side + idx);
             const uint32_t w[4] = {v.x, v.y, v.z, v.w};
 #pragma unroll
             for (int j = 0; j < 4; ++j) {
-                atomicAdd(&h[w[j] & 255u], 1u);
-                atomicAdd(&h[(w[j] >> 8) & 255u], 1u);
-                atomicAdd(&h[(w[j] >> 16) & 255u], 1u);
-                atomicAdd(&h[w[j] >> 24], 1u);
+                if constexpr (BITS > 8) {
+                    atomicAdd(&h[w[j] & kMask], 1u);
+                    atomicAdd(&h[(w[j] >> 16) & kMask], 1u);
+                } else {
+                    atomicAdd(&h[w[j] & 255u], 1u);
+                    atomicAdd(&h[(w[j] >> 8) & 255u], 1u);
+                    atomicAdd(&h[(w[j] >> 16) & 255u], 1u);
+                    atomicAdd(&h[w[j] >> 24], 1u);
+                }
             }
         } else {
-            for (uint64_t i = idx; i < n && i < idx + 16; ++i) atomicAdd(&h[side[i]], 1u);
+            for (uint64_t i = idx; i < n && i < idx + kPerLoad; ++i) atomicAdd(&h[side[i] & kMask], 1u);
         }
     }
     __syncthreads();
-    for (int i = threadIdx.x; i < 256; i += kSortThreads) hist[(uint64_t)i * n_tiles + tile] = h[i];
+    for (int i = threadIdx.x; i < kVals; i += kSortThreads) hist[(uint64_t)i * n_tiles + tile] = h[i];
 }
 
 // Closed-form key generation (see item_write_closed_kernel) cut along the census tiles of the first global sort pass: workgroup t
@@ -917,13 +952,14 @@ template <int W> struct ScatterCfg {
     static constexpr int kChunk = kSub / kSortWaves;
 };
 
-// shared state of one scatter workgroup
-template <int W>
+// shared state of one scatter workgroup (BITS: width of the digit it scatters by, 8..10)
+template <int W, int BITS = 8>
 struct ScatterShared {
+    static constexpr int kVals = 1 << BITS;
     Key<W> keys[ScatterCfg<W>::kSub];
-    uint16_t whist[kSortWaves][256];   // per wave: running count, then position of the wave's first key of the digit value in the sorted sub-tile
-    uint64_t gbase[256];               // global destination of the next key of each digit value
-    uint64_t gdelta[256];              // global destination minus position in the sorted sub-tile
+    uint16_t whist[kSortWaves][kVals]; // per wave: running count, then position of the wave's first key of the digit value in the sorted sub-tile
+    uint64_t gbase[kVals];             // global destination of the next key of each digit value
+    uint64_t gdelta[kVals];            // global destination minus position in the sorted sub-tile
     uint32_t scratch[kSortThreads / 64 + 1];
 };
 
@@ -933,22 +969,30 @@ struct ScatterShared {
 // tile are collected in LDS in the order the tile's keys land in (per digit value the eight sub-tiles append to ONE run of ~128 keys)
 // and written run by run when the tile is done: byte stores straight from the sub-tiles (runs of ~16 bytes, four per wave
 // instruction) cost the scatter 21 % (100 M reads: 43.9 -> 53.4 ms per launch).
+// An entry is as wide as the digit it carries (NEXT_BITS, SideEntry): uint16_t where the next pass sorts on more than 8 bits.
+template <int BITS = 8, int NEXT_BITS = 8>
 struct SideShared {
-    uint8_t bytes[kBlockTile];
-    uint64_t gtile[256];               // global destination of the tile's first key of a digit value minus that key's place in `bytes`
-    uint32_t toff[257];                // place in `bytes` of the tile's first key of a digit value
+    static constexpr int kVals = 1 << BITS;
+    SideEntry<NEXT_BITS> bytes[kBlockTile];
+    uint64_t gtile[kVals];             // global destination of the tile's first key of a digit value minus that key's place in `bytes`
+    uint32_t toff[kVals + 1];          // place in `bytes` of the tile's first key of a digit value
 };
 
 // STABLE = false: keys of one digit value may leave in any order -- all the FIRST pass of an LSD sort needs (nothing is ordered yet).
 // The rank inside the wave's chunk then comes from an LDS atomic on the wave's counter instead of the eight ballots of wave_match,
 // which are 45 % of the stable kernel's vector instructions (54 of ~120 per key).
-template <int W, bool BIASED = false, bool SIDE = false, bool STABLE = true>
-__device__ __forceinline__ void scatter_subtiles(ScatterShared<W> &sh, const Key<W> *in, Key<W> *out, uint64_t n, Digit d, SideShared *ss = nullptr,
-                                                 Digit d_next = Digit{0, 0, 0}) {
+// BITS: width of d (1 << BITS digit values: 8, or 9..10 for the wide passes of a plan); NEXT_BITS: width of d_next (SIDE).
+template <int W, bool BIASED = false, bool SIDE = false, bool STABLE = true, int BITS = 8, int NEXT_BITS = 8>
+__device__ __forceinline__ void scatter_subtiles(ScatterShared<W, BITS> &sh, const Key<W> *in, Key<W> *out, uint64_t n, Digit d,
+                                                 SideShared<BITS, NEXT_BITS> *ss = nullptr, Digit d_next = Digit{0, 0, 0}) {
     constexpr int kItemsPerThread = ScatterCfg<W>::kIpt, kSubTile = ScatterCfg<W>::kSub, kWaveChunk = ScatterCfg<W>::kChunk;   // (shadow the 4096-key constants)
+    constexpr int kVals = 1 << BITS, kValWaves = kVals / 64;       // digit values; waves that hold one value per thread in phase 2
+    constexpr uint32_t kDigitMask = kVals - 1;
+    static_assert(BITS >= 8 && kValWaves <= kSortWaves && BITS + 13 <= 31, "a thread per digit value; digit | place in the sub-tile << BITS | valid << 31");
+    static_assert(STABLE || BITS == 8, "only the first pass to run is unstable, and that one sorts on 8 bits");
     const int tid = threadIdx.x, lane = lane_id(), wv = wave_id();
     uint16_t *whist = sh.whist[wv];               // wave-private row, updated lane-to-lane inside the wave
-    for (int i = lane; i < 256; i += 64) whist[i] = 0;
+    for (int i = lane; i < kVals; i += 64) whist[i] = 0;
     constexpr bool kPrefetch = W * kItemsPerThread <= 16;   // wider keys: the registers are better spent on the keys in flight
     Key<W> key[kItemsPerThread], nxt[kItemsPerThread];
     auto load = [&](Key<W> (&dst)[kItemsPerThread], uint64_t sub_base) {   // wave w owns keys [w*512, w*512+512) of the sub-tile, 64 at a time
@@ -962,7 +1006,7 @@ __device__ __forceinline__ void scatter_subtiles(ScatterShared<W> &sh, const Key
     for (uint64_t sub_base = 0; sub_base < n; sub_base += kSubTile) {
         uint32_t n_valid = (uint32_t)((n - sub_base) < (uint64_t)kSubTile ? (n - sub_base) : (uint64_t)kSubTile);
         // phase 1: rank inside the wave chunk: digit + peers of every key, then the wave's running counts round by round
-        uint32_t dr[kItemsPerThread], cnt[kItemsPerThread];   // digit | rank-in-wave-chunk << 8 | valid << 31
+        uint32_t dr[kItemsPerThread], cnt[kItemsPerThread];   // digit | rank-in-wave-chunk << BITS | valid << 31
         get_digits<W, kItemsPerThread, BIASED>(key, d, dr);
         if constexpr (STABLE) {
 #pragma unroll
@@ -970,15 +1014,16 @@ __device__ __forceinline__ void scatter_subtiles(ScatterShared<W> &sh, const Key
                 uint32_t j = (uint32_t)wv * kWaveChunk + (uint32_t)it * 64 + (uint32_t)lane;
                 bool valid = j < n_valid;
                 uint32_t dg = valid ? dr[it] : 0u, rank;
-                wave_match(dg, d.bits, valid, rank, cnt[it]);
-                dr[it] = dg | (rank << 8) | ((uint32_t)valid << 31);
+                if constexpr (BITS > 8) wave_match_wide<BITS>(dg, valid, rank, cnt[it]);
+                else wave_match(dg, d.bits, valid, rank, cnt[it]);
+                dr[it] = dg | (rank << BITS) | ((uint32_t)valid << 31);
             }
 #pragma unroll
             for (int it = 0; it < kItemsPerThread; ++it) {
                 if (dr[it] >> 31) {
-                    const uint32_t dg = dr[it] & 255u, rank = (dr[it] >> 8) & 0xFFu, prev = whist[dg];
+                    const uint32_t dg = dr[it] & kDigitMask, rank = (dr[it] >> BITS) & 0xFFu, prev = whist[dg];
                     if (rank == cnt[it] - 1) whist[dg] = (uint16_t)(prev + cnt[it]);   // highest peer lane publishes the new count
-                    dr[it] += prev << 8;
+                    dr[it] += prev << BITS;
                 }
                 wave_lds_fence();
             }
@@ -991,22 +1036,22 @@ __device__ __forceinline__ void scatter_subtiles(ScatterShared<W> &sh, const Key
                 const uint32_t dg = valid ? dr[it] : 0u;
                 uint32_t taken = 0;
                 if (valid) taken = (atomicAdd(&wh32[dg >> 1], 1u << (16u * (dg & 1u))) >> (16u * (dg & 1u))) & 0xFFFFu;   // keys of the value before this one, in any order
-                dr[it] = dg | (taken << 8) | ((uint32_t)valid << 31);
+                dr[it] = dg | (taken << BITS) | ((uint32_t)valid << 31);
             }
             wave_lds_fence();
         }
         if (kPrefetch && sub_base + kSubTile < n) load(nxt, sub_base + kSubTile);
         __syncthreads();
-        // phase 2: per digit value (threads 0..255 = waves 0..3): total over the waves, scan over the values, wave bases, global bases
+        // phase 2: per digit value (threads 0..255 = waves 0..3 at 8 bits): total over the waves, scan over the values, wave bases, global bases
         uint32_t tot = 0, inc = 0;
-        if (wv < 4) {
+        if (wv < kValWaves) {
 #pragma unroll
             for (int w = 0; w < kSortWaves; ++w) tot += sh.whist[w][tid];
             inc = wave_incl_scan(tot);
             if (lane == 63) sh.scratch[wv] = inc;
         }
         __syncthreads();
-        if (wv < 4) {
+        if (wv < kValWaves) {
             uint32_t running = inc - tot;
             for (int w = 0; w < wv; ++w) running += sh.scratch[w];
             const uint64_t g = sh.gbase[tid];
@@ -1020,13 +1065,13 @@ __device__ __forceinline__ void scatter_subtiles(ScatterShared<W> &sh, const Key
 #pragma unroll
         for (int it = 0; it < kItemsPerThread; ++it) {
             if (dr[it] >> 31) {
-                const uint32_t pos = whist[dr[it] & 255u] + ((dr[it] >> 8) & 0x7FFFFFu);
+                const uint32_t pos = whist[dr[it] & kDigitMask] + ((dr[it] >> BITS) & (0x7FFFFFFFu >> BITS));
 #pragma unroll
                 for (int w = 0; w < W; ++w) sh.keys[pos].w[w] = key[it].w[w];
             }
         }
         __syncthreads();
-        for (int i = lane; i < 256; i += 64) whist[i] = 0;                // own row, read by this wave only since the last barrier
+        for (int i = lane; i < kVals; i += 64) whist[i] = 0;              // own row, read by this wave only since the last barrier
         // phase 4: stream the sorted sub-tile out; consecutive threads hit consecutive addresses inside a run
         if (kPrefetch) {
             Key<W> kk[kItemsPerThread];
@@ -1046,7 +1091,7 @@ __device__ __forceinline__ void scatter_subtiles(ScatterShared<W> &sh, const Key
                     if (j < n_valid) {
                         const uint64_t to = sh.gdelta[dg[it]] + j;
                         out[to] = kk[it];
-                        ss->bytes[(uint32_t)(to - ss->gtile[dg[it]])] = (uint8_t)dn[it];
+                        ss->bytes[(uint32_t)(to - ss->gtile[dg[it]])] = (SideEntry<NEXT_BITS>)dn[it];
                     }
                 }
             } else {
@@ -1067,7 +1112,7 @@ __device__ __forceinline__ void scatter_subtiles(ScatterShared<W> &sh, const Key
                     const uint32_t dg = get_digit<W, BIASED>(kk, d);
                     const uint64_t to = sh.gdelta[dg] + j;
                     out[to] = kk;
-                    if constexpr (SIDE) ss->bytes[(uint32_t)(to - ss->gtile[dg])] = (uint8_t)get_digit<W, BIASED>(kk, d_next);
+                    if constexpr (SIDE) ss->bytes[(uint32_t)(to - ss->gtile[dg])] = (SideEntry<NEXT_BITS>)get_digit<W, BIASED>(kk, d_next);
                 }
             }
             if (sub_base + kSubTile < n) load(key, sub_base + kSubTile);
@@ -1076,55 +1121,66 @@ __device__ __forceinline__ void scatter_subtiles(ScatterShared<W> &sh, const Key
 }
 
 // stable scatter of one 32768-key tile by the current digit
-// side digits only where the tile's bytes fit the LDS next to the staged keys (W <= 7 key words)
-template <int W> constexpr bool kSideFits = sizeof(ScatterShared<W>) + sizeof(SideShared) + 1024 <= 160 * 1024;
+// What a key width supports: the staged keys, the tables of 1 << BITS digit values and (SIDE_BITS > 0) the tile's side entries of a
+// SIDE_BITS-wide next digit must fit the 160 KB of LDS.  Side digits at all: W <= 7 key words.  Wide digits (9 bits with 16-bit side
+// entries, 8 bits with 16-bit side entries): W = 2 and 3; every other key width, stage 1's W + 2 words among them, keeps 8-bit
+// digits (W = 4 with 9 bits and 16-bit entries would come within 952 bytes of the 160 KB, the 1 KB of slack included: not built).
+// 10 bits fit W = 3 without side entries only (98 KB; with them 176 KB), i.e. as a plan's last pass: 8 + 8 + 10 was measured equal
+// to 8 + 9 + 9 and is not built (profiles/r08/build_wide/README.md).
+template <int W, int BITS, int SIDE_BITS>
+constexpr bool kScatterFits = sizeof(ScatterShared<W, BITS>) + (SIDE_BITS ? sizeof(SideShared<BITS, (SIDE_BITS ? SIDE_BITS : 8)>) : 0) + 1024 <= 160 * 1024;
+template <int W> constexpr bool kSideFits = kScatterFits<W, 8, 8>;
+template <int W> constexpr bool kWideFits = W >= 2 && W <= 3 && kSideFits<W> && kScatterFits<W, 9, 9> && kScatterFits<W, 8, 9>;
+static_assert(kWideFits<3> && kWideFits<2> && !kWideFits<4> && !kScatterFits<3, 10, 9>, "DESIGN.md 5: the LDS bound of the wide scatter variants");
 
-template <int W, bool BIASED, bool SIDE = false, bool STABLE = true>
+template <int W, bool BIASED, bool SIDE = false, bool STABLE = true, int BITS = 8, int NEXT_BITS = 8>
 __global__ __launch_bounds__(kSortThreads, 4) void radix_scatter_kernel(const Key<W> *in, Key<W> *out, uint64_t n, Digit d,
                                                                       uint64_t n_tiles, const uint64_t *rowoff,
-                                                                      const uint64_t *totals, uint8_t *side = nullptr,
+                                                                      const uint64_t *totals, SideEntry<NEXT_BITS> *side = nullptr,
                                                                       Digit d_next = Digit{0, 0, 0}) {
-    __shared__ ScatterShared<W> sh;
+    constexpr int kVals = 1 << BITS;
+    static_assert(kVals <= kSortThreads, "a thread per digit value");
+    __shared__ ScatterShared<W, BITS> sh;
     __shared__ uint64_t s64[kSortThreads / 64 + 1];
     const int tid = threadIdx.x;
     // workgroups go to the 8 XCDs in turn: XCD x takes the x-th eighth of the tiles, so that the tiles that run side by side on one
     // L2 are neighbours (their runs of a digit value are adjacent in the output: lines shared by two tiles are completed in one L2)
     const uint32_t tile = xcd_tile(blockIdx.x, (uint32_t)n_tiles);
     // global base of every digit value for this tile = scan(totals)[digit] + rowoff[digit][tile]
-    uint64_t t = tid < 256 ? totals[tid] : 0;
+    uint64_t t = tid < kVals ? totals[tid] : 0;
     uint64_t ex = block_excl_scan64<kSortThreads>(t, s64, nullptr);
-    const uint64_t my_off = tid < 256 ? rowoff[(uint64_t)tid * n_tiles + tile] : 0;
-    if (tid < 256) sh.gbase[tid] = ex + my_off;
+    const uint64_t my_off = tid < kVals ? rowoff[(uint64_t)tid * n_tiles + tile] : 0;
+    if (tid < kVals) sh.gbase[tid] = ex + my_off;
     const uint64_t tile_base = (uint64_t)tile * kBlockTile;
     if constexpr (SIDE) {
-        __shared__ SideShared ss;
+        __shared__ SideShared<BITS, NEXT_BITS> ss;
         // keys of the tile per digit value: the next tile's row offset (the row total behind the last tile) minus this tile's
         uint64_t c = 0;
-        if (tid < 256) c = (tile + 1 < n_tiles ? rowoff[(uint64_t)tid * n_tiles + tile + 1] : t) - my_off;
+        if (tid < kVals) c = (tile + 1 < n_tiles ? rowoff[(uint64_t)tid * n_tiles + tile + 1] : t) - my_off;
         __syncthreads();                                                 // s64 is free again
         const uint64_t place = block_excl_scan64<kSortThreads>(c, s64, nullptr);
-        if (tid < 256) {
+        if (tid < kVals) {
             ss.toff[tid] = (uint32_t)place;
             ss.gtile[tid] = ex + my_off - place;
-            if (tid == 255) ss.toff[256] = (uint32_t)(place + c);
+            if (tid == kVals - 1) ss.toff[kVals] = (uint32_t)(place + c);
         }
         __syncthreads();
         if (tile_base >= n) return;
         const uint64_t cnt = (n - tile_base) < (uint64_t)kBlockTile ? (n - tile_base) : (uint64_t)kBlockTile;
-        scatter_subtiles<W, BIASED, true, STABLE>(sh, in + tile_base, out, cnt, d, &ss, d_next);
+        scatter_subtiles<W, BIASED, true, STABLE, BITS, NEXT_BITS>(sh, in + tile_base, out, cnt, d, &ss, d_next);
         __syncthreads();
-        // the tile's bytes, run by run: a wave per 16 digit values, consecutive lanes consecutive bytes
+        // the tile's entries, run by run: a wave per 16 (32, 64) digit values, consecutive lanes consecutive entries
         const int lane = lane_id(), wv = wave_id();
-        for (int v = wv * (256 / kSortWaves); v < (wv + 1) * (256 / kSortWaves); ++v) {
+        for (int v = wv * (kVals / kSortWaves); v < (wv + 1) * (kVals / kSortWaves); ++v) {
             const uint32_t from = ss.toff[v], len = ss.toff[v + 1] - from;
-            uint8_t *to = side + ss.gtile[v] + from;
+            SideEntry<NEXT_BITS> *to = side + ss.gtile[v] + from;
             for (uint32_t i = lane; i < len; i += 64) to[i] = ss.bytes[from + i];
         }
     } else {
         __syncthreads();
         if (tile_base >= n) return;
         const uint64_t cnt = (n - tile_base) < (uint64_t)kBlockTile ? (n - tile_base) : (uint64_t)kBlockTile;
-        scatter_subtiles<W, BIASED, false, STABLE>(sh, in + tile_base, out, cnt, d);
+        scatter_subtiles<W, BIASED, false, STABLE, BITS>(sh, in + tile_base, out, cnt, d);
     }
 }
 
@@ -1969,11 +2025,13 @@ static uint64_t pool_bytes(const mgta_ctx *ctx) {
 // of the keys (tests).  Read once per build and never cached: tests and scripts flip them between builds.
 // MGTA_SORT_FUSED: the key writer of a range pass does the first global sort pass (see Build::count_pass) 0 never, 1 (default) where
 // the plan of the pass was known when its items were counted, 2 the same and the writer's output checked on the device (tests).
+// MGTA_SORT_WIDE: global passes on digits of more than 8 bits (see widen_top_plan) 0 never, 1 (default) where they save a global pass
+// and leave short segments, 2 every pass but the first to run, whatever it saves (tests: small inputs take the wide kernels).
 struct SortModes {
-    int bias = 1, side = 1, fused = 1;
+    int bias = 1, side = 1, fused = 1, wide = 1;
     static SortModes from_env() {
-        const char *bias = getenv("MGTA_SORT_BIAS"), *side = getenv("MGTA_SORT_SIDE"), *fused = getenv("MGTA_SORT_FUSED");
-        return SortModes{bias ? atoi(bias) : 1, side ? atoi(side) : 1, fused ? atoi(fused) : 1};
+        const char *bias = getenv("MGTA_SORT_BIAS"), *side = getenv("MGTA_SORT_SIDE"), *fused = getenv("MGTA_SORT_FUSED"), *wide = getenv("MGTA_SORT_WIDE");
+        return SortModes{bias ? atoi(bias) : 1, side ? atoi(side) : 1, fused ? atoi(fused) : 1, wide ? atoi(wide) : 1};
     }
 };
 
@@ -1982,17 +2040,36 @@ struct SortModes {
 // word 0.  prefix_frac: share of the leading-byte values the keys can take (a pass over a bucket sub-range only holds that share of
 // the prefixes, so its segments are as long as those of the whole key set)
 static double avg_segment_len(uint64_t n_items, int p, double prefix_frac) { return (double)n_items / std::max(1.0, std::pow(256.0, p) * prefix_frac); }
+// the same for passes that sorted on `bits` key bits in all
+static double avg_segment_len_bits(uint64_t n_items, int bits, double prefix_frac) { return (double)n_items / std::max(1.0, std::pow(2.0, bits) * prefix_frac); }
 // The global passes of a build over the buckets [b_lo, b_hi) need not spend digit values on prefixes no key has: word 0 minus
 // (b_lo << 16) has `skip` leading zero bits, and P digits of 8 bits taken right below them order the keys by their leading
 // T = 8P + skip bits (a third of the buckets: skip = 1, so three passes leave the 645-key segments that otherwise take four).
 // T >= 16 is required: then the bias is a multiple of 2^(32 - T) and equal biased prefixes are equal key prefixes.
+// A pass may sort on more than 8 bits (width[]): the pass that runs first keeps 8 (its census comes from the key writers), later
+// ones take 9 where the scatter of the key width has the LDS for 512 digit values and 16-bit side entries (kWideFits).
+constexpr int kMaxTop = 4;
 struct TopPlan {
     int P = 0, skip = 0;
     uint32_t bias = 0;
     double frac = 1.0;           // share of the 2^T prefix values the keys can take
-    int T() const { return 8 * P + skip; }
-    // digit of global pass i, most significant first (i = 0: the 8 key bits right below the `skip` bits every key shares, after the bias)
-    Digit pass_digit(int W, int i) const { return Digit{32 * W - 8 * (i + 1) - skip, 8, bias}; }
+    int width[kMaxTop] = {8, 8, 8, 8};   // bits of global pass i, most significant first (pass P - 1 runs first)
+    int key_bits() const { int t = 0; for (int i = 0; i < P; ++i) t += width[i]; return t; }
+    int T() const { return key_bits() + skip; }
+    int n_wide() const { int c = 0; for (int i = 0; i < P; ++i) c += width[i] > 8; return c; }
+    int max_width() const { int m = 8; for (int i = 0; i < P; ++i) m = std::max(m, width[i]); return m; }
+    bool same_digits(const TopPlan &o) const {
+        bool same = P == o.P && skip == o.skip && bias == o.bias;
+        for (int i = 0; same && i < P; ++i) same = width[i] == o.width[i];
+        return same;
+    }
+    // digit of global pass i, most significant first (i = 0: the key bits right below the `skip` bits every key shares, after the bias)
+    Digit pass_digit(int W, int i) const {
+        int below = skip;
+        for (int j = 0; j <= i; ++j) below += width[j];
+        return Digit{32 * W - below, width[i], bias};
+    }
+    double avg_segment(uint64_t n_items) const { return avg_segment_len_bits(n_items, key_bits(), frac); }
 };
 // mode: SortModes::bias
 static TopPlan choose_top_plan(const mgta_ctx *ctx, uint64_t n_items, int max_top, double prefix_frac, uint32_t b_lo = 0, uint32_t b_hi = 0,
@@ -2019,6 +2096,40 @@ static TopPlan choose_top_plan(const mgta_ctx *ctx, uint64_t n_items, int max_to
     return plain;
 }
 
+// Wide digits (wide: SortModes::wide, for key widths with kWideFits only).  `base` is choose_top_plan's choice.  1: one pass fewer
+// with 8 bits in the pass that runs first and 9 in every later one, below the most leading bits the range's keys share that still
+// fit 32 (bias_mode != 0), where that leaves segments of <= 256 keys on average -- at 100 M reads (7.2 G keys per range, a third of
+// the buckets) 8 + 9 + 9 bits below 1 skipped bit, T = 27, 161-key segments, in place of four 8-bit passes.  2: the passes of `base`,
+// as many of the later ones 9 bits wide as fit 32 bits (the leading ones first), the skipped bits cut to what is left.
+static TopPlan widen_top_plan(const TopPlan &base, uint64_t n_items, int max_top, double prefix_frac, uint32_t b_lo, uint32_t b_hi, int bias_mode,
+                              int wide) {
+    const int max_bits = 8 * std::min(max_top, kMaxTop);
+    if (wide <= 0 || base.P < 2) return base;
+    if (wide >= 2) {
+        TopPlan tp = base;
+        for (int i = 0; i < tp.P - 1 && tp.key_bits() < max_bits; ++i) tp.width[i] = 9;
+        if (tp.key_bits() + tp.skip > max_bits) {
+            tp.skip = max_bits - tp.key_bits();
+            if (tp.skip < 0 || (tp.skip > 0 && tp.T() < 16)) return base;
+            if (tp.skip == 0) tp.bias = 0;
+            tp.frac = std::min(1.0, prefix_frac * std::pow(2.0, tp.skip));
+        }
+        return tp;
+    }
+    if (base.P < 3) return base;               // (one pass fewer must still hold a wide pass behind the first)
+    TopPlan tp;
+    tp.P = base.P - 1;
+    for (int i = 0; i < tp.P - 1; ++i) tp.width[i] = 9;
+    const bool sub_range = bias_mode != 0 && b_hi > b_lo && !(b_lo == 0 && b_hi >= (uint32_t)MGTA_NUM_BUCKETS);
+    const int skip_full = sub_range ? __builtin_clz((((b_hi - b_lo) << 16) - 1u) | 1u) : 0;
+    tp.skip = std::max(0, std::min(skip_full, max_bits - tp.key_bits()));
+    if (tp.skip > 0 && tp.T() < 16) tp.skip = 0;
+    tp.bias = tp.skip > 0 ? b_lo << 16 : 0u;
+    tp.frac = std::min(1.0, prefix_frac * std::pow(2.0, tp.skip));
+    if (tp.key_bits() > max_bits || tp.avg_segment(n_items) > 256.0) return base;
+    return tp;
+}
+
 // One sort: n keys of WT words in `a` (`b` is the other buffer of the ping-pong) ascending on the digits that matter: top.P global LSD
 // passes on the leading bytes, then every segment of equal prefix finished inside LDS on the `low` digits.  The key writer of a build
 // pass reads the same object (fused census, side digits), so the writer and the sort cannot disagree on the plan.
@@ -2036,59 +2147,100 @@ struct SortJob {
     // side digits: the scatter of a pass leaves the NEXT pass's digit of every key in a byte array (S_SIDE), and that pass's census
     // reads the bytes instead of the keys
     bool uses_side() const { return side_mode > 0 && top.P >= 2 && kSideFits<WT>; }
+    // bytes of S_SIDE (an entry is as wide as the digit it carries) and of the census table S_HIST (a row per digit value of the widest
+    // pass): the key writer and the sort ask for the same, so that neither's request moves what the other left there
+    uint64_t side_bytes() const { return n * (top.max_width() > 8 ? 2u : 1u) + 64; }
+    uint64_t hist_bytes() const { return std::max<uint64_t>(1, (n + kBlockTile - 1) / kBlockTile) * ((uint64_t)8 << top.max_width()); }
 };
+// keys per digit value of the pass about to run (radix_rowscan_kernel -> radix_scatter_kernel, the fused key writer)
+static uint64_t *digit_totals(mgta_ctx *ctx) { return pool_get<uint64_t>(ctx, S_DIGIT_TOTALS, 1024 * 8); }
 struct SortLog {                              // what the stats of a build take from its sorts
     mgta_build_stats *S = nullptr;
     std::vector<Timer> scatter;               // one per global scatter, read when the build is done (ms_sort_scatter)
 };
 
+// census, row scan and scatter of ONE global pass on a digit of BITS bits (NEXT_BITS: width of the next pass's digit, whose side
+// entries this scatter writes where write_side); false on an error (set)
+template <int WT, int BITS, int NEXT_BITS>
+static bool global_pass(mgta_ctx *ctx, const SortJob<WT> &job, SortLog *log, const Key<WT> *src, Key<WT> *dst, Digit dg, Digit dn, bool first,
+                        bool side_valid, bool write_side, void *d_side, uint64_t *d_hist, uint64_t *d_totals) {
+    hipStream_t stream = ctx->stream;
+    const uint64_t n = job.n, tiles = (n + kBlockTile - 1) / kBlockTile;
+    constexpr uint64_t kVals = 1ull << BITS;
+    const dim3 grid((unsigned)tiles), block(kSortThreads);
+    if (!(first && job.census_done)) {
+        if (side_valid) {
+            hipLaunchKernelGGL((radix_census_side_kernel<BITS>), grid, block, 0, stream, static_cast<const SideEntry<BITS> *>(d_side), n, tiles, d_hist);
+            if (job.side_mode >= 2) {                               // (test aid) the same census from the keys must agree
+                std::vector<uint64_t> h_side(tiles * kVals), h_keys(tiles * kVals);
+                MGTA_HIP_CHECK(hipStreamSynchronize(stream));
+                MGTA_HIP_CHECK(hipMemcpy(h_side.data(), d_hist, tiles * kVals * 8, hipMemcpyDeviceToHost));
+                hipLaunchKernelGGL((radix_census_kernel<WT, BITS>), grid, block, 0, stream, src, n, dg, tiles, d_hist);
+                MGTA_HIP_CHECK(hipStreamSynchronize(stream));
+                MGTA_HIP_CHECK(hipMemcpy(h_keys.data(), d_hist, tiles * kVals * 8, hipMemcpyDeviceToHost));
+                if (h_side != h_keys) { set_error("internal: side-digit census differs from the census of the keys"); return false; }
+            }
+        } else
+            hipLaunchKernelGGL((radix_census_kernel<WT, BITS>), grid, block, 0, stream, src, n, dg, tiles, d_hist);
+    }
+    hipLaunchKernelGGL(radix_rowscan_kernel, dim3((unsigned)kVals), dim3(1024), 0, stream, d_hist, tiles, d_totals);   // a row per digit value
+    if (log) log->scatter.emplace_back(stream).start();
+    // (the first pass of the sort orders nothing that was ordered before: its ranks need not be stable)
+    auto launch = [&](auto biased, auto side, auto stable) {
+        constexpr bool kSide = decltype(side)::value;
+        hipLaunchKernelGGL((radix_scatter_kernel<WT, decltype(biased)::value, kSide, decltype(stable)::value, BITS, kSide ? NEXT_BITS : 8>), grid, block, 0, stream,
+                           src, dst, n, dg, tiles, d_hist, d_totals, kSide ? static_cast<SideEntry<kSide ? NEXT_BITS : 8> *>(d_side) : nullptr, dn);
+    };
+    auto pick_stable = [&](auto biased, auto side) {
+        if constexpr (BITS == 8) {
+            if (first) { launch(biased, side, std::false_type{}); return; }
+        }
+        launch(biased, side, std::true_type{});                 // (a wide pass never runs first)
+    };
+    auto pick_side = [&](auto biased) {
+        if constexpr (kScatterFits<WT, BITS, NEXT_BITS>) {
+            if (write_side) { pick_stable(biased, std::true_type{}); return; }
+        }
+        pick_stable(biased, std::false_type{});
+    };
+    dg.bias ? pick_side(std::true_type{}) : pick_side(std::false_type{});
+    if (log) {
+        log->scatter.back().end();
+        log->S->n_sort_launches++;
+        if (BITS > 8) log->S->n_wide_passes++;
+    }
+    return true;
+}
+
 // the top.P global passes, least significant digit first; returns the buffer that holds their result, nullptr on an error (set)
 template <int WT>
 static Key<WT> *global_passes(mgta_ctx *ctx, const SortJob<WT> &job, SortLog *log) {
-    hipStream_t stream = ctx->stream;
-    const uint64_t n = job.n, tiles = (n + kBlockTile - 1) / kBlockTile;
-    uint64_t *d_hist = pool_get<uint64_t>(ctx, S_HIST, std::max<uint64_t>(1, tiles) * 256 * 8);
-    uint64_t *d_totals = pool_get<uint64_t>(ctx, S_SMALL, 4096) + 8;
-    uint8_t *d_side = job.uses_side() ? pool_get<uint8_t>(ctx, S_SIDE, n + 64) : nullptr;
+    uint64_t *d_hist = pool_get<uint64_t>(ctx, S_HIST, job.hist_bytes());
+    uint64_t *d_totals = digit_totals(ctx);
+    void *d_side = job.uses_side() ? pool_get<uint8_t>(ctx, S_SIDE, job.side_bytes()) : nullptr;
     bool side_valid = job.side_done && d_side;                          // d_side holds the digits of the pass about to run
-    const dim3 grid((unsigned)tiles), block(kSortThreads);
     Key<WT> *src = job.a, *dst = job.b;
     for (int i = job.top.P - 1 - (job.first_pass_done ? 1 : 0); i >= 0; --i) {
         const bool first = i == job.top.P - 1;
         const Digit dg = job.top.pass_digit(WT, i), dn = i > 0 ? job.top.pass_digit(WT, i - 1) : Digit{0, 0, 0};
-        if (!(first && job.census_done)) {
-            if (side_valid) {
-                hipLaunchKernelGGL(radix_census_side_kernel, grid, block, 0, stream, d_side, n, tiles, d_hist);
-                if (job.side_mode >= 2) {                               // (test aid) the same census from the keys must agree
-                    std::vector<uint64_t> h_side(tiles * 256), h_keys(tiles * 256);
-                    MGTA_HIP_CHECK(hipStreamSynchronize(stream));
-                    MGTA_HIP_CHECK(hipMemcpy(h_side.data(), d_hist, tiles * 256 * 8, hipMemcpyDeviceToHost));
-                    hipLaunchKernelGGL((radix_census_kernel<WT>), grid, block, 0, stream, src, n, dg, tiles, d_hist);
-                    MGTA_HIP_CHECK(hipStreamSynchronize(stream));
-                    MGTA_HIP_CHECK(hipMemcpy(h_keys.data(), d_hist, tiles * 256 * 8, hipMemcpyDeviceToHost));
-                    if (h_side != h_keys) { set_error("internal: side-digit census differs from the census of the keys"); return nullptr; }
-                }
-            } else
-                hipLaunchKernelGGL((radix_census_kernel<WT>), grid, block, 0, stream, src, n, dg, tiles, d_hist);
-        }
-        hipLaunchKernelGGL(radix_rowscan_kernel, dim3(256), dim3(1024), 0, stream, d_hist, tiles, d_totals);
-        if (log) log->scatter.emplace_back(stream).start();
         const bool write_side = d_side && i > 0;
-        // (the first pass of the sort orders nothing that was ordered before: its ranks need not be stable)
-        auto launch = [&](auto biased, auto side, auto stable) {
-            hipLaunchKernelGGL((radix_scatter_kernel<WT, decltype(biased)::value, decltype(side)::value, decltype(stable)::value>), grid, block, 0, stream, src, dst, n,
-                               dg, tiles, d_hist, d_totals, decltype(side)::value ? d_side : nullptr, dn);
+        // the kernels of the plan's widths: 8 (next 8 or 9), 9 (next 9, or none: a plan's last pass)
+        const int bits = dg.bits, next = i > 0 ? dn.bits : 8;
+        bool ok = false, known = true;
+        auto run = [&](auto b, auto nb) {
+            ok = global_pass<WT, decltype(b)::value, decltype(nb)::value>(ctx, job, log, src, dst, dg, dn, first, side_valid, write_side, d_side, d_hist, d_totals);
         };
-        auto pick_stable = [&](auto biased, auto side) { first ? launch(biased, side, std::false_type{}) : launch(biased, side, std::true_type{}); };
-        auto pick_side = [&](auto biased) {
-            if constexpr (kSideFits<WT>) {
-                if (write_side) { pick_stable(biased, std::true_type{}); return; }
-            }
-            pick_stable(biased, std::false_type{});
-        };
-        dg.bias ? pick_side(std::true_type{}) : pick_side(std::false_type{});
+        using std::integral_constant;
+        if (bits == 8 && next == 8) run(integral_constant<int, 8>{}, integral_constant<int, 8>{});
+        else if constexpr (kWideFits<WT>) {
+            if (bits == 8 && next == 9) run(integral_constant<int, 8>{}, integral_constant<int, 9>{});
+            else if (bits == 9 && (next == 9 || i == 0)) run(integral_constant<int, 9>{}, integral_constant<int, 9>{});
+            else known = false;
+        } else
+            known = false;
+        if (!known) { set_error("internal: no scatter kernel for a %d-bit digit before a %d-bit one at %d key words", bits, next, WT); return nullptr; }
+        if (!ok) return nullptr;
         side_valid = write_side;
-        if (log) { log->scatter.back().end(); log->S->n_sort_launches++; }
         std::swap(src, dst);
     }
     return src;
@@ -2107,7 +2259,7 @@ static Key<WT> *lds_finish(mgta_ctx *ctx, const SortJob<WT> &job, Key<WT> *src, 
     Digit *d_plan = pool_get<Digit>(ctx, S_PLAN, 64 * sizeof(Digit));
     MGTA_HIP_CHECK(hipMemcpyAsync(d_plan, low.data(), low.size() * sizeof(Digit), hipMemcpyHostToDevice, stream));
     // room behind the stride for the last segment of a tile: ~2.5 average segments, an eighth of the tile at least, half at most
-    const double avg_seg = avg_segment_len(n_items, job.top.P, job.top.frac);
+    const double avg_seg = job.top.avg_segment(n_items);
     uint32_t margin = (uint32_t)std::min<double>(LocalCfg<WT>::kTile / 2, std::max<double>(LocalCfg<WT>::kTile / 8, 2.5 * avg_seg));
     margin = (margin + 63u) & ~63u;
     const uint32_t stride = (uint32_t)LocalCfg<WT>::kTile - margin;
@@ -2358,7 +2510,7 @@ struct Build {                                 // a build of keys of W words: wh
     // every range's count is estimated from that attempt's (its share of the buckets), the plan chosen from the estimate, and the
     // scan counts that plan's first digit per workgroup next to the items (fz_table: [range][digit value][workgroup]).  A pass
     // whose real plan equals the estimated one takes the fused writer; any other the plain route, its histogram unused.
-    struct FusedAhead { bool on = false; int P = 0, skip = 0; uint32_t bias = 0; };
+    struct FusedAhead { bool on = false; TopPlan top; };
     FusedAhead fz_plan[kMaxFusedRanges];
     uint64_t *fz_table = nullptr;              // nullptr: the ranges ahead were counted without the digits
     uint64_t wide_items = 0;                   // items and buckets of the last attempt admit_pass refused
@@ -2428,7 +2580,7 @@ struct Build {                                 // a build of keys of W words: wh
         ctx->acc_n_large = 0; ctx->acc_has_large = acc && ctx->keep_multiplicity;   // (the large words stay with a kept stream only on request)
         if (acc) ctx->acc_items.assign(MGTA_NUM_BUCKETS, 0);
         point_scans_at_pool();
-        uint64_t *d_small = pool_get<uint64_t>(ctx, S_SMALL, 4096);   // [0] total, [1] kmers, [2..4] emit totals, [5] sentinels, [8..263] digit totals
+        uint64_t *d_small = pool_get<uint64_t>(ctx, S_SMALL, 4096);   // [0] total, [1] kmers, [2..4] emit totals, [5] sentinels (the digit totals of the sort: S_DIGIT_TOTALS)
         d_total = d_small; d_kmers = d_small + 1; d_tot3 = d_small + 2; d_sentinel = d_small + 5;
         sa.packed = rd->d_packed; sa.n_words = rd->n_words; sa.start = rd->d_start; sa.n_reads = rd->n_reads; sa.k = k; sa.n_short = n_short;
         sa.n_kmers = (unsigned long long *)d_kmers; sa.n_sentinel = (unsigned long long *)d_sentinel;
@@ -2503,6 +2655,13 @@ struct Build {                                 // a build of keys of W words: wh
     }
 
     int max_top() const { return (2 * k + 4 + 7) / 8 > 1 ? std::min(4, (32 * W - 8) / 8) : 0; }
+    // the global passes of a sort of n_items keys of the buckets [b_lo, b_hi)
+    TopPlan top_plan(uint64_t n_items, uint32_t b_lo, uint32_t b_hi) const {
+        const double frac = (double)(b_hi - b_lo) / MGTA_NUM_BUCKETS;
+        const TopPlan tp = choose_top_plan(ctx, n_items, max_top(), frac, b_lo, b_hi, modes.bias);
+        if (!kWideFits<W> || ctx->force_full_lsd) return tp;
+        return widen_top_plan(tp, n_items, max_top(), frac, b_lo, b_hi, modes.bias, modes.wide);
+    }
     uint64_t fused_table_bytes(uint32_t ranges) const { return (uint64_t)ranges * 256 * std::max<uint64_t>(1, n_blocks) * 8; }
 
     // The plan of every range the count scan is about to count (see fz_plan), into the scan's arguments.  False: count without the
@@ -2512,31 +2671,34 @@ struct Build {                                 // a build of keys of W words: wh
         for (FusedAhead &f : fz_plan) f = FusedAhead{};
         if (modes.fused <= 0 || W < 2 || !wide_nb || ranges > (uint32_t)kMaxFusedRanges) return false;
         bool any = false;
+        int max_width = 8;
         uint64_t est_max = 0;
         for (uint32_t g = 0; g < ranges; ++g) {
             const uint32_t lo = b_lo + g * width, hi = std::min<uint32_t>(bucket_end, lo + width);
             const uint64_t est = (uint64_t)((double)wide_items * (double)(hi - lo) / (double)wide_nb);
-            const TopPlan tp = choose_top_plan(ctx, est, max_top(), (double)(hi - lo) / MGTA_NUM_BUCKETS, lo, hi, modes.bias);
+            const TopPlan tp = top_plan(est, lo, hi);
             est_max = std::max(est_max, est);
+            max_width = std::max(max_width, tp.max_width());
             sm.fz_bias[g] = 0; sm.fz_shift[g] = 0;
             if (tp.P < 1 || tp.T() > 32) continue;
-            fz_plan[g] = FusedAhead{true, tp.P, tp.skip, tp.bias};
+            fz_plan[g] = FusedAhead{true, tp};
             sm.fz_bias[g] = tp.bias; sm.fz_shift[g] = (uint32_t)(32 - tp.T());
             any = true;
         }
         if (!any) return false;
         uint64_t key_b = 0;
-        const uint64_t need = pass_need(est_max, &key_b) + fused_table_bytes(ranges);
+        const uint64_t need = pass_need(est_max, &key_b, max_width) + fused_table_bytes(ranges);
         return need + need / 8 <= avail_bytes();
     }
 
     // device bytes of a pass of n_items (two key buffers, the second doubles as emit scratch, + census + outputs (estimate))
-    uint64_t pass_need(uint64_t n_items, uint64_t *key_b) const {
+    // max_width: of the global passes' digits (side entries of 2 bytes and a census row per value of a digit wider than 8 bits)
+    uint64_t pass_need(uint64_t n_items, uint64_t *key_b, int max_width) const {
         const uint64_t n_tiles = (n_items + kBlockTile - 1) / kBlockTile;
         // either key buffer may end up as the emitter's scratch (11 bytes per key: run start u64, record u16, info u8), whichever
         // the last sort pass leaves idle: both hold >= 12 bytes per key
         *key_b = std::max<uint64_t>(n_items * sizeof(Key<W>), n_items * 12) + 4096;
-        return 2 * *key_b + n_tiles * 256 * 8 + n_items * 2 + n_items /* side digits */ + (8u << 20);
+        return 2 * *key_b + n_tiles * ((uint64_t)8 << max_width) + n_items * 2 + n_items * (max_width > 8 ? 2 : 1) /* side digits */ + (8u << 20);
     }
     uint64_t avail_bytes() const {
         uint64_t other = ctx->live_bytes - pool_bytes(ctx);
@@ -2554,7 +2716,7 @@ struct Build {                                 // a build of keys of W words: wh
     // the table goes and the ranges it covered take the plain route.
     int admit_pass(Pass &p, int n_pass) {
         p.n_tiles = (p.n_items + kBlockTile - 1) / kBlockTile;
-        uint64_t need = pass_need(p.n_items, &p.key_b);
+        uint64_t need = pass_need(p.n_items, &p.key_b, top_plan(p.n_items, p.b_lo, p.b_hi).max_width());
         const uint64_t avail = avail_bytes();
         if ((int)ctx->pool.size() > S_FUSED_HIST && ctx->pool[S_FUSED_HIST].bytes) {
             const uint64_t with = need + ctx->pool[S_FUSED_HIST].bytes;
@@ -2568,7 +2730,7 @@ struct Build {                                 // a build of keys of W words: wh
 
     // the one plan of the pass's sort, for the key writer and the sort
     SortJob<W> plan_sort(const Pass &p, Key<W> *a, Key<W> *b) const {
-        SortJob<W> job{a, b, p.n_items, choose_top_plan(ctx, p.n_items, max_top(), (double)p.nb() / MGTA_NUM_BUCKETS, p.b_lo, p.b_hi, modes.bias)};
+        SortJob<W> job{a, b, p.n_items, top_plan(p.n_items, p.b_lo, p.b_hi)};
         job.low = low_digit_plan(k, W, job.top.T());
         job.side_mode = modes.side;
         // closed form + at least one global sort pass: the key writer works tile by tile of that pass and leaves its census behind;
@@ -2581,7 +2743,7 @@ struct Build {                                 // a build of keys of W words: wh
             const uint32_t g = (p.b_lo - multi_lo) / p.width;
             if (g < multi_n && g < (uint32_t)kMaxFusedRanges) {
                 const FusedAhead &f = fz_plan[g];
-                job.first_pass_done = f.on && job.top.P >= 1 && f.P == job.top.P && f.skip == job.top.skip && f.bias == job.top.bias;
+                job.first_pass_done = f.on && job.top.P >= 1 && f.top.same_digits(job.top);
             }
         }
         return job;
@@ -2594,7 +2756,7 @@ struct Build {                                 // a build of keys of W words: wh
         if (p.closed_form) MGTA_HIP_CHECK(hipMemsetAsync(d_sentinel, 0, 8, stream));
         const int shift = 32 - job.top.T();    // of the first global pass's digit in key word 0
         if (job.census_done) {
-            uint64_t *d_hist = pool_get<uint64_t>(ctx, S_HIST, std::max<uint64_t>(1, p.n_tiles) * 256 * 8);   // the buffer the sort uses
+            uint64_t *d_hist = pool_get<uint64_t>(ctx, S_HIST, job.hist_bytes());   // the buffer the sort uses
             hipLaunchKernelGGL((item_write_tiled_kernel<W>), dim3((unsigned)p.n_tiles), dim3(kScanBlock), 0, stream, sa, n_blocks, p.n_items,
                                shift, p.n_tiles, d_hist);
         } else if (p.closed_form)
@@ -2602,14 +2764,15 @@ struct Build {                                 // a build of keys of W words: wh
         else if (job.first_pass_done) {
             // the range's table -> row offsets and digit totals, as for a scatter whose tiles are the scan's workgroups
             uint64_t *tab = fz_table + (uint64_t)((p.b_lo - multi_lo) / p.width) * 256 * n_blocks;
-            uint64_t *d_totals = pool_get<uint64_t>(ctx, S_SMALL, 4096) + 8;
+            uint64_t *d_totals = digit_totals(ctx);
             hipLaunchKernelGGL(radix_rowscan_kernel, dim3(256), dim3(1024), 0, stream, tab, n_blocks, d_totals);
             sa.fz_hist = tab; sa.fz_totals = d_totals; sa.fz_n = p.n_items;
             sa.fz_bias[0] = job.top.bias; sa.fz_shift[0] = (uint32_t)shift;
-            if (job.side_done) {               // the digit of the pass that now runs first: the byte above
-                sa.side = pool_get<uint8_t>(ctx, S_SIDE, p.n_items + 64);
+            if (job.side_done) {               // the digit of the pass that now runs first: the 8 to 10 bits above
+                sa.side = pool_get<uint8_t>(ctx, S_SIDE, job.side_bytes());
                 sa.side_shift = shift + 8;
                 sa.side_bias = job.top.bias;
+                sa.side_bits = job.top.P >= 2 ? job.top.width[job.top.P - 2] : 8;
             }
             if constexpr (W >= 2)
                 hipLaunchKernelGGL((item_write_fused_kernel<W>), dim3((unsigned)n_blocks), dim3(kScanBlock), 0, stream, sa);
@@ -2627,9 +2790,10 @@ struct Build {                                 // a build of keys of W words: wh
             }
         } else {
             if (job.side_done) {
-                sa.side = pool_get<uint8_t>(ctx, S_SIDE, p.n_items + 64);
+                sa.side = pool_get<uint8_t>(ctx, S_SIDE, job.side_bytes());
                 sa.side_shift = shift;
                 sa.side_bias = job.top.bias;
+                sa.side_bits = 8;
             }
             hipLaunchKernelGGL((item_scan_kernel<W, true>), dim3((unsigned)n_blocks), dim3(kScanBlock), 0, stream, sa);
             sa.side = nullptr;
@@ -2885,6 +3049,23 @@ int mgta_sort_plan(uint64_t n_items, int words_per_key, uint32_t bucket_begin, u
                                        bucket_begin, bucket_end, SortModes::from_env().bias);
     *n_passes = tp.P;
     *skip_bits = tp.skip;
+    return MGTA_OK;
+}
+
+int mgta_sort_plan_wide(uint64_t n_items, int words_per_key, uint32_t bucket_begin, uint32_t bucket_end, int *n_passes, int *skip_bits, int *widths) {
+    if (!n_passes || !skip_bits || !widths || words_per_key < 2 || bucket_end > (uint32_t)MGTA_NUM_BUCKETS || bucket_begin >= bucket_end) {
+        set_error("mgta_sort_plan_wide: bad argument");
+        return MGTA_EINVAL;
+    }
+    const SortModes modes = SortModes::from_env();
+    const int max_top = std::min(4, (32 * words_per_key - 8) / 8);
+    const double frac = (double)(bucket_end - bucket_begin) / MGTA_NUM_BUCKETS;
+    TopPlan tp = choose_top_plan(nullptr, n_items, max_top, frac, bucket_begin, bucket_end, modes.bias);
+    const bool fits = with_key_words(words_per_key, [&](auto w) { return (int)kWideFits<decltype(w)::value>; }) > 0;
+    if (fits) tp = widen_top_plan(tp, n_items, max_top, frac, bucket_begin, bucket_end, modes.bias, modes.wide);
+    *n_passes = tp.P;
+    *skip_bits = tp.skip;
+    for (int i = 0; i < kMaxTop; ++i) widths[i] = i < tp.P ? tp.width[tp.P - 1 - i] : 0;
     return MGTA_OK;
 }
 
