@@ -352,6 +352,66 @@ int mgta_reads_match_contigs(mgta_sdbg *, const mgta_reads *reads, int reads_rev
                              uint32_t *hit_windows /* optional [n_short_reads] */, mgta_match_stats *stats /* optional */);
 
 /* ------------------------------------------------------------------------------------------------
+ * Per-library coverage: how many read windows of every library (sample) lie on the windows of a set of contigs, counted from the
+ * READS.  (The graph's multiplicities are pooled over the read set and, in a multi-k run, include the contigs of the earlier k: they
+ * cannot tell libraries apart.)  Any loaded graph serves: no multiplicities are needed and none are allocated.
+ * Libraries: library s holds the reads [lib_end[s - 1], lib_end[s]) of `reads`, lib_end[-1] = 0; lib_end must not descend (an empty
+ * library is legal) and lib_end[n_libs - 1] <= the reads uploaded; the reads at and behind lib_end[n_libs - 1] (the assist sequences
+ * of a multi-k library) are not scanned.  reads_reversed as in mgta_reads_match_contigs.
+ * Contigs, windows and edge(w) are exactly those of mgta_contig_coverage: only the string as given is looked up, a window with a letter
+ * other than A, C, G, T in either case has no edge, there is no N -> G folding.  With
+ *   share(e)     the number of windows OF THIS CALL whose edge is e, as in mgta_contig_share_coverage (occurrences are counted),
+ *   count(w, s)  the number of windows v of the reads of library s, each read taken as sequenced, with v = w or v = revcomp(w) as
+ *                strings; ONE read window counts once, also when w is its own reverse complement; 0 when w has no edge.  (A read
+ *                window is found by its edge, so the graph has to hold it: every graph built from these reads holds both strands of
+ *                all their windows.  The validity bit of an edge is not looked at.)
+ *   mass[i * n_libs + s] = the sum over the windows p of contig i of floor(count(w_ip, s) * 65536 / share(edge(w_ip))), Q16.
+ * Counts are 64-bit; there is no cap.  per_contig (may be NULL): len, n_windows as in mgta_contig_cov; n_covered = windows with
+ * count > 0 in at least one library; n_unique, max_share over those as in mgta_contig_share; mass = the sum of the contig's masses
+ * over the libraries.  per_window_count (may be NULL): count(w, s) window-major in the window order of mgta_contig_coverage's
+ * per_window, the library index minor.  per_window_share (may be NULL): share(edge(w)), 0 = no edge.  lib_hit_windows (may be NULL):
+ * per library, the read windows that were credited to at least one key.
+ * Consequences.  On a `-m 1` graph of exactly these reads the sum of count(w, s) over the libraries is the uncapped multiplicity of
+ * edge(w) (twice that where w is its own reverse complement: the graph counts such a read window on both strands), and wherever the
+ * multiplicity is below 65535 one library over all reads gives mass[i] = mgta_contig_share_coverage's mass bit for bit.  In general
+ * the sum of mass[i][s] over s differs from the pooled mass by less than n_libs units per covered window.
+ * Every output and every stats field but ms_* and n_batches is a function of (graph, reads, lib_end, contigs): neither
+ * mgta_ctx_set_coverage_batch nor mgta_ctx_set_share_hash_bits nor the order of the reads inside a library moves any of them.  Uses
+ * the graph's mark bits, cleared at the start of the call.  Limits: 1 <= n_libs <= 256, n < 2^31 contigs, fewer than 2^32 windows in
+ * the call, k + 1 <= 128; beyond any the call returns MGTA_EINVAL, names the limit and writes nothing.  MGTA_EINVAL too for a NULL
+ * graph, reads, lib_end or mass and for a graph and reads of different contexts.  Device memory: 16 bytes per window of a batch (the
+ * edge ids of both strands), 8 bytes per window of the call (two slot numbers), 16 bytes per table slot (2 to 4 slots per key; the
+ * keys are the distinct edges of both strands) and 8 * n_libs bytes per key, accounted like every other buffer of the context; what
+ * does not fit is MGTA_ENOMEM, nothing is truncated.  n = 0: MGTA_OK, stats all zero.
+ * ------------------------------------------------------------------------------------------------ */
+typedef struct mgta_sample_cov_stats {
+    int64_t n_contigs, n_windows;
+    int64_t n_walked, n_index_searches;   /* contig windows of BOTH strands found by one forward step / by IndexBinarySearchEdge */
+    int64_t n_batches;
+    int64_t n_covered;               /* covered windows of the call */
+    int64_t n_keys;                  /* distinct edges of the contig windows, both strands */
+    int64_t n_libs;
+    int64_t n_reads, n_read_windows; /* reads scanned = lib_end[n_libs - 1]; sum max(0, len - k) over them */
+    int64_t n_read_walked, n_read_index_searches;
+    int64_t n_hit_windows;           /* read windows credited to a key = the sum of lib_hit_windows */
+    int64_t groups_per_cu;           /* as in mgta_coverage_stats, for the read scan */
+    uint64_t total_mass;             /* sum of per_contig[i].mass */
+    uint64_t table_slots;            /* slots of the key table */
+    uint64_t table_bytes;            /* its bytes (key, share and key number per slot) */
+    uint64_t window_bytes;           /* the two slot numbers of every window */
+    uint64_t count_bytes;            /* the rows of counts: (n_keys + 1) * n_libs * 8 */
+    double ms_mark;                  /* contig walks, table and key numbers (HIP events) */
+    double ms_scan;                  /* the read scan */
+    double ms_mass;                  /* counts -> masses and per-contig records */
+    double ms_total;                 /* the three together */
+} mgta_sample_cov_stats;
+int mgta_contig_sample_coverage(mgta_sdbg *, const mgta_reads *reads, int reads_reversed, const uint64_t *lib_end /* [n_libs] */, int n_libs,
+                                const char *seqs, const uint64_t *offsets /* [n + 1] */, int64_t n, uint64_t *mass /* [n * n_libs], Q16 */,
+                                mgta_contig_share *per_contig /* optional [n] */, uint64_t *per_window_count /* optional [windows * n_libs] */,
+                                uint32_t *per_window_share /* optional [windows] */, uint64_t *lib_hit_windows /* optional [n_libs] */,
+                                mgta_sample_cov_stats *stats /* optional */);
+
+/* ------------------------------------------------------------------------------------------------
  * De-replication ("get the unique merged contigs", the first step of the reference's bin/post_proc.sh:50-55: `Clustering.jar derep`,
  * then `ReadSeq.jar rm-dupseq -d`, both from a submodule the reference does not ship).  Needs no graph.  Sequence i =
  * seqs[offsets[i] .. offsets[i + 1]), a byte string compared byte for byte: no case folding, no reverse complement (a gene's contigs

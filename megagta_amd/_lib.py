@@ -105,6 +105,17 @@ class MatchStats(C.Structure):
         return {n: getattr(self, n) for n, _ in self._fields_}
 
 
+class SampleCovStats(C.Structure):
+    _fields_ = [("n_contigs", C.c_int64), ("n_windows", C.c_int64), ("n_walked", C.c_int64), ("n_index_searches", C.c_int64), ("n_batches", C.c_int64),
+                ("n_covered", C.c_int64), ("n_keys", C.c_int64), ("n_libs", C.c_int64), ("n_reads", C.c_int64), ("n_read_windows", C.c_int64),
+                ("n_read_walked", C.c_int64), ("n_read_index_searches", C.c_int64), ("n_hit_windows", C.c_int64), ("groups_per_cu", C.c_int64),
+                ("total_mass", C.c_uint64), ("table_slots", C.c_uint64), ("table_bytes", C.c_uint64), ("window_bytes", C.c_uint64),
+                ("count_bytes", C.c_uint64), ("ms_mark", C.c_double), ("ms_scan", C.c_double), ("ms_mass", C.c_double), ("ms_total", C.c_double)]
+
+    def as_dict(self):
+        return {n: getattr(self, n) for n, _ in self._fields_}
+
+
 class DerepStats(C.Structure):
     _fields_ = [("n_seqs", C.c_int64), ("n_letters", C.c_int64), ("n_first", C.c_int64), ("n_duplicates", C.c_int64), ("n_contained", C.c_int64),
                 ("n_kept", C.c_int64), ("n_windows", C.c_int64), ("anchor_len", C.c_int64), ("n_compares", C.c_int64), ("ms_dups", C.c_double),
@@ -232,6 +243,8 @@ SYMBOLS = {
     "mgta_ctx_set_share_hash_bits": (C.c_int, [C.c_void_p, C.c_int]),
     "mgta_reads_match_contigs": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_uint64, C.c_char_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p,
                                           C.c_void_p]),
+    "mgta_contig_sample_coverage": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_char_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p,
+                                             C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "mgta_seqs_derep": (C.c_int, [C.c_void_p, C.c_char_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "mgta_ctx_set_derep_hash_bits": (C.c_int, [C.c_void_p, C.c_int]),
     "mgta_seqs_align": (C.c_int, [C.c_void_p, C.c_void_p, C.c_char_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),

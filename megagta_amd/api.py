@@ -538,6 +538,41 @@ class Graph:
         bits = np.unpackbits(words.view(np.uint8), bitorder="little")[:ns].astype(bool)
         return dict(bits=bits, hit_windows=hits, stats=st.as_dict())
 
+    def contig_sample_coverage(self, reads: "Reads", lib_end, seqs, per_window: bool = False, reads_reversed: bool = True) -> dict:
+        """mgta_contig_sample_coverage: the read windows of every library on the windows of the contigs `seqs` (str or bytes, any case),
+        counted from the reads on either strand and split among the windows of THIS call on one edge.  Library s holds the reads
+        [lib_end[s - 1], lib_end[s]) of `reads`; what lies behind lib_end[-1] is not scanned.  -> dict(mass = uint64[n, n_libs] (Q16),
+        contigs = structured array as of contig_share_coverage (mass = the sum over the libraries), lib_hit_windows = uint64[n_libs],
+        stats, and with per_window=True per_window_count = uint64[windows, n_libs], per_window_share = uint32[windows] (0 = no edge) +
+        window_offsets int64[n + 1]).  Any loaded graph will do; one call = one set of contigs."""
+        raw = [s if isinstance(s, (bytes, bytearray)) else str(s).encode() for s in seqs]
+        n = len(raw)
+        offsets = np.zeros(n + 1, dtype=np.uint64)
+        if n:
+            np.cumsum([len(s) for s in raw], out=offsets[1:])
+        ends = np.ascontiguousarray(lib_end, dtype=np.uint64)
+        if ends.ndim != 1:
+            raise ValueError("lib_end is a list of read numbers")
+        nl = int(ends.size)
+        rec = np.zeros(n, dtype=SHARE_DTYPE)
+        nw = np.maximum(0, np.diff(offsets.astype(np.int64)) - self.ctx._L.mgta_sdbg_k(self.h))      # (the graph's own k sizes the buffers)
+        woff = np.zeros(n + 1, dtype=np.int64)
+        np.cumsum(nw, out=woff[1:])
+        mass = np.zeros((n, nl), dtype=np.uint64)
+        hits = np.zeros(max(1, nl), dtype=np.uint64)
+        pwc = np.zeros((int(woff[-1]), nl), dtype=np.uint64) if per_window else None
+        pws = np.zeros(int(woff[-1]), dtype=np.uint32) if per_window else None
+        keep = np.zeros(1, dtype=np.uint64)                                    # (never a NULL mass for n = 0: NULL is an error of its own)
+        st = _lib.SampleCovStats()
+        check(self.ctx._L.mgta_contig_sample_coverage(self.h, reads.h, int(bool(reads_reversed)), ends.ctypes.data if nl else None, nl, b"".join(raw),
+                                                      offsets.ctypes.data, n, mass.ctypes.data if mass.size else keep.ctypes.data, rec.ctypes.data if n else None,
+                                                      pwc.ctypes.data if per_window and pwc.size else None, pws.ctypes.data if per_window and pws.size else None,
+                                                      hits.ctypes.data, C.byref(st)), "mgta_contig_sample_coverage")
+        out = dict(mass=mass, contigs=rec, lib_hit_windows=hits[:nl], stats=st.as_dict(), per_window_count=pwc, per_window_share=pws)
+        if per_window:
+            out["window_offsets"] = woff
+        return out
+
     def denovo(self, max_tip_len: int = 150, no_bubble: bool = False, min_contig: int = 0) -> tuple[str, dict]:
         """`megagta denovo` (main_assemble, assembler.cpp:98-167): tips, bubbles, unitigs -> (text of PREFIX.contigs.fa, stats).
         The result is the reference's one-thread output.  CONSUMES the validity bits of this graph."""

@@ -1,7 +1,8 @@
 // coverage.hip — per-contig k-mer coverage and abundance from the resident graph, the batched EdgeMultiplicity query, and read
 // recruitment (the reads that share a (k+1)-mer with a set of contigs: the same walk, over reads; further down), and the
 // window-shared coverage (every edge's multiplicity split among the windows of the call that land on it: the same walk, once, then
-// a count per distinct edge; at the end).
+// a count per distinct edge), and the per-library coverage (the read windows of every library on the windows of a set of contigs: the
+// read walk again, with a count per key and library; at the end).
 //
 // The reference's last post-processing step (`kmer_coverage`, bin/post_proc.sh:113-118) counts the (k+1)-mers of the contigs in a
 // second pass over all reads.  That count is the multiplicity the edge stream already carries (sdbg_multi_io.h:83-112) and a graph
@@ -573,6 +574,285 @@ __global__ __launch_bounds__(256) void share_mass_kernel(const uint64_t *woff, c
     if (lane == 0) out[i] = res;
 }
 
+// ---- per-library coverage (mgta_contig_sample_coverage): the read windows of every library on the windows of a set of contigs --------
+// The multiplicities of the graph are pooled over the read set, so this count comes from the reads.  Four phases.
+// (1) share_walk_kernel over BOTH strands of every contig of a batch (the reverse complements lie mirrored behind the symbols, as for
+// the read recruitment), then the edge ids go into an open-addressing table keyed by the edge id: 8 bytes of key, the share (the
+// windows AS GIVEN on the key; a reverse-complement window adds 0) and, later, the key's dense number.  The lane that makes a key
+// turns the edge's mark bit on.  Every window keeps two slot numbers for the whole call: that of its own edge and that of the edge
+// of its reverse complement (0 = none).  (2) When all batches are in, the keys are numbered 1 .. n_keys and a row of n_libs 64-bit
+// counts per key is zeroed (row 0 stays zero: "no edge").  (3) The read scan: match_walk_kernel's walk with count_all; a window whose
+// edge is marked probes the table and adds 1 to counts[key][library] -- ONE add per read window, so a window that is its own reverse
+// complement (one key, two equal slot numbers) is counted once.  (4) count(w, s) = counts[own][s] + counts[partner][s] where the two
+// rows differ, divided by the share: one wave per contig.
+//
+// A read that occurs hundreds of times sits side by side in the read queue, so the 8 groups of a wave walk copies in step and hit the
+// same (key, library) together: the group leaders with equal addresses elect the lowest lane, which adds their number.
+
+struct SampleTable {
+    unsigned long long *keys;
+    uint32_t *share, *dense;
+    uint64_t n_slots, hmask;
+};
+
+// `times` as-given occurrences of edge e (0 for a reverse-complement window) -> its slot; 0 and *full = 1 when the table has no room
+__device__ __forceinline__ uint32_t sample_table_add(const SampleTable &t, int64_t e, uint32_t times, uint32_t *marks, uint32_t &n_new, unsigned long long *full) {
+    uint64_t slot = mix64_share((uint64_t)e) & t.hmask & (t.n_slots - 1);
+    if (slot == 0) slot = 1;
+    for (uint64_t tries = 0; tries < t.n_slots; ++tries) {
+        unsigned long long key = __hip_atomic_load(&t.keys[slot], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        if (key == kShareEmpty) {
+            key = atomicCAS(&t.keys[slot], kShareEmpty, (unsigned long long)e);
+            if (key == kShareEmpty) {                                     // this lane made the key: the read scan looks at marked edges only
+                atomicOr(&marks[e >> 5], 1u << (e & 31));
+                ++n_new;
+                key = (unsigned long long)e;
+            }
+        }
+        if (key == (unsigned long long)e) {
+            if (times) atomicAdd(&t.share[slot], times);
+            return (uint32_t)slot;
+        }
+        slot = (slot + 1) & (t.n_slots - 1);
+        if (slot == 0) slot = 1;
+    }
+    atomicExch(full, 1ull);
+    return 0;
+}
+
+// the slot of edge e, 0 when it is no key (the table is final and at most half full: an empty slot ends every probe)
+__device__ __forceinline__ uint32_t sample_table_find(const SampleTable &t, int64_t e) {
+    uint64_t slot = mix64_share((uint64_t)e) & t.hmask & (t.n_slots - 1);
+    if (slot == 0) slot = 1;
+    for (uint64_t tries = 0; tries < t.n_slots; ++tries) {
+        const unsigned long long key = t.keys[slot];
+        if (key == (unsigned long long)e) return (uint32_t)slot;
+        if (key == kShareEmpty) return 0;
+        slot = (slot + 1) & (t.n_slots - 1);
+        if (slot == 0) slot = 1;
+    }
+    return 0;
+}
+
+// share_count_kernel's shape over the jobs of both strands (job.idx = 2 * contig + strand; the ids of a reverse-complement job lie
+// n_win_batch behind those of its contig, its window p is window n_win - 1 - p of the contig).
+// counters: [3] keys made, [5] set when the table ran full
+__global__ __launch_bounds__(256) void sample_count_kernel(SampleTable t, const CovJob *jobs, uint32_t n_jobs, int k, const int64_t *ids, uint64_t n_win_batch,
+                                                           uint64_t win_done, uint32_t *slots_own, uint32_t *slots_rc, uint32_t *marks, unsigned long long *counters) {
+    const int lane = lane_id();
+    const uint32_t j = blockIdx.x * 64 + (uint32_t)lane;
+    uint32_t n_win = 0;
+    uint64_t base = 0;
+    bool rc = false;
+    if (j < n_jobs) {
+        const CovJob job = jobs[j];
+        n_win = job.len > (uint32_t)k ? job.len - (uint32_t)k : 0;
+        base = job.win_base;
+        rc = job.idx & 1u;
+    }
+    const uint64_t longest = wave_max(n_win);
+    const uint64_t given = __ballot(!rc);
+    uint32_t n_new = 0;
+    for (uint64_t p0 = ((uint64_t)blockIdx.y * 4 + (uint64_t)wave_id()) * 64; p0 < longest; p0 += (uint64_t)gridDim.y * 256) {
+        const uint64_t p1 = min(longest, p0 + 64);
+        for (uint64_t p = p0; p < p1; ++p) {
+            const bool in = p < n_win;
+            const int64_t e = in ? ids[base + p] : -1;
+            int leader = lane;
+            uint32_t times = rc ? 0u : 1u;
+            uint64_t todo = __ballot(e >= 0);
+            while (todo) {                                                // one turn per distinct id among the 64
+                const int src = __ffsll((long long)todo) - 1;
+                const int64_t e0 = wave_read64(e, src);
+                const uint64_t same = __ballot(e == e0);
+                if (e == e0) { leader = src; times = (uint32_t)__popcll(same & given); }
+                todo &= ~same;
+            }
+            uint32_t slot = 0;
+            if (e >= 0 && leader == lane) slot = sample_table_add(t, e, times, marks, n_new, &counters[5]);
+            slot = __shfl(slot, leader, 64);
+            if (in) {
+                if (rc) slots_rc[win_done + (base - n_win_batch) + ((uint64_t)n_win - 1 - p)] = slot;
+                else slots_own[win_done + base + p] = slot;
+            }
+        }
+    }
+    n_new = wave_sum(n_new);
+    if (lane == 0 && n_new) atomicAdd(&counters[3], (unsigned long long)n_new);
+}
+
+// the keys get the numbers 1 .. n_keys (the order is the table's, which no output depends on); n_slots is a multiple of 1024
+// counters: [6] keys numbered so far
+__global__ __launch_bounds__(256) void sample_dense_kernel(SampleTable t, unsigned long long *counters) {
+    const int lane = lane_id();
+    const uint64_t stride = (uint64_t)gridDim.x * 256;
+    for (uint64_t i = (uint64_t)blockIdx.x * 256 + threadIdx.x; i < t.n_slots; i += stride) {
+        const bool used = t.keys[i] != kShareEmpty;
+        const uint64_t m = __ballot(used);
+        unsigned long long first = 0;
+        if (lane == 0 && m) first = atomicAdd(&counters[6], (unsigned long long)__popcll(m));
+        first = wave_uniform((uint64_t)first);
+        t.dense[i] = used ? (uint32_t)(first + (uint64_t)__popcll(m & lanemask_lt()) + 1) : 0u;
+    }
+}
+
+constexpr int kSampleMaxLibs = 256;
+
+// match_walk_kernel's walk over the reads [0, n_reads), every window counted.  Read r belongs to the library s with
+// lib_end[s - 1] <= r < lib_end[s]; the boundaries sit in LDS, s is found by bisection for the first read of a queue chunk and moves
+// on with the reads of the chunk (a boundary may fall anywhere inside it, and empty libraries are stepped over).
+// counters: [0] queue head, [1] windows found by a step, [2] index searches, [3] hit windows, [4] read windows
+__global__ __launch_bounds__(kCovThreads) void sample_scan_kernel(GraphDev g, const uint32_t *packed, const uint64_t *start, uint64_t n_reads, int reversed, uint32_t chunk,
+                                                                  const uint32_t *marks, SampleTable t, unsigned long long *counts, const uint64_t *lib_end, int n_libs,
+                                                                  unsigned long long *lib_hits, unsigned long long *counters) {
+    __shared__ uint8_t s_seq[kCovThreads / 8][kMatchMaxWindow];
+    __shared__ uint64_t s_end[kSampleMaxLibs];
+    __shared__ unsigned long long s_hits[kSampleMaxLibs];
+    for (int i = threadIdx.x; i < n_libs; i += kCovThreads) { s_end[i] = lib_end[i]; s_hits[i] = 0; }
+    __syncthreads();
+    const int sub = threadIdx.x & 7, lane = lane_id();
+    const int k = g.k;
+    uint8_t *seq = s_seq[threadIdx.x >> 3];
+    const uint32_t flip = reversed ? 3u : 0u;                             // base b -> symbol (b ^ flip) + 1: the complement when stored reversed
+    uint32_t walked = 0, searched = 0;
+    unsigned long long windows = 0, all_hits = 0;
+    for (;;) {
+        unsigned long long first = 0;
+        if (sub == 0) first = atomicAdd(&counters[0], (unsigned long long)chunk);
+        first = __shfl(first, 0, 8);
+        if (first >= n_reads) break;
+        const uint64_t r_end = min((unsigned long long)n_reads, first + chunk);
+        int s = 0;
+        for (int hi = n_libs - 1; s < hi;) {                              // the first library that ends behind read `first` (first < n_reads = the last end)
+            const int mid = (s + hi) >> 1;
+            if (s_end[mid] > first) hi = mid; else s = mid + 1;
+        }
+        for (uint64_t r = first; r < r_end; ++r) {
+            while (s + 1 < n_libs && s_end[s] <= r) ++s;
+            const uint64_t s0 = start[r], len = start[r + 1] - s0;
+            const uint64_t n_win = len > (uint64_t)k ? len - (uint64_t)k : 0;
+            windows += n_win;
+            int64_t e = -1;                                               // the edge of the window before, -1 = the walk has to start again
+            LineR L{};
+            uint32_t hits = 0, w = 0;
+            for (uint64_t p = 0; p < n_win; ++p) {
+                const uint64_t q = s0 + p + (uint64_t)k;                  // the window's last base
+                if (p == 0 || (q & 15) == 0) w = packed[q >> 4];
+                const int c = (int)(((w >> (30 - 2 * (int)(q & 15))) & 3u) ^ flip) + 1;
+                if (e >= 0) {
+                    e = cov_step(g, L, e, c, sub);
+                    if (e >= 0) ++walked;
+                } else {
+                    // every lane writes all k + 1 symbols itself and reads back only what it wrote (the same values in every lane of the group)
+                    for (int i = 0; i <= k; ++i) {
+                        const uint64_t qi = s0 + p + (uint64_t)i;
+                        seq[i] = (uint8_t)((((packed[qi >> 4] >> (30 - 2 * (int)(qi & 15))) & 3u) ^ flip) + 1);
+                    }
+                    e = g_index_edge(g, seq);
+                    ++searched;
+                    if (e >= 0) L = grp_load_line(g, (uint64_t)e >> 6, sub);
+                }
+                if (e >= 0 && ((marks[e >> 5] >> (e & 31)) & 1u)) {       // the one-bit filter in front of the table
+                    ++hits;
+                    if (sub == 0) {
+                        const uint32_t slot = sample_table_find(t, e);
+                        const int64_t at = slot ? (int64_t)((uint64_t)t.dense[slot] * (uint64_t)n_libs + (uint64_t)s) : -1;
+                        // the group leaders that are here together: equal addresses elect the lowest lane
+                        int leader = lane;
+                        uint32_t times = 1;
+                        uint64_t todo = __ballot(1);
+                        while (todo) {
+                            const int src = __ffsll((long long)todo) - 1;
+                            const int64_t a0 = wave_read64(at, src);
+                            const uint64_t same = __ballot(at == a0);
+                            if (at == a0) { leader = src; times = (uint32_t)__popcll(same); }
+                            todo &= ~same;
+                        }
+                        if (leader == lane && at >= 0) atomicAdd(&counts[at], (unsigned long long)times);
+                    }
+                }
+            }
+            if (sub == 0 && hits) {
+                atomicAdd(&s_hits[s], (unsigned long long)hits);
+                all_hits += hits;
+            }
+        }
+    }
+    __syncthreads();
+    for (int i = threadIdx.x; i < n_libs; i += kCovThreads)
+        if (s_hits[i]) atomicAdd(&lib_hits[i], s_hits[i]);
+    const uint32_t wk = wave_sum(sub == 0 ? walked : 0u), sc = wave_sum(sub == 0 ? searched : 0u);
+    const uint64_t wn = wave_sum64(sub == 0 ? windows : 0ull), ht = wave_sum64(all_hits);
+    if (lane == 0) {
+        if (wk) atomicAdd(&counters[1], (unsigned long long)wk);
+        if (sc) atomicAdd(&counters[2], (unsigned long long)sc);
+        if (ht) atomicAdd(&counters[3], (unsigned long long)ht);
+        if (wn) atomicAdd(&counters[4], (unsigned long long)wn);
+    }
+}
+
+// floor(c * 65536 / share) without a 128-bit product: c = q * share + r gives q * 65536 + floor(r * 65536 / share), and r < 2^32
+__device__ __forceinline__ uint64_t sample_q16(uint64_t c, uint32_t share) {
+    if (c < (1ull << 48)) return (c << 16) / share;
+    const uint64_t q = c / share, r = c % share;
+    return (q << 16) + (r << 16) / share;
+}
+
+// One wave per contig, a lane per window, the libraries inside: per window two slot numbers -> two rows of counts, per library one
+// gather from each row and one division.  The per-library sums are kept in LDS (n_libs 64-bit words per wave); lane l starts at
+// library l mod n_libs, so the lanes of one add are on different words wherever n_libs allows.  Integer sums: no order matters.
+__global__ __launch_bounds__(256) void sample_mass_kernel(const uint64_t *woff, const uint32_t *lens, uint32_t n, const uint32_t *slots_own, const uint32_t *slots_rc,
+                                                          SampleTable t, const unsigned long long *counts, int n_libs, uint64_t *mass_out, mgta_contig_share *out,
+                                                          uint64_t *pw_count, uint32_t *pw_share) {
+    __shared__ unsigned long long s_mass[4][kSampleMaxLibs];
+    const int lane = lane_id();
+    const uint32_t i = blockIdx.x * 4 + (uint32_t)wave_id();
+    if (i >= n) return;                                                   // (whole waves leave; the rest use wave-level ordering only)
+    unsigned long long *acc = s_mass[wave_id()];
+    for (int s = lane; s < n_libs; s += 64) acc[s] = 0;
+    wave_lds_fence();
+    const uint64_t b = woff[i];
+    const uint32_t n_win = (uint32_t)(woff[i + 1] - b);
+    const int s_first = lane % n_libs;
+    uint64_t mass = 0;
+    uint32_t nc = 0, nu = 0, mx = 0;
+    for (uint32_t q = lane; q < n_win; q += 64) {
+        const uint32_t so = slots_own[b + q], sr = slots_rc[b + q];
+        uint32_t share = 0, d_own = 0, d_rc = 0;
+        if (so) {                                                         // a window without an edge counts nothing, whatever its reverse complement finds
+            share = t.share[so];
+            d_own = t.dense[so];
+            d_rc = sr && sr != so ? t.dense[sr] : 0u;                     // its own reverse complement: one row, counted once
+        }
+        const unsigned long long *row_own = counts + (uint64_t)d_own * (uint64_t)n_libs, *row_rc = counts + (uint64_t)d_rc * (uint64_t)n_libs;
+        bool any = false;
+        int s = s_first;
+        for (int j = 0; j < n_libs; ++j) {
+            const uint64_t c = so ? row_own[s] + row_rc[s] : 0ull;
+            if (pw_count) pw_count[(b + q) * (uint64_t)n_libs + (uint64_t)s] = c;
+            if (c) {
+                const uint64_t m = sample_q16(c, share);
+                atomicAdd(&acc[s], (unsigned long long)m);
+                mass += m;
+                any = true;
+            }
+            if (++s == n_libs) s = 0;
+        }
+        if (any) {
+            ++nc;
+            nu += share == 1u;
+            mx = max(mx, share);
+        }
+        if (pw_share) pw_share[b + q] = share;
+    }
+    mgta_contig_share res;
+    res.mass = wave_sum64(mass); res.len = lens[i]; res.n_windows = n_win; res.n_covered = wave_sum(nc); res.n_unique = wave_sum(nu);
+    res.max_share = wave_max(mx); res.reserved_ = 0;
+    if (lane == 0 && out) out[i] = res;
+    wave_lds_fence();
+    for (int s = lane; s < n_libs; s += 64) mass_out[(uint64_t)i * (uint64_t)n_libs + (uint64_t)s] = acc[s];
+}
+
 }  // namespace
 }  // namespace mgta
 
@@ -951,6 +1231,214 @@ int mgta_contig_share_coverage(mgta_sdbg *g, const char *seqs, const uint64_t *o
             stats->n_batches = n_batches; stats->n_covered = (int64_t)covered; stats->n_distinct_edges = (int64_t)cnt[3]; stats->total_mult = cnt[4];
             stats->total_mass = mass; stats->table_slots = n_slots; stats->table_bytes = n_slots * 16; stats->window_bytes = total_win * 4;
             stats->ms_walk = ms_walk; stats->ms_count = ms_count; stats->ms_share = t_share.ms(); stats->ms_total = ms_walk + ms_count + stats->ms_share;
+        }
+        return MGTA_OK;
+    });
+}
+
+int mgta_contig_sample_coverage(mgta_sdbg *g, const mgta_reads *reads, int reads_reversed, const uint64_t *lib_end, int n_libs, const char *seqs, const uint64_t *offsets,
+                                int64_t n, uint64_t *mass, mgta_contig_share *per_contig, uint64_t *per_window_count, uint32_t *per_window_share,
+                                uint64_t *lib_hit_windows, mgta_sample_cov_stats *stats) {
+    if (!g || !reads) { set_error("mgta_contig_sample_coverage: the graph and the reads must not be NULL"); return MGTA_EINVAL; }
+    if (g->ctx != reads->ctx) { set_error("mgta_contig_sample_coverage: the graph and the reads belong to different contexts"); return MGTA_EINVAL; }
+    if (n_libs < 1 || n_libs > kSampleMaxLibs) { set_error("mgta_contig_sample_coverage: n_libs = %d (1 .. %d libraries are supported)", n_libs, kSampleMaxLibs); return MGTA_EINVAL; }
+    if (!lib_end || !mass) { set_error("mgta_contig_sample_coverage: lib_end and mass must not be NULL"); return MGTA_EINVAL; }
+    for (int s = 1; s < n_libs; ++s)
+        if (lib_end[s] < lib_end[s - 1]) { set_error("mgta_contig_sample_coverage: lib_end[%d] < lib_end[%d]: the ends must not descend", s, s - 1); return MGTA_EINVAL; }
+    if (lib_end[n_libs - 1] > reads->n_reads) {
+        set_error("mgta_contig_sample_coverage: lib_end[%d] = %llu, the upload holds %llu reads", n_libs - 1, (unsigned long long)lib_end[n_libs - 1],
+                  (unsigned long long)reads->n_reads);
+        return MGTA_EINVAL;
+    }
+    if (n < 0 || (n > 0 && !offsets)) { set_error("mgta_contig_sample_coverage: bad contig count or offsets"); return MGTA_EINVAL; }
+    if (n > 0x7FFFFFFFll) { set_error("mgta_contig_sample_coverage: %lld contigs (n < 2^31 is supported)", (long long)n); return MGTA_EINVAL; }
+    if (g->dev.k + 1 > kMatchMaxWindow) { set_error("mgta_contig_sample_coverage: k = %d (k + 1 <= %d is supported)", g->dev.k, kMatchMaxWindow); return MGTA_EINVAL; }
+    const uint64_t k = (uint64_t)g->dev.k;
+    uint64_t total_win = 0;
+    for (int64_t i = 0; i < n; ++i) {
+        if (offsets[i + 1] < offsets[i] || offsets[i + 1] - offsets[i] > 0xFFFFFFF0ull || (offsets[i + 1] > offsets[i] && !seqs)) {
+            set_error("mgta_contig_sample_coverage: contig %lld: offsets must ascend, a contig holds < 2^32 letters", (long long)i);
+            return MGTA_EINVAL;
+        }
+        const uint64_t len = offsets[i + 1] - offsets[i];
+        total_win += len > k ? len - k : 0;
+        if (total_win > 0xFFFFFFFFull) {
+            set_error("mgta_contig_sample_coverage: more than 2^32 - 1 windows in the call (a share is a 32-bit count); contig %lld is the first beyond", (long long)i);
+            return MGTA_EINVAL;
+        }
+    }
+    // the table holds the edges of both strands: at most half full, a slot number is 32 bits
+    const uint64_t most_keys = std::min<uint64_t>(2 * total_win, (uint64_t)std::max<int64_t>(g->dev.size, 0));
+    if (2 * most_keys + 2 > (1ull << 32)) {
+        set_error("mgta_contig_sample_coverage: %llu keys need a count table of more than 2^32 slots", (unsigned long long)most_keys);
+        return MGTA_ENOMEM;
+    }
+    const uint64_t L = (uint64_t)n_libs;
+    if (stats) memset(stats, 0, sizeof(*stats));
+    if (lib_hit_windows) memset(lib_hit_windows, 0, L * 8);
+    if (n == 0) return MGTA_OK;
+    return guarded("mgta_contig_sample_coverage", [&]() {
+        mgta_ctx *ctx = g->ctx;
+        MGTA_HIP_CHECK(hipSetDevice(ctx->device));
+        hipStream_t st = ctx->stream;
+        constexpr int kGroups = kCovThreads / 8;
+        Timer t_walk(st), t_count(st), t_scan(st), t_mass(st);
+        const uint64_t cap = ctx->coverage_batch_windows ? ctx->coverage_batch_windows : 1ull << 28;   // windows per batch: 4 GB of edge ids, both strands
+        int walk_per_cu = 0, scan_per_cu = 0;
+        MGTA_HIP_CHECK(hipOccupancyMaxActiveBlocksPerMultiprocessor(&walk_per_cu, share_walk_kernel, kCovThreads, 0));
+        MGTA_HIP_CHECK(hipOccupancyMaxActiveBlocksPerMultiprocessor(&scan_per_cu, sample_scan_kernel, kCovThreads, 0));
+        walk_per_cu = std::max(1, walk_per_cu);
+        scan_per_cu = std::max(1, scan_per_cu);
+        SampleTable tab{nullptr, nullptr, nullptr, 1024, ctx->share_hash_bits >= 64 ? ~0ull : (1ull << ctx->share_hash_bits) - 1};
+        while (tab.n_slots < 2 * most_keys + 2) tab.n_slots <<= 1;
+        // one mark bit per edge, the graph's own, zeroed per call
+        const size_t mark_b = ((size_t)std::max<int64_t>(g->dev.size, 0) / 32 + 2) * 4;
+        if (g->marks.bytes < mark_b) g->marks.alloc(mark_b, &ctx->live_bytes, &ctx->peak_bytes);
+        MGTA_HIP_CHECK(hipMemsetAsync(g->marks.p, 0, mark_b, st));
+        DevBuf d_cnt, d_sym, d_jobs, d_keys, d_share, d_dense, d_own, d_rc, d_counts, d_ends, d_hits, d_woff, d_lens, d_out, d_mass, d_pwc, d_pws;
+        d_cnt.alloc(128);
+        MGTA_HIP_CHECK(hipMemsetAsync(d_cnt.p, 0, 128, st));
+        unsigned long long *cnt_mark = d_cnt.as<unsigned long long>(), *cnt_scan = cnt_mark + 8;
+        d_keys.alloc(tab.n_slots * 8, &ctx->live_bytes, &ctx->peak_bytes);
+        d_share.alloc(tab.n_slots * 4, &ctx->live_bytes, &ctx->peak_bytes);
+        d_dense.alloc(tab.n_slots * 4, &ctx->live_bytes, &ctx->peak_bytes);
+        d_own.alloc(total_win * 4 + 16, &ctx->live_bytes, &ctx->peak_bytes);
+        d_rc.alloc(total_win * 4 + 16, &ctx->live_bytes, &ctx->peak_bytes);
+        tab.keys = d_keys.as<unsigned long long>(); tab.share = d_share.as<uint32_t>(); tab.dense = d_dense.as<uint32_t>();
+        MGTA_HIP_CHECK(hipMemsetAsync(d_keys.p, 0xFF, tab.n_slots * 8, st));
+        MGTA_HIP_CHECK(hipMemsetAsync(d_share.p, 0, tab.n_slots * 4, st));
+        std::vector<CovJob> jobs;
+        uint64_t win_done = 0;
+        double ms_walk = 0, ms_count = 0;
+        int64_t n_batches = 0;
+        for (int64_t c0 = 0; c0 < n;) {
+            // the contigs [c0, c1) of this batch, as mgta_contig_coverage cuts them; every contig is two jobs, idx = 2 * number + strand
+            int64_t c1 = c0;
+            uint64_t n_win = 0;
+            jobs.clear();
+            while (c1 < n) {
+                const uint64_t len = offsets[c1 + 1] - offsets[c1], wn = len > k ? len - k : 0;
+                if (c1 > c0 && n_win + wn > cap) break;
+                jobs.push_back(CovJob{offsets[c1] - offsets[c0], n_win, (uint32_t)len, (uint32_t)(c1 - c0) * 2u});
+                n_win += wn;
+                ++c1;
+            }
+            const uint64_t n_bytes = offsets[c1] - offsets[c0];
+            const size_t n_given = jobs.size();
+            for (size_t j = 0; j < n_given; ++j) {                        // the reverse complement of [a, a + len) lies at [2 n_bytes - a - len, 2 n_bytes - a)
+                const CovJob f = jobs[j];
+                jobs.push_back(CovJob{2 * n_bytes - f.off - f.len, n_win + f.win_base, f.len, f.idx + 1u});
+            }
+            const uint32_t nj = (uint32_t)jobs.size();
+            std::sort(jobs.begin(), jobs.end(), [](const CovJob &a, const CovJob &b) { return a.len != b.len ? a.len > b.len : a.idx < b.idx; });
+            const uint64_t batch_longest = jobs[0].len > k ? jobs[0].len - k : 0;
+            if (d_sym.bytes < 2 * n_bytes + 16) d_sym.alloc(2 * n_bytes + 16, &ctx->live_bytes, &ctx->peak_bytes);
+            if (d_jobs.bytes < (size_t)nj * sizeof(CovJob)) d_jobs.alloc((size_t)nj * sizeof(CovJob), &ctx->live_bytes, &ctx->peak_bytes);
+            int64_t *d_ids = reinterpret_cast<int64_t *>(window_scratch(ctx, 2 * n_win * 8 + 64));
+            if (n_bytes) MGTA_HIP_CHECK(hipMemcpyAsync(d_sym.p, seqs + offsets[c0], n_bytes, hipMemcpyHostToDevice, st));
+            MGTA_HIP_CHECK(hipMemcpyAsync(d_jobs.p, jobs.data(), (size_t)nj * sizeof(CovJob), hipMemcpyHostToDevice, st));
+            MGTA_HIP_CHECK(hipMemsetAsync(d_cnt.p, 0, 8, st));            // the queue head
+            if (n_bytes) {
+                const unsigned sym_blocks = (unsigned)std::min<uint64_t>((n_bytes + 255) / 256, (uint64_t)ctx->num_cus * 16);
+                hipLaunchKernelGGL(cov_symbols_kernel, dim3(sym_blocks), dim3(256), 0, st, d_sym.as<uint8_t>(), n_bytes);
+                hipLaunchKernelGGL(match_rc_symbols_kernel, dim3(sym_blocks), dim3(256), 0, st, d_sym.as<uint8_t>(), n_bytes);
+            }
+            const uint64_t groups = (uint64_t)ctx->num_cus * (uint64_t)walk_per_cu * kGroups;
+            const uint32_t chunk = nj >= groups * 64 ? 4u : 1u;
+            const unsigned blocks = (unsigned)std::min<uint64_t>((uint64_t)ctx->num_cus * (uint64_t)walk_per_cu, ((uint64_t)nj + kGroups - 1) / kGroups);
+            t_walk.start();
+            if (g->dev.size > 0)
+                hipLaunchKernelGGL(share_walk_kernel, dim3(blocks), dim3(kCovThreads), 0, st, g->dev, d_sym.as<uint8_t>(), d_jobs.as<CovJob>(), nj, chunk, d_ids, cnt_mark);
+            else
+                MGTA_HIP_CHECK(hipMemsetAsync(d_ids, 0xFF, 2 * n_win * 8 + 64, st));   // no edge anywhere
+            MGTA_HIP_CHECK(hipGetLastError());
+            t_walk.end();
+            t_count.start();
+            if (batch_longest) {
+                const unsigned gy = (unsigned)std::min<uint64_t>((batch_longest + 255) / 256, 1024);
+                hipLaunchKernelGGL(sample_count_kernel, dim3((nj + 63) / 64, gy), dim3(256), 0, st, tab, d_jobs.as<CovJob>(), nj, (int)k, d_ids, n_win, win_done,
+                                   d_own.as<uint32_t>(), d_rc.as<uint32_t>(), g->marks.as<uint32_t>(), cnt_mark);
+            }
+            MGTA_HIP_CHECK(hipGetLastError());
+            t_count.end();
+            MGTA_HIP_CHECK(hipStreamSynchronize(st));                     // (jobs and the device buffers serve the next batch)
+            ms_walk += t_walk.ms();
+            ms_count += t_count.ms();
+            win_done += n_win;
+            ++n_batches;
+            c0 = c1;
+        }
+        unsigned long long cnt[16] = {0};
+        MGTA_HIP_CHECK(hipMemcpyAsync(cnt, d_cnt.p, 64, hipMemcpyDeviceToHost, st));
+        MGTA_HIP_CHECK(hipStreamSynchronize(st));
+        if (cnt[5]) { set_error("mgta_contig_sample_coverage: the count table of %llu slots ran full", (unsigned long long)tab.n_slots); return MGTA_EHIP; }
+        // every batch is in: the keys are final.  The batch buffers make room for the counts and the outputs.
+        d_sym.release(); d_jobs.release();
+        const uint64_t n_keys = cnt[3], n_scan = lib_end[n_libs - 1];
+        const uint64_t count_b = (n_keys + 1) * L * 8;
+        d_counts.alloc(count_b, &ctx->live_bytes, &ctx->peak_bytes);
+        d_ends.alloc(L * 8); d_hits.alloc(L * 8);
+        MGTA_HIP_CHECK(hipMemsetAsync(d_counts.p, 0, count_b, st));
+        MGTA_HIP_CHECK(hipMemsetAsync(d_hits.p, 0, L * 8, st));
+        MGTA_HIP_CHECK(hipMemcpyAsync(d_ends.p, lib_end, L * 8, hipMemcpyHostToDevice, st));
+        t_count.start();
+        hipLaunchKernelGGL(sample_dense_kernel, dim3((unsigned)std::min<uint64_t>(tab.n_slots / 256, (uint64_t)ctx->num_cus * 16)), dim3(256), 0, st, tab, cnt_mark);
+        MGTA_HIP_CHECK(hipGetLastError());
+        t_count.end();
+        t_scan.start();
+        if (n_scan && g->dev.size > 0) {
+            // a group takes `chunk` reads per visit to the queue head, as in the read recruitment
+            const uint64_t groups = (uint64_t)ctx->num_cus * (uint64_t)scan_per_cu * kGroups;
+            const uint32_t chunk = n_scan >= groups * 256 ? 16u : 1u;
+            const unsigned blocks = (unsigned)std::min<uint64_t>((uint64_t)ctx->num_cus * (uint64_t)scan_per_cu, (n_scan + (uint64_t)kGroups * chunk - 1) / ((uint64_t)kGroups * chunk));
+            hipLaunchKernelGGL(sample_scan_kernel, dim3(blocks), dim3(kCovThreads), 0, st, g->dev, reads->d_packed, reads->d_start, n_scan, reads_reversed ? 1 : 0, chunk,
+                               g->marks.as<uint32_t>(), tab, d_counts.as<unsigned long long>(), d_ends.as<uint64_t>(), n_libs, d_hits.as<unsigned long long>(), cnt_scan);
+        }
+        MGTA_HIP_CHECK(hipGetLastError());
+        t_scan.end();
+        std::vector<uint64_t> woff((size_t)n + 1, 0);
+        std::vector<uint32_t> lens((size_t)n);
+        for (int64_t i = 0; i < n; ++i) {
+            const uint64_t len = offsets[i + 1] - offsets[i];
+            lens[(size_t)i] = (uint32_t)len;
+            woff[(size_t)i + 1] = woff[(size_t)i] + (len > k ? len - k : 0);
+        }
+        d_woff.alloc(((size_t)n + 1) * 8, &ctx->live_bytes, &ctx->peak_bytes);
+        d_lens.alloc((size_t)n * 4, &ctx->live_bytes, &ctx->peak_bytes);
+        d_out.alloc((size_t)n * sizeof(mgta_contig_share), &ctx->live_bytes, &ctx->peak_bytes);
+        d_mass.alloc((size_t)n * L * 8, &ctx->live_bytes, &ctx->peak_bytes);
+        if (per_window_count && total_win) d_pwc.alloc(total_win * L * 8, &ctx->live_bytes, &ctx->peak_bytes);
+        if (per_window_share && total_win) d_pws.alloc(total_win * 4, &ctx->live_bytes, &ctx->peak_bytes);
+        MGTA_HIP_CHECK(hipMemcpyAsync(d_woff.p, woff.data(), ((size_t)n + 1) * 8, hipMemcpyHostToDevice, st));
+        MGTA_HIP_CHECK(hipMemcpyAsync(d_lens.p, lens.data(), (size_t)n * 4, hipMemcpyHostToDevice, st));
+        t_mass.start();
+        hipLaunchKernelGGL(sample_mass_kernel, dim3((unsigned)(((uint64_t)n + 3) / 4)), dim3(256), 0, st, d_woff.as<uint64_t>(), d_lens.as<uint32_t>(), (uint32_t)n,
+                           d_own.as<uint32_t>(), d_rc.as<uint32_t>(), tab, d_counts.as<unsigned long long>(), n_libs, d_mass.as<uint64_t>(), d_out.as<mgta_contig_share>(),
+                           d_pwc.as<uint64_t>(), d_pws.as<uint32_t>());
+        MGTA_HIP_CHECK(hipGetLastError());
+        t_mass.end();
+        std::vector<mgta_contig_share> rec((size_t)n);
+        std::vector<uint64_t> hits((size_t)L);
+        MGTA_HIP_CHECK(hipMemcpyAsync(mass, d_mass.p, (size_t)n * L * 8, hipMemcpyDeviceToHost, st));
+        MGTA_HIP_CHECK(hipMemcpyAsync(rec.data(), d_out.p, (size_t)n * sizeof(mgta_contig_share), hipMemcpyDeviceToHost, st));
+        MGTA_HIP_CHECK(hipMemcpyAsync(hits.data(), d_hits.p, L * 8, hipMemcpyDeviceToHost, st));
+        MGTA_HIP_CHECK(hipMemcpyAsync(cnt, d_cnt.p, 128, hipMemcpyDeviceToHost, st));
+        if (d_pwc.p) MGTA_HIP_CHECK(hipMemcpyAsync(per_window_count, d_pwc.p, total_win * L * 8, hipMemcpyDeviceToHost, st));
+        if (d_pws.p) MGTA_HIP_CHECK(hipMemcpyAsync(per_window_share, d_pws.p, total_win * 4, hipMemcpyDeviceToHost, st));
+        MGTA_HIP_CHECK(hipStreamSynchronize(st));
+        if (per_contig) memcpy(per_contig, rec.data(), (size_t)n * sizeof(mgta_contig_share));
+        if (lib_hit_windows) memcpy(lib_hit_windows, hits.data(), L * 8);
+        if (stats) {
+            uint64_t total = 0, covered = 0;
+            for (int64_t i = 0; i < n; ++i) { total += rec[(size_t)i].mass; covered += rec[(size_t)i].n_covered; }
+            stats->n_contigs = n; stats->n_windows = (int64_t)total_win; stats->n_walked = (int64_t)cnt[1]; stats->n_index_searches = (int64_t)cnt[2];
+            stats->n_batches = n_batches; stats->n_covered = (int64_t)covered; stats->n_keys = (int64_t)n_keys; stats->n_libs = n_libs;
+            stats->n_reads = (int64_t)n_scan; stats->n_read_windows = (int64_t)cnt[12]; stats->n_read_walked = (int64_t)cnt[9];
+            stats->n_read_index_searches = (int64_t)cnt[10]; stats->n_hit_windows = (int64_t)cnt[11]; stats->groups_per_cu = (int64_t)scan_per_cu * kGroups;
+            stats->total_mass = total; stats->table_slots = tab.n_slots; stats->table_bytes = tab.n_slots * 16; stats->window_bytes = total_win * 8;
+            stats->count_bytes = count_b;
+            stats->ms_mark = ms_walk + ms_count + t_count.ms(); stats->ms_scan = t_scan.ms(); stats->ms_mass = t_mass.ms();
+            stats->ms_total = stats->ms_mark + stats->ms_scan + stats->ms_mass;
         }
         return MGTA_OK;
     });

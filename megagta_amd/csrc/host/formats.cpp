@@ -165,6 +165,29 @@ void PackedReads::finish() {
     if (words.empty()) words.push_back(0);
 }
 
+std::vector<LibRow> read_lib_table(const std::string &prefix) {
+    std::ifstream info(prefix + ".lib_info");
+    std::string line;
+    long long total_bases = 0, num_reads = 0;
+    if (!std::getline(info, line) || sscanf(line.c_str(), "%lld %lld", &total_bases, &num_reads) != 2) die("cannot read %s.lib_info", prefix.c_str());
+    std::vector<LibRow> table;
+    long long at = 0;
+    LibRow row;
+    while (std::getline(info, row.text)) {
+        char kind[8] = {0};
+        if (!std::getline(info, line) || sscanf(line.c_str(), "%lld %lld %d %7s", &row.from, &row.to, &row.max_len, kind) != 4 ||
+            (std::string(kind) != "pe" && std::string(kind) != "se"))
+            die("%s.lib_info: library %zu: bad line behind '%s'", prefix.c_str(), table.size() + 1, row.text.c_str());
+        row.pe = std::string(kind) == "pe";
+        if (row.from != at || row.to < row.from - 1)
+            die("%s.lib_info: library %zu holds the reads %lld .. %lld, the libraries before it end at %lld", prefix.c_str(), table.size() + 1, row.from, row.to, at);
+        at = row.to + 1;
+        table.push_back(row);
+    }
+    if (at != num_reads) die("%s.lib_info: the libraries hold %lld reads, the first line says %lld", prefix.c_str(), at, num_reads);
+    return table;
+}
+
 void load_read_lib(const std::string &prefix, bool reverse, PackedReads &out) {
     std::ifstream info(prefix + ".lib_info");
     long long total_bases = 0, num_reads = 0;

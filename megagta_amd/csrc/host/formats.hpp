@@ -55,6 +55,10 @@ struct PackedReads {
     }
 };
 void load_read_lib(const std::string &prefix, bool reverse, PackedReads &out);          // ReadBinaryLibs
+// the libraries of PREFIX.lib_info: the two lines per library behind the first line (the library's line of the read_lib file, then
+// `from to max_read_len pe|se`, `to` inclusive: an empty library has to = from - 1).  The ranges must tile [0, num_reads) in order: dies otherwise.
+struct LibRow { std::string text; long long from, to; int max_len; bool pe; };
+std::vector<LibRow> read_lib_table(const std::string &prefix);
 void load_assist_fasta(const std::string &path, bool reverse, PackedReads &out);        // s1.cpp:104-134
 void load_read_bin(const std::string &bin_path, bool reverse, PackedReads &out);         // a bare reads.lib.bin, read to EOF (findstart)
 void load_fastx(const std::string &path, bool reverse, PackedReads &out);                // FASTA / FASTQ (plain or .gz), N -> G (sequence_package.h:67-69)

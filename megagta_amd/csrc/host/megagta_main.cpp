@@ -991,6 +991,90 @@ static int main_matchreads(int argc, char **argv) {
     return 0;
 }
 
+// ---- samplecov: the read windows of every library of the read set on the windows of every record of a FASTA
+// (mgta_contig_sample_coverage), what `megagta.py --sample-abund` sums per cluster.  A paired library is one sample: both mates count.
+// The file format is this project's own: INTEGRATION.md 2o; megagta_amd/samplecov.py prints the same bytes.
+static int main_samplecov(int argc, char **argv) {
+    if (argc != 5) { fprintf(stderr, "Usage: megagta samplecov <sdbg_prefix> <read.lib> <contigs.fasta> <out_prefix>\n"); return 1; }
+    RssLine rss;
+    const std::string prefix = argv[1], lib = argv[2], fasta = argv[3], out_prefix = argv[4];
+    std::vector<std::string> names;
+    std::string seqs;
+    std::vector<uint64_t> offsets;
+    read_fasta_records(fasta, names, seqs, offsets);
+    const int64_t n = (int64_t)names.size();
+    const std::vector<LibRow> libs = read_lib_table(lib);
+    if (libs.empty() || libs.size() > 256) die("samplecov: %s.lib_info names %zu libraries (1 .. 256 are supported)", lib.c_str(), libs.size());
+    const size_t n_libs = libs.size();
+    double t0 = now_s();
+    PackedReads local;
+    PackedReads::Mark mk;
+    PackedReads &pr = lib_get(lib + ".bin", lib, "", false, local, mk);  // reversed, as buildgraph uploads it: a worker that still holds it does not read it again
+    const uint64_t n_reads = pr.start.size() - 1;
+    logf("%llu reads, %llu total bases in %zu librar%s (load %.3f s)", (unsigned long long)n_reads, (unsigned long long)pr.start.back(), n_libs, n_libs == 1 ? "y" : "ies",
+         now_s() - t0);
+    std::vector<uint64_t> lib_end(n_libs), read_windows(n_libs, 0), hits(n_libs, 0);
+    for (size_t s = 0; s < n_libs; ++s) lib_end[s] = (uint64_t)(libs[s].to + 1);
+    if (lib_end.back() != n_reads) die("samplecov: %s.lib_info names %llu reads, %s.bin holds %llu", lib.c_str(), (unsigned long long)lib_end.back(), lib.c_str(), (unsigned long long)n_reads);
+    t0 = now_s();
+    mgta_ctx *ctx = ctx_get();
+    // The graph: any load will do, by matchreads' rules.
+    if (writer_join() != 0) die("the graph files of %s are incomplete", prefix.c_str());
+    const std::string key = file_key(prefix + ".sdbg_info");
+    mgta_sdbg *g = nullptr;
+    if (g_sess.active && g_sess.cov_graph && g_sess.cov_key == key) g = g_sess.cov_graph;
+    else if (g_sess.active && g_sess.match_graph && g_sess.match_key == key) g = g_sess.match_graph;
+    if (g) logf("graph %s: still on the device", prefix.c_str());
+    else {
+        graph_drop();
+        if (mgta_sdbg_load_files(ctx, prefix.c_str(), &g) != MGTA_OK) die("mgta_sdbg_load_files: %s", mgta_last_error());
+        if (g_sess.active) { g_sess.match_graph = g; g_sess.match_key = key; }
+    }
+    const uint64_t k = (uint64_t)mgta_sdbg_k(g);
+    logf("Number of Edges: %lld; K value: %d (load %.3f s)", (long long)mgta_sdbg_size(g), (int)k, now_s() - t0);
+    for (size_t s = 0; s < n_libs; ++s)
+        for (uint64_t r = s ? lib_end[s - 1] : 0; r < lib_end[s]; ++r) {
+            const uint64_t len = pr.start[(size_t)r + 1] - pr.start[(size_t)r];
+            read_windows[s] += len > k ? len - k : 0;
+        }
+    t0 = now_s();
+    mgta_reads *rd = nullptr;
+    if (mgta_reads_upload(ctx, pr.words.data(), pr.words.size(), pr.start.data(), n_reads, &rd) != MGTA_OK) die("mgta_reads_upload: %s", mgta_last_error());
+    std::vector<uint64_t> mass((size_t)n * n_libs + 1);
+    std::vector<mgta_contig_share> rec((size_t)n + 1);
+    mgta_sample_cov_stats st;
+    // all records in ONE call: the shares are counted over the file
+    if (mgta_contig_sample_coverage(g, rd, 1, lib_end.data(), (int)n_libs, seqs.data(), offsets.data(), n, mass.data(), rec.data(), nullptr, nullptr, hits.data(), &st) != MGTA_OK)
+        die("mgta_contig_sample_coverage: %s", mgta_last_error());
+    mgta_reads_free(rd);
+    logf("per-library coverage of %lld contigs: %lld windows, %lld covered, %lld keys (%.1f ms); %lld reads, %lld read windows, %lld on a key, %lld by the walk, %lld index "
+         "searches, %lld groups per CU (%.1f ms); masses %.1f ms; table %.1f MB, counts %.1f MB; wall %.3f s", (long long)n, (long long)st.n_windows, (long long)st.n_covered,
+         (long long)st.n_keys, st.ms_mark, (long long)st.n_reads, (long long)st.n_read_windows, (long long)st.n_hit_windows, (long long)st.n_read_walked,
+         (long long)st.n_read_index_searches, (long long)st.groups_per_cu, st.ms_scan, st.ms_mass, (double)st.table_bytes / 1e6, (double)st.count_bytes / 1e6, now_s() - t0);
+    const std::string path = out_prefix + "_samplecov.txt";
+    FILE *sf = fopen(path.c_str(), "w");
+    if (!sf) die("cannot write %s", path.c_str());
+    for (size_t s = 0; s < n_libs; ++s)
+        fprintf(sf, "#lib\t%zu\t%lld\t%llu\t%llu\t%s\n", s + 1, libs[s].to - libs[s].from + 1, (unsigned long long)read_windows[s], (unsigned long long)hits[s],
+                libs[s].text.c_str());
+    fprintf(sf, "#contig\tlen\twindows\tcovered\tunique\tmax_share");
+    for (size_t s = 0; s < n_libs; ++s) fprintf(sf, "\tmass_%zu", s + 1);
+    fputc('\n', sf);
+    for (int64_t i = 0; i < n; ++i) {
+        const mgta_contig_share &c = rec[(size_t)i];
+        fprintf(sf, "%s\t%u\t%u\t%u\t%u\t%u", names[(size_t)i].c_str(), c.len, c.n_windows, c.n_covered, c.n_unique, c.max_share);
+        for (size_t s = 0; s < n_libs; ++s) {
+            fputc('\t', sf);
+            print_q16(sf, mass[(size_t)i * n_libs + s]);
+        }
+        fputc('\n', sf);
+    }
+    if (fclose(sf) != 0) die("short write to %s", path.c_str());
+    if (!g_sess.active) mgta_sdbg_free(g);
+    ctx_put(ctx);
+    return 0;
+}
+
 // ---- derep: the unique, non-contained records of a gene's protein contigs, and the nucleotide records they select ("get the unique
 // merged contigs", bin/post_proc.sh:50-55,84-85).  Needs no graph and leaves a worker's resident graphs alone.  Formats: INTEGRATION.md 2i.
 static bool write_text_file(const std::string &path, const std::string &text) {
@@ -1544,7 +1628,7 @@ int main(int argc, char **argv) {
 static int dispatch(int argc, char **argv) {
     if (argc < 2) {
         fprintf(stderr, "Usage: %s <sub_program> [sub options]\n    sub-programs on the MI355X hot path:\n        buildgraph    build succinct de Bruijn graph\n"
-                        "        denovo        tips, bubbles, contigs of an intermediate k\n        search        HMM-guided search of gene contigs\n        findstart     find starting kmers of the search\n        coverage      per-contig k-mer coverage and abundance from the graph\n        sharecov      per-contig coverage shared among the windows of the file: masses that add up\n        matchreads    the reads that share a (k+1)-mer with a set of contigs\n        derep         the unique, non-contained records of a FASTA\n        align         protein records placed on the columns of a profile HMM\n        cluster       complete-linkage clusters of aligned protein records\n        nearest       the closest reference protein of every protein record\n        chimera       protein records that two references explain better than one\n        dumpversion   dump version\n", argv[0]);
+                        "        denovo        tips, bubbles, contigs of an intermediate k\n        search        HMM-guided search of gene contigs\n        findstart     find starting kmers of the search\n        coverage      per-contig k-mer coverage and abundance from the graph\n        sharecov      per-contig coverage shared among the windows of the file: masses that add up\n        matchreads    the reads that share a (k+1)-mer with a set of contigs\n        samplecov     per-library coverage of a set of contigs, counted from the reads\n        derep         the unique, non-contained records of a FASTA\n        align         protein records placed on the columns of a profile HMM\n        cluster       complete-linkage clusters of aligned protein records\n        nearest       the closest reference protein of every protein record\n        chimera       protein records that two references explain better than one\n        dumpversion   dump version\n", argv[0]);
         return 1;
     }
     std::string sub = argv[1];
@@ -1555,6 +1639,7 @@ static int dispatch(int argc, char **argv) {
     if (sub == "coverage") return main_coverage(argc - 1, argv + 1);
     if (sub == "sharecov") return main_sharecov(argc - 1, argv + 1);
     if (sub == "matchreads") return main_matchreads(argc - 1, argv + 1);
+    if (sub == "samplecov") return main_samplecov(argc - 1, argv + 1);
     if (sub == "derep") return main_derep(argc - 1, argv + 1);
     if (sub == "align") return main_align(argc - 1, argv + 1);
     if (sub == "cluster") return main_cluster(argc - 1, argv + 1);
@@ -1662,6 +1747,6 @@ static int dispatch(int argc, char **argv) {
         return 0;
     }
     if (sub == "dumpversion") { printf("%s\n", mgta_version()); return 0; }
-    fprintf(stderr, "sub-command '%s' is not built here (buildlib, buildgraph, denovo, findstart, search, coverage, sharecov, matchreads, derep, align, cluster, nearest, chimera, filterbylen, translate are): run it with the reference's megagta binary\n", sub.c_str());
+    fprintf(stderr, "sub-command '%s' is not built here (buildlib, buildgraph, denovo, findstart, search, coverage, sharecov, matchreads, samplecov, derep, align, cluster, nearest, chimera, filterbylen, translate are): run it with the reference's megagta binary\n", sub.c_str());
     return 1;
 }

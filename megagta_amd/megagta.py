@@ -70,7 +70,11 @@ USAGE = """Usage:
                      coverage of every clustered contig with each edge's multiplicity split among the contig windows on it, so that it adds
                      up), prot_merged[_rmdup]_otu_abund.txt (mass and ppm per cluster) and, with --nearest,
                      prot_merged[_rmdup]_taxon_abund.txt (per reference protein and its lineage); --chimera's verdicts are used when that
-                     flag runs too (GPU 0)"""
+                     flag runs too (GPU 0)
+    --sample-abund   needs --align --cluster; after every other step: per gene contigs/<gene>/nucl_merged[_rmdup]_samplecov.txt (the read
+                     windows of every library -- one per -r file, --12 file or -1/-2 pair, a pair being one sample -- on every clustered
+                     contig, counted from the reads and split among the contig windows on one edge), prot_merged[_rmdup]_otu_samples.txt
+                     (mass per cluster and library) and prot_merged[_rmdup]_otu_samples_ppm.txt (GPU 0)"""
 
 
 class Usage(Exception):
@@ -116,6 +120,7 @@ class Opt:
         self.chimera_min_seg = 10
         self.chimera_min_gain = 15
         self.taxon_abund = False
+        self.sample_abund = False
 
 
 opt = Opt()
@@ -125,7 +130,7 @@ LONG = ["help", "read=", "12=", "out-dir=", "memory=", "gpu-mem=", "min-contig-l
         "min-count=", "max-tip-len=", "no-mercy", "keep-tmp-files", "mem-flag=", "version", "verbose", "continue", "gene-list=",
         "prune-len=", "low-cov-penalty=", "bin=", "one-process-per-step", "gpus=", "coverage", "match-reads", "derep", "align", "cluster",
         "cluster-dist=", "cluster-min-overlap=", "nearest", "nearest-scoring=", "nearest-gap-open=", "nearest-gap-extend=",
-        "chimera", "chimera-min-seg=", "chimera-min-gain=", "taxon-abund"]
+        "chimera", "chimera-min-seg=", "chimera-min-gain=", "taxon-abund", "sample-abund"]
 
 
 def parse_opt(argv):
@@ -186,6 +191,7 @@ def parse_opt(argv):
         elif o == "--chimera-min-seg": opt.chimera_min_seg = int(v)
         elif o == "--chimera-min-gain": opt.chimera_min_gain = int(v)
         elif o == "--taxon-abund": opt.taxon_abund = True
+        elif o == "--sample-abund": opt.sample_abund = True
         else:
             raise Usage("Invalid option " + o)
     opt.temp_dir = opt.out_dir + "tmp/"
@@ -239,6 +245,8 @@ def check_opt():
         raise Usage("--cluster needs --align: it clusters the rows that step writes")
     if opt.taxon_abund and not (opt.align and opt.cluster):
         raise Usage("--taxon-abund needs --align --cluster: it sums the coverage of the clusters those steps write")
+    if opt.sample_abund and not (opt.align and opt.cluster):
+        raise Usage("--sample-abund needs --align --cluster: it sums the coverage of the clusters those steps write")
     if not 0 <= opt.cluster_dist <= 1:
         raise Usage("--cluster-dist should be between [0, 1]")
     if opt.cluster_min_overlap < 1:
@@ -747,6 +755,32 @@ def taxon_abund(k):
         write_cp()
 
 
+def sample_abund(k):
+    """--sample-abund: per gene the per-library coverage of the clustered nucleotide contigs (`megagta samplecov` on the last k's graph
+    and the run's read library, GPU 0, with --match-reads' rules for what a worker keeps; one call per gene, so the shares are counted
+    over the gene), then the join with the table of --cluster (megagta_amd/samplecov.py, host only).  One checkpoint per gene, after
+    every other checkpoint, those of --taxon-abund included, so `--continue` works under any combination."""
+    stem = "_merged_rmdup" if opt.derep else "_merged"
+    for gene in opt.gene_info:
+        d = opt.out_dir + "contigs/" + gene
+        if should_run():
+            run_step([opt.bin, "samplecov", graph_prefix(k), opt.lib, d + "/nucl" + stem + ".fasta", d + "/nucl" + stem],
+                     "Counting the reads of every library on the contigs of %s" % gene)
+            what = "Summing the clusters of %s per library" % gene
+            logging.info("--- [%s] %s ---" % (datetime.now().strftime("%c"), what))
+            root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+            if root not in sys.path:
+                sys.path.insert(0, root)
+            from megagta_amd import samplecov
+            try:
+                res = samplecov.write_otu_samples(d + "/prot" + stem, d + "/nucl" + stem + "_samplecov.txt", d + "/prot" + stem + "_clust.txt")
+            except (ValueError, OSError) as e:
+                logging.error(str(e))
+                fail_step("running \"%s\"" % what, 1)
+            logging.debug("%d clusters x %d libraries" % (sum(r["cluster"] is not None for r in res["rows"]), len(res["libs"])))
+        write_cp()
+
+
 def after_search(k):
     """the opt-in steps on the last k's graph, in a fixed order behind every checkpoint of a run without them"""
     if opt.coverage:
@@ -765,6 +799,8 @@ def after_search(k):
         chimera(k)
     if opt.taxon_abund:
         taxon_abund(k)
+    if opt.sample_abund:
+        sample_abund(k)
 
 
 def main(argv=None):

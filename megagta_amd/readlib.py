@@ -20,6 +20,35 @@ def read_lib_info(prefix: str) -> tuple[int, int]:
     return total_bases, num_reads
 
 
+def read_lib_table(prefix: str) -> list:
+    """[(text, from, to, max_read_len, is_pe)] per library, from the two lines per library behind the first line of `.lib_info`: the
+    library's line of the read_lib file as it stood, then `from to max_read_len pe|se` (read numbers, `to` inclusive: an empty library
+    has to = from - 1).  The ranges must tile [0, num_reads) in order; anything else is a ValueError."""
+    with open(prefix + ".lib_info", encoding="latin-1") as f:
+        lines = f.read().split("\n")
+    try:
+        num_reads = int(lines[0].split()[1])
+    except (IndexError, ValueError):
+        raise ValueError(f"{prefix}.lib_info: the first line is not `total_bases num_reads`") from None
+    if lines and lines[-1] == "":
+        lines.pop()
+    if len(lines) % 2 != 1:
+        raise ValueError(f"{prefix}.lib_info: a library is two lines, {len(lines) - 1} lines follow the first")
+    table, at = [], 0
+    for i in range(1, len(lines), 2):
+        f = lines[i + 1].split()
+        if len(f) != 4 or f[3] not in ("pe", "se") or not all(x.lstrip("-").isdigit() for x in f[:3]):
+            raise ValueError(f"{prefix}.lib_info: bad library line {lines[i + 1]!r}")
+        frm, to, max_len = int(f[0]), int(f[1]), int(f[2])
+        if frm != at or to < frm - 1:
+            raise ValueError(f"{prefix}.lib_info: library {len(table) + 1} holds the reads {frm} .. {to}, the libraries before it end at {at}")
+        table.append((lines[i], frm, to, max_len, f[3] == "pe"))
+        at = to + 1
+    if at != num_reads:
+        raise ValueError(f"{prefix}.lib_info: the libraries hold {at} reads, the first line says {num_reads}")
+    return table
+
+
 def load_lib_bin(prefix: str) -> list[np.ndarray]:
     """Returns the reads as arrays of base codes (forward orientation)."""
     raw = np.fromfile(prefix + ".bin", dtype=np.uint32)
