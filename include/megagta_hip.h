@@ -163,6 +163,8 @@ typedef struct mgta_build_stats {
     double ms_stage1;                /* min_count >= 2: solid-edge counting + mercy edges, before (and not part of) ms_total */
     int64_t n_fused_passes;          /* passes whose key writer placed the keys by the first global sort digit (no scatter launch for it) */
     int64_t n_wide_passes;           /* radix scatter launches that sorted on a digit wider than 8 bits (MGTA_SORT_WIDE) */
+    int64_t n_split_levels;          /* most levels any sort of the build split its oversized segments by (a digit per level, from the
+                                        top of the bits the global passes left); 0: no segment was too long for an LDS tile */
 } mgta_build_stats;
 
 /* a1: packed reads as `buildgraph` holds them — every read REVERSED (cx1_read2sdbg_s1.cpp:97,117),

@@ -90,7 +90,8 @@ struct Timer {                   // owns its two events
 // fits without it
 enum Slot { S_BLOCK_COUNT, S_BLOCK_BASE, S_SCAN_TMP, S_SMALL, S_KEYS_A, S_KEYS_B, S_HIST, S_TILE_HEADS, S_TILE_BASE, S_CNT, S_BASE,
             S_FIRST, S_OUT_REC, S_OUT_LARGE, S_OUT_TIPS, S_PLAN, S_BIG, S_LSD, S_MULTI_COUNT, S_POS2ID, S_SOLID, S_MERCY, S_EDGE_COUNT, S_SIDE, S_FUSED_HIST,
-            S_DIGIT_TOTALS /* keys per digit value of the global sort pass about to run: up to 1024 values */, S_NUM };
+            S_DIGIT_TOTALS /* keys per digit value of the global sort pass about to run: up to 1024 values */,
+            S_SPLIT /* range lists of the oversized segments of a sort (sdbg_build.hip, split_oversized): part of a pass's memory need */, S_NUM };
 
 }  // namespace mgta
 
@@ -107,6 +108,7 @@ struct mgta_ctx {
     uint64_t mem_limit = 0;       // 0 = auto
     int force_full_lsd = 0;
     int lsd_skip_left = 0;       // sorts left that go straight to LSD passes in LDS (the last look found mostly long runs)
+    int split_levels = 0;        // most split levels a sort of the current build ran on its oversized segments (mgta_build_stats::n_split_levels)
     int astar_log_b0 = 0;        // base arena of a search slot = 1 << astar_log_b0 nodes (0 = default 12); searches grow beyond it in place
     uint64_t astar_pool_bytes = 0;   // device memory the searches may grow into (0 = auto)
     int search_page_limit = 0;   // pages one array of a search may hold (mgta_ctx_set_search_page_limit; 0 = kMaxPages)

@@ -24,7 +24,8 @@
 //        the keys cross HBM once per pass for the scatter, not twice), then every segment of equal prefix is finished inside LDS:
 //        one counting pass on (segment, next <= 8 bits) with LDS atomics, then every key ranks itself inside its short run of
 //        equal leading bits by comparison (local_sort_kernel); tiles with long runs and segments that did not fit take LSD
-//        passes in LDS (local_lsd_kernel), segments longer than a tile global passes over their own range (segment_sort_kernel)
+//        passes in LDS (local_lsd_kernel), segments longer than a tile are split by their leading digits, one scatter per level,
+//        until the pieces fit (segment_split_kernel)
 //     5. edge emission: run descriptors (a, b, group head, bucket head) compacted in one read of the keys by a chained scan
 //        across workgroups -> per run decision (W, last, tip, multiplicity, $-suppression) -> order-preserving compaction of
 //        records, large multiplicities and tip labels + per-bucket boundaries
@@ -40,6 +41,7 @@
 #include "common.hpp"
 #include "device_utils.hpp"
 #include "scan.hpp"
+#include "segment_split.hpp"
 
 namespace mgta {
 
@@ -1184,35 +1186,109 @@ __global__ __launch_bounds__(kSortThreads, 4) void radix_scatter_kernel(const Ke
     }
 }
 
-// One workgroup sorts ONE oversized segment [big[b], big_end[b]) on all the low digits: census, scan and scatter of
-// every pass inside the same launch, ping-ponging between the two key buffers (the range is private to the workgroup).
+// The oversized route: segments longer than lds_cap keys (no LDS tile holds them) are split by their most significant digit not yet
+// split on, level by level, until every piece fits a tile (lds_finish drives the levels).  A list entry is (first | buffer << 63,
+// end): positions in the key array, and which of the two key buffers holds the keys (0: buf0, where the result belongs).
+constexpr uint64_t kSegInOther = 1ull << 63;
+struct SegList {
+    uint64_t *first, *end;
+    uint32_t *count;         // entries wanted (the host compares it with cap: beyond cap nothing is written)
+    uint32_t cap;
+};
+struct SplitLists {
+    SegList small, mid, next;   // SplitClass (segment_split.hpp)
+    uint32_t *n_split;          // segments this level found longer than lds_cap
+};
+
+// One level: one workgroup per listed segment.  Census of digit d over the segment, exclusive scan, ONE stable scatter into the
+// other key buffer; then one wave packs the pieces (the keys of a digit value, now contiguous) into the lists of the finishers and
+// of the next level.  A segment whose keys all share the digit value stays where it is and goes to the next level as it is.  The
+// launch never reads what it wrote.
 template <int W>
-__global__ __launch_bounds__(kSortThreads) void segment_sort_kernel(Key<W> *buf_a, Key<W> *buf_b, const uint64_t *big, const uint64_t *big_end,
-                                                                     const Digit *low_plan, int n_low, uint32_t lds_cap) {
+__global__ __launch_bounds__(kSortThreads) void segment_split_kernel(Key<W> *buf0, Key<W> *buf1, const uint64_t *seg_first, const uint64_t *seg_end,
+                                                                      Digit d, uint32_t local_tile, uint32_t lds_cap, SplitLists out) {
     __shared__ ScatterShared<W> sh;
     __shared__ uint64_t s64[kSortThreads / 64 + 1];
     __shared__ uint32_t s_cnt[256];
-    const int tid = threadIdx.x;
-    const uint64_t s0 = big[blockIdx.x], cnt = big_end[blockIdx.x] - s0;
-    if (cnt <= (uint64_t)lds_cap) return;                           // sorted in LDS by local_deferred_kernel
-    Key<W> *x = buf_a + s0, *y = buf_b + s0;
-    for (int pass = 0; pass < n_low; ++pass) {
-        const Digit d = low_plan[pass];
-        if (tid < 256) s_cnt[tid] = 0;
-        __syncthreads();
-        for (uint64_t i = tid; i < cnt; i += kSortThreads) atomicAdd(&s_cnt[get_digit<W>(x[i], d)], 1u);
-        __syncthreads();
-        uint64_t c = tid < 256 ? s_cnt[tid] : 0;
-        uint64_t ex = block_excl_scan64<kSortThreads>(c, s64, nullptr);
-        if (tid < 256) sh.gbase[tid] = ex;
-        __syncthreads();
-        scatter_subtiles<W>(sh, x, y, cnt, d);
-        __threadfence();                         // the next pass re-reads what this one wrote (other waves' stores, L1 lines of an older pass)
-        __syncthreads();
-        Key<W> *t = x; x = y; y = t;
+    __shared__ uint32_t e_meta[256];                                // class | index among the segment's ranges of that class << 2
+    __shared__ uint32_t s_one;
+    const int tid = threadIdx.x, lane = lane_id(), wv = wave_id();
+    const uint64_t f = wave_uniform(seg_first[blockIdx.x]), s0 = f & ~kSegInOther, cnt = wave_uniform(seg_end[blockIdx.x]) - s0;
+    if (cnt <= (uint64_t)lds_cap) return;                           // (level 0 lists every deferred segment: the shorter ones are sorted in LDS)
+    const bool in_other = (f & kSegInOther) != 0;
+    const Key<W> *x = (in_other ? buf1 : buf0) + s0;
+    Key<W> *y = (in_other ? buf0 : buf1) + s0;
+    if (tid < 256) s_cnt[tid] = 0;
+    if (tid == 0) { s_one = 0; atomicAdd(out.n_split, 1u); }
+    __syncthreads();
+    for (uint64_t base = (uint64_t)wv * 64; base < cnt; base += kSortThreads) {   // (wave-uniform trip count)
+        const uint64_t i = base + (uint64_t)lane;
+        const bool valid = i < cnt;
+        const uint32_t dg = valid ? get_digit<W>(x[i], d) : 0u;
+        const uint32_t dg0 = wave_uniform(dg);                      // lane 0 is valid in every round
+        const uint64_t vm = __ballot(valid);
+        if (__ballot(valid && dg == dg0) == vm) {                   // hot k-mers: one add for the wave instead of 64 to one address
+            if (lane == 0) atomicAdd(&s_cnt[dg0], (uint32_t)__popcll(vm));
+        } else if (valid)
+            atomicAdd(&s_cnt[dg], 1u);
     }
-    if (x != buf_a + s0)                         // odd number of passes: bring the result back to the main buffer
-        for (uint64_t i = tid; i < cnt; i += kSortThreads) y[i] = x[i];
+    __syncthreads();
+    const uint64_t c = tid < 256 ? s_cnt[tid] : 0;
+    if (c == cnt) s_one = 1;
+    const uint64_t ex = block_excl_scan64<kSortThreads>(c, s64, nullptr);
+    if (tid < 256) sh.gbase[tid] = ex;
+    __syncthreads();
+    auto append = [&](const SegList &l, uint32_t q, uint64_t first, uint64_t end) {
+        if (q < l.cap) { l.first[q] = first; l.end[q] = end; }
+    };
+    if (s_one) {
+        if (tid == 0) append(out.next, atomicAdd(out.next.count, 1u), f, s0 + cnt);
+        return;
+    }
+    scatter_subtiles<W>(sh, x, y, cnt, d);
+    __syncthreads();                                                // the scatter's tables are free: they hold the segment's ranges now
+    if (wv != 0) return;
+    uint64_t *const e_first = sh.gbase, *const e_end = sh.gdelta;   // at most one range per non-empty digit value
+    // the pieces lie in y in digit order: pack them (wave-uniform walk over the counts, which lane v & 63 holds for value v)
+    uint32_t cv[4], n_cls[kSplitClasses] = {0, 0, 0}, n_ent = 0;
+#pragma unroll
+    for (int q = 0; q < 4; ++q) cv[q] = s_cnt[q * 64 + lane];
+    SplitPacker pk(s0, local_tile, lds_cap);
+    auto emit = [&](uint32_t cls, uint64_t first, uint64_t end) {
+        const uint32_t idx = cls == kSplitSmall ? n_cls[0]++ : (cls == kSplitMid ? n_cls[1]++ : n_cls[2]++);
+        if (lane == 0) { e_first[n_ent] = first; e_end[n_ent] = end; e_meta[n_ent] = cls | (idx << 2); }
+        ++n_ent;
+    };
+#pragma unroll
+    for (int q = 0; q < 4; ++q)
+        for (int i = 0; i < 64; ++i) pk.step((uint32_t)__builtin_amdgcn_readlane((int)cv[q], i), emit);
+    pk.finish(emit);
+    uint32_t base[kSplitClasses] = {0, 0, 0};
+    if (lane == 0) {
+        if (n_cls[0]) base[0] = atomicAdd(out.small.count, n_cls[0]);
+        if (n_cls[1]) base[1] = atomicAdd(out.mid.count, n_cls[1]);
+        if (n_cls[2]) base[2] = atomicAdd(out.next.count, n_cls[2]);
+    }
+#pragma unroll
+    for (int q = 0; q < kSplitClasses; ++q) base[q] = wave_uniform(base[q]);
+    wave_lds_fence();
+    const uint64_t where = in_other ? 0ull : kSegInOther;           // the pieces are in the buffer the segment was not in
+    for (uint32_t e = lane; e < n_ent; e += 64) {
+        const uint32_t cls = e_meta[e] & 3u, idx = e_meta[e] >> 2;
+        const uint64_t first = e_first[e] | where, end = e_end[e];
+        if (cls == kSplitSmall) append(out.small, base[0] + idx, first, end);
+        else if (cls == kSplitMid) append(out.mid, base[1] + idx, first, end);
+        else append(out.next, base[2] + idx, first, end);
+    }
+}
+
+// what is still listed after the last level: runs of keys equal on every compared bit, finished as they stand.  Those that sit in
+// the other buffer are copied to the result buffer.
+template <int W>
+__global__ __launch_bounds__(kSortThreads) void segment_copy_kernel(Key<W> *res, const Key<W> *other, const uint64_t *seg_first, const uint64_t *seg_end) {
+    const uint64_t f = seg_first[blockIdx.x], s0 = f & ~kSegInOther, cnt = seg_end[blockIdx.x] - s0;
+    if (!(f & kSegInOther)) return;
+    for (uint64_t i = threadIdx.x; i < cnt; i += kSortThreads) res[s0 + i] = other[s0 + i];
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -1226,7 +1302,10 @@ __global__ __launch_bounds__(kSortThreads) void segment_sort_kernel(Key<W> *buf_
 //                      with the run's other keys and goes straight to its final place.
 //   local_lsd_kernel   tiles whose runs are too long for that (reported by the first kernel), and single segments
 //                      that did not fit a tile next to their neighbours: LSD passes in LDS over every remaining digit.
-//   segment_sort_kernel (above)  segments longer than a tile: global passes over just that range.
+//   segment_lds_kernel   single segments of up to twice a tile: the same passes with the LDS of a whole CU.
+//   segment_split_kernel (above)  longer segments: split by the highest digit below the prefix, one stable scatter per level into
+//                      the other key buffer; the pieces are packed into ranges that the two kernels above finish (reading from the
+//                      buffer the pieces are in, writing to the result buffer), pieces still longer than a tile go down a level.
 // ---------------------------------------------------------------------------------------------
 template <int W> struct LocalCfg {
     static constexpr int kTile = W <= 4 ? 4096 : 2048;           // keys sorted in LDS by one workgroup (LDS budget: kTile * 4W bytes)
@@ -1642,20 +1721,23 @@ __global__ __launch_bounds__(kSortThreads, 8) void local_sort_kernel(Key<W> *key
     if (!done) leave_to_lsd();                                        // global memory still holds the tile as it was
 }
 
-// one workgroup per listed range [start[b], end[b]) of whole segments (<= kTile keys, longer ones are skipped: segment_sort_kernel):
-// stable LSD passes in LDS over every significant digit below the prefix, then the segment rank
+// one workgroup per listed range [start[b], end[b]) of whole segments (<= kTile keys, longer ones are skipped: the oversized route):
+// stable LSD passes in LDS over every significant digit below the prefix, then the segment rank.  A range whose start carries
+// kSegInOther (a packed range of the oversized route) is read from `other` instead of `keys`; the result always goes to `keys`.
 template <int W>
-__global__ __launch_bounds__(kSortThreads, 8) void local_lsd_kernel(Key<W> *keys, const uint64_t *start, const uint64_t *end, int stride,
-                                                                    LocalPlan lp) {
+__global__ __launch_bounds__(kSortThreads, 8) void local_lsd_kernel(Key<W> *keys, const Key<W> *other, const uint64_t *start, const uint64_t *end,
+                                                                    int stride, LocalPlan lp) {
     constexpr int kIpt = LocalCfg<W>::kIpt;
     __shared__ LocalShared<W> sh;
     const int tid = threadIdx.x;
-    const uint64_t first = wave_uniform(start[(uint64_t)blockIdx.x * stride]), cnt = wave_uniform(end[(uint64_t)blockIdx.x * stride]) - first;
+    const uint64_t f = wave_uniform(start[(uint64_t)blockIdx.x * stride]), first = f & ~kSegInOther;
+    const uint64_t cnt = wave_uniform(end[(uint64_t)blockIdx.x * stride]) - first;
     if (cnt > (uint64_t)LocalCfg<W>::kTile || cnt == 0) return;
     const uint32_t nt = (uint32_t)cnt;
+    const Key<W> *in = (f & kSegInOther) ? other : keys;
     Key<W> key[kIpt];
     uint32_t seg[kIpt];
-    const int n_seg_pass = tile_load<W>(sh, keys, first, nt, lp.T, key, seg);
+    const int n_seg_pass = tile_load<W>(sh, in, first, nt, lp.T, key, seg);
     const int n_pass = lp.n_low + n_seg_pass;
     tile_zero_counts<W>(sh);
     for (int pass = 0; pass < n_pass; ++pass) {
@@ -1674,22 +1756,24 @@ __global__ __launch_bounds__(kSortThreads, 8) void local_lsd_kernel(Key<W> *keys
 }
 
 // one workgroup per listed segment of LocalCfg::kTile < keys <= BigCfg::kTile: the same LSD passes with the LDS of a whole CU (a
-// hot 16-mer prefix of 5-8 thousand keys took eight global census + scatter round trips of ~100 us each in segment_sort_kernel)
+// hot 16-mer prefix of 5-8 thousand keys took eight global census + scatter round trips of ~100 us each); `other` as in local_lsd_kernel
 template <int W>
-__global__ __launch_bounds__(kSortThreads) void segment_lds_kernel(Key<W> *keys, const uint64_t *start, const uint64_t *end, LocalPlan lp) {
+__global__ __launch_bounds__(kSortThreads) void segment_lds_kernel(Key<W> *keys, const Key<W> *other, const uint64_t *start, const uint64_t *end,
+                                                                    LocalPlan lp) {
     constexpr int TILE = BigCfg<W>::kTile > 0 ? BigCfg<W>::kTile : LocalCfg<W>::kTile, kIpt = TILE / kSortThreads, kChunk = TILE / kSortWaves;
     __shared__ LocalShared<W, TILE> sh;
     const int tid = threadIdx.x, lane = lane_id(), wv = wave_id();
-    const uint64_t first = wave_uniform(start[blockIdx.x]), cnt = wave_uniform(end[blockIdx.x]) - first;
+    const uint64_t f = wave_uniform(start[blockIdx.x]), first = f & ~kSegInOther, cnt = wave_uniform(end[blockIdx.x]) - first;
     if (cnt <= (uint64_t)LocalCfg<W>::kTile || cnt > (uint64_t)BigCfg<W>::kTile) return;
     const uint32_t nt = (uint32_t)cnt;
+    const Key<W> *in = (f & kSegInOther) ? other : keys;
     Key<W> key[kIpt];
     uint32_t seg[kIpt];
 #pragma unroll
     for (int it = 0; it < kIpt; ++it) {
         const uint32_t j = (uint32_t)wv * kChunk + (uint32_t)it * 64 + (uint32_t)lane;
         seg[it] = 0;
-        if (j < nt) key[it] = keys[first + j];
+        if (j < nt) key[it] = in[first + j];
     }
     tile_zero_counts<W, TILE>(sh);
     for (int pass = 0; pass < lp.n_low; ++pass) lds_pass<W, TILE>(sh, key, seg, nt, lp.low_plan[pass], false, 0, pass + 1 < lp.n_low);
@@ -2246,9 +2330,54 @@ static Key<WT> *global_passes(mgta_ctx *ctx, const SortJob<WT> &job, SortLog *lo
     return src;
 }
 
+// keys of the longest segment an LDS kernel finishes at WT key words
+template <int WT> constexpr uint32_t kLdsCap = BigCfg<WT>::kTile > 0 ? BigCfg<WT>::kTile : LocalCfg<WT>::kTile;
+template <int WT>
+static uint64_t split_list_bytes(uint64_t n_items) { return split_list_caps(n_items, LocalCfg<WT>::kTile, kLdsCap<WT>).bytes(); }
+
+// The oversized route of lds_finish: the n_seg listed segments (seg_first, seg_end; all in src) that are longer than kLdsCap are split
+// on the low digits from the top down, a launch per level; what a level leaves short enough is finished in LDS from the buffer it
+// is in, into src.  The host reads a level's four counts back before it launches the next, so a level with nothing listed is never
+// launched.  Returns the number of levels that split something, -1 on an error (set).
+template <int WT>
+static int split_oversized(mgta_ctx *ctx, const SortJob<WT> &job, Key<WT> *src, Key<WT> *dst, const uint64_t *seg_first, const uint64_t *seg_end,
+                           uint32_t n_seg, const LocalPlan &lp) {
+    hipStream_t stream = ctx->stream;
+    const SplitCaps caps = split_list_caps(job.n, LocalCfg<WT>::kTile, kLdsCap<WT>);
+    if (caps.n_small > 0xFFFFFFFFull) { set_error("too many keys for the lists of the oversized segments"); return -1; }
+    uint64_t *d_lists = pool_get<uint64_t>(ctx, S_SPLIT, caps.bytes());
+    uint64_t *at = d_lists;
+    auto take = [&](uint64_t entries) { SegList l{at, at + entries, nullptr, (uint32_t)entries}; at += 2 * entries; return l; };
+    SegList small = take(caps.n_small), mid = take(caps.n_mid), next[2] = {take(caps.n_next), take(caps.n_next)};
+    uint32_t *d_counts = reinterpret_cast<uint32_t *>(at);            // small, mid, next, segments split
+    small.count = d_counts; mid.count = d_counts + 1; next[0].count = next[1].count = d_counts + 2;
+    int levels = 0;
+    const int n_low = (int)job.low.size();
+    for (int level = 0; level < n_low && n_seg > 0; ++level) {
+        MGTA_HIP_CHECK(hipMemsetAsync(d_counts, 0, 16, stream));
+        const SplitLists out{small, mid, next[level & 1], d_counts + 3};
+        hipLaunchKernelGGL((segment_split_kernel<WT>), dim3(n_seg), dim3(kSortThreads), 0, stream, src, dst, seg_first, seg_end, job.low[n_low - 1 - level],
+                           (uint32_t)LocalCfg<WT>::kTile, kLdsCap<WT>, out);
+        uint32_t h[4] = {0, 0, 0, 0};
+        MGTA_HIP_CHECK(hipMemcpyAsync(h, d_counts, 16, hipMemcpyDeviceToHost, stream));
+        MGTA_HIP_CHECK(hipStreamSynchronize(stream));
+        if (h[0] > small.cap || h[1] > mid.cap || h[2] > out.next.cap) {
+            set_error("internal: list overflow of the oversized segments at level %d (%u / %u / %u entries)", level, h[0], h[1], h[2]);
+            return -1;
+        }
+        if (h[3] > 0) ++levels;
+        if (h[0] > 0) hipLaunchKernelGGL((local_lsd_kernel<WT>), dim3(h[0]), dim3(kSortThreads), 0, stream, src, dst, small.first, small.end, 1, lp);
+        if (h[1] > 0) hipLaunchKernelGGL((segment_lds_kernel<WT>), dim3(h[1]), dim3(kSortThreads), 0, stream, src, dst, mid.first, mid.end, lp);
+        seg_first = out.next.first; seg_end = out.next.end; n_seg = h[2];
+    }
+    // behind the last digit: runs of keys equal on every compared bit stay as they are, in src
+    if (n_seg > 0) hipLaunchKernelGGL((segment_copy_kernel<WT>), dim3(n_seg), dim3(kSortThreads), 0, stream, src, dst, seg_first, seg_end);
+    return levels;
+}
+
 // every segment of equal leading top.T() bits finished inside LDS (local_sort_kernel, local_lsd_kernel), segments that did not fit a
-// tile on their own (segment_lds_kernel, segment_sort_kernel).  `src` holds the keys, `dst` is scratch.  Returns src, nullptr on an
-// error (set).
+// tile on their own (segment_lds_kernel, and the split levels of split_oversized for the longer ones).  `src` holds the keys, `dst`
+// is scratch.  Returns src, nullptr on an error (set).
 template <int WT>
 static Key<WT> *lds_finish(mgta_ctx *ctx, const SortJob<WT> &job, Key<WT> *src, Key<WT> *dst, SortLog *log) {
     hipStream_t stream = ctx->stream;
@@ -2299,16 +2428,19 @@ static Key<WT> *lds_finish(mgta_ctx *ctx, const SortJob<WT> &job, Key<WT> *src, 
     if (ub > 0 && l_blocks >= 64 && 2 * (uint64_t)n_lsd_tiles > l_blocks) ctx->lsd_skip_left = 7;   // then look again
     t.start();
     if (n_lsd_tiles > 0 && !(lp.debug & 2))
-        hipLaunchKernelGGL((local_lsd_kernel<WT>), dim3(n_lsd_tiles), dim3(kSortThreads), 0, stream, src, d_lsd, d_lsd + 1, 2, lp);
+        hipLaunchKernelGGL((local_lsd_kernel<WT>), dim3(n_lsd_tiles), dim3(kSortThreads), 0, stream, src, dst, d_lsd, d_lsd + 1, 2, lp);
     if (n_big > 0) {
-        // segments that did not fit a tile next to their neighbours: alone in LDS if they fit, else (hot k-mers, or the whole array
-        // when it is tiny) one workgroup each with global ping-pong passes
+        // segments that did not fit a tile next to their neighbours: alone in LDS if they fit, else (hot k-mers, conserved genes, or
+        // the whole array when it is tiny) split level by level
         hipLaunchKernelGGL((segment_end_kernel<WT>), dim3(n_big), dim3(256), 0, stream, src, n_items, T, d_big, d_big + big_cap);
-        hipLaunchKernelGGL((local_lsd_kernel<WT>), dim3(n_big), dim3(kSortThreads), 0, stream, src, d_big, d_big + big_cap, 1, lp);
+        hipLaunchKernelGGL((local_lsd_kernel<WT>), dim3(n_big), dim3(kSortThreads), 0, stream, src, dst, d_big, d_big + big_cap, 1, lp);
         const bool use_big = BigCfg<WT>::kTile > 0 && !low.empty();
-        if (use_big) hipLaunchKernelGGL((segment_lds_kernel<WT>), dim3(n_big), dim3(kSortThreads), 0, stream, src, d_big, d_big + big_cap, lp);
-        hipLaunchKernelGGL((segment_sort_kernel<WT>), dim3(n_big), dim3(kSortThreads), 0, stream, src, dst, d_big, d_big + big_cap, d_plan,
-                           (int)low.size(), (uint32_t)(use_big ? BigCfg<WT>::kTile : LocalCfg<WT>::kTile));
+        if (use_big) hipLaunchKernelGGL((segment_lds_kernel<WT>), dim3(n_big), dim3(kSortThreads), 0, stream, src, dst, d_big, d_big + big_cap, lp);
+        if (!low.empty()) {
+            const int levels = split_oversized<WT>(ctx, job, src, dst, d_big, d_big + big_cap, n_big, lp);
+            if (levels < 0) return nullptr;
+            ctx->split_levels = std::max(ctx->split_levels, levels);
+        }
     }
     t.end();
     MGTA_HIP_CHECK(hipEventSynchronize(t.b));
@@ -2559,6 +2691,7 @@ struct Build {                                 // a build of keys of W words: wh
         S.ms_total = t_all.stop();
         for (const Timer &t : log.scatter) S.ms_sort_scatter += t.ms();
         S.bytes_peak = ctx->peak_bytes;
+        S.n_split_levels = ctx->split_levels;
         return MGTA_OK;
     }
 
@@ -2570,6 +2703,7 @@ struct Build {                                 // a build of keys of W words: wh
         if (n_blocks * (uint64_t)kScanBlock >= (1ull << 32)) { set_error("too many reads for one launch (%llu)", (unsigned long long)rd->n_reads); return MGTA_EUNSUPPORTED; }
         S.k = k; S.words_per_key = W; S.words_per_tip = words_per_tip; S.n_reads = (int64_t)rd->n_reads;
         ctx->peak_bytes = ctx->live_bytes;
+        ctx->split_levels = 0;
         size_t free_b = 0, total_b = 0;
         MGTA_HIP_CHECK(hipMemGetInfo(&free_b, &total_b));
         // what the build may hold: the explicit limit, else 90 % of (free + what our pool already holds)
@@ -2691,14 +2825,16 @@ struct Build {                                 // a build of keys of W words: wh
         return need + need / 8 <= avail_bytes();
     }
 
-    // device bytes of a pass of n_items (two key buffers, the second doubles as emit scratch, + census + outputs (estimate))
+    // device bytes of a pass of n_items (two key buffers, the second doubles as emit scratch, + census + outputs (estimate) + the range
+    // lists of the oversized segments, sized for the worst case)
     // max_width: of the global passes' digits (side entries of 2 bytes and a census row per value of a digit wider than 8 bits)
     uint64_t pass_need(uint64_t n_items, uint64_t *key_b, int max_width) const {
         const uint64_t n_tiles = (n_items + kBlockTile - 1) / kBlockTile;
         // either key buffer may end up as the emitter's scratch (11 bytes per key: run start u64, record u16, info u8), whichever
         // the last sort pass leaves idle: both hold >= 12 bytes per key
         *key_b = std::max<uint64_t>(n_items * sizeof(Key<W>), n_items * 12) + 4096;
-        return 2 * *key_b + n_tiles * ((uint64_t)8 << max_width) + n_items * 2 + n_items * (max_width > 8 ? 2 : 1) /* side digits */ + (8u << 20);
+        return 2 * *key_b + n_tiles * ((uint64_t)8 << max_width) + n_items * 2 + n_items * (max_width > 8 ? 2 : 1) /* side digits */ + split_list_bytes<W>(n_items) +
+               (8u << 20);
     }
     uint64_t avail_bytes() const {
         uint64_t other = ctx->live_bytes - pool_bytes(ctx);
