@@ -563,6 +563,61 @@ int mgta_pairs_link(const mgta_row_pair *pairs /* [n_pairs], ascending by (i, j)
 int mgta_ctx_set_cluster_tile(mgta_ctx *, int64_t rows_per_tile);   /* 0 = default */
 
 /* ------------------------------------------------------------------------------------------------
+ * The merge tree of aligned rows: clusters at several cut-offs from one pass over the pairs.  Definitions as in the block above.
+ *   Tree.   Input: the kept pairs of n rows ascending by (i, j), as mgta_rows_pairs gives them for (min_overlap, D), and
+ *           n_residues[n].  The tree is the SET of merges the rule of mgta_rows_cluster makes on these pairs.  One merge is an
+ *           mgta_tree_merge: a < b are the lowest members of the two clusters when they merge (the merged cluster keeps name a),
+ *           n_diff / n_overlap their complete-linkage distance, the largest fraction over their cross pairs, IN LOWEST TERMS, 0 as
+ *           0 / 1: which cross pair attains it never shows.  The list is sorted ascending by (fraction compared exactly, a, b); this
+ *           is not the order in which the sequential rule makes the merges, it is a function of the input.  n_merges = aligned rows -
+ *           clusters at D.
+ *   Cut.    The clusters at cut-off c, an fp64 with 0 <= c <= D, are BY DEFINITION what mgta_pairs_link returns for the sub-list of the
+ *           pairs kept at c ((double)n_diff <= c * (double)n_overlap): the same four outputs, numbering and representative.  Merge
+ *           distances of complete linkage never decrease, so a cut is a prefix of the tree WHERE THE KEPT RULE IS MONOTONE in the
+ *           fraction.  One rounded product is not: for a cut-off an ulp below a small rational it may keep 3 / 22 and not 15 / 110.
+ *           So mgta_tree_cut takes, in one pass over the pairs, hi = the largest fraction among the pairs kept at c and lo = the
+ *           smallest among those not kept; when no pair is "not kept" or hi < lo exactly, the clusters are the union of the merges
+ *           whose fraction is <= hi (none when no pair is kept), numbered and given representatives as by mgta_pairs_link; otherwise
+ *           it runs mgta_pairs_link's linkage on the kept sub-list and counts that in stats.n_cut_fallbacks.  Both routes give the
+ *           same answer where both apply.  mgta_tree_cut is host only, no context and no device; `merges` must be the tree of
+ *           `pairs`.  It cannot know D: a caller that cuts above D gets the clusters at D's pairs; mgta_rows_clusters checks c <= D.
+ * mgta_pairs_tree is the device part: symmetric neighbour lists per cluster built once from the pairs, then rounds launched by the
+ * host in which every pair of clusters that are each other's smallest key merges at once (under the strict order of the keys the
+ * sequential rule merges exactly those, whatever else it merges before; complete linkage is reducible), with one small read-back a
+ * round and at most n - 1 rounds.  A clique of m clusters at one distance merges one pair a round: m - 1 rounds over m lists
+ * (stats.n_rounds and n_entries_visited show it).  At most `cap` merges are stored: *n_merges is the number found; when it exceeds cap
+ * NOTHING is stored.  Device memory: 32 bytes per kept pair for the lists (two buffers), 12 more while they are built, about 80 per
+ * row; MGTA_ENOMEM names the need.  The limits of the linkage apply: n < 2^31 and fewer than 2^32 kept pairs (MGTA_ENOMEM).
+ * MGTA_EINVAL: the cases of mgta_pairs_link, NULL context, cap < 0, NULL merges with cap > 0, NULL n_merges (nothing is written).
+ * mgta_rows_clusters runs mgta_rows_pairs' pass once at D = the largest of cutoffs[n_cutoffs] (n_cutoffs >= 1, each in [0, 1]), the
+ * tree on the device and one cut per cut-off on the host: cluster, rep, rep_diff, rep_overlap hold n_cutoffs * n values, cut-off k at
+ * [k * n, (k + 1) * n); merges [n] may be NULL (then n_merges may be NULL too).  n = 0: MGTA_OK, stats all zero.  Every output is a
+ * function of the inputs only, except stats.ms_*, peak_bytes and the counters of work done.
+ * ------------------------------------------------------------------------------------------------ */
+typedef struct mgta_tree_merge { int32_t a, b; uint16_t n_diff, n_overlap; } mgta_tree_merge;   /* a < b; the fraction in lowest terms */
+typedef struct mgta_tree_stats {
+    int64_t n_rows, n_pairs, n_merges;
+    int64_t n_rounds;                      /* rounds that merged something */
+    int64_t n_entries_visited;             /* list entries read: every list once for its first nearest, then the old lists of every rewrite */
+    int64_t n_lists_rewritten;             /* summed over the rounds */
+    int64_t n_cut_fallbacks;               /* cuts that ran the host linkage on the kept sub-list */
+    int64_t n_unaligned, n_clusters, n_singletons, largest_cluster;   /* of the last cut */
+    int64_t peak_bytes;                    /* most device memory the call held at once */
+    double ms_pairs;                       /* mgta_rows_clusters: the pairs pass */
+    double ms_build, ms_rounds;            /* HIP events: the lists; the rounds (read-backs included) */
+    double ms_cut;                         /* host clock, summed over the cuts */
+} mgta_tree_stats;
+int mgta_pairs_tree(mgta_ctx *, const mgta_row_pair *pairs /* [n_pairs], ascending by (i, j) */, int64_t n_pairs, const int32_t *n_residues /* [n] */,
+                    int64_t n, mgta_tree_merge *merges /* [cap] or NULL */, int64_t cap, int64_t *n_merges, mgta_tree_stats *stats /* may be NULL */);
+int mgta_tree_cut(const mgta_row_pair *pairs, int64_t n_pairs, const mgta_tree_merge *merges, int64_t n_merges, const int32_t *n_residues /* [n] */,
+                  const int64_t *lens /* [n] */, int64_t n, double cutoff, int32_t *cluster, int64_t *rep, uint16_t *rep_diff, uint16_t *rep_overlap,
+                  mgta_tree_stats *stats /* may be NULL */);
+int mgta_rows_clusters(mgta_ctx *, const uint8_t *rows /* [n * M] */, const int64_t *lens /* [n] */, int64_t n, int64_t M, int64_t min_overlap,
+                       const double *cutoffs /* [n_cutoffs] */, int64_t n_cutoffs, int32_t *cluster /* [n_cutoffs * n] */, int64_t *rep,
+                       uint16_t *rep_diff, uint16_t *rep_overlap, mgta_tree_merge *merges /* [n] or NULL */, int64_t *n_merges,
+                       mgta_tree_stats *stats /* may be NULL */);
+
+/* ------------------------------------------------------------------------------------------------
  * The nearest reference protein of every contig (the place of FrameBot in the reference's bin/post_proc.sh:106-111, which names
  * `AlignmentTool pairwise-knn` on the protein representatives as the alternative; neither tool nor a BLOSUM file is part of the
  * reference, and the rule below is this library's own, not theirs).  Needs no graph.  Contig i = seqs[offsets[i] .. offsets[i + 1]),

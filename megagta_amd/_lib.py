@@ -153,6 +153,16 @@ class ClusterStats(C.Structure):
         return {n: getattr(self, n) for n, _ in self._fields_}
 
 
+class TreeStats(C.Structure):
+    _fields_ = [("n_rows", C.c_int64), ("n_pairs", C.c_int64), ("n_merges", C.c_int64), ("n_rounds", C.c_int64), ("n_entries_visited", C.c_int64),
+                ("n_lists_rewritten", C.c_int64), ("n_cut_fallbacks", C.c_int64), ("n_unaligned", C.c_int64), ("n_clusters", C.c_int64),
+                ("n_singletons", C.c_int64), ("largest_cluster", C.c_int64), ("peak_bytes", C.c_int64), ("ms_pairs", C.c_double), ("ms_build", C.c_double),
+                ("ms_rounds", C.c_double), ("ms_cut", C.c_double)]
+
+    def as_dict(self):
+        return {n: getattr(self, n) for n, _ in self._fields_}
+
+
 class NearestRec(C.Structure):
     _fields_ = [("status", C.c_int32), ("ref", C.c_int32), ("score", C.c_int32), ("ref_from", C.c_int32), ("ref_to", C.c_int32), ("n_match", C.c_int32),
                 ("n_ident", C.c_int32), ("n_insert", C.c_int32), ("n_delete", C.c_int32)]
@@ -254,6 +264,11 @@ SYMBOLS = {
                                     C.c_void_p, C.c_void_p]),
     "mgta_pairs_link": (C.c_int, [C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "mgta_ctx_set_cluster_tile": (C.c_int, [C.c_void_p, C.c_int64]),
+    "mgta_pairs_tree": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p]),
+    "mgta_tree_cut": (C.c_int, [C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_int64, C.c_double, C.c_void_p, C.c_void_p, C.c_void_p,
+                                C.c_void_p, C.c_void_p]),
+    "mgta_rows_clusters": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_int64, C.c_int64, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p,
+                                     C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "mgta_seqs_nearest": (C.c_int, [C.c_void_p, C.c_char_p, C.c_void_p, C.c_int64, C.c_char_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_int32, C.c_int32,
                                     C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "mgta_ctx_set_nearest_batch": (C.c_int, [C.c_void_p, C.c_int64]),

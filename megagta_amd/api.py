@@ -221,6 +221,41 @@ class Context:
                                         rd.ctypes.data, ro.ctypes.data, C.byref(st)), "mgta_rows_cluster")
         return dict(cluster=cl[:n], rep=rep[:n], rep_diff=rd[:n], rep_overlap=ro[:n], stats=st.as_dict())
 
+    def pairs_tree(self, pairs, n_residues) -> dict:
+        """mgta_pairs_tree: the complete-linkage merge tree of the kept pairs of n rows (a ROW_PAIR array ascending by (i, j), or tuples),
+        on the device -> dict(merges = TREE_MERGE array: a < b, n_diff / n_overlap in lowest terms, ascending by (fraction, a, b); stats)."""
+        p = _pair_array(pairs)
+        nr = np.ascontiguousarray(n_residues, dtype=np.int32)
+        if nr.ndim != 1:
+            raise ValueError("n_residues must hold one value per row")
+        n = nr.size
+        merges = np.zeros(max(1, n), dtype=TREE_MERGE)
+        cnt, st = C.c_int64(0), _lib.TreeStats()
+        check(self._L.mgta_pairs_tree(self.h, p.ctypes.data if p.size else None, p.size, nr.ctypes.data, n, merges.ctypes.data, n, C.byref(cnt), C.byref(st)),
+              "mgta_pairs_tree")
+        return dict(merges=merges[:cnt.value], stats=st.as_dict())
+
+    def clusters(self, rows, lens, min_overlap: int, cutoffs) -> dict:
+        """mgta_rows_clusters: the clusters of the aligned rows at every cut-off of `cutoffs` from one pass over the pairs (at the
+        largest) and one merge tree -> dict(cluster = int32[n_cutoffs, n], rep = int64[n_cutoffs, n], rep_diff, rep_overlap =
+        uint16[n_cutoffs, n]: row k is what `cluster` gives at cutoffs[k]; merges = the tree (TREE_MERGE array); stats)."""
+        r = self._rows(rows)
+        n, M = r.shape
+        ln = np.ascontiguousarray(lens, dtype=np.int64)
+        if ln.shape != (n,):
+            raise ValueError("lens must hold one length per row")
+        cut = np.ascontiguousarray(cutoffs, dtype=np.float64)
+        if cut.ndim != 1:
+            raise ValueError("cutoffs must be a list of numbers")
+        k = cut.size
+        cl, rep = np.zeros((k, n), dtype=np.int32), np.zeros((k, n), dtype=np.int64)                  # cut-off j at [j * n, (j + 1) * n)
+        rd, ro = np.zeros((k, n), dtype=np.uint16), np.zeros((k, n), dtype=np.uint16)
+        merges = np.zeros(max(1, n), dtype=TREE_MERGE)
+        cnt, st = C.c_int64(0), _lib.TreeStats()
+        check(self._L.mgta_rows_clusters(self.h, r.ctypes.data, ln.ctypes.data, n, M, int(min_overlap), cut.ctypes.data if k else None, k, cl.ctypes.data,
+                                         rep.ctypes.data, rd.ctypes.data, ro.ctypes.data, merges.ctypes.data, C.byref(cnt), C.byref(st)), "mgta_rows_clusters")
+        return dict(cluster=cl, rep=rep, rep_diff=rd, rep_overlap=ro, merges=merges[:cnt.value], stats=st.as_dict())
+
     def set_nearest_batch(self, cells: int = 0):
         """cells (L * R) of one trace batch of `nearest` (0 = the default: by the context's free memory); a batch holds at least one
         pair.  For tests: the result does not depend on it; only stats["n_batches"] does."""
@@ -624,8 +659,32 @@ def link_pairs(pairs, n_residues, lens) -> dict:
     return dict(cluster=cl[:n], rep=rep[:n], rep_diff=rd[:n], rep_overlap=ro[:n], stats=st.as_dict())
 
 
+def _pair_array(pairs) -> np.ndarray:
+    return np.ascontiguousarray(pairs, dtype=ROW_PAIR) if isinstance(pairs, np.ndarray) else np.array([tuple(x) for x in pairs], dtype=ROW_PAIR)
+
+
+def tree_cut(pairs, merges, n_residues, lens, cutoff: float) -> dict:
+    """mgta_tree_cut: the clusters at `cutoff` read off the merge tree of `pairs` (Context.pairs_tree / Context.clusters), on the host,
+    no context and no device: what link_pairs gives for the pairs kept at `cutoff` -> dict(cluster, rep, rep_diff, rep_overlap, stats);
+    stats["n_cut_fallbacks"] = 1 when the kept rule split equal fractions and the host linkage ran instead."""
+    p = _pair_array(pairs)
+    m = np.ascontiguousarray(merges, dtype=TREE_MERGE) if isinstance(merges, np.ndarray) else np.array([tuple(x) for x in merges], dtype=TREE_MERGE)
+    nr, ln = np.ascontiguousarray(n_residues, dtype=np.int32), np.ascontiguousarray(lens, dtype=np.int64)
+    n = nr.size
+    if ln.shape != (n,) or nr.ndim != 1:
+        raise ValueError("n_residues and lens must hold one value per row")
+    cl, rep = np.zeros(max(1, n), dtype=np.int32), np.zeros(max(1, n), dtype=np.int64)
+    rd, ro = np.zeros(max(1, n), dtype=np.uint16), np.zeros(max(1, n), dtype=np.uint16)
+    st = _lib.TreeStats()
+    check(_lib.load().mgta_tree_cut(p.ctypes.data if p.size else None, p.size, m.ctypes.data if m.size else None, m.size, nr.ctypes.data, ln.ctypes.data, n,
+                                    float(cutoff), cl.ctypes.data, rep.ctypes.data, rd.ctypes.data, ro.ctypes.data, C.byref(st)), "mgta_tree_cut")
+    return dict(cluster=cl[:n], rep=rep[:n], rep_diff=rd[:n], rep_overlap=ro[:n], stats=st.as_dict())
+
+
 # mgta_row_pair
 ROW_PAIR = np.dtype([("i", np.int32), ("j", np.int32), ("n_diff", np.uint16), ("n_overlap", np.uint16)], align=True)
+# mgta_tree_merge
+TREE_MERGE = np.dtype([("a", np.int32), ("b", np.int32), ("n_diff", np.uint16), ("n_overlap", np.uint16)], align=True)
 
 
 class DeviceHmm:

@@ -9,6 +9,12 @@ Host only, no device.
   PREFIX_rep_seqs.fasta   the representatives in input order: `>` + the header line as it stood + newline + the A2M line without `-`,
                           upper-cased (ASCII letters only) + newline
 
+`megagta clustertree` / `megagta.py --cluster-dists` write the same two files per cut-off as PREFIX_d<tag>_clust.txt and
+PREFIX_d<tag>_rep_seqs.fasta (tag = the cut-off as the user wrote it), and once
+  PREFIX_tree.txt         `#a_row<TAB>b_row<TAB>a<TAB>b<TAB>n_diff<TAB>n_overlap`, then one line per merge of the complete-linkage tree up to
+                          the largest cut-off, ascending by (n_diff / n_overlap, a_row, b_row): a_row < b_row are the lowest records of the
+                          two clusters when they merge, a and b their names, n_diff / n_overlap the distance in lowest terms (0 as 0/1)
+
 The input is PREFIX_aligned.fasta of `megagta align` (megagta_amd/align.py): the row of a record is its A2M line without the
 lower-case letters, its length the characters of the line that are not `-`.  The definitions are those of mgta_rows_cluster
 (include/megagta_hip.h).
@@ -74,6 +80,67 @@ def write_cluster(prefix: str, headers, lines, result: dict, nucl=None, nucl_pre
     if nucl is not None:
         with open(nucl_prefix + "_rep_seqs.fasta", "w", encoding="latin-1") as fh:
             fh.write("".join(">%s\n%s\n" % (h, s) for i, (h, s) in enumerate(nucl) if status_of(i, result["cluster"], result["rep"]) == 0))
+
+
+TREE_HEADER = "#a_row\tb_row\ta\tb\tn_diff\tn_overlap\n"
+
+
+def tree_text(names, merges) -> str:
+    """the text of PREFIX_tree.txt from the merges of Context.clusters / Context.pairs_tree (a TREE_MERGE array, or tuples (a, b, n_diff,
+    n_overlap)) over records called `names`"""
+    rows = merges.tolist() if isinstance(merges, np.ndarray) else [tuple(m) for m in merges]
+    return TREE_HEADER + "".join("%d\t%d\t%s\t%s\t%d\t%d\n" % (a, b, names[a], names[b], d, o) for a, b, d, o in rows)
+
+
+def parse_tree(text: str) -> dict:
+    """the text of PREFIX_tree.txt -> dict(merges = [(a_row, b_row, n_diff, n_overlap)], names = {row: name} of the rows the file names)"""
+    lines = text.splitlines()
+    if not lines or lines[0] + "\n" != TREE_HEADER:
+        raise ValueError("tree table: the header line is missing")
+    merges, names = [], {}
+    for line in lines[1:]:
+        f = line.split("\t")
+        if len(f) != 6 or not all(f[k].isdigit() for k in (0, 1, 4, 5)):
+            raise ValueError(f"tree table: bad line {line!r}")
+        a, b, d, o = int(f[0]), int(f[1]), int(f[4]), int(f[5])
+        if not (a < b and 1 <= o and d <= o) or names.setdefault(a, f[2]) != f[2] or names.setdefault(b, f[3]) != f[3]:
+            raise ValueError(f"tree table: bad line {line!r}")
+        merges.append((a, b, d, o))
+    return dict(merges=merges, names=names)
+
+
+def read_tree(path: str) -> dict:
+    with open(path, encoding="latin-1") as fh:
+        return parse_tree(fh.read())
+
+
+def write_cluster_tree(prefix: str, headers, lines, tags, result: dict, nucl=None, nucl_prefix: str | None = None) -> None:
+    """the files of `megagta clustertree` from the result of Context.clusters over the rows of the A2M `lines`, tags[k] naming cut-off k:
+    per tag what write_cluster writes under PREFIX_d<tag> (and NUCL_PREFIX_d<tag>), and PREFIX_tree.txt"""
+    if len(tags) != len(result["cluster"]):
+        raise ValueError("cluster: one tag per cut-off")
+    for k, tag in enumerate(tags):
+        one = dict(cluster=result["cluster"][k], rep=result["rep"][k], rep_diff=result["rep_diff"][k], rep_overlap=result["rep_overlap"][k])
+        write_cluster(prefix + "_d" + tag, headers, lines, one, nucl, None if nucl_prefix is None else nucl_prefix + "_d" + tag)
+    with open(prefix + "_tree.txt", "w", encoding="latin-1") as fh:
+        fh.write(tree_text([record_name(h) for h in headers], result["merges"]))
+
+
+def parse_cutoff_list(text: str):
+    """`c1,c2,...` -> (tags, cutoffs): every item is made of 0-9 and `.`, a number in [0, 1]; its text is its tag; two items with the same
+    value are an error (ValueError names the item)"""
+    tags, cutoffs = [], []
+    for item in text.split(","):
+        if not item or item.strip("0123456789.") or item.count(".") > 1 or not item.strip("."):
+            raise ValueError(f"cut-off {item!r} is not a number in [0, 1] written with 0-9 and .")
+        c = float(item)
+        if not 0 <= c <= 1:
+            raise ValueError(f"cut-off {item!r} is not a number in [0, 1] written with 0-9 and .")
+        if c in cutoffs:
+            raise ValueError(f"cut-offs {tags[cutoffs.index(c)]!r} and {item!r} are the same number")
+        tags.append(item)
+        cutoffs.append(c)
+    return tags, cutoffs
 
 
 def parse_clust(text: str) -> dict:

@@ -38,6 +38,7 @@
 #include "common.hpp"
 #include "device_utils.hpp"
 #include "scan.hpp"
+#include "cluster_tree.hpp"
 
 namespace mgta {
 namespace {
@@ -372,6 +373,40 @@ void link_component(uint32_t m, const std::vector<uint32_t> &pu, const std::vect
     }
 }
 
+struct ClusterCounts { int64_t n_unaligned, n_clusters, n_singletons, largest; };
+
+// name[i] = the lowest row of i's cluster -> the four outputs: numbers by the lowest member, the representative by lens then index
+ClusterCounts number_clusters(const mgta_row_pair *P, size_t n_pairs, const uint32_t *n_res, const int64_t *lens, uint32_t nn, const std::vector<uint32_t> &name,
+                              int32_t *cluster, int64_t *rep, uint16_t *rep_diff, uint16_t *rep_overlap) {
+    const uint32_t kNone = 0xFFFFFFFFu;
+    std::vector<int32_t> number(nn, -1);
+    std::vector<uint32_t> best(nn, kNone), csize(nn, 0);
+    int32_t n_clusters = 0;
+    for (uint32_t i = 0; i < nn; ++i) {
+        if (n_res[i] == 0) continue;
+        const uint32_t c = name[i];
+        if (c == i) number[i] = n_clusters++;
+        ++csize[c];
+        if (best[c] == kNone || lens[i] > lens[best[c]]) best[c] = i;
+    }
+    int64_t n_unaligned = 0, n_singletons = 0, largest = 0;
+    for (uint32_t i = 0; i < nn; ++i) {
+        if (n_res[i] == 0) { cluster[i] = -1; rep[i] = -1; rep_diff[i] = 0; rep_overlap[i] = 0; ++n_unaligned; continue; }
+        const uint32_t c = name[i];
+        cluster[i] = number[c];
+        rep[i] = (int64_t)best[c];
+        rep_diff[i] = 0;
+        rep_overlap[i] = (uint16_t)n_res[i];                          // the representative's own; a member's comes from its pair below
+        if (c == i) { n_singletons += csize[c] == 1; largest = std::max<int64_t>(largest, csize[c]); }
+    }
+    for (size_t e_ = 0; e_ < n_pairs; ++e_) {
+        const mgta_row_pair &p = P[e_];
+        if (rep[p.i] == (int64_t)p.j) { rep_diff[p.i] = p.n_diff; rep_overlap[p.i] = p.n_overlap; }
+        if (rep[p.j] == (int64_t)p.i) { rep_diff[p.j] = p.n_diff; rep_overlap[p.j] = p.n_overlap; }
+    }
+    return ClusterCounts{n_unaligned, (int64_t)n_clusters, n_singletons, largest};
+}
+
 // the clusters of nn rows from their kept pairs (sorted by (i, j)), the residue columns of every row and the lengths; fills the
 // linkage's fields of *stats and leaves the others alone
 int link_rows(const char *who, const mgta_row_pair *P, size_t n_pairs, const uint32_t *n_res, const int64_t *lens, uint32_t nn, int32_t *cluster, int64_t *rep,
@@ -439,39 +474,127 @@ int link_rows(const char *who, const mgta_row_pair *P, size_t n_pairs, const uin
         }
     }
 
-    // numbers by the lowest member, the representative by lens then index
-    std::vector<int32_t> number(nn, -1);
-    std::vector<uint32_t> best(nn, kNone), csize(nn, 0);
-    int32_t n_clusters = 0;
-    for (uint32_t i = 0; i < nn; ++i) {
-        if (n_res[i] == 0) continue;
-        const uint32_t c = name[i];
-        if (c == i) number[i] = n_clusters++;
-        ++csize[c];
-        if (best[c] == kNone || lens[i] > lens[best[c]]) best[c] = i;
-    }
-    int64_t n_unaligned = 0, n_singletons = 0, largest = 0;
-    for (uint32_t i = 0; i < nn; ++i) {
-        if (n_res[i] == 0) { cluster[i] = -1; rep[i] = -1; rep_diff[i] = 0; rep_overlap[i] = 0; ++n_unaligned; continue; }
-        const uint32_t c = name[i];
-        cluster[i] = number[c];
-        rep[i] = (int64_t)best[c];
-        rep_diff[i] = 0;
-        rep_overlap[i] = (uint16_t)n_res[i];                          // the representative's own; a member's comes from its pair below
-        if (c == i) { n_singletons += csize[c] == 1; largest = std::max<int64_t>(largest, csize[c]); }
-    }
-    for (size_t e_ = 0; e_ < n_pairs; ++e_) {
-        const mgta_row_pair &p = P[e_];
-        if (rep[p.i] == (int64_t)p.j) { rep_diff[p.i] = p.n_diff; rep_overlap[p.i] = p.n_overlap; }
-        if (rep[p.j] == (int64_t)p.i) { rep_diff[p.j] = p.n_diff; rep_overlap[p.j] = p.n_overlap; }
-    }
+    const ClusterCounts cc = number_clusters(P, n_pairs, n_res, lens, nn, name, cluster, rep, rep_diff, rep_overlap);
     if (stats) {
         stats->n_rows = nn; stats->n_pairs_kept = (int64_t)n_pairs;
-        stats->n_unaligned = n_unaligned; stats->n_clusters = n_clusters; stats->n_singletons = n_singletons; stats->largest_cluster = largest;
+        stats->n_unaligned = cc.n_unaligned; stats->n_clusters = cc.n_clusters; stats->n_singletons = cc.n_singletons; stats->largest_cluster = cc.largest;
         stats->n_components = n_components; stats->n_link_pops = n_pops;
         stats->ms_link = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
     }
     return (int)MGTA_OK;
+}
+
+// ---- the merge tree: what the host does around cluster_tree.hpp ------------------------------------------------------------------------
+// the pair list of mgta_pairs_link and of the tree entries: every message names `who`
+int check_pair_list(const char *who, const mgta_row_pair *pairs, int64_t n_pairs, const int32_t *n_residues, int64_t n) {
+    for (int64_t i = 0; i < n; ++i)
+        if (n_residues[i] < 0 || n_residues[i] >= kMaxColumns) { set_error("%s: n_residues[%lld] = %d (0 .. 65535)", who, (long long)i, n_residues[i]); return MGTA_EINVAL; }
+    for (int64_t e = 0; e < n_pairs; ++e) {
+        const mgta_row_pair &p = pairs[e];
+        if (p.i < 0 || p.i >= p.j || p.j >= n || p.n_overlap < 1 || p.n_diff > p.n_overlap || n_residues[p.i] == 0 || n_residues[p.j] == 0) {
+            set_error("%s: pair %lld = (%d, %d, %u / %u): 0 <= i < j < n, 1 <= n_overlap, n_diff <= n_overlap, both rows with residues", who, (long long)e, p.i, p.j,
+                      (unsigned)p.n_diff, (unsigned)p.n_overlap);
+            return MGTA_EINVAL;
+        }
+        if (e > 0 && !(pairs[e - 1].i < p.i || (pairs[e - 1].i == p.i && pairs[e - 1].j < p.j))) {
+            set_error("%s: pair %lld: the pairs must ascend by (i, j)", who, (long long)e);
+            return MGTA_EINVAL;
+        }
+    }
+    return MGTA_OK;
+}
+
+// what the device found -> the list of the contract: fractions in lowest terms, ascending by (fraction, a, b)
+void finish_merges(const std::vector<TreeMerge> &found, std::vector<mgta_tree_merge> &out) {
+    out.clear();
+    out.reserve(found.size());
+    for (const TreeMerge &m : found) {
+        const uint32_t d = m.f >> 16, o = m.f & 0xFFFFu, g = d ? std::gcd(d, o) : o;
+        out.push_back(mgta_tree_merge{(int32_t)m.a, (int32_t)m.b, (uint16_t)(d / g), (uint16_t)(o / g)});
+    }
+    std::sort(out.begin(), out.end(), [](const mgta_tree_merge &x, const mgta_tree_merge &y) {
+        const Frac fx{x.n_diff, x.n_overlap}, fy{y.n_diff, y.n_overlap};
+        if (frac_less(fx, fy)) return true;
+        if (frac_less(fy, fx)) return false;
+        return x.a != y.a ? x.a < y.a : x.b < y.b;
+    });
+}
+
+// one cut of the tree (the caller has checked pairs, merges and the rest); adds to n_cut_fallbacks and ms_cut, sets the counts of the cut
+int cut_rows(const char *who, const mgta_row_pair *P, size_t n_pairs, const mgta_tree_merge *T, size_t n_merges, const uint32_t *n_res, const int64_t *lens, uint32_t nn,
+             double cutoff, int32_t *cluster, int64_t *rep, uint16_t *rep_diff, uint16_t *rep_overlap, mgta_tree_stats *st) {
+    const auto t0 = std::chrono::steady_clock::now();
+    bool any_kept = false, any_apart = false;
+    Frac hi{0, 1}, lo{0, 1};
+    size_t n_kept = 0;
+    for (size_t e = 0; e < n_pairs; ++e) {
+        const Frac f{P[e].n_diff, P[e].n_overlap};
+        if ((double)f.d <= cutoff * (double)f.o) {
+            if (!any_kept || frac_less(hi, f)) hi = f;
+            any_kept = true; ++n_kept;
+        } else {
+            if (!any_apart || frac_less(f, lo)) lo = f;
+            any_apart = true;
+        }
+    }
+    ClusterCounts cc;
+    if (!any_apart || !any_kept || frac_less(hi, lo)) {
+        // the merges up to hi: b goes into a < b, and every row above its cluster's name was a `b` once
+        std::vector<uint32_t> name(nn);
+        std::iota(name.begin(), name.end(), 0u);
+        if (any_kept)
+            for (size_t m = 0; m < n_merges; ++m)
+                if (!frac_less(hi, Frac{T[m].n_diff, T[m].n_overlap})) name[(uint32_t)T[m].b] = (uint32_t)T[m].a;
+        for (uint32_t i = 0; i < nn; ++i) name[i] = name[name[i]];       // name[i] <= i is final already
+        cc = number_clusters(P, n_pairs, n_res, lens, nn, name, cluster, rep, rep_diff, rep_overlap);
+    } else {
+        std::vector<mgta_row_pair> kept;
+        kept.reserve(n_kept);
+        for (size_t e = 0; e < n_pairs; ++e)
+            if ((double)P[e].n_diff <= cutoff * (double)P[e].n_overlap) kept.push_back(P[e]);
+        mgta_cluster_stats cs;
+        memset(&cs, 0, sizeof cs);
+        const int r = link_rows(who, kept.data(), kept.size(), n_res, lens, nn, cluster, rep, rep_diff, rep_overlap, &cs);
+        if (r != MGTA_OK) return r;
+        cc = ClusterCounts{cs.n_unaligned, cs.n_clusters, cs.n_singletons, cs.largest_cluster};
+        if (st) ++st->n_cut_fallbacks;
+    }
+    if (st) {
+        st->n_unaligned = cc.n_unaligned; st->n_clusters = cc.n_clusters; st->n_singletons = cc.n_singletons; st->largest_cluster = cc.largest;
+        st->ms_cut += std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+    }
+    return (int)MGTA_OK;
+}
+
+int check_merges(const char *who, const mgta_tree_merge *T, int64_t n_merges, const int32_t *n_residues, int64_t n) {
+    if (n_merges < 0 || n_merges > std::max<int64_t>(0, n - 1)) { set_error("%s: n_merges = %lld (0 .. n - 1)", who, (long long)n_merges); return MGTA_EINVAL; }
+    if (n_merges > 0 && !T) { set_error("%s: merges must not be NULL", who); return MGTA_EINVAL; }
+    std::vector<uint8_t> gone((size_t)n, 0);
+    for (int64_t m = 0; m < n_merges; ++m) {
+        const mgta_tree_merge &t = T[m];
+        if (t.a < 0 || t.a >= t.b || t.b >= n || t.n_overlap < 1 || t.n_diff > t.n_overlap || n_residues[t.a] == 0 || n_residues[t.b] == 0 || gone[(size_t)t.b]) {
+            set_error("%s: merge %lld = (%d, %d, %u / %u): 0 <= a < b < n, 1 <= n_overlap, n_diff <= n_overlap, both rows with residues, b merged once", who, (long long)m,
+                      t.a, t.b, (unsigned)t.n_diff, (unsigned)t.n_overlap);
+            return MGTA_EINVAL;
+        }
+        gone[(size_t)t.b] = 1;
+        if (m > 0 && frac_less(Frac{t.n_diff, t.n_overlap}, Frac{T[m - 1].n_diff, T[m - 1].n_overlap})) {
+            set_error("%s: merge %lld: the merges must ascend by their fraction", who, (long long)m);
+            return MGTA_EINVAL;
+        }
+    }
+    return MGTA_OK;
+}
+
+std::vector<uint32_t> residue_columns(const uint8_t *rows, uint32_t nn, int64_t M) {
+    std::vector<uint32_t> n_res(nn);
+    for (uint32_t i = 0; i < nn; ++i) {
+        const uint8_t *p = rows + (size_t)i * (size_t)M;
+        uint32_t c = 0;
+        for (int64_t k = 0; k < M; ++k) c += p[k] != (uint8_t)'-';
+        n_res[i] = c;
+    }
+    return n_res;
 }
 
 }  // namespace
@@ -526,15 +649,8 @@ int mgta_rows_cluster(mgta_ctx *ctx, const uint8_t *rows, const int64_t *lens, i
         memset(&s, 0, sizeof s);
         const int r = pairs_impl(ctx, who, rows, n, M, min_overlap, cutoff, &P, &count, &s);
         if (r != MGTA_OK) return r;
-        // residue columns of every row; a row without any is in no cluster
         const uint32_t nn = (uint32_t)n;
-        std::vector<uint32_t> n_res(nn);
-        for (uint32_t i = 0; i < nn; ++i) {
-            const uint8_t *p = rows + (size_t)i * (size_t)M;
-            uint32_t c = 0;
-            for (int64_t k = 0; k < M; ++k) c += p[k] != (uint8_t)'-';
-            n_res[i] = c;
-        }
+        const std::vector<uint32_t> n_res = residue_columns(rows, nn, M);   // a row without any is in no cluster
         if (stats) *stats = s;
         return link_rows(who, P.data(), P.size(), n_res.data(), lens, nn, cluster, rep, rep_diff, rep_overlap, stats);
     });
@@ -548,26 +664,113 @@ int mgta_pairs_link(const mgta_row_pair *pairs, int64_t n_pairs, const int32_t *
     if (n_pairs > 0 && !pairs) { set_error("%s: pairs must not be NULL", who); return MGTA_EINVAL; }
     if (n > 0 && (!n_residues || !lens)) { set_error("%s: n_residues and lens must not be NULL", who); return MGTA_EINVAL; }
     if (n > 0 && (!cluster || !rep || !rep_diff || !rep_overlap)) { set_error("%s: cluster, rep, rep_diff and rep_overlap must not be NULL", who); return MGTA_EINVAL; }
-    for (int64_t i = 0; i < n; ++i)
-        if (n_residues[i] < 0 || n_residues[i] >= kMaxColumns) { set_error("%s: n_residues[%lld] = %d (0 .. 65535)", who, (long long)i, n_residues[i]); return MGTA_EINVAL; }
-    for (int64_t e = 0; e < n_pairs; ++e) {
-        const mgta_row_pair &p = pairs[e];
-        if (p.i < 0 || p.i >= p.j || p.j >= n || p.n_overlap < 1 || p.n_diff > p.n_overlap || n_residues[p.i] == 0 || n_residues[p.j] == 0) {
-            set_error("%s: pair %lld = (%d, %d, %u / %u): 0 <= i < j < n, 1 <= n_overlap, n_diff <= n_overlap, both rows with residues", who, (long long)e, p.i, p.j,
-                      (unsigned)p.n_diff, (unsigned)p.n_overlap);
-            return MGTA_EINVAL;
-        }
-        if (e > 0 && !(pairs[e - 1].i < p.i || (pairs[e - 1].i == p.i && pairs[e - 1].j < p.j))) {
-            set_error("%s: pair %lld: the pairs must ascend by (i, j)", who, (long long)e);
-            return MGTA_EINVAL;
-        }
-    }
+    const int rc = check_pair_list(who, pairs, n_pairs, n_residues, n);
+    if (rc != MGTA_OK) return rc;
     if (stats) memset(stats, 0, sizeof(*stats));
     if (n == 0) return MGTA_OK;
     return guarded(who, [&]() {
         std::vector<uint32_t> n_res((size_t)n);
         for (int64_t i = 0; i < n; ++i) n_res[(size_t)i] = (uint32_t)n_residues[i];
         return link_rows(who, pairs, (size_t)n_pairs, n_res.data(), lens, (uint32_t)n, cluster, rep, rep_diff, rep_overlap, stats);
+    });
+}
+
+int mgta_pairs_tree(mgta_ctx *ctx, const mgta_row_pair *pairs, int64_t n_pairs, const int32_t *n_residues, int64_t n, mgta_tree_merge *merges, int64_t cap,
+                    int64_t *n_merges, mgta_tree_stats *stats) {
+    const char *who = "mgta_pairs_tree";
+    if (!ctx) { set_error("%s: ctx must not be NULL", who); return MGTA_EINVAL; }
+    if (n < 0 || n >= (1ll << 31)) { set_error("%s: n = %lld (0 <= n < 2^31 rows)", who, (long long)n); return MGTA_EINVAL; }
+    if (n_pairs < 0) { set_error("%s: n_pairs = %lld must not be negative", who, (long long)n_pairs); return MGTA_EINVAL; }
+    if (n_pairs > 0 && !pairs) { set_error("%s: pairs must not be NULL", who); return MGTA_EINVAL; }
+    if (n > 0 && !n_residues) { set_error("%s: n_residues must not be NULL", who); return MGTA_EINVAL; }
+    if (cap < 0) { set_error("%s: cap = %lld must not be negative", who, (long long)cap); return MGTA_EINVAL; }
+    if (cap > 0 && !merges) { set_error("%s: merges must not be NULL when cap > 0", who); return MGTA_EINVAL; }
+    if (!n_merges) { set_error("%s: n_merges must not be NULL", who); return MGTA_EINVAL; }
+    const int rc = check_pair_list(who, pairs, n_pairs, n_residues, n);
+    if (rc != MGTA_OK) return rc;
+    if (stats) memset(stats, 0, sizeof(*stats));
+    *n_merges = 0;
+    if (n == 0) return MGTA_OK;
+    return guarded(who, [&]() {
+        mgta_tree_stats s;
+        memset(&s, 0, sizeof s);
+        std::vector<TreeMerge> found;
+        const int r = tree_impl(ctx, who, pairs, (uint64_t)n_pairs, (uint32_t)n, found, &s);
+        if (r != MGTA_OK) return r;
+        std::vector<mgta_tree_merge> T;
+        finish_merges(found, T);
+        s.n_rows = n; s.n_pairs = n_pairs; s.n_merges = (int64_t)T.size();
+        *n_merges = (int64_t)T.size();
+        if (!T.empty() && (int64_t)T.size() <= cap) memcpy(merges, T.data(), T.size() * sizeof(mgta_tree_merge));
+        if (stats) *stats = s;
+        return (int)MGTA_OK;
+    });
+}
+
+int mgta_tree_cut(const mgta_row_pair *pairs, int64_t n_pairs, const mgta_tree_merge *merges, int64_t n_merges, const int32_t *n_residues, const int64_t *lens, int64_t n,
+                  double cutoff, int32_t *cluster, int64_t *rep, uint16_t *rep_diff, uint16_t *rep_overlap, mgta_tree_stats *stats) {
+    const char *who = "mgta_tree_cut";
+    if (n < 0 || n >= (1ll << 31)) { set_error("%s: n = %lld (0 <= n < 2^31 rows)", who, (long long)n); return MGTA_EINVAL; }
+    if (n_pairs < 0) { set_error("%s: n_pairs = %lld must not be negative", who, (long long)n_pairs); return MGTA_EINVAL; }
+    if (n_pairs > 0 && !pairs) { set_error("%s: pairs must not be NULL", who); return MGTA_EINVAL; }
+    if (n > 0 && (!n_residues || !lens)) { set_error("%s: n_residues and lens must not be NULL", who); return MGTA_EINVAL; }
+    if (n > 0 && (!cluster || !rep || !rep_diff || !rep_overlap)) { set_error("%s: cluster, rep, rep_diff and rep_overlap must not be NULL", who); return MGTA_EINVAL; }
+    if (!(cutoff >= 0.0 && cutoff <= 1.0)) { set_error("%s: cutoff = %g must lie in [0, 1]", who, cutoff); return MGTA_EINVAL; }
+    int rc = check_pair_list(who, pairs, n_pairs, n_residues, n);
+    if (rc != MGTA_OK) return rc;
+    rc = check_merges(who, merges, n_merges, n_residues, n);
+    if (rc != MGTA_OK) return rc;
+    if (stats) memset(stats, 0, sizeof(*stats));
+    if (n == 0) return MGTA_OK;
+    return guarded(who, [&]() {
+        std::vector<uint32_t> n_res((size_t)n);
+        for (int64_t i = 0; i < n; ++i) n_res[(size_t)i] = (uint32_t)n_residues[i];
+        if (stats) { stats->n_rows = n; stats->n_pairs = n_pairs; stats->n_merges = n_merges; }
+        return cut_rows(who, pairs, (size_t)n_pairs, merges, (size_t)n_merges, n_res.data(), lens, (uint32_t)n, cutoff, cluster, rep, rep_diff, rep_overlap, stats);
+    });
+}
+
+int mgta_rows_clusters(mgta_ctx *ctx, const uint8_t *rows, const int64_t *lens, int64_t n, int64_t M, int64_t min_overlap, const double *cutoffs, int64_t n_cutoffs,
+                       int32_t *cluster, int64_t *rep, uint16_t *rep_diff, uint16_t *rep_overlap, mgta_tree_merge *merges, int64_t *n_merges, mgta_tree_stats *stats) {
+    const char *who = "mgta_rows_clusters";
+    if (n_cutoffs < 1 || !cutoffs) { set_error("%s: n_cutoffs = %lld: at least one cut-off, cutoffs must not be NULL", who, (long long)n_cutoffs); return MGTA_EINVAL; }
+    double D = 0.0;
+    for (int64_t k = 0; k < n_cutoffs; ++k) {
+        const int rc = check_rows(who, ctx, rows, n, M, min_overlap, cutoffs[k]);
+        if (rc != MGTA_OK) return rc;
+        D = std::max(D, cutoffs[k]);
+    }
+    if (n > 0 && !lens) { set_error("%s: lens must not be NULL", who); return MGTA_EINVAL; }
+    if (n > 0 && (!cluster || !rep || !rep_diff || !rep_overlap)) { set_error("%s: cluster, rep, rep_diff and rep_overlap must not be NULL", who); return MGTA_EINVAL; }
+    if (merges && !n_merges) { set_error("%s: n_merges must not be NULL when merges is given", who); return MGTA_EINVAL; }
+    if (stats) memset(stats, 0, sizeof(*stats));
+    if (n_merges) *n_merges = 0;
+    if (n == 0) return MGTA_OK;
+    return guarded(who, [&]() {
+        std::vector<mgta_row_pair> P;
+        int64_t count = 0;
+        mgta_cluster_stats ps;
+        memset(&ps, 0, sizeof ps);
+        int r = pairs_impl(ctx, who, rows, n, M, min_overlap, D, &P, &count, &ps);
+        if (r != MGTA_OK) return r;
+        const uint32_t nn = (uint32_t)n;
+        const std::vector<uint32_t> n_res = residue_columns(rows, nn, M);
+        mgta_tree_stats s;
+        memset(&s, 0, sizeof s);
+        std::vector<TreeMerge> found;
+        r = tree_impl(ctx, who, P.data(), P.size(), nn, found, &s);
+        if (r != MGTA_OK) return r;
+        std::vector<mgta_tree_merge> T;
+        finish_merges(found, T);
+        s.n_rows = n; s.n_pairs = count; s.n_merges = (int64_t)T.size(); s.ms_pairs = ps.ms_pairs; s.peak_bytes = std::max<int64_t>(s.peak_bytes, ps.peak_bytes);
+        for (int64_t k = 0; k < n_cutoffs; ++k) {
+            r = cut_rows(who, P.data(), P.size(), T.data(), T.size(), n_res.data(), lens, nn, cutoffs[k], cluster + k * n, rep + k * n, rep_diff + k * n, rep_overlap + k * n, &s);
+            if (r != MGTA_OK) return r;
+        }
+        if (n_merges) *n_merges = (int64_t)T.size();
+        if (merges && !T.empty()) memcpy(merges, T.data(), T.size() * sizeof(mgta_tree_merge));
+        if (stats) *stats = s;
+        return (int)MGTA_OK;
     });
 }
 

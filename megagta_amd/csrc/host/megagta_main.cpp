@@ -1204,65 +1204,108 @@ static int main_align(int argc, char **argv) {
 // ---- cluster: complete-linkage clusters of a gene's aligned protein contigs, their representatives and the nucleotide records those select
 // ("cluster at 99% aa identity", bin/post_proc.sh:57-85; the rule is mgta_rows_cluster's own).  Needs no graph and leaves a worker's resident
 // graphs alone.  Formats: INTEGRATION.md 2k.
+struct ClusterInput {
+    std::string fasta;
+    std::vector<std::string> names, headers, nnames, nheaders;
+    std::string lines, nseqs, rows;
+    std::vector<uint64_t> offsets, noffsets;
+    std::vector<int64_t> lens;
+    int64_t n = 0;
+    size_t M = 1;
+    bool nucl = false;
+};
+// the rows and lengths of <aligned.fasta> and, with a path, the nucleotide records that go with them; false after an [ERROR] line
+static bool cluster_read(const char *who, const char *aligned, const char *nucl, ClusterInput &in) {
+    in.fasta = aligned;
+    read_fasta_records(in.fasta, in.names, in.lines, in.offsets, &in.headers);
+    const int64_t n = in.n = (int64_t)in.names.size();
+    // the row of a record: its A2M line without the lower-case (inserted) residues; its length: the characters that are not '-'
+    in.lens.assign((size_t)n + 1, 0);
+    for (int64_t i = 0; i < n; ++i) {
+        const size_t before = in.rows.size();
+        int64_t len = 0;
+        for (uint64_t p = in.offsets[(size_t)i]; p < in.offsets[(size_t)i + 1]; ++p) {
+            const char c = in.lines[p];
+            len += c != '-';
+            if (!(c >= 'a' && c <= 'z')) in.rows += c;
+        }
+        in.lens[(size_t)i] = len;
+        if (i == 0) in.M = in.rows.size();
+        if (in.rows.size() - before != in.M || in.M == 0) {
+            fprintf(stderr, "    [ERROR] %s: record %lld (%s) of %s has %zu columns, the first record has %zu: nothing written\n", who, (long long)i,
+                    in.names[(size_t)i].c_str(), in.fasta.c_str(), in.rows.size() - before, in.M);
+            return false;
+        }
+    }
+    in.nucl = nucl != nullptr;
+    if (nucl) {
+        // `derep`'s check: one nucleotide record per protein record, in order and under the same name
+        read_fasta_records(nucl, in.nnames, in.nseqs, in.noffsets, &in.nheaders);
+        if (in.nnames.size() != in.names.size()) {
+            fprintf(stderr, "    [ERROR] %s: %s holds %zu records, %s holds %zu: nothing written\n", who, in.fasta.c_str(), in.names.size(), nucl, in.nnames.size());
+            return false;
+        }
+        for (int64_t i = 0; i < n; ++i)
+            if (in.nnames[(size_t)i] != in.names[(size_t)i]) {
+                fprintf(stderr, "    [ERROR] %s: record %lld is %s in %s and %s in %s: nothing written\n", who, (long long)i, in.names[(size_t)i].c_str(), in.fasta.c_str(),
+                        in.nnames[(size_t)i].c_str(), nucl);
+                return false;
+            }
+    }
+    return true;
+}
+// PREFIX_clust.txt, PREFIX_rep_seqs.fasta and, with the nucleotide records, NUCL_PREFIX_rep_seqs.fasta from the four outputs of a linkage
+static void cluster_write(const ClusterInput &in, const int32_t *cluster, const int64_t *rep, const uint16_t *rep_diff, const uint16_t *rep_overlap,
+                          const std::string &out_prefix, const std::string &nucl_prefix) {
+    std::string table = "#contig\tstatus\tcluster\trep\tlen\tn_diff\tn_overlap\n", reps, nreps;
+    for (int64_t i = 0; i < in.n; ++i) {
+        const size_t u = (size_t)i;
+        const bool unaligned = cluster[u] < 0, is_rep = !unaligned && rep[u] == i;
+        table += in.names[u] + "\t" + (unaligned ? "unaligned" : is_rep ? "rep" : "member") + "\t" + (unaligned ? std::string("-") : std::to_string(cluster[u])) + "\t" +
+                 (unaligned ? std::string("-") : in.names[(size_t)rep[u]]) + "\t" + std::to_string(in.lens[u]) + "\t" + std::to_string(rep_diff[u]) + "\t" +
+                 std::to_string(rep_overlap[u]) + "\n";
+        if (!is_rep) continue;
+        reps += ">" + in.headers[u] + "\n";
+        for (uint64_t p = in.offsets[u]; p < in.offsets[u + 1]; ++p) {
+            const char c = in.lines[p];
+            if (c != '-') reps += (c >= 'a' && c <= 'z') ? (char)(c - 32) : c;
+        }
+        reps += "\n";
+        if (in.nucl) {
+            nreps += ">" + in.nheaders[u] + "\n";
+            nreps.append(in.nseqs, (size_t)in.noffsets[u], (size_t)(in.noffsets[u + 1] - in.noffsets[u]));
+            nreps += "\n";
+        }
+    }
+    if (!write_text_file(out_prefix + "_clust.txt", table)) die("cannot write %s_clust.txt", out_prefix.c_str());
+    if (!write_text_file(out_prefix + "_rep_seqs.fasta", reps)) die("cannot write %s_rep_seqs.fasta", out_prefix.c_str());
+    if (in.nucl && !write_text_file(nucl_prefix + "_rep_seqs.fasta", nreps)) die("cannot write %s_rep_seqs.fasta", nucl_prefix.c_str());
+}
+
 static int main_cluster(int argc, char **argv) {
     if (argc != 5 && argc != 7) {
         fprintf(stderr, "Usage: megagta cluster <aligned.fasta> <out_prefix> <dist_cutoff> <min_overlap> [<nucl.fasta> <nucl_out_prefix>]\n");
         return 1;
     }
     RssLine rss;
-    const std::string fasta = argv[1], out_prefix = argv[2];
+    const std::string out_prefix = argv[2];
     char *end = nullptr;
     const double cutoff = strtod(argv[3], &end);
     if (end == argv[3] || *end) { fprintf(stderr, "    [ERROR] cluster: dist_cutoff '%s' is not a number\n", argv[3]); return 1; }
     const long long min_overlap = strtoll(argv[4], &end, 10);
     if (end == argv[4] || *end) { fprintf(stderr, "    [ERROR] cluster: min_overlap '%s' is not an integer\n", argv[4]); return 1; }
-    std::vector<std::string> names, headers, nnames, nheaders;
-    std::string lines, nseqs;
-    std::vector<uint64_t> offsets, noffsets;
-    read_fasta_records(fasta, names, lines, offsets, &headers);
-    const int64_t n = (int64_t)names.size();
-    // the row of a record: its A2M line without the lower-case (inserted) residues; its length: the characters that are not '-'
-    std::string rows;
-    std::vector<int64_t> lens((size_t)n + 1);
-    size_t M = 1;
-    for (int64_t i = 0; i < n; ++i) {
-        const size_t before = rows.size();
-        int64_t len = 0;
-        for (uint64_t p = offsets[(size_t)i]; p < offsets[(size_t)i + 1]; ++p) {
-            const char c = lines[p];
-            len += c != '-';
-            if (!(c >= 'a' && c <= 'z')) rows += c;
-        }
-        lens[(size_t)i] = len;
-        if (i == 0) M = rows.size();
-        if (rows.size() - before != M || M == 0) {
-            fprintf(stderr, "    [ERROR] cluster: record %lld (%s) of %s has %zu columns, the first record has %zu: nothing written\n", (long long)i, names[(size_t)i].c_str(),
-                    fasta.c_str(), rows.size() - before, M);
-            return 1;
-        }
-    }
-    if (argc == 7) {
-        // `derep`'s check: one nucleotide record per protein record, in order and under the same name
-        read_fasta_records(argv[5], nnames, nseqs, noffsets, &nheaders);
-        if (nnames.size() != names.size()) {
-            fprintf(stderr, "    [ERROR] cluster: %s holds %zu records, %s holds %zu: nothing written\n", fasta.c_str(), names.size(), argv[5], nnames.size());
-            return 1;
-        }
-        for (int64_t i = 0; i < n; ++i)
-            if (nnames[(size_t)i] != names[(size_t)i]) {
-                fprintf(stderr, "    [ERROR] cluster: record %lld is %s in %s and %s in %s: nothing written\n", (long long)i, names[(size_t)i].c_str(), fasta.c_str(),
-                        nnames[(size_t)i].c_str(), argv[5]);
-                return 1;
-            }
-    }
+    ClusterInput in;
+    if (!cluster_read("cluster", argv[1], argc == 7 ? argv[5] : nullptr, in)) return 1;
+    const int64_t n = in.n;
+    const size_t M = in.M;
     const double t0 = now_s();
     mgta_ctx *ctx = ctx_get();
     std::vector<int32_t> cluster((size_t)n + 1);
     std::vector<int64_t> rep((size_t)n + 1);
     std::vector<uint16_t> rep_diff((size_t)n + 1), rep_overlap((size_t)n + 1);
     mgta_cluster_stats st;
-    if (mgta_rows_cluster(ctx, (const uint8_t *)rows.data(), lens.data(), n, (int64_t)M, min_overlap, cutoff, cluster.data(), rep.data(), rep_diff.data(), rep_overlap.data(),
-                          &st) != MGTA_OK) {
+    if (mgta_rows_cluster(ctx, (const uint8_t *)in.rows.data(), in.lens.data(), n, (int64_t)M, min_overlap, cutoff, cluster.data(), rep.data(), rep_diff.data(),
+                          rep_overlap.data(), &st) != MGTA_OK) {
         fprintf(stderr, "    [ERROR] cluster: %s: nothing written\n", mgta_last_error());
         ctx_put(ctx);
         return 1;
@@ -1272,29 +1315,75 @@ static int main_cluster(int argc, char **argv) {
          min_overlap, (long long)st.n_unaligned, (long long)st.n_pairs_kept, (long long)st.n_components, (long long)st.n_clusters, (long long)st.n_singletons,
          (long long)st.largest_cluster, (long long)st.n_tiles, (long long)st.grid_blocks, (long long)st.blocks_per_cu, (long long)st.lds_bytes, (long long)st.peak_bytes,
          st.ms_pairs, st.ms_link, now_s() - t0);
-    std::string table = "#contig\tstatus\tcluster\trep\tlen\tn_diff\tn_overlap\n", reps, nreps;
-    for (int64_t i = 0; i < n; ++i) {
-        const size_t u = (size_t)i;
-        const bool unaligned = cluster[u] < 0, is_rep = !unaligned && rep[u] == i;
-        table += names[u] + "\t" + (unaligned ? "unaligned" : is_rep ? "rep" : "member") + "\t" + (unaligned ? std::string("-") : std::to_string(cluster[u])) + "\t" +
-                 (unaligned ? std::string("-") : names[(size_t)rep[u]]) + "\t" + std::to_string(lens[u]) + "\t" + std::to_string(rep_diff[u]) + "\t" +
-                 std::to_string(rep_overlap[u]) + "\n";
-        if (!is_rep) continue;
-        reps += ">" + headers[u] + "\n";
-        for (uint64_t p = offsets[u]; p < offsets[u + 1]; ++p) {
-            const char c = lines[p];
-            if (c != '-') reps += (c >= 'a' && c <= 'z') ? (char)(c - 32) : c;
-        }
-        reps += "\n";
-        if (argc == 7) {
-            nreps += ">" + nheaders[u] + "\n";
-            nreps.append(nseqs, (size_t)noffsets[u], (size_t)(noffsets[u + 1] - noffsets[u]));
-            nreps += "\n";
-        }
+    cluster_write(in, cluster.data(), rep.data(), rep_diff.data(), rep_overlap.data(), out_prefix, argc == 7 ? argv[6] : "");
+    ctx_put(ctx);
+    return 0;
+}
+
+// ---- clustertree: the clusters of `cluster` at several cut-offs from one pass over the pairs and one merge tree (mgta_rows_clusters), and the
+// tree itself.  Per item of <c1,c2,...>, whose text is the tag: <out_prefix>_d<tag>_clust.txt, <out_prefix>_d<tag>_rep_seqs.fasta and
+// <nucl_out_prefix>_d<tag>_rep_seqs.fasta, each what `cluster` writes at that cut-off; once: <out_prefix>_tree.txt.  Formats: INTEGRATION.md 2k'.
+static int main_clustertree(int argc, char **argv) {
+    if (argc != 5 && argc != 7) {
+        fprintf(stderr, "Usage: megagta clustertree <aligned.fasta> <out_prefix> <c1,c2,...> <min_overlap> [<nucl.fasta> <nucl_out_prefix>]\n");
+        return 1;
     }
-    if (!write_text_file(out_prefix + "_clust.txt", table)) die("cannot write %s_clust.txt", out_prefix.c_str());
-    if (!write_text_file(out_prefix + "_rep_seqs.fasta", reps)) die("cannot write %s_rep_seqs.fasta", out_prefix.c_str());
-    if (argc == 7 && !write_text_file(std::string(argv[6]) + "_rep_seqs.fasta", nreps)) die("cannot write %s_rep_seqs.fasta", argv[6]);
+    RssLine rss;
+    const std::string out_prefix = argv[2], list = argv[3];
+    std::vector<std::string> tags;
+    std::vector<double> cutoffs;
+    for (size_t at = 0; at <= list.size();) {
+        const size_t comma = std::min(list.find(',', at), list.size());
+        const std::string item = list.substr(at, comma - at);
+        at = comma + 1;
+        const bool text_ok = !item.empty() && item.find_first_not_of("0123456789.") == std::string::npos && item.find_first_of("0123456789") != std::string::npos &&
+                             std::count(item.begin(), item.end(), '.') <= 1;
+        char *end = nullptr;
+        const double c = text_ok ? strtod(item.c_str(), &end) : -1.0;
+        if (!text_ok || *end || !(c >= 0.0 && c <= 1.0)) {
+            fprintf(stderr, "    [ERROR] clustertree: cut-off '%s' is not a number in [0, 1] written with 0-9 and .\n", item.c_str());
+            return 1;
+        }
+        for (size_t k = 0; k < cutoffs.size(); ++k)
+            if (cutoffs[k] == c) { fprintf(stderr, "    [ERROR] clustertree: cut-offs '%s' and '%s' are the same number\n", tags[k].c_str(), item.c_str()); return 1; }
+        tags.push_back(item);
+        cutoffs.push_back(c);
+    }
+    char *end = nullptr;
+    const long long min_overlap = strtoll(argv[4], &end, 10);
+    if (end == argv[4] || *end) { fprintf(stderr, "    [ERROR] clustertree: min_overlap '%s' is not an integer\n", argv[4]); return 1; }
+    ClusterInput in;
+    if (!cluster_read("clustertree", argv[1], argc == 7 ? argv[5] : nullptr, in)) return 1;
+    const int64_t n = in.n;
+    const size_t K = cutoffs.size(), stride = (size_t)n;
+    const double t0 = now_s();
+    mgta_ctx *ctx = ctx_get();
+    std::vector<int32_t> cluster(K * stride + 1);
+    std::vector<int64_t> rep(K * stride + 1);
+    std::vector<uint16_t> rep_diff(K * stride + 1), rep_overlap(K * stride + 1);
+    std::vector<mgta_tree_merge> merges((size_t)n + 1);
+    int64_t n_merges = 0;
+    mgta_tree_stats st;
+    if (mgta_rows_clusters(ctx, (const uint8_t *)in.rows.data(), in.lens.data(), n, (int64_t)in.M, min_overlap, cutoffs.data(), (int64_t)K, cluster.data(), rep.data(),
+                           rep_diff.data(), rep_overlap.data(), merges.data(), &n_merges, &st) != MGTA_OK) {
+        fprintf(stderr, "    [ERROR] clustertree: %s: nothing written\n", mgta_last_error());
+        ctx_put(ctx);
+        return 1;
+    }
+    logf("clustertree of %lld rows of %zu columns at %zu cut-offs, overlap >= %lld: %lld kept pairs, %lld merges in %lld rounds, %lld lists rewritten, %lld entries "
+         "visited, %lld cuts by the host linkage, peak %lld B; pairs %.1f ms, lists %.1f ms, rounds %.1f ms, cuts %.1f ms; wall %.3f s", (long long)st.n_rows, in.M, K,
+         min_overlap, (long long)st.n_pairs, (long long)st.n_merges, (long long)st.n_rounds, (long long)st.n_lists_rewritten, (long long)st.n_entries_visited,
+         (long long)st.n_cut_fallbacks, (long long)st.peak_bytes, st.ms_pairs, st.ms_build, st.ms_rounds, st.ms_cut, now_s() - t0);
+    for (size_t k = 0; k < K; ++k)
+        cluster_write(in, cluster.data() + k * stride, rep.data() + k * stride, rep_diff.data() + k * stride, rep_overlap.data() + k * stride, out_prefix + "_d" + tags[k],
+                      argc == 7 ? std::string(argv[6]) + "_d" + tags[k] : "");
+    std::string tree = "#a_row\tb_row\ta\tb\tn_diff\tn_overlap\n";
+    for (int64_t m = 0; m < n_merges; ++m) {
+        const mgta_tree_merge &t = merges[(size_t)m];
+        tree += std::to_string(t.a) + "\t" + std::to_string(t.b) + "\t" + in.names[(size_t)t.a] + "\t" + in.names[(size_t)t.b] + "\t" + std::to_string(t.n_diff) + "\t" +
+                std::to_string(t.n_overlap) + "\n";
+    }
+    if (!write_text_file(out_prefix + "_tree.txt", tree)) die("cannot write %s_tree.txt", out_prefix.c_str());
     ctx_put(ctx);
     return 0;
 }
@@ -1628,7 +1717,7 @@ int main(int argc, char **argv) {
 static int dispatch(int argc, char **argv) {
     if (argc < 2) {
         fprintf(stderr, "Usage: %s <sub_program> [sub options]\n    sub-programs on the MI355X hot path:\n        buildgraph    build succinct de Bruijn graph\n"
-                        "        denovo        tips, bubbles, contigs of an intermediate k\n        search        HMM-guided search of gene contigs\n        findstart     find starting kmers of the search\n        coverage      per-contig k-mer coverage and abundance from the graph\n        sharecov      per-contig coverage shared among the windows of the file: masses that add up\n        matchreads    the reads that share a (k+1)-mer with a set of contigs\n        samplecov     per-library coverage of a set of contigs, counted from the reads\n        derep         the unique, non-contained records of a FASTA\n        align         protein records placed on the columns of a profile HMM\n        cluster       complete-linkage clusters of aligned protein records\n        nearest       the closest reference protein of every protein record\n        chimera       protein records that two references explain better than one\n        dumpversion   dump version\n", argv[0]);
+                        "        denovo        tips, bubbles, contigs of an intermediate k\n        search        HMM-guided search of gene contigs\n        findstart     find starting kmers of the search\n        coverage      per-contig k-mer coverage and abundance from the graph\n        sharecov      per-contig coverage shared among the windows of the file: masses that add up\n        matchreads    the reads that share a (k+1)-mer with a set of contigs\n        samplecov     per-library coverage of a set of contigs, counted from the reads\n        derep         the unique, non-contained records of a FASTA\n        align         protein records placed on the columns of a profile HMM\n        cluster       complete-linkage clusters of aligned protein records\n        clustertree   those clusters at several cut-offs from one merge tree\n        nearest       the closest reference protein of every protein record\n        chimera       protein records that two references explain better than one\n        dumpversion   dump version\n", argv[0]);
         return 1;
     }
     std::string sub = argv[1];
@@ -1643,6 +1732,7 @@ static int dispatch(int argc, char **argv) {
     if (sub == "derep") return main_derep(argc - 1, argv + 1);
     if (sub == "align") return main_align(argc - 1, argv + 1);
     if (sub == "cluster") return main_cluster(argc - 1, argv + 1);
+    if (sub == "clustertree") return main_clustertree(argc - 1, argv + 1);
     if (sub == "nearest") return main_nearest(argc - 1, argv + 1);
     if (sub == "chimera") return main_chimera(argc - 1, argv + 1);
     if (sub == "filterbylen") return main_filterbylen(argc - 1, argv + 1);
@@ -1747,6 +1837,6 @@ static int dispatch(int argc, char **argv) {
         return 0;
     }
     if (sub == "dumpversion") { printf("%s\n", mgta_version()); return 0; }
-    fprintf(stderr, "sub-command '%s' is not built here (buildlib, buildgraph, denovo, findstart, search, coverage, sharecov, matchreads, samplecov, derep, align, cluster, nearest, chimera, filterbylen, translate are): run it with the reference's megagta binary\n", sub.c_str());
+    fprintf(stderr, "sub-command '%s' is not built here (buildlib, buildgraph, denovo, findstart, search, coverage, sharecov, matchreads, samplecov, derep, align, cluster, clustertree, nearest, chimera, filterbylen, translate are): run it with the reference's megagta binary\n", sub.c_str());
     return 1;
 }

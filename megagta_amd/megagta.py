@@ -53,6 +53,10 @@ USAGE = """Usage:
                      nucl_merged[_rmdup]_rep_seqs.fasta (one representative per cluster: the longest member) (GPU 0)
     --cluster-dist D          largest share of differing columns inside a cluster [0.01: the reference's "99% aa identity"]
     --cluster-min-overlap N   columns two contigs must share to be compared at all [25: the reference's `dmatrix -l 25`]
+    --cluster-dists LIST      needs --cluster; after every other step: per gene the clusters at every cut-off of LIST (c1,c2,..., each
+                     written with 0-9 and `.`; the text is the tag) from one merge tree: prot_merged[_rmdup]_d<tag>_clust.txt,
+                     prot_merged[_rmdup]_d<tag>_rep_seqs.fasta, nucl_merged[_rmdup]_d<tag>_rep_seqs.fasta, prot_merged[_rmdup]_tree.txt and,
+                     with --taxon-abund / --sample-abund, prot_merged[_rmdup]_d<tag>_otu_abund.txt / _d<tag>_otu_samples[_ppm].txt (GPU 0)
     --nearest        after every other step: per gene the closest sequence of the gene's reference proteins (column 4 of the gene list)
                      for every protein contig and the identity to it: contigs/<gene>/prot_merged[_rmdup]_nearest.txt and
                      prot_merged[_rmdup]_nearest_refs.txt (per reference: its contigs and their mean identity); with --cluster the
@@ -112,6 +116,7 @@ class Opt:
         self.cluster = False
         self.cluster_dist = 0.01
         self.cluster_min_overlap = 25
+        self.cluster_dists = None
         self.nearest = False
         self.nearest_scoring = "5,-4"
         self.nearest_gap_open = 10
@@ -129,7 +134,7 @@ cp = 0
 LONG = ["help", "read=", "12=", "out-dir=", "memory=", "gpu-mem=", "min-contig-len=", "num-cpu-threads=", "kmin-1pass", "k-list=",
         "min-count=", "max-tip-len=", "no-mercy", "keep-tmp-files", "mem-flag=", "version", "verbose", "continue", "gene-list=",
         "prune-len=", "low-cov-penalty=", "bin=", "one-process-per-step", "gpus=", "coverage", "match-reads", "derep", "align", "cluster",
-        "cluster-dist=", "cluster-min-overlap=", "nearest", "nearest-scoring=", "nearest-gap-open=", "nearest-gap-extend=",
+        "cluster-dist=", "cluster-min-overlap=", "cluster-dists=", "nearest", "nearest-scoring=", "nearest-gap-open=", "nearest-gap-extend=",
         "chimera", "chimera-min-seg=", "chimera-min-gain=", "taxon-abund", "sample-abund"]
 
 
@@ -183,6 +188,7 @@ def parse_opt(argv):
         elif o == "--cluster": opt.cluster = True
         elif o == "--cluster-dist": opt.cluster_dist = float(v)
         elif o == "--cluster-min-overlap": opt.cluster_min_overlap = int(v)
+        elif o == "--cluster-dists": opt.cluster_dists = v
         elif o == "--nearest": opt.nearest = True
         elif o == "--nearest-scoring": opt.nearest_scoring = v
         elif o == "--nearest-gap-open": opt.nearest_gap_open = int(v)
@@ -247,6 +253,13 @@ def check_opt():
         raise Usage("--taxon-abund needs --align --cluster: it sums the coverage of the clusters those steps write")
     if opt.sample_abund and not (opt.align and opt.cluster):
         raise Usage("--sample-abund needs --align --cluster: it sums the coverage of the clusters those steps write")
+    if opt.cluster_dists is not None:
+        if not opt.cluster:
+            raise Usage("--cluster-dists needs --cluster: it cuts the tree of the rows that step clusters")
+        try:
+            cluster_cutoff_tags(opt.cluster_dists)
+        except ValueError as e:
+            raise Usage("--cluster-dists: " + str(e))
     if not 0 <= opt.cluster_dist <= 1:
         raise Usage("--cluster-dist should be between [0, 1]")
     if opt.cluster_min_overlap < 1:
@@ -781,6 +794,45 @@ def sample_abund(k):
         write_cp()
 
 
+def cluster_cutoff_tags(text):
+    """the tags of --cluster-dists LIST (megagta_amd/cluster.py parse_cutoff_list; ValueError says what is wrong with an item)"""
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    if root not in sys.path:
+        sys.path.insert(0, root)
+    from megagta_amd.cluster import parse_cutoff_list
+    return parse_cutoff_list(text)[0]
+
+
+def cluster_dists(k):
+    """--cluster-dists: per gene the clusters of the rows --align wrote at every cut-off of the list, from one pass over the pairs and one
+    merge tree (`megagta clustertree`, GPU 0; no graph is needed, k only names the step), and per cut-off the OTU tables of --taxon-abund
+    and --sample-abund where those ran: their coverage files do not depend on the cut-off.  The nearest / chimera joins belong to the
+    representatives of --cluster-dist and are not repeated.  One checkpoint per gene, after every other checkpoint, those of
+    --sample-abund included, so `--continue` works under any combination."""
+    stem = "_merged_rmdup" if opt.derep else "_merged"
+    tags = cluster_cutoff_tags(opt.cluster_dists)
+    for gene in opt.gene_info:
+        d = opt.out_dir + "contigs/" + gene
+        if should_run():
+            run_step([opt.bin, "clustertree", d + "/prot" + stem + "_aligned.fasta", d + "/prot" + stem, opt.cluster_dists, str(opt.cluster_min_overlap),
+                      d + "/nucl" + stem + ".fasta", d + "/nucl" + stem], "Clustering the aligned contigs of %s at %d cut-offs" % (gene, len(tags)))
+            if opt.taxon_abund or opt.sample_abund:
+                what = "Summing the clusters of %s at every cut-off" % gene
+                logging.info("--- [%s] %s ---" % (datetime.now().strftime("%c"), what))
+                from megagta_amd import samplecov, taxonabund
+                try:
+                    for tag in tags:
+                        prefix = d + "/prot" + stem + "_d" + tag
+                        if opt.taxon_abund:
+                            taxonabund.write_taxonabund(prefix, d + "/nucl" + stem + "_sharecov.txt", prefix + "_clust.txt", None, None, None)
+                        if opt.sample_abund:
+                            samplecov.write_otu_samples(prefix, d + "/nucl" + stem + "_samplecov.txt", prefix + "_clust.txt")
+                except (ValueError, OSError) as e:
+                    logging.error(str(e))
+                    fail_step("running \"%s\"" % what, 1)
+        write_cp()
+
+
 def after_search(k):
     """the opt-in steps on the last k's graph, in a fixed order behind every checkpoint of a run without them"""
     if opt.coverage:
@@ -801,6 +853,8 @@ def after_search(k):
         taxon_abund(k)
     if opt.sample_abund:
         sample_abund(k)
+    if opt.cluster_dists is not None:
+        cluster_dists(k)
 
 
 def main(argv=None):
