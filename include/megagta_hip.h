@@ -498,6 +498,70 @@ int mgta_seqs_align(mgta_ctx *, const mgta_hmm *, const char *seqs, const uint64
 int mgta_ctx_set_align_batch(mgta_ctx *, int64_t cells);   /* 0 = by memory (default) */
 
 /* ------------------------------------------------------------------------------------------------
+ * Forward score and per-residue posteriors of protein sequences on a profile HMM: how far a placement of mgta_seqs_align can be
+ * trusted (what a user of `hmmalign` read from its PP lines and a user of Xander from a bit score).  The rule below is this
+ * library's own, as mgta_seqs_align's is: HMMER is on none of the project's machines and nothing here is checked against it.  No
+ * optimal-accuracy re-alignment is made from the posteriors.  Needs no graph.
+ *   Tables, residues, mode and WHICH CELLS EXIST are exactly mgta_seqs_align's: global in the sequence, local in the model; the
+ *              first residue is emitted by some match state at no entry cost, the last one by some match state; insert emissions
+ *              are 0; the insert state exists for i > 1 and j < M, the delete state for i > 1 and j > 1, and FM[i][j] for i > 1
+ *              needs j > 1.  e(j, i) = msc[j][alpha[x_i]], or 0 for a letter without a column; t.. is the transition OUT OF the
+ *              node named.  Whatever is not defined is -inf.
+ *   lse.       Every max of that rule becomes lse(a, b, c) = m + log(exp(a - m) + exp(b - m) + exp(c - m)), m = max(a, b, c); with
+ *              m = -inf the result is -inf.  -inf - -inf is never evaluated, so `*` entries of a model stay legal and no NaN
+ *              arises.  Everything is fp64.
+ *   Forward (i = 1 .. L, j = 1 .. M):
+ *              FM[1][j] = e(j, 1)
+ *              FM[i][j] = lse(FM[i-1][j-1] + tMM[j-1], FI[i-1][j-1] + tIM[j-1], FD[i-1][j-1] + tDM[j-1]) + e(j, i)     i > 1, j > 1
+ *              FI[i][j] = lse(FM[i-1][j] + tMI[j], FI[i-1][j] + tII[j])                                                i > 1, j < M
+ *              FD[i][j] = lse(FM[i][j-1] + tMD[j-1], FD[i][j-1] + tDD[j-1])                                            i > 1, j > 1
+ *              F = lse over j of FM[L][j]
+ *   Backward (i = L .. 1, j = M .. 1), with N(i, j) = e(j+1, i+1) + BM[i+1][j+1] for j < M, else -inf:
+ *              BM[L][j] = 0;  BI[L][j] = BD[L][j] = -inf
+ *              BM[i][j] = lse(tMM[j] + N(i, j), tMI[j] + BI[i+1][j] (j < M), tMD[j] + BD[i][j+1] (j < M and i > 1))    i < L
+ *              BI[i][j] = lse(tIM[j] + N(i, j), tII[j] + BI[i+1][j])                                                   1 < i < L, j < M
+ *              BD[i][j] = lse(tDM[j] + N(i, j), tDD[j] + BD[i][j+1])                                                   1 < i < L, 1 < j < M
+ *              Bt = lse over j of e(j, 1) + BM[1][j]       (equals F up to rounding; reported as a check value)
+ *   Posteriors. PM[i][j] = exp(FM[i][j] + BM[i][j] - F), PI[i][j] = exp(FI[i][j] + BI[i][j] - F); 0 where either factor is -inf.
+ *              For every residue i the sum over j of PM[i][j] + PI[i][j] is 1.
+ *   Unaligned. L == 0 or F == -inf (exactly when mgta_seqs_align calls the sequence unaligned): status 1, fwd = bwd = -inf, zeros
+ *              everywhere else.
+ * Labels: labels[r] (r as in seqs: offsets[i] + the residue's place) names the state whose posterior pp[r] is: +j the match state
+ * of node j, -j the insert state of node j (1 <= j < M), 0 none (pp[r] = 0).  Any labelling is evaluated, not only Viterbi's; the
+ * callers above pass the one the path of mgta_seqs_align gives.  Outputs: recs[i]; pp[offsets[0] .. offsets[n]) when given (needs
+ * labels); col_match[i*M + j-1] = sum over the rows of PM[.][j] and col_insert[i*M + j-1] = that of PI[.][j] when given.  Everything
+ * but stats.ms_*, n_batches and the residency fields (workgroups, waves_per_block, blocks_per_cu, lds_bytes, msc_in_lds,
+ * peak_bytes) is a function of (tables, sequences, labels), the same to the last bit whatever the batch and across runs: every
+ * output has one writer and one fixed order of additions.  mgta_ctx_set_posterior_batch (cells = L * M of one batch; 0 = by the
+ * context's free memory; a batch always holds at least one sequence) is a switch for tests and moves no output.  Limits: L <= 4096
+ * residues per sequence and n < 2^31; beyond, MGTA_EINVAL names the limit.  Device memory: the letters, the labels and pp, 16 bytes
+ * per cell of a batch (FM and FI) and the batch's outputs, accounted like every other buffer; what does not fit is MGTA_ENOMEM.
+ * MGTA_EINVAL: NULL context / model / recs / offsets (n > 0), pp without labels, n < 0, descending offsets, a model of another
+ * context, a label above M or below -(M - 1) (the first one is named); nothing is written.  n = 0: MGTA_OK, stats all zero.
+ * ------------------------------------------------------------------------------------------------ */
+typedef struct mgta_post_rec {
+    double fwd, bwd;                       /* F and Bt in nats; -inf when unaligned */
+    int32_t status, pad;                   /* 0 scored, 1 unaligned */
+} mgta_post_rec;
+typedef struct mgta_post_stats {
+    int64_t n_seqs, n_scored, n_unaligned;
+    int64_t n_cells;                       /* sum of L * M */
+    int64_t n_batches;
+    int64_t workgroups;                    /* of the largest launch */
+    int64_t waves_per_block;               /* sequences in flight per workgroup: 4, 2 or 1 by the longest sequence of the batch (smallest over the batches) */
+    int64_t blocks_per_cu;                 /* what the runtime answered, the smaller of the two kernels (largest over the batches) */
+    int64_t lds_bytes;                     /* LDS of a workgroup of the backward kernel (largest over the batches) */
+    int64_t msc_in_lds;                    /* 1: every batch read the match scores from LDS; 0: some batch read them from device memory */
+    int64_t peak_bytes;                    /* most device memory the context held during the call */
+    double ms_forward, ms_backward;        /* HIP events, summed over the batches */
+} mgta_post_stats;
+int mgta_seqs_posterior(mgta_ctx *, const mgta_hmm *, const char *seqs, const uint64_t *offsets /* [n + 1] */, int64_t n,
+                        const int32_t *labels /* [offsets[n]] or NULL */, mgta_post_rec *recs /* [n] */,
+                        double *pp /* [offsets[n]] or NULL; needs labels */, double *col_match /* [n * M] or NULL */,
+                        double *col_insert /* [n * M] or NULL */, mgta_post_stats *stats /* may be NULL */);
+int mgta_ctx_set_posterior_batch(mgta_ctx *, int64_t cells);   /* 0 = by memory (default); a switch for tests, moves no output */
+
+/* ------------------------------------------------------------------------------------------------
  * Complete-linkage clusters of aligned rows ("cluster at 99% aa identity", the reference's bin/post_proc.sh:57-85: `Clustering.jar
  * dmatrix -l 25`, `cluster`, `rep-seqs -l <cutoff>`, from a submodule the reference does not ship; the rule below is this library's
  * own and is not checked against the jars).  Needs no graph.  Input: n rows of M bytes, row r = rows[r*M .. (r+1)*M), the `cols` rows

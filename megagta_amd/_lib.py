@@ -139,6 +139,19 @@ class AlignStats(C.Structure):
         return {n: getattr(self, n) for n, _ in self._fields_}
 
 
+class PostRec(C.Structure):
+    _fields_ = [("fwd", C.c_double), ("bwd", C.c_double), ("status", C.c_int32), ("pad", C.c_int32)]
+
+
+class PostStats(C.Structure):
+    _fields_ = [("n_seqs", C.c_int64), ("n_scored", C.c_int64), ("n_unaligned", C.c_int64), ("n_cells", C.c_int64), ("n_batches", C.c_int64),
+                ("workgroups", C.c_int64), ("waves_per_block", C.c_int64), ("blocks_per_cu", C.c_int64), ("lds_bytes", C.c_int64),
+                ("msc_in_lds", C.c_int64), ("peak_bytes", C.c_int64), ("ms_forward", C.c_double), ("ms_backward", C.c_double)]
+
+    def as_dict(self):
+        return {n: getattr(self, n) for n, _ in self._fields_}
+
+
 class RowPair(C.Structure):
     _fields_ = [("i", C.c_int32), ("j", C.c_int32), ("n_diff", C.c_uint16), ("n_overlap", C.c_uint16)]
 
@@ -259,6 +272,9 @@ SYMBOLS = {
     "mgta_ctx_set_derep_hash_bits": (C.c_int, [C.c_void_p, C.c_int]),
     "mgta_seqs_align": (C.c_int, [C.c_void_p, C.c_void_p, C.c_char_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "mgta_ctx_set_align_batch": (C.c_int, [C.c_void_p, C.c_int64]),
+    "mgta_seqs_posterior": (C.c_int, [C.c_void_p, C.c_void_p, C.c_char_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                                      C.c_void_p]),
+    "mgta_ctx_set_posterior_batch": (C.c_int, [C.c_void_p, C.c_int64]),
     "mgta_rows_pairs": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_int64, C.c_int64, C.c_double, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p]),
     "mgta_rows_cluster": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_int64, C.c_int64, C.c_double, C.c_void_p, C.c_void_p, C.c_void_p,
                                     C.c_void_p, C.c_void_p]),

@@ -168,6 +168,46 @@ class Context:
             out["paths"] = [p[int(offsets[i]) + i * M:int(offsets[i]) + i * M + int(plen[i])].tobytes().decode() for i in range(n)]
         return out
 
+    def set_posterior_batch(self, cells: int = 0):
+        """cells (L * M) of one batch of `posterior` (0 = the default: by the context's free memory); a batch holds at least one
+        sequence.  For tests: no output depends on it; only stats["n_batches"] and the residency fields do."""
+        check(self._L.mgta_ctx_set_posterior_batch(self.h, int(cells)), "mgta_ctx_set_posterior_batch")
+
+    def posterior(self, hmm: "DeviceHmm", seqs, labels=None, cols: bool = True) -> dict:
+        """mgta_seqs_posterior: the Forward score of every sequence of `seqs` (str or bytes) on `hmm` and the posteriors of its residues
+        (the rule: include/megagta_hip.h) -> dict(recs = structured array [n] with fwd, bwd (nats; -inf when unaligned) and status
+        (0 scored, 1 unaligned); pp = list of float64 arrays, one per sequence, when `labels` is given: per residue the posterior of the
+        state its label names (+j the match state of node j, -j its insert state, 0 none), `labels` being one sequence of ints per
+        sequence (posterior.labels_from_path makes Viterbi's); col_match, col_insert = float64[n, M] when `cols`: the posteriors of
+        every match / insert state summed over the residues; stats).  Needs no graph."""
+        raw = [s if isinstance(s, (bytes, bytearray)) else str(s).encode() for s in seqs]
+        n, M = len(raw), hmm.M
+        offsets = np.zeros(n + 1, dtype=np.uint64)
+        if n:
+            np.cumsum([len(s) for s in raw], out=offsets[1:])
+        total = int(offsets[n])
+        lab = pp = None
+        if labels is not None:
+            if len(labels) != n or any(len(l) != len(s) for l, s in zip(labels, raw)):
+                raise ValueError("posterior: one label per residue of every sequence")
+            lab = np.zeros(total + 1, dtype=np.int32)
+            if total:
+                lab[:total] = np.concatenate([np.asarray(l, dtype=np.int32).reshape(-1) for l in labels])
+            pp = np.zeros(total + 1, dtype=np.float64)
+        recs = np.zeros(max(1, n), dtype=POST_REC)
+        cm = np.zeros((max(1, n), M), dtype=np.float64) if cols else None
+        ci = np.zeros((max(1, n), M), dtype=np.float64) if cols else None
+        st = _lib.PostStats()
+        check(self._L.mgta_seqs_posterior(self.h, hmm.h, b"".join(raw), offsets.ctypes.data, n, lab.ctypes.data if lab is not None else None, recs.ctypes.data,
+                                          pp.ctypes.data if pp is not None else None, cm.ctypes.data if cols else None, ci.ctypes.data if cols else None,
+                                          C.byref(st)), "mgta_seqs_posterior")
+        out = dict(recs=recs[:n], stats=st.as_dict())
+        if pp is not None:
+            out["pp"] = [pp[int(offsets[i]):int(offsets[i + 1])].copy() for i in range(n)]
+        if cols:
+            out["col_match"], out["col_insert"] = cm[:n], ci[:n]
+        return out
+
     def set_cluster_tile(self, rows: int = 0):
         """rows of one row block of `row_pairs` / `cluster` (0 = the default): the device works on one row block x row block tile at a
         time.  For tests: the result does not depend on it; only stats["n_tiles"] does."""
@@ -628,6 +668,8 @@ class Graph:
     __del__ = free
 
 
+# mgta_post_rec
+POST_REC = np.dtype([("fwd", np.float64), ("bwd", np.float64), ("status", np.int32), ("pad", np.int32)], align=True)
 # mgta_align_rec
 ALIGN_REC = np.dtype([("score", np.float64), ("status", np.int32), ("model_from", np.int32), ("model_to", np.int32), ("n_match", np.int32),
                       ("n_insert", np.int32), ("n_delete", np.int32)], align=True)

@@ -142,6 +142,7 @@ struct mgta_ctx {
     int keep_multiplicity = 0;
     uint64_t coverage_batch_windows = 0;   // mgta_ctx_set_coverage_batch (0 = the library's default)
     uint64_t align_batch_cells = 0;        // mgta_ctx_set_align_batch: cells (L * M) of one batch of mgta_seqs_align (0 = by free memory)
+    uint64_t posterior_batch_cells = 0;    // mgta_ctx_set_posterior_batch: cells (L * M) of one batch of mgta_seqs_posterior (0 = by free memory)
     uint64_t nearest_batch_cells = 0;      // mgta_ctx_set_nearest_batch: cells (L * R) of one trace batch of mgta_seqs_nearest (0 = by free memory)
     uint64_t chimera_segment_cols = 0;     // mgta_ctx_set_chimera_segment: reference columns of one segment of mgta_seqs_chimera (0 = the library's default)
     uint64_t chimera_groups = 0;           // mgta_ctx_set_chimera_groups: groups of segments per (contig, direction) of mgta_seqs_chimera (0 = by the number of contigs)

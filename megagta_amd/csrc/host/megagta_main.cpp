@@ -16,6 +16,7 @@
 #include <unistd.h>
 #include <sys/time.h>
 
+#include <cmath>
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
@@ -1201,6 +1202,103 @@ static int main_align(int argc, char **argv) {
     return 0;
 }
 
+// ---- posterior: the Forward score of a gene's protein contigs on the gene's profile HMM and the posterior of every residue on the path
+// `align` gives it (mgta_seqs_align for the path, then mgta_seqs_posterior; the rule and the PP code are this project's own).  Needs no
+// graph and leaves a worker's resident graphs alone.  Formats: INTEGRATION.md 2j'.
+static char pp_char(double p) {
+    const double q = p + 0.05;
+    return q >= 1.0 ? '*' : (char)('0' + (int)std::floor(q * 10.0));
+}
+
+static int main_posterior(int argc, char **argv) {
+    if (argc != 4) { fprintf(stderr, "Usage: megagta posterior <model.hmm> <prot.fasta> <out_prefix>\n"); return 1; }
+    RssLine rss;
+    const std::string fasta = argv[2], out_prefix = argv[3];
+    std::vector<std::string> names, headers;
+    std::string seqs;
+    std::vector<uint64_t> offsets;
+    read_fasta_records(fasta, names, seqs, offsets, &headers);
+    const int64_t n = (int64_t)names.size();
+    const double t0 = now_s();
+    mgta_ctx *ctx = ctx_get();
+    ProfileHmm model;
+    if (!parse_hmm(argv[1], model)) die("cannot open HMM %s", argv[1]);
+    mgta_hmm *hm = nullptr;
+    if (mgta_hmm_load(ctx, model.M, model.A, model.msc.data(), model.tsc.data(), model.max_match.data(), model.h.data(), model.alpha, &hm) != MGTA_OK)
+        die("mgta_hmm_load(%s): %s", argv[1], mgta_last_error());
+    const size_t M = (size_t)model.M;
+    std::vector<mgta_align_rec> recs((size_t)n + 1);
+    std::vector<uint8_t> cols((size_t)n * M + 1);
+    std::vector<char> path(seqs.size() + (size_t)n * M + 1);
+    std::vector<int32_t> plen((size_t)n + 1);
+    mgta_align_stats ast;
+    if (mgta_seqs_align(ctx, hm, seqs.data(), offsets.data(), n, recs.data(), cols.data(), path.data(), plen.data(), &ast) != MGTA_OK)
+        die("mgta_seqs_align: %s", mgta_last_error());
+    // the label of every residue: the state of the path that emitted it (0 for the residues of an unaligned record)
+    std::vector<int32_t> labels(seqs.size() + 1, 0);
+    for (int64_t i = 0; i < n; ++i) {
+        const size_t u = (size_t)i;
+        if (recs[u].status != 0) continue;
+        const char *p = path.data() + offsets[u] + u * M;
+        int32_t j = recs[u].model_from - 1;
+        uint64_t r = offsets[u];
+        for (int32_t s = 0; s < plen[u]; ++s) {
+            if (p[s] == 'M') labels[r++] = ++j;
+            else if (p[s] == 'I') labels[r++] = -j;
+            else ++j;
+        }
+    }
+    std::vector<mgta_post_rec> post((size_t)n + 1);
+    std::vector<double> pp(seqs.size() + 1, 0.0);
+    mgta_post_stats st;
+    if (mgta_seqs_posterior(ctx, hm, seqs.data(), offsets.data(), n, labels.data(), post.data(), pp.data(), nullptr, nullptr, &st) != MGTA_OK)
+        die("mgta_seqs_posterior: %s", mgta_last_error());
+    logf("posterior of %lld records on %zu columns: %lld scored, %lld unaligned; %lld cells in %lld batches, %lld workgroups of %lld waves, %lld per CU, %lld B of LDS, "
+         "match scores in %s; peak %lld B; forward %.1f ms, backward %.1f ms; wall %.3f s", (long long)st.n_seqs, M, (long long)st.n_scored, (long long)st.n_unaligned,
+         (long long)st.n_cells, (long long)st.n_batches, (long long)st.workgroups, (long long)st.waves_per_block, (long long)st.blocks_per_cu, (long long)st.lds_bytes,
+         st.msc_in_lds ? "LDS" : "device memory", (long long)st.peak_bytes, st.ms_forward, st.ms_backward, now_s() - t0);
+    std::string fa, table = "#contig\tlen\tstatus\tfwd_nats\tfwd_bits\tviterbi\tmean_pp\tmin_pp\tn_below_half\n";
+    char num[256];
+    for (int64_t i = 0; i < n; ++i) {
+        const size_t u = (size_t)i;
+        const bool un = post[u].status != 0 || recs[u].status != 0;
+        const uint64_t L = offsets[u + 1] - offsets[u];
+        const double *q = pp.data() + offsets[u];
+        fa += ">" + headers[u] + "\n";
+        if (un) fa.append(M, '.');
+        else {
+            const char *p = path.data() + offsets[u] + u * M;
+            size_t xi = 0, j = (size_t)recs[u].model_from - 1;
+            fa.append(j, '.');
+            for (int32_t s = 0; s < plen[u]; ++s) {
+                if (p[s] == 'D') { fa += '.'; ++j; }
+                else { fa += pp_char(q[xi++]); j += p[s] == 'M'; }
+            }
+            fa.append(M - j, '.');
+        }
+        fa += "\n";
+        table += names[u] + "\t" + std::to_string(L) + "\t";
+        if (un) table += "unaligned\t-inf\t-inf\t-inf\t0.0000\t0.0000\t0\n";
+        else {
+            double total = 0.0, low = q[0];
+            long long below = 0;
+            for (uint64_t r = 0; r < L; ++r) {
+                total += q[r];
+                if (q[r] < low) low = q[r];
+                below += q[r] < 0.5;
+            }
+            snprintf(num, sizeof num, "scored\t%.4f\t%.4f\t%.4f\t%.4f\t%.4f\t%lld\n", post[u].fwd, post[u].fwd / 0.6931471805599453, recs[u].score, total / (double)L, low,
+                     below);
+            table += num;
+        }
+    }
+    mgta_hmm_free(hm);
+    if (!write_text_file(out_prefix + "_posterior.txt", table)) die("cannot write %s_posterior.txt", out_prefix.c_str());
+    if (!write_text_file(out_prefix + "_aligned_pp.fasta", fa)) die("cannot write %s_aligned_pp.fasta", out_prefix.c_str());
+    ctx_put(ctx);
+    return 0;
+}
+
 // ---- cluster: complete-linkage clusters of a gene's aligned protein contigs, their representatives and the nucleotide records those select
 // ("cluster at 99% aa identity", bin/post_proc.sh:57-85; the rule is mgta_rows_cluster's own).  Needs no graph and leaves a worker's resident
 // graphs alone.  Formats: INTEGRATION.md 2k.
@@ -1717,7 +1815,7 @@ int main(int argc, char **argv) {
 static int dispatch(int argc, char **argv) {
     if (argc < 2) {
         fprintf(stderr, "Usage: %s <sub_program> [sub options]\n    sub-programs on the MI355X hot path:\n        buildgraph    build succinct de Bruijn graph\n"
-                        "        denovo        tips, bubbles, contigs of an intermediate k\n        search        HMM-guided search of gene contigs\n        findstart     find starting kmers of the search\n        coverage      per-contig k-mer coverage and abundance from the graph\n        sharecov      per-contig coverage shared among the windows of the file: masses that add up\n        matchreads    the reads that share a (k+1)-mer with a set of contigs\n        samplecov     per-library coverage of a set of contigs, counted from the reads\n        derep         the unique, non-contained records of a FASTA\n        align         protein records placed on the columns of a profile HMM\n        cluster       complete-linkage clusters of aligned protein records\n        clustertree   those clusters at several cut-offs from one merge tree\n        nearest       the closest reference protein of every protein record\n        chimera       protein records that two references explain better than one\n        dumpversion   dump version\n", argv[0]);
+                        "        denovo        tips, bubbles, contigs of an intermediate k\n        search        HMM-guided search of gene contigs\n        findstart     find starting kmers of the search\n        coverage      per-contig k-mer coverage and abundance from the graph\n        sharecov      per-contig coverage shared among the windows of the file: masses that add up\n        matchreads    the reads that share a (k+1)-mer with a set of contigs\n        samplecov     per-library coverage of a set of contigs, counted from the reads\n        derep         the unique, non-contained records of a FASTA\n        align         protein records placed on the columns of a profile HMM\n        posterior     Forward score and per-residue confidence of aligned protein records\n        cluster       complete-linkage clusters of aligned protein records\n        clustertree   those clusters at several cut-offs from one merge tree\n        nearest       the closest reference protein of every protein record\n        chimera       protein records that two references explain better than one\n        dumpversion   dump version\n", argv[0]);
         return 1;
     }
     std::string sub = argv[1];
@@ -1731,6 +1829,7 @@ static int dispatch(int argc, char **argv) {
     if (sub == "samplecov") return main_samplecov(argc - 1, argv + 1);
     if (sub == "derep") return main_derep(argc - 1, argv + 1);
     if (sub == "align") return main_align(argc - 1, argv + 1);
+    if (sub == "posterior") return main_posterior(argc - 1, argv + 1);
     if (sub == "cluster") return main_cluster(argc - 1, argv + 1);
     if (sub == "clustertree") return main_clustertree(argc - 1, argv + 1);
     if (sub == "nearest") return main_nearest(argc - 1, argv + 1);
@@ -1837,6 +1936,6 @@ static int dispatch(int argc, char **argv) {
         return 0;
     }
     if (sub == "dumpversion") { printf("%s\n", mgta_version()); return 0; }
-    fprintf(stderr, "sub-command '%s' is not built here (buildlib, buildgraph, denovo, findstart, search, coverage, sharecov, matchreads, samplecov, derep, align, cluster, clustertree, nearest, chimera, filterbylen, translate are): run it with the reference's megagta binary\n", sub.c_str());
+    fprintf(stderr, "sub-command '%s' is not built here (buildlib, buildgraph, denovo, findstart, search, coverage, sharecov, matchreads, samplecov, derep, align, posterior, cluster, clustertree, nearest, chimera, filterbylen, translate are): run it with the reference's megagta binary\n", sub.c_str());
     return 1;
 }

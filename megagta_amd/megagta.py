@@ -48,6 +48,11 @@ USAGE = """Usage:
                      of the gene's forward model: contigs/<gene>/prot_merged_aligned.fasta (A2M rows) and prot_merged_aligned.txt (score,
                      columns and counts per contig); with --derep the input is prot_merged_rmdup.fasta and the files are
                      prot_merged_rmdup_aligned.* (GPU 0)
+    --posterior      needs --align; directly behind every gene's --align step and on the same input: the Forward score of every contig
+                     on the gene's forward model and the posterior of every residue on the path --align gave it:
+                     contigs/<gene>/prot_merged[_rmdup]_posterior.txt (Forward score in nats and bits, the Viterbi score, mean and
+                     lowest posterior per contig) and prot_merged[_rmdup]_aligned_pp.fasta (one PP line per row of
+                     ..._aligned.fasta, column for column); the rule is this project's own, not hmmalign's (GPU 0)
     --cluster        needs --align; after its steps: per gene the complete-linkage clusters of the aligned rows,
                      contigs/<gene>/prot_merged[_rmdup]_clust.txt (what became of every contig), prot_merged[_rmdup]_rep_seqs.fasta and
                      nucl_merged[_rmdup]_rep_seqs.fasta (one representative per cluster: the longest member) (GPU 0)
@@ -113,6 +118,7 @@ class Opt:
         self.match_reads = False
         self.derep = False
         self.align = False
+        self.posterior = False
         self.cluster = False
         self.cluster_dist = 0.01
         self.cluster_min_overlap = 25
@@ -133,7 +139,7 @@ cp = 0
 
 LONG = ["help", "read=", "12=", "out-dir=", "memory=", "gpu-mem=", "min-contig-len=", "num-cpu-threads=", "kmin-1pass", "k-list=",
         "min-count=", "max-tip-len=", "no-mercy", "keep-tmp-files", "mem-flag=", "version", "verbose", "continue", "gene-list=",
-        "prune-len=", "low-cov-penalty=", "bin=", "one-process-per-step", "gpus=", "coverage", "match-reads", "derep", "align", "cluster",
+        "prune-len=", "low-cov-penalty=", "bin=", "one-process-per-step", "gpus=", "coverage", "match-reads", "derep", "align", "posterior", "cluster",
         "cluster-dist=", "cluster-min-overlap=", "cluster-dists=", "nearest", "nearest-scoring=", "nearest-gap-open=", "nearest-gap-extend=",
         "chimera", "chimera-min-seg=", "chimera-min-gain=", "taxon-abund", "sample-abund"]
 
@@ -185,6 +191,7 @@ def parse_opt(argv):
         elif o == "--match-reads": opt.match_reads = True
         elif o == "--derep": opt.derep = True
         elif o == "--align": opt.align = True
+        elif o == "--posterior": opt.posterior = True
         elif o == "--cluster": opt.cluster = True
         elif o == "--cluster-dist": opt.cluster_dist = float(v)
         elif o == "--cluster-min-overlap": opt.cluster_min_overlap = int(v)
@@ -247,6 +254,8 @@ def detect_available_mem():
 
 
 def check_opt():
+    if opt.posterior and not opt.align:
+        raise Usage("--posterior needs --align: it scores the path that step finds")
     if opt.cluster and not opt.align:
         raise Usage("--cluster needs --align: it clusters the rows that step writes")
     if opt.taxon_abund and not (opt.align and opt.cluster):
@@ -688,12 +697,18 @@ def derep(k):
 def align(k):
     """--align: per gene the protein contigs placed on the columns of the gene's forward model (`megagta align`, GPU 0; no graph is
     needed, k only names the step).  The input is what --derep kept when that flag runs too.  Its checkpoints come after every other
-    checkpoint, those of --coverage, --match-reads and --derep included, so `--continue` works under any of them."""
+    checkpoint, those of --coverage, --match-reads and --derep included, so `--continue` works under any of them.  With --posterior
+    every gene's step is followed by `megagta posterior` on the same input, with a checkpoint of its own."""
     for gene in opt.gene_info:
         prefix = opt.out_dir + "contigs/" + gene + ("/prot_merged_rmdup" if opt.derep else "/prot_merged")
         if should_run():
             run_step([opt.bin, "align", opt.gene_info[gene][0], prefix + ".fasta", prefix], "Aligning the contigs of %s to its model" % gene)
         write_cp()
+        if opt.posterior:
+            if should_run():
+                run_step([opt.bin, "posterior", opt.gene_info[gene][0], prefix + ".fasta", prefix],
+                         "Scoring the placement of the contigs of %s on its model" % gene)
+            write_cp()
 
 
 def cluster(k):
