@@ -414,6 +414,64 @@ int mgta_contig_sample_coverage(mgta_sdbg *, const mgta_reads *reads, int reads_
                                 mgta_sample_cov_stats *stats /* optional */);
 
 /* ------------------------------------------------------------------------------------------------
+ * Pileup: the reads placed on the contigs of ONE set (a gene's FASTA), per-base depth in the contig's strand, the reads that fit a
+ * contig end to end, the positions where the reads disagree with it.  The rule is this project's own; no mapper is consulted.  Any
+ * loaded graph serves (no multiplicities needed); the reads [0, n_short_reads) are scanned; reads_reversed as in
+ * mgta_reads_match_contigs.
+ *   Read     s = the packed bases as sequenced (an N of the input is a G); s^0 = s, s^1 = revcomp(s), L its length.
+ *   Contig   c_i = its letters folded to upper case; a letter other than A, C, G, T equals no base, a window that holds one is no key.
+ *   Anchor   (o, p, i, q): window p of s^o and window q of c_i are the same k + 1 letters and that (k+1)-mer has an edge in the graph
+ *            (found by the read's walk: a graph built from these reads holds both strands of all their windows; the validity bit of
+ *            an edge is not looked at).  On any other graph a window without an edge anchors nothing.
+ *   Candidate  a distinct (i, o, d) with at least one anchor on the diagonal d = q - p (d may be negative, d + L may exceed len_i).
+ *            votes = its anchors (distinct p); overlap = the positions x in [max(0, d), min(len_i, d + L)), n_ov their number; n_mm =
+ *            the number of x with c_i[x] != s^o[x - d]; score = n_ov - 2 * n_mm.
+ *   Pass     votes >= min_anchors (default 1), n_ov >= min_overlap (default k + 1), n_mm * 1000 <= max_mismatch_permille * n_ov
+ *            (default 50).  A parameter given as 0 takes its default.
+ *   Placements of a read = ALL passing candidates with the read's highest score; ties are all placed.  Two equal contigs give two
+ *            placements, two diagonals of one contig (an internal repeat) are two candidates, and a read equal to its own reverse
+ *            complement has the candidates o = 0 and o = 1 and may be placed on both: nothing is special-cased.
+ *   Pile     every placement adds 1 to counts[(offsets[i] + x) * 4 + b] for every x of its overlap, b = s^o[x - d] (A C G T = 0 1 2 3);
+ *            a read with exactly one placement also adds 1 to uniq[offsets[i] + x].  depth = A + C + G + T.
+ * per_contig (may be NULL): len; n_covered = positions with depth > 0; min_depth, max_depth over all positions (0 for len 0);
+ * n_placed = placements on the contig, n_unique = those of reads placed once; depth_sum; mismatch_sum = the sum of n_mm over the
+ * placements.  per_read (may be NULL): the lowest placement by (contig, orient, diag) with its score and n_mismatch (which all ties
+ * share the score of), n_placed = the number of placements; {0, -1, 0, 0, 0, 0} for a read without one.  No output and no stats field
+ * but ms_* depends on the order of anything: all sums are integers, the choice is a maximum over a total order; neither
+ * mgta_ctx_set_pileup_chunk nor mgta_ctx_set_share_hash_bits moves any.  Uses the graph's mark bits, cleared at the start of the call.
+ * Limits, each MGTA_EINVAL naming it with nothing written: k + 1 <= 128, n < 2^31, offsets[0] = 0 and offsets[n] < 2^32, reads of at
+ * most 65535 bases, no negative parameter, permille <= 1000.  MGTA_EINVAL too for a NULL graph, reads or counts and for a graph and
+ * reads of different contexts.  All contigs of the call are resident at once (the best-hit rule needs them): 2 bytes per letter, 8 per
+ * window for the two slot numbers, 16 per table slot, 8 per occurrence (at most 2 per window), 20 per letter for counts and uniq, one
+ * 32-bit word per window of the longest read for every group of lanes in flight; what does not fit is MGTA_ENOMEM, nothing is
+ * truncated and there is no cap on candidates.  n = 0 or n_short_reads = 0: MGTA_OK, counts and stats zero.
+ * ------------------------------------------------------------------------------------------------ */
+typedef struct mgta_pileup_params { int32_t min_anchors, min_overlap, max_mismatch_permille; } mgta_pileup_params;  /* 0 = the default of each */
+typedef struct mgta_contig_pileup { uint32_t len, n_covered, min_depth, max_depth; uint64_t n_placed, n_unique, depth_sum, mismatch_sum; } mgta_contig_pileup;
+typedef struct mgta_read_place { int32_t score, contig, diag, orient; uint32_t n_placed, n_mismatch; } mgta_read_place;
+typedef struct mgta_pileup_stats {
+    int64_t n_contigs, n_contig_letters, n_contig_windows;
+    int64_t n_keys;                  /* distinct edges of the contig windows, both strands */
+    int64_t n_occurrences;           /* entries of the occurrence index: (contig, window, strand) per key */
+    int64_t n_reads, n_read_windows; /* reads scanned; sum max(0, len - k) over them */
+    int64_t n_hit_windows;           /* read windows whose edge is a key */
+    int64_t n_read_walked, n_read_index_searches;
+    int64_t n_reads_with_candidate, n_candidates;
+    int64_t n_verified;              /* anchors that start a run on their diagonal: each is compared along its whole overlap */
+    int64_t n_reads_placed, n_reads_multi, n_placements;
+    int64_t n_bases_piled;           /* the sum of all counts */
+    int64_t groups_per_cu;           /* as in mgta_coverage_stats, for the read scan */
+    uint64_t peak_bytes;             /* most device bytes of the call's own buffers */
+    double ms_keys, ms_index, ms_scan, ms_records, ms_total;   /* HIP events */
+} mgta_pileup_stats;
+int mgta_reads_pileup(mgta_sdbg *, const mgta_reads *reads, int reads_reversed, uint64_t n_short_reads, const char *seqs,
+                      const uint64_t *offsets /* [n + 1] */, int64_t n, const mgta_pileup_params *params /* NULL = defaults */,
+                      uint32_t *counts /* [offsets[n] * 4], A C G T */, uint32_t *uniq /* [offsets[n]] or NULL */,
+                      mgta_contig_pileup *per_contig /* [n] or NULL */, mgta_read_place *per_read /* [n_short_reads] or NULL */,
+                      mgta_pileup_stats *stats /* or NULL */);
+int mgta_ctx_set_pileup_chunk(mgta_ctx *, uint32_t reads);   /* reads per queue grab, 0 = the library's; a switch for tests, moves no output */
+
+/* ------------------------------------------------------------------------------------------------
  * De-replication ("get the unique merged contigs", the first step of the reference's bin/post_proc.sh:50-55: `Clustering.jar derep`,
  * then `ReadSeq.jar rm-dupseq -d`, both from a submodule the reference does not ship).  Needs no graph.  Sequence i =
  * seqs[offsets[i] .. offsets[i + 1]), a byte string compared byte for byte: no case folding, no reverse complement (a gene's contigs

@@ -206,6 +206,22 @@ class ChimeraStats(C.Structure):
         return {n: getattr(self, n) for n, _ in self._fields_}
 
 
+class PileupParams(C.Structure):
+    _fields_ = [("min_anchors", C.c_int32), ("min_overlap", C.c_int32), ("max_mismatch_permille", C.c_int32)]
+
+
+class PileupStats(C.Structure):
+    _fields_ = [("n_contigs", C.c_int64), ("n_contig_letters", C.c_int64), ("n_contig_windows", C.c_int64), ("n_keys", C.c_int64), ("n_occurrences", C.c_int64),
+                ("n_reads", C.c_int64), ("n_read_windows", C.c_int64), ("n_hit_windows", C.c_int64), ("n_read_walked", C.c_int64),
+                ("n_read_index_searches", C.c_int64), ("n_reads_with_candidate", C.c_int64), ("n_candidates", C.c_int64), ("n_verified", C.c_int64),
+                ("n_reads_placed", C.c_int64), ("n_reads_multi", C.c_int64), ("n_placements", C.c_int64), ("n_bases_piled", C.c_int64),
+                ("groups_per_cu", C.c_int64), ("peak_bytes", C.c_uint64), ("ms_keys", C.c_double), ("ms_index", C.c_double), ("ms_scan", C.c_double),
+                ("ms_records", C.c_double), ("ms_total", C.c_double)]
+
+    def as_dict(self):
+        return {n: getattr(self, n) for n, _ in self._fields_}
+
+
 EDGE_SINK = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_int32, C.c_int32, C.POINTER(C.c_int64), C.POINTER(C.c_uint16), C.c_int64,
                         C.POINTER(C.c_uint16), C.c_int64, C.POINTER(C.c_uint32), C.c_int64)
 CONTIG_SINK = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_void_p, C.c_int64,
@@ -268,6 +284,9 @@ SYMBOLS = {
                                           C.c_void_p]),
     "mgta_contig_sample_coverage": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_char_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p,
                                              C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "mgta_reads_pileup": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_uint64, C.c_char_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                                   C.c_void_p, C.c_void_p]),
+    "mgta_ctx_set_pileup_chunk": (C.c_int, [C.c_void_p, C.c_uint32]),
     "mgta_seqs_derep": (C.c_int, [C.c_void_p, C.c_char_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "mgta_ctx_set_derep_hash_bits": (C.c_int, [C.c_void_p, C.c_int]),
     "mgta_seqs_align": (C.c_int, [C.c_void_p, C.c_void_p, C.c_char_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),

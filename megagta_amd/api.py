@@ -118,6 +118,11 @@ class Context:
         collide and move no output -- a switch for tests"""
         check(self._L.mgta_ctx_set_share_hash_bits(self.h, int(bits)), "mgta_ctx_set_share_hash_bits")
 
+    def set_pileup_chunk(self, reads: int = 0):
+        """reads a group of lanes of Graph.pileup takes per visit to the queue head (0 = the library's choice); moves no output -- a
+        switch for tests"""
+        check(self._L.mgta_ctx_set_pileup_chunk(self.h, int(reads)), "mgta_ctx_set_pileup_chunk")
+
     def set_derep_hash_bits(self, bits: int = 64):
         """bits of both hashes `derep` keeps (1 .. 64, the default): with a few bits nearly every key collides.  The result does not
         depend on it; only stats["n_compares"] does."""
@@ -647,6 +652,37 @@ class Graph:
         if per_window:
             out["window_offsets"] = woff
         return out
+
+    def pileup(self, reads: "Reads", seqs, n_short_reads: int | None = None, params: dict | None = None, per_read: bool = False,
+               reads_reversed: bool = True) -> dict:
+        """mgta_reads_pileup: the first n_short_reads reads (default: all of `reads`) placed on the contigs `seqs` (str or bytes, any
+        case) by the rule of include/megagta_hip.h.  params = dict(min_anchors=, min_overlap=, max_mismatch_permille=), 0 or missing =
+        the default of each.  -> dict(counts = uint32[letters, 4] (A C G T, in the contig's strand), uniq = uint32[letters], contigs =
+        structured array (pileup.CONTIG_DTYPE), offsets = int64[n + 1], stats, and with per_read=True reads = structured array
+        (pileup.READ_DTYPE) of n_short_reads records).  Any loaded graph will do; one call = one set of contigs."""
+        from .pileup import CONTIG_DTYPE, READ_DTYPE
+        raw = [s if isinstance(s, (bytes, bytearray)) else str(s).encode() for s in seqs]
+        n = len(raw)
+        offsets = np.zeros(n + 1, dtype=np.uint64)
+        if n:
+            np.cumsum([len(s) for s in raw], out=offsets[1:])
+        ns = reads.n_reads if n_short_reads is None else int(n_short_reads)
+        total = int(offsets[-1])
+        counts = np.zeros((total, 4), dtype=np.uint32)
+        uniq = np.zeros(total, dtype=np.uint32)
+        rec = np.zeros(n, dtype=CONTIG_DTYPE)
+        pr = np.zeros(ns, dtype=READ_DTYPE) if per_read else None
+        par = _lib.PileupParams()
+        unknown = set(params or {}) - {"min_anchors", "min_overlap", "max_mismatch_permille"}
+        if unknown:
+            raise ValueError(f"unknown pileup parameters: {sorted(unknown)}")
+        for name, v in (params or {}).items():
+            setattr(par, name, int(v))
+        st = _lib.PileupStats()
+        check(self.ctx._L.mgta_reads_pileup(self.h, reads.h, int(bool(reads_reversed)), ns, b"".join(raw), offsets.ctypes.data, n, C.byref(par) if params else None,
+                                            counts.ctypes.data if total else None, uniq.ctypes.data if total else None, rec.ctypes.data if n else None,
+                                            pr.ctypes.data if per_read and ns else None, C.byref(st)), "mgta_reads_pileup")
+        return dict(counts=counts, uniq=uniq, contigs=rec, offsets=offsets.astype(np.int64), stats=st.as_dict(), reads=pr)
 
     def denovo(self, max_tip_len: int = 150, no_bubble: bool = False, min_contig: int = 0) -> tuple[str, dict]:
         """`megagta denovo` (main_assemble, assembler.cpp:98-167): tips, bubbles, unitigs -> (text of PREFIX.contigs.fa, stats).

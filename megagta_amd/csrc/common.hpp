@@ -149,6 +149,7 @@ struct mgta_ctx {
     uint64_t cluster_tile_rows = 0;        // mgta_ctx_set_cluster_tile: rows of one row block of mgta_rows_pairs (0 = the library's default)
     int derep_hash_bits = 64;    // mgta_ctx_set_derep_hash_bits: bits of both hashes mgta_seqs_derep keeps (fewer = more collisions, same answers)
     int share_hash_bits = 64;    // mgta_ctx_set_share_hash_bits: bits of the hash the count table of mgta_contig_share_coverage keeps (fewer = more collisions, same answers)
+    uint32_t pileup_chunk = 0;   // mgta_ctx_set_pileup_chunk: reads a group takes per visit to the queue head of mgta_reads_pileup (0 = the library's choice)
     const void *last_large = nullptr;
     uint64_t last_n_large = 0;
     mgta::DevBuf acc_large;

@@ -812,4 +812,39 @@ RefWords load_reference_words(const std::string &faa_path, int kaa) {
     return out;
 }
 
+// ---- pileup files ----------------------------------------------------------------------------------------------------------------------
+PileupTexts format_pileup(const std::vector<std::string> &names, const std::string &seqs, const std::vector<uint64_t> &offsets, const uint32_t *counts,
+                          const uint32_t *uniq, const PileupRow *rows, uint32_t min_depth, uint32_t min_alt_permille, bool per_base) {
+    PileupTexts out;
+    out.summary = "#contig\tlen\treads\tunique\tcovered\tmin\tmax\tmean\tmismatches\tvariants\n";
+    out.variants = "#contig\tpos\tref\tdepth\tA\tC\tG\tT\tunique\n";
+    if (per_base) out.depth = out.variants;
+    char buf[256];
+    for (size_t i = 0; i < names.size(); ++i) {
+        const uint64_t b = offsets[i], len = offsets[i + 1] - b;
+        uint64_t listed = 0;
+        for (uint64_t x = 0; x < len; ++x) {
+            const uint32_t *c = counts + (b + x) * 4;
+            const uint64_t depth = (uint64_t)c[0] + c[1] + c[2] + c[3];
+            const char ref = seqs[(size_t)(b + x)], up = (char)(ref & 0xDF);
+            const int code = up == 'A' ? 0 : up == 'C' ? 1 : up == 'G' ? 2 : up == 'T' ? 3 : -1;
+            const uint64_t alt = depth - (code >= 0 ? c[code] : 0);
+            const bool is_variant = depth >= min_depth && alt * 1000 >= (uint64_t)min_alt_permille * depth;
+            if (!is_variant && !per_base) continue;
+            const int m = snprintf(buf, sizeof buf, "\t%llu\t%c\t%llu\t%u\t%u\t%u\t%u\t%u\n", (unsigned long long)(x + 1), ref, (unsigned long long)depth, c[0], c[1], c[2],
+                                   c[3], uniq[b + x]);
+            if (is_variant) { out.variants += names[i]; out.variants.append(buf, (size_t)m); ++listed; }
+            if (per_base) { out.depth += names[i]; out.depth.append(buf, (size_t)m); }
+        }
+        const PileupRow &r = rows[i];
+        const unsigned long long mean = len ? (unsigned long long)(r.depth_sum * 10000 / len) : 0ull;   // (depth_sum < 2^32 * 2^32 / 10000 in any call that fits a device)
+        const int m = snprintf(buf, sizeof buf, "\t%llu\t%llu\t%llu\t%u\t%u\t%u\t%llu.%04llu\t%llu\t%llu\n", (unsigned long long)len, (unsigned long long)r.n_placed,
+                               (unsigned long long)r.n_unique, r.n_covered, r.min_depth, r.max_depth, mean / 10000, mean % 10000, (unsigned long long)r.mismatch_sum,
+                               (unsigned long long)listed);
+        out.summary += names[i];
+        out.summary.append(buf, (size_t)m);
+    }
+    return out;
+}
+
 }  // namespace mgta_host

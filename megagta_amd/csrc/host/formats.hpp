@@ -117,4 +117,11 @@ struct GeneEntry { std::string name, fwd_hmm, rev_hmm; };
 std::vector<GeneEntry> read_gene_list(const std::string &path);                           // search.cpp:105-122
 bool read_seeds(const std::string &path, std::vector<std::string> &kmers, std::vector<int32_t> &start_state);   // :146-162
 
+// ---- pileup files (megagta_amd/pileup.py prints the same bytes) ---------------------------------------------------
+struct PileupRow { uint32_t len, n_covered, min_depth, max_depth; uint64_t n_placed, n_unique, depth_sum, mismatch_sum; };   // mgta_contig_pileup
+struct PileupTexts { std::string summary, variants, depth; };                             // depth stays empty without per_base
+// counts [offsets[n] * 4] (A C G T), uniq [offsets[n]]; a position is listed iff depth >= min_depth and alt * 1000 >= min_alt_permille * depth
+PileupTexts format_pileup(const std::vector<std::string> &names, const std::string &seqs, const std::vector<uint64_t> &offsets, const uint32_t *counts,
+                          const uint32_t *uniq, const PileupRow *rows, uint32_t min_depth, uint32_t min_alt_permille, bool per_base);
+
 }  // namespace mgta_host

@@ -1084,6 +1084,83 @@ static bool write_text_file(const std::string &path, const std::string &text) {
     const bool ok = fwrite(text.data(), 1, text.size(), f) == text.size();
     return (fclose(f) == 0) && ok;
 }
+// ---- pileup: the reads of the library placed on the records of a FASTA (mgta_reads_pileup): per-base depth, placements and the positions
+// where the reads disagree with a contig.  The rule and the file formats are this project's own: INTEGRATION.md 2p; megagta_amd/pileup.py
+// prints the same bytes.
+static int main_pileup(int argc, char **argv) {
+    const char *usage = "Usage: megagta pileup <sdbg_prefix> <read.lib> <contigs.fasta> <out_prefix> [--min-anchors N] [--min-overlap N] [--max-mismatch-permille N] "
+                        "[--min-depth N] [--min-alt-permille N] [--per-base]\n";
+    if (argc < 5) { fputs(usage, stderr); return 1; }
+    mgta_pileup_params par{0, 0, 0};
+    long long min_depth = 8, min_alt = 100;
+    bool per_base = false;
+    for (int i = 5; i < argc; ++i) {
+        const std::string a = argv[i];
+        if (a == "--per-base") { per_base = true; continue; }
+        long long *into64 = a == "--min-depth" ? &min_depth : a == "--min-alt-permille" ? &min_alt : nullptr;
+        int32_t *into = a == "--min-anchors" ? &par.min_anchors : a == "--min-overlap" ? &par.min_overlap : a == "--max-mismatch-permille" ? &par.max_mismatch_permille : nullptr;
+        char *end = nullptr;
+        if ((!into && !into64) || i + 1 >= argc) { fputs(usage, stderr); return 1; }
+        const long long v = strtoll(argv[++i], &end, 10);
+        if (!*argv[i] || *end || v < 0 || v > 0x7FFFFFFFll) { fprintf(stderr, "megagta pileup: %s %s is not a count\n%s", a.c_str(), argv[i], usage); return 1; }
+        if (into) *into = (int32_t)v; else *into64 = v;
+    }
+    RssLine rss;
+    const std::string prefix = argv[1], lib = argv[2], fasta = argv[3], out_prefix = argv[4];
+    std::vector<std::string> names;
+    std::string seqs;
+    std::vector<uint64_t> offsets;
+    read_fasta_records(fasta, names, seqs, offsets);
+    const int64_t n = (int64_t)names.size();
+    double t0 = now_s();
+    PackedReads local;
+    PackedReads::Mark mk;
+    PackedReads &pr = lib_get(lib + ".bin", lib, "", false, local, mk);  // reversed, as buildgraph uploads it: a worker that still holds it does not read it again
+    const uint64_t n_reads = pr.start.size() - 1;
+    logf("%llu reads, %llu total bases (load %.3f s)", (unsigned long long)n_reads, (unsigned long long)pr.start.back(), now_s() - t0);
+    t0 = now_s();
+    mgta_ctx *ctx = ctx_get();
+    // The graph: any load will do, by matchreads' rules.
+    if (writer_join() != 0) die("the graph files of %s are incomplete", prefix.c_str());
+    const std::string key = file_key(prefix + ".sdbg_info");
+    mgta_sdbg *g = nullptr;
+    if (g_sess.active && g_sess.cov_graph && g_sess.cov_key == key) g = g_sess.cov_graph;
+    else if (g_sess.active && g_sess.match_graph && g_sess.match_key == key) g = g_sess.match_graph;
+    if (g) logf("graph %s: still on the device", prefix.c_str());
+    else {
+        graph_drop();
+        if (mgta_sdbg_load_files(ctx, prefix.c_str(), &g) != MGTA_OK) die("mgta_sdbg_load_files: %s", mgta_last_error());
+        if (g_sess.active) { g_sess.match_graph = g; g_sess.match_key = key; }
+    }
+    logf("Number of Edges: %lld; K value: %d (load %.3f s)", (long long)mgta_sdbg_size(g), mgta_sdbg_k(g), now_s() - t0);
+    t0 = now_s();
+    mgta_reads *rd = nullptr;
+    if (mgta_reads_upload(ctx, pr.words.data(), pr.words.size(), pr.start.data(), n_reads, &rd) != MGTA_OK) die("mgta_reads_upload: %s", mgta_last_error());
+    const size_t n_sym = (size_t)offsets.back();
+    std::vector<uint32_t> counts(n_sym * 4 + 4), uniq(n_sym + 1);
+    std::vector<mgta_contig_pileup> rec((size_t)n + 1);
+    mgta_pileup_stats st;
+    // all records in ONE call: the best-hit rule looks at every contig of the file
+    if (mgta_reads_pileup(g, rd, 1, n_reads, seqs.data(), offsets.data(), n, &par, counts.data(), uniq.data(), rec.data(), nullptr, &st) != MGTA_OK)
+        die("mgta_reads_pileup: %s", mgta_last_error());
+    mgta_reads_free(rd);
+    logf("pileup of %lld contigs: %lld windows, %lld keys, %lld occurrences (%.1f + %.1f ms); %lld reads, %lld read windows, %lld on a key; %lld reads with a candidate, "
+         "%lld candidates, %lld verified; %lld reads placed, %lld more than once, %lld placements, %lld bases (%.1f ms); records %.1f ms; %.1f MB on the device; wall %.3f s",
+         (long long)n, (long long)st.n_contig_windows, (long long)st.n_keys, (long long)st.n_occurrences, st.ms_keys, st.ms_index, (long long)st.n_reads,
+         (long long)st.n_read_windows, (long long)st.n_hit_windows, (long long)st.n_reads_with_candidate, (long long)st.n_candidates, (long long)st.n_verified,
+         (long long)st.n_reads_placed, (long long)st.n_reads_multi, (long long)st.n_placements, (long long)st.n_bases_piled, st.ms_scan, st.ms_records,
+         (double)st.peak_bytes / 1e6, now_s() - t0);
+    static_assert(sizeof(PileupRow) == sizeof(mgta_contig_pileup), "PileupRow is mgta_contig_pileup");
+    const PileupTexts txt = format_pileup(names, seqs, offsets, counts.data(), uniq.data(), reinterpret_cast<const PileupRow *>(rec.data()), (uint32_t)min_depth,
+                                          (uint32_t)min_alt, per_base);
+    if (!write_text_file(out_prefix + "_pileup.txt", txt.summary)) die("cannot write %s_pileup.txt", out_prefix.c_str());
+    if (!write_text_file(out_prefix + "_pileup_variants.txt", txt.variants)) die("cannot write %s_pileup_variants.txt", out_prefix.c_str());
+    if (per_base && !write_text_file(out_prefix + "_pileup_depth.txt", txt.depth)) die("cannot write %s_pileup_depth.txt", out_prefix.c_str());
+    if (!g_sess.active) mgta_sdbg_free(g);
+    ctx_put(ctx);
+    return 0;
+}
+
 static int main_derep(int argc, char **argv) {
     if (argc != 3 && argc != 5) { fprintf(stderr, "Usage: megagta derep <prot.fasta> <out_prefix> [<nucl.fasta> <nucl_out_prefix>]\n"); return 1; }
     RssLine rss;
@@ -1815,7 +1892,7 @@ int main(int argc, char **argv) {
 static int dispatch(int argc, char **argv) {
     if (argc < 2) {
         fprintf(stderr, "Usage: %s <sub_program> [sub options]\n    sub-programs on the MI355X hot path:\n        buildgraph    build succinct de Bruijn graph\n"
-                        "        denovo        tips, bubbles, contigs of an intermediate k\n        search        HMM-guided search of gene contigs\n        findstart     find starting kmers of the search\n        coverage      per-contig k-mer coverage and abundance from the graph\n        sharecov      per-contig coverage shared among the windows of the file: masses that add up\n        matchreads    the reads that share a (k+1)-mer with a set of contigs\n        samplecov     per-library coverage of a set of contigs, counted from the reads\n        derep         the unique, non-contained records of a FASTA\n        align         protein records placed on the columns of a profile HMM\n        posterior     Forward score and per-residue confidence of aligned protein records\n        cluster       complete-linkage clusters of aligned protein records\n        clustertree   those clusters at several cut-offs from one merge tree\n        nearest       the closest reference protein of every protein record\n        chimera       protein records that two references explain better than one\n        dumpversion   dump version\n", argv[0]);
+                        "        denovo        tips, bubbles, contigs of an intermediate k\n        search        HMM-guided search of gene contigs\n        findstart     find starting kmers of the search\n        coverage      per-contig k-mer coverage and abundance from the graph\n        sharecov      per-contig coverage shared among the windows of the file: masses that add up\n        matchreads    the reads that share a (k+1)-mer with a set of contigs\n        samplecov     per-library coverage of a set of contigs, counted from the reads\n        pileup        the reads placed on a set of contigs: per-base depth and variants\n        derep         the unique, non-contained records of a FASTA\n        align         protein records placed on the columns of a profile HMM\n        posterior     Forward score and per-residue confidence of aligned protein records\n        cluster       complete-linkage clusters of aligned protein records\n        clustertree   those clusters at several cut-offs from one merge tree\n        nearest       the closest reference protein of every protein record\n        chimera       protein records that two references explain better than one\n        dumpversion   dump version\n", argv[0]);
         return 1;
     }
     std::string sub = argv[1];
@@ -1827,6 +1904,7 @@ static int dispatch(int argc, char **argv) {
     if (sub == "sharecov") return main_sharecov(argc - 1, argv + 1);
     if (sub == "matchreads") return main_matchreads(argc - 1, argv + 1);
     if (sub == "samplecov") return main_samplecov(argc - 1, argv + 1);
+    if (sub == "pileup") return main_pileup(argc - 1, argv + 1);
     if (sub == "derep") return main_derep(argc - 1, argv + 1);
     if (sub == "align") return main_align(argc - 1, argv + 1);
     if (sub == "posterior") return main_posterior(argc - 1, argv + 1);
@@ -1936,6 +2014,6 @@ static int dispatch(int argc, char **argv) {
         return 0;
     }
     if (sub == "dumpversion") { printf("%s\n", mgta_version()); return 0; }
-    fprintf(stderr, "sub-command '%s' is not built here (buildlib, buildgraph, denovo, findstart, search, coverage, sharecov, matchreads, samplecov, derep, align, posterior, cluster, clustertree, nearest, chimera, filterbylen, translate are): run it with the reference's megagta binary\n", sub.c_str());
+    fprintf(stderr, "sub-command '%s' is not built here (buildlib, buildgraph, denovo, findstart, search, coverage, sharecov, matchreads, samplecov, pileup, derep, align, posterior, cluster, clustertree, nearest, chimera, filterbylen, translate are): run it with the reference's megagta binary\n", sub.c_str());
     return 1;
 }

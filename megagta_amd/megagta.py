@@ -83,7 +83,16 @@ USAGE = """Usage:
     --sample-abund   needs --align --cluster; after every other step: per gene contigs/<gene>/nucl_merged[_rmdup]_samplecov.txt (the read
                      windows of every library -- one per -r file, --12 file or -1/-2 pair, a pair being one sample -- on every clustered
                      contig, counted from the reads and split among the contig windows on one edge), prot_merged[_rmdup]_otu_samples.txt
-                     (mass per cluster and library) and prot_merged[_rmdup]_otu_samples_ppm.txt (GPU 0)"""
+                     (mass per cluster and library) and prot_merged[_rmdup]_otu_samples_ppm.txt (GPU 0)
+    --pileup         after every other step: per gene the reads of the run placed on contigs/<gene>/nucl_merged[_rmdup].fasta (with
+                     --derep the _rmdup file) on the last k's graph: nucl_merged[_rmdup]_pileup.txt (per contig: placements, depth,
+                     mismatches) and nucl_merged[_rmdup]_pileup_variants.txt (the positions where the reads disagree with the contig);
+                     the rule is this project's own, no read mapper is consulted (GPU 0)
+    --min-anchors N           needs --pileup: fewest windows a read shares with a contig on one diagonal [1]
+    --min-overlap N           needs --pileup: fewest contig positions a placement covers [k + 1 of the last graph]
+    --max-mismatch-permille N needs --pileup: most mismatches per 1000 covered positions [50]
+    --min-depth N             needs --pileup: fewest reads on a listed variant position [8]
+    --min-alt-permille N      needs --pileup: smallest share of reads that differ from the contig there, per 1000 [100]"""
 
 
 class Usage(Exception):
@@ -132,6 +141,8 @@ class Opt:
         self.chimera_min_gain = 15
         self.taxon_abund = False
         self.sample_abund = False
+        self.pileup = False
+        self.pileup_opts = {}            # the numeric options of --pileup that were given: flag -> value
 
 
 opt = Opt()
@@ -141,7 +152,8 @@ LONG = ["help", "read=", "12=", "out-dir=", "memory=", "gpu-mem=", "min-contig-l
         "min-count=", "max-tip-len=", "no-mercy", "keep-tmp-files", "mem-flag=", "version", "verbose", "continue", "gene-list=",
         "prune-len=", "low-cov-penalty=", "bin=", "one-process-per-step", "gpus=", "coverage", "match-reads", "derep", "align", "posterior", "cluster",
         "cluster-dist=", "cluster-min-overlap=", "cluster-dists=", "nearest", "nearest-scoring=", "nearest-gap-open=", "nearest-gap-extend=",
-        "chimera", "chimera-min-seg=", "chimera-min-gain=", "taxon-abund", "sample-abund"]
+        "chimera", "chimera-min-seg=", "chimera-min-gain=", "taxon-abund", "sample-abund", "pileup", "min-anchors=", "min-overlap=",
+        "max-mismatch-permille=", "min-depth=", "min-alt-permille="]
 
 
 def parse_opt(argv):
@@ -205,6 +217,11 @@ def parse_opt(argv):
         elif o == "--chimera-min-gain": opt.chimera_min_gain = int(v)
         elif o == "--taxon-abund": opt.taxon_abund = True
         elif o == "--sample-abund": opt.sample_abund = True
+        elif o == "--pileup": opt.pileup = True
+        elif o in ("--min-anchors", "--min-overlap", "--max-mismatch-permille", "--min-depth", "--min-alt-permille"):
+            if not v.isdigit():
+                raise Usage("%s %s: a count is expected" % (o, v))
+            opt.pileup_opts[o] = int(v)
         else:
             raise Usage("Invalid option " + o)
     opt.temp_dir = opt.out_dir + "tmp/"
@@ -262,6 +279,10 @@ def check_opt():
         raise Usage("--taxon-abund needs --align --cluster: it sums the coverage of the clusters those steps write")
     if opt.sample_abund and not (opt.align and opt.cluster):
         raise Usage("--sample-abund needs --align --cluster: it sums the coverage of the clusters those steps write")
+    if opt.pileup_opts and not opt.pileup:
+        raise Usage("%s needs --pileup: it is an option of that step" % sorted(opt.pileup_opts)[0])
+    if opt.pileup_opts.get("--max-mismatch-permille", 0) > 1000 or opt.pileup_opts.get("--min-alt-permille", 0) > 1000:
+        raise Usage("--max-mismatch-permille and --min-alt-permille are shares of 1000")
     if opt.cluster_dists is not None:
         if not opt.cluster:
             raise Usage("--cluster-dists needs --cluster: it cuts the tree of the rows that step clusters")
@@ -809,6 +830,20 @@ def sample_abund(k):
         write_cp()
 
 
+def pileup(k):
+    """--pileup: per gene the reads placed on the gene's nucleotide contigs (`megagta pileup` on the last k's graph and the run's read
+    library, GPU 0, with --match-reads' rules for what a worker keeps; one call per gene: the best-hit rule looks at all contigs of the
+    gene).  One checkpoint per gene, after every other checkpoint, so `--continue` works under any combination."""
+    stem = "_merged_rmdup" if opt.derep else "_merged"
+    extra = [x for flag in sorted(opt.pileup_opts) for x in (flag, str(opt.pileup_opts[flag]))]
+    for gene in opt.gene_info:
+        d = opt.out_dir + "contigs/" + gene
+        if should_run():
+            run_step([opt.bin, "pileup", graph_prefix(k), opt.lib, d + "/nucl" + stem + ".fasta", d + "/nucl" + stem] + extra,
+                     "Placing the reads on the contigs of %s" % gene)
+        write_cp()
+
+
 def cluster_cutoff_tags(text):
     """the tags of --cluster-dists LIST (megagta_amd/cluster.py parse_cutoff_list; ValueError says what is wrong with an item)"""
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -870,6 +905,8 @@ def after_search(k):
         sample_abund(k)
     if opt.cluster_dists is not None:
         cluster_dists(k)
+    if opt.pileup:
+        pileup(k)
 
 
 def main(argv=None):
