@@ -187,6 +187,9 @@ int mgta_sdbg_build_resident(mgta_ctx *, const mgta_reads *, uint64_t n_short_re
 /* (k+1)-mer multiplicity histogram of the last min_count >= 2 build: hist[i] = number of distinct (k+1)-mers seen i times
  * (i = 65535: that or more) — what s1_post_proc accumulates into PREFIX.counting (cx1_read2sdbg_s1.cpp:905-930). */
 int mgta_sdbg_last_counting(mgta_ctx *, int64_t *hist /* [65536] */);
+/* Passes of the last build on this context whose emitter compacted the info bytes their sort left behind and did not read the keys
+ * again (MGTA_EMIT_FUSED); 0 before the first build.  (Not a field of mgta_build_stats: the struct keeps its layout.) */
+int mgta_sdbg_last_emit_fused(mgta_ctx *, int64_t *n_passes);
 /* Records of the LAST build pass are still on the device: copy them (device -> device) into a caller-owned device
  * buffer (e.g. a torch tensor that is then all-gathered over RCCL).  d_dst = NULL only queries *n_records. */
 int mgta_sdbg_export_records_device(mgta_ctx *, void *d_dst, uint64_t capacity_bytes, uint64_t *n_records);

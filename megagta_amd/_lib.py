@@ -243,6 +243,7 @@ SYMBOLS = {
     "mgta_sdbg_build_resident": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint64, C.c_int, C.c_int, C.c_int, C.c_int32, C.c_int32,
                                           EDGE_SINK, C.c_void_p, C.POINTER(BuildStats)]),
     "mgta_sdbg_last_counting": (C.c_int, [C.c_void_p, C.c_void_p]),
+    "mgta_sdbg_last_emit_fused": (C.c_int, [C.c_void_p, C.POINTER(C.c_int64)]),
     "mgta_sdbg_export_records_device": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint64, C.POINTER(C.c_uint64)]),
     "mgta_sdbg_build": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint64, C.c_uint64, C.c_int, C.c_int,
                                  C.c_int, EDGE_SINK, C.c_void_p, C.POINTER(BuildStats)]),

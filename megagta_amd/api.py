@@ -430,9 +430,13 @@ class Context:
                                                cb, None, C.byref(st)),
               "mgta_sdbg_build_resident")
         cat = lambda xs, dt: np.concatenate(xs) if xs else np.zeros(0, dt)
+        stats = st.as_dict()
+        fused = C.c_int64(0)                   # (kept out of mgta_build_stats: the struct's layout stays)
+        check(self._L.mgta_sdbg_last_emit_fused(self.h, C.byref(fused)), "mgta_sdbg_last_emit_fused")
+        stats["n_emit_fused"] = fused.value
         return EdgeStream(k=k, words_per_tip=wpt, bucket_items=counts[:, 0].copy(), records=cat(recs, np.uint16),
                           large=cat(large, np.uint16), tips=cat(tips, np.uint32), bucket_large=counts[:, 1].copy(),
-                          bucket_tips=counts[:, 2].copy(), stats=st.as_dict())
+                          bucket_tips=counts[:, 2].copy(), stats=stats)
 
 
 def export_records_to_torch(ctx: "Context"):

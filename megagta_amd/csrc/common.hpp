@@ -108,6 +108,7 @@ struct mgta_ctx {
     uint64_t mem_limit = 0;       // 0 = auto
     int force_full_lsd = 0;
     int lsd_skip_left = 0;       // sorts left that go straight to LSD passes in LDS (the last look found mostly long runs)
+    int64_t emit_fused_passes = 0;   // passes of the current build whose emitter took the sort's info bytes (mgta_sdbg_last_emit_fused)
     int split_levels = 0;        // most split levels a sort of the current build ran on its oversized segments (mgta_build_stats::n_split_levels)
     int astar_log_b0 = 0;        // base arena of a search slot = 1 << astar_log_b0 nodes (0 = default 12); searches grow beyond it in place
     uint64_t astar_pool_bytes = 0;   // device memory the searches may grow into (0 = auto)

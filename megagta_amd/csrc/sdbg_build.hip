@@ -26,9 +26,12 @@
 //        equal leading bits by comparison (local_sort_kernel); tiles with long runs and segments that did not fit take LSD
 //        passes in LDS (local_lsd_kernel), segments longer than a tile are split by their leading digits, one scatter per level,
 //        until the pieces fit (segment_split_kernel)
-//     5. edge emission: run descriptors (a, b, group head, bucket head) compacted in one read of the keys by a chained scan
-//        across workgroups -> per run decision (W, last, tip, multiplicity, $-suppression) -> order-preserving compaction of
-//        records, large multiplicities and tip labels + per-bucket boundaries
+//     5. edge emission: run descriptors (a, b, group head, bucket head) compacted by a chained scan across workgroups -- from one
+//        byte per key position that the segment-local finish wrote while the sorted keys were still in LDS (local_sort_kernel's
+//        epilogue; emit_info_range_kernel for the ranges the other finishers sorted; emit_compact_info_kernel, MGTA_EMIT_FUSED), or
+//        where the sort left no such bytes in one more read of the keys (emit_compact_kernel) -> per run decision (W, last, tip,
+//        multiplicity, $-suppression) -> order-preserving compaction of records, large multiplicities and tip labels + per-bucket
+//        boundaries
 //
 // Everything is integer / byte work bound by HBM traffic; no MFMA.  Parity: bit-exact edge stream vs
 // the oracle (tests/test_sdbg_build_gpu.py).
@@ -1299,7 +1302,9 @@ __global__ __launch_bounds__(kSortThreads) void segment_copy_kernel(Key<W> *res,
 //   local_sort_kernel  two or three stable LSD passes in LDS (the 8 key bits below the prefix, then the rank of the
 //                      segment inside the tile) leave runs of equal leading 8P+8 bits — a handful of keys unless the
 //                      input is highly redundant; every key then finds its rank inside its run by comparing itself
-//                      with the run's other keys and goes straight to its final place.
+//                      with the run's other keys and goes straight to its final place -- or, where the edge emission wants them
+//                      (LocalPlan::info), to its place in the LDS tile first, so that every position can be compared with the one
+//                      before it and leave with the emitter's info byte.
 //   local_lsd_kernel   tiles whose runs are too long for that (reported by the first kernel), and single segments
 //                      that did not fit a tile next to their neighbours: LSD passes in LDS over every remaining digit.
 //   segment_lds_kernel   single segments of up to twice a tile: the same passes with the LDS of a whole CU.
@@ -1346,6 +1351,55 @@ struct CompareShared {
 template <int W>
 __device__ __forceinline__ uint32_t key_prefix(const Key<W> &key, int T) { return T == 0 ? 0u : (key.w[0] >> (32 - T)); }   // leading T <= 32 bits
 
+// What the edge emission (5.) takes from a sorted key and its predecessor: one definition for the emitter, the epilogue of
+// local_sort_kernel and emit_info_range_kernel.
+template <int W>
+__device__ __forceinline__ bool keys_equal(const Key<W> &x, const Key<W> &y) {
+    bool eq = true;
+#pragma unroll
+    for (int j = 0; j < W; ++j) eq = eq && (x.w[j] == y.w[j]);
+    return eq;
+}
+template <int W>
+__device__ __forceinline__ bool same_km1(const Key<W> &x, const Key<W> &y, int k) {   // IsDiffKMinusOneMer, s2.cpp:54-75
+    int full = (k - 1) >> 4, rem = (k - 1) & 15;
+    bool eq = true;
+#pragma unroll
+    for (int j = 0; j < W; ++j) {
+        if (j < full) eq = eq && (x.w[j] == y.w[j]);
+        else if (j == full && rem > 0) eq = eq && ((x.w[j] >> (16 - rem) * 2) == (y.w[j] >> (16 - rem) * 2));
+    }
+    return eq;
+}
+template <int W>
+__device__ __forceinline__ int key_a(const Key<W> &x, int k) {   // Extract_a, s2.cpp:83-94
+    if ((x.w[W - 1] >> 3) & 1u) {
+        int wi = (k - 1) >> 4, ci = (k - 1) & 15;
+        uint32_t word = 0;
+#pragma unroll
+        for (int j = 0; j < W; ++j) if (j == wi) word = x.w[j];
+        return (word >> (15 - ci) * 2) & 3;
+    }
+    return kDollar;
+}
+template <int W>
+__device__ __forceinline__ int key_b(const Key<W> &x) { return x.w[W - 1] & 7u; }   // Extract_b, s2.cpp:96-98
+
+// the descriptor byte of a run (distinct key) whose first key is `cur`: a | b << 3 | group head << 6 | bucket head << 7
+template <int W>
+__device__ __forceinline__ uint8_t head_info(const Key<W> &cur, int k, bool ghead, bool bhead) {
+    return (uint8_t)(key_a<W>(cur, k) | (key_b<W>(cur) << 3) | ((int)ghead << 6) | ((int)bhead << 7));
+}
+// the same for a key whose predecessor in the sorted array is `prv`; head: the key is the first of its run
+template <int W>
+__device__ __forceinline__ uint8_t key_info(const Key<W> &cur, const Key<W> &prv, int k, bool &head) {
+    head = !keys_equal<W>(cur, prv);
+    return head_info<W>(cur, k, !same_km1<W>(cur, prv, k), (cur.w[0] >> 16) != (prv.w[0] >> 16));
+}
+// The info array of a sort (one byte per key position, MGTA_EMIT_FUSED): the descriptor byte where the key is the first of its
+// run, else this marker (a = 7; a run head has a <= 4)
+constexpr uint8_t kInfoNoHead = 7;
+
 // What the segment-local kernels need besides the keys (host-built, passed by value)
 struct LocalPlan {
     const Digit *low_plan;   // every significant digit below the 8P-bit prefix, least significant first
@@ -1360,6 +1414,8 @@ struct LocalPlan {
     uint32_t *lsd_count;
     uint32_t lsd_cap;
     int debug;               // timing experiments only
+    uint8_t *info;           // local_sort_kernel<W, true, true>: the info byte of every key position of the tiles it finishes (kInfoNoHead
+    int emit_k;              // where no run starts), for the edge emission of a graph of this k; needs T <= 2 (k - 1) and unmasked keys
 };
 
 constexpr uint32_t kMaxAvgRun = 40;    // finish by comparison when the runs of equal (prefix, upper digit) are short on average ...
@@ -1508,9 +1564,9 @@ __device__ __forceinline__ uint64_t key_top(const Key<W> &k) {
     return PW == 1 ? (uint64_t)k.w[0] : (((uint64_t)k.w[0] << 32) | (uint64_t)k.w[W > 1 ? 1 : 0]);
 }
 
-template <int W, int FIRST, bool MASKED, int PW>
+template <int W, int FIRST, bool MASKED, int PW, bool INFO = false>   // INFO: see the epilogue (info, emit_k = the graph's k, emit_T = LocalPlan::T)
 __device__ __forceinline__ bool finish_by_comparison(CompareShared<W> &sh, Key<W> *keys, uint64_t first, uint32_t nt, int run_bits, uint32_t m2,
-                                                     uint32_t m1, bool skip_compare) {
+                                                     uint32_t m1, bool skip_compare, uint8_t *info = nullptr, int emit_k = 0, int emit_T = 0) {
     const int run_shift = 32 * PW - run_bits;                          // runs = equal leading run_bits bits
     constexpr int kIpt = LocalCfg<W>::kIpt, kWindows = LocalCfg<W>::kTile / 64;
     const int lane = lane_id(), wv = wave_id();
@@ -1553,27 +1609,72 @@ __device__ __forceinline__ bool finish_by_comparison(CompareShared<W> &sh, Key<W
     if (__ballot(over) && lane == 0) sh.flags[1] = 1;
     __syncthreads();
     if (wave_uniform(sh.flags[1])) return false;
+    // place of key j (= mine) in the sorted tile
+    auto place = [&](uint32_t j, uint32_t rn, const Key<W> &mine) {
+        const uint32_t rs = rn & 0xFFFFu, re = rs + (rn >> 16);
+        uint32_t r = j - rs;
+        if (!skip_compare) {
+            r = 0;
+#pragma unroll 2
+            for (uint32_t t = rs; t < j; ++t) r += key_less<W, FIRST, MASKED>(mine, sh.keys[t], m2, m1) ? 0u : 1u;
+#pragma unroll 2
+            for (uint32_t t = j + 1; t < re; ++t) r += key_less<W, FIRST, MASKED>(sh.keys[t], mine, m2, m1) ? 1u : 0u;
+        }
+        return rs + r;
+    };
+    if constexpr (!INFO) {
 #pragma unroll
-    for (int it = 0; it < kIpt; ++it) {
-        const uint32_t j = ((uint32_t)it * kSortWaves + (uint32_t)wv) * 64 + (uint32_t)lane;
-        if (j < nt) {
-            const Key<W> mine = sh.keys[j];
-            const uint32_t rs = run[it] & 0xFFFFu, re = rs + (run[it] >> 16);
-            uint32_t r = j - rs;
-            if (!skip_compare) {
-                r = 0;
-#pragma unroll 2
-                for (uint32_t t = rs; t < j; ++t) r += key_less<W, FIRST, MASKED>(mine, sh.keys[t], m2, m1) ? 0u : 1u;
-#pragma unroll 2
-                for (uint32_t t = j + 1; t < re; ++t) r += key_less<W, FIRST, MASKED>(sh.keys[t], mine, m2, m1) ? 1u : 0u;
+        for (int it = 0; it < kIpt; ++it) {
+            const uint32_t j = ((uint32_t)it * kSortWaves + (uint32_t)wv) * 64 + (uint32_t)lane;
+            if (j < nt) {
+                const Key<W> mine = sh.keys[j];
+                keys[first + place(j, run[it], mine)] = mine;
             }
-            keys[first + rs + r] = mine;
+        }
+    } else {
+        // The keys take their places inside the tile in LDS first; then every position reads its key and the one before it, and
+        // the key leaves with its info byte (edge emission, 5.), both coalesced.  The tile starts a segment of equal leading T bits,
+        // T <= 2 (k - 1): its first key starts a run and a group, and a bucket too when T < 16; else one word of the key before the
+        // tile tells (whatever the workgroup that owns it has made of its tile by now: every key of that segment carries the same
+        // leading T >= 16 bits).
+        static_assert(!MASKED, "stage 1 emits no edges");
+        Key<W> mine[kIpt];
+#pragma unroll
+        for (int it = 0; it < kIpt; ++it) {
+            const uint32_t j = ((uint32_t)it * kSortWaves + (uint32_t)wv) * 64 + (uint32_t)lane;
+            if (j < nt) {
+                mine[it] = sh.keys[j];
+                run[it] = place(j, run[it], mine[it]);
+            }
+        }
+        __syncthreads();                                                  // the last read of the tile in run order
+#pragma unroll
+        for (int it = 0; it < kIpt; ++it) {
+            const uint32_t j = ((uint32_t)it * kSortWaves + (uint32_t)wv) * 64 + (uint32_t)lane;
+            if (j < nt) sh.keys[run[it]] = mine[it];
+        }
+        __syncthreads();
+#pragma unroll
+        for (int it = 0; it < kIpt; ++it) {
+            const uint32_t j = ((uint32_t)it * kSortWaves + (uint32_t)wv) * 64 + (uint32_t)lane;
+            if (j < nt) {
+                const Key<W> cur = sh.keys[j];
+                bool head = true;
+                uint8_t byte;
+                if (j == 0) {
+                    const bool bhead = emit_T < 16 || first == 0 || (cur.w[0] >> 16) != (keys[first - 1].w[0] >> 16);
+                    byte = head_info<W>(cur, emit_k, true, bhead);
+                } else
+                    byte = key_info<W>(cur, sh.keys[j - 1], emit_k, head);
+                keys[first + j] = cur;
+                info[first + j] = head ? byte : kInfoNoHead;
+            }
         }
     }
     return true;
 }
 
-template <int W, bool WANT_KEYS>   // !WANT_KEYS: only the tile bounds are wanted (every tile goes to local_lsd_kernel)
+template <int W, bool WANT_KEYS, bool INFO = false>   // !WANT_KEYS: only the tile bounds are wanted (every tile goes to local_lsd_kernel)
 __global__ __launch_bounds__(kSortThreads, 8) void local_sort_kernel(Key<W> *keys, uint64_t n, LocalPlan lp, uint64_t *big, uint32_t *big_count,
                                                                      uint32_t big_cap) {
     constexpr int kTile = LocalCfg<W>::kTile, kIpt = LocalCfg<W>::kIpt, kChunk = LocalCfg<W>::kChunk, kWindows = kTile / 64;
@@ -1709,7 +1810,14 @@ __global__ __launch_bounds__(kSortThreads, 8) void local_sort_kernel(Key<W> *key
     const bool skip = (lp.debug & 1) != 0;
     const bool masked = (lp.mask_last2 & lp.mask_last) != ~0u;
     bool done;
-    if (run_bits > 32 && W > 1)
+    if constexpr (INFO) {                                             // (the host asks for info bytes of unmasked keys only)
+        if (run_bits > 32 && W > 1)
+            done = finish_by_comparison<W, (W > 1 ? 1 : 0), false, 2, true>(sh, keys, first, nt, run_bits, ~0u, ~0u, skip, lp.info, lp.emit_k, T);
+        else if (run_bits == 32 && W > 1)
+            done = finish_by_comparison<W, (W > 1 ? 1 : 0), false, 1, true>(sh, keys, first, nt, run_bits, ~0u, ~0u, skip, lp.info, lp.emit_k, T);
+        else
+            done = finish_by_comparison<W, 0, false, 1, true>(sh, keys, first, nt, run_bits, ~0u, ~0u, skip, lp.info, lp.emit_k, T);
+    } else if (run_bits > 32 && W > 1)
         done = masked ? finish_by_comparison<W, (W > 1 ? 1 : 0), true, 2>(sh, keys, first, nt, run_bits, lp.mask_last2, lp.mask_last, skip)
                       : finish_by_comparison<W, (W > 1 ? 1 : 0), false, 2>(sh, keys, first, nt, run_bits, lp.mask_last2, lp.mask_last, skip);
     else if (run_bits == 32 && W > 1)
@@ -1812,38 +1920,7 @@ __global__ __launch_bounds__(256) void segment_end_kernel(const Key<W> *keys, ui
 constexpr int kEmitThreads = 256;
 constexpr int kEmitPerThread = 16;
 constexpr int kEmitTile = kEmitThreads * kEmitPerThread;   // 4096 sorted keys per workgroup
-
-template <int W>
-__device__ __forceinline__ bool keys_equal(const Key<W> &x, const Key<W> &y) {
-    bool eq = true;
-#pragma unroll
-    for (int j = 0; j < W; ++j) eq = eq && (x.w[j] == y.w[j]);
-    return eq;
-}
-template <int W>
-__device__ __forceinline__ bool same_km1(const Key<W> &x, const Key<W> &y, int k) {   // IsDiffKMinusOneMer, s2.cpp:54-75
-    int full = (k - 1) >> 4, rem = (k - 1) & 15;
-    bool eq = true;
-#pragma unroll
-    for (int j = 0; j < W; ++j) {
-        if (j < full) eq = eq && (x.w[j] == y.w[j]);
-        else if (j == full && rem > 0) eq = eq && ((x.w[j] >> (16 - rem) * 2) == (y.w[j] >> (16 - rem) * 2));
-    }
-    return eq;
-}
-template <int W>
-__device__ __forceinline__ int key_a(const Key<W> &x, int k) {   // Extract_a, s2.cpp:83-94
-    if ((x.w[W - 1] >> 3) & 1u) {
-        int wi = (k - 1) >> 4, ci = (k - 1) & 15;
-        uint32_t word = 0;
-#pragma unroll
-        for (int j = 0; j < W; ++j) if (j == wi) word = x.w[j];
-        return (word >> (15 - ci) * 2) & 3;
-    }
-    return kDollar;
-}
-template <int W>
-__device__ __forceinline__ int key_b(const Key<W> &x) { return x.w[W - 1] & 7u; }   // Extract_b, s2.cpp:96-98
+// (keys_equal, same_km1, key_a, key_b, key_info: with the segment-local finish above, whose epilogue shares them)
 
 // Where the runs start: the low 32 bits per run, the full 64 bits for every kRunBaseStep-th run.  Runs are consecutive, so a
 // length is a 32-bit difference (a run never holds 2^32 keys) and a full start is rebuilt from the nearest base.
@@ -1891,15 +1968,11 @@ __global__ __launch_bounds__(kEmitThreads) void emit_compact_kernel(const Key<W>
         info[it] = 0;
         if (idx < n) {
             Key<W> cur = keys[idx];
-            bool ghead = true, bhead = true;
-            if (idx == 0) head = true;
-            else {
-                Key<W> prv = keys[idx - 1];                              // (taking it from the neighbouring lane by a shuffle was slower: 9.3 -> 11.2 ms)
-                head = !keys_equal<W>(cur, prv);
-                ghead = !same_km1<W>(cur, prv, k);
-                bhead = (cur.w[0] >> 16) != (prv.w[0] >> 16);             // first key of its bucket
-            }
-            info[it] = (uint8_t)(key_a<W>(cur, k) | (key_b<W>(cur) << 3) | ((int)ghead << 6) | ((int)bhead << 7));
+            if (idx == 0) {
+                head = true;
+                info[it] = head_info<W>(cur, k, true, true);
+            } else
+                info[it] = key_info<W>(cur, keys[idx - 1], k, head);     // (taking it from the neighbouring lane by a shuffle was slower: 9.3 -> 11.2 ms)
         }
         uint64_t bal = __ballot(head);
         rank_in_wave[it] = (uint32_t)__popcll(bal & lanemask_lt());
@@ -1930,6 +2003,117 @@ __global__ __launch_bounds__(kEmitThreads) void emit_compact_kernel(const Key<W>
             if ((s & ((1u << kRunBaseStepLog) - 1)) == 0) sub_start.base[s >> kRunBaseStepLog] = idx;
             sub_info[s] = info[it];
         }
+    }
+}
+
+// The same compaction from the info array the sort left behind (one byte per key position, kInfoNoHead where no run starts): the
+// keys are not read.  A workgroup takes kInfoRounds rounds of kEmitTile positions, 16 per lane and round in one 16-byte load, all
+// loads first; one chained scan per workgroup; the descriptors of a round are collected in LDS and leave as one coalesced run.
+// (One round per workgroup and every lane storing its own descriptors took 20.8 ms per 7.2 G positions: 1.76 M workgroups, each a
+// chain of load, scan, look-back and scattered stores.)  Order of the positions of a tile: round, thread, byte.  The array holds at
+// least 16 bytes behind position n - 1 (SortJob::side_bytes).
+constexpr int kInfoRounds = 8;
+constexpr int kInfoTile = kEmitTile * kInfoRounds;         // 32768 positions per workgroup
+template <bool TICKET>
+__global__ __launch_bounds__(kEmitThreads) void emit_compact_info_kernel(const uint8_t *info_in, uint64_t n, EmitChain chain, uint32_t n_tiles,
+                                                                          RunStarts sub_start, uint8_t *sub_info) {
+    static_assert(kEmitPerThread == 16, "one 16-byte load per lane and round");
+    static_assert(kInfoRounds == 8 && kEmitTile <= 65535, "round counts are scanned as 2 x 4 fields of 16 bits");
+    __shared__ uint64_t s_scr[kEmitThreads / 64 + 1];
+    __shared__ uint32_t s_tile;
+    __shared__ unsigned long long s_base;
+    __shared__ uint16_t s_off[kEmitTile];                  // the descriptors of a round: position inside the round, info byte
+    __shared__ uint8_t s_inf[kEmitTile];
+    const uint32_t tile = TICKET ? chain_ticket(chain.ticket, &s_tile) : blockIdx.x;
+    const uint64_t base = (uint64_t)tile * kInfoTile;
+    const uint32_t mine = threadIdx.x * kEmitPerThread;    // first position of the lane inside a round
+    uint4 v[kInfoRounds];
+#pragma unroll
+    for (int r = 0; r < kInfoRounds; ++r) {
+        const uint64_t idx0 = base + (uint64_t)r * kEmitTile + mine;
+        v[r] = make_uint4(0, 0, 0, 0);
+        if (idx0 < n) v[r] = *reinterpret_cast<const uint4 *>(info_in + idx0);
+    }
+    uint32_t headbits[kInfoRounds];
+    uint64_t packed[2] = {0, 0};                           // heads of the lane per round, 16 bits each
+#pragma unroll
+    for (int r = 0; r < kInfoRounds; ++r) {
+        const uint64_t idx0 = base + (uint64_t)r * kEmitTile + mine;
+        const uint32_t left = idx0 < n ? (uint32_t)(n - idx0 < (uint64_t)kEmitPerThread ? n - idx0 : (uint64_t)kEmitPerThread) : 0u;
+        const uint32_t wd[4] = {v[r].x, v[r].y, v[r].z, v[r].w};
+        uint32_t hb = 0;
+#pragma unroll
+        for (int b = 0; b < kEmitPerThread; ++b) hb |= (uint32_t)(((wd[b >> 2] >> (8 * (b & 3))) & 7u) != (uint32_t)kInfoNoHead) << b;
+        headbits[r] = hb & ((1u << left) - 1u);            // (left <= 16)
+        packed[r >> 2] |= (uint64_t)__popc(headbits[r]) << (16 * (r & 3));
+    }
+    uint64_t ex[2], tot[2];
+    ex[0] = block_excl_scan64<kEmitThreads>(packed[0], s_scr, &tot[0]);
+    ex[1] = block_excl_scan64<kEmitThreads>(packed[1], s_scr, &tot[1]);
+    uint32_t round_total[kInfoRounds], round_first[kInfoRounds], tile_total = 0;
+#pragma unroll
+    for (int r = 0; r < kInfoRounds; ++r) {
+        round_total[r] = (uint32_t)(tot[r >> 2] >> (16 * (r & 3))) & 0xFFFFu;
+        round_first[r] = tile_total;
+        tile_total += round_total[r];
+    }
+    if (wave_id() == 0) {
+        const uint64_t before = chain_exclusive(chain.state, tile, tile_total, chain.error);
+        if (lane_id() == 0) {
+            s_base = before;
+            if (tile + 1 == n_tiles) *chain.total = before + tile_total;
+        }
+    }
+    uint64_t tb = 0;
+#pragma unroll
+    for (int r = 0; r < kInfoRounds; ++r) {
+        if (round_total[r] == 0) continue;                 // (workgroup-uniform)
+        const uint32_t wd[4] = {v[r].x, v[r].y, v[r].z, v[r].w};
+        uint32_t q = (uint32_t)(ex[r >> 2] >> (16 * (r & 3))) & 0xFFFFu;
+#pragma unroll
+        for (int b = 0; b < kEmitPerThread; ++b) {
+            if ((headbits[r] >> b) & 1u) {
+                s_off[q] = (uint16_t)(mine + (uint32_t)b);
+                s_inf[q] = (uint8_t)((wd[b >> 2] >> (8 * (b & 3))) & 255u);
+                ++q;
+            }
+        }
+        __syncthreads();                                   // the round's descriptors are staged (the first time: s_base is known)
+        tb = s_base;
+        const uint64_t out0 = tb + round_first[r], pos0 = base + (uint64_t)r * kEmitTile;
+        for (uint32_t i = threadIdx.x; i < round_total[r]; i += kEmitThreads) {
+            const uint64_t s = out0 + i, idx = pos0 + s_off[i];
+            sub_start.lo[s] = (uint32_t)idx;
+            if ((s & ((1u << kRunBaseStepLog) - 1)) == 0) sub_start.base[s >> kRunBaseStepLog] = idx;
+            sub_info[s] = s_inf[i];
+        }
+        __syncthreads();                                   // the stage is free again
+    }
+}
+
+// MGTA_EMIT_FUSED=2: the m run descriptors of emit_compact_info_kernel against those of emit_compact_kernel (bad[0]: starts, bad[1]: info bytes)
+__global__ __launch_bounds__(256) void emit_check_kernel(const uint32_t *lo, const uint8_t *info, const uint32_t *lo_ref, const uint8_t *info_ref, uint64_t m,
+                                                         uint32_t *bad) {
+    for (uint64_t s = (uint64_t)blockIdx.x * 256 + threadIdx.x; s < m; s += (uint64_t)gridDim.x * 256) {
+        if (lo[s] != lo_ref[s]) atomicAdd(&bad[0], 1u);
+        if (info[s] != info_ref[s]) atomicAdd(&bad[1], 1u);
+    }
+}
+
+// The info bytes of the key ranges local_sort_kernel did not finish itself (the tiles left to local_lsd_kernel, the deferred
+// segments): one workgroup per listed range [start[b * stride], end[b * stride]) of the sorted array, every key against its
+// predecessor -- the first of the range included: a range may start inside a group or a bucket.
+template <int W>
+__global__ __launch_bounds__(256) void emit_info_range_kernel(const Key<W> *keys, uint64_t n, int k, const uint64_t *start, const uint64_t *end, int stride,
+                                                              uint8_t *key_info_out) {
+    const uint64_t first = start[(uint64_t)blockIdx.x * stride] & ~kSegInOther;
+    uint64_t last = end[(uint64_t)blockIdx.x * stride];
+    if (last > n) last = n;
+    for (uint64_t i = first + threadIdx.x; i < last; i += 256) {
+        const Key<W> cur = keys[i];
+        bool head = true;
+        const uint8_t info = i == 0 ? head_info<W>(cur, k, true, true) : key_info<W>(cur, keys[i - 1], k, head);
+        key_info_out[i] = head ? info : kInfoNoHead;
     }
 }
 
@@ -2111,11 +2295,15 @@ static uint64_t pool_bytes(const mgta_ctx *ctx) {
 // the plan of the pass was known when its items were counted, 2 the same and the writer's output checked on the device (tests).
 // MGTA_SORT_WIDE: global passes on digits of more than 8 bits (see widen_top_plan) 0 never, 1 (default) where they save a global pass
 // and leave short segments, 2 every pass but the first to run, whatever it saves (tests: small inputs take the wide kernels).
+// MGTA_EMIT_FUSED: the segment-local finish leaves the emitter's info byte of every key position behind, and the emitter compacts
+// those bytes instead of reading the keys again (see lds_finish) 0 never, 1 (default) wherever the sorted prefix lies inside the
+// (k-1)-mer, 2 the same and the run descriptors checked on the device against those of emit_compact_kernel (tests).
 struct SortModes {
-    int bias = 1, side = 1, fused = 1, wide = 1;
+    int bias = 1, side = 1, fused = 1, wide = 1, emit_fused = 1;
     static SortModes from_env() {
         const char *bias = getenv("MGTA_SORT_BIAS"), *side = getenv("MGTA_SORT_SIDE"), *fused = getenv("MGTA_SORT_FUSED"), *wide = getenv("MGTA_SORT_WIDE");
-        return SortModes{bias ? atoi(bias) : 1, side ? atoi(side) : 1, fused ? atoi(fused) : 1, wide ? atoi(wide) : 1};
+        const char *emit_fused = getenv("MGTA_EMIT_FUSED");
+        return SortModes{bias ? atoi(bias) : 1, side ? atoi(side) : 1, fused ? atoi(fused) : 1, wide ? atoi(wide) : 1, emit_fused ? atoi(emit_fused) : 1};
     }
 };
 
@@ -2228,6 +2416,7 @@ struct SortJob {
     bool census_done = false;                 // the first global pass's census (tiles of kBlockTile keys of a) is already in S_HIST
     bool side_done = false;                   // S_SIDE already holds the digit of every key that the first global pass to run sorts on
     bool first_pass_done = false;             // the key writer placed the keys by the first global pass's digit: the passes start at the second
+    int emit_k = 0;                           // > 0: the keys are those of a graph of this k, and the finish may leave the emitter's info bytes behind
     // side digits: the scatter of a pass leaves the NEXT pass's digit of every key in a byte array (S_SIDE), and that pass's census
     // reads the bytes instead of the keys
     bool uses_side() const { return side_mode > 0 && top.P >= 2 && kSideFits<WT>; }
@@ -2379,7 +2568,7 @@ static int split_oversized(mgta_ctx *ctx, const SortJob<WT> &job, Key<WT> *src, 
 // tile on their own (segment_lds_kernel, and the split levels of split_oversized for the longer ones).  `src` holds the keys, `dst`
 // is scratch.  Returns src, nullptr on an error (set).
 template <int WT>
-static Key<WT> *lds_finish(mgta_ctx *ctx, const SortJob<WT> &job, Key<WT> *src, Key<WT> *dst, SortLog *log) {
+static Key<WT> *lds_finish(mgta_ctx *ctx, const SortJob<WT> &job, Key<WT> *src, Key<WT> *dst, SortLog *log, const uint8_t **info_out = nullptr) {
     hipStream_t stream = ctx->stream;
     const uint64_t n_items = job.n;
     const int T = job.top.T();
@@ -2411,7 +2600,19 @@ static Key<WT> *lds_finish(mgta_ctx *ctx, const SortJob<WT> &job, Key<WT> *src, 
     lp.mask_last2 = job.mask_last2; lp.mask_last = job.mask_last; lp.stride = stride;
     lp.lsd_list = d_lsd; lp.lsd_count = d_big_count + 1; lp.lsd_cap = (uint32_t)l_blocks;
     lp.debug = ctx->force_lsd_tiles >> 1;
-    if (ub > 0)
+    // The emitter's info byte of every key position, for jobs that ask (emit_k): the tiles local_sort_kernel finishes write theirs as
+    // the keys leave LDS, emit_info_range_kernel those of every other range once its keys are final.  Its rule for a tile's first
+    // key needs the sorted prefix inside the (k-1)-mer; masked keys (stage 1) emit nothing.  The bytes take the S_SIDE slot, idle since
+    // the last global pass read its digits (same request as the sort's where it has a side array: the slot does not move).
+    uint8_t *d_info = nullptr;
+    if (info_out) *info_out = nullptr;
+    if (info_out && job.emit_k > 0 && T <= 2 * (job.emit_k - 1) && (job.mask_last2 & job.mask_last) == ~0u && !lp.debug)
+        d_info = pool_get<uint8_t>(ctx, S_SIDE, job.uses_side() ? job.side_bytes() : n_items + 64);
+    lp.info = d_info; lp.emit_k = job.emit_k;
+    if (ub > 0 && d_info)
+        hipLaunchKernelGGL((local_sort_kernel<WT, true, true>), dim3((unsigned)l_blocks), dim3(kSortThreads), 0, stream, src, n_items, lp, d_big, d_big_count,
+                           big_cap);
+    else if (ub > 0)
         hipLaunchKernelGGL((local_sort_kernel<WT, true>), dim3((unsigned)l_blocks), dim3(kSortThreads), 0, stream, src, n_items, lp, d_big, d_big_count,
                            big_cap);
     else
@@ -2442,6 +2643,13 @@ static Key<WT> *lds_finish(mgta_ctx *ctx, const SortJob<WT> &job, Key<WT> *src, 
             ctx->split_levels = std::max(ctx->split_levels, levels);
         }
     }
+    if (d_info) {
+        if (n_lsd_tiles > 0)
+            hipLaunchKernelGGL((emit_info_range_kernel<WT>), dim3(n_lsd_tiles), dim3(256), 0, stream, src, n_items, job.emit_k, d_lsd, d_lsd + 1, 2, d_info);
+        if (n_big > 0)
+            hipLaunchKernelGGL((emit_info_range_kernel<WT>), dim3(n_big), dim3(256), 0, stream, src, n_items, job.emit_k, d_big, d_big + big_cap, 1, d_info);
+        *info_out = d_info;
+    }
     t.end();
     MGTA_HIP_CHECK(hipEventSynchronize(t.b));
     const float ms = t.ms();
@@ -2451,9 +2659,9 @@ static Key<WT> *lds_finish(mgta_ctx *ctx, const SortJob<WT> &job, Key<WT> *src, 
 
 // Sort job.n keys (see SortJob).  Returns the buffer (a or b) that holds the result, nullptr on an unsupported input (error set).
 template <int WT>
-static Key<WT> *device_sort(mgta_ctx *ctx, const SortJob<WT> &job, SortLog *log = nullptr) {
+static Key<WT> *device_sort(mgta_ctx *ctx, const SortJob<WT> &job, SortLog *log = nullptr, const uint8_t **info_out = nullptr) {
     Key<WT> *src = global_passes(ctx, job, log);
-    return src ? lds_finish(ctx, job, src, src == job.a ? job.b : job.a, log) : nullptr;
+    return src ? lds_finish(ctx, job, src, src == job.a ? job.b : job.a, log, info_out) : nullptr;
 }
 
 // ---- stage 1 (min_count >= 2): fills the is_solid bit-vector (+ mercy edges) that stage 2 then honours -------------
@@ -2648,6 +2856,7 @@ struct Build {                                 // a build of keys of W words: wh
     uint64_t wide_items = 0;                   // items and buckets of the last attempt admit_pass refused
     uint32_t wide_nb = 0;
     bool fz_check_failed = false;              // MGTA_SORT_FUSED=2: the fused writer's output failed its check
+    const uint8_t *sorted_info = nullptr;      // the info bytes the pass's sort left behind (MGTA_EMIT_FUSED), nullptr: the emitter reads the keys
     mgta_build_stats S{};
     Timer t_all{stream}, t_ph{stream};
     SortLog log{&S, {}};
@@ -2704,6 +2913,7 @@ struct Build {                                 // a build of keys of W words: wh
         S.k = k; S.words_per_key = W; S.words_per_tip = words_per_tip; S.n_reads = (int64_t)rd->n_reads;
         ctx->peak_bytes = ctx->live_bytes;
         ctx->split_levels = 0;
+        ctx->emit_fused_passes = 0;
         size_t free_b = 0, total_b = 0;
         MGTA_HIP_CHECK(hipMemGetInfo(&free_b, &total_b));
         // what the build may hold: the explicit limit, else 90 % of (free + what our pool already holds)
@@ -2869,6 +3079,7 @@ struct Build {                                 // a build of keys of W words: wh
         SortJob<W> job{a, b, p.n_items, top_plan(p.n_items, p.b_lo, p.b_hi)};
         job.low = low_digit_plan(k, W, job.top.T());
         job.side_mode = modes.side;
+        job.emit_k = modes.emit_fused > 0 ? k : 0;
         // closed form + at least one global sort pass: the key writer works tile by tile of that pass and leaves its census behind;
         // the general writer leaves that pass's digit of every key in the side array instead
         job.census_done = p.closed_form && job.top.P >= 1 && p.n_tiles <= 0x7FFFFFFFull;
@@ -2940,7 +3151,7 @@ struct Build {                                 // a build of keys of W words: wh
     // ---- 4. sort: P global passes on the most significant bytes, then the segment-local finish in LDS
     Key<W> *sort_keys(const SortJob<W> &job) {
         t_ph.start();
-        Key<W> *sorted = device_sort(ctx, job, &log);
+        Key<W> *sorted = device_sort(ctx, job, &log, &sorted_info);
         if (sorted) S.ms_sort += t_ph.stop();
         return sorted;
     }
@@ -2967,29 +3178,71 @@ struct Build {                                 // a build of keys of W words: wh
         // n_items runs (<= 7.01 bytes per key of a >= 12-byte-per-key buffer): start u32 | rec u16 | info u8 | full start u64 per 1024 runs
         if (e_tiles > 0xFFFFFFFFull) { set_error("too many emit tiles"); return MGTA_EUNSUPPORTED; }
         unsigned long long *d_chain = pool_get<unsigned long long>(ctx, S_TILE_BASE, (e_tiles + 4) * 8);
-        EmitChain chain;
-        chain.state = d_chain; chain.total = d_chain + e_tiles;
-        chain.ticket = reinterpret_cast<uint32_t *>(d_chain + e_tiles + 1); chain.error = reinterpret_cast<uint32_t *>(d_chain + e_tiles + 2);
         RunStarts sub_start;
         sub_start.lo = reinterpret_cast<uint32_t *>(scratch);
         uint16_t *rec = reinterpret_cast<uint16_t *>(scratch + n_items * 4);
         uint8_t *info = reinterpret_cast<uint8_t *>(scratch + n_items * 6);
         sub_start.base = reinterpret_cast<uint64_t *>(scratch + ((n_items * 7 + 7) & ~7ull));
-        unsigned long long chain_out[3] = {0, 0, 0};               // total, ticket, error
-        for (int attempt = 0; attempt < 2; ++attempt) {
-            MGTA_HIP_CHECK(hipMemsetAsync(d_chain, 0, (e_tiles + 4) * 8, stream));
-            if (attempt == 0 && !ctx->force_full_lsd)
-                hipLaunchKernelGGL((emit_compact_kernel<W, false>), dim3((unsigned)e_tiles), dim3(kEmitThreads), 0, stream, sorted, n_items, k, chain,
-                                   (uint32_t)e_tiles, sub_start, info);
-            else
-                hipLaunchKernelGGL((emit_compact_kernel<W, true>), dim3((unsigned)e_tiles), dim3(kEmitThreads), 0, stream, sorted, n_items, k, chain,
-                                   (uint32_t)e_tiles, sub_start, info);
-            MGTA_HIP_CHECK(hipMemcpyAsync(chain_out, d_chain + e_tiles, 24, hipMemcpyDeviceToHost, stream));
-            MGTA_HIP_CHECK(hipStreamSynchronize(stream));
-            if ((uint32_t)chain_out[2] == 0) break;
+        // from the info bytes the sort left behind where it did (MGTA_EMIT_FUSED), else from the keys; returns the number of runs
+        auto compact = [&](const uint8_t *key_info, RunStarts st, uint8_t *st_info, uint64_t *m_out) {
+            unsigned long long chain_out[3] = {0, 0, 0};           // total, ticket, error
+            const uint64_t tiles = key_info ? (n_items + kInfoTile - 1) / kInfoTile : e_tiles;   // (<= e_tiles: the chain's buffer holds either)
+            EmitChain chain;
+            chain.state = d_chain; chain.total = d_chain + tiles;
+            chain.ticket = reinterpret_cast<uint32_t *>(d_chain + tiles + 1); chain.error = reinterpret_cast<uint32_t *>(d_chain + tiles + 2);
+            for (int attempt = 0; attempt < 2; ++attempt) {
+                MGTA_HIP_CHECK(hipMemsetAsync(d_chain, 0, (tiles + 4) * 8, stream));
+                const bool ticket = !(attempt == 0 && !ctx->force_full_lsd);
+                const dim3 grid((unsigned)tiles), block(kEmitThreads);
+                if (key_info && !ticket)
+                    hipLaunchKernelGGL((emit_compact_info_kernel<false>), grid, block, 0, stream, key_info, n_items, chain, (uint32_t)tiles, st, st_info);
+                else if (key_info)
+                    hipLaunchKernelGGL((emit_compact_info_kernel<true>), grid, block, 0, stream, key_info, n_items, chain, (uint32_t)tiles, st, st_info);
+                else if (!ticket)
+                    hipLaunchKernelGGL((emit_compact_kernel<W, false>), grid, block, 0, stream, sorted, n_items, k, chain, (uint32_t)tiles, st, st_info);
+                else
+                    hipLaunchKernelGGL((emit_compact_kernel<W, true>), grid, block, 0, stream, sorted, n_items, k, chain, (uint32_t)tiles, st, st_info);
+                MGTA_HIP_CHECK(hipMemcpyAsync(chain_out, d_chain + tiles, 24, hipMemcpyDeviceToHost, stream));
+                MGTA_HIP_CHECK(hipStreamSynchronize(stream));
+                if ((uint32_t)chain_out[2] == 0) break;
+            }
+            if ((uint32_t)chain_out[2] != 0) { set_error("internal: chained scan of the emitter timed out"); return MGTA_EINTERNAL; }
+            *m_out = chain_out[0];
+            return MGTA_OK;
+        };
+        uint64_t m = 0;
+        if (int rc = compact(sorted_info, sub_start, info, &m)) return rc;
+        if (sorted_info) {
+            ctx->emit_fused_passes++;
+            if (modes.emit_fused >= 2) {       // (test aid) the same from the keys, into the part of the scratch that is still idle
+                RunStarts ref;
+                uint8_t *ref_info = reinterpret_cast<uint8_t *>(rec);          // (the records are written by emit_decide_kernel)
+                char *behind = reinterpret_cast<char *>(sub_start.base + (n_items >> kRunBaseStepLog) + 1);
+                ref.lo = reinterpret_cast<uint32_t *>(behind);                 // <= 11.02 bytes per key in all
+                ref.base = reinterpret_cast<uint64_t *>(behind + ((n_items * 4 + 7) & ~7ull));
+                if ((uint64_t)(reinterpret_cast<char *>(ref.base + (n_items >> kRunBaseStepLog) + 1) - scratch) > p.key_b) {
+                    set_error("internal: no room to check the emitter's info bytes");
+                    return MGTA_EINTERNAL;
+                }
+                uint64_t m_ref = 0;
+                if (int rc = compact(nullptr, ref, ref_info, &m_ref)) return rc;
+                uint32_t *d_bad = reinterpret_cast<uint32_t *>(pool_get<uint64_t>(ctx, S_SMALL, 4096) + 320);
+                uint32_t bad[2] = {0, 0};
+                MGTA_HIP_CHECK(hipMemsetAsync(d_bad, 0, 8, stream));
+                const uint64_t m_min = std::min(m, m_ref);
+                if (m_min > 0) {
+                    const unsigned grid = (unsigned)std::min<uint64_t>((m_min + 255) / 256, (uint64_t)ctx->num_cus * 16);
+                    hipLaunchKernelGGL(emit_check_kernel, dim3(grid), dim3(256), 0, stream, sub_start.lo, info, ref.lo, ref_info, m_min, d_bad);
+                }
+                MGTA_HIP_CHECK(hipMemcpyAsync(bad, d_bad, 8, hipMemcpyDeviceToHost, stream));
+                MGTA_HIP_CHECK(hipStreamSynchronize(stream));
+                if (m != m_ref || bad[0] || bad[1]) {
+                    set_error("internal: the info bytes of the sort give %llu runs, the keys %llu; %u starts and %u info bytes differ",
+                              (unsigned long long)m, (unsigned long long)m_ref, bad[0], bad[1]);
+                    return MGTA_EINTERNAL;
+                }
+            }
         }
-        if ((uint32_t)chain_out[2] != 0) { set_error("internal: chained scan of the emitter timed out"); return MGTA_EINTERNAL; }
-        const uint64_t m = chain_out[0];
         uint64_t d_tiles = (m + kDecideTile - 1) / kDecideTile;
         uint32_t *ce = pool_get<uint32_t>(ctx, S_CNT, d_tiles * 4 * 3), *cl = ce + d_tiles, *ct = cl + d_tiles;
         uint64_t *be = pool_get<uint64_t>(ctx, S_BASE, d_tiles * 8 * 3), *bl = be + d_tiles, *bt = bl + d_tiles;
@@ -3173,6 +3426,12 @@ int mgta_sdbg_last_counting(mgta_ctx *ctx, int64_t *hist) {
     if (!ctx || !hist) { set_error("mgta_sdbg_last_counting: null argument"); return MGTA_EINVAL; }
     if (ctx->edge_counting.size() != 65536) { set_error("no stage-1 run (min_count > 1) on this context yet"); return MGTA_EINVAL; }
     std::copy(ctx->edge_counting.begin(), ctx->edge_counting.end(), hist);
+    return MGTA_OK;
+}
+
+int mgta_sdbg_last_emit_fused(mgta_ctx *ctx, int64_t *n_passes) {
+    if (!ctx || !n_passes) { set_error("mgta_sdbg_last_emit_fused: null argument"); return MGTA_EINVAL; }
+    *n_passes = ctx->emit_fused_passes;
     return MGTA_OK;
 }
 
