@@ -228,6 +228,51 @@ int mgta_sdbg_k(const mgta_sdbg *);                 /* the graph's k (node lengt
  * outgoing edges in the reference's order (descending id) [succinct_dbg.cpp:78-97];
  * outdeg[i] = -1 for an invalid edge.  out4 = n x 4 int64 (unused slots -1). Host pointers. */
 int mgta_sdbg_outgoing(mgta_sdbg *, const int64_t *edges, int64_t n, int64_t *out4, int8_t *outdeg);
+/* Navigation probe (test hook): operation `op` on n argument tuples, one device lane per tuple, each answered by the very device
+ * function the kernels of this library walk the graph with (csrc/graph.hpp, csrc/graph_nav.hpp).  Host pointers.
+ *
+ *   op                          arg0      arg1     arg2    out (int64 per tuple)             defined for
+ *   MGTA_NAV_RANK_LAST          pos       -        -       1: `last` bits in [0..pos]        pos in [-1, size)
+ *   MGTA_NAV_RANK_TIP           pos       -        -       1: tip bits in [0..pos]           pos in [0, size)  (no early-out for -1)
+ *   MGTA_NAV_RANK_W             pos       c        -       1: edges with W == c in [0..pos]  c in 1..4 (plain symbols), pos in [-1, size)
+ *   MGTA_NAV_SELECT_LAST        r         -        -       1: position of the r-th one,      r in [-1, total]: -1 -> -1, total -> size
+ *   MGTA_NAV_SELECT_W           r         c        -       1:   0-based                      c in 1..4, r in [-1, total of c]
+ *   MGTA_NAV_FORWARD            edge      -        -       1: Forward (size / -1 past the    any edge with W != 0 (tips included);
+ *                                                             ends of `last`)                   W == 0: MGTA_NAV_UNDEFINED
+ *   MGTA_NAV_BACKWARD           edge      -        -       1: Backward                       any edge of a node that is no tip (a tip has no edge
+ *                                                                                               into it); a tip: MGTA_NAV_UNDEFINED
+ *   MGTA_NAV_LAST_INDEX         edge      -        -       1: the node's last edge           any edge (size when no `last` bit follows)
+ *   MGTA_NAV_OUTGOING           edge      -        -       5: degree, 4 x (id << 4 |         any edge; degree -1 for one that is not valid
+ *                                                             multi1 << 3 | label), -1 unused
+ *   MGTA_NAV_INCOMING           edge      -        -       5: degree, 4 ids, -1 unused       any edge; degree -1 for one that is not valid
+ *   MGTA_NAV_PREV_SIMPLE        edge      -        -       1: PrevSimplePathEdge or -1       any edge (-1 for one that is not valid)
+ *   MGTA_NAV_NEXT_SIMPLE        edge      -        -       1: NextSimplePathEdge or -1       any edge (-1 for one that is not valid)
+ *   MGTA_NAV_REVERSE_COMPLEMENT edge      -        -       1: its edge or -1                 any edge (-1 for one that is not valid), k <= 255
+ *   MGTA_NAV_LABEL              edge      -        -       1: k; out_sym: k symbols 1..4     any edge, k <= 255
+ *   MGTA_NAV_OUT_FD             edge      r        hint    29, see below                     any edge; hint -1 ("none": the descriptor is read
+ *                                                                                               from the edge's own line) or a line < ceil(size / 64)
+ *
+ * MGTA_NAV_OUT_FD walks one step of the forward-descriptor chain of the search kernel (g_out_all_fd, g_out_nth_fd): a descriptor (r, hint) of
+ * an edge is the Select argument of its Forward and a line at or before the line of that `last` bit.  out[0] = out-degree (min(4, .), -1 for
+ * an edge that is not valid and has no descriptor), out[1..4] = the packed out-edges, out[5..8] / out[9..12] = r / hint of their own
+ * descriptors (hint -1 = none: the edge lies in the line before the target line, r is then 0), then g_out_nth_fd for n = 0..3:
+ * out[13..16] = its degree, out[17..20] = its edge, out[21..24] / out[25..28] = r / hint.  Slots the device function leaves alone (n >= degree)
+ * hold MGTA_NAV_UNTOUCHED.  A descriptor whose hint line lies behind the bit it looks for: out[0] = MGTA_NAV_UNDEFINED.
+ *
+ * Ids, positions, ranks and symbols outside the ranges above: MGTA_EINVAL before anything is launched, `out` untouched.  What only the graph
+ * knows is checked on the device before the function is called and answered with MGTA_NAV_UNDEFINED in out[0]; besides the two cases in the
+ * table that is an edge whose Forward / Backward leaves [0, size) under OUTGOING / NEXT_SIMPLE / INCOMING / PREV_SIMPLE, which no stream of a
+ * build contains.  The rank and select operations hold for ANY records; the others need a stream a build produced (as every kernel of the
+ * library does).  An empty graph answers the few tuples in range (rank of -1, select of -1 and 0) without a launch. */
+enum {
+    MGTA_NAV_RANK_LAST = 0, MGTA_NAV_RANK_TIP = 1, MGTA_NAV_RANK_W = 2, MGTA_NAV_SELECT_LAST = 3, MGTA_NAV_SELECT_W = 4, MGTA_NAV_FORWARD = 5,
+    MGTA_NAV_BACKWARD = 6, MGTA_NAV_LAST_INDEX = 7, MGTA_NAV_OUTGOING = 8, MGTA_NAV_INCOMING = 9, MGTA_NAV_PREV_SIMPLE = 10,
+    MGTA_NAV_NEXT_SIMPLE = 11, MGTA_NAV_REVERSE_COMPLEMENT = 12, MGTA_NAV_LABEL = 13, MGTA_NAV_OUT_FD = 14
+};
+#define MGTA_NAV_UNTOUCHED (-2)
+#define MGTA_NAV_UNDEFINED (-3)
+int mgta_sdbg_navigate(mgta_sdbg *, int op, const int64_t *arg0, const int64_t *arg1, const int64_t *arg2, int64_t n, int64_t *out,
+                       uint8_t *out_sym /* n x k, MGTA_NAV_LABEL only */);
 /* batched IndexBinarySearchEdge over (k+1)-symbol strings (symbols 1..4) [succinct_dbg.cpp:427-549]. */
 /* the validity bits as they are now (SuccinctDBG::invalid_, succinct_dbg.h:117-131): bit e of words[e / 64]; ceil(size / 64) words.
  * Set for tips and $ edges after a load, and for everything `mgta_denovo` removed. */

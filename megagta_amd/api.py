@@ -530,6 +530,29 @@ class Graph:
         check(self.ctx._L.mgta_sdbg_outgoing(self.h, e.ctypes.data, e.size, out.ctypes.data, deg.ctypes.data), "mgta_sdbg_outgoing")
         return deg, out
 
+    NAV_OPS = {"rank_last": 0, "rank_tip": 1, "rank_w": 2, "select_last": 3, "select_w": 4, "forward": 5, "backward": 6, "last_index": 7,
+               "outgoing": 8, "incoming": 9, "prev_simple": 10, "next_simple": 11, "reverse_complement": 12, "label": 13, "out_fd": 14}
+    NAV_WIDTH = {"outgoing": 5, "incoming": 5, "out_fd": 29}
+    NAV_UNTOUCHED, NAV_UNDEFINED = -2, -3
+
+    def navigate(self, op: str, arg0, arg1=None, arg2=None):
+        """mgta_sdbg_navigate: the device navigation function `op` (a key of NAV_OPS) on a batch of argument tuples (include/megagta_hip.h
+        has the table: arg0 = position, rank or edge id; arg1 = the symbol of rank_w / select_w, a scalar or one per tuple, or r of an
+        out_fd descriptor; arg2 = the descriptor's hint, -1 = none).  -> int64[n] for the one-value operations, int64[n, 5] for outgoing /
+        incoming, int64[n, 29] for out_fd, uint8[n, k] symbols 1..4 for label."""
+        a0 = np.ascontiguousarray(arg0, dtype=np.int64).reshape(-1)
+        n = a0.size
+        full = lambda a: None if a is None else np.ascontiguousarray(np.broadcast_to(np.asarray(a, dtype=np.int64), (n,)))
+        a1, a2 = full(arg1), full(arg2)
+        width = self.NAV_WIDTH.get(op, 1)
+        out = np.full((n, width), self.NAV_UNTOUCHED, dtype=np.int64)
+        sym = np.zeros((n, self.k), dtype=np.uint8) if op == "label" else None
+        ptr = lambda a: None if a is None else a.ctypes.data
+        check(self.ctx._L.mgta_sdbg_navigate(self.h, self.NAV_OPS[op], ptr(a0), ptr(a1), ptr(a2), n, ptr(out), ptr(sym)), "mgta_sdbg_navigate")
+        if op == "label":
+            return sym
+        return out[:, 0].copy() if width == 1 else out
+
     def index_edges(self, kmers: list[str]) -> np.ndarray:
         """IndexBinarySearchEdge (succinct_dbg.cpp:530-549) of (k+1)-mers; -1 = absent"""
         m = {"A": 1, "C": 2, "G": 3, "T": 4, "N": 3}

@@ -16,6 +16,7 @@
 #include "common.hpp"
 #include "device_utils.hpp"
 #include "graph.hpp"
+#include "graph_nav.hpp"
 #include "scan.hpp"
 
 namespace mgta {
@@ -158,6 +159,93 @@ __global__ __launch_bounds__(256) void graph_outgoing_kernel(GraphDev g, const i
     int od = g_outgoing(g, edges[i], o);
     outdeg[i] = (int8_t)od;
     for (int j = 0; j < 4; ++j) out4[i * 4 + j] = (j < od) ? (o[j] >> 4) : -1;
+}
+
+// mgta_sdbg_navigate: one lane per query, the product's own device functions.  The host has checked every id, position, rank and symbol
+// against the ranges the header states; what only the graph knows is checked here, from the lines, before the primitive is called, and
+// answered with MGTA_NAV_UNDEFINED.  `out` is n x nav_width(op) and arrives filled with MGTA_NAV_UNTOUCHED.
+__device__ __forceinline__ int64_t nav_hint_out(uint32_t h) { return h == kFdNone ? -1 : (int64_t)h; }
+__global__ __launch_bounds__(64) void graph_navigate_kernel(GraphDev g, int op, const int64_t *a0, const int64_t *a1, const int64_t *a2, int64_t n,
+                                                            int width, int64_t *out, uint8_t *out_sym) {
+    const int64_t i = (int64_t)blockIdx.x * 64 + threadIdx.x;
+    if (i >= n) return;
+    const int64_t x = a0[i];
+    int64_t *o = out + i * width;
+    // Forward(x) is defined and lands on an edge of the graph: what OutgoingEdges and the steps built on it walk down from
+    auto forward_lands = [&](int64_t e) {
+        if (g_W(g, e) == 0) return false;
+        const int64_t t = g_forward(g, e);
+        return t >= 0 && t < g.size;
+    };
+    // Backward(x) is defined (the node is no tip: a tip has no edge into it, its label is stored) and lands on an edge of the graph
+    auto backward_lands = [&](int64_t e) {
+        if (g_tip(g, e) || g_node_last_char(g, e) == 0) return false;
+        const int64_t t = g_backward(g, e);
+        return t >= 0 && t < g.size;
+    };
+    switch (op) {
+    case MGTA_NAV_RANK_LAST: o[0] = g_rank_last(g, x); break;
+    case MGTA_NAV_RANK_TIP: o[0] = g_rank_tip(g, x); break;
+    case MGTA_NAV_RANK_W: o[0] = g_rank_w(g, (int)a1[i], x); break;
+    case MGTA_NAV_SELECT_LAST: o[0] = g_select_last(g, x); break;
+    case MGTA_NAV_SELECT_W: o[0] = g_select_w(g, (int)a1[i], x); break;
+    case MGTA_NAV_FORWARD: o[0] = g_W(g, x) == 0 ? MGTA_NAV_UNDEFINED : g_forward(g, x); break;
+    case MGTA_NAV_BACKWARD: o[0] = (g_tip(g, x) || g_node_last_char(g, x) == 0) ? MGTA_NAV_UNDEFINED : g_backward(g, x); break;
+    case MGTA_NAV_LAST_INDEX: o[0] = d_last_index(g, x); break;
+    case MGTA_NAV_OUTGOING: {
+        if (g_valid(g, x) && !forward_lands(x)) { o[0] = MGTA_NAV_UNDEFINED; break; }
+        int64_t t[4] = {-1, -1, -1, -1};
+        const int od = g_outgoing(g, x, t);
+        o[0] = od;
+        for (int j = 0; j < 4; ++j) o[1 + j] = j < od ? t[j] : -1;
+        break;
+    }
+    case MGTA_NAV_INCOMING: {
+        if (g_valid(g, x) && !backward_lands(x)) { o[0] = MGTA_NAV_UNDEFINED; break; }
+        int64_t t[8];
+        const int id = d_incoming(g, x, t);
+        o[0] = id;
+        for (int j = 0; j < 4; ++j) o[1 + j] = j < id ? t[j] : -1;
+        break;
+    }
+    case MGTA_NAV_PREV_SIMPLE:
+        o[0] = (g_valid(g, x) && !backward_lands(x)) ? MGTA_NAV_UNDEFINED : prev_simple(g, x);
+        break;
+    case MGTA_NAV_NEXT_SIMPLE:
+        o[0] = (g_valid(g, x) && !forward_lands(x)) ? MGTA_NAV_UNDEFINED : next_simple(g, x);
+        break;
+    case MGTA_NAV_REVERSE_COMPLEMENT: o[0] = edge_reverse_complement(g, x); break;
+    case MGTA_NAV_LABEL:
+        d_label(g, x, out_sym + i * g.k);
+        o[0] = g.k;
+        break;
+    case MGTA_NAV_OUT_FD: {
+        FwdDesc in;
+        in.r = a1[i];
+        in.hint = a2[i] < 0 ? kFdNone : (uint32_t)a2[i];
+        // a descriptor's hint line must not lie behind the bit it looks for: the look-up only walks forwards
+        if (in.hint != kFdNone && in.r >= 0 && in.r < g.total_last && (int64_t)g.lines[in.hint].rank_last > in.r) { o[0] = MGTA_NAV_UNDEFINED; break; }
+        int64_t e0 = MGTA_NAV_UNTOUCHED, e1 = MGTA_NAV_UNTOUCHED, e2 = MGTA_NAV_UNTOUCHED, e3 = MGTA_NAV_UNTOUCHED;
+        FwdDesc f0, f1, f2, f3;
+        const int od = g_out_all_fd(g, x, in, e0, e1, e2, e3, f0, f1, f2, f3);
+        o[0] = od;
+        o[1] = e0; o[2] = e1; o[3] = e2; o[4] = e3;
+        if (od > 0) { o[5] = f0.r; o[9] = nav_hint_out(f0.hint); }
+        if (od > 1) { o[6] = f1.r; o[10] = nav_hint_out(f1.hint); }
+        if (od > 2) { o[7] = f2.r; o[11] = nav_hint_out(f2.hint); }
+        if (od > 3) { o[8] = f3.r; o[12] = nav_hint_out(f3.hint); }
+        for (int j = 0; j < 4; ++j) {
+            int64_t e = MGTA_NAV_UNTOUCHED;
+            FwdDesc f;
+            const int odn = g_out_nth_fd(g, x, in, j, e, f);
+            o[13 + j] = odn;
+            o[17 + j] = e;
+            if (j < odn) { o[21 + j] = f.r; o[25 + j] = nav_hint_out(f.hint); }
+        }
+        break;
+    }
+    default: break;
+    }
 }
 
 __global__ __launch_bounds__(64) void graph_index_kernel(GraphDev g, const uint8_t *seqs, int64_t n, int64_t *ids) {
@@ -719,6 +807,75 @@ int mgta_sdbg_outgoing(mgta_sdbg *g, const int64_t *edges, int64_t n, int64_t *o
         MGTA_HIP_CHECK(hipMemcpyAsync(out4, d_o.p, n * 32, hipMemcpyDeviceToHost, ctx->stream));
         MGTA_HIP_CHECK(hipMemcpyAsync(outdeg, d_d.p, n, hipMemcpyDeviceToHost, ctx->stream));
         MGTA_HIP_CHECK(hipStreamSynchronize(ctx->stream));
+        return MGTA_OK;
+    });
+}
+
+// int64 values per query in mgta_sdbg_navigate's `out` (include/megagta_hip.h has the layouts)
+static int nav_width(int op) {
+    switch (op) {
+    case MGTA_NAV_RANK_LAST: case MGTA_NAV_RANK_TIP: case MGTA_NAV_RANK_W: case MGTA_NAV_SELECT_LAST: case MGTA_NAV_SELECT_W:
+    case MGTA_NAV_FORWARD: case MGTA_NAV_BACKWARD: case MGTA_NAV_LAST_INDEX: case MGTA_NAV_PREV_SIMPLE: case MGTA_NAV_NEXT_SIMPLE:
+    case MGTA_NAV_REVERSE_COMPLEMENT: case MGTA_NAV_LABEL: return 1;
+    case MGTA_NAV_OUTGOING: case MGTA_NAV_INCOMING: return 5;
+    case MGTA_NAV_OUT_FD: return 29;
+    default: return -1;
+    }
+}
+
+int mgta_sdbg_navigate(mgta_sdbg *g, int op, const int64_t *arg0, const int64_t *arg1, const int64_t *arg2, int64_t n, int64_t *out, uint8_t *out_sym) {
+    const int width = nav_width(op);
+    const bool needs1 = op == MGTA_NAV_RANK_W || op == MGTA_NAV_SELECT_W || op == MGTA_NAV_OUT_FD, needs2 = op == MGTA_NAV_OUT_FD;
+    if (!g || width < 0 || n < 0 || (n > 0 && (!arg0 || !out || (needs1 && !arg1) || (needs2 && !arg2) || (op == MGTA_NAV_LABEL && !out_sym)))) {
+        set_error("mgta_sdbg_navigate: bad argument");
+        return MGTA_EINVAL;
+    }
+    const GraphDev &d = g->dev;
+    if (n > 0 && (op == MGTA_NAV_LABEL || op == MGTA_NAV_REVERSE_COMPLEMENT) && d.k > kMaxK) {
+        set_error("mgta_sdbg_navigate: k = %d > %d", d.k, kMaxK);
+        return MGTA_EUNSUPPORTED;
+    }
+    // every range below is the one the operation's own early-outs define (graph.hpp); nothing is launched before all n tuples passed
+    for (int64_t i = 0; i < n; ++i) {
+        const int64_t x = arg0[i];
+        bool ok;
+        switch (op) {
+        case MGTA_NAV_RANK_LAST: ok = x >= -1 && x < d.size; break;
+        case MGTA_NAV_RANK_W: ok = arg1[i] >= 1 && arg1[i] <= 4 && x >= -1 && x < d.size; break;
+        case MGTA_NAV_SELECT_LAST: ok = x >= -1 && x <= d.total_last; break;
+        case MGTA_NAV_SELECT_W: ok = arg1[i] >= 1 && arg1[i] <= 4 && x >= -1 && x <= d.total_w[arg1[i]]; break;
+        case MGTA_NAV_OUT_FD: ok = x >= 0 && x < d.size && arg2[i] >= -1 && arg2[i] < (int64_t)d.n_lines; break;
+        default: ok = x >= 0 && x < d.size; break;                       // an edge id; rank_tip has no early-out either
+        }
+        if (!ok) { set_error("mgta_sdbg_navigate: argument %lld of operation %d out of range", (long long)i, op); return MGTA_EINVAL; }
+    }
+    if (n == 0) return MGTA_OK;
+    if (d.size == 0) {                                                   // only rank(-1) and select(-1 | 0) are in range: no lines, no launch
+        for (int64_t i = 0; i < n; ++i) out[i] = (op == MGTA_NAV_SELECT_LAST || op == MGTA_NAV_SELECT_W) ? (arg0[i] < 0 ? -1 : 0) : 0;
+        return MGTA_OK;
+    }
+    return guarded("mgta_sdbg_navigate", [&]() -> int {
+        mgta_ctx *ctx = g->ctx;
+        MGTA_HIP_CHECK(hipSetDevice(ctx->device));
+        DevBuf d_a0, d_a1, d_a2, d_o, d_s;
+        const size_t ob = (size_t)n * width * 8, sb = op == MGTA_NAV_LABEL ? (size_t)n * d.k : 0;
+        d_a0.alloc(n * 8); d_o.alloc(ob);
+        MGTA_HIP_CHECK(hipMemcpyAsync(d_a0.p, arg0, n * 8, hipMemcpyHostToDevice, ctx->stream));
+        if (needs1) { d_a1.alloc(n * 8); MGTA_HIP_CHECK(hipMemcpyAsync(d_a1.p, arg1, n * 8, hipMemcpyHostToDevice, ctx->stream)); }
+        if (needs2) { d_a2.alloc(n * 8); MGTA_HIP_CHECK(hipMemcpyAsync(d_a2.p, arg2, n * 8, hipMemcpyHostToDevice, ctx->stream)); }
+        if (sb) { d_s.alloc(sb); MGTA_HIP_CHECK(hipMemsetAsync(d_s.p, 0, sb, ctx->stream)); }
+        std::vector<int64_t> fill((size_t)n * width, (int64_t)MGTA_NAV_UNTOUCHED);
+        MGTA_HIP_CHECK(hipMemcpyAsync(d_o.p, fill.data(), ob, hipMemcpyHostToDevice, ctx->stream));
+        hipLaunchKernelGGL(graph_navigate_kernel, dim3((unsigned)((n + 63) / 64)), dim3(64), 0, ctx->stream, g->dev, op, d_a0.as<int64_t>(), d_a1.as<int64_t>(),
+                           d_a2.as<int64_t>(), n, width, d_o.as<int64_t>(), d_s.as<uint8_t>());
+        MGTA_HIP_CHECK(hipGetLastError());
+        // (into buffers of our own first: the caller's outputs stay untouched unless everything succeeded)
+        std::vector<uint8_t> sym(sb);
+        MGTA_HIP_CHECK(hipMemcpyAsync(fill.data(), d_o.p, ob, hipMemcpyDeviceToHost, ctx->stream));
+        if (sb) MGTA_HIP_CHECK(hipMemcpyAsync(sym.data(), d_s.p, sb, hipMemcpyDeviceToHost, ctx->stream));
+        MGTA_HIP_CHECK(hipStreamSynchronize(ctx->stream));
+        memcpy(out, fill.data(), ob);
+        if (sb) memcpy(out_sym, sym.data(), sb);
         return MGTA_OK;
     });
 }

@@ -48,7 +48,7 @@ __device__ __forceinline__ LineR grp_load_line(const GraphDev &g, uint64_t li, i
 // Out: the edge of the next window, i.e. the edge of the node Forward(e) points to (succinct_dbg.h:155-164) whose label is c or c + 4,
 // with L = its line; -1 when that node has no such edge.
 //
-// This is NOT g_outgoing / g_outgoing_line: those answer -1 for a start edge whose `invalid` bit is set and skip invalid target edges
+// This is NOT g_outgoing / g_out_all_fd: those answer -1 for a start edge whose `invalid` bit is set and skip invalid target edges
 // (tips and $ edges after a load, everything `denovo` removed), while IndexBinarySearchEdge -- the contract of a window -- does not look
 // at that bit, and such an edge has a multiplicity in the stream like any other.  So the step forwards from any edge and scans the
 // target node exactly as IndexBinarySearchEdge scans the node it found: from the node's `last` edge downwards to the next last | tip bit.

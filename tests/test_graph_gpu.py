@@ -26,6 +26,25 @@ def _graphs(ctx, oracle, lib_prefix, k):
     return api.Graph(ctx, stream), og
 
 
+def _check_label_and_multi1_bits(g, og, ids, deg, out, qs=()):
+    """what mgta_sdbg_outgoing shifts away: the out-label and the multi1 bit A* translates and penalises by, as mgta_sdbg_navigate hands
+    them back (id << 4 | multi1 << 3 | label), against the oracle's bit vectors and, for an out-edge the reference's probe lists, its columns"""
+    ids = np.asarray(ids, dtype=np.int64)
+    nav = g.navigate("outgoing", ids)
+    assert np.array_equal(nav[:, 0], deg) and np.array_equal(np.where(nav[:, 1:] >= 0, nav[:, 1:] >> 4, -1), out)
+    bv = og.bitvectors()
+    packed = nav[:, 1:][nav[:, 1:] >= 0]
+    x = packed >> 4
+    w = ((bv["w"][x >> 4] >> ((x & 15) * 4).astype(np.uint64)) & np.uint64(15)).astype(np.int64)
+    m1 = ((bv["multi1"][x >> 6] >> (x & 63).astype(np.uint64)) & np.uint64(1)).astype(np.int64)
+    assert packed.size > 0 and np.array_equal(packed & 7, np.where(w > 4, w - 4, w)) and np.array_equal((packed >> 3) & 1, m1)
+    probed = {q["e"]: q for q in qs}
+    hits = [(v, probed[v >> 4]) for v in packed.tolist() if v >> 4 in probed]
+    assert len(hits) > 10 or ids.size <= len(qs)                        # (every edge asked: the probed ones are among the out-edges)
+    for v, q in hits:
+        assert v & 7 == (q["w"] - 4 if q["w"] > 4 else q["w"]) and (v >> 3) & 1 == q["multi1"], q["e"]
+
+
 def test_outgoing_all_edges_toy(ctx, oracle, golden_dir):
     g, og = _graphs(ctx, oracle, os.path.join(golden_dir, "toy", "reads.lib"), 44)
     assert g.size == og.size
@@ -37,9 +56,11 @@ def test_outgoing_all_edges_toy(ctx, oracle, golden_dir):
         assert d == n and o[:max(n, 0)] == ref, e
     # and the reference's own answers (probe)
     _, qs = H.parse_probe_graph(H.gz_lines(os.path.join(golden_dir, "toy", "graph_k44.txt.gz")))
+    _check_label_and_multi1_bits(g, og, ids, deg, out, qs)
     deg, out = g.outgoing([q["e"] for q in qs])
     for q, d, o in zip(qs, deg.tolist(), out.tolist()):
         assert d == q["od"] and o[:max(d, 0)] == q["out"]
+    _check_label_and_multi1_bits(g, og, [q["e"] for q in qs], deg, out, qs)
 
 
 @pytest.mark.parametrize("k", [29, 47])
@@ -52,9 +73,11 @@ def test_outgoing_ragged_every_edge(ctx, oracle, golden_dir, k):
         n, ref = og.outgoing(e)
         assert deg[e] == n and out[e, :max(n, 0)].tolist() == ref, e
     _, qs = H.parse_probe_graph(H.gz_lines(os.path.join(golden_dir, "ragged", f"graph_k{k}.txt.gz")))
+    _check_label_and_multi1_bits(g, og, ids, deg, out, qs)
     deg, out = g.outgoing([q["e"] for q in qs])
     for q, d, o in zip(qs, deg.tolist(), out.tolist()):
         assert d == q["od"] and o[:max(d, 0)] == q["out"]
+    _check_label_and_multi1_bits(g, og, [q["e"] for q in qs], deg, out, qs)
 
 
 def test_index_edges(ctx, oracle, golden_dir):
