@@ -520,6 +520,61 @@ int mgta_reads_pileup(mgta_sdbg *, const mgta_reads *reads, int reads_reversed, 
 int mgta_ctx_set_pileup_chunk(mgta_ctx *, uint32_t reads);   /* reads per queue grab, 0 = the library's; a switch for tests, moves no output */
 
 /* ------------------------------------------------------------------------------------------------
+ * Phase: which alleles of the variant positions (sites) of a contig travel together on one fragment -- a read, or two mates of a
+ * paired library.  The rule is this project's own; it counts, it reconstructs no haplotype.  Needs no graph: the inputs are the reads,
+ * the placements mgta_reads_pileup returned for them (per_read) and the sites.
+ *   Contigs  0 .. n - 1, len_i = offsets[i + 1] - offsets[i].  Their letters are not an input: an allele is the read's base.
+ *   Sites    contig i has the sites site_pos[site_off[i] .. site_off[i + 1]): 0-based positions, strictly ascending, each below len_i;
+ *            site_off[0] = 0, S = site_off[n].  A site is named by its index u in site_pos, counted over all contigs of the call.
+ *   Libraries  lib_end as in mgta_contig_sample_coverage: library s holds the reads [lib_end[s - 1], lib_end[s]), lib_end[-1] = 0;
+ *            lib_paired[s] != 0 says its reads are interleaved mates.  The reads scanned are [0, lib_end[n_libs - 1]).
+ *   Usable   read r is usable iff place[r].n_placed == 1.  With (i, o, d) = its contig, orient and diag it covers the positions
+ *            x in [max(0, d), min(len_i, d + L)) of contig i (none where that range is empty) and shows there the letter s^o[x - d],
+ *            s^o and L as in mgta_reads_pileup.  A record with another n_placed is not looked at beyond that field.
+ *   Mates    in a paired library that starts at read f, the reads f + 2j and f + 2j + 1 are mates (the interleaving `buildlib` writes);
+ *            an odd last read has no mate.  No read of an unpaired library has one.
+ *   Fragment two mates are ONE fragment iff both are usable, both lie on the same contig and their orients differ.  Every other usable
+ *            read is a fragment of its own.  The fragment's allele at a site is the letter of the read that covers the site; where
+ *            both mates cover it, that letter if they agree, and where they disagree there is no allele: one conflict.
+ *   Pairs    the sites u < v of one contig are tabled iff pos_v - pos_u < max_span (default 1000; 0 takes the default).  pair_off[u] =
+ *            the number of tabled pairs (u', v') with u' < u, pair_off[S] = n_pairs; the pair (u, v) has the index pair_off[u] + (v - u - 1).
+ * Outputs.  site_counts[u * 4 + b] = the fragments with the allele b (A C G T = 0 1 2 3) at site u.  joint[p * 16 + b_u * 4 + b_v] = the
+ * fragments that have the allele b_u at u AND the allele b_v at v, p the index of the tabled pair (u, v).  Stats: n_reads = the reads
+ * scanned; n_usable; n_fragments; n_mate_fragments = those of two mates; n_fragments_allele / n_fragments_linked = the fragments with at
+ * least one / at least two alleles; n_alleles = the sum of site_counts; n_conflicts = (fragment, site) with two letters that differ;
+ * n_pair_adds = the sum of joint; n_sites = S; n_pairs.  Everything but ms_* and peak_bytes is a function of the inputs alone: all sums
+ * are integers, no output depends on the order of the reads inside a library (mates moved together), of the contigs or of any device
+ * work, and mgta_ctx_set_phase_chunk moves none.
+ * mgta_phase_pairs is host-only (no device, no context): it validates the site lists (site_off[0] = 0, site_off ascending, the
+ * positions of a contig strictly ascending) and fills pair_off[S + 1], so that a caller can size joint.
+ * Limits, each MGTA_EINVAL naming it with nothing written: sites ascending and below the contig's length; place[r].contig < n (and not
+ * negative) for every usable read; lib_end not descending and lib_end[n_libs - 1] <= the reads uploaded; 1 <= n_libs <= 256;
+ * joint_cap (in pairs) >= pair_off[S], the message names the count needed; reads of at most 65535 bases; n < 2^31, S < 2^32,
+ * max_span >= 0; offsets ascending.  MGTA_EINVAL too for NULL reads, place, lib_end, lib_paired, offsets, site_off or pair_off, and for
+ * NULL site_pos, site_counts or joint where S or n_pairs is not 0.  Device memory: 24 bytes per read scanned, 20 per site, 64 per
+ * tabled pair; what does not fit is MGTA_ENOMEM.  n = 0 or S = 0: MGTA_OK and all outputs zero.
+ * ------------------------------------------------------------------------------------------------ */
+typedef struct mgta_phase_params { int32_t max_span; } mgta_phase_params;   /* 0 = the default, 1000 */
+typedef struct mgta_phase_stats {
+    int64_t n_reads, n_usable;
+    int64_t n_fragments, n_mate_fragments;
+    int64_t n_fragments_allele, n_fragments_linked;
+    int64_t n_alleles, n_conflicts, n_pair_adds;
+    int64_t n_sites, n_pairs;
+    uint64_t peak_bytes;             /* most device bytes of the call's own buffers */
+    double ms_upload, ms_scan, ms_total;   /* HIP events: place and tables host -> device; the scan; the two together */
+} mgta_phase_stats;
+int mgta_phase_pairs(const uint64_t *site_off /* [n + 1] */, const uint32_t *site_pos /* [S] */, int64_t n, int32_t max_span,
+                     uint64_t *pair_off /* [S + 1] */);
+int mgta_reads_phase(const mgta_reads *reads, int reads_reversed, const mgta_read_place *place /* [lib_end[n_libs - 1]] */,
+                     const uint64_t *lib_end /* [n_libs] */, const uint8_t *lib_paired /* [n_libs] */, int n_libs,
+                     const uint64_t *offsets /* [n + 1] */, int64_t n, const uint64_t *site_off /* [n + 1] */,
+                     const uint32_t *site_pos /* [S] */, const mgta_phase_params *params /* NULL = defaults */,
+                     uint32_t *site_counts /* [S * 4] */, uint64_t *pair_off /* [S + 1] */, uint32_t *joint /* [joint_cap * 16] */,
+                     uint64_t joint_cap /* pairs */, mgta_phase_stats *stats /* or NULL */);
+int mgta_ctx_set_phase_chunk(mgta_ctx *, uint32_t slots);   /* fragment slots per queue grab, 0 = the library's; a switch for tests, moves no output */
+
+/* ------------------------------------------------------------------------------------------------
  * De-replication ("get the unique merged contigs", the first step of the reference's bin/post_proc.sh:50-55: `Clustering.jar derep`,
  * then `ReadSeq.jar rm-dupseq -d`, both from a submodule the reference does not ship).  Needs no graph.  Sequence i =
  * seqs[offsets[i] .. offsets[i + 1]), a byte string compared byte for byte: no case folding, no reverse complement (a gene's contigs

@@ -222,6 +222,20 @@ class PileupStats(C.Structure):
         return {n: getattr(self, n) for n, _ in self._fields_}
 
 
+class PhaseParams(C.Structure):
+    _fields_ = [("max_span", C.c_int32)]
+
+
+class PhaseStats(C.Structure):
+    _fields_ = [("n_reads", C.c_int64), ("n_usable", C.c_int64), ("n_fragments", C.c_int64), ("n_mate_fragments", C.c_int64),
+                ("n_fragments_allele", C.c_int64), ("n_fragments_linked", C.c_int64), ("n_alleles", C.c_int64), ("n_conflicts", C.c_int64),
+                ("n_pair_adds", C.c_int64), ("n_sites", C.c_int64), ("n_pairs", C.c_int64), ("peak_bytes", C.c_uint64), ("ms_upload", C.c_double),
+                ("ms_scan", C.c_double), ("ms_total", C.c_double)]
+
+    def as_dict(self):
+        return {n: getattr(self, n) for n, _ in self._fields_}
+
+
 EDGE_SINK = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_int32, C.c_int32, C.POINTER(C.c_int64), C.POINTER(C.c_uint16), C.c_int64,
                         C.POINTER(C.c_uint16), C.c_int64, C.POINTER(C.c_uint32), C.c_int64)
 CONTIG_SINK = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_void_p, C.c_int64,
@@ -288,6 +302,10 @@ SYMBOLS = {
     "mgta_reads_pileup": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_uint64, C.c_char_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
                                    C.c_void_p, C.c_void_p]),
     "mgta_ctx_set_pileup_chunk": (C.c_int, [C.c_void_p, C.c_uint32]),
+    "mgta_phase_pairs": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_int32, C.c_void_p]),
+    "mgta_reads_phase": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p,
+                                  C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p]),
+    "mgta_ctx_set_phase_chunk": (C.c_int, [C.c_void_p, C.c_uint32]),
     "mgta_seqs_derep": (C.c_int, [C.c_void_p, C.c_char_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "mgta_ctx_set_derep_hash_bits": (C.c_int, [C.c_void_p, C.c_int]),
     "mgta_seqs_align": (C.c_int, [C.c_void_p, C.c_void_p, C.c_char_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),

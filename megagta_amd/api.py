@@ -123,6 +123,73 @@ class Context:
         switch for tests"""
         check(self._L.mgta_ctx_set_pileup_chunk(self.h, int(reads)), "mgta_ctx_set_pileup_chunk")
 
+    def set_phase_chunk(self, slots: int = 0):
+        """fragment slots a group of lanes of Context.phase takes per visit to the queue head (0 = the library's choice); moves no
+        output -- a switch for tests"""
+        check(self._L.mgta_ctx_set_phase_chunk(self.h, int(slots)), "mgta_ctx_set_phase_chunk")
+
+    @staticmethod
+    def _site_lists(sites) -> tuple[np.ndarray, np.ndarray]:
+        """per contig a list of 0-based positions -> (site_off uint64[n + 1], site_pos uint32[S])"""
+        lists = [np.asarray(s, dtype=np.int64).reshape(-1) for s in sites]
+        for s in lists:
+            if s.size and (int(s.min()) < 0 or int(s.max()) > 0xFFFFFFFF):
+                raise ValueError("a site is a position 0 .. 2^32 - 1")
+        off = np.zeros(len(lists) + 1, dtype=np.uint64)
+        if lists:
+            np.cumsum([s.size for s in lists], out=off[1:])
+        pos = np.concatenate(lists).astype(np.uint32) if lists else np.zeros(0, dtype=np.uint32)
+        return off, np.ascontiguousarray(pos)
+
+    @staticmethod
+    def phase_pairs(sites, max_span: int = 0) -> np.ndarray:
+        """mgta_phase_pairs (host only, so it needs no context): sites = per contig a list of ascending 0-based positions -> pair_off uint64[S + 1], the number of
+        tabled pairs in front of every site; pair (u, v) has the index pair_off[u] + (v - u - 1), pair_off[S] sizes `joint`."""
+        off, pos = Context._site_lists(sites)
+        pair_off = np.zeros(int(off[-1]) + 1, dtype=np.uint64)
+        check(_lib.load().mgta_phase_pairs(off.ctypes.data, pos.ctypes.data if pos.size else None, len(off) - 1, int(max_span), pair_off.ctypes.data), "mgta_phase_pairs")
+        return pair_off
+
+    def phase(self, reads: "Reads", place, libs, lens_or_seqs, sites, params: dict | None = None, reads_reversed: bool = True, joint_cap: int | None = None) -> dict:
+        """mgta_reads_phase: the alleles of the sites that one fragment shows together, by the rule of include/megagta_hip.h.  place =
+        Graph.pileup(..., per_read=True)["reads"] of `reads` against the same contigs; libs = [(lib_end, paired), ...] in read order;
+        lens_or_seqs = per contig its length or its letters; sites = per contig a list of ascending 0-based positions; params =
+        dict(max_span=), 0 or missing = 1000.  joint_cap (pairs) defaults to what the sites need.  -> dict(site_counts = uint32[S, 4],
+        pair_off = uint64[S + 1], joint = uint32[n_pairs, 16], site_off = int64[n + 1], site_pos = uint32[S], stats)."""
+        from .pileup import READ_DTYPE
+        if reads.ctx is not self:
+            raise MegaGtaError("mgta_reads_phase: the reads belong to another context")
+        lens = [int(x) if isinstance(x, (int, np.integer)) else len(x) for x in lens_or_seqs]
+        n = len(lens)
+        offsets = np.zeros(n + 1, dtype=np.uint64)
+        if n:
+            np.cumsum(lens, out=offsets[1:])
+        off, pos = self._site_lists(sites)
+        if len(off) - 1 != n:
+            raise ValueError("sites and contigs differ in number")
+        unknown = set(params or {}) - {"max_span"}
+        if unknown:
+            raise ValueError(f"unknown phase parameters: {sorted(unknown)}")
+        par = _lib.PhaseParams()
+        par.max_span = int((params or {}).get("max_span", 0))
+        ends = np.ascontiguousarray([int(e) for e, _ in libs], dtype=np.uint64)
+        paired = np.ascontiguousarray([1 if p else 0 for _, p in libs], dtype=np.uint8)
+        pl = np.ascontiguousarray(place, dtype=READ_DTYPE)
+        if ends.size and pl.size < int(ends[-1]):
+            raise ValueError(f"{pl.size} placement records for {int(ends[-1])} reads")
+        S = int(off[-1])
+        if joint_cap is None:
+            joint_cap = int(self.phase_pairs(sites, par.max_span)[-1])
+        counts = np.zeros((S, 4), dtype=np.uint32)
+        pair_off = np.zeros(S + 1, dtype=np.uint64)
+        joint = np.zeros((int(joint_cap), 16), dtype=np.uint32)
+        st = _lib.PhaseStats()
+        check(self._L.mgta_reads_phase(reads.h, int(bool(reads_reversed)), pl.ctypes.data if pl.size else None, ends.ctypes.data if ends.size else None,
+                                       paired.ctypes.data if paired.size else None, int(ends.size), offsets.ctypes.data, n, off.ctypes.data,
+                                       pos.ctypes.data if S else None, C.byref(par), counts.ctypes.data if S else None, pair_off.ctypes.data,
+                                       joint.ctypes.data if joint.size else None, int(joint_cap), C.byref(st)), "mgta_reads_phase")
+        return dict(site_counts=counts, pair_off=pair_off, joint=joint[:int(pair_off[-1])], site_off=off.astype(np.int64), site_pos=pos, stats=st.as_dict())
+
     def set_derep_hash_bits(self, bits: int = 64):
         """bits of both hashes `derep` keeps (1 .. 64, the default): with a few bits nearly every key collides.  The result does not
         depend on it; only stats["n_compares"] does."""

@@ -813,6 +813,15 @@ RefWords load_reference_words(const std::string &faa_path, int kaa) {
 }
 
 // ---- pileup files ----------------------------------------------------------------------------------------------------------------------
+// the variant rule of one position: its four counts and the contig's letter as given
+static bool pileup_is_variant(const uint32_t *c, char ref, uint32_t min_depth, uint32_t min_alt_permille) {
+    const uint64_t depth = (uint64_t)c[0] + c[1] + c[2] + c[3];
+    const char up = (char)(ref & 0xDF);
+    const int code = up == 'A' ? 0 : up == 'C' ? 1 : up == 'G' ? 2 : up == 'T' ? 3 : -1;
+    const uint64_t alt = depth - (code >= 0 ? c[code] : 0);
+    return depth >= min_depth && alt * 1000 >= (uint64_t)min_alt_permille * depth;
+}
+
 PileupTexts format_pileup(const std::vector<std::string> &names, const std::string &seqs, const std::vector<uint64_t> &offsets, const uint32_t *counts,
                           const uint32_t *uniq, const PileupRow *rows, uint32_t min_depth, uint32_t min_alt_permille, bool per_base) {
     PileupTexts out;
@@ -826,10 +835,8 @@ PileupTexts format_pileup(const std::vector<std::string> &names, const std::stri
         for (uint64_t x = 0; x < len; ++x) {
             const uint32_t *c = counts + (b + x) * 4;
             const uint64_t depth = (uint64_t)c[0] + c[1] + c[2] + c[3];
-            const char ref = seqs[(size_t)(b + x)], up = (char)(ref & 0xDF);
-            const int code = up == 'A' ? 0 : up == 'C' ? 1 : up == 'G' ? 2 : up == 'T' ? 3 : -1;
-            const uint64_t alt = depth - (code >= 0 ? c[code] : 0);
-            const bool is_variant = depth >= min_depth && alt * 1000 >= (uint64_t)min_alt_permille * depth;
+            const char ref = seqs[(size_t)(b + x)];
+            const bool is_variant = pileup_is_variant(c, ref, min_depth, min_alt_permille);
             if (!is_variant && !per_base) continue;
             const int m = snprintf(buf, sizeof buf, "\t%llu\t%c\t%llu\t%u\t%u\t%u\t%u\t%u\n", (unsigned long long)(x + 1), ref, (unsigned long long)depth, c[0], c[1], c[2],
                                    c[3], uniq[b + x]);
@@ -843,6 +850,92 @@ PileupTexts format_pileup(const std::vector<std::string> &names, const std::stri
                                (unsigned long long)listed);
         out.summary += names[i];
         out.summary.append(buf, (size_t)m);
+    }
+    return out;
+}
+
+// ---- phase files -----------------------------------------------------------------------------------------------------------------------
+void pileup_variant_sites(const std::string &seqs, const std::vector<uint64_t> &offsets, const uint32_t *counts, uint32_t min_depth, uint32_t min_alt_permille,
+                          std::vector<uint64_t> &site_off, std::vector<uint32_t> &site_pos) {
+    site_off.assign(1, 0);
+    site_pos.clear();
+    for (size_t i = 0; i + 1 < offsets.size(); ++i) {
+        const uint64_t b = offsets[i], len = offsets[i + 1] - b;
+        for (uint64_t x = 0; x < len; ++x)
+            if (pileup_is_variant(counts + (b + x) * 4, seqs[(size_t)(b + x)], min_depth, min_alt_permille)) site_pos.push_back((uint32_t)x);
+        site_off.push_back(site_pos.size());
+    }
+}
+
+PhaseTexts format_phase(const std::vector<std::string> &names, const std::vector<uint64_t> &site_off, const std::vector<uint32_t> &site_pos,
+                        const std::vector<uint64_t> &pair_off, const uint32_t *joint, uint64_t min_link, uint64_t min_hap_permille) {
+    PhaseTexts out;
+    out.links = "#contig\tpos1\tpos2\tfragments\thaplotypes\tphased\n";
+    out.blocks = "#contig\tblock\tsites\tfirst\tlast\tpositions\n";
+    const size_t S = site_pos.size();
+    std::vector<uint64_t> parent(S);
+    for (size_t u = 0; u < S; ++u) parent[u] = u;
+    auto find = [&](uint64_t a) {
+        while (parent[a] != a) { parent[a] = parent[parent[a]]; a = parent[a]; }
+        return a;
+    };
+    char buf[128];
+    for (size_t i = 0; i < names.size(); ++i) {
+        for (uint64_t u = site_off[i]; u < site_off[i + 1]; ++u)
+            for (uint64_t p = pair_off[u]; p < pair_off[u + 1]; ++p) {
+                const uint32_t *c = joint + p * 16;
+                const uint64_t v = u + 1 + (p - pair_off[u]);
+                uint64_t total = 0;
+                for (int j = 0; j < 16; ++j) total += c[j];
+                if (total < std::max<uint64_t>(1, min_link)) continue;
+                int order[16], n_cells = 0;
+                for (int j = 0; j < 16; ++j) if (c[j]) order[n_cells++] = j;
+                std::sort(order, order + n_cells, [&](int a, int b) { return c[a] != c[b] ? c[a] > c[b] : a < b; });   // (the cell number orders the letters)
+                int n_major = 0;
+                unsigned seen1 = 0, seen2 = 0;
+                bool shared = false;
+                for (int q = 0; q < n_cells; ++q) {
+                    const int j = order[q];
+                    if ((uint64_t)c[j] * 1000 < min_hap_permille * total) continue;
+                    ++n_major;
+                    if (((seen1 >> (j >> 2)) & 1u) || ((seen2 >> (j & 3)) & 1u)) shared = true;
+                    seen1 |= 1u << (j >> 2); seen2 |= 1u << (j & 3);
+                }
+                const bool phased = n_major >= 2 && !shared;
+                int m = snprintf(buf, sizeof buf, "\t%u\t%u\t%llu\t", site_pos[u] + 1, site_pos[v] + 1, (unsigned long long)total);
+                out.links += names[i];
+                out.links.append(buf, (size_t)m);
+                for (int q = 0; q < n_cells; ++q) {
+                    m = snprintf(buf, sizeof buf, "%s%c%c:%u", q ? "," : "", "ACGT"[order[q] >> 2], "ACGT"[order[q] & 3], c[order[q]]);
+                    out.links.append(buf, (size_t)m);
+                }
+                out.links += phased ? "\t1\n" : "\t0\n";
+                if (phased) {
+                    const uint64_t a = find(u), b = find(v);
+                    parent[std::max(a, b)] = std::min(a, b);                  // the root is the component's first site
+                }
+            }
+        // the components of this contig, by their first site
+        uint64_t number = 0;
+        for (uint64_t r = site_off[i]; r < site_off[i + 1]; ++r) {
+            if (find(r) != r) continue;
+            std::string positions;
+            uint64_t n_sites = 0;
+            uint32_t last = 0;
+            for (uint64_t u = r; u < site_off[i + 1]; ++u) {
+                if (find(u) != r) continue;
+                const int m = snprintf(buf, sizeof buf, "%s%u", n_sites ? "," : "", site_pos[u] + 1);
+                positions.append(buf, (size_t)m);
+                last = site_pos[u] + 1;
+                ++n_sites;
+            }
+            if (n_sites < 2) continue;
+            const int m = snprintf(buf, sizeof buf, "\t%llu\t%llu\t%u\t%u\t", (unsigned long long)++number, (unsigned long long)n_sites, site_pos[r] + 1, last);
+            out.blocks += names[i];
+            out.blocks.append(buf, (size_t)m);
+            out.blocks += positions;
+            out.blocks += '\n';
+        }
     }
     return out;
 }

@@ -124,4 +124,13 @@ struct PileupTexts { std::string summary, variants, depth; };                   
 PileupTexts format_pileup(const std::vector<std::string> &names, const std::string &seqs, const std::vector<uint64_t> &offsets, const uint32_t *counts,
                           const uint32_t *uniq, const PileupRow *rows, uint32_t min_depth, uint32_t min_alt_permille, bool per_base);
 
+// ---- phase files (megagta_amd/phase.py prints the same bytes) -------------------------------------------------------
+struct PhaseTexts { std::string links, blocks; };
+// the positions format_pileup lists as variants: site_off[n + 1] and the 0-based site_pos
+void pileup_variant_sites(const std::string &seqs, const std::vector<uint64_t> &offsets, const uint32_t *counts, uint32_t min_depth, uint32_t min_alt_permille,
+                          std::vector<uint64_t> &site_off, std::vector<uint32_t> &site_pos);
+// names in the call's order; site_off[n + 1], site_pos[S], pair_off[S + 1] and joint[pair_off[S]][16] as mgta_reads_phase leaves them
+PhaseTexts format_phase(const std::vector<std::string> &names, const std::vector<uint64_t> &site_off, const std::vector<uint32_t> &site_pos,
+                        const std::vector<uint64_t> &pair_off, const uint32_t *joint, uint64_t min_link, uint64_t min_hap_permille);
+
 }  // namespace mgta_host

@@ -1086,18 +1086,23 @@ static bool write_text_file(const std::string &path, const std::string &text) {
 }
 // ---- pileup: the reads of the library placed on the records of a FASTA (mgta_reads_pileup): per-base depth, placements and the positions
 // where the reads disagree with a contig.  The rule and the file formats are this project's own: INTEGRATION.md 2p; megagta_amd/pileup.py
-// prints the same bytes.
+// prints the same bytes.  With --phase the same call also returns the placement of every read, the positions listed as variants are
+// the sites and mgta_reads_phase counts which of their alleles one fragment shows together (the library table of .lib_info says which
+// reads are mates): INTEGRATION.md 2q; megagta_amd/phase.py prints the same bytes.
 static int main_pileup(int argc, char **argv) {
     const char *usage = "Usage: megagta pileup <sdbg_prefix> <read.lib> <contigs.fasta> <out_prefix> [--min-anchors N] [--min-overlap N] [--max-mismatch-permille N] "
-                        "[--min-depth N] [--min-alt-permille N] [--per-base]\n";
+                        "[--min-depth N] [--min-alt-permille N] [--per-base] [--phase [--max-span N] [--min-link N] [--min-hap-permille N]]\n";
     if (argc < 5) { fputs(usage, stderr); return 1; }
     mgta_pileup_params par{0, 0, 0};
-    long long min_depth = 8, min_alt = 100;
-    bool per_base = false;
+    long long min_depth = 8, min_alt = 100, max_span = 0, min_link = 4, min_hap = 100;
+    bool per_base = false, phase = false, phase_opt = false;
     for (int i = 5; i < argc; ++i) {
         const std::string a = argv[i];
         if (a == "--per-base") { per_base = true; continue; }
-        long long *into64 = a == "--min-depth" ? &min_depth : a == "--min-alt-permille" ? &min_alt : nullptr;
+        if (a == "--phase") { phase = true; continue; }
+        long long *into64 = a == "--min-depth" ? &min_depth : a == "--min-alt-permille" ? &min_alt : a == "--max-span" ? &max_span : a == "--min-link" ? &min_link :
+                            a == "--min-hap-permille" ? &min_hap : nullptr;
+        if (into64 == &max_span || into64 == &min_link || into64 == &min_hap) phase_opt = true;
         int32_t *into = a == "--min-anchors" ? &par.min_anchors : a == "--min-overlap" ? &par.min_overlap : a == "--max-mismatch-permille" ? &par.max_mismatch_permille : nullptr;
         char *end = nullptr;
         if ((!into && !into64) || i + 1 >= argc) { fputs(usage, stderr); return 1; }
@@ -1105,6 +1110,7 @@ static int main_pileup(int argc, char **argv) {
         if (!*argv[i] || *end || v < 0 || v > 0x7FFFFFFFll) { fprintf(stderr, "megagta pileup: %s %s is not a count\n%s", a.c_str(), argv[i], usage); return 1; }
         if (into) *into = (int32_t)v; else *into64 = v;
     }
+    if (phase_opt && !phase) { fprintf(stderr, "megagta pileup: --max-span, --min-link and --min-hap-permille are options of --phase\n%s", usage); return 1; }
     RssLine rss;
     const std::string prefix = argv[1], lib = argv[2], fasta = argv[3], out_prefix = argv[4];
     std::vector<std::string> names;
@@ -1112,11 +1118,18 @@ static int main_pileup(int argc, char **argv) {
     std::vector<uint64_t> offsets;
     read_fasta_records(fasta, names, seqs, offsets);
     const int64_t n = (int64_t)names.size();
+    std::vector<LibRow> libs;
+    if (phase) {
+        libs = read_lib_table(lib);
+        if (libs.empty() || libs.size() > 256) die("pileup --phase: %s.lib_info names %zu libraries (1 .. 256 are supported)", lib.c_str(), libs.size());
+    }
     double t0 = now_s();
     PackedReads local;
     PackedReads::Mark mk;
     PackedReads &pr = lib_get(lib + ".bin", lib, "", false, local, mk);  // reversed, as buildgraph uploads it: a worker that still holds it does not read it again
     const uint64_t n_reads = pr.start.size() - 1;
+    if (phase && (uint64_t)(libs.back().to + 1) != n_reads)
+        die("pileup --phase: %s.lib_info names %lld reads, %s.bin holds %llu", lib.c_str(), libs.back().to + 1, lib.c_str(), (unsigned long long)n_reads);
     logf("%llu reads, %llu total bases (load %.3f s)", (unsigned long long)n_reads, (unsigned long long)pr.start.back(), now_s() - t0);
     t0 = now_s();
     mgta_ctx *ctx = ctx_get();
@@ -1139,23 +1152,48 @@ static int main_pileup(int argc, char **argv) {
     const size_t n_sym = (size_t)offsets.back();
     std::vector<uint32_t> counts(n_sym * 4 + 4), uniq(n_sym + 1);
     std::vector<mgta_contig_pileup> rec((size_t)n + 1);
+    std::vector<mgta_read_place> place(phase ? (size_t)n_reads + 1 : 0);
     mgta_pileup_stats st;
     // all records in ONE call: the best-hit rule looks at every contig of the file
-    if (mgta_reads_pileup(g, rd, 1, n_reads, seqs.data(), offsets.data(), n, &par, counts.data(), uniq.data(), rec.data(), nullptr, &st) != MGTA_OK)
+    if (mgta_reads_pileup(g, rd, 1, n_reads, seqs.data(), offsets.data(), n, &par, counts.data(), uniq.data(), rec.data(), phase ? place.data() : nullptr, &st) != MGTA_OK)
         die("mgta_reads_pileup: %s", mgta_last_error());
-    mgta_reads_free(rd);
     logf("pileup of %lld contigs: %lld windows, %lld keys, %lld occurrences (%.1f + %.1f ms); %lld reads, %lld read windows, %lld on a key; %lld reads with a candidate, "
          "%lld candidates, %lld verified; %lld reads placed, %lld more than once, %lld placements, %lld bases (%.1f ms); records %.1f ms; %.1f MB on the device; wall %.3f s",
          (long long)n, (long long)st.n_contig_windows, (long long)st.n_keys, (long long)st.n_occurrences, st.ms_keys, st.ms_index, (long long)st.n_reads,
          (long long)st.n_read_windows, (long long)st.n_hit_windows, (long long)st.n_reads_with_candidate, (long long)st.n_candidates, (long long)st.n_verified,
          (long long)st.n_reads_placed, (long long)st.n_reads_multi, (long long)st.n_placements, (long long)st.n_bases_piled, st.ms_scan, st.ms_records,
          (double)st.peak_bytes / 1e6, now_s() - t0);
+    PhaseTexts ptxt;
+    if (phase) {
+        const double t1 = now_s();
+        std::vector<uint64_t> site_off, lib_end(libs.size());
+        std::vector<uint32_t> site_pos;
+        std::vector<uint8_t> lib_paired(libs.size());
+        for (size_t s = 0; s < libs.size(); ++s) { lib_end[s] = (uint64_t)(libs[s].to + 1); lib_paired[s] = libs[s].pe ? 1 : 0; }
+        pileup_variant_sites(seqs, offsets, counts.data(), (uint32_t)min_depth, (uint32_t)min_alt, site_off, site_pos);
+        std::vector<uint64_t> pair_off(site_pos.size() + 1);
+        if (mgta_phase_pairs(site_off.data(), site_pos.data(), n, (int32_t)max_span, pair_off.data()) != MGTA_OK) die("mgta_phase_pairs: %s", mgta_last_error());
+        std::vector<uint32_t> site_counts(site_pos.size() * 4 + 4), joint((size_t)pair_off.back() * 16 + 16);
+        const mgta_phase_params pp{(int32_t)max_span};
+        mgta_phase_stats ps;
+        if (mgta_reads_phase(rd, 1, place.data(), lib_end.data(), lib_paired.data(), (int)libs.size(), offsets.data(), n, site_off.data(), site_pos.data(), &pp,
+                             site_counts.data(), pair_off.data(), joint.data(), pair_off.back(), &ps) != MGTA_OK)
+            die("mgta_reads_phase: %s", mgta_last_error());
+        logf("phase of %lld sites, %lld pairs: %lld reads, %lld usable, %lld fragments, %lld of two mates; %lld with an allele, %lld with two or more; %lld alleles, %lld "
+             "conflicts, %lld pair adds (upload %.1f ms, scan %.1f ms); %.1f MB on the device; wall %.3f s", (long long)ps.n_sites, (long long)ps.n_pairs, (long long)ps.n_reads,
+             (long long)ps.n_usable, (long long)ps.n_fragments, (long long)ps.n_mate_fragments, (long long)ps.n_fragments_allele, (long long)ps.n_fragments_linked,
+             (long long)ps.n_alleles, (long long)ps.n_conflicts, (long long)ps.n_pair_adds, ps.ms_upload, ps.ms_scan, (double)ps.peak_bytes / 1e6, now_s() - t1);
+        ptxt = format_phase(names, site_off, site_pos, pair_off, joint.data(), (uint64_t)min_link, (uint64_t)min_hap);
+    }
+    mgta_reads_free(rd);
     static_assert(sizeof(PileupRow) == sizeof(mgta_contig_pileup), "PileupRow is mgta_contig_pileup");
     const PileupTexts txt = format_pileup(names, seqs, offsets, counts.data(), uniq.data(), reinterpret_cast<const PileupRow *>(rec.data()), (uint32_t)min_depth,
                                           (uint32_t)min_alt, per_base);
     if (!write_text_file(out_prefix + "_pileup.txt", txt.summary)) die("cannot write %s_pileup.txt", out_prefix.c_str());
     if (!write_text_file(out_prefix + "_pileup_variants.txt", txt.variants)) die("cannot write %s_pileup_variants.txt", out_prefix.c_str());
     if (per_base && !write_text_file(out_prefix + "_pileup_depth.txt", txt.depth)) die("cannot write %s_pileup_depth.txt", out_prefix.c_str());
+    if (phase && !write_text_file(out_prefix + "_phase_links.txt", ptxt.links)) die("cannot write %s_phase_links.txt", out_prefix.c_str());
+    if (phase && !write_text_file(out_prefix + "_phase_blocks.txt", ptxt.blocks)) die("cannot write %s_phase_blocks.txt", out_prefix.c_str());
     if (!g_sess.active) mgta_sdbg_free(g);
     ctx_put(ctx);
     return 0;

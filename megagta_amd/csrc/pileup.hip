@@ -58,13 +58,6 @@ struct PileArgs {
     unsigned long long *counters;
 };
 
-__global__ __launch_bounds__(256) void pile_maxlen_kernel(const uint64_t *start, uint64_t n_reads, unsigned long long *out) {
-    const uint64_t stride = (uint64_t)gridDim.x * 256;
-    unsigned long long mx = 0;
-    for (uint64_t r = (uint64_t)blockIdx.x * 256 + threadIdx.x; r < n_reads; r += stride) mx = max(mx, (unsigned long long)(start[r + 1] - start[r]));
-    if (mx) atomicMax(out, mx);
-}
-
 // the occurrences per key: a window as given lies on the key of its own edge (strand 0), and its reverse complement on the key of that
 // one's edge (strand 1; only where the window itself has an edge: an anchor is a window of the contig as given)
 __global__ __launch_bounds__(256) void pile_occ_count_kernel(const uint32_t *own, const uint32_t *rc, const uint32_t *dense, uint64_t n_win, uint32_t *cnt) {
@@ -95,12 +88,6 @@ __global__ __launch_bounds__(256) void pile_occ_fill_kernel(const uint64_t *woff
             occ[occ_off[d1] + atomicAdd(&cursor[d1], 1u)] = v | 1ull;
         }
     }
-}
-
-// base j of the read in orientation o as a symbol 1..4.  same = (o == the orientation the stored order walks), comp = 3 for o = 1
-__device__ __forceinline__ uint32_t pile_base(const uint32_t *packed, uint64_t s0, uint32_t len, int same, uint32_t comp, uint32_t j) {
-    const uint64_t q = s0 + (same ? j : len - 1 - j);
-    return (((packed[q >> 4] >> (30 - 2 * (int)(q & 15))) & 3u) ^ comp) + 1;
 }
 
 // One pass over the anchors of a read.  COMMIT = false: the best score, its ties and the lowest of them.  COMMIT = true: the adds of

@@ -1,7 +1,7 @@
 // walk.hpp -- what the walks over the graph share: the forward step of a walk (cov_step) behind an index search (g_index_edge, graph.hpp),
 // the walk that leaves the edge id of every window of a set of contigs (share_walk_kernel), and the edge-keyed table of a call's
-// contig windows on both strands (SampleTable with its add, find, count and numbering kernels).  coverage.hip and pileup.hip include it;
-// every kernel has internal linkage, so each of the two compiles its own copy.
+// contig windows on both strands (SampleTable with its add, find, count and numbering kernels).  coverage.hip and pileup.hip include it,
+// and phase.hip for the letter of a packed read (pile_base); every kernel has internal linkage, so each of them compiles its own copy.
 #pragma once
 #include <algorithm>
 #include <vector>
@@ -287,6 +287,22 @@ __global__ __launch_bounds__(256) void sample_dense_kernel(SampleTable t, unsign
         first = wave_uniform((uint64_t)first);
         t.dense[i] = used ? (uint32_t)(first + (uint64_t)__popcll(m & lanemask_lt()) + 1) : 0u;
     }
+}
+
+// ---- the packed reads, as the scans of pileup.hip and phase.hip read them
+
+// the longest of the reads [0, n_reads) (atomicMax into *out, zeroed by the caller)
+__global__ __launch_bounds__(256) void pile_maxlen_kernel(const uint64_t *start, uint64_t n_reads, unsigned long long *out) {
+    const uint64_t stride = (uint64_t)gridDim.x * 256;
+    unsigned long long mx = 0;
+    for (uint64_t r = (uint64_t)blockIdx.x * 256 + threadIdx.x; r < n_reads; r += stride) mx = max(mx, (unsigned long long)(start[r + 1] - start[r]));
+    if (mx) atomicMax(out, mx);
+}
+
+// base j of the read in orientation o as a symbol 1..4.  same = (o == the orientation the stored order walks), comp = 3 for o = 1
+__device__ __forceinline__ uint32_t pile_base(const uint32_t *packed, uint64_t s0, uint32_t len, int same, uint32_t comp, uint32_t j) {
+    const uint64_t q = s0 + (same ? j : len - 1 - j);
+    return (((packed[q >> 4] >> (30 - 2 * (int)(q & 15))) & 3u) ^ comp) + 1;
 }
 }  // namespace
 }  // namespace mgta

@@ -92,7 +92,13 @@ USAGE = """Usage:
     --min-overlap N           needs --pileup: fewest contig positions a placement covers [k + 1 of the last graph]
     --max-mismatch-permille N needs --pileup: most mismatches per 1000 covered positions [50]
     --min-depth N             needs --pileup: fewest reads on a listed variant position [8]
-    --min-alt-permille N      needs --pileup: smallest share of reads that differ from the contig there, per 1000 [100]"""
+    --min-alt-permille N      needs --pileup: smallest share of reads that differ from the contig there, per 1000 [100]
+    --phase          needs --pileup: the listed variant positions of a contig linked through reads and mates (the pairs of the -1/-2 and
+                     --12 libraries): nucl_merged[_rmdup]_phase_links.txt (per pair of positions the alleles one fragment shows at
+                     both) and nucl_merged[_rmdup]_phase_blocks.txt (the positions joined by phased links)
+    --max-span N              needs --phase: pairs of positions less than N apart are tabled [1000]
+    --min-link N              needs --phase: fewest fragments on a listed pair [4]
+    --min-hap-permille N      needs --phase: smallest share of a pair's fragments that makes a haplotype count, per 1000 [100]"""
 
 
 class Usage(Exception):
@@ -143,6 +149,8 @@ class Opt:
         self.sample_abund = False
         self.pileup = False
         self.pileup_opts = {}            # the numeric options of --pileup that were given: flag -> value
+        self.phase = False
+        self.phase_opts = {}             # the numeric options of --phase that were given: flag -> value
 
 
 opt = Opt()
@@ -153,7 +161,7 @@ LONG = ["help", "read=", "12=", "out-dir=", "memory=", "gpu-mem=", "min-contig-l
         "prune-len=", "low-cov-penalty=", "bin=", "one-process-per-step", "gpus=", "coverage", "match-reads", "derep", "align", "posterior", "cluster",
         "cluster-dist=", "cluster-min-overlap=", "cluster-dists=", "nearest", "nearest-scoring=", "nearest-gap-open=", "nearest-gap-extend=",
         "chimera", "chimera-min-seg=", "chimera-min-gain=", "taxon-abund", "sample-abund", "pileup", "min-anchors=", "min-overlap=",
-        "max-mismatch-permille=", "min-depth=", "min-alt-permille="]
+        "max-mismatch-permille=", "min-depth=", "min-alt-permille=", "phase", "max-span=", "min-link=", "min-hap-permille="]
 
 
 def parse_opt(argv):
@@ -222,6 +230,11 @@ def parse_opt(argv):
             if not v.isdigit():
                 raise Usage("%s %s: a count is expected" % (o, v))
             opt.pileup_opts[o] = int(v)
+        elif o == "--phase": opt.phase = True
+        elif o in ("--max-span", "--min-link", "--min-hap-permille"):
+            if not v.isdigit():
+                raise Usage("%s %s: a count is expected" % (o, v))
+            opt.phase_opts[o] = int(v)
         else:
             raise Usage("Invalid option " + o)
     opt.temp_dir = opt.out_dir + "tmp/"
@@ -283,6 +296,12 @@ def check_opt():
         raise Usage("%s needs --pileup: it is an option of that step" % sorted(opt.pileup_opts)[0])
     if opt.pileup_opts.get("--max-mismatch-permille", 0) > 1000 or opt.pileup_opts.get("--min-alt-permille", 0) > 1000:
         raise Usage("--max-mismatch-permille and --min-alt-permille are shares of 1000")
+    if opt.phase_opts and not opt.phase:
+        raise Usage("%s needs --phase: it is an option of that step" % sorted(opt.phase_opts)[0])
+    if opt.phase and not opt.pileup:
+        raise Usage("--phase needs --pileup: it is an option of that step")
+    if opt.phase_opts.get("--min-hap-permille", 0) > 1000:
+        raise Usage("--min-hap-permille is a share of 1000")
     if opt.cluster_dists is not None:
         if not opt.cluster:
             raise Usage("--cluster-dists needs --cluster: it cuts the tree of the rows that step clusters")
@@ -836,6 +855,8 @@ def pileup(k):
     gene).  One checkpoint per gene, after every other checkpoint, so `--continue` works under any combination."""
     stem = "_merged_rmdup" if opt.derep else "_merged"
     extra = [x for flag in sorted(opt.pileup_opts) for x in (flag, str(opt.pileup_opts[flag]))]
+    if opt.phase:
+        extra += ["--phase"] + [x for flag in sorted(opt.phase_opts) for x in (flag, str(opt.phase_opts[flag]))]
     for gene in opt.gene_info:
         d = opt.out_dir + "contigs/" + gene
         if should_run():
