@@ -238,3 +238,72 @@ def stagewise_finish(started, oracle, min_multiset: float = 0.95):
         res[gene] = (common_n, len(ref), a == b)
         assert (out / "contigs" / gene / "nucl_merged.fasta").stat().st_size > 0 and (out / "contigs" / gene / "prot_merged.fasta").stat().st_size > 0
     return res
+
+
+# ---- reads behind the 2^31 and 2^32 base marks: a small payload of real reads behind a filler of reads too short to yield a window
+MARKS = (1 << 31, 1 << 32)
+
+
+def split_payload(n: int) -> tuple[int, int]:
+    """the payload reads [0, n1), [n1, n2), [n2, n) are the blocks B1, B2, B3 (even sizes: mates stay side by side)"""
+    n1 = (n // 3) & ~1
+    return n1, 2 * n1
+
+
+def reads_behind_marks(payload_reads, fill_len: int, mode: str, seed: int):
+    """-> (packed uint32[], start uint64[n + 1], ids int64[len(payload_reads)]): the payload reads (arrays of base codes as sequenced)
+    stored as readlib.pack_for_build stores them (reversed, 2 bits per base, no padding between reads) behind poly-A filler reads of
+    fill_len bases (at most one shorter filler read in front of a block), ids[i] = the number of payload read i in the layout.
+
+    The payload is three contiguous blocks (split_payload).  mode "straddle": base 2^31 lies inside the middle read of B1, half way
+    along it, base 2^32 inside the middle read of B2, and B3 follows B2 directly.  mode "exact": the middle read of B1 ends at base
+    2^31 - 1 and the next one starts at 2^31; the last read of B2 ends at 2^32 - 1 and B3 starts at 2^32.  Decoys: the filler words at
+    x mod 2^32 and x mod 2^31 of every payload base offset x hold random non-zero bits (seed), so a read taken from a wrapped offset
+    yields foreign k-mers.  No array of one byte per base is ever made."""
+    from megagta_amd import readlib
+    if mode not in ("straddle", "exact"):
+        raise ValueError(f"mode {mode!r}")
+    reads = [np.asarray(r, dtype=np.uint8) for r in payload_reads]
+    n = len(reads)
+    n1, n2 = split_payload(n)
+    if n1 < 2 or n2 >= n:
+        raise ValueError("the payload needs at least six reads")
+    lens = np.array([r.size for r in reads], dtype=np.int64)
+    local = np.zeros(n + 1, dtype=np.int64)
+    np.cumsum(lens, out=local[1:])
+    j1, j2 = n1 // 2, (n1 + n2) // 2                                     # the reads at the marks
+    if mode == "straddle":
+        if min(lens[j1], lens[j2]) < 33:
+            raise ValueError("the reads at the marks need 33 bases")
+        at1 = MARKS[0] - int(lens[j1]) // 2 - int(local[j1] - local[0])   # base offset of B1
+        at2 = MARKS[1] - int(lens[j2]) // 2 - int(local[j2] - local[n1])  # base offset of B2 (B3 behind it)
+    else:
+        at1 = MARKS[0] - int(local[j1 + 1] - local[0])
+        at2 = MARKS[1] - int(local[n2] - local[n1])
+    end1 = at1 + int(local[n1])
+    if at1 < 0 or at2 < end1:
+        raise ValueError("the payload is too long for the marks")
+
+    def filler(first: int, last: int) -> np.ndarray:
+        """starts of the filler reads over the bases [first, last): reads of fill_len, then one shorter read"""
+        n_full, rest = divmod(last - first, fill_len)
+        return np.uint64(first) + np.uint64(fill_len) * np.arange(n_full + (rest > 0), dtype=np.uint64)
+
+    f0, f1 = filler(0, at1), filler(end1, at2)
+    s1 = (at1 + local[:n1]).astype(np.uint64)
+    s2 = (at2 + (local[n1:] - local[n1])).astype(np.uint64)                # B2, B3 and the end of the last read
+    start = np.concatenate([f0, s1, f1, s2])
+    ids = np.concatenate([f0.size + np.arange(n1), f0.size + n1 + f1.size + np.arange(n - n1)]).astype(np.int64)
+    total = int(start[-1])
+    packed = np.zeros((total + 15) // 16, dtype=np.uint32)
+    spans = []
+    for at, lo, hi in ((at1, 0, n1), (at2, n1, n)):
+        codes = np.concatenate([np.zeros(at % 16, dtype=np.uint8)] + [r[::-1] for r in reads[lo:hi]])
+        words = readlib.pack_codes(codes)
+        packed[at >> 4:(at >> 4) + words.size] |= words
+        spans.append((at >> 4, (at >> 4) + words.size))
+    rng = np.random.default_rng(seed)
+    own = np.concatenate([np.arange(a, b) for a, b in spans])
+    decoy = np.setdiff1d(np.concatenate([own % (m >> 4) for m in MARKS]), own)
+    packed[decoy] = rng.integers(1, 1 << 32, decoy.size, dtype=np.uint64).astype(np.uint32)
+    return packed, start, ids
