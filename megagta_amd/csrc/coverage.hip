@@ -18,8 +18,15 @@
 // = 128 groups = 128 independent lines in flight per CU, half of the 256 DESIGN 5 names for the full random-line rate: asking the
 // compiler for 8 waves per SIMD (64 VGPRs) spills 72 VGPRs to scratch memory (its resource report), so it is not asked.  Contigs are
 // handed out longest first from one atomic head, a few at a time.
-// What pileup.hip shares with this file -- grp_load_line, cov_step, share_walk_kernel, the symbol kernels, SampleTable with its add,
-// find, count and numbering kernels, window_scratch -- lives in walk.hpp.
+//
+// What the walks share is in walk.hpp: the step-or-search of a window (walk_next), the contig walker walk_contig, the queue dequeue
+// (grp_next_chunk), the decode of a packed base (packed_symbol), the mark bits and the counts of a walk.  cov_walk_kernel
+// (multiplicity, abundance) and match_mark_kernel (marking) are a prologue, a call of walk_contig with what they do with a window's
+// edge, and an epilogue.  match_walk_kernel and sample_scan_kernel keep the read walk written out, as share_walk_kernel in walk.hpp
+// keeps the contig walk: on a walker they were measurably slower (profiles/walk/README.md).  SampleTable and the symbol kernels,
+// which pileup.hip uses too, are in walk.hpp as well.  The host side of the entry points stands on contig_jobs.hpp (the offsets
+// check, the batch cutter, the job list of one strand or both, the window offsets) and on walk.hpp's marks_reset,
+// sample_table_alloc, stage_symbols and queue_launch.
 #include <algorithm>
 #include <numeric>
 #include <vector>
@@ -34,6 +41,7 @@ namespace {
 
 constexpr int kCovLowBins = 256;          // abundance bins counted in LDS per workgroup (where nearly all edges are); the rest go straight to device memory
 
+// walk_contig with the multiplicity of every window's edge (0 = none) as the per-window value, and the abundance of the call's edges
 // counters: [0] queue head, [1] windows found by a step, [2] index searches
 __global__ __launch_bounds__(kCovThreads) void cov_walk_kernel(GraphDev g, MultDev m, const uint8_t *sym, const CovJob *jobs, uint32_t n_jobs, uint32_t chunk,
                                                                uint16_t *pw, uint32_t *marks, unsigned long long *abund, unsigned long long *counters) {
@@ -41,66 +49,39 @@ __global__ __launch_bounds__(kCovThreads) void cov_walk_kernel(GraphDev g, MultD
     for (int i = threadIdx.x; i < kCovLowBins; i += kCovThreads) s_hist[i] = 0;
     __syncthreads();
     const int sub = threadIdx.x & 7;
-    const int k = g.k;
-    uint32_t walked = 0, searched = 0;
+    WalkCounts n;
     for (;;) {
-        unsigned long long first = 0;
-        if (sub == 0) first = atomicAdd(&counters[0], (unsigned long long)chunk);
-        first = __shfl(first, 0, 8);
+        const unsigned long long first = grp_next_chunk(&counters[0], chunk, sub);
         if (first >= n_jobs) break;
         const uint32_t j_end = (uint32_t)min((unsigned long long)n_jobs, first + chunk);
         for (uint32_t j = (uint32_t)first; j < j_end; ++j) {
             const CovJob job = jobs[j];
-            const uint8_t *s = sym + job.off;
-            const uint32_t n_win = job.len > (uint32_t)k ? job.len - (uint32_t)k : 0;
+            const uint32_t n_win = job.len > (uint32_t)g.k ? job.len - (uint32_t)g.k : 0;
             uint16_t *out = pw + job.win_base;
-            int run = 0;                                                  // A C G T letters in a row, up to the window's last letter
-            for (int i = 0; i < k && (uint32_t)i < job.len; ++i) run = s[i] ? run + 1 : 0;
-            int64_t e = -1;                                               // the edge of the window before, -1 = the walk has to start again
-            LineR L{};
             uint32_t mine = 0;
-            for (uint32_t p = 0; p < n_win; ++p) {
-                const int c = s[p + k];
-                run = c ? run + 1 : 0;
+            walk_contig(g, sym + job.off, job.len, sub, n, [&](uint32_t p, int64_t e) {
                 uint32_t cov = 0;
-                if (run > k) {
-                    if (e >= 0) {
-                        e = cov_step(g, L, e, c, sub);
-                        if (e >= 0) ++walked;
-                    } else {
-                        e = g_index_edge(g, s + p);
-                        ++searched;
-                        if (e >= 0) L = grp_load_line(g, (uint64_t)e >> 6, sub);
+                if (e >= 0) {
+                    cov = g_edge_mult(m, e);
+                    if (marks && sub == 0 && mark_edge(marks, e)) {       // abundance: the lane that turns the edge's bit on counts the edge
+                        if (cov < (uint32_t)kCovLowBins) atomicAdd(&s_hist[cov], 1u);
+                        else atomicAdd(&abund[cov], 1ull);
                     }
-                    if (e >= 0) {
-                        cov = g_edge_mult(m, e);
-                        if (marks && sub == 0) {                          // abundance: the lane that turns the edge's bit on counts the edge
-                            const uint32_t bit = 1u << (e & 31);
-                            if (!(atomicOr(&marks[e >> 5], bit) & bit)) {
-                                if (cov < (uint32_t)kCovLowBins) atomicAdd(&s_hist[cov], 1u);
-                                else atomicAdd(&abund[cov], 1ull);
-                            }
-                        }
-                    }
-                } else e = -1;
+                }
                 // eight windows leave as one 16-byte store of the group
                 if ((int)(p & 7) == sub) mine = cov;
                 if ((p & 7) == 7 || p + 1 == n_win) {
                     const uint32_t q = (p & ~7u) + (uint32_t)sub;
                     if (q <= p) out[q] = (uint16_t)mine;
                 }
-            }
+            });
         }
     }
     __syncthreads();
     if (marks)
         for (int i = threadIdx.x; i < kCovLowBins; i += kCovThreads)
             if (s_hist[i]) atomicAdd(&abund[i], (unsigned long long)s_hist[i]);
-    const uint32_t w = wave_sum(sub == 0 ? walked : 0u), sc = wave_sum(sub == 0 ? searched : 0u);
-    if (lane_id() == 0) {
-        if (w) atomicAdd(&counters[1], (unsigned long long)w);
-        if (sc) atomicAdd(&counters[2], (unsigned long long)sc);
-    }
+    walk_counts_flush(n, sub, &counters[1], &counters[2]);
 }
 
 // the bin of `h` (256 bins, 4 per lane) that holds the r-th element (0-based) of what was counted; rem = its rank inside the bin
@@ -176,61 +157,37 @@ __global__ __launch_bounds__(256) void edge_mult_kernel(MultDev m, const int64_t
 // of one of its windows is marked.  Both passes are the walk above -- one index search, then one dependent line per window -- without
 // multiplicities and without the per-window scratch.
 
-struct MarkJob {                          // one strand of one contig
-    uint64_t off;                         // its first symbol
-    uint32_t len, pad_;
-};
-
+// walk_contig over both strands of every contig (the jobs of cut_batch), marking
 // counters: [0] queue head, [1] edges whose bit this launch turned on
-__global__ __launch_bounds__(kCovThreads) void match_mark_kernel(GraphDev g, const uint8_t *sym, const MarkJob *jobs, uint32_t n_jobs, uint32_t chunk, uint32_t *marks,
+__global__ __launch_bounds__(kCovThreads) void match_mark_kernel(GraphDev g, const uint8_t *sym, const CovJob *jobs, uint32_t n_jobs, uint32_t chunk, uint32_t *marks,
                                                                  unsigned long long *counters) {
     const int sub = threadIdx.x & 7;
-    const int k = g.k;
+    WalkCounts n;                                                         // (not reported)
     uint32_t marked = 0;
     for (;;) {
-        unsigned long long first = 0;
-        if (sub == 0) first = atomicAdd(&counters[0], (unsigned long long)chunk);
-        first = __shfl(first, 0, 8);
+        const unsigned long long first = grp_next_chunk(&counters[0], chunk, sub);
         if (first >= n_jobs) break;
         const uint32_t j_end = (uint32_t)min((unsigned long long)n_jobs, first + chunk);
         for (uint32_t j = (uint32_t)first; j < j_end; ++j) {
-            const MarkJob job = jobs[j];
-            const uint8_t *s = sym + job.off;
-            const uint32_t n_win = job.len > (uint32_t)k ? job.len - (uint32_t)k : 0;
-            int run = 0;                                                  // A C G T letters in a row, up to the window's last letter
-            for (int i = 0; i < k && (uint32_t)i < job.len; ++i) run = s[i] ? run + 1 : 0;
-            int64_t e = -1;                                               // the edge of the window before, -1 = the walk has to start again
-            LineR L{};
-            for (uint32_t p = 0; p < n_win; ++p) {
-                const int c = s[p + k];
-                run = c ? run + 1 : 0;
-                if (run <= k) { e = -1; continue; }
-                if (e >= 0) e = cov_step(g, L, e, c, sub);
-                else {
-                    e = g_index_edge(g, s + p);
-                    if (e >= 0) L = grp_load_line(g, (uint64_t)e >> 6, sub);
-                }
-                if (e >= 0 && sub == 0) {                                 // the lane that turns the edge's bit on counts the edge
-                    const uint32_t bit = 1u << (e & 31);
-                    if (!(atomicOr(&marks[e >> 5], bit) & bit)) ++marked;
-                }
-            }
+            const CovJob job = jobs[j];
+            walk_contig(g, sym + job.off, job.len, sub, n, [&](uint32_t, int64_t e) {
+                if (e >= 0 && sub == 0 && mark_edge(marks, e)) ++marked;  // the lane that turns the edge's bit on counts the edge
+            });
         }
     }
     const uint32_t m = wave_sum(marked);
     if (lane_id() == 0 && m) atomicAdd(&counters[1], (unsigned long long)m);
 }
 
-// A group of 8 lanes owns a read.  Its bases come straight from the packed words (2 bits per base, base j of a word at bits 30 - 2j;
-// one 32-bit load per 16 bases, the same for all lanes of the group) in STORED order, words ascending.  Reads stored as sequenced are
-// walked as they are; reads stored reversed are walked with complemented bases, i.e. along their reverse complement: the marks hold
-// both strands of every contig window, so that walk hits exactly when the read does, window for window.  count_all = 0: the walk of
-// a read ends at its first hit.
+// The read walk, written out (walk.hpp says why), over the reads [0, n_reads): a group of 8 lanes owns a read and walks it in
+// STORED order, words ascending -- as it is when stored as sequenced, with complemented bases, i.e. along its reverse complement,
+// when stored reversed.  A read matches when the edge of one of its windows is marked: the marks hold both strands of every contig
+// window, so that walk hits exactly when the read does, window for window.  count_all = 0: the walk of a read ends at its first hit.
 // counters: [0] queue head, [1] windows found by a step, [2] index searches, [3] matched reads, [4] read windows
 __global__ __launch_bounds__(kCovThreads) void match_walk_kernel(GraphDev g, const uint32_t *packed, const uint64_t *start, uint64_t n_reads, int reversed, uint32_t chunk,
                                                                  const uint32_t *marks, uint32_t *bits, uint32_t *hit_windows, int count_all,
                                                                  unsigned long long *counters) {
-    __shared__ uint8_t s_seq[kCovThreads / 8][kMatchMaxWindow];
+    __shared__ uint8_t s_seq[kCovGroups][kMatchMaxWindow];
     const int sub = threadIdx.x & 7;
     const int k = g.k;
     uint8_t *seq = s_seq[threadIdx.x >> 3];
@@ -238,9 +195,7 @@ __global__ __launch_bounds__(kCovThreads) void match_walk_kernel(GraphDev g, con
     uint32_t walked = 0, searched = 0, matched = 0;
     unsigned long long windows = 0;
     for (;;) {
-        unsigned long long first = 0;
-        if (sub == 0) first = atomicAdd(&counters[0], (unsigned long long)chunk);
-        first = __shfl(first, 0, 8);
+        const unsigned long long first = grp_next_chunk(&counters[0], chunk, sub);
         if (first >= n_reads) break;
         const uint64_t r_end = min((unsigned long long)n_reads, first + chunk);
         for (uint64_t r = first; r < r_end; ++r) {
@@ -253,7 +208,7 @@ __global__ __launch_bounds__(kCovThreads) void match_walk_kernel(GraphDev g, con
             for (uint64_t p = 0; p < n_win; ++p) {
                 const uint64_t q = s0 + p + (uint64_t)k;                  // the window's last base
                 if (p == 0 || (q & 15) == 0) w = packed[q >> 4];
-                const int c = (int)(((w >> (30 - 2 * (int)(q & 15))) & 3u) ^ flip) + 1;
+                const int c = (int)packed_symbol(w, q, flip);
                 if (e >= 0) {
                     e = cov_step(g, L, e, c, sub);
                     if (e >= 0) ++walked;
@@ -261,13 +216,13 @@ __global__ __launch_bounds__(kCovThreads) void match_walk_kernel(GraphDev g, con
                     // every lane writes all k + 1 symbols itself and reads back only what it wrote (the same values in every lane of the group)
                     for (int i = 0; i <= k; ++i) {
                         const uint64_t qi = s0 + p + (uint64_t)i;
-                        seq[i] = (uint8_t)((((packed[qi >> 4] >> (30 - 2 * (int)(qi & 15))) & 3u) ^ flip) + 1);
+                        seq[i] = (uint8_t)packed_symbol(packed[qi >> 4], qi, flip);
                     }
                     e = g_index_edge(g, seq);
                     ++searched;
                     if (e >= 0) L = grp_load_line(g, (uint64_t)e >> 6, sub);
                 }
-                if (e >= 0 && ((marks[e >> 5] >> (e & 31)) & 1u)) {
+                if (e >= 0 && edge_marked(marks, e)) {
                     ++hits;
                     if (!count_all) break;
                 }
@@ -433,7 +388,7 @@ constexpr int kSampleMaxLibs = 256;
 __global__ __launch_bounds__(kCovThreads) void sample_scan_kernel(GraphDev g, const uint32_t *packed, const uint64_t *start, uint64_t n_reads, int reversed, uint32_t chunk,
                                                                   const uint32_t *marks, SampleTable t, unsigned long long *counts, const uint64_t *lib_end, int n_libs,
                                                                   unsigned long long *lib_hits, unsigned long long *counters) {
-    __shared__ uint8_t s_seq[kCovThreads / 8][kMatchMaxWindow];
+    __shared__ uint8_t s_seq[kCovGroups][kMatchMaxWindow];
     __shared__ uint64_t s_end[kSampleMaxLibs];
     __shared__ unsigned long long s_hits[kSampleMaxLibs];
     for (int i = threadIdx.x; i < n_libs; i += kCovThreads) { s_end[i] = lib_end[i]; s_hits[i] = 0; }
@@ -445,9 +400,7 @@ __global__ __launch_bounds__(kCovThreads) void sample_scan_kernel(GraphDev g, co
     uint32_t walked = 0, searched = 0;
     unsigned long long windows = 0, all_hits = 0;
     for (;;) {
-        unsigned long long first = 0;
-        if (sub == 0) first = atomicAdd(&counters[0], (unsigned long long)chunk);
-        first = __shfl(first, 0, 8);
+        const unsigned long long first = grp_next_chunk(&counters[0], chunk, sub);
         if (first >= n_reads) break;
         const uint64_t r_end = min((unsigned long long)n_reads, first + chunk);
         int s = 0;
@@ -466,7 +419,7 @@ __global__ __launch_bounds__(kCovThreads) void sample_scan_kernel(GraphDev g, co
             for (uint64_t p = 0; p < n_win; ++p) {
                 const uint64_t q = s0 + p + (uint64_t)k;                  // the window's last base
                 if (p == 0 || (q & 15) == 0) w = packed[q >> 4];
-                const int c = (int)(((w >> (30 - 2 * (int)(q & 15))) & 3u) ^ flip) + 1;
+                const int c = (int)packed_symbol(w, q, flip);
                 if (e >= 0) {
                     e = cov_step(g, L, e, c, sub);
                     if (e >= 0) ++walked;
@@ -474,13 +427,13 @@ __global__ __launch_bounds__(kCovThreads) void sample_scan_kernel(GraphDev g, co
                     // every lane writes all k + 1 symbols itself and reads back only what it wrote (the same values in every lane of the group)
                     for (int i = 0; i <= k; ++i) {
                         const uint64_t qi = s0 + p + (uint64_t)i;
-                        seq[i] = (uint8_t)((((packed[qi >> 4] >> (30 - 2 * (int)(qi & 15))) & 3u) ^ flip) + 1);
+                        seq[i] = (uint8_t)packed_symbol(packed[qi >> 4], qi, flip);
                     }
                     e = g_index_edge(g, seq);
                     ++searched;
                     if (e >= 0) L = grp_load_line(g, (uint64_t)e >> 6, sub);
                 }
-                if (e >= 0 && ((marks[e >> 5] >> (e & 31)) & 1u)) {       // the one-bit filter in front of the table
+                if (e >= 0 && edge_marked(marks, e)) {       // the one-bit filter in front of the table
                     ++hits;
                     if (sub == 0) {
                         const uint32_t slot = sample_table_find(t, e);
@@ -612,11 +565,8 @@ int mgta_contig_coverage(mgta_sdbg *g, const char *seqs, const uint64_t *offsets
                          int64_t *abundance, mgta_coverage_stats *stats) {
     if (!g || n < 0 || n > 0xFFFFFFF0ll || (n > 0 && (!offsets || !per_contig))) { set_error("mgta_contig_coverage: bad argument"); return MGTA_EINVAL; }
     if (!g->has_mult) { set_error("mgta_contig_coverage: the graph was loaded without multiplicities (mgta_ctx_keep_multiplicity)"); return MGTA_EINVAL; }
-    for (int64_t i = 0; i < n; ++i)
-        if (offsets[i + 1] < offsets[i] || offsets[i + 1] - offsets[i] > 0xFFFFFFF0ull || (offsets[i + 1] > offsets[i] && !seqs)) {
-            set_error("mgta_contig_coverage: contig %lld: offsets must ascend, a contig holds < 2^32 letters", (long long)i);
-            return MGTA_EINVAL;
-        }
+    const uint64_t k = (uint64_t)g->dev.k;
+    if (!check_contigs("mgta_contig_coverage", seqs, offsets, n, k, kMaxContigLetters, 0, nullptr, nullptr)) return MGTA_EINVAL;
     if (stats) memset(stats, 0, sizeof(*stats));
     if (abundance) memset(abundance, 0, 65536 * sizeof(int64_t));
     if (n == 0) return MGTA_OK;
@@ -624,62 +574,37 @@ int mgta_contig_coverage(mgta_sdbg *g, const char *seqs, const uint64_t *offsets
         mgta_ctx *ctx = g->ctx;
         MGTA_HIP_CHECK(hipSetDevice(ctx->device));
         hipStream_t st = ctx->stream;
-        const uint64_t k = (uint64_t)g->dev.k;
         Timer t_walk(st), t_stats(st);
         const uint64_t cap = ctx->coverage_batch_windows ? ctx->coverage_batch_windows : 1ull << 29;   // windows per batch: 1 GB of per-window scratch
-        // workgroups of the walk a CU holds at once: what its registers allow (never assumed)
-        int blocks_per_cu = 0;
-        MGTA_HIP_CHECK(hipOccupancyMaxActiveBlocksPerMultiprocessor(&blocks_per_cu, cov_walk_kernel, kCovThreads, 0));
-        blocks_per_cu = std::max(1, blocks_per_cu);
         DevBuf d_cnt, d_abund, d_sym, d_jobs, d_out;
         d_cnt.alloc(64);
         MGTA_HIP_CHECK(hipMemsetAsync(d_cnt.p, 0, 64, st));
         uint32_t *d_marks = nullptr;
-        if (abundance) {                                                  // one mark bit per edge, zeroed per call = per set of contigs
-            const size_t mark_b = ((size_t)g->dev.size / 32 + 2) * 4;
-            if (g->marks.bytes < mark_b) g->marks.alloc(mark_b, &ctx->live_bytes, &ctx->peak_bytes);
-            MGTA_HIP_CHECK(hipMemsetAsync(g->marks.p, 0, mark_b, st));
-            d_marks = g->marks.as<uint32_t>();
+        if (abundance) {
+            d_marks = marks_reset(g, st);
             d_abund.alloc(65536 * 8);
             MGTA_HIP_CHECK(hipMemsetAsync(d_abund.p, 0, 65536 * 8, st));
         }
+        const int walk_per_cu = queue_per_cu(cov_walk_kernel);
         std::vector<CovJob> jobs;
-        uint64_t win_done = 0;
+        uint64_t win_done = 0, n_win = 0;
         double ms_walk = 0, ms_stats = 0;
         int64_t n_batches = 0;
-        for (int64_t c0 = 0; c0 < n;) {
-            // the contigs [c0, c1) of this batch: as many as fit the scratch (one at least)
-            int64_t c1 = c0;
-            uint64_t n_win = 0;
-            jobs.clear();
-            while (c1 < n) {
-                const uint64_t len = offsets[c1 + 1] - offsets[c1], wn = len > k ? len - k : 0;
-                if (c1 > c0 && n_win + wn > cap) break;
-                jobs.push_back(CovJob{offsets[c1] - offsets[c0], n_win, (uint32_t)len, (uint32_t)(c1 - c0)});
-                n_win += wn;
-                ++c1;
-            }
+        for (int64_t c0 = 0, c1; c0 < n; c0 = c1) {
+            c1 = cut_batch(offsets, n, k, c0, cap, false, jobs, &n_win);
             const uint32_t nj = (uint32_t)jobs.size();
-            // longest first, so that no group starts a long contig when the others are about to finish (ties by number: the order is fixed)
-            std::sort(jobs.begin(), jobs.end(), [](const CovJob &a, const CovJob &b) { return a.len != b.len ? a.len > b.len : a.idx < b.idx; });
             const uint64_t n_bytes = offsets[c1] - offsets[c0];
             if (d_sym.bytes < n_bytes + 16) d_sym.alloc(n_bytes + 16, &ctx->live_bytes, &ctx->peak_bytes);
             if (d_jobs.bytes < (size_t)nj * sizeof(CovJob)) d_jobs.alloc((size_t)nj * sizeof(CovJob), &ctx->live_bytes, &ctx->peak_bytes);
             if (d_out.bytes < (size_t)nj * sizeof(mgta_contig_cov)) d_out.alloc((size_t)nj * sizeof(mgta_contig_cov), &ctx->live_bytes, &ctx->peak_bytes);
             uint16_t *d_pw = window_scratch(ctx, n_win * 2 + 64);
-            if (n_bytes) MGTA_HIP_CHECK(hipMemcpyAsync(d_sym.p, seqs + offsets[c0], n_bytes, hipMemcpyHostToDevice, st));
             MGTA_HIP_CHECK(hipMemcpyAsync(d_jobs.p, jobs.data(), (size_t)nj * sizeof(CovJob), hipMemcpyHostToDevice, st));
             MGTA_HIP_CHECK(hipMemsetAsync(d_cnt.p, 0, 8, st));            // the queue head
-            if (n_bytes)
-                hipLaunchKernelGGL(cov_symbols_kernel, dim3((unsigned)std::min<uint64_t>((n_bytes + 255) / 256, (uint64_t)ctx->num_cus * 16)), dim3(256), 0, st,
-                                   d_sym.as<uint8_t>(), n_bytes);
-            // a group takes `chunk` contigs per visit to the queue head (one word saturates near 88 dequeues per microsecond)
-            const uint64_t groups = (uint64_t)ctx->num_cus * (uint64_t)blocks_per_cu * (kCovThreads / 8);
-            const uint32_t chunk = nj >= groups * 64 ? 4u : 1u;
-            const unsigned blocks = (unsigned)std::min<uint64_t>((uint64_t)ctx->num_cus * (uint64_t)blocks_per_cu, ((uint64_t)nj + kCovThreads / 8 - 1) / (kCovThreads / 8));
+            stage_symbols(ctx, st, d_sym, seqs + offsets[c0], n_bytes, false);
+            const QueueLaunch q = queue_launch(ctx, walk_per_cu, nj, 64, 4);
             t_walk.start();
             if (g->dev.size > 0)
-                hipLaunchKernelGGL(cov_walk_kernel, dim3(blocks), dim3(kCovThreads), 0, st, g->dev, g->mult, d_sym.as<uint8_t>(), d_jobs.as<CovJob>(), nj, chunk, d_pw,
+                hipLaunchKernelGGL(cov_walk_kernel, dim3(q.blocks), dim3(kCovThreads), 0, st, g->dev, g->mult, d_sym.as<uint8_t>(), d_jobs.as<CovJob>(), nj, q.chunk, d_pw,
                                    d_marks, d_abund.as<unsigned long long>(), d_cnt.as<unsigned long long>());
             else
                 MGTA_HIP_CHECK(hipMemsetAsync(d_pw, 0, n_win * 2 + 64, st));
@@ -696,7 +621,6 @@ int mgta_contig_coverage(mgta_sdbg *g, const char *seqs, const uint64_t *offsets
             ms_stats += t_stats.ms();
             win_done += n_win;
             ++n_batches;
-            c0 = c1;
         }
         unsigned long long cnt[3] = {0, 0, 0};
         MGTA_HIP_CHECK(hipMemcpyAsync(cnt, d_cnt.p, 24, hipMemcpyDeviceToHost, st));
@@ -704,7 +628,7 @@ int mgta_contig_coverage(mgta_sdbg *g, const char *seqs, const uint64_t *offsets
         MGTA_HIP_CHECK(hipStreamSynchronize(st));
         if (stats) {
             stats->n_contigs = n; stats->n_windows = (int64_t)win_done; stats->n_walked = (int64_t)cnt[1]; stats->n_index_searches = (int64_t)cnt[2];
-            stats->groups_per_cu = (int64_t)blocks_per_cu * (kCovThreads / 8);
+            stats->groups_per_cu = (int64_t)walk_per_cu * kCovGroups;
             stats->n_batches = n_batches; stats->ms_walk = ms_walk; stats->ms_kernel = ms_walk + ms_stats;
         }
         return MGTA_OK;
@@ -721,11 +645,9 @@ int mgta_reads_match_contigs(mgta_sdbg *g, const mgta_reads *reads, int reads_re
     }
     if (n_short_reads > 0 && !match_bits) { set_error("mgta_reads_match_contigs: match_bits must not be NULL"); return MGTA_EINVAL; }
     if (n < 0 || n > 0x7FFFFFF0ll || (n > 0 && !offsets)) { set_error("mgta_reads_match_contigs: bad contig count or offsets"); return MGTA_EINVAL; }
-    for (int64_t i = 0; i < n; ++i)
-        if (offsets[i + 1] < offsets[i] || offsets[i + 1] - offsets[i] > 0xFFFFFFF0ull || (offsets[i + 1] > offsets[i] && !seqs)) {
-            set_error("mgta_reads_match_contigs: contig %lld: offsets must ascend, a contig holds < 2^32 letters", (long long)i);
-            return MGTA_EINVAL;
-        }
+    const uint64_t k = (uint64_t)g->dev.k;
+    uint64_t n_contig_win = 0;
+    if (!check_contigs("mgta_reads_match_contigs", seqs, offsets, n, k, kMaxContigLetters, 0, &n_contig_win, nullptr)) return MGTA_EINVAL;
     if (g->dev.k + 1 > kMatchMaxWindow) { set_error("mgta_reads_match_contigs: k = %d (k + 1 <= %d is supported)", g->dev.k, kMatchMaxWindow); return MGTA_EINVAL; }
     const uint64_t n_bit_words = (n_short_reads + 63) / 64;
     if (stats) memset(stats, 0, sizeof(*stats));
@@ -736,67 +658,34 @@ int mgta_reads_match_contigs(mgta_sdbg *g, const mgta_reads *reads, int reads_re
         mgta_ctx *ctx = g->ctx;
         MGTA_HIP_CHECK(hipSetDevice(ctx->device));
         hipStream_t st = ctx->stream;
-        const uint64_t k = (uint64_t)g->dev.k;
-        constexpr int kGroups = kCovThreads / 8;
-        // the two strands of every contig, longest first (ties by number: the order is fixed); the reverse complements lie mirrored behind the symbols
-        const uint64_t n_sym = offsets[n] - offsets[0];
-        std::vector<MarkJob> jobs;
-        jobs.reserve((size_t)n * 2);
-        uint64_t contig_windows = 0;
-        for (int64_t i = 0; i < n; ++i) {
-            const uint64_t a = offsets[i] - offsets[0], b = offsets[i + 1] - offsets[0];
-            contig_windows += b - a > k ? b - a - k : 0;
-            jobs.push_back(MarkJob{a, (uint32_t)(b - a), 0});
-            jobs.push_back(MarkJob{2 * n_sym - b, (uint32_t)(b - a), 0});
-        }
-        std::stable_sort(jobs.begin(), jobs.end(), [](const MarkJob &x, const MarkJob &y) { return x.len > y.len; });
+        // the two strands of every contig as one batch
+        std::vector<CovJob> jobs;
+        uint64_t n_win = 0;
+        cut_batch(offsets, n, k, 0, ~0ull, true, jobs, &n_win);
         const uint32_t nj = (uint32_t)jobs.size();
-        // workgroups a CU holds at once: what the kernels' registers allow (never assumed)
-        int mark_per_cu = 0, walk_per_cu = 0;
-        MGTA_HIP_CHECK(hipOccupancyMaxActiveBlocksPerMultiprocessor(&mark_per_cu, match_mark_kernel, kCovThreads, 0));
-        MGTA_HIP_CHECK(hipOccupancyMaxActiveBlocksPerMultiprocessor(&walk_per_cu, match_walk_kernel, kCovThreads, 0));
-        mark_per_cu = std::max(1, mark_per_cu);
-        walk_per_cu = std::max(1, walk_per_cu);
-        // one mark bit per edge, the graph's own, zeroed per call
-        const size_t mark_b = ((size_t)g->dev.size / 32 + 2) * 4;
-        if (g->marks.bytes < mark_b) g->marks.alloc(mark_b, &ctx->live_bytes, &ctx->peak_bytes);
-        MGTA_HIP_CHECK(hipMemsetAsync(g->marks.p, 0, mark_b, st));
+        const uint64_t n_sym = offsets[n] - offsets[0];
+        uint32_t *d_marks = marks_reset(g, st);
         DevBuf d_cnt, d_sym, d_jobs, d_bits, d_hits;
         d_cnt.alloc(128);
         d_sym.alloc(2 * n_sym + 16, &ctx->live_bytes, &ctx->peak_bytes);
-        d_jobs.alloc((size_t)nj * sizeof(MarkJob), &ctx->live_bytes, &ctx->peak_bytes);
+        d_jobs.alloc((size_t)nj * sizeof(CovJob), &ctx->live_bytes, &ctx->peak_bytes);
         d_bits.alloc(n_bit_words * 8, &ctx->live_bytes, &ctx->peak_bytes);
         if (hit_windows) d_hits.alloc(n_short_reads * 4, &ctx->live_bytes, &ctx->peak_bytes);
         MGTA_HIP_CHECK(hipMemsetAsync(d_cnt.p, 0, 128, st));
         MGTA_HIP_CHECK(hipMemsetAsync(d_bits.p, 0, n_bit_words * 8, st));
-        if (n_sym) MGTA_HIP_CHECK(hipMemcpyAsync(d_sym.p, seqs + offsets[0], n_sym, hipMemcpyHostToDevice, st));
-        MGTA_HIP_CHECK(hipMemcpyAsync(d_jobs.p, jobs.data(), (size_t)nj * sizeof(MarkJob), hipMemcpyHostToDevice, st));
+        MGTA_HIP_CHECK(hipMemcpyAsync(d_jobs.p, jobs.data(), (size_t)nj * sizeof(CovJob), hipMemcpyHostToDevice, st));
         unsigned long long *cnt_mark = d_cnt.as<unsigned long long>(), *cnt_walk = cnt_mark + 8;
+        const QueueLaunch q_mark = queue_launch(ctx, queue_per_cu(match_mark_kernel), nj, 64, 4),
+                          q_walk = queue_launch(ctx, queue_per_cu(match_walk_kernel), n_short_reads, 256, 16);
         Timer t_mark(st), t_walk(st);
-        t_mark.start();
-        if (n_sym) {
-            const unsigned sym_blocks = (unsigned)std::min<uint64_t>((n_sym + 255) / 256, (uint64_t)ctx->num_cus * 16);
-            hipLaunchKernelGGL(cov_symbols_kernel, dim3(sym_blocks), dim3(256), 0, st, d_sym.as<uint8_t>(), n_sym);
-            hipLaunchKernelGGL(match_rc_symbols_kernel, dim3(sym_blocks), dim3(256), 0, st, d_sym.as<uint8_t>(), n_sym);
-        }
-        {
-            const uint64_t groups = (uint64_t)ctx->num_cus * (uint64_t)mark_per_cu * kGroups;
-            const uint32_t chunk = nj >= groups * 64 ? 4u : 1u;
-            const unsigned blocks = (unsigned)std::min<uint64_t>((uint64_t)ctx->num_cus * (uint64_t)mark_per_cu, ((uint64_t)nj + kGroups - 1) / kGroups);
-            hipLaunchKernelGGL(match_mark_kernel, dim3(blocks), dim3(kCovThreads), 0, st, g->dev, d_sym.as<uint8_t>(), d_jobs.as<MarkJob>(), nj, chunk,
-                               g->marks.as<uint32_t>(), cnt_mark);
-        }
+        stage_symbols(ctx, st, d_sym, seqs + offsets[0], n_sym, true, &t_mark);   // (t_mark starts behind the upload)
+        hipLaunchKernelGGL(match_mark_kernel, dim3(q_mark.blocks), dim3(kCovThreads), 0, st, g->dev, d_sym.as<uint8_t>(), d_jobs.as<CovJob>(), nj, q_mark.chunk, d_marks,
+                           cnt_mark);
         MGTA_HIP_CHECK(hipGetLastError());
         t_mark.end();
         t_walk.start();
-        {
-            // a group takes `chunk` reads per visit to the queue head (one word saturates near 88 dequeues per microsecond)
-            const uint64_t groups = (uint64_t)ctx->num_cus * (uint64_t)walk_per_cu * kGroups;
-            const uint32_t chunk = n_short_reads >= groups * 256 ? 16u : 1u;
-            const unsigned blocks = (unsigned)std::min<uint64_t>((uint64_t)ctx->num_cus * (uint64_t)walk_per_cu, (n_short_reads + (uint64_t)kGroups * chunk - 1) / ((uint64_t)kGroups * chunk));
-            hipLaunchKernelGGL(match_walk_kernel, dim3(blocks), dim3(kCovThreads), 0, st, g->dev, reads->d_packed, reads->d_start, n_short_reads, reads_reversed ? 1 : 0, chunk,
-                               g->marks.as<uint32_t>(), d_bits.as<uint32_t>(), d_hits.as<uint32_t>(), hit_windows ? 1 : 0, cnt_walk);
-        }
+        hipLaunchKernelGGL(match_walk_kernel, dim3(q_walk.blocks), dim3(kCovThreads), 0, st, g->dev, reads->d_packed, reads->d_start, n_short_reads, reads_reversed ? 1 : 0,
+                           q_walk.chunk, d_marks, d_bits.as<uint32_t>(), d_hits.as<uint32_t>(), hit_windows ? 1 : 0, cnt_walk);
         MGTA_HIP_CHECK(hipGetLastError());
         t_walk.end();
         unsigned long long cnt[16] = {0};
@@ -805,10 +694,10 @@ int mgta_reads_match_contigs(mgta_sdbg *g, const mgta_reads *reads, int reads_re
         if (hit_windows) MGTA_HIP_CHECK(hipMemcpyAsync(hit_windows, d_hits.p, n_short_reads * 4, hipMemcpyDeviceToHost, st));
         MGTA_HIP_CHECK(hipStreamSynchronize(st));
         if (stats) {
-            stats->n_contigs = n; stats->n_contig_windows = (int64_t)contig_windows; stats->n_marked_edges = (int64_t)cnt[1];
+            stats->n_contigs = n; stats->n_contig_windows = (int64_t)n_contig_win; stats->n_marked_edges = (int64_t)cnt[1];
             stats->n_reads = (int64_t)n_short_reads; stats->n_read_windows = (int64_t)cnt[12];
             stats->n_walked = (int64_t)cnt[9]; stats->n_index_searches = (int64_t)cnt[10]; stats->n_matched_reads = (int64_t)cnt[11];
-            stats->groups_per_cu = (int64_t)walk_per_cu * kGroups;
+            stats->groups_per_cu = q_walk.groups_per_cu();
             stats->ms_mark = t_mark.ms(); stats->ms_walk = t_walk.ms();
         }
         return MGTA_OK;
@@ -828,20 +717,8 @@ int mgta_contig_share_coverage(mgta_sdbg *g, const char *seqs, const uint64_t *o
     if (n > 0x7FFFFFFFll) { set_error("mgta_contig_share_coverage: %lld contigs (n < 2^31 is supported)", (long long)n); return MGTA_EINVAL; }
     if (!g->has_mult) { set_error("mgta_contig_share_coverage: the graph was loaded without multiplicities (mgta_ctx_keep_multiplicity)"); return MGTA_EINVAL; }
     const uint64_t k = (uint64_t)g->dev.k;
-    uint64_t total_win = 0, longest_win = 0;
-    for (int64_t i = 0; i < n; ++i) {
-        if (offsets[i + 1] < offsets[i] || offsets[i + 1] - offsets[i] > 0xFFFFFFF0ull || (offsets[i + 1] > offsets[i] && !seqs)) {
-            set_error("mgta_contig_share_coverage: contig %lld: offsets must ascend, a contig holds < 2^32 letters", (long long)i);
-            return MGTA_EINVAL;
-        }
-        const uint64_t len = offsets[i + 1] - offsets[i], wn = len > k ? len - k : 0;
-        total_win += wn;
-        longest_win = std::max(longest_win, wn);
-        if (total_win > 0xFFFFFFFFull) {
-            set_error("mgta_contig_share_coverage: more than 2^32 - 1 windows in the call (a share is a 32-bit count); contig %lld is the first beyond", (long long)i);
-            return MGTA_EINVAL;
-        }
-    }
+    uint64_t total_win = 0;
+    if (!check_contigs("mgta_contig_share_coverage", seqs, offsets, n, k, kMaxContigLetters, kMaxCallWindows, &total_win, nullptr)) return MGTA_EINVAL;
     if (stats) memset(stats, 0, sizeof(*stats));
     if (n == 0) return MGTA_OK;
     return guarded("mgta_contig_share_coverage", [&]() {
@@ -850,15 +727,8 @@ int mgta_contig_share_coverage(mgta_sdbg *g, const char *seqs, const uint64_t *o
         hipStream_t st = ctx->stream;
         Timer t_walk(st), t_count(st), t_share(st);
         const uint64_t cap = ctx->coverage_batch_windows ? ctx->coverage_batch_windows : 1ull << 29;   // windows per batch: 4 GB of edge ids
-        int blocks_per_cu = 0;
-        MGTA_HIP_CHECK(hipOccupancyMaxActiveBlocksPerMultiprocessor(&blocks_per_cu, share_walk_kernel, kCovThreads, 0));
-        blocks_per_cu = std::max(1, blocks_per_cu);
-        // the table: at most half full, never larger than 2^32 slots (a slot number is 32 bits; slot 0 is "no edge"), and sized by the
-        // windows of the call -- or by the graph where that has fewer edges than the call has windows
-        const uint64_t most_keys = std::min<uint64_t>(total_win, (uint64_t)std::max<int64_t>(g->dev.size, 0));
-        uint64_t n_slots = 1024;
-        while (n_slots < 2 * most_keys + 2 && n_slots < (1ull << 32)) n_slots <<= 1;
-        const uint64_t hmask = ctx->share_hash_bits >= 64 ? ~0ull : (1ull << ctx->share_hash_bits) - 1;
+        // the table is sized by the windows of the call -- or by the graph where that has fewer edges than the call has windows
+        const uint64_t n_slots = table_slots(std::min<uint64_t>(total_win, (uint64_t)std::max<int64_t>(g->dev.size, 0))), hmask = table_hmask(ctx);
         DevBuf d_cnt, d_sym, d_jobs, d_keys, d_vals, d_slots, d_woff, d_lens, d_out, d_pws, d_pwm;
         d_cnt.alloc(64);
         MGTA_HIP_CHECK(hipMemsetAsync(d_cnt.p, 0, 64, st));
@@ -867,41 +737,26 @@ int mgta_contig_share_coverage(mgta_sdbg *g, const char *seqs, const uint64_t *o
         d_slots.alloc(total_win * 4 + 16, &ctx->live_bytes, &ctx->peak_bytes);
         MGTA_HIP_CHECK(hipMemsetAsync(d_keys.p, 0xFF, n_slots * 8, st));
         MGTA_HIP_CHECK(hipMemsetAsync(d_vals.p, 0, n_slots * 8, st));
+        const int walk_per_cu = queue_per_cu(share_walk_kernel);
         std::vector<CovJob> jobs;
-        uint64_t win_done = 0;
+        uint64_t win_done = 0, n_win = 0;
         double ms_walk = 0, ms_count = 0;
         int64_t n_batches = 0;
-        for (int64_t c0 = 0; c0 < n;) {
-            // the contigs [c0, c1) of this batch: as many as fit the scratch (one at least), exactly as mgta_contig_coverage cuts them
-            int64_t c1 = c0;
-            uint64_t n_win = 0;
-            jobs.clear();
-            while (c1 < n) {
-                const uint64_t len = offsets[c1 + 1] - offsets[c1], wn = len > k ? len - k : 0;
-                if (c1 > c0 && n_win + wn > cap) break;
-                jobs.push_back(CovJob{offsets[c1] - offsets[c0], n_win, (uint32_t)len, (uint32_t)(c1 - c0)});
-                n_win += wn;
-                ++c1;
-            }
+        for (int64_t c0 = 0, c1; c0 < n; c0 = c1) {
+            c1 = cut_batch(offsets, n, k, c0, cap, false, jobs, &n_win);
             const uint32_t nj = (uint32_t)jobs.size();
-            std::sort(jobs.begin(), jobs.end(), [](const CovJob &a, const CovJob &b) { return a.len != b.len ? a.len > b.len : a.idx < b.idx; });
-            const uint64_t batch_longest = jobs[0].len > k ? jobs[0].len - k : 0;
+            const uint64_t batch_longest = contig_windows(jobs[0].len, k);
             const uint64_t n_bytes = offsets[c1] - offsets[c0];
             if (d_sym.bytes < n_bytes + 16) d_sym.alloc(n_bytes + 16, &ctx->live_bytes, &ctx->peak_bytes);
             if (d_jobs.bytes < (size_t)nj * sizeof(CovJob)) d_jobs.alloc((size_t)nj * sizeof(CovJob), &ctx->live_bytes, &ctx->peak_bytes);
             int64_t *d_ids = reinterpret_cast<int64_t *>(window_scratch(ctx, n_win * 8 + 64));
-            if (n_bytes) MGTA_HIP_CHECK(hipMemcpyAsync(d_sym.p, seqs + offsets[c0], n_bytes, hipMemcpyHostToDevice, st));
             MGTA_HIP_CHECK(hipMemcpyAsync(d_jobs.p, jobs.data(), (size_t)nj * sizeof(CovJob), hipMemcpyHostToDevice, st));
             MGTA_HIP_CHECK(hipMemsetAsync(d_cnt.p, 0, 8, st));            // the queue head
-            if (n_bytes)
-                hipLaunchKernelGGL(cov_symbols_kernel, dim3((unsigned)std::min<uint64_t>((n_bytes + 255) / 256, (uint64_t)ctx->num_cus * 16)), dim3(256), 0, st,
-                                   d_sym.as<uint8_t>(), n_bytes);
-            const uint64_t groups = (uint64_t)ctx->num_cus * (uint64_t)blocks_per_cu * (kCovThreads / 8);
-            const uint32_t chunk = nj >= groups * 64 ? 4u : 1u;
-            const unsigned blocks = (unsigned)std::min<uint64_t>((uint64_t)ctx->num_cus * (uint64_t)blocks_per_cu, ((uint64_t)nj + kCovThreads / 8 - 1) / (kCovThreads / 8));
+            stage_symbols(ctx, st, d_sym, seqs + offsets[c0], n_bytes, false);
+            const QueueLaunch q = queue_launch(ctx, walk_per_cu, nj, 64, 4);
             t_walk.start();
             if (g->dev.size > 0)
-                hipLaunchKernelGGL(share_walk_kernel, dim3(blocks), dim3(kCovThreads), 0, st, g->dev, d_sym.as<uint8_t>(), d_jobs.as<CovJob>(), nj, chunk, d_ids,
+                hipLaunchKernelGGL(share_walk_kernel, dim3(q.blocks), dim3(kCovThreads), 0, st, g->dev, d_sym.as<uint8_t>(), d_jobs.as<CovJob>(), nj, q.chunk, d_ids,
                                    d_cnt.as<unsigned long long>());
             else
                 MGTA_HIP_CHECK(hipMemsetAsync(d_ids, 0xFF, n_win * 8 + 64, st));   // no edge anywhere
@@ -921,7 +776,6 @@ int mgta_contig_share_coverage(mgta_sdbg *g, const char *seqs, const uint64_t *o
             ms_count += t_count.ms();
             win_done += n_win;
             ++n_batches;
-            c0 = c1;
         }
         unsigned long long cnt[6] = {0, 0, 0, 0, 0, 0};
         MGTA_HIP_CHECK(hipMemcpyAsync(cnt, d_cnt.p, 48, hipMemcpyDeviceToHost, st));
@@ -929,13 +783,8 @@ int mgta_contig_share_coverage(mgta_sdbg *g, const char *seqs, const uint64_t *o
         if (cnt[5]) { set_error("mgta_contig_share_coverage: the count table of %llu slots ran full", (unsigned long long)n_slots); return MGTA_EHIP; }
         // every batch is counted: the shares are final.  The batch buffers make room for the outputs.
         d_sym.release(); d_jobs.release();
-        std::vector<uint64_t> woff((size_t)n + 1, 0);
-        std::vector<uint32_t> lens((size_t)n);
-        for (int64_t i = 0; i < n; ++i) {
-            const uint64_t len = offsets[i + 1] - offsets[i];
-            lens[(size_t)i] = (uint32_t)len;
-            woff[(size_t)i + 1] = woff[(size_t)i] + (len > k ? len - k : 0);
-        }
+        std::vector<uint32_t> lens;
+        const std::vector<uint64_t> woff = window_offsets(offsets, n, k, &lens);
         d_woff.alloc(((size_t)n + 1) * 8, &ctx->live_bytes, &ctx->peak_bytes);
         d_lens.alloc((size_t)n * 4, &ctx->live_bytes, &ctx->peak_bytes);
         d_out.alloc((size_t)n * sizeof(mgta_contig_share), &ctx->live_bytes, &ctx->peak_bytes);
@@ -983,18 +832,7 @@ int mgta_contig_sample_coverage(mgta_sdbg *g, const mgta_reads *reads, int reads
     if (g->dev.k + 1 > kMatchMaxWindow) { set_error("mgta_contig_sample_coverage: k = %d (k + 1 <= %d is supported)", g->dev.k, kMatchMaxWindow); return MGTA_EINVAL; }
     const uint64_t k = (uint64_t)g->dev.k;
     uint64_t total_win = 0;
-    for (int64_t i = 0; i < n; ++i) {
-        if (offsets[i + 1] < offsets[i] || offsets[i + 1] - offsets[i] > 0xFFFFFFF0ull || (offsets[i + 1] > offsets[i] && !seqs)) {
-            set_error("mgta_contig_sample_coverage: contig %lld: offsets must ascend, a contig holds < 2^32 letters", (long long)i);
-            return MGTA_EINVAL;
-        }
-        const uint64_t len = offsets[i + 1] - offsets[i];
-        total_win += len > k ? len - k : 0;
-        if (total_win > 0xFFFFFFFFull) {
-            set_error("mgta_contig_sample_coverage: more than 2^32 - 1 windows in the call (a share is a 32-bit count); contig %lld is the first beyond", (long long)i);
-            return MGTA_EINVAL;
-        }
-    }
+    if (!check_contigs("mgta_contig_sample_coverage", seqs, offsets, n, k, kMaxContigLetters, kMaxCallWindows, &total_win, nullptr)) return MGTA_EINVAL;
     // the table holds the edges of both strands: at most half full, a slot number is 32 bits
     const uint64_t most_keys = std::min<uint64_t>(2 * total_win, (uint64_t)std::max<int64_t>(g->dev.size, 0));
     if (2 * most_keys + 2 > (1ull << 32)) {
@@ -1009,74 +847,39 @@ int mgta_contig_sample_coverage(mgta_sdbg *g, const mgta_reads *reads, int reads
         mgta_ctx *ctx = g->ctx;
         MGTA_HIP_CHECK(hipSetDevice(ctx->device));
         hipStream_t st = ctx->stream;
-        constexpr int kGroups = kCovThreads / 8;
         Timer t_walk(st), t_count(st), t_scan(st), t_mass(st);
         const uint64_t cap = ctx->coverage_batch_windows ? ctx->coverage_batch_windows : 1ull << 28;   // windows per batch: 4 GB of edge ids, both strands
-        int walk_per_cu = 0, scan_per_cu = 0;
-        MGTA_HIP_CHECK(hipOccupancyMaxActiveBlocksPerMultiprocessor(&walk_per_cu, share_walk_kernel, kCovThreads, 0));
-        MGTA_HIP_CHECK(hipOccupancyMaxActiveBlocksPerMultiprocessor(&scan_per_cu, sample_scan_kernel, kCovThreads, 0));
-        walk_per_cu = std::max(1, walk_per_cu);
-        scan_per_cu = std::max(1, scan_per_cu);
-        SampleTable tab{nullptr, nullptr, nullptr, 1024, ctx->share_hash_bits >= 64 ? ~0ull : (1ull << ctx->share_hash_bits) - 1};
-        while (tab.n_slots < 2 * most_keys + 2) tab.n_slots <<= 1;
-        // one mark bit per edge, the graph's own, zeroed per call
-        const size_t mark_b = ((size_t)std::max<int64_t>(g->dev.size, 0) / 32 + 2) * 4;
-        if (g->marks.bytes < mark_b) g->marks.alloc(mark_b, &ctx->live_bytes, &ctx->peak_bytes);
-        MGTA_HIP_CHECK(hipMemsetAsync(g->marks.p, 0, mark_b, st));
-        DevBuf d_cnt, d_sym, d_jobs, d_keys, d_share, d_dense, d_own, d_rc, d_counts, d_ends, d_hits, d_woff, d_lens, d_out, d_mass, d_pwc, d_pws;
+        uint32_t *d_marks = marks_reset(g, st);
+        DevBuf d_cnt, d_sym, d_jobs, d_own, d_rc, d_counts, d_ends, d_hits, d_woff, d_lens, d_out, d_mass, d_pwc, d_pws;
         d_cnt.alloc(128);
         MGTA_HIP_CHECK(hipMemsetAsync(d_cnt.p, 0, 128, st));
         unsigned long long *cnt_mark = d_cnt.as<unsigned long long>(), *cnt_scan = cnt_mark + 8;
-        d_keys.alloc(tab.n_slots * 8, &ctx->live_bytes, &ctx->peak_bytes);
-        d_share.alloc(tab.n_slots * 4, &ctx->live_bytes, &ctx->peak_bytes);
-        d_dense.alloc(tab.n_slots * 4, &ctx->live_bytes, &ctx->peak_bytes);
+        SampleTableMem tm;
+        sample_table_alloc(ctx, st, most_keys, &ctx->live_bytes, &ctx->peak_bytes, tm);
+        const SampleTable &tab = tm.t;
         d_own.alloc(total_win * 4 + 16, &ctx->live_bytes, &ctx->peak_bytes);
         d_rc.alloc(total_win * 4 + 16, &ctx->live_bytes, &ctx->peak_bytes);
-        tab.keys = d_keys.as<unsigned long long>(); tab.share = d_share.as<uint32_t>(); tab.dense = d_dense.as<uint32_t>();
-        MGTA_HIP_CHECK(hipMemsetAsync(d_keys.p, 0xFF, tab.n_slots * 8, st));
-        MGTA_HIP_CHECK(hipMemsetAsync(d_share.p, 0, tab.n_slots * 4, st));
+        // ---- the keys: both strands of every contig, batch by batch
+        const int walk_per_cu = queue_per_cu(share_walk_kernel);
         std::vector<CovJob> jobs;
-        uint64_t win_done = 0;
+        uint64_t win_done = 0, n_win = 0;
         double ms_walk = 0, ms_count = 0;
         int64_t n_batches = 0;
-        for (int64_t c0 = 0; c0 < n;) {
-            // the contigs [c0, c1) of this batch, as mgta_contig_coverage cuts them; every contig is two jobs, idx = 2 * number + strand
-            int64_t c1 = c0;
-            uint64_t n_win = 0;
-            jobs.clear();
-            while (c1 < n) {
-                const uint64_t len = offsets[c1 + 1] - offsets[c1], wn = len > k ? len - k : 0;
-                if (c1 > c0 && n_win + wn > cap) break;
-                jobs.push_back(CovJob{offsets[c1] - offsets[c0], n_win, (uint32_t)len, (uint32_t)(c1 - c0) * 2u});
-                n_win += wn;
-                ++c1;
-            }
-            const uint64_t n_bytes = offsets[c1] - offsets[c0];
-            const size_t n_given = jobs.size();
-            for (size_t j = 0; j < n_given; ++j) {                        // the reverse complement of [a, a + len) lies at [2 n_bytes - a - len, 2 n_bytes - a)
-                const CovJob f = jobs[j];
-                jobs.push_back(CovJob{2 * n_bytes - f.off - f.len, n_win + f.win_base, f.len, f.idx + 1u});
-            }
+        for (int64_t c0 = 0, c1; c0 < n; c0 = c1) {
+            c1 = cut_batch(offsets, n, k, c0, cap, true, jobs, &n_win);
             const uint32_t nj = (uint32_t)jobs.size();
-            std::sort(jobs.begin(), jobs.end(), [](const CovJob &a, const CovJob &b) { return a.len != b.len ? a.len > b.len : a.idx < b.idx; });
-            const uint64_t batch_longest = jobs[0].len > k ? jobs[0].len - k : 0;
+            const uint64_t batch_longest = contig_windows(jobs[0].len, k);
+            const uint64_t n_bytes = offsets[c1] - offsets[c0];
             if (d_sym.bytes < 2 * n_bytes + 16) d_sym.alloc(2 * n_bytes + 16, &ctx->live_bytes, &ctx->peak_bytes);
             if (d_jobs.bytes < (size_t)nj * sizeof(CovJob)) d_jobs.alloc((size_t)nj * sizeof(CovJob), &ctx->live_bytes, &ctx->peak_bytes);
             int64_t *d_ids = reinterpret_cast<int64_t *>(window_scratch(ctx, 2 * n_win * 8 + 64));
-            if (n_bytes) MGTA_HIP_CHECK(hipMemcpyAsync(d_sym.p, seqs + offsets[c0], n_bytes, hipMemcpyHostToDevice, st));
             MGTA_HIP_CHECK(hipMemcpyAsync(d_jobs.p, jobs.data(), (size_t)nj * sizeof(CovJob), hipMemcpyHostToDevice, st));
             MGTA_HIP_CHECK(hipMemsetAsync(d_cnt.p, 0, 8, st));            // the queue head
-            if (n_bytes) {
-                const unsigned sym_blocks = (unsigned)std::min<uint64_t>((n_bytes + 255) / 256, (uint64_t)ctx->num_cus * 16);
-                hipLaunchKernelGGL(cov_symbols_kernel, dim3(sym_blocks), dim3(256), 0, st, d_sym.as<uint8_t>(), n_bytes);
-                hipLaunchKernelGGL(match_rc_symbols_kernel, dim3(sym_blocks), dim3(256), 0, st, d_sym.as<uint8_t>(), n_bytes);
-            }
-            const uint64_t groups = (uint64_t)ctx->num_cus * (uint64_t)walk_per_cu * kGroups;
-            const uint32_t chunk = nj >= groups * 64 ? 4u : 1u;
-            const unsigned blocks = (unsigned)std::min<uint64_t>((uint64_t)ctx->num_cus * (uint64_t)walk_per_cu, ((uint64_t)nj + kGroups - 1) / kGroups);
+            stage_symbols(ctx, st, d_sym, seqs + offsets[c0], n_bytes, true);
+            const QueueLaunch q = queue_launch(ctx, walk_per_cu, nj, 64, 4);
             t_walk.start();
             if (g->dev.size > 0)
-                hipLaunchKernelGGL(share_walk_kernel, dim3(blocks), dim3(kCovThreads), 0, st, g->dev, d_sym.as<uint8_t>(), d_jobs.as<CovJob>(), nj, chunk, d_ids, cnt_mark);
+                hipLaunchKernelGGL(share_walk_kernel, dim3(q.blocks), dim3(kCovThreads), 0, st, g->dev, d_sym.as<uint8_t>(), d_jobs.as<CovJob>(), nj, q.chunk, d_ids, cnt_mark);
             else
                 MGTA_HIP_CHECK(hipMemsetAsync(d_ids, 0xFF, 2 * n_win * 8 + 64, st));   // no edge anywhere
             MGTA_HIP_CHECK(hipGetLastError());
@@ -1085,7 +888,7 @@ int mgta_contig_sample_coverage(mgta_sdbg *g, const mgta_reads *reads, int reads
             if (batch_longest) {
                 const unsigned gy = (unsigned)std::min<uint64_t>((batch_longest + 255) / 256, 1024);
                 hipLaunchKernelGGL(sample_count_kernel, dim3((nj + 63) / 64, gy), dim3(256), 0, st, tab, d_jobs.as<CovJob>(), nj, (int)k, d_ids, n_win, win_done,
-                                   d_own.as<uint32_t>(), d_rc.as<uint32_t>(), g->marks.as<uint32_t>(), cnt_mark);
+                                   d_own.as<uint32_t>(), d_rc.as<uint32_t>(), d_marks, cnt_mark);
             }
             MGTA_HIP_CHECK(hipGetLastError());
             t_count.end();
@@ -1094,13 +897,12 @@ int mgta_contig_sample_coverage(mgta_sdbg *g, const mgta_reads *reads, int reads
             ms_count += t_count.ms();
             win_done += n_win;
             ++n_batches;
-            c0 = c1;
         }
         unsigned long long cnt[16] = {0};
         MGTA_HIP_CHECK(hipMemcpyAsync(cnt, d_cnt.p, 64, hipMemcpyDeviceToHost, st));
         MGTA_HIP_CHECK(hipStreamSynchronize(st));
         if (cnt[5]) { set_error("mgta_contig_sample_coverage: the count table of %llu slots ran full", (unsigned long long)tab.n_slots); return MGTA_EHIP; }
-        // every batch is in: the keys are final.  The batch buffers make room for the counts and the outputs.
+        // ---- every batch is in: the keys are final and get their numbers.  The batch buffers make room for the counts and the outputs.
         d_sym.release(); d_jobs.release();
         const uint64_t n_keys = cnt[3], n_scan = lib_end[n_libs - 1];
         const uint64_t count_b = (n_keys + 1) * L * 8;
@@ -1113,24 +915,17 @@ int mgta_contig_sample_coverage(mgta_sdbg *g, const mgta_reads *reads, int reads
         hipLaunchKernelGGL(sample_dense_kernel, dim3((unsigned)std::min<uint64_t>(tab.n_slots / 256, (uint64_t)ctx->num_cus * 16)), dim3(256), 0, st, tab, cnt_mark);
         MGTA_HIP_CHECK(hipGetLastError());
         t_count.end();
+        // ---- the read scan
+        const QueueLaunch q_scan = queue_launch(ctx, queue_per_cu(sample_scan_kernel), n_scan, 256, 16);
         t_scan.start();
-        if (n_scan && g->dev.size > 0) {
-            // a group takes `chunk` reads per visit to the queue head, as in the read recruitment
-            const uint64_t groups = (uint64_t)ctx->num_cus * (uint64_t)scan_per_cu * kGroups;
-            const uint32_t chunk = n_scan >= groups * 256 ? 16u : 1u;
-            const unsigned blocks = (unsigned)std::min<uint64_t>((uint64_t)ctx->num_cus * (uint64_t)scan_per_cu, (n_scan + (uint64_t)kGroups * chunk - 1) / ((uint64_t)kGroups * chunk));
-            hipLaunchKernelGGL(sample_scan_kernel, dim3(blocks), dim3(kCovThreads), 0, st, g->dev, reads->d_packed, reads->d_start, n_scan, reads_reversed ? 1 : 0, chunk,
-                               g->marks.as<uint32_t>(), tab, d_counts.as<unsigned long long>(), d_ends.as<uint64_t>(), n_libs, d_hits.as<unsigned long long>(), cnt_scan);
-        }
+        if (n_scan && g->dev.size > 0)
+            hipLaunchKernelGGL(sample_scan_kernel, dim3(q_scan.blocks), dim3(kCovThreads), 0, st, g->dev, reads->d_packed, reads->d_start, n_scan, reads_reversed ? 1 : 0,
+                               q_scan.chunk, d_marks, tab, d_counts.as<unsigned long long>(), d_ends.as<uint64_t>(), n_libs, d_hits.as<unsigned long long>(), cnt_scan);
         MGTA_HIP_CHECK(hipGetLastError());
         t_scan.end();
-        std::vector<uint64_t> woff((size_t)n + 1, 0);
-        std::vector<uint32_t> lens((size_t)n);
-        for (int64_t i = 0; i < n; ++i) {
-            const uint64_t len = offsets[i + 1] - offsets[i];
-            lens[(size_t)i] = (uint32_t)len;
-            woff[(size_t)i + 1] = woff[(size_t)i] + (len > k ? len - k : 0);
-        }
+        // ---- the masses: one wave per contig
+        std::vector<uint32_t> lens;
+        const std::vector<uint64_t> woff = window_offsets(offsets, n, k, &lens);
         d_woff.alloc(((size_t)n + 1) * 8, &ctx->live_bytes, &ctx->peak_bytes);
         d_lens.alloc((size_t)n * 4, &ctx->live_bytes, &ctx->peak_bytes);
         d_out.alloc((size_t)n * sizeof(mgta_contig_share), &ctx->live_bytes, &ctx->peak_bytes);
@@ -1162,7 +957,7 @@ int mgta_contig_sample_coverage(mgta_sdbg *g, const mgta_reads *reads, int reads
             stats->n_contigs = n; stats->n_windows = (int64_t)total_win; stats->n_walked = (int64_t)cnt[1]; stats->n_index_searches = (int64_t)cnt[2];
             stats->n_batches = n_batches; stats->n_covered = (int64_t)covered; stats->n_keys = (int64_t)n_keys; stats->n_libs = n_libs;
             stats->n_reads = (int64_t)n_scan; stats->n_read_windows = (int64_t)cnt[12]; stats->n_read_walked = (int64_t)cnt[9];
-            stats->n_read_index_searches = (int64_t)cnt[10]; stats->n_hit_windows = (int64_t)cnt[11]; stats->groups_per_cu = (int64_t)scan_per_cu * kGroups;
+            stats->n_read_index_searches = (int64_t)cnt[10]; stats->n_hit_windows = (int64_t)cnt[11]; stats->groups_per_cu = q_scan.groups_per_cu();
             stats->total_mass = total; stats->table_slots = tab.n_slots; stats->table_bytes = tab.n_slots * 16; stats->window_bytes = total_win * 8;
             stats->count_bytes = count_b;
             stats->ms_mark = ms_walk + ms_count + t_count.ms(); stats->ms_scan = t_scan.ms(); stats->ms_mass = t_mass.ms();

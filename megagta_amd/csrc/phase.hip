@@ -154,9 +154,7 @@ __global__ __launch_bounds__(kCovThreads) void phase_scan_kernel(PhaseArgs A) {
     uint32_t n_usable = 0, n_frag = 0, n_mate = 0, n_frag_allele = 0, n_frag_linked = 0, n_alleles = 0, n_conflicts = 0;
     unsigned long long n_adds = 0;
     for (;;) {
-        // every lane takes part and only the group's first counts (no branch on the lane in front of the group-wide read)
-        unsigned long long first = atomicAdd(&A.counters[HC_HEAD], sub == 0 ? (unsigned long long)A.chunk : 0ull);
-        first = __shfl(first, 0, 8);
+        const unsigned long long first = grp_next_chunk(&A.counters[HC_HEAD], A.chunk, sub);
         if (first >= A.n_slots) break;
         const uint64_t slot_end = min((unsigned long long)A.n_slots, first + A.chunk);
         for (uint64_t slot = first; slot < slot_end; ++slot) {
@@ -306,7 +304,6 @@ int mgta_reads_phase(const mgta_reads *reads, int reads_reversed, const mgta_rea
         mgta_ctx *ctx = reads->ctx;
         MGTA_HIP_CHECK(hipSetDevice(ctx->device));
         hipStream_t st = ctx->stream;
-        constexpr int kGroups = kCovThreads / 8;
         uint64_t live = 0, peak = 0;                                          // the buffers of this call
         DevBuf d_cnt;
         d_cnt.alloc(256, &live, &peak);
@@ -353,20 +350,15 @@ int mgta_reads_phase(const mgta_reads *reads, int reads_reversed, const mgta_rea
         MGTA_HIP_CHECK(hipMemsetAsync(d_counts.p, 0, (size_t)S * 16, st));
         if (n_pairs) MGTA_HIP_CHECK(hipMemsetAsync(d_joint.p, 0, (size_t)n_pairs * 64, st));
         t_up.end();
-        int per_cu = 0;
-        MGTA_HIP_CHECK(hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, phase_scan_kernel, kCovThreads, 0));
-        per_cu = std::max(1, per_cu);
-        const uint64_t groups = (uint64_t)ctx->num_cus * (uint64_t)per_cu * kGroups;
-        const uint32_t chunk = ctx->phase_chunk ? ctx->phase_chunk : (n_slots >= groups * 256 ? 16u : 1u);
-        const uint64_t blocks = std::max<uint64_t>(1, std::min<uint64_t>((uint64_t)ctx->num_cus * (uint64_t)per_cu, (n_slots + (uint64_t)kGroups * chunk - 1) / ((uint64_t)kGroups * chunk)));
+        const QueueLaunch q = queue_launch(ctx, queue_per_cu(phase_scan_kernel), n_slots, 256, 16, ctx->phase_chunk);
         t_scan.start();
         if (n_slots) {
             PhaseArgs A;
-            A.packed = reads->d_packed; A.start = reads->d_start; A.reversed = reads_reversed ? 1 : 0; A.chunk = chunk; A.place = d_place.as<mgta_read_place>();
+            A.packed = reads->d_packed; A.start = reads->d_start; A.reversed = reads_reversed ? 1 : 0; A.chunk = q.chunk; A.place = d_place.as<mgta_read_place>();
             A.libs = d_libs.as<PhaseLib>(); A.n_libs = n_libs; A.n_slots = n_slots; A.coff = d_coff.as<uint64_t>(); A.site_off = d_soff.as<uint64_t>();
             A.site_pos = d_spos.as<uint32_t>(); A.pair_off = d_poff.as<uint64_t>(); A.site_counts = d_counts.as<uint32_t>(); A.joint = d_joint.as<uint32_t>();
             A.counters = cnt_scan;
-            hipLaunchKernelGGL(phase_scan_kernel, dim3((unsigned)blocks), dim3(kCovThreads), 0, st, A);
+            hipLaunchKernelGGL(phase_scan_kernel, dim3(q.blocks), dim3(kCovThreads), 0, st, A);
         }
         MGTA_HIP_CHECK(hipGetLastError());
         t_scan.end();

@@ -1,14 +1,15 @@
 // pileup.hip — the reads placed on a gene's contigs: per-base depth, the reads that fit a contig end to end and the positions where the
 // reads disagree with it (mgta_reads_pileup; the rule is this project's own and is stated in include/megagta_hip.h).
 //
-// Four phases.  (1) Keys: both strands of every contig go through share_walk_kernel into the edge-keyed table (walk.hpp), exactly as
-// the per-library coverage does it, marks included: every window keeps the slot of its own edge and of the edge of its reverse
-// complement.  (2) Occurrence index: per key the list of (contig, window, strand) that lie on it -- a count per key, a prefix sum
-// (scan.hpp) and a fill through an atomic cursor; the order inside a key is the device's and no output depends on it.  (3) The read
-// scan, below.  (4) One wave per contig over its counts for the per-contig record.
+// Four phases.  (1) Keys: both strands of every contig (one batch of cut_batch, contig_jobs.hpp) go through share_walk_kernel into
+// the edge-keyed table (walk.hpp: sample_table_alloc, stage_symbols, queue_launch), exactly as the per-library coverage does it,
+// marks included: every window keeps the slot of its own edge and of the edge of its reverse complement.  (2) Occurrence index: per
+// key the list of (contig, window, strand) that lie on it -- a count per key, a prefix sum (scan.hpp) and a fill through an atomic
+// cursor; the order inside a key is the device's and no output depends on it.  (3) The read scan, below.  (4) One wave per contig
+// over its counts for the per-contig record.
 //
-// The read scan.  A group of 8 lanes owns a read (32 groups per workgroup, reads from one atomic head), walks it as
-// sample_scan_kernel does and leaves one word per window in the group's own scratch row: 0 = no edge, the slot of its key, or "an
+// The read scan.  A group of 8 lanes owns a read (32 groups per workgroup, reads from one atomic head), walks it
+// as sample_scan_kernel does and leaves one word per window in the group's own scratch row: 0 = no edge, the slot of its key, or "an
 // edge that is no key".  A window on a key has, per occurrence, one anchor (o, p, i, q) on the diagonal d = q - p.  Candidates are
 // never listed: an anchor whose left neighbour on the diagonal is an anchor too (window p - 1 has an edge and c[q - 1] = s[p - 1]:
 // one byte compare) is skipped; every other anchor -- a run start -- is verified along the whole overlap, the lanes comparing 8
@@ -16,8 +17,8 @@
 // finds the first of them.  Only the first anchor of a diagonal owns the candidate, so a candidate is judged once whatever the number
 // of its runs.  Pass one keeps the best score, the number of candidates that have it and the lowest of them; pass two repeats the
 // sweeps, leaving one as soon as its mismatches put it below that score, and commits the candidates that have it: integer atomicAdds,
-// so no order matters.  Every loop is bounded by a read
-// length, an occurrence count or the table size; no workgroup waits for another.
+// so no order matters.  Every loop is bounded by a read length, an occurrence count or the table size; no workgroup waits for
+// another.
 #include <algorithm>
 #include <numeric>
 #include <vector>
@@ -168,7 +169,7 @@ __device__ __forceinline__ void pile_pass(const PileArgs &A, int k, int a, uint6
 }
 
 __global__ __launch_bounds__(kCovThreads) void pile_scan_kernel(GraphDev g, PileArgs A) {
-    __shared__ uint8_t s_seq[kCovThreads / 8][kMatchMaxWindow];
+    __shared__ uint8_t s_seq[kCovGroups][kMatchMaxWindow];
     __shared__ unsigned long long s_cnt[PC_NUM];
     if (threadIdx.x < PC_NUM) s_cnt[threadIdx.x] = 0;
     __syncthreads();
@@ -176,10 +177,11 @@ __global__ __launch_bounds__(kCovThreads) void pile_scan_kernel(GraphDev g, Pile
     const int k = g.k;
     const int a = A.reversed ? 1 : 0;                                         // the stored order, complemented when reversed, is the read in orientation a
     uint8_t *seq = s_seq[threadIdx.x >> 3];
-    uint32_t *wvp = A.wv + ((uint64_t)blockIdx.x * (kCovThreads / 8) + (threadIdx.x >> 3)) * A.wv_stride;
+    uint32_t *wvp = A.wv + ((uint64_t)blockIdx.x * (kCovGroups) + (threadIdx.x >> 3)) * A.wv_stride;
     const uint32_t flip = A.reversed ? 3u : 0u;
     for (;;) {
-        // every lane takes part and only the group's first counts (no branch on the lane in front of the group-wide read)
+        // every lane takes part and only the group's first counts.  (grp_next_chunk, the leader-only form of the other kernels, measured
+        // 0.4 % slower here where the scan is the walk alone: profiles/walk/README.md)
         unsigned long long first = atomicAdd(&A.counters[PC_HEAD], sub == 0 ? (unsigned long long)A.chunk : 0ull);
         first = __shfl(first, 0, 8);
         if (first >= A.n_reads) break;
@@ -194,7 +196,7 @@ __global__ __launch_bounds__(kCovThreads) void pile_scan_kernel(GraphDev g, Pile
             for (uint32_t p = 0; p < n_win; ++p) {
                 const uint64_t q = s0 + p + (uint64_t)k;                      // the window's last base
                 if (p == 0 || (q & 15) == 0) w = A.packed[q >> 4];
-                const int c = (int)(((w >> (30 - 2 * (int)(q & 15))) & 3u) ^ flip) + 1;
+                const int c = (int)packed_symbol(w, q, flip);
                 if (e >= 0) {
                     e = cov_step(g, L, e, c, sub);
                     if (e >= 0) ++walked;
@@ -202,7 +204,7 @@ __global__ __launch_bounds__(kCovThreads) void pile_scan_kernel(GraphDev g, Pile
                     // every lane writes all k + 1 symbols itself and reads back only what it wrote (the same values in every lane of the group)
                     for (int i = 0; i <= k; ++i) {
                         const uint64_t qi = s0 + p + (uint64_t)i;
-                        seq[i] = (uint8_t)((((A.packed[qi >> 4] >> (30 - 2 * (int)(qi & 15))) & 3u) ^ flip) + 1);
+                        seq[i] = (uint8_t)packed_symbol(A.packed[qi >> 4], qi, flip);
                     }
                     e = g_index_edge(g, seq);
                     ++searched;
@@ -211,7 +213,7 @@ __global__ __launch_bounds__(kCovThreads) void pile_scan_kernel(GraphDev g, Pile
                 uint32_t v = 0;
                 if (e >= 0) {
                     v = kPileNoKey;
-                    if ((A.marks[e >> 5] >> (e & 31)) & 1u) {                 // the one-bit filter in front of the table
+                    if (edge_marked(A.marks, e)) {                 // the one-bit filter in front of the table
                         const uint32_t slot = sample_table_find(A.t, e);
                         if (slot) { v = slot; ++hits; }
                     }
@@ -305,14 +307,7 @@ int mgta_reads_pileup(mgta_sdbg *g, const mgta_reads *reads, int reads_reversed,
     if (par.min_overlap == 0) par.min_overlap = (int32_t)k + 1;
     if (par.max_mismatch_permille == 0) par.max_mismatch_permille = 50;
     uint64_t total_win = 0;
-    for (int64_t i = 0; i < n; ++i) {
-        if (offsets[i + 1] < offsets[i] || (offsets[i + 1] > offsets[i] && !seqs)) {
-            set_error("mgta_reads_pileup: contig %lld: offsets must ascend", (long long)i);
-            return MGTA_EINVAL;
-        }
-        const uint64_t len = offsets[i + 1] - offsets[i];
-        total_win += len > k ? len - k : 0;
-    }
+    if (!check_contigs("mgta_reads_pileup", seqs, offsets, n, k, 0, 0, &total_win, nullptr)) return MGTA_EINVAL;   // (no cap per contig: offsets[n] is checked below)
     if (n > 0 && offsets[0] != 0) { set_error("mgta_reads_pileup: offsets[0] = %llu (the counts are indexed by the offsets: 0 is expected)", (unsigned long long)offsets[0]); return MGTA_EINVAL; }
     const uint64_t n_sym = n > 0 ? offsets[n] : 0;
     if (n_sym > 0xFFFFFFFFull) { set_error("mgta_reads_pileup: %llu letters in the call (offsets[n] < 2^32 is supported)", (unsigned long long)n_sym); return MGTA_EINVAL; }
@@ -337,7 +332,6 @@ int mgta_reads_pileup(mgta_sdbg *g, const mgta_reads *reads, int reads_reversed,
         mgta_ctx *ctx = g->ctx;
         MGTA_HIP_CHECK(hipSetDevice(ctx->device));
         hipStream_t st = ctx->stream;
-        constexpr int kGroups = kCovThreads / 8;
         uint64_t live = 0, peak = 0;                                          // the buffers of this call
         DevBuf d_cnt;
         d_cnt.alloc(256, &live, &peak);
@@ -355,68 +349,41 @@ int mgta_reads_pileup(mgta_sdbg *g, const mgta_reads *reads, int reads_reversed,
         }
         zero_outputs();
         Timer t_keys(st), t_index(st), t_scan(st), t_rec(st);
-        int walk_per_cu = 0, scan_per_cu = 0;
-        MGTA_HIP_CHECK(hipOccupancyMaxActiveBlocksPerMultiprocessor(&walk_per_cu, share_walk_kernel, kCovThreads, 0));
-        MGTA_HIP_CHECK(hipOccupancyMaxActiveBlocksPerMultiprocessor(&scan_per_cu, pile_scan_kernel, kCovThreads, 0));
-        walk_per_cu = std::max(1, walk_per_cu);
-        scan_per_cu = std::max(1, scan_per_cu);
-        SampleTable tab{nullptr, nullptr, nullptr, 1024, ctx->share_hash_bits >= 64 ? ~0ull : (1ull << ctx->share_hash_bits) - 1};
-        while (tab.n_slots < 2 * most_keys + 2) tab.n_slots <<= 1;
-        // one mark bit per edge, the graph's own, zeroed per call
-        const size_t mark_b = ((size_t)std::max<int64_t>(g->dev.size, 0) / 32 + 2) * 4;
-        if (g->marks.bytes < mark_b) g->marks.alloc(mark_b, &ctx->live_bytes, &ctx->peak_bytes);
-        MGTA_HIP_CHECK(hipMemsetAsync(g->marks.p, 0, mark_b, st));
-        DevBuf d_sym, d_jobs, d_keys, d_share, d_dense, d_own, d_rc, d_coff, d_woff, d_occ_cnt, d_occ_off, d_occ, d_tmp, d_counts, d_uniq, d_ctg, d_wv, d_pr, d_out;
-        d_keys.alloc(tab.n_slots * 8, &live, &peak);
-        d_share.alloc(tab.n_slots * 4, &live, &peak);
-        d_dense.alloc(tab.n_slots * 4, &live, &peak);
+        uint32_t *d_marks = marks_reset(g, st);
+        DevBuf d_sym, d_jobs, d_own, d_rc, d_coff, d_woff, d_occ_cnt, d_occ_off, d_occ, d_tmp, d_counts, d_uniq, d_ctg, d_wv, d_pr, d_out;
+        SampleTableMem tm;
+        sample_table_alloc(ctx, st, most_keys, &live, &peak, tm);
+        const SampleTable &tab = tm.t;
         d_own.alloc(total_win * 4 + 16, &live, &peak);
         d_rc.alloc(total_win * 4 + 16, &live, &peak);
-        tab.keys = d_keys.as<unsigned long long>(); tab.share = d_share.as<uint32_t>(); tab.dense = d_dense.as<uint32_t>();
-        MGTA_HIP_CHECK(hipMemsetAsync(d_keys.p, 0xFF, tab.n_slots * 8, st));
-        MGTA_HIP_CHECK(hipMemsetAsync(d_share.p, 0, tab.n_slots * 4, st));
         // ---- phase 1: the keys.  All contigs are one batch: the best-hit rule needs them all
         std::vector<CovJob> jobs;
-        std::vector<uint64_t> woff((size_t)n + 1, 0);
-        for (int64_t i = 0; i < n; ++i) {
-            const uint64_t len = offsets[i + 1] - offsets[i], wn = len > k ? len - k : 0;
-            jobs.push_back(CovJob{offsets[i], woff[(size_t)i], (uint32_t)len, (uint32_t)i * 2u});
-            woff[(size_t)i + 1] = woff[(size_t)i] + wn;
-        }
-        for (int64_t j = 0; j < n; ++j) {                                     // the reverse complement of [a, a + len) lies at [2 n_sym - a - len, 2 n_sym - a)
-            const CovJob f = jobs[(size_t)j];
-            jobs.push_back(CovJob{2 * n_sym - f.off - f.len, total_win + f.win_base, f.len, f.idx + 1u});
-        }
+        uint64_t n_win = 0;
+        cut_batch(offsets, n, k, 0, ~0ull, true, jobs, &n_win);
+        const std::vector<uint64_t> woff = window_offsets(offsets, n, k);
         const uint32_t nj = (uint32_t)jobs.size();
-        std::sort(jobs.begin(), jobs.end(), [](const CovJob &a, const CovJob &b) { return a.len != b.len ? a.len > b.len : a.idx < b.idx; });
-        const uint64_t longest = jobs[0].len > k ? jobs[0].len - k : 0;
+        const uint64_t longest = contig_windows(jobs[0].len, k);
         d_sym.alloc(2 * n_sym + 16, &live, &peak);
         d_jobs.alloc((size_t)nj * sizeof(CovJob), &live, &peak);
         d_coff.alloc(((size_t)n + 1) * 8, &live, &peak);
         d_woff.alloc(((size_t)n + 1) * 8, &live, &peak);
         int64_t *d_ids = reinterpret_cast<int64_t *>(window_scratch(ctx, 2 * total_win * 8 + 64));
-        if (n_sym) MGTA_HIP_CHECK(hipMemcpyAsync(d_sym.p, seqs, n_sym, hipMemcpyHostToDevice, st));
         MGTA_HIP_CHECK(hipMemcpyAsync(d_jobs.p, jobs.data(), (size_t)nj * sizeof(CovJob), hipMemcpyHostToDevice, st));
         MGTA_HIP_CHECK(hipMemcpyAsync(d_coff.p, offsets, ((size_t)n + 1) * 8, hipMemcpyHostToDevice, st));
         MGTA_HIP_CHECK(hipMemcpyAsync(d_woff.p, woff.data(), ((size_t)n + 1) * 8, hipMemcpyHostToDevice, st));
-        if (n_sym) {
-            const unsigned sym_blocks = (unsigned)std::min<uint64_t>((n_sym + 255) / 256, (uint64_t)ctx->num_cus * 16);
-            hipLaunchKernelGGL(cov_symbols_kernel, dim3(sym_blocks), dim3(256), 0, st, d_sym.as<uint8_t>(), n_sym);
-            hipLaunchKernelGGL(match_rc_symbols_kernel, dim3(sym_blocks), dim3(256), 0, st, d_sym.as<uint8_t>(), n_sym);
-        }
+        stage_symbols(ctx, st, d_sym, seqs, n_sym, true);
+        const QueueLaunch q_walk = queue_launch(ctx, queue_per_cu(share_walk_kernel), nj, 64, 4);
         t_keys.start();
-        if (g->dev.size > 0) {
-            const uint64_t groups = (uint64_t)ctx->num_cus * (uint64_t)walk_per_cu * kGroups;
-            const uint32_t chunk = nj >= groups * 64 ? 4u : 1u;
-            const unsigned blocks = (unsigned)std::min<uint64_t>((uint64_t)ctx->num_cus * (uint64_t)walk_per_cu, ((uint64_t)nj + kGroups - 1) / kGroups);
-            hipLaunchKernelGGL(share_walk_kernel, dim3(blocks), dim3(kCovThreads), 0, st, g->dev, d_sym.as<uint8_t>(), d_jobs.as<CovJob>(), nj, chunk, d_ids, cnt_mark);
-        } else
+        if (g->dev.size > 0)
+            hipLaunchKernelGGL(share_walk_kernel, dim3(q_walk.blocks), dim3(kCovThreads), 0, st, g->dev, d_sym.as<uint8_t>(), d_jobs.as<CovJob>(), nj, q_walk.chunk, d_ids,
+                               cnt_mark);
+        else
             MGTA_HIP_CHECK(hipMemsetAsync(d_ids, 0xFF, 2 * total_win * 8 + 64, st));   // no edge anywhere
         MGTA_HIP_CHECK(hipGetLastError());
         if (longest) {
             const unsigned gy = (unsigned)std::min<uint64_t>((longest + 255) / 256, 1024);
             hipLaunchKernelGGL(sample_count_kernel, dim3((nj + 63) / 64, gy), dim3(256), 0, st, tab, d_jobs.as<CovJob>(), nj, (int)k, d_ids, total_win, (uint64_t)0,
-                               d_own.as<uint32_t>(), d_rc.as<uint32_t>(), g->marks.as<uint32_t>(), cnt_mark);
+                               d_own.as<uint32_t>(), d_rc.as<uint32_t>(), d_marks, cnt_mark);
         }
         hipLaunchKernelGGL(sample_dense_kernel, dim3((unsigned)std::min<uint64_t>(tab.n_slots / 256, (uint64_t)ctx->num_cus * 16)), dim3(256), 0, st, tab, cnt_mark);
         MGTA_HIP_CHECK(hipGetLastError());
@@ -459,20 +426,18 @@ int mgta_reads_pileup(mgta_sdbg *g, const mgta_reads *reads, int reads_reversed,
         MGTA_HIP_CHECK(hipMemsetAsync(d_ctg.p, 0, (size_t)n * 24, st));
         const uint64_t max_win = max_len > k ? max_len - k : 0;
         const uint64_t wv_stride = std::max<uint64_t>(16, (max_win + 15) & ~15ull);
-        const uint64_t groups = (uint64_t)ctx->num_cus * (uint64_t)scan_per_cu * kGroups;
-        const uint32_t chunk = ctx->pileup_chunk ? ctx->pileup_chunk : (n_short_reads >= groups * 256 ? 16u : 1u);
-        uint64_t blocks = std::min<uint64_t>((uint64_t)ctx->num_cus * (uint64_t)scan_per_cu, (n_short_reads + (uint64_t)kGroups * chunk - 1) / ((uint64_t)kGroups * chunk));
-        blocks = std::max<uint64_t>(1, std::min<uint64_t>(blocks, kPileScratchBytes / (wv_stride * 4 * kGroups)));
-        d_wv.alloc(blocks * kGroups * wv_stride * 4, &live, &peak);
+        QueueLaunch q_scan = queue_launch(ctx, queue_per_cu(pile_scan_kernel), n_short_reads, 256, 16, ctx->pileup_chunk);
+        q_scan.blocks = (unsigned)std::max<uint64_t>(1, std::min<uint64_t>(q_scan.blocks, kPileScratchBytes / (wv_stride * 4 * kCovGroups)));   // the scratch rows of the groups in flight
+        d_wv.alloc((uint64_t)q_scan.blocks * kCovGroups * wv_stride * 4, &live, &peak);
         t_scan.start();
         if (g->dev.size > 0) {
             PileArgs A;
-            A.packed = reads->d_packed; A.start = reads->d_start; A.n_reads = n_short_reads; A.reversed = reads_reversed ? 1 : 0; A.chunk = chunk;
-            A.marks = g->marks.as<uint32_t>(); A.t = tab; A.sym = d_sym.as<uint8_t>(); A.coff = d_coff.as<uint64_t>(); A.occ_off = d_occ_off.as<uint64_t>();
+            A.packed = reads->d_packed; A.start = reads->d_start; A.n_reads = n_short_reads; A.reversed = reads_reversed ? 1 : 0; A.chunk = q_scan.chunk;
+            A.marks = d_marks; A.t = tab; A.sym = d_sym.as<uint8_t>(); A.coff = d_coff.as<uint64_t>(); A.occ_off = d_occ_off.as<uint64_t>();
             A.occ = d_occ.as<uint64_t>(); A.counts = d_counts.as<uint32_t>(); A.uniq = d_uniq.as<uint32_t>(); A.ctg = d_ctg.as<unsigned long long>();
             A.per_read = per_read ? d_pr.as<mgta_read_place>() : nullptr; A.wv = d_wv.as<uint32_t>(); A.wv_stride = wv_stride;
             A.min_anchors = par.min_anchors; A.min_overlap = par.min_overlap; A.max_permille = par.max_mismatch_permille; A.counters = cnt_scan;
-            hipLaunchKernelGGL(pile_scan_kernel, dim3((unsigned)blocks), dim3(kCovThreads), 0, st, g->dev, A);
+            hipLaunchKernelGGL(pile_scan_kernel, dim3(q_scan.blocks), dim3(kCovThreads), 0, st, g->dev, A);
         }
         MGTA_HIP_CHECK(hipGetLastError());
         t_scan.end();
@@ -496,7 +461,7 @@ int mgta_reads_pileup(mgta_sdbg *g, const mgta_reads *reads, int reads_reversed,
             stats->n_hit_windows = (int64_t)c[PC_HITS]; stats->n_read_walked = (int64_t)c[PC_WALKED]; stats->n_read_index_searches = (int64_t)c[PC_SEARCHED];
             stats->n_reads_with_candidate = (int64_t)c[PC_READS_CAND]; stats->n_candidates = (int64_t)c[PC_CAND]; stats->n_verified = (int64_t)c[PC_VERIFIED];
             stats->n_reads_placed = (int64_t)c[PC_PLACED]; stats->n_reads_multi = (int64_t)c[PC_MULTI]; stats->n_placements = (int64_t)c[PC_PLACEMENTS];
-            stats->n_bases_piled = (int64_t)c[PC_PILED]; stats->groups_per_cu = (int64_t)scan_per_cu * kGroups; stats->peak_bytes = peak;
+            stats->n_bases_piled = (int64_t)c[PC_PILED]; stats->groups_per_cu = q_scan.groups_per_cu(); stats->peak_bytes = peak;
             stats->ms_keys = t_keys.ms(); stats->ms_index = t_index.ms(); stats->ms_scan = t_scan.ms(); stats->ms_records = t_rec.ms();
             stats->ms_total = stats->ms_keys + stats->ms_index + stats->ms_scan + stats->ms_records;
         }

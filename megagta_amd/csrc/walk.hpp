@@ -1,12 +1,26 @@
-// walk.hpp -- what the walks over the graph share: the forward step of a walk (cov_step) behind an index search (g_index_edge, graph.hpp),
-// the walk that leaves the edge id of every window of a set of contigs (share_walk_kernel), and the edge-keyed table of a call's
-// contig windows on both strands (SampleTable with its add, find, count and numbering kernels).  coverage.hip and pileup.hip include it,
-// and phase.hip for the letter of a packed read (pile_base); every kernel has internal linkage, so each of them compiles its own copy.
+// walk.hpp -- the walk along the resident graph, k + 1 letters at a time, and what the kernels that walk share.
+//
+// Device.  A group of 8 lanes owns a sequence.  walk_next is the step-or-search of one window: a forward step (cov_step) from the
+// edge of the window before, an index search (g_index_edge, graph.hpp) where that window had none.  On it stands walk_contig, the
+// walk over symbols 0..4 (0 = no base: the walk starts again behind it), which hands every window's edge (-1 = none) to a sink;
+// cov_walk_kernel and match_mark_kernel (coverage.hip) call it.
+// Four kernels keep the loop written out, because each was measurably slower on a walker (profiles/walk/README.md):
+// share_walk_kernel here for the contig walk; match_walk_kernel, sample_scan_kernel (coverage.hip) and pile_scan_kernel (pileup.hip)
+// for the read walk, which therefore has no walker.  A change of the walk is made in five places: walk_next and these four.
+// They share the small pieces: the queue dequeue of a group (grp_next_chunk; phase.hip's slot queue too, pile_scan_kernel not:
+// its all-lanes form measured faster), the decode of a
+// packed base (packed_symbol) and the mark bits (edge_marked, mark_edge); walk_contig's callers also the counts of a walk and their
+// flush (WalkCounts).  Further down: the edge-keyed table of a call's contig windows on both strands (SampleTable with its add,
+// find, count and numbering kernels) and the symbol kernels.
+// Host (needs HIP; the plain part -- CovJob, the offsets check, the batch cutter -- is contig_jobs.hpp): marks_reset, table_slots
+// and sample_table_alloc, stage_symbols, queue_per_cu and queue_launch, window_scratch.
+// coverage.hip, pileup.hip and phase.hip include this file; every kernel has internal linkage, so each compiles its own copy.
 #pragma once
 #include <algorithm>
 #include <vector>
 
 #include "common.hpp"
+#include "contig_jobs.hpp"
 #include "device_utils.hpp"
 #include "graph.hpp"
 
@@ -14,12 +28,7 @@ namespace mgta {
 namespace {
 
 constexpr int kCovThreads = 256;          // 4 waves = 32 groups of 8 lanes
-
-struct CovJob {                           // one contig of a batch
-    uint64_t off;                         // its first letter in the batch's symbols
-    uint64_t win_base;                    // its first window in the batch's per-window scratch
-    uint32_t len, idx;                    // letters; contig number inside the batch
-};
+constexpr int kCovGroups = kCovThreads / 8;
 
 // letters -> symbols 1..4 (A C G T in either case), 0 for anything else (an N is NOT folded to G: it was never counted); in place
 __global__ __launch_bounds__(256) void cov_symbols_kernel(uint8_t *s, uint64_t n) {
@@ -94,16 +103,72 @@ __device__ __forceinline__ int64_t cov_step(const GraphDev &g, LineR &L, int64_t
     return -1;
 }
 
-// the per-window scratch: a key buffer of the build pool when it is large enough (it sits idle between the steps), grown otherwise
-uint16_t *window_scratch(mgta_ctx *ctx, uint64_t bytes) {
-    if ((int)ctx->pool.size() < S_NUM) ctx->pool.resize(S_NUM);
-    DevBuf &b = ctx->pool[S_KEYS_A];
-    if (!b.p || b.bytes < bytes) {
-        b.release();
-        b.alloc(bytes, &ctx->live_bytes, &ctx->peak_bytes);
+struct WalkCounts {                       // of one lane's walks; all 8 lanes of a group hold the same numbers
+    uint32_t walked = 0, searched = 0;    // windows found by a step; index searches
+};
+
+// the groups' counts -> *walked and *searched: the sum over the group leaders of a wave, one atomic per wave and counter
+__device__ __forceinline__ void walk_counts_flush(const WalkCounts &n, int sub, unsigned long long *walked, unsigned long long *searched) {
+    const uint32_t w = wave_sum(sub == 0 ? n.walked : 0u), sc = wave_sum(sub == 0 ? n.searched : 0u);
+    if (lane_id() == 0) {
+        if (w) atomicAdd(walked, (unsigned long long)w);
+        if (sc) atomicAdd(searched, (unsigned long long)sc);
     }
-    return b.as<uint16_t>();
 }
+
+// A group takes the next `chunk` items of a queue: its first lane moves the head, and the shuffle that hands the old value round sits
+// behind the branch, where the 8 lanes are together again.
+__device__ __forceinline__ unsigned long long grp_next_chunk(unsigned long long *head, uint32_t chunk, int sub) {
+    unsigned long long first = 0;
+    if (sub == 0) first = atomicAdd(head, (unsigned long long)chunk);
+    return __shfl(first, 0, 8);
+}
+
+// one mark bit per edge (mgta_sdbg::marks)
+__device__ __forceinline__ bool edge_marked(const uint32_t *marks, int64_t e) { return (marks[e >> 5] >> (e & 31)) & 1u; }
+
+// turns the bit of edge e on; true in the one lane that found it off
+__device__ __forceinline__ bool mark_edge(uint32_t *marks, int64_t e) {
+    const uint32_t bit = 1u << (e & 31);
+    return !(atomicOr(&marks[e >> 5], bit) & bit);
+}
+
+// The edge of the next window.  In: e = the edge of the window before (L = its line), -1 = the walk has to start again; c = the
+// window's last symbol; window() = its k + 1 symbols, asked for only when it has to be searched.
+template <class Window>
+__device__ __forceinline__ int64_t walk_next(const GraphDev &g, LineR &L, int64_t e, int c, int sub, WalkCounts &n, Window &&window) {
+    if (e >= 0) {
+        e = cov_step(g, L, e, c, sub);
+        if (e >= 0) ++n.walked;
+    } else {
+        e = g_index_edge(g, window());
+        ++n.searched;
+        if (e >= 0) L = grp_load_line(g, (uint64_t)e >> 6, sub);
+    }
+    return e;
+}
+
+// The walk along the len symbols at s (1..4, 0 = no base): sink(p, e) once per window p, e = its edge, -1 for none.  A window with a
+// 0 in it has no edge, and the walk starts again with the first window behind it.
+template <class Sink>
+__device__ __forceinline__ void walk_contig(const GraphDev &g, const uint8_t *s, uint32_t len, int sub, WalkCounts &n, Sink &&sink) {
+    const int k = g.k;
+    const uint32_t n_win = len > (uint32_t)k ? len - (uint32_t)k : 0;
+    int run = 0;                                                          // A C G T letters in a row, up to the window's last letter
+    for (int i = 0; i < k && (uint32_t)i < len; ++i) run = s[i] ? run + 1 : 0;
+    int64_t e = -1;
+    LineR L{};
+    for (uint32_t p = 0; p < n_win; ++p) {
+        const int c = s[p + k];
+        run = c ? run + 1 : 0;
+        e = run > k ? walk_next(g, L, e, c, sub, n, [&]() { return s + p; }) : -1;
+        sink(p, e);
+    }
+}
+
+// base q of the packed reads (2 bits per base, base j of a word at bits 30 - 2j) out of its word w = packed[q >> 4], as a symbol
+// 1..4; flip = 3 gives the complement
+__device__ __forceinline__ uint32_t packed_symbol(uint32_t w, uint64_t q, uint32_t flip) { return (((w >> (30 - 2 * (int)(q & 15))) & 3u) ^ flip) + 1; }
 
 constexpr int kMatchMaxWindow = 128;      // k + 1 symbols of an index search, staged in LDS per group (32 groups: 4 KB per workgroup)
 
@@ -119,16 +184,17 @@ __global__ __launch_bounds__(256) void match_rc_symbols_kernel(uint8_t *s, uint6
 
 constexpr unsigned long long kShareEmpty = ~0ull;                         // (an edge id is < 2^63)
 
-// counters: [0] queue head, [1] windows found by a step, [2] index searches (cov_walk_kernel's; [3] .. [5] belong to share_count_kernel)
+// The edge id of every window of the jobs (8 bytes, -1 = none), where cov_walk_kernel leaves the multiplicity.  The loop is
+// walk_contig's, written out: on walk_contig this kernel compiled to the same registers and loads, yet took 2.7 % longer where
+// every window is an index search (profiles/walk/README.md).
+// counters: [0] queue head, [1] windows found by a step, [2] index searches ([3] .. [6] belong to the count and numbering kernels)
 __global__ __launch_bounds__(kCovThreads) void share_walk_kernel(GraphDev g, const uint8_t *sym, const CovJob *jobs, uint32_t n_jobs, uint32_t chunk, int64_t *ids,
                                                                  unsigned long long *counters) {
     const int sub = threadIdx.x & 7;
     const int k = g.k;
     uint32_t walked = 0, searched = 0;
     for (;;) {
-        unsigned long long first = 0;
-        if (sub == 0) first = atomicAdd(&counters[0], (unsigned long long)chunk);
-        first = __shfl(first, 0, 8);
+        const unsigned long long first = grp_next_chunk(&counters[0], chunk, sub);
         if (first >= n_jobs) break;
         const uint32_t j_end = (uint32_t)min((unsigned long long)n_jobs, first + chunk);
         for (uint32_t j = (uint32_t)first; j < j_end; ++j) {
@@ -197,7 +263,7 @@ __device__ __forceinline__ uint32_t sample_table_add(const SampleTable &t, int64
         if (key == kShareEmpty) {
             key = atomicCAS(&t.keys[slot], kShareEmpty, (unsigned long long)e);
             if (key == kShareEmpty) {                                     // this lane made the key: the read scan looks at marked edges only
-                atomicOr(&marks[e >> 5], 1u << (e & 31));
+                mark_edge(marks, e);
                 ++n_new;
                 key = (unsigned long long)e;
             }
@@ -302,7 +368,91 @@ __global__ __launch_bounds__(256) void pile_maxlen_kernel(const uint64_t *start,
 // base j of the read in orientation o as a symbol 1..4.  same = (o == the orientation the stored order walks), comp = 3 for o = 1
 __device__ __forceinline__ uint32_t pile_base(const uint32_t *packed, uint64_t s0, uint32_t len, int same, uint32_t comp, uint32_t j) {
     const uint64_t q = s0 + (same ? j : len - 1 - j);
-    return (((packed[q >> 4] >> (30 - 2 * (int)(q & 15))) & 3u) ^ comp) + 1;
+    return packed_symbol(packed[q >> 4], q, comp);
+}
+
+// ---- the host side the calls share (the part that needs no HIP is contig_jobs.hpp)
+
+// the per-window scratch: a key buffer of the build pool when it is large enough (it sits idle between the steps), grown otherwise
+uint16_t *window_scratch(mgta_ctx *ctx, uint64_t bytes) {
+    if ((int)ctx->pool.size() < S_NUM) ctx->pool.resize(S_NUM);
+    DevBuf &b = ctx->pool[S_KEYS_A];
+    if (!b.p || b.bytes < bytes) {
+        b.release();
+        b.alloc(bytes, &ctx->live_bytes, &ctx->peak_bytes);
+    }
+    return b.as<uint16_t>();
+}
+
+// one mark bit per edge, the graph's own, grown where needed and zeroed per call = per set of contigs
+uint32_t *marks_reset(mgta_sdbg *g, hipStream_t st) {
+    const size_t mark_b = ((size_t)std::max<int64_t>(g->dev.size, 0) / 32 + 2) * 4;
+    if (g->marks.bytes < mark_b) g->marks.alloc(mark_b, &g->ctx->live_bytes, &g->ctx->peak_bytes);
+    MGTA_HIP_CHECK(hipMemsetAsync(g->marks.p, 0, mark_b, st));
+    return g->marks.as<uint32_t>();
+}
+
+// the slots of an edge-keyed table of at most most_keys keys: at most half full, a power of two, never more than 2^32 (a slot number is
+// 32 bits; slot 0 is "no edge"); and the bits of the hash the context lets it keep
+uint64_t table_slots(uint64_t most_keys) {
+    uint64_t n_slots = 1024;
+    while (n_slots < 2 * most_keys + 2 && n_slots < (1ull << 32)) n_slots <<= 1;
+    return n_slots;
+}
+uint64_t table_hmask(const mgta_ctx *ctx) { return ctx->share_hash_bits >= 64 ? ~0ull : (1ull << ctx->share_hash_bits) - 1; }
+
+struct SampleTableMem {
+    DevBuf keys, share, dense;
+    SampleTable t;
+};
+
+// an empty SampleTable for most_keys keys (the caller has checked that its slots fit); the bytes are counted in *live and *peak
+void sample_table_alloc(mgta_ctx *ctx, hipStream_t st, uint64_t most_keys, uint64_t *live, uint64_t *peak, SampleTableMem &m) {
+    const uint64_t n_slots = table_slots(most_keys);
+    m.keys.alloc(n_slots * 8, live, peak);
+    m.share.alloc(n_slots * 4, live, peak);
+    m.dense.alloc(n_slots * 4, live, peak);
+    m.t = SampleTable{m.keys.as<unsigned long long>(), m.share.as<uint32_t>(), m.dense.as<uint32_t>(), n_slots, table_hmask(ctx)};
+    MGTA_HIP_CHECK(hipMemsetAsync(m.keys.p, 0xFF, n_slots * 8, st));
+    MGTA_HIP_CHECK(hipMemsetAsync(m.share.p, 0, n_slots * 4, st));
+}
+
+// n_bytes letters -> symbols in d_sym (which holds n_bytes, or 2 n_bytes with both_strands: the reverse complement of all of them
+// behind).  timed, where given, is started behind the upload: it measures the symbol kernels and what the caller launches next.
+void stage_symbols(mgta_ctx *ctx, hipStream_t st, DevBuf &d_sym, const char *seqs, uint64_t n_bytes, bool both_strands, Timer *timed = nullptr) {
+    if (n_bytes) MGTA_HIP_CHECK(hipMemcpyAsync(d_sym.p, seqs, n_bytes, hipMemcpyHostToDevice, st));
+    if (timed) timed->start();
+    if (!n_bytes) return;
+    const unsigned blocks = (unsigned)std::min<uint64_t>((n_bytes + 255) / 256, (uint64_t)ctx->num_cus * 16);
+    hipLaunchKernelGGL(cov_symbols_kernel, dim3(blocks), dim3(256), 0, st, d_sym.as<uint8_t>(), n_bytes);
+    if (both_strands) hipLaunchKernelGGL(match_rc_symbols_kernel, dim3(blocks), dim3(256), 0, st, d_sym.as<uint8_t>(), n_bytes);
+}
+
+// The launch of a kernel whose groups of 8 lanes take their items from one atomic head.  per_cu = the workgroups a CU holds at once:
+// what the kernel's registers allow, asked of the runtime once per call (queue_per_cu; never assumed).  A group takes `chunk` items
+// per visit to the head (one word saturates near 88 dequeues per microsecond): big_chunk where every group in flight has at least
+// `threshold` items, else 1; 64 and 4 for contigs, 256 and 16 for reads.  chunk_override != 0 is the caller's own chunk.
+struct QueueLaunch {
+    int per_cu;
+    uint32_t chunk;
+    unsigned blocks;
+    int64_t groups_per_cu() const { return (int64_t)per_cu * kCovGroups; }
+};
+
+template <class K>
+int queue_per_cu(K kernel) {
+    int per_cu = 0;
+    MGTA_HIP_CHECK(hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, kernel, kCovThreads, 0));
+    return std::max(1, per_cu);
+}
+
+QueueLaunch queue_launch(const mgta_ctx *ctx, int per_cu, uint64_t n_items, uint64_t threshold, uint32_t big_chunk, uint32_t chunk_override = 0) {
+    QueueLaunch q{per_cu, 1, 1};
+    const uint64_t resident = (uint64_t)ctx->num_cus * (uint64_t)per_cu;
+    q.chunk = chunk_override ? chunk_override : (n_items >= resident * kCovGroups * threshold ? big_chunk : 1u);
+    const uint64_t per_block = (uint64_t)kCovGroups * q.chunk;
+    q.blocks = (unsigned)std::max<uint64_t>(1, std::min<uint64_t>(resident, (n_items + per_block - 1) / per_block));
+    return q;
 }
 }  // namespace
 }  // namespace mgta
