@@ -7,6 +7,9 @@
 // Four kernels keep the loop written out, because each was measurably slower on a walker (profiles/walk/README.md):
 // share_walk_kernel here for the contig walk; match_walk_kernel, sample_scan_kernel (coverage.hip) and pile_scan_kernel (pileup.hip)
 // for the read walk, which therefore has no walker.  A change of the walk is made in five places: walk_next and these four.
+// tests/test_walk_edges_gpu.py pins all five copies edge by edge: on graphs whose edge i has multiplicity i + 1 the two contig walks
+// must report the id of every window's edge, and the three read walks the same edges up to strand, at k = 20 .. 127, over every
+// branch of cov_step (the census in tests/test_walk_edges_host.py), before and after `denovo` has consumed the validity bits.
 // They share the small pieces: the queue dequeue of a group (grp_next_chunk; phase.hip's slot queue too, pile_scan_kernel not:
 // its all-lanes form measured faster), the decode of a
 // packed base (packed_symbol) and the mark bits (edge_marked, mark_edge); walk_contig's callers also the counts of a walk and their
