@@ -38,20 +38,14 @@
 //
 // Steps 2 to 5 of the rule are O(L) per contig and run on the host inside the library.
 #include <algorithm>
-#include <numeric>
 #include <vector>
 
-#include "common.hpp"
-#include "device_utils.hpp"
+#include "seq_dp.hpp"
 
 namespace mgta {
 namespace {
 
 constexpr int kChimeraMaxLen = 4096;
-constexpr int kSubLdsBytes = 27 * 32;               // sub[reference class][contig class], rows padded to 32
-constexpr int32_t kUndef = -(1 << 30);
-constexpr int32_t kDefinedFloor = -(1 << 29);
-constexpr uint32_t kFirstColumn = 32;               // bit of a column's byte: the first column of its reference (bits 0-4: the class)
 constexpr uint32_t kIsColumn = 64;                  // bit of a column's byte: a column of the segment
 constexpr uint64_t kDefaultSegment = 4096;          // columns of a segment (plus what the last reference needs to end)
 constexpr int kSweepWaves = 4;
@@ -81,30 +75,16 @@ struct ChimArgs {
     unsigned long long *head;
 };
 
-__device__ __forceinline__ uint32_t residue_class(uint32_t b) {           // 1 .. 26 for an ASCII letter of either case, else 0
-    const uint32_t c = (b | 32u) - 'a';
-    return (b < 128u && c < 26u) ? c + 1u : 0u;
-}
-
-// lane l takes v of lane l - 1, lane 0 keeps `first`: one v_mov_b32 with the DPP control wave_shr:1
-__device__ __forceinline__ int32_t from_left(int32_t v, int32_t first) { return __builtin_amdgcn_update_dpp(first, v, 0x138, 0xF, 0xF, false); }
-
 template <int MODE>
 __global__ __launch_bounds__(kSweepWaves * 64) void chimera_sweep_kernel(ChimArgs a) {
     __shared__ int8_t s_sub[kSubLdsBytes];
-    for (int c = threadIdx.x; c < kSubLdsBytes; c += blockDim.x) {
-        const int cy = c >> 5, cx = c & 31;
-        s_sub[c] = cx < 27 ? a.sub[cx * 27 + cy] : (int8_t)0;
-    }
-    __syncthreads();
+    stage_sub(s_sub, a.sub);
     const int lane = lane_id();
     const int32_t go = a.go, ge = a.ge;
     int2 *bound = a.bound ? a.bound + ((size_t)blockIdx.x * kSweepWaves + (size_t)wave_id()) * a.bound_stride : nullptr;
 
     for (;;) {
-        // every lane takes part and only lane 0 counts (as align_fill_kernel does: no leader-only branch in front of the wave-wide read)
-        unsigned long long k = atomicAdd(a.head, lane == 0 ? 1ull : 0ull);
-        k = wave_uniform((uint64_t)k);
+        const unsigned long long k = next_item(a.head);
         if (k >= a.n_items) break;
         const ChimItem it = a.items[k];
         const uint64_t o0 = a.off[it.contig];
@@ -236,8 +216,8 @@ int mgta_seqs_chimera(mgta_ctx *ctx, const char *seqs, const uint64_t *offsets, 
     if (!ctx) { set_error("mgta_seqs_chimera: ctx must not be NULL"); return MGTA_EINVAL; }
     if (n < 0) { set_error("mgta_seqs_chimera: n = %lld must not be negative", (long long)n); return MGTA_EINVAL; }
     if (n_ref < 0) { set_error("mgta_seqs_chimera: n_ref = %lld must not be negative", (long long)n_ref); return MGTA_EINVAL; }
-    if (n >= (1ll << 31)) { set_error("mgta_seqs_chimera: n = %lld (the limit is n < 2^31 contigs)", (long long)n); return MGTA_EINVAL; }
-    if (n_ref >= (1ll << 31)) { set_error("mgta_seqs_chimera: n_ref = %lld (the limit is n_ref < 2^31 references)", (long long)n_ref); return MGTA_EINVAL; }
+    if (!check_seq_count("mgta_seqs_chimera", kContigs, n)) return MGTA_EINVAL;
+    if (!check_seq_count("mgta_seqs_chimera", kReferences, n_ref)) return MGTA_EINVAL;
     if (gap_extend < 0 || gap_extend > gap_open || gap_open > 1024) {
         set_error("mgta_seqs_chimera: gap_open = %d, gap_extend = %d (the rule needs 0 <= gap_extend <= gap_open <= 1024)", gap_open, gap_extend);
         return MGTA_EINVAL;
@@ -248,29 +228,12 @@ int mgta_seqs_chimera(mgta_ctx *ctx, const char *seqs, const uint64_t *offsets, 
     if (n > 0 && !recs) { set_error("mgta_seqs_chimera: recs must not be NULL"); return MGTA_EINVAL; }
     if (n > 0 && !sub) { set_error("mgta_seqs_chimera: sub must not be NULL"); return MGTA_EINVAL; }
     if (n > 0 && n_ref > 0 && !ref_offsets) { set_error("mgta_seqs_chimera: ref_offsets must not be NULL"); return MGTA_EINVAL; }
-    for (int64_t i = 0; i < n; ++i) {
-        if (offsets[i + 1] < offsets[i]) { set_error("mgta_seqs_chimera: contig %lld: offsets must ascend", (long long)i); return MGTA_EINVAL; }
-        if (offsets[i + 1] - offsets[i] > (uint64_t)kChimeraMaxLen) {
-            set_error("mgta_seqs_chimera: contig %lld holds %llu residues (the limit is %d residues per contig)", (long long)i,
-                      (unsigned long long)(offsets[i + 1] - offsets[i]), kChimeraMaxLen);
-            return MGTA_EINVAL;
-        }
-    }
-    for (int64_t i = 0; n > 0 && i < n_ref; ++i) {
-        if (ref_offsets[i + 1] < ref_offsets[i]) { set_error("mgta_seqs_chimera: reference %lld: ref_offsets must ascend", (long long)i); return MGTA_EINVAL; }
-        if (ref_offsets[i + 1] - ref_offsets[i] > (uint64_t)kChimeraMaxLen) {
-            set_error("mgta_seqs_chimera: reference %lld holds %llu residues (the limit is %d residues per reference)", (long long)i,
-                      (unsigned long long)(ref_offsets[i + 1] - ref_offsets[i]), kChimeraMaxLen);
-            return MGTA_EINVAL;
-        }
-    }
+    if (!check_seq_offsets("mgta_seqs_chimera", kContigs, offsets, n, kChimeraMaxLen)) return MGTA_EINVAL;
+    if (!check_seq_offsets("mgta_seqs_chimera", kReferences, ref_offsets, n > 0 ? n_ref : 0, kChimeraMaxLen)) return MGTA_EINVAL;
     const uint64_t n_letters = n > 0 ? offsets[n] - offsets[0] : 0, n_cols = (n > 0 && n_ref > 0) ? ref_offsets[n_ref] - ref_offsets[0] : 0;
-    if (n_cols >= (1ull << 31)) {
-        set_error("mgta_seqs_chimera: the references hold %llu residues together (the limit is fewer than 2^31 residues in all references)", (unsigned long long)n_cols);
-        return MGTA_EINVAL;
-    }
-    if (n_letters && !seqs) { set_error("mgta_seqs_chimera: seqs must not be NULL"); return MGTA_EINVAL; }
-    if (n_cols && !refs) { set_error("mgta_seqs_chimera: refs must not be NULL"); return MGTA_EINVAL; }
+    if (!check_ref_columns("mgta_seqs_chimera", n_cols)) return MGTA_EINVAL;
+    if (!check_seq_letters("mgta_seqs_chimera", kContigs, seqs, n_letters)) return MGTA_EINVAL;
+    if (!check_seq_letters("mgta_seqs_chimera", kReferences, refs, n_cols)) return MGTA_EINVAL;
     if (stats) memset(stats, 0, sizeof(*stats));
     if (n == 0) return MGTA_OK;
     return guarded("mgta_seqs_chimera", [&]() {
@@ -290,25 +253,18 @@ int mgta_seqs_chimera(mgta_ctx *ctx, const char *seqs, const uint64_t *offsets, 
         MGTA_HIP_CHECK(hipSetDevice(ctx->device));
         hipStream_t st = ctx->stream;
         uint64_t *live = &ctx->live_bytes, *peak = &ctx->peak_bytes;
-        struct PeakOfCall {                                               // peak_bytes is this call's while it runs, the context's again on every way out
-            uint64_t *peak, before;
-            ~PeakOfCall() { *peak = std::max(*peak, before); }
-        } peak_of_call{peak, *peak};
-        *peak = *live;
+        PeakOfCall peak_of_call(ctx);
 
         // the contigs: where they start, longest first
-        std::vector<uint64_t> rel((size_t)nn + 1);
-        for (uint32_t i = 0; i <= nn; ++i) rel[i] = offsets[i] - offsets[0];
-        std::vector<uint32_t> order(nn);
-        std::iota(order.begin(), order.end(), 0u);
-        std::stable_sort(order.begin(), order.end(), [&](uint32_t x, uint32_t y) { return rel[x + 1] - rel[x] > rel[y + 1] - rel[y]; });
+        const std::vector<uint64_t> rel = rel_offsets(offsets, n);
+        const std::vector<uint32_t> order = longest_first(rel);
         const uint32_t l_max = (uint32_t)(rel[order[0] + 1] - rel[order[0]]);
-        // the columns, forwards and with every reference reversed in its place: class and first-column bit
+        // the columns, forwards and, behind them, with every reference reversed in its place: class and first-column bit
         const uint32_t nc = (uint32_t)n_cols;
-        std::vector<uint32_t> rstart((size_t)n_ref + 1);
-        for (int64_t r = 0; r <= n_ref; ++r) rstart[(size_t)r] = (uint32_t)(ref_offsets[r] - ref_offsets[0]);
-        std::vector<uint8_t> rcls((size_t)nc * 2);
-        const unsigned char *rtext = reinterpret_cast<const unsigned char *>(refs) + ref_offsets[0];
+        std::vector<uint32_t> rstart;
+        std::vector<uint8_t> rcls;
+        ref_columns(refs, ref_offsets, n_ref, rstart, rcls);
+        rcls.resize((size_t)nc * 2);
         std::vector<int32_t> nz_ref;                                      // the references that have residues
         std::vector<uint32_t> nz_at((size_t)n_ref + 1);                   // how many of them lie before reference r
         for (int64_t r = 0; r < n_ref; ++r) {
@@ -316,12 +272,8 @@ int mgta_seqs_chimera(mgta_ctx *ctx, const char *seqs, const uint64_t *offsets, 
             nz_at[(size_t)r] = (uint32_t)nz_ref.size();
             if (e == b) continue;
             nz_ref.push_back((int32_t)r);
-            for (uint32_t g = b; g < e; ++g) {
-                const uint32_t ch = rtext[g], c = (ch | 32u) - 'a';
-                const uint8_t cls = (uint8_t)((ch < 128u && c < 26u) ? c + 1u : 0u);
-                rcls[g] = cls; rcls[(size_t)nc + (b + (e - 1 - g))] = cls;
-            }
-            rcls[b] |= kFirstColumn; rcls[(size_t)nc + b] |= kFirstColumn;
+            for (uint32_t g = b; g < e; ++g) rcls[(size_t)nc + (b + (e - 1 - g))] = rcls[g] & 31u;
+            rcls[(size_t)nc + b] |= kFirstColumn;
         }
         nz_at[(size_t)n_ref] = (uint32_t)nz_ref.size();
         // segments: whole references, as few columns over the target as the last reference needs
@@ -364,34 +316,31 @@ int mgta_seqs_chimera(mgta_ctx *ctx, const char *seqs, const uint64_t *offsets, 
         const unsigned grid = (unsigned)std::max<uint64_t>(1, std::min<uint64_t>((uint64_t)ctx->num_cus * (uint64_t)bpc, (n_items + kSweepWaves - 1) / kSweepWaves));
         const uint64_t bound_stride = l_max > 64 ? (((uint64_t)w_max + 63) & ~63ull) : 0;
 
-        DevBuf d_seqs, d_off, d_rcls, d_seg, d_segref, d_items, d_sub, d_head, d_part, d_tops, d_nz, d_bound;
-        d_seqs.alloc(n_letters + 16, live, peak);
-        d_off.alloc((size_t)(nn + 1) * 8, live, peak);
+        SeqStage dev;
+        dev.upload(ctx, seqs, offsets, rel, nullptr);
+        DevBuf d_rcls, d_seg, d_segref, d_items, d_sub, d_part, d_tops, d_nz, d_bound;
         d_rcls.alloc((size_t)nc * 2 + 16, live, peak);
         d_seg.alloc((size_t)n_seg * sizeof(uint2), live, peak);
         d_segref.alloc((size_t)n_seg * 4, live, peak);
         d_items.alloc((size_t)n_items * sizeof(ChimItem), live, peak);
         d_sub.alloc(27 * 27, live, peak);
-        d_head.alloc(64, live, peak);
         d_nz.alloc(nz_ref.size() * 4, live, peak);
         d_part.alloc((size_t)n_groups * 2 * n_letters * sizeof(int4), live, peak);
         d_tops.alloc((size_t)n_letters * 2 * sizeof(int4), live, peak);
         if (bound_stride) d_bound.alloc((size_t)grid * kSweepWaves * bound_stride * sizeof(int2), live, peak);
-        MGTA_HIP_CHECK(hipMemcpyAsync(d_seqs.p, seqs + offsets[0], n_letters, hipMemcpyHostToDevice, st));
-        MGTA_HIP_CHECK(hipMemcpyAsync(d_off.p, rel.data(), (size_t)(nn + 1) * 8, hipMemcpyHostToDevice, st));
         MGTA_HIP_CHECK(hipMemcpyAsync(d_rcls.p, rcls.data(), (size_t)nc * 2, hipMemcpyHostToDevice, st));
         MGTA_HIP_CHECK(hipMemcpyAsync(d_seg.p, seg.data(), (size_t)n_seg * sizeof(uint2), hipMemcpyHostToDevice, st));
         MGTA_HIP_CHECK(hipMemcpyAsync(d_segref.p, segref.data(), (size_t)n_seg * 4, hipMemcpyHostToDevice, st));
         MGTA_HIP_CHECK(hipMemcpyAsync(d_items.p, items.data(), (size_t)n_items * sizeof(ChimItem), hipMemcpyHostToDevice, st));
         MGTA_HIP_CHECK(hipMemcpyAsync(d_sub.p, sub, 27 * 27, hipMemcpyHostToDevice, st));
         MGTA_HIP_CHECK(hipMemcpyAsync(d_nz.p, nz_ref.data(), nz_ref.size() * 4, hipMemcpyHostToDevice, st));
-        MGTA_HIP_CHECK(hipMemsetAsync(d_head.p, 0, 64, st));
+        dev.reset_head(st);
 
         ChimArgs sa;
         memset(&sa, 0, sizeof sa);
-        sa.seqs = d_seqs.as<uint8_t>(); sa.off = d_off.as<uint64_t>(); sa.rcls = d_rcls.as<uint8_t>(); sa.seg = d_seg.as<uint2>(); sa.segref = d_segref.as<uint32_t>();
+        sa.seqs = dev.seqs.as<uint8_t>(); sa.off = dev.off.as<uint64_t>(); sa.rcls = d_rcls.as<uint8_t>(); sa.seg = d_seg.as<uint2>(); sa.segref = d_segref.as<uint32_t>();
         sa.items = d_items.as<ChimItem>(); sa.sub = d_sub.as<int8_t>(); sa.go = gap_open; sa.ge = gap_extend; sa.n_items = n_items; sa.n_rows = n_letters;
-        sa.part = d_part.as<int4>(); sa.bound = bound_stride ? d_bound.as<int2>() : nullptr; sa.bound_stride = bound_stride; sa.head = d_head.as<unsigned long long>();
+        sa.part = d_part.as<int4>(); sa.bound = bound_stride ? d_bound.as<int2>() : nullptr; sa.bound_stride = bound_stride; sa.head = dev.head.as<unsigned long long>();
         Timer t_top(st), t_par(st);
         t_top.start();
         launch_sweep<0>(ctx, sa, grid);
@@ -425,7 +374,12 @@ int mgta_seqs_chimera(mgta_ctx *ctx, const char *seqs, const uint64_t *offsets, 
             c.par[0] = recs[i].ref >= 0 ? recs[i].ref : c.pair.lref; c.par[1] = c.pair.lref; c.par[2] = c.pair.rref;
             checked.push_back(c);
         }
-        std::stable_sort(checked.begin(), checked.end(), [&](const Checked &x, const Checked &y) { return rel[x.idx + 1] - rel[x.idx] > rel[y.idx + 1] - rel[y.idx]; });
+        {                                                                 // longest first
+            std::vector<Checked> sorted;
+            sorted.reserve(checked.size());
+            for (uint32_t q : longest_first((uint32_t)checked.size(), [&](uint32_t q) { return rel[checked[q].idx + 1] - rel[checked[q].idx]; })) sorted.push_back(checked[q]);
+            checked.swap(sorted);
+        }
 
         // step 4: the rows' maxima over N, A, B in both directions
         double ms_par = 0;
@@ -459,7 +413,7 @@ int mgta_seqs_chimera(mgta_ctx *ctx, const char *seqs, const uint64_t *offsets, 
             MGTA_HIP_CHECK(hipMemcpyAsync(d_pseg.p, pseg.data(), pseg.size() * sizeof(uint2), hipMemcpyHostToDevice, st));
             MGTA_HIP_CHECK(hipMemcpyAsync(d_psegref.p, psegref.data(), psegref.size() * 4, hipMemcpyHostToDevice, st));
             MGTA_HIP_CHECK(hipMemcpyAsync(d_pitems.p, pitems.data(), pitems.size() * sizeof(ChimItem), hipMemcpyHostToDevice, st));
-            MGTA_HIP_CHECK(hipMemsetAsync(d_head.p, 0, 64, st));
+            dev.reset_head(st);
             ChimArgs pa = sa;
             pa.seg = d_pseg.as<uint2>(); pa.segref = d_psegref.as<uint32_t>(); pa.items = d_pitems.as<ChimItem>(); pa.n_items = pitems.size();
             pa.part = nullptr; pa.rowmax = d_rowmax.as<int32_t>();

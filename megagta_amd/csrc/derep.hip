@@ -23,8 +23,7 @@
 #include <algorithm>
 #include <vector>
 
-#include "common.hpp"
-#include "device_utils.hpp"
+#include "seq_dp.hpp"
 
 namespace mgta {
 namespace {
@@ -293,18 +292,11 @@ int mgta_ctx_set_derep_hash_bits(mgta_ctx *ctx, int bits) {
 int mgta_seqs_derep(mgta_ctx *ctx, const char *seqs, const uint64_t *offsets, int64_t n, uint8_t *status, int64_t *rep, uint32_t *copies, mgta_derep_stats *stats) {
     if (!ctx) { set_error("mgta_seqs_derep: ctx must not be NULL"); return MGTA_EINVAL; }
     if (n < 0) { set_error("mgta_seqs_derep: n = %lld must not be negative", (long long)n); return MGTA_EINVAL; }
-    if (n >= (1ll << 31)) { set_error("mgta_seqs_derep: n = %lld (the limit is n < 2^31 sequences)", (long long)n); return MGTA_EINVAL; }
+    if (!check_seq_count("mgta_seqs_derep", kSequences, n)) return MGTA_EINVAL;
     if (n > 0 && !offsets) { set_error("mgta_seqs_derep: offsets must not be NULL"); return MGTA_EINVAL; }
     if (n > 0 && (!status || !rep || !copies)) { set_error("mgta_seqs_derep: status, rep and copies must not be NULL"); return MGTA_EINVAL; }
-    for (int64_t i = 0; i < n; ++i) {
-        if (offsets[i + 1] < offsets[i]) { set_error("mgta_seqs_derep: sequence %lld: offsets must ascend", (long long)i); return MGTA_EINVAL; }
-        if (offsets[i + 1] - offsets[i] >= (1ull << 32)) {
-            set_error("mgta_seqs_derep: sequence %lld holds %llu letters (the limit is < 2^32 letters in the first occurrences)", (long long)i,
-                      (unsigned long long)(offsets[i + 1] - offsets[i]));
-            return MGTA_EINVAL;
-        }
-    }
-    if (n > 0 && offsets[n] > offsets[0] && !seqs) { set_error("mgta_seqs_derep: seqs must not be NULL"); return MGTA_EINVAL; }
+    if (!check_seq_offsets("mgta_seqs_derep", kSequences, offsets, n, 0xFFFFFFFFull, "letters", "< 2^32 letters in the first occurrences")) return MGTA_EINVAL;
+    if (!check_seq_letters("mgta_seqs_derep", kSequences, seqs, n > 0 ? offsets[n] - offsets[0] : 0)) return MGTA_EINVAL;
     if (stats) memset(stats, 0, sizeof(*stats));
     if (n == 0) return MGTA_OK;
     return guarded("mgta_seqs_derep", [&]() {
@@ -325,8 +317,7 @@ int mgta_seqs_derep(mgta_ctx *ctx, const char *seqs, const uint64_t *offsets, in
         d_off.alloc((size_t)(nn + 1) * 8, live, peak);
         d_rep.alloc((size_t)nn * 4, live, peak);
         d_cop.alloc((size_t)nn * 4, live, peak);
-        std::vector<uint64_t> rel((size_t)nn + 1);
-        for (uint32_t i = 0; i <= nn; ++i) rel[i] = offsets[i] - offsets[0];
+        const std::vector<uint64_t> rel = rel_offsets(offsets, n);
         if (n_letters) MGTA_HIP_CHECK(hipMemcpyAsync(d_all.p, seqs + offsets[0], n_letters, hipMemcpyHostToDevice, st));
         MGTA_HIP_CHECK(hipMemsetAsync(d_all.as<uint8_t>() + n_letters, 0, 32, st));
         MGTA_HIP_CHECK(hipMemcpyAsync(d_off.p, rel.data(), (size_t)(nn + 1) * 8, hipMemcpyHostToDevice, st));

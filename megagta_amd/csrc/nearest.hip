@@ -33,21 +33,15 @@
 //
 // Walk (nearest_trace_kernel).  One thread per pair walks the bytes back from (L, lowest end column) and writes the record and the path.
 #include <algorithm>
-#include <numeric>
 #include <vector>
 
-#include "common.hpp"
-#include "device_utils.hpp"
+#include "seq_dp.hpp"
 
 namespace mgta {
 namespace {
 
 constexpr int kNearestMaxLen = 4096;                // residues of a contig or a reference: 9 bytes of LDS per row of the wave that owns the contig
 constexpr size_t kNearestLdsBudget = 80 * 1024;     // of a workgroup: two fit a CU
-constexpr int kSubLdsBytes = 27 * 32;               // sub[reference class][contig class], rows padded to 32
-constexpr int32_t kUndef = -(1 << 30);
-constexpr int32_t kDefinedFloor = -(1 << 29);
-constexpr int kFirstColumn = 32;                    // bit of a column's byte: the first column of its reference (bits 0-4: the class)
 
 struct SweepArgs {
     const uint8_t *seqs;         // the letters of every contig
@@ -73,14 +67,6 @@ struct SweepArgs {
     unsigned long long *head;
 };
 
-__device__ __forceinline__ uint32_t residue_class(uint32_t b) {           // 1 .. 26 for an ASCII letter of either case, else 0
-    const uint32_t c = (b | 32u) - 'a';
-    return (b < 128u && c < 26u) ? c + 1u : 0u;
-}
-
-// lane l takes v of lane l - 1, lane 0 keeps `first`: one v_mov_b32 with the DPP control wave_shr:1
-__device__ __forceinline__ int32_t from_left(int32_t v, int32_t first) { return __builtin_amdgcn_update_dpp(first, v, 0x138, 0xF, 0xF, false); }
-
 __device__ __forceinline__ unsigned long long wave_max_u64(unsigned long long v) {
 #pragma unroll
     for (int d = 32; d > 0; d >>= 1) {
@@ -99,18 +85,12 @@ __global__ __launch_bounds__(256) void nearest_sweep_kernel(SweepArgs a) {
     const int n_waves = blockDim.x >> 6;
     int2 *s_bound = reinterpret_cast<int2 *>(lds_raw + kSubLdsBytes) + (size_t)wave_id() * a.rows_lds;
     uint8_t *s_x = lds_raw + kSubLdsBytes + (size_t)n_waves * a.rows_lds * 8 + (size_t)wave_id() * a.rows_lds;
-    for (int c = threadIdx.x; c < kSubLdsBytes; c += blockDim.x) {
-        const int cy = c >> 5, cx = c & 31;
-        s_sub[c] = cx < 27 ? a.sub[cx * 27 + cy] : (int8_t)0;
-    }
-    __syncthreads();
+    stage_sub(s_sub, a.sub);
     const int lane = lane_id();
     const int32_t go = a.go, ge = a.ge;
 
     for (;;) {
-        // every lane takes part and only lane 0 counts (as align_fill_kernel does: no leader-only branch in front of the wave-wide read)
-        unsigned long long k = atomicAdd(a.head, lane == 0 ? 1ull : 0ull);
-        k = wave_uniform((uint64_t)k);
+        const unsigned long long k = next_item(a.head);
         if (k >= a.n_items) break;
         uint32_t idx, c0, c1;
         if (MODE == 2) {
@@ -214,11 +194,6 @@ struct WalkArgs {
     int32_t *path_len;           // [count] (with path)
 };
 
-__device__ __forceinline__ uint8_t nearest_tb_at(const uint8_t *tb, int L, int R, int i, int j) {
-    const int s = (j - 1) >> 6, l = (j - 1) & 63, w = min(64, R - 64 * s);
-    return tb[(size_t)s * 64 * L + (size_t)((i - 1 + l) % L) * w + l];
-}
-
 __global__ __launch_bounds__(256) void nearest_trace_kernel(WalkArgs a) {
     const uint32_t k = blockIdx.x * 256 + threadIdx.x;
     if (k >= a.count) return;
@@ -232,53 +207,16 @@ __global__ __launch_bounds__(256) void nearest_trace_kernel(WalkArgs a) {
     if (L > 0 && R > 0 && score >= kDefinedFloor) {
         const uint8_t *x = a.seqs + o0;
         const uint8_t *y = a.rcls + a.pair_c0[k];
-        const uint8_t *tb = a.tb + a.cell_base[k];
-        char *slot = a.path ? a.path + a.path_base[k] : nullptr;
-        const int slot_len = L + R;
-        int i = L, j = a.jend[k], state = 0;
-        r.status = 0; r.score = score; r.ref_to = j;
-        // every step consumes a residue or a column: at most L + R of them
-        for (int guard = 0; guard < L + R && i >= 1 && j >= 1 && j <= R; ++guard) {
-            if (slot) slot[slot_len - 1 - plen] = state == 0 ? 'M' : state == 1 ? 'I' : 'D';
-            ++plen;
-            if (state == 0) {
-                ++r.n_match;
-                const uint32_t cx = residue_class(x[i - 1]), cy = y[j - 1] & 31u;
-                r.n_ident += cx == cy && cx != 0;
-                r.ref_from = j;
-                if (i == 1) break;
-                if (j == 1) break;                                        // (not reached: M[i > 1][1] is undefined)
-                state = nearest_tb_at(tb, L, R, i - 1, j - 1) & 3;
-                --i; --j;
-            } else if (state == 1) {
-                ++r.n_insert;
-                if (i == 1) break;                                        // (not reached: X[1][.] is undefined)
-                state = (nearest_tb_at(tb, L, R, i - 1, j) & 8) ? 1 : 0;
-                --i;
-            } else {
-                ++r.n_delete;
-                if (j == 1) break;                                        // (not reached: Y[.][1] is undefined)
-                state = (nearest_tb_at(tb, L, R, i, j - 1) & 4) ? 2 : 0;
-                --j;
-            }
-        }
-        if (slot)
-            for (int p = 0; p < plen; ++p) slot[p] = slot[slot_len - plen + p];   // forwards: the source is never behind the target
+        int n_ident = 0;
+        const Walked w = trace_walk(a.tb + a.cell_base[k], L, R, a.jend[k], a.path ? a.path + a.path_base[k] : nullptr, [&](int i, int j) {
+            const uint32_t cx = residue_class(x[i - 1]), cy = y[j - 1] & 31u;
+            n_ident += cx == cy && cx != 0;
+        });
+        r.status = 0; r.score = score; r.ref_to = a.jend[k]; r.ref_from = w.from; r.n_match = w.n_match; r.n_ident = n_ident; r.n_insert = w.n_insert; r.n_delete = w.n_delete;
+        plen = w.plen;
     }
     a.recs[k] = r;
     if (a.path_len) a.path_len[k] = plen;
-}
-
-template <int MODE> void launch_sweep(mgta_ctx *ctx, const SweepArgs &a, int waves, size_t lds, uint64_t n_items, int *blocks_per_cu, unsigned *grid_out) {
-    MGTA_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void *>(nearest_sweep_kernel<MODE>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-    // workgroups a CU holds at once: what the runtime answers for these registers and this LDS (never assumed)
-    int bpc = 0;
-    MGTA_HIP_CHECK(hipOccupancyMaxActiveBlocksPerMultiprocessor(&bpc, nearest_sweep_kernel<MODE>, waves * 64, lds));
-    bpc = std::max(1, bpc);
-    const unsigned grid = (unsigned)std::max<uint64_t>(1, std::min<uint64_t>((uint64_t)ctx->num_cus * (uint64_t)bpc, (n_items + waves - 1) / waves));
-    hipLaunchKernelGGL(nearest_sweep_kernel<MODE>, dim3(grid), dim3(waves * 64), lds, ctx->stream, a);
-    MGTA_HIP_CHECK(hipGetLastError());
-    *blocks_per_cu = bpc; *grid_out = grid;
 }
 
 }  // namespace
@@ -301,8 +239,8 @@ int mgta_seqs_nearest(mgta_ctx *ctx, const char *seqs, const uint64_t *offsets, 
     if (!ctx) { set_error("mgta_seqs_nearest: ctx must not be NULL"); return MGTA_EINVAL; }
     if (n < 0) { set_error("mgta_seqs_nearest: n = %lld must not be negative", (long long)n); return MGTA_EINVAL; }
     if (n_ref < 0) { set_error("mgta_seqs_nearest: n_ref = %lld must not be negative", (long long)n_ref); return MGTA_EINVAL; }
-    if (n >= (1ll << 31)) { set_error("mgta_seqs_nearest: n = %lld (the limit is n < 2^31 contigs)", (long long)n); return MGTA_EINVAL; }
-    if (n_ref >= (1ll << 31)) { set_error("mgta_seqs_nearest: n_ref = %lld (the limit is n_ref < 2^31 references)", (long long)n_ref); return MGTA_EINVAL; }
+    if (!check_seq_count("mgta_seqs_nearest", kContigs, n)) return MGTA_EINVAL;
+    if (!check_seq_count("mgta_seqs_nearest", kReferences, n_ref)) return MGTA_EINVAL;
     if (gap_extend < 0 || gap_extend > gap_open || gap_open > 1024) {
         set_error("mgta_seqs_nearest: gap_open = %d, gap_extend = %d (the rule needs 0 <= gap_extend <= gap_open <= 1024)", gap_open, gap_extend);
         return MGTA_EINVAL;
@@ -312,29 +250,12 @@ int mgta_seqs_nearest(mgta_ctx *ctx, const char *seqs, const uint64_t *offsets, 
     if (n > 0 && !sub) { set_error("mgta_seqs_nearest: sub must not be NULL"); return MGTA_EINVAL; }
     if (n > 0 && n_ref > 0 && !ref_offsets) { set_error("mgta_seqs_nearest: ref_offsets must not be NULL"); return MGTA_EINVAL; }
     if (n > 0 && path && !path_len) { set_error("mgta_seqs_nearest: path_len must not be NULL when path is given"); return MGTA_EINVAL; }
-    for (int64_t i = 0; i < n; ++i) {
-        if (offsets[i + 1] < offsets[i]) { set_error("mgta_seqs_nearest: contig %lld: offsets must ascend", (long long)i); return MGTA_EINVAL; }
-        if (offsets[i + 1] - offsets[i] > (uint64_t)kNearestMaxLen) {
-            set_error("mgta_seqs_nearest: contig %lld holds %llu residues (the limit is %d residues per contig)", (long long)i,
-                      (unsigned long long)(offsets[i + 1] - offsets[i]), kNearestMaxLen);
-            return MGTA_EINVAL;
-        }
-    }
-    for (int64_t i = 0; n > 0 && i < n_ref; ++i) {
-        if (ref_offsets[i + 1] < ref_offsets[i]) { set_error("mgta_seqs_nearest: reference %lld: ref_offsets must ascend", (long long)i); return MGTA_EINVAL; }
-        if (ref_offsets[i + 1] - ref_offsets[i] > (uint64_t)kNearestMaxLen) {
-            set_error("mgta_seqs_nearest: reference %lld holds %llu residues (the limit is %d residues per reference)", (long long)i,
-                      (unsigned long long)(ref_offsets[i + 1] - ref_offsets[i]), kNearestMaxLen);
-            return MGTA_EINVAL;
-        }
-    }
+    if (!check_seq_offsets("mgta_seqs_nearest", kContigs, offsets, n, kNearestMaxLen)) return MGTA_EINVAL;
+    if (!check_seq_offsets("mgta_seqs_nearest", kReferences, ref_offsets, n > 0 ? n_ref : 0, kNearestMaxLen)) return MGTA_EINVAL;
     const uint64_t n_letters = n > 0 ? offsets[n] - offsets[0] : 0, n_cols = (n > 0 && n_ref > 0) ? ref_offsets[n_ref] - ref_offsets[0] : 0;
-    if (n_cols >= (1ull << 31)) {
-        set_error("mgta_seqs_nearest: the references hold %llu residues together (the limit is fewer than 2^31 residues in all references)", (unsigned long long)n_cols);
-        return MGTA_EINVAL;
-    }
-    if (n_letters && !seqs) { set_error("mgta_seqs_nearest: seqs must not be NULL"); return MGTA_EINVAL; }
-    if (n_cols && !refs) { set_error("mgta_seqs_nearest: refs must not be NULL"); return MGTA_EINVAL; }
+    if (!check_ref_columns("mgta_seqs_nearest", n_cols)) return MGTA_EINVAL;
+    if (!check_seq_letters("mgta_seqs_nearest", kContigs, seqs, n_letters)) return MGTA_EINVAL;
+    if (!check_seq_letters("mgta_seqs_nearest", kReferences, refs, n_cols)) return MGTA_EINVAL;
     if (stats) memset(stats, 0, sizeof(*stats));
     if (n == 0) return MGTA_OK;
     return guarded("mgta_seqs_nearest", [&]() {
@@ -356,30 +277,16 @@ int mgta_seqs_nearest(mgta_ctx *ctx, const char *seqs, const uint64_t *offsets, 
         MGTA_HIP_CHECK(hipSetDevice(ctx->device));
         hipStream_t st = ctx->stream;
         uint64_t *live = &ctx->live_bytes, *peak = &ctx->peak_bytes;
-        struct PeakOfCall {                                               // peak_bytes is this call's while it runs, the context's again on every way out
-            uint64_t *peak, before;
-            ~PeakOfCall() { *peak = std::max(*peak, before); }
-        } peak_of_call{peak, *peak};
-        *peak = *live;
+        PeakOfCall peak_of_call(ctx);
 
         // the contigs: letters, where they start, longest first
-        std::vector<uint64_t> rel((size_t)nn + 1);
-        for (uint32_t i = 0; i <= nn; ++i) rel[i] = offsets[i] - offsets[0];
-        std::vector<uint32_t> order(nn);
-        std::iota(order.begin(), order.end(), 0u);
-        std::stable_sort(order.begin(), order.end(), [&](uint32_t x, uint32_t y) { return rel[x + 1] - rel[x] > rel[y + 1] - rel[y]; });
+        const std::vector<uint64_t> rel = rel_offsets(offsets, n);
+        const std::vector<uint32_t> order = longest_first(rel);
         // the columns: class and first-column bit; where every reference starts
         const uint32_t nc = (uint32_t)n_cols;
-        std::vector<uint32_t> rstart((size_t)n_ref + 1);
-        for (int64_t r = 0; r <= n_ref; ++r) rstart[(size_t)r] = (uint32_t)(ref_offsets[r] - ref_offsets[0]);
-        std::vector<uint8_t> rcls(nc);
-        const unsigned char *rtext = reinterpret_cast<const unsigned char *>(refs) + ref_offsets[0];
-        for (uint32_t g = 0; g < nc; ++g) {
-            const uint32_t b = rtext[g], c = (b | 32u) - 'a';
-            rcls[g] = (uint8_t)((b < 128u && c < 26u) ? c + 1u : 0u);
-        }
-        for (int64_t r = 0; r < n_ref; ++r)
-            if (rstart[(size_t)r + 1] > rstart[(size_t)r]) rcls[rstart[(size_t)r]] |= kFirstColumn;
+        std::vector<uint32_t> rstart;
+        std::vector<uint8_t> rcls;
+        ref_columns(refs, ref_offsets, n_ref, rstart, rcls);
         // segments: whole references, enough of them that (contig, segment) items fill the device when the contigs are few
         const uint64_t want_items = (uint64_t)ctx->num_cus * 32;
         const uint64_t want_seg = std::max<uint64_t>(1, std::min<uint64_t>((want_items + nn - 1) / nn, std::max<uint64_t>(1, n_cols / 1024)));
@@ -393,26 +300,20 @@ int mgta_seqs_nearest(mgta_ctx *ctx, const char *seqs, const uint64_t *offsets, 
 
         const uint32_t l_max = (uint32_t)(rel[order[0] + 1] - rel[order[0]]);
         const uint32_t rows_lds = (std::max(1u, l_max) + 7u) & ~7u;
-        int waves = 4;
-        while (waves > 1 && kSubLdsBytes + (size_t)waves * rows_lds * 9 > kNearestLdsBudget) waves >>= 1;
+        const int waves = waves_that_fit(rows_lds, 9, kSubLdsBytes, kNearestLdsBudget);
         const size_t lds = kSubLdsBytes + (size_t)waves * rows_lds * 9;
 
-        DevBuf d_seqs, d_off, d_order, d_rcls, d_seg, d_sub, d_head, d_keys, d_colref, d_scores;
-        d_seqs.alloc(n_letters + 16, live, peak);
-        d_off.alloc((size_t)(nn + 1) * 8, live, peak);
-        d_order.alloc((size_t)nn * 4, live, peak);
+        SeqStage dev;
+        dev.upload(ctx, seqs, offsets, rel, &order);
+        DevBuf d_rcls, d_seg, d_sub, d_keys, d_colref, d_scores;
         d_rcls.alloc((size_t)nc + 16, live, peak);
         d_seg.alloc((size_t)(n_seg + 1) * 4, live, peak);
         d_sub.alloc(27 * 27, live, peak);
-        d_head.alloc(64, live, peak);
         d_keys.alloc((size_t)n_items * 8, live, peak);
-        MGTA_HIP_CHECK(hipMemcpyAsync(d_seqs.p, seqs + offsets[0], n_letters, hipMemcpyHostToDevice, st));
-        MGTA_HIP_CHECK(hipMemcpyAsync(d_off.p, rel.data(), (size_t)(nn + 1) * 8, hipMemcpyHostToDevice, st));
-        MGTA_HIP_CHECK(hipMemcpyAsync(d_order.p, order.data(), (size_t)nn * 4, hipMemcpyHostToDevice, st));
         MGTA_HIP_CHECK(hipMemcpyAsync(d_rcls.p, rcls.data(), nc, hipMemcpyHostToDevice, st));
         MGTA_HIP_CHECK(hipMemcpyAsync(d_seg.p, seg.data(), (size_t)(n_seg + 1) * 4, hipMemcpyHostToDevice, st));
         MGTA_HIP_CHECK(hipMemcpyAsync(d_sub.p, sub, 27 * 27, hipMemcpyHostToDevice, st));
-        MGTA_HIP_CHECK(hipMemsetAsync(d_head.p, 0, 64, st));
+        dev.reset_head(st);
         std::vector<int32_t> col_ref;
         if (scores) {
             col_ref.resize(nc);
@@ -425,16 +326,13 @@ int mgta_seqs_nearest(mgta_ctx *ctx, const char *seqs, const uint64_t *offsets, 
 
         SweepArgs sa;
         memset(&sa, 0, sizeof sa);
-        sa.seqs = d_seqs.as<uint8_t>(); sa.off = d_off.as<uint64_t>(); sa.order = d_order.as<uint32_t>(); sa.rcls = d_rcls.as<uint8_t>(); sa.seg = d_seg.as<uint32_t>();
+        sa.seqs = dev.seqs.as<uint8_t>(); sa.off = dev.off.as<uint64_t>(); sa.order = dev.order.as<uint32_t>(); sa.rcls = d_rcls.as<uint8_t>(); sa.seg = d_seg.as<uint32_t>();
         sa.col_ref = d_colref.as<int32_t>(); sa.sub = d_sub.as<int8_t>(); sa.go = gap_open; sa.ge = gap_extend; sa.n_items = n_items; sa.n_seg = n_seg;
         sa.n_ref = (uint64_t)n_ref; sa.keys = d_keys.as<unsigned long long>(); sa.scores = d_scores.as<int32_t>(); sa.rows_lds = rows_lds;
-        sa.head = d_head.as<unsigned long long>();
+        sa.head = dev.head.as<unsigned long long>();
         Timer t_score(st), t_trace(st);
-        int blocks_per_cu = 0;
-        unsigned grid = 0;
         t_score.start();
-        if (scores) launch_sweep<1>(ctx, sa, waves, lds, n_items, &blocks_per_cu, &grid);
-        else launch_sweep<0>(ctx, sa, waves, lds, n_items, &blocks_per_cu, &grid);
+        const WaveLaunch sweep = launch_waves(ctx, scores ? nearest_sweep_kernel<1> : nearest_sweep_kernel<0>, sa, waves, lds, n_items);
         t_score.end();
         std::vector<unsigned long long> keys((size_t)n_items);
         MGTA_HIP_CHECK(hipMemcpyAsync(keys.data(), d_keys.p, (size_t)n_items * 8, hipMemcpyDeviceToHost, st));
@@ -461,37 +359,24 @@ int mgta_seqs_nearest(mgta_ctx *ctx, const char *seqs, const uint64_t *offsets, 
         }
         const uint32_t n_al = (uint32_t)t_order.size();
 
-        // cells of a batch: the switch, or half of what the context may still take (one traceback byte per cell)
-        uint64_t cap = ctx->nearest_batch_cells;
-        if (!cap) {
-            size_t free_b = 0, total_b = 0;
-            MGTA_HIP_CHECK(hipMemGetInfo(&free_b, &total_b));
-            uint64_t avail = free_b;
-            if (ctx->mem_limit) avail = std::min<uint64_t>(avail, ctx->mem_limit > ctx->live_bytes ? ctx->mem_limit - ctx->live_bytes : 0);
-            cap = std::max<uint64_t>(avail / 2, 1);
-        }
+        const uint64_t cap = batch_cap(ctx, ctx->nearest_batch_cells, 1);    // one traceback byte per cell
         double ms_trace = 0;
         int64_t n_batches = 0, n_trace_cells = 0;
-        if (n_al) MGTA_HIP_CHECK(hipMemcpyAsync(d_order.p, t_order.data(), (size_t)n_al * 4, hipMemcpyHostToDevice, st));
+        if (n_al) MGTA_HIP_CHECK(hipMemcpyAsync(dev.order.p, t_order.data(), (size_t)n_al * 4, hipMemcpyHostToDevice, st));
         std::vector<uint64_t> cell_base, path_base;
         std::vector<uint32_t> pair_c0, pair_w;
         std::vector<mgta_nearest_rec> h_recs;
         std::vector<char> h_path;
         std::vector<int32_t> h_plen;
         for (uint32_t b0 = 0; b0 < n_al;) {
-            // the batch [b0, b1): at least one pair
-            uint32_t b1 = b0;
+            // the batch [b0, b1): a pair is a contig and its nearest reference
             uint64_t cells = 0, path_bytes = 0;
-            cell_base.clear(); path_base.clear(); pair_c0.clear(); pair_w.clear();
-            while (b1 < n_al) {
-                const uint32_t idx = t_order[b1], r = near_ref[idx];
-                const uint64_t L = rel[idx + 1] - rel[idx], R = rstart[r + 1] - rstart[r];
-                if (b1 > b0 && cells + L * R > cap) break;
-                cell_base.push_back(cells); path_base.push_back(path_bytes); pair_c0.push_back(rstart[r]); pair_w.push_back((uint32_t)R);
-                cells += L * R; path_bytes += L + R;
-                ++b1;
-            }
+            const auto ref_of = [&](uint32_t k) { return near_ref[t_order[k]]; };
+            const uint32_t b1 = cut_cells(b0, n_al, cap, [&](uint32_t k) { return rel[t_order[k] + 1] - rel[t_order[k]]; },
+                                          [&](uint32_t k) { return (uint64_t)(rstart[ref_of(k) + 1] - rstart[ref_of(k)]); }, cell_base, &path_base, &cells, &path_bytes);
             const uint32_t count = b1 - b0;
+            pair_c0.clear(); pair_w.clear();
+            for (uint32_t k = b0; k < b1; ++k) { pair_c0.push_back(rstart[ref_of(k)]); pair_w.push_back(rstart[ref_of(k) + 1] - rstart[ref_of(k)]); }
             DevBuf d_tb, d_cbase, d_pbase, d_c0, d_w, d_score, d_jend, d_recs, d_path, d_plen;
             d_tb.alloc(cells + 16, live, peak);
             d_cbase.alloc((size_t)count * 8, live, peak);
@@ -509,16 +394,14 @@ int mgta_seqs_nearest(mgta_ctx *ctx, const char *seqs, const uint64_t *offsets, 
                 d_plen.alloc((size_t)count * 4, live, peak);
                 MGTA_HIP_CHECK(hipMemcpyAsync(d_pbase.p, path_base.data(), (size_t)count * 8, hipMemcpyHostToDevice, st));
             }
-            MGTA_HIP_CHECK(hipMemsetAsync(d_head.p, 0, 64, st));
+            dev.reset_head(st);
 
             SweepArgs fa = sa;
-            fa.order = d_order.as<uint32_t>() + b0; fa.seg = nullptr; fa.col_ref = nullptr; fa.keys = nullptr; fa.scores = nullptr; fa.n_seg = 1;
+            fa.order = dev.order.as<uint32_t>() + b0; fa.seg = nullptr; fa.col_ref = nullptr; fa.keys = nullptr; fa.scores = nullptr; fa.n_seg = 1;
             fa.pair_c0 = d_c0.as<uint32_t>(); fa.pair_w = d_w.as<uint32_t>(); fa.cell_base = d_cbase.as<uint64_t>(); fa.n_items = count;
             fa.tb = d_tb.as<uint8_t>(); fa.score = d_score.as<int32_t>(); fa.jend = d_jend.as<int32_t>();
-            int bpc2 = 0;
-            unsigned grid2 = 0;
             t_trace.start();
-            launch_sweep<2>(ctx, fa, waves, lds, count, &bpc2, &grid2);
+            launch_waves(ctx, nearest_sweep_kernel<2>, fa, waves, lds, count);
             WalkArgs wa;
             wa.seqs = fa.seqs; wa.off = fa.off; wa.order = fa.order; wa.rcls = fa.rcls; wa.pair_c0 = fa.pair_c0; wa.pair_w = fa.pair_w; wa.cell_base = fa.cell_base;
             wa.path_base = d_pbase.as<uint64_t>(); wa.count = count; wa.tb = fa.tb; wa.score = fa.score; wa.jend = fa.jend; wa.recs = d_recs.as<mgta_nearest_rec>();
@@ -555,7 +438,7 @@ int mgta_seqs_nearest(mgta_ctx *ctx, const char *seqs, const uint64_t *offsets, 
         }
         if (stats) {
             stats->n_unaligned = n - (int64_t)n_al; stats->n_trace_cells = n_trace_cells; stats->n_batches = n_batches; stats->n_segments = n_seg;
-            stats->blocks_per_cu = blocks_per_cu; stats->waves_per_block = waves; stats->grid_blocks = grid; stats->lds_bytes = (int64_t)lds;
+            stats->blocks_per_cu = sweep.blocks_per_cu; stats->waves_per_block = waves; stats->grid_blocks = sweep.grid; stats->lds_bytes = (int64_t)lds;
             stats->peak_bytes = (int64_t)ctx->peak_bytes; stats->ms_score = ms_score; stats->ms_trace = ms_trace;
         }
         return (int)MGTA_OK;

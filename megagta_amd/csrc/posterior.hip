@@ -2,15 +2,9 @@
 // placement of mgta_seqs_align can be trusted.  The rule is this library's own (include/megagta_hip.h): mgta_seqs_align's cells with
 // every max replaced by log-sum-exp, fp64, a backward sweep over the same cells, posterior = exp(forward + backward - F).
 //
-// Forward.  align_fill_kernel's scheme: one wave owns a sequence; waves take sequences longest first from one atomic head.  Lanes own
-// model columns, 64 at a time (a strip); at step t of a strip lane l computes row i = t - l + 1 of its column j.  Written from the
-// cell outwards: the lane of cell (i, j) holds the seven transitions out of node j and computes what its neighbours need,
-//     X = lse(FM + MM, FI + IM, FD + DM)   the sum into FM[i+1][j+1]  (taken by lane l + 1 two steps later)
-//     Y = lse(FM + MD, FD + DD)            FD[i][j+1]                 (taken by lane l + 1 at the next step)
-//     I = lse(FM + MI, FI + II)            FI[i+1][j]                 (its own next step)
-// X and Y move to lane l + 1 by a cross-lane move; the last lane of a strip leaves them per row in LDS for lane 0 of the next strip
-// (one wave, LDS in program order: row i is read before the rows <= i - 62 are written, in place).  FM and FI of every cell are
-// stored, two planes of doubles, a strip of width w at ((i - 1 + l) mod L) * w + l: a step's lanes write one run.  FD is not kept.
+// Forward.  align_fill_kernel's scheme on the same sweep (profile_forward, seq_dp.hpp) with ForwardCell: X, Y and I are log-sum-exps,
+// and FM and FI of every cell are stored, two planes of doubles, a strip of width w at ((i - 1 + l) mod L) * w + l: a step's lanes
+// write one run.  FD is not kept.
 //
 // Backward.  The mirror: strips from the last to the first, at step t lane l computes row i = L - t + (w - 1 - l), the neighbour is
 // column j + 1 (lane l + 1, or LDS across a strip edge: lane 0 writes row i while lane 63 reads the rows <= i - 62).  Every
@@ -26,21 +20,16 @@
 // exponentials and one logarithm are evaluated.  m = -inf gives -inf and -inf - -inf is never evaluated.
 #include <algorithm>
 #include <cmath>
-#include <numeric>
 #include <vector>
 
-#include "common.hpp"
-#include "device_utils.hpp"
+#include "seq_dp.hpp"
 
 namespace mgta {
 namespace {
 
 constexpr int kPostMaxLen = 4096;                  // residues of one sequence: 20 bytes of LDS per row of the wave that owns it
 constexpr size_t kPostLdsBudget = 82 * 1024;       // of a workgroup: the longest sequence alone (4096 * 20 + 128 bytes) still fits
-constexpr int kPostAlphaBytes = 128;
 constexpr uint64_t kPostCellBytes = 16;            // FM and FI of a cell
-
-__device__ __forceinline__ double neg_inf() { return -__builtin_huge_val(); }
 
 __device__ __forceinline__ double lse2(double a, double b) {
     const double m = fmax(a, b), lo = fmin(a, b);
@@ -81,30 +70,28 @@ struct PostArgs {
     unsigned long long *head;
 };
 
+// the cell of profile_forward (seq_dp.hpp): log-sum-exp, FM and FI of every cell stored in two planes of doubles
+struct ForwardCell {
+    double *pm, *pi, *pms, *pis;
+    int L;
+    double f_acc;                                                         // lse of this lane's FM[L][.] over the strips
+    __device__ __forceinline__ void strip(int s) { pms = pm + (size_t)s * 64 * L; pis = pi + (size_t)s * 64 * L; }
+    __device__ __forceinline__ double three(double a, double b, double c, uint32_t &) const { return lse3(a, b, c); }
+    __device__ __forceinline__ double two(double a, double b, uint32_t &, uint32_t) const { return lse2(a, b); }
+    __device__ __forceinline__ void store(size_t at, double v_m, double v_i, uint32_t) const { pms[at] = v_m; pis[at] = v_i; }
+    __device__ __forceinline__ void last_row(double v_m, int) { f_acc = lse2(f_acc, v_m); }
+};
+
 template <bool MSC_LDS>
 __global__ __launch_bounds__(256) void post_forward_kernel(PostArgs a) {
     extern __shared__ __align__(16) unsigned char lds_raw[];
-    // [alpha 128 B][boundary: waves x rows_lds x (X, Y)][msc (M+1)*A doubles when MSC_LDS]
-    int8_t *s_alpha = reinterpret_cast<int8_t *>(lds_raw);
-    const int n_waves = blockDim.x >> 6;
-    double *s_bound = reinterpret_cast<double *>(lds_raw + kPostAlphaBytes) + (size_t)wave_id() * a.rows_lds * 2;
-    double *s_msc = reinterpret_cast<double *>(lds_raw + kPostAlphaBytes) + (size_t)n_waves * a.rows_lds * 2;
-    const int M = a.M, A = a.A;
-    const size_t M1 = (size_t)M + 1;
-    for (int c = threadIdx.x; c < kPostAlphaBytes; c += blockDim.x) s_alpha[c] = a.alpha[c];
-    if (MSC_LDS)
-        for (size_t c = threadIdx.x; c < M1 * A; c += blockDim.x) s_msc[c] = a.tab[c];
-    __syncthreads();
-    const double *msc = MSC_LDS ? s_msc : a.tab;
-    const double *tsc = a.tab + M1 * A;
+    const size_t n_msc = ((size_t)a.M + 1) * a.A;
+    const ProfileLds lds = profile_lds<MSC_LDS>(lds_raw, a.rows_lds, a.tab, a.alpha, n_msc);
     const int lane = lane_id();
     const double NINF = neg_inf();
-    const int n_strips = (M + 63) / 64;
 
     for (;;) {
-        // every lane takes part and only lane 0 counts (align_fill_kernel: no branch on the lane in front of the wave-wide read)
-        unsigned long long k = atomicAdd(a.head, lane == 0 ? 1ull : 0ull);
-        k = wave_uniform((uint64_t)k);
+        const unsigned long long k = next_item(a.head);
         if (k >= a.count) break;
         const uint32_t idx = a.order[k];
         const uint64_t o0 = a.off[idx];
@@ -113,63 +100,9 @@ __global__ __launch_bounds__(256) void post_forward_kernel(PostArgs a) {
             if (lane == 0) a.fwd[k] = NINF;
             continue;
         }
-        const uint8_t *x = a.seqs + o0;
-        double *pm = a.fm + a.cell_base[k], *pi = a.fi + a.cell_base[k];
-        double f_acc = NINF;                                              // lse of this lane's FM[L][.] over the strips
-        for (int s = 0; s < n_strips; ++s) {
-            const int w = min(64, M - 64 * s);
-            const int j = 64 * s + lane + 1;
-            const bool own = lane < w;
-            const int jc = own ? j : M;                                   // (idle lanes read a valid node and store nothing)
-            const double tMM = tsc[0 * M1 + jc], tMI = tsc[1 * M1 + jc], tMD = tsc[2 * M1 + jc], tIM = tsc[3 * M1 + jc], tII = tsc[4 * M1 + jc],
-                         tDM = tsc[5 * M1 + jc], tDD = tsc[6 * M1 + jc];
-            const double *mrow = msc + (size_t)jc * A;
-            double *pms = pm + (size_t)s * 64 * L, *pis = pi + (size_t)s * 64 * L;
-            const bool last_strip = s == n_strips - 1;
-            double x_out = NINF, y_out = NINF, x_held = NINF, v_i = NINF;
-            const int n_steps = L + w - 1;
-            int t_mod = 0;                                                // t mod L
-            for (int t = 0; t < n_steps; ++t) {
-                const int i = t - lane + 1;                               // this lane's row
-                const bool valid = own && i >= 1 && i <= L;
-                // what the left neighbour computed at the last step: X of its row i (for this lane's row i + 1), Y = FD[i][j]
-                double x_new = __shfl_up(x_out, 1, 64), v_d = __shfl_up(y_out, 1, 64);
-                double x_use = x_held;
-                if (lane == 0) {
-                    const int r = min(max(i, 1), L) - 1;                  // = i - 1: lane 0 is valid at every step t < L
-                    const bool have = s > 0 && i <= L;
-                    x_use = have ? s_bound[2 * r] : NINF;
-                    v_d = have ? s_bound[2 * r + 1] : NINF;
-                }
-                x_held = x_new;
-                const int ii = min(max(i, 1), L);
-                const uint32_t c = x[ii - 1];
-                const int col = c < 127 ? (int)s_alpha[c] : -1;
-                const double e = col < 0 ? 0.0 : mrow[col];
-                if (i <= 1) { x_use = 0.0; v_i = NINF; v_d = NINF; }      // row 1: FM = e, no insert and no delete state
-                const double v_m = x_use + e;
-                const double X = lse3(v_m + tMM, v_i + tIM, v_d + tDM);
-                double Y = lse2(v_m + tMD, v_d + tDD);
-                if (i <= 1) Y = NINF;                                     // FD[1][.] does not exist
-                double I = lse2(v_m + tMI, v_i + tII);
-                if (j >= M) I = NINF;                                     // node M has no insert state
-                x_out = X; y_out = Y;
-                if (valid) {
-                    const size_t at = (size_t)t_mod * w + lane;           // (i - 1 + lane) mod L = t mod L
-                    pms[at] = v_m;
-                    pis[at] = v_i;
-                    v_i = I;
-                    if (i == L) f_acc = lse2(f_acc, v_m);
-                    if (!last_strip && lane == 63) {
-                        s_bound[2 * (i - 1) + 1] = Y;                     // FD[i][j + 1]
-                        if (i < L) s_bound[2 * i] = X;                    // the sum into FM[i + 1][j + 1]
-                    }
-                }
-                if (++t_mod == L) t_mod = 0;
-            }
-            wave_lds_fence();
-        }
-        const double F = wave_lse(f_acc);
+        ForwardCell cell{a.fm + a.cell_base[k], a.fi + a.cell_base[k], nullptr, nullptr, L, NINF};
+        profile_forward(a.seqs + o0, L, a.M, a.A, a.tab + n_msc, lds, cell);
+        const double F = wave_lse(cell.f_acc);
         if (lane == 0) a.fwd[k] = F;
     }
 }
@@ -177,19 +110,12 @@ __global__ __launch_bounds__(256) void post_forward_kernel(PostArgs a) {
 template <bool MSC_LDS>
 __global__ __launch_bounds__(256) void post_backward_kernel(PostArgs a) {
     extern __shared__ __align__(16) unsigned char lds_raw[];
-    // [alpha 128 B][boundary: waves x rows_lds x (N, BD)][msc (M+1)*A doubles when MSC_LDS][labels: waves x rows_lds x int32]
-    int8_t *s_alpha = reinterpret_cast<int8_t *>(lds_raw);
-    const int n_waves = blockDim.x >> 6;
+    // profile_lds' carve-up with (N, BD) in the boundary rows, and behind it [labels: waves x rows_lds x int32]
     const int M = a.M, A = a.A;
     const size_t M1 = (size_t)M + 1;
-    double *s_bound = reinterpret_cast<double *>(lds_raw + kPostAlphaBytes) + (size_t)wave_id() * a.rows_lds * 2;
-    double *s_msc = reinterpret_cast<double *>(lds_raw + kPostAlphaBytes) + (size_t)n_waves * a.rows_lds * 2;
-    int32_t *s_lab = reinterpret_cast<int32_t *>(s_msc + (MSC_LDS ? M1 * A : 0)) + (size_t)wave_id() * a.rows_lds;
-    for (int c = threadIdx.x; c < kPostAlphaBytes; c += blockDim.x) s_alpha[c] = a.alpha[c];
-    if (MSC_LDS)
-        for (size_t c = threadIdx.x; c < M1 * A; c += blockDim.x) s_msc[c] = a.tab[c];
-    __syncthreads();
-    const double *msc = MSC_LDS ? s_msc : a.tab;
+    const ProfileLds lds = profile_lds<MSC_LDS>(lds_raw, a.rows_lds, a.tab, a.alpha, M1 * A);
+    double *s_bound = lds.bound;
+    int32_t *s_lab = reinterpret_cast<int32_t *>(lds.past) + (size_t)wave_id() * a.rows_lds;
     const double *tsc = a.tab + M1 * A;
     const int lane = lane_id();
     const double NINF = neg_inf();
@@ -197,8 +123,7 @@ __global__ __launch_bounds__(256) void post_backward_kernel(PostArgs a) {
     const bool want_pp = a.labels != nullptr && a.pp != nullptr;
 
     for (;;) {
-        unsigned long long k = atomicAdd(a.head, lane == 0 ? 1ull : 0ull);
-        k = wave_uniform((uint64_t)k);
+        const unsigned long long k = next_item(a.head);
         if (k >= a.count) break;
         const uint32_t idx = a.order[k];
         const uint64_t o0 = a.off[idx];
@@ -219,10 +144,7 @@ __global__ __launch_bounds__(256) void post_backward_kernel(PostArgs a) {
             const int w = min(64, M - 64 * s);
             const int j = 64 * s + lane + 1;
             const bool own = lane < w;
-            const int jc = own ? j : M;
-            const double tMM = tsc[0 * M1 + jc], tMI = tsc[1 * M1 + jc], tMD = tsc[2 * M1 + jc], tIM = tsc[3 * M1 + jc], tII = tsc[4 * M1 + jc],
-                         tDM = tsc[5 * M1 + jc], tDD = tsc[6 * M1 + jc];
-            const double *mrow = msc + (size_t)jc * A;
+            const Node nd = load_node(tsc, lds.msc, M1, A, own ? j : M);
             const double *pms = pm + (size_t)s * 64 * L, *pis = pi + (size_t)s * 64 * L;
             const bool rightmost = s == n_strips - 1;                     // no column behind this strip
             double n_out = NINF, d_out = NINF, n_held = NINF, b_i = NINF, sum_m = 0.0, sum_i = 0.0;
@@ -242,12 +164,10 @@ __global__ __launch_bounds__(256) void post_backward_kernel(PostArgs a) {
                 }
                 n_held = n_new;
                 const int ii = min(max(i, 1), L);
-                const uint32_t c = x[ii - 1];
-                const int col = c < 127 ? (int)s_alpha[c] : -1;
-                const double e = col < 0 ? 0.0 : mrow[col];
-                double BM = lse3(tMM + n_use, tMI + b_i, tMD + b_d);      // (b_i is -inf at j = M, b_d at j = M and from row 1)
-                double BI = lse2(tIM + n_use, tII + b_i);
-                double BD = lse2(tDM + n_use, tDD + b_d);
+                const double e = emission(lds.alpha, nd.mrow, x[ii - 1]);
+                double BM = lse3(nd.mm + n_use, nd.mi + b_i, nd.md + b_d);      // (b_i is -inf at j = M, b_d at j = M and from row 1)
+                double BI = lse2(nd.im + n_use, nd.ii + b_i);
+                double BD = lse2(nd.dm + n_use, nd.dd + b_d);
                 if (i >= L) { BM = 0.0; BI = NINF; BD = NINF; }           // row L: the alignment ends in a match state
                 if (i <= 1) { BI = NINF; BD = NINF; }                     // row 1 has no insert and no delete state
                 if (j >= M) { BI = NINF; BD = NINF; }                     // node M has no insert state, and nothing behind it
@@ -304,19 +224,12 @@ int mgta_seqs_posterior(mgta_ctx *ctx, const mgta_hmm *hmm, const char *seqs, co
     if (!hmm) { set_error("mgta_seqs_posterior: the model must not be NULL"); return MGTA_EINVAL; }
     if (hmm->ctx != ctx) { set_error("mgta_seqs_posterior: the model belongs to another context"); return MGTA_EINVAL; }
     if (n < 0) { set_error("mgta_seqs_posterior: n = %lld must not be negative", (long long)n); return MGTA_EINVAL; }
-    if (n >= (1ll << 31)) { set_error("mgta_seqs_posterior: n = %lld (the limit is n < 2^31 sequences)", (long long)n); return MGTA_EINVAL; }
+    if (!check_seq_count("mgta_seqs_posterior", kSequences, n)) return MGTA_EINVAL;
     if (n > 0 && !offsets) { set_error("mgta_seqs_posterior: offsets must not be NULL"); return MGTA_EINVAL; }
     if (n > 0 && !recs) { set_error("mgta_seqs_posterior: recs must not be NULL"); return MGTA_EINVAL; }
     if (n > 0 && pp && !labels) { set_error("mgta_seqs_posterior: labels must not be NULL when pp is given"); return MGTA_EINVAL; }
-    for (int64_t i = 0; i < n; ++i) {
-        if (offsets[i + 1] < offsets[i]) { set_error("mgta_seqs_posterior: sequence %lld: offsets must ascend", (long long)i); return MGTA_EINVAL; }
-        if (offsets[i + 1] - offsets[i] > (uint64_t)kPostMaxLen) {
-            set_error("mgta_seqs_posterior: sequence %lld holds %llu residues (the limit is %d residues per sequence)", (long long)i,
-                      (unsigned long long)(offsets[i + 1] - offsets[i]), kPostMaxLen);
-            return MGTA_EINVAL;
-        }
-    }
-    if (n > 0 && offsets[n] > offsets[0] && !seqs) { set_error("mgta_seqs_posterior: seqs must not be NULL"); return MGTA_EINVAL; }
+    if (!check_seq_offsets("mgta_seqs_posterior", kSequences, offsets, n, kPostMaxLen)) return MGTA_EINVAL;
+    if (!check_seq_letters("mgta_seqs_posterior", kSequences, seqs, n > 0 ? offsets[n] - offsets[0] : 0)) return MGTA_EINVAL;
     if (n > 0 && labels) {
         const int64_t M = hmm->M;
         for (int64_t i = 0; i < n; ++i)
@@ -333,11 +246,7 @@ int mgta_seqs_posterior(mgta_ctx *ctx, const mgta_hmm *hmm, const char *seqs, co
         MGTA_HIP_CHECK(hipSetDevice(ctx->device));
         hipStream_t st = ctx->stream;
         uint64_t *live = &ctx->live_bytes, *peak = &ctx->peak_bytes;
-        struct PeakOfCall {                                               // peak_bytes is this call's while it runs, the context's again on every way out
-            uint64_t *peak, before;
-            ~PeakOfCall() { *peak = std::max(*peak, before); }
-        } peak_of_call{peak, *peak};
-        *peak = *live;
+        PeakOfCall peak_of_call(ctx);
         const uint32_t nn = (uint32_t)n;
         const int M = hmm->M, A = hmm->A;
         const uint64_t n_letters = offsets[n] - offsets[0];
@@ -345,19 +254,12 @@ int mgta_seqs_posterior(mgta_ctx *ctx, const mgta_hmm *hmm, const char *seqs, co
         const bool want_pp = labels && pp;
 
         // the letters, the labels and where they start, once; the sequences longest first
-        std::vector<uint64_t> rel((size_t)nn + 1);
-        for (uint32_t i = 0; i <= nn; ++i) rel[i] = offsets[i] - offsets[0];
-        std::vector<uint32_t> order(nn);
-        std::iota(order.begin(), order.end(), 0u);
-        std::stable_sort(order.begin(), order.end(), [&](uint32_t x, uint32_t y) { return rel[x + 1] - rel[x] > rel[y + 1] - rel[y]; });
-        DevBuf d_seqs, d_off, d_order, d_head, d_labels, d_pp;
-        d_seqs.alloc(n_letters + 16, live, peak);
-        d_off.alloc((size_t)(nn + 1) * 8, live, peak);
-        d_order.alloc((size_t)nn * 4, live, peak);
-        d_head.alloc(64, live, peak);
-        if (n_letters) MGTA_HIP_CHECK(hipMemcpyAsync(d_seqs.p, seqs + offsets[0], n_letters, hipMemcpyHostToDevice, st));
-        MGTA_HIP_CHECK(hipMemcpyAsync(d_off.p, rel.data(), (size_t)(nn + 1) * 8, hipMemcpyHostToDevice, st));
-        MGTA_HIP_CHECK(hipMemcpyAsync(d_order.p, order.data(), (size_t)nn * 4, hipMemcpyHostToDevice, st));
+        const std::vector<uint64_t> rel = rel_offsets(offsets, n);
+        const std::vector<uint32_t> order = longest_first(rel);
+        const auto len_of = [&](uint32_t k) { return rel[order[k] + 1] - rel[order[k]]; };
+        SeqStage dev;
+        dev.upload(ctx, seqs, offsets, rel, &order);
+        DevBuf d_labels, d_pp;
         if (want_pp) {
             d_labels.alloc((size_t)n_letters * 4 + 16, live, peak);
             d_pp.alloc((size_t)n_letters * 8 + 16, live, peak);
@@ -365,17 +267,8 @@ int mgta_seqs_posterior(mgta_ctx *ctx, const mgta_hmm *hmm, const char *seqs, co
             MGTA_HIP_CHECK(hipMemsetAsync(d_pp.p, 0, (size_t)n_letters * 8 + 16, st));
         }
 
-        // cells of a batch: the switch, or what half of the memory the context may still take holds (16 bytes per cell; the rest of
-        // a batch's buffers are far smaller)
         uint64_t avail = 0;
-        {
-            size_t free_b = 0, total_b = 0;
-            MGTA_HIP_CHECK(hipMemGetInfo(&free_b, &total_b));
-            avail = free_b;
-            if (ctx->mem_limit) avail = std::min<uint64_t>(avail, ctx->mem_limit > ctx->live_bytes ? ctx->mem_limit - ctx->live_bytes : 0);
-        }
-        uint64_t cap = ctx->posterior_batch_cells;
-        if (!cap) cap = std::max<uint64_t>(avail / 2 / kPostCellBytes, 1);
+        const uint64_t cap = batch_cap(ctx, ctx->posterior_batch_cells, kPostCellBytes, &avail);
 
         Timer t_fwd(st), t_bwd(st);
         double ms_fwd = 0, ms_bwd = 0;
@@ -383,17 +276,8 @@ int mgta_seqs_posterior(mgta_ctx *ctx, const mgta_hmm *hmm, const char *seqs, co
         std::vector<uint64_t> cell_base;
         std::vector<double> h_fwd, h_bwd, h_cm, h_ci;
         for (uint32_t b0 = 0; b0 < nn;) {
-            // the batch [b0, b1): at least one sequence
-            uint32_t b1 = b0;
             uint64_t cells = 0;
-            cell_base.clear();
-            while (b1 < nn) {
-                const uint64_t L = rel[order[b1] + 1] - rel[order[b1]];
-                if (b1 > b0 && cells + L * (uint64_t)M > cap) break;
-                cell_base.push_back(cells);
-                cells += L * (uint64_t)M;
-                ++b1;
-            }
+            const uint32_t b1 = cut_cells(b0, nn, cap, len_of, [&](uint32_t) { return (uint64_t)M; }, cell_base, nullptr, &cells);
             const uint32_t count = b1 - b0;
             const uint64_t plane_bytes = cells * 8 + 16;
             if (2 * plane_bytes > avail) {                                // (one sequence alone may be more than the device has left)
@@ -401,12 +285,10 @@ int mgta_seqs_posterior(mgta_ctx *ctx, const mgta_hmm *hmm, const char *seqs, co
                           (unsigned long long)(2 * plane_bytes), (unsigned long long)avail);
                 return (int)MGTA_ENOMEM;
             }
-            const uint32_t l_max = (uint32_t)(rel[order[b0] + 1] - rel[order[b0]]);
-            const uint32_t rows_lds = std::max(1u, l_max);
+            const uint32_t rows_lds = std::max(1u, (uint32_t)len_of(b0));
             // one geometry for both kernels: the backward one needs 4 more bytes per row, for the labels
-            int waves = 4;
-            while (waves > 1 && kPostAlphaBytes + (size_t)waves * rows_lds * 20 > kPostLdsBudget) waves >>= 1;
-            size_t lds_f = kPostAlphaBytes + (size_t)waves * rows_lds * 16, lds_b = kPostAlphaBytes + (size_t)waves * rows_lds * 20;
+            const int waves = waves_that_fit(rows_lds, 20, kAlphaLdsBytes, kPostLdsBudget);
+            size_t lds_f = kAlphaLdsBytes + (size_t)waves * rows_lds * 16, lds_b = kAlphaLdsBytes + (size_t)waves * rows_lds * 20;
             const bool msc_lds = lds_b + msc_bytes <= kPostLdsBudget;
             if (msc_lds) { lds_f += msc_bytes; lds_b += msc_bytes; }
 
@@ -427,38 +309,23 @@ int mgta_seqs_posterior(mgta_ctx *ctx, const mgta_hmm *hmm, const char *seqs, co
             }
 
             PostArgs pa;
-            pa.seqs = d_seqs.as<uint8_t>(); pa.off = d_off.as<uint64_t>(); pa.order = d_order.as<uint32_t>() + b0; pa.cell_base = d_cbase.as<uint64_t>();
+            pa.seqs = dev.seqs.as<uint8_t>(); pa.off = dev.off.as<uint64_t>(); pa.order = dev.order.as<uint32_t>() + b0; pa.cell_base = d_cbase.as<uint64_t>();
             pa.count = count; pa.M = M; pa.A = A; pa.tab = hmm->tab.as<double>(); pa.alpha = hmm->d_alpha.as<int8_t>();
             pa.fm = d_fm.as<double>(); pa.fi = d_fi.as<double>(); pa.fwd = d_fwd.as<double>(); pa.bwd = d_bwd.as<double>();
             pa.labels = want_pp ? d_labels.as<int32_t>() : nullptr; pa.pp = want_pp ? d_pp.as<double>() : nullptr;
             pa.col_m = col_match ? d_cm.as<double>() : nullptr; pa.col_i = col_insert ? d_ci.as<double>() : nullptr;
-            pa.rows_lds = rows_lds; pa.head = d_head.as<unsigned long long>();
-            // workgroups a CU holds at once: what the runtime answers for these registers and this LDS (never assumed)
-            const void *fn_f = msc_lds ? reinterpret_cast<const void *>(post_forward_kernel<true>) : reinterpret_cast<const void *>(post_forward_kernel<false>);
-            const void *fn_b = msc_lds ? reinterpret_cast<const void *>(post_backward_kernel<true>) : reinterpret_cast<const void *>(post_backward_kernel<false>);
-            MGTA_HIP_CHECK(hipFuncSetAttribute(fn_f, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_f));
-            MGTA_HIP_CHECK(hipFuncSetAttribute(fn_b, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_b));
-            int bpc_f = 0, bpc_b = 0;
-            if (msc_lds) {
-                MGTA_HIP_CHECK(hipOccupancyMaxActiveBlocksPerMultiprocessor(&bpc_f, post_forward_kernel<true>, waves * 64, lds_f));
-                MGTA_HIP_CHECK(hipOccupancyMaxActiveBlocksPerMultiprocessor(&bpc_b, post_backward_kernel<true>, waves * 64, lds_b));
-            } else {
-                MGTA_HIP_CHECK(hipOccupancyMaxActiveBlocksPerMultiprocessor(&bpc_f, post_forward_kernel<false>, waves * 64, lds_f));
-                MGTA_HIP_CHECK(hipOccupancyMaxActiveBlocksPerMultiprocessor(&bpc_b, post_backward_kernel<false>, waves * 64, lds_b));
-            }
-            const int blocks_per_cu = std::max(1, std::min(bpc_f, bpc_b));
-            const unsigned grid = (unsigned)std::min<uint64_t>((uint64_t)ctx->num_cus * (uint64_t)blocks_per_cu, ((uint64_t)count + waves - 1) / waves);
-            MGTA_HIP_CHECK(hipMemsetAsync(d_head.p, 0, 64, st));
+            pa.rows_lds = rows_lds; pa.head = dev.head.as<unsigned long long>();
+            // one grid for both kernels: the workgroups a CU holds of the one that needs more
+            const auto forward = msc_lds ? post_forward_kernel<true> : post_forward_kernel<false>;
+            const auto backward = msc_lds ? post_backward_kernel<true> : post_backward_kernel<false>;
+            const int blocks_per_cu = std::min(blocks_per_cu_of(forward, waves, lds_f), blocks_per_cu_of(backward, waves, lds_b));
+            dev.reset_head(st);
             t_fwd.start();
-            if (msc_lds) hipLaunchKernelGGL(post_forward_kernel<true>, dim3(grid), dim3(waves * 64), lds_f, st, pa);
-            else hipLaunchKernelGGL(post_forward_kernel<false>, dim3(grid), dim3(waves * 64), lds_f, st, pa);
-            MGTA_HIP_CHECK(hipGetLastError());
+            const unsigned grid = launch_waves(ctx, forward, pa, waves, lds_f, count, blocks_per_cu).grid;
             t_fwd.end();
-            MGTA_HIP_CHECK(hipMemsetAsync(d_head.p, 0, 64, st));
+            dev.reset_head(st);
             t_bwd.start();
-            if (msc_lds) hipLaunchKernelGGL(post_backward_kernel<true>, dim3(grid), dim3(waves * 64), lds_b, st, pa);
-            else hipLaunchKernelGGL(post_backward_kernel<false>, dim3(grid), dim3(waves * 64), lds_b, st, pa);
-            MGTA_HIP_CHECK(hipGetLastError());
+            launch_waves(ctx, backward, pa, waves, lds_b, count, blocks_per_cu);
             t_bwd.end();
 
             h_fwd.resize(count); h_bwd.resize(count);
