@@ -520,6 +520,68 @@ int mgta_reads_pileup(mgta_sdbg *, const mgta_reads *reads, int reads_reversed, 
 int mgta_ctx_set_pileup_chunk(mgta_ctx *, uint32_t reads);   /* reads per queue grab, 0 = the library's; a switch for tests, moves no output */
 
 /* ------------------------------------------------------------------------------------------------
+ * Gapped pileup: mgta_reads_pileup with reads placed across ONE insertion or deletion.  An entry of its own; mgta_reads_pileup is
+ * what it was.  Read, contig, anchor, candidate (i, o, d), votes, n_ov, n_mm, the pass test and the pile are those of
+ * mgta_reads_pileup, word for word.  The rule is this project's own.
+ *   Parameters  the three of mgta_reads_pileup, and max_gap G (default 32, at most 255), gap_open (default 4), gap_extend (default 1),
+ *            0 <= gap_extend <= gap_open <= 255.  A parameter given as 0 takes its default.  Parameters of the rule, not measurements.
+ *   One-gap candidate  a distinct (i, o, d1, d2), d1 != d2, g = |d2 - d1| <= G.  P1 = the anchor windows p of s^o on (i, o, d1), P2 those
+ *            on (i, o, d2).  ins = max(0, d1 - d2) read letters have no partner, del = max(0, d2 - d1) contig letters are skipped.
+ *            A breakpoint b is legal iff min(P1) + k + 1 <= b and b + ins <= max(P2); the candidate exists iff a legal b exists.
+ *            Under b the read letters p in [0, b) lie at x = p + d1, the letters p in [b + ins, L) at x = p + d2; a pair with x
+ *            outside [0, len_i) does not count.  n_ov = the pairs, n_mm = those that differ (n_ov is the same for every legal b).
+ *            votes = |{p in P1 : p + k + 1 <= b}| + |{p in P2 : p >= b + ins}|.
+ *            score = n_ov - 2 * n_mm - (gap_open + gap_extend * g).
+ *            The candidate's b = the legal b of the highest score, the lowest such b on a tie: a gap inside a repeat is left-aligned.
+ *            pos = b + d1 = the first contig position right of the gap's left side: the first deleted letter, or the letter in front
+ *            of which the insertion lies.  (d1, d2) and (d2, d1) are two candidates.
+ *   Pass     the three tests of mgta_reads_pileup on the candidate's votes, n_ov and n_mm (both sides have an anchor by construction).
+ *   Placements of a read = ALL passing candidates, gapped and ungapped (d2 = d1, score = n_ov - 2 * n_mm) alike, with the read's
+ *            highest score; ties are all placed.  "The lowest" is by (contig, orient, d1, d2).
+ *   Pile     every placement piles its pairs into counts / uniq as mgta_reads_pileup does; the deleted contig positions get nothing
+ *            from it, the inserted read letters go nowhere.
+ * per_contig as in mgta_reads_pileup over all placements.  per_read (may be NULL): mgta_gap_place = mgta_read_place of the lowest
+ * placement (diag = d1) with diag2 = d2 and brk = b; an ungapped placement has diag2 = diag and brk = 0; {0, -1, 0, 0, 0, 0, 0, 0}
+ * for a read without one.  gaps[gap_cap]: one mgta_gap_rec per gapped placement -- read, contig, pos, len = d2 - d1 (> 0 letters
+ * deleted, < 0 inserted), brk, orient, unique = 1 iff it is the read's only placement -- sorted by (contig, pos, len, read, orient,
+ * d1 = pos - brk) before the call returns: no device order shows.  More records than gap_cap: MGTA_EINVAL, the message names the
+ * count needed, stats->n_gap_placements holds it and nothing else is written (gaps may be NULL with gap_cap = 0).
+ * Stats: the fields of mgta_pileup_stats -- n_candidates and n_verified count the ungapped candidates; n_reads_placed, n_reads_multi,
+ * n_placements and n_bases_piled all placements -- then n_gap_candidates = one-gap candidates, n_gap_passing = those that pass,
+ * n_reads_gapped = reads whose per_read record is gapped, n_gap_placements, n_inserted / n_deleted = the letters of the gapped
+ * placements' gaps.  All but ms_*, peak_bytes, groups_per_cu, n_read_walked and n_read_index_searches are functions of the inputs
+ * alone; neither mgta_ctx_set_pileup_chunk nor mgta_ctx_set_share_hash_bits moves any.
+ * Limits: those of mgta_reads_pileup, and max_gap in [0, 255], 0 <= gap_extend <= gap_open <= 255 (after the defaults); each
+ * MGTA_EINVAL naming the limit with nothing written.  Memory: that of mgta_reads_pileup, and per group of lanes in flight a list of the
+ * read's diagonals of 24 bytes each, sized for the most a read of the call can have: (windows of the longest read) * (the most
+ * occurrences of one key); fewer groups run where the rows would pass 1 GiB and what does not fit is MGTA_ENOMEM: no cap on
+ * candidates.  n = 0 or n_short_reads = 0: MGTA_OK, everything zero.
+ * What it is not: one gap per read; a gap nearer than k + 1 letters to an end of the read has no anchor on its short side and the read
+ * stays with the ungapped rule; no quality values; mgta_reads_phase takes no allele from a gapped placement.
+ * ------------------------------------------------------------------------------------------------ */
+typedef struct mgta_gapped_params { int32_t min_anchors, min_overlap, max_mismatch_permille, max_gap, gap_open, gap_extend; } mgta_gapped_params;
+typedef struct mgta_gap_place { int32_t score, contig, diag, orient; uint32_t n_placed, n_mismatch; int32_t diag2; uint32_t brk; } mgta_gap_place;
+typedef struct mgta_gap_rec { uint64_t read; int32_t contig; uint32_t pos; int32_t len; uint32_t brk; int32_t orient, unique; } mgta_gap_rec;
+typedef struct mgta_gapped_stats {
+    int64_t n_contigs, n_contig_letters, n_contig_windows, n_keys, n_occurrences, n_reads, n_read_windows, n_hit_windows;
+    int64_t n_read_walked, n_read_index_searches, n_reads_with_candidate, n_candidates, n_verified;
+    int64_t n_reads_placed, n_reads_multi, n_placements, n_bases_piled, groups_per_cu;
+    uint64_t peak_bytes;
+    double ms_keys, ms_index, ms_scan, ms_records, ms_total;   /* up to here mgta_pileup_stats */
+    int64_t n_gap_candidates;        /* one-gap candidates: (i, o, d1, d2) with a legal breakpoint */
+    int64_t n_gap_passing;           /* those that pass the three tests */
+    int64_t n_reads_gapped;          /* reads whose per_read record (the lowest placement) is gapped */
+    int64_t n_gap_placements;        /* = the gap records */
+    int64_t n_inserted, n_deleted;   /* letters, summed over the gapped placements */
+    int64_t diag_list_entries;       /* entries of one group's diagonal list (a function of the inputs too) */
+} mgta_gapped_stats;
+int mgta_reads_pileup_gapped(mgta_sdbg *, const mgta_reads *reads, int reads_reversed, uint64_t n_short_reads, const char *seqs,
+                             const uint64_t *offsets /* [n + 1] */, int64_t n, const mgta_gapped_params *params /* NULL = defaults */,
+                             uint32_t *counts /* [offsets[n] * 4] */, uint32_t *uniq /* [offsets[n]] or NULL */,
+                             mgta_contig_pileup *per_contig /* [n] or NULL */, mgta_gap_place *per_read /* [n_short_reads] or NULL */,
+                             mgta_gap_rec *gaps /* [gap_cap] */, uint64_t gap_cap, mgta_gapped_stats *stats /* or NULL */);
+
+/* ------------------------------------------------------------------------------------------------
  * Phase: which alleles of the variant positions (sites) of a contig travel together on one fragment -- a read, or two mates of a
  * paired library.  The rule is this project's own; it counts, it reconstructs no haplotype.  Needs no graph: the inputs are the reads,
  * the placements mgta_reads_pileup returned for them (per_read) and the sites.

@@ -222,6 +222,19 @@ class PileupStats(C.Structure):
         return {n: getattr(self, n) for n, _ in self._fields_}
 
 
+class GappedParams(C.Structure):
+    _fields_ = [("min_anchors", C.c_int32), ("min_overlap", C.c_int32), ("max_mismatch_permille", C.c_int32), ("max_gap", C.c_int32), ("gap_open", C.c_int32),
+                ("gap_extend", C.c_int32)]
+
+
+class GappedStats(C.Structure):
+    _fields_ = PileupStats._fields_ + [("n_gap_candidates", C.c_int64), ("n_gap_passing", C.c_int64), ("n_reads_gapped", C.c_int64), ("n_gap_placements", C.c_int64),
+                                       ("n_inserted", C.c_int64), ("n_deleted", C.c_int64), ("diag_list_entries", C.c_int64)]
+
+    def as_dict(self):
+        return {n: getattr(self, n) for n, _ in self._fields_}
+
+
 class PhaseParams(C.Structure):
     _fields_ = [("max_span", C.c_int32)]
 
@@ -302,6 +315,8 @@ SYMBOLS = {
     "mgta_reads_pileup": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_uint64, C.c_char_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
                                    C.c_void_p, C.c_void_p]),
     "mgta_ctx_set_pileup_chunk": (C.c_int, [C.c_void_p, C.c_uint32]),
+    "mgta_reads_pileup_gapped": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_uint64, C.c_char_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p,
+                                          C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p]),
     "mgta_phase_pairs": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_int32, C.c_void_p]),
     "mgta_reads_phase": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p,
                                   C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p]),

@@ -778,6 +778,46 @@ class Graph:
                                             pr.ctypes.data if per_read and ns else None, C.byref(st)), "mgta_reads_pileup")
         return dict(counts=counts, uniq=uniq, contigs=rec, offsets=offsets.astype(np.int64), stats=st.as_dict(), reads=pr)
 
+    def pileup_gapped(self, reads: "Reads", seqs, n_short_reads: int | None = None, params: dict | None = None, per_read: bool = False,
+                      reads_reversed: bool = True, gap_cap: int | None = None) -> dict:
+        """mgta_reads_pileup_gapped: Graph.pileup with reads placed across one insertion or deletion (the rule: include/megagta_hip.h).
+        params = the three of pileup and max_gap=, gap_open=, gap_extend=, 0 or missing = the default of each.  -> the dict of
+        Graph.pileup with reads = gapped.PLACE_DTYPE records and gaps = gapped.GAP_DTYPE records, sorted by the library.  The buffer
+        of the gap records is sized from the reads scanned and the call repeated once with the count the library names."""
+        from .gapped import GAP_DTYPE, PLACE_DTYPE
+        from .pileup import CONTIG_DTYPE
+        raw = [s if isinstance(s, (bytes, bytearray)) else str(s).encode() for s in seqs]
+        n = len(raw)
+        offsets = np.zeros(n + 1, dtype=np.uint64)
+        if n:
+            np.cumsum([len(s) for s in raw], out=offsets[1:])
+        ns = reads.n_reads if n_short_reads is None else int(n_short_reads)
+        total = int(offsets[-1])
+        counts = np.zeros((total, 4), dtype=np.uint32)
+        uniq = np.zeros(total, dtype=np.uint32)
+        rec = np.zeros(n, dtype=CONTIG_DTYPE)
+        pr = np.zeros(ns, dtype=PLACE_DTYPE) if per_read else None
+        par = _lib.GappedParams()
+        unknown = set(params or {}) - {name for name, _ in _lib.GappedParams._fields_}
+        if unknown:
+            raise ValueError(f"unknown gapped pileup parameters: {sorted(unknown)}")
+        for name, v in (params or {}).items():
+            setattr(par, name, int(v))
+        st = _lib.GappedStats()
+        cap = max(16, ns // 8) if gap_cap is None else int(gap_cap)
+        for attempt in (0, 1):
+            gaps = np.zeros(cap, dtype=GAP_DTYPE)
+            rc = self.ctx._L.mgta_reads_pileup_gapped(self.h, reads.h, int(bool(reads_reversed)), ns, b"".join(raw), offsets.ctypes.data, n,
+                                                      C.byref(par) if params else None, counts.ctypes.data if total else None, uniq.ctypes.data if total else None,
+                                                      rec.ctypes.data if n else None, pr.ctypes.data if per_read and ns else None, gaps.ctypes.data if cap else None,
+                                                      cap, C.byref(st))
+            if rc == -1 and attempt == 0 and gap_cap is None and st.n_gap_placements > cap:
+                cap = int(st.n_gap_placements)
+                continue
+            check(rc, "mgta_reads_pileup_gapped")
+            break
+        return dict(counts=counts, uniq=uniq, contigs=rec, offsets=offsets.astype(np.int64), stats=st.as_dict(), reads=pr, gaps=gaps[:int(st.n_gap_placements)].copy())
+
     def denovo(self, max_tip_len: int = 150, no_bubble: bool = False, min_contig: int = 0) -> tuple[str, dict]:
         """`megagta denovo` (main_assemble, assembler.cpp:98-167): tips, bubbles, unitigs -> (text of PREFIX.contigs.fa, stats).
         The result is the reference's one-thread output.  CONSUMES the validity bits of this graph."""

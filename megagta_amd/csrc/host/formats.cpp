@@ -855,6 +855,28 @@ PileupTexts format_pileup(const std::vector<std::string> &names, const std::stri
 }
 
 // ---- phase files -----------------------------------------------------------------------------------------------------------------------
+std::string format_indels(const std::vector<std::string> &names, const std::vector<uint64_t> &offsets, const uint32_t *counts, const std::vector<GapEvent> &events,
+                          uint32_t min_depth, uint32_t min_alt_permille) {
+    // the records that agree in (contig, pos, type, len, letters) are one event; insertions sort before deletions
+    std::map<std::tuple<int32_t, uint32_t, bool, uint32_t, std::string>, std::pair<uint64_t, uint64_t>> found;
+    for (const GapEvent &e : events) {
+        auto &c = found[std::make_tuple(e.contig, e.pos, e.is_del, e.len, e.letters)];
+        ++c.first;
+        c.second += e.unique ? 1 : 0;
+    }
+    const uint64_t need = std::max<uint64_t>(1, ((uint64_t)min_depth * min_alt_permille + 999) / 1000);
+    std::string out = "#contig\tpos\ttype\tlen\tseq\treads\tunique\tdepth\n";
+    for (const auto &kv : found) {
+        if (kv.second.first < need) continue;
+        const int32_t i = std::get<0>(kv.first);
+        const uint32_t *c = counts + (offsets[(size_t)i] + std::get<1>(kv.first)) * 4;
+        out += names[(size_t)i] + "\t" + std::to_string(std::get<1>(kv.first) + 1) + "\t" + (std::get<2>(kv.first) ? "del" : "ins") + "\t" +
+               std::to_string(std::get<3>(kv.first)) + "\t" + std::get<4>(kv.first) + "\t" + std::to_string(kv.second.first) + "\t" + std::to_string(kv.second.second) +
+               "\t" + std::to_string((uint64_t)c[0] + c[1] + c[2] + c[3]) + "\n";
+    }
+    return out;
+}
+
 void pileup_variant_sites(const std::string &seqs, const std::vector<uint64_t> &offsets, const uint32_t *counts, uint32_t min_depth, uint32_t min_alt_permille,
                           std::vector<uint64_t> &site_off, std::vector<uint32_t> &site_pos) {
     site_off.assign(1, 0);

@@ -126,6 +126,11 @@ PileupTexts format_pileup(const std::vector<std::string> &names, const std::stri
 
 // ---- phase files (megagta_amd/phase.py prints the same bytes) -------------------------------------------------------
 struct PhaseTexts { std::string links, blocks; };
+// PREFIX_pileup_indels.txt (INTEGRATION.md 2p'; megagta_amd/gapped.py prints the same bytes): one GapEvent per gap record, in any order
+struct GapEvent { int32_t contig; uint32_t pos; bool is_del; uint32_t len; std::string letters; bool unique; };
+std::string format_indels(const std::vector<std::string> &names, const std::vector<uint64_t> &offsets, const uint32_t *counts, const std::vector<GapEvent> &events,
+                          uint32_t min_depth, uint32_t min_alt_permille);
+
 // the positions format_pileup lists as variants: site_off[n + 1] and the 0-based site_pos
 void pileup_variant_sites(const std::string &seqs, const std::vector<uint64_t> &offsets, const uint32_t *counts, uint32_t min_depth, uint32_t min_alt_permille,
                           std::vector<uint64_t> &site_off, std::vector<uint32_t> &site_pos);

@@ -1091,18 +1091,21 @@ static bool write_text_file(const std::string &path, const std::string &text) {
 // reads are mates): INTEGRATION.md 2q; megagta_amd/phase.py prints the same bytes.
 static int main_pileup(int argc, char **argv) {
     const char *usage = "Usage: megagta pileup <sdbg_prefix> <read.lib> <contigs.fasta> <out_prefix> [--min-anchors N] [--min-overlap N] [--max-mismatch-permille N] "
-                        "[--min-depth N] [--min-alt-permille N] [--per-base] [--phase [--max-span N] [--min-link N] [--min-hap-permille N]]\n";
+                        "[--min-depth N] [--min-alt-permille N] [--per-base] [--phase [--max-span N] [--min-link N] [--min-hap-permille N]]\n"
+                        "                      [--gapped [--max-gap N] [--gap-open N] [--gap-extend N]]\n";
     if (argc < 5) { fputs(usage, stderr); return 1; }
     mgta_pileup_params par{0, 0, 0};
-    long long min_depth = 8, min_alt = 100, max_span = 0, min_link = 4, min_hap = 100;
-    bool per_base = false, phase = false, phase_opt = false;
+    long long min_depth = 8, min_alt = 100, max_span = 0, min_link = 4, min_hap = 100, max_gap = 0, gap_open = 0, gap_extend = 0;
+    bool per_base = false, phase = false, phase_opt = false, gapped = false, gap_opt = false;
     for (int i = 5; i < argc; ++i) {
         const std::string a = argv[i];
         if (a == "--per-base") { per_base = true; continue; }
         if (a == "--phase") { phase = true; continue; }
+        if (a == "--gapped") { gapped = true; continue; }
         long long *into64 = a == "--min-depth" ? &min_depth : a == "--min-alt-permille" ? &min_alt : a == "--max-span" ? &max_span : a == "--min-link" ? &min_link :
-                            a == "--min-hap-permille" ? &min_hap : nullptr;
+                            a == "--min-hap-permille" ? &min_hap : a == "--max-gap" ? &max_gap : a == "--gap-open" ? &gap_open : a == "--gap-extend" ? &gap_extend : nullptr;
         if (into64 == &max_span || into64 == &min_link || into64 == &min_hap) phase_opt = true;
+        if (into64 == &max_gap || into64 == &gap_open || into64 == &gap_extend) gap_opt = true;
         int32_t *into = a == "--min-anchors" ? &par.min_anchors : a == "--min-overlap" ? &par.min_overlap : a == "--max-mismatch-permille" ? &par.max_mismatch_permille : nullptr;
         char *end = nullptr;
         if ((!into && !into64) || i + 1 >= argc) { fputs(usage, stderr); return 1; }
@@ -1111,6 +1114,7 @@ static int main_pileup(int argc, char **argv) {
         if (into) *into = (int32_t)v; else *into64 = v;
     }
     if (phase_opt && !phase) { fprintf(stderr, "megagta pileup: --max-span, --min-link and --min-hap-permille are options of --phase\n%s", usage); return 1; }
+    if (gap_opt && !gapped) { fprintf(stderr, "megagta pileup: --max-gap, --gap-open and --gap-extend are options of --gapped\n%s", usage); return 1; }
     RssLine rss;
     const std::string prefix = argv[1], lib = argv[2], fasta = argv[3], out_prefix = argv[4];
     std::vector<std::string> names;
@@ -1154,8 +1158,49 @@ static int main_pileup(int argc, char **argv) {
     std::vector<mgta_contig_pileup> rec((size_t)n + 1);
     std::vector<mgta_read_place> place(phase ? (size_t)n_reads + 1 : 0);
     mgta_pileup_stats st;
+    std::string indels;
     // all records in ONE call: the best-hit rule looks at every contig of the file
-    if (mgta_reads_pileup(g, rd, 1, n_reads, seqs.data(), offsets.data(), n, &par, counts.data(), uniq.data(), rec.data(), phase ? place.data() : nullptr, &st) != MGTA_OK)
+    if (gapped) {
+        // INTEGRATION.md 2p': the same files from the gapped counts and PREFIX_pileup_indels.txt; megagta_amd/gapped.py prints the same bytes
+        const mgta_gapped_params gpar{par.min_anchors, par.min_overlap, par.max_mismatch_permille, (int32_t)max_gap, (int32_t)gap_open, (int32_t)gap_extend};
+        std::vector<mgta_gap_place> gplace(phase ? (size_t)n_reads + 1 : 0);
+        std::vector<mgta_gap_rec> gaps(std::max<size_t>(16, (size_t)n_reads / 8));
+        mgta_gapped_stats gs;
+        memset(&gs, 0, sizeof(gs));
+        int rcode = mgta_reads_pileup_gapped(g, rd, 1, n_reads, seqs.data(), offsets.data(), n, &gpar, counts.data(), uniq.data(), rec.data(), phase ? gplace.data() : nullptr,
+                                             gaps.data(), gaps.size(), &gs);
+        if (rcode == MGTA_EINVAL && (uint64_t)gs.n_gap_placements > gaps.size()) {   // the buffer was sized from the reads: once more with the count the library names
+            gaps.resize((size_t)gs.n_gap_placements);
+            rcode = mgta_reads_pileup_gapped(g, rd, 1, n_reads, seqs.data(), offsets.data(), n, &gpar, counts.data(), uniq.data(), rec.data(), phase ? gplace.data() : nullptr,
+                                             gaps.data(), gaps.size(), &gs);
+        }
+        if (rcode != MGTA_OK) die("mgta_reads_pileup_gapped: %s", mgta_last_error());
+        gaps.resize((size_t)gs.n_gap_placements);
+        memcpy(&st, &gs, sizeof(st));                                         // (the first fields of mgta_gapped_stats are mgta_pileup_stats)
+        logf("gapped: %lld one-gap candidates, %lld pass; %lld reads placed across a gap, %lld gapped placements, %lld letters inserted, %lld deleted",
+             (long long)gs.n_gap_candidates, (long long)gs.n_gap_passing, (long long)gs.n_reads_gapped, (long long)gs.n_gap_placements, (long long)gs.n_inserted,
+             (long long)gs.n_deleted);
+        for (size_t r = 0; phase && r < (size_t)n_reads; ++r) {               // a gapped placement gives --phase no allele
+            const mgta_gap_place &p = gplace[r];
+            place[r] = mgta_read_place{p.score, p.contig, p.diag, p.orient, p.diag2 != p.diag ? 0u : p.n_placed, p.n_mismatch};
+        }
+        std::vector<GapEvent> evs;
+        for (const mgta_gap_rec &x : gaps) {
+            GapEvent e;
+            e.contig = x.contig; e.pos = x.pos; e.is_del = x.len > 0; e.len = (uint32_t)(x.len > 0 ? x.len : -x.len); e.unique = x.unique != 0;
+            if (e.is_del) e.letters = seqs.substr((size_t)offsets[(size_t)x.contig] + x.pos, e.len);
+            else {
+                const uint64_t s0 = pr.start[(size_t)x.read], len = pr.start[(size_t)x.read + 1] - s0;
+                for (uint32_t j = 0; j < e.len; ++j) {                        // the stored order is the read reversed
+                    const uint64_t p = x.brk + j, q = s0 + (x.orient ? p : len - 1 - p);
+                    const uint32_t c = (pr.words[(size_t)(q >> 4)] >> (30 - 2 * (q & 15))) & 3u;
+                    e.letters.push_back("ACGT"[x.orient ? 3 - c : c]);
+                }
+            }
+            evs.push_back(std::move(e));
+        }
+        indels = format_indels(names, offsets, counts.data(), evs, (uint32_t)min_depth, (uint32_t)min_alt);
+    } else if (mgta_reads_pileup(g, rd, 1, n_reads, seqs.data(), offsets.data(), n, &par, counts.data(), uniq.data(), rec.data(), phase ? place.data() : nullptr, &st) != MGTA_OK)
         die("mgta_reads_pileup: %s", mgta_last_error());
     logf("pileup of %lld contigs: %lld windows, %lld keys, %lld occurrences (%.1f + %.1f ms); %lld reads, %lld read windows, %lld on a key; %lld reads with a candidate, "
          "%lld candidates, %lld verified; %lld reads placed, %lld more than once, %lld placements, %lld bases (%.1f ms); records %.1f ms; %.1f MB on the device; wall %.3f s",
@@ -1192,6 +1237,7 @@ static int main_pileup(int argc, char **argv) {
     if (!write_text_file(out_prefix + "_pileup.txt", txt.summary)) die("cannot write %s_pileup.txt", out_prefix.c_str());
     if (!write_text_file(out_prefix + "_pileup_variants.txt", txt.variants)) die("cannot write %s_pileup_variants.txt", out_prefix.c_str());
     if (per_base && !write_text_file(out_prefix + "_pileup_depth.txt", txt.depth)) die("cannot write %s_pileup_depth.txt", out_prefix.c_str());
+    if (gapped && !write_text_file(out_prefix + "_pileup_indels.txt", indels)) die("cannot write %s_pileup_indels.txt", out_prefix.c_str());
     if (phase && !write_text_file(out_prefix + "_phase_links.txt", ptxt.links)) die("cannot write %s_phase_links.txt", out_prefix.c_str());
     if (phase && !write_text_file(out_prefix + "_phase_blocks.txt", ptxt.blocks)) die("cannot write %s_phase_blocks.txt", out_prefix.c_str());
     if (!g_sess.active) mgta_sdbg_free(g);

@@ -98,7 +98,12 @@ USAGE = """Usage:
                      both) and nucl_merged[_rmdup]_phase_blocks.txt (the positions joined by phased links)
     --max-span N              needs --phase: pairs of positions less than N apart are tabled [1000]
     --min-link N              needs --phase: fewest fragments on a listed pair [4]
-    --min-hap-permille N      needs --phase: smallest share of a pair's fragments that makes a haplotype count, per 1000 [100]"""
+    --min-hap-permille N      needs --phase: smallest share of a pair's fragments that makes a haplotype count, per 1000 [100]
+    --gapped         needs --pileup: reads are also placed across one insertion or deletion; the pileup files come from those
+                     placements, and nucl_merged[_rmdup]_pileup_indels.txt lists the insertions and deletions the reads show
+    --max-gap N               needs --gapped: most letters of an insertion or deletion [32, at most 255]
+    --gap-open N              needs --gapped: what a gap costs a placement's score [4]
+    --gap-extend N            needs --gapped: what every letter of the gap costs on top [1]"""
 
 
 class Usage(Exception):
@@ -151,6 +156,8 @@ class Opt:
         self.pileup_opts = {}            # the numeric options of --pileup that were given: flag -> value
         self.phase = False
         self.phase_opts = {}             # the numeric options of --phase that were given: flag -> value
+        self.gapped = False
+        self.gapped_opts = {}            # the numeric options of --gapped that were given: flag -> value
 
 
 opt = Opt()
@@ -161,7 +168,8 @@ LONG = ["help", "read=", "12=", "out-dir=", "memory=", "gpu-mem=", "min-contig-l
         "prune-len=", "low-cov-penalty=", "bin=", "one-process-per-step", "gpus=", "coverage", "match-reads", "derep", "align", "posterior", "cluster",
         "cluster-dist=", "cluster-min-overlap=", "cluster-dists=", "nearest", "nearest-scoring=", "nearest-gap-open=", "nearest-gap-extend=",
         "chimera", "chimera-min-seg=", "chimera-min-gain=", "taxon-abund", "sample-abund", "pileup", "min-anchors=", "min-overlap=",
-        "max-mismatch-permille=", "min-depth=", "min-alt-permille=", "phase", "max-span=", "min-link=", "min-hap-permille="]
+        "max-mismatch-permille=", "min-depth=", "min-alt-permille=", "phase", "max-span=", "min-link=", "min-hap-permille=",
+        "gapped", "max-gap=", "gap-open=", "gap-extend="]
 
 
 def parse_opt(argv):
@@ -235,6 +243,11 @@ def parse_opt(argv):
             if not v.isdigit():
                 raise Usage("%s %s: a count is expected" % (o, v))
             opt.phase_opts[o] = int(v)
+        elif o == "--gapped": opt.gapped = True
+        elif o in ("--max-gap", "--gap-open", "--gap-extend"):
+            if not v.isdigit():
+                raise Usage("%s %s: a count is expected" % (o, v))
+            opt.gapped_opts[o] = int(v)
         else:
             raise Usage("Invalid option " + o)
     opt.temp_dir = opt.out_dir + "tmp/"
@@ -300,6 +313,12 @@ def check_opt():
         raise Usage("%s needs --phase: it is an option of that step" % sorted(opt.phase_opts)[0])
     if opt.phase and not opt.pileup:
         raise Usage("--phase needs --pileup: it is an option of that step")
+    if opt.gapped_opts and not opt.gapped:
+        raise Usage("%s needs --gapped: it is an option of that step" % sorted(opt.gapped_opts)[0])
+    if opt.gapped and not opt.pileup:
+        raise Usage("--gapped needs --pileup: it is an option of that step")
+    if max(opt.gapped_opts.values(), default=0) > 255:
+        raise Usage("--max-gap, --gap-open and --gap-extend are at most 255")
     if opt.phase_opts.get("--min-hap-permille", 0) > 1000:
         raise Usage("--min-hap-permille is a share of 1000")
     if opt.cluster_dists is not None:
@@ -857,6 +876,8 @@ def pileup(k):
     extra = [x for flag in sorted(opt.pileup_opts) for x in (flag, str(opt.pileup_opts[flag]))]
     if opt.phase:
         extra += ["--phase"] + [x for flag in sorted(opt.phase_opts) for x in (flag, str(opt.phase_opts[flag]))]
+    if opt.gapped:
+        extra += ["--gapped"] + [x for flag in sorted(opt.gapped_opts) for x in (flag, str(opt.gapped_opts[flag]))]
     for gene in opt.gene_info:
         d = opt.out_dir + "contigs/" + gene
         if should_run():
