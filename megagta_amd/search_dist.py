@@ -69,11 +69,11 @@ def write_fasta(path: str, gene: str, contigs, offsets) -> None:
             f.write(b"\n")
 
 
-DEFAULT_COST_KNEE, DEFAULT_COST_RATE2 = 0, 0      # (kDefaultCostKnee / kDefaultCostRate2 of csrc/host/megagta_main.cpp)
+DEFAULT_COST_KNEE, DEFAULT_COST_RATE2 = 0, 0      # (kDefaultCostKnee / kDefaultCostRate2 of csrc/host/cli_graph.cpp)
 
 
 def search_plan(n_seeds: int) -> tuple[int, int, int, int]:
-    """as `megagta search` (csrc/host/megagta_main.cpp::search_plan): the ordered-commit window and the cost term (rate, knee, rate beyond
+    """as `megagta search` (csrc/host/cli_graph.cpp::search_plan): the ordered-commit window and the cost term (rate, knee, rate beyond
     the knee; knee 0 = one rate) by the number of seeds the batch holds; MEGAGTA_CACHE_WINDOW / MEGAGTA_CACHE_COST_RATE /
     MEGAGTA_CACHE_COST_KNEE / MEGAGTA_CACHE_COST_RATE2 override (any integer >= -64 for the rate: < 0 = seeds per expansion)"""
     w, r = _env_int("MEGAGTA_CACHE_WINDOW"), _env_int("MEGAGTA_CACHE_COST_RATE")
