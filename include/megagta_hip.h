@@ -968,6 +968,75 @@ int mgta_seqs_nearest(mgta_ctx *, const char *seqs, const uint64_t *offsets /* [
 int mgta_ctx_set_nearest_batch(mgta_ctx *, int64_t cells);   /* 0 = by memory (default); a switch for tests, the outputs do not move */
 
 /* ------------------------------------------------------------------------------------------------
+ * The nearest reference protein of every NUCLEOTIDE contig, with shifts of the reading frame (the place of FrameBot on the nucleotide
+ * representatives in the reference's bin/post_proc.sh:106-109; FrameBot is not part of the reference, and the rule below is this
+ * library's own, not FrameBot's).  Needs no graph.  Contig i = nucl[offsets[i] .. offsets[i + 1]), L nucleotides x_1 .. x_L;
+ * reference r = refs[ref_offsets[r] .. ref_offsets[r + 1]), R residues y_1 .. y_R.  Residue classes c(), sub, gap_open and gap_extend
+ * are those of mgta_seqs_nearest; frameshift is one more cost, 0 <= frameshift <= 1024.
+ *   Nucleotide. A, C, G, T of either case are 0 .. 3; every other byte is unknown.
+ *   Codon.      For i >= 3, a(i) is the residue of (x_{i-2}, x_{i-1}, x_i) by the standard code (codon = 16 * b0 + 4 * b1 + b2 into
+ *               KNKNTTTTRSRSIIMIQHQHPPPPRRRRLLLLEDEDAAAAGGGGVVVV*Y*YSSSS*CWCLFLF); a codon with an unknown letter gives X; a stop gives
+ *               `*`, which is class 0.  e(i, j) = sub[c(a(i))][c(y_j)], u(j) = sub[c('X')][c(y_j)].
+ *   Mode.       Global in the contig, local in the reference: every nucleotide is consumed, the alignment begins before x_1 at no
+ *               cost against any reference position, and it ends in a match state at row L.
+ *   Recurrence  (rows i = 1 .. L are nucleotide positions, j = 1 .. R; int32; whatever is not defined is never a candidate):
+ *               P[i][j]  = the maximum of the defined M[i][j], X[i][j], Y[i][j], preference M, X, Y.
+ *               prev(i', j') = 0 when i' = 0 (B, any j'); P[i'][j'] for i' >= 1 and j' >= 1; undefined otherwise.
+ *               M[i][j]  = the maximum, the first candidate winning a tie, of
+ *                            1. i >= 3:  e(i, j) + prev(i-3, j-1)                  (a codon)
+ *                            2. i >= 2:  u(j) - frameshift + prev(i-2, j-1)        (one nucleotide missing: two letters stand for a
+ *                                                                                  residue nobody knows)
+ *                            3. i >= 4:  e(i, j) - frameshift + prev(i-4, j-1)     (one nucleotide too many: x_{i-3} is dropped, the
+ *                                                                                  codon is the last three)
+ *               X[i][j]  = max( M[i-3][j] - gap_open, X[i-3][j] - gap_extend )    i >= 4    (a whole codon against a gap: insert)
+ *               Y[i][j]  = max( M[i][j-1] - gap_open, Y[i][j-1] - gap_extend )    j >= 2    (y_j skipped: delete)
+ *   Score.      score(contig, ref) = max_j M[L][j], the end column the LOWEST such j; no score where no M[L][j] is defined (L = 0,
+ *               L = 1, R = 0, and R = 1 with L >= 5 are such cases).  For X and Y the candidate written first wins a tie (M).
+ *   Nearest.    The reference with the highest score; on a tie the lowest reference index.  A contig with no scored pair is
+ *               UNALIGNED: status 1, ref -1, every other field 0, an empty path.
+ *   Record.     From the traceback against the nearest reference only: ref, score; ref_from, ref_to: the reference position of the
+ *               first and of the last match state, 1-based; n_match, n_short, n_long: match states of candidate 1, 2, 3; n_ident:
+ *               candidate 1 and 3 states with c(a(i)) == c(y_j) != 0; n_insert: inserted codons; n_delete.  When path is given,
+ *               the state path in path order over 'M' (candidate 1), '<' (2, short), '>' (3, long), 'I', 'D' at
+ *               path + offsets[i] + i*4096 (the caller's offsets as they are), at most L/2 + R characters, not terminated, its length
+ *               in path_len[i] (required with path).
+ *   Range.      A path has at most 4096 residue-consuming states, 4096 inserted codons, 4096 deleted residues and 4096 shifts (a
+ *               shift is a residue-consuming state), so a defined value is at most 127 * 4096 + 1024 * 3 * 4096 = 13 103 104 < 2^24
+ *               in magnitude.  The kernels hold "undefined" as the sentinel -2^30; whatever derives from it has moved by at most
+ *               12288 + 4096 + 128 steps of between -(128 + 1024 + 1024) and +127 each, so it lies within [-3.6e7, +2.1e6] of the
+ *               sentinel: below every defined value, below the floor -2^29 under which nothing is reported, above INT32_MIN.
+ * scores, when given, takes score(i, r) of EVERY pair at scores[i * n_ref + r], INT32_MIN where the pair has no score.  The passes,
+ * the batches (mgta_ctx_set_nearest_batch sets this call's trace batch too, in cells = L * R), the device memory, MGTA_ENOMEM and
+ * the MGTA_EINVAL cases are those of mgta_seqs_nearest, with `nucl` for `seqs` and frameshift out of range as one more; the workgroup
+ * holds 4, 2 or 1 waves within 80 KB of LDS while the longest contig allows it, and one wave with up to 864 + 9 * 12288 bytes above
+ * that.  Every output is a function of the inputs only, except stats.ms_*, the counters of work done and the residency fields.
+ * Limits: L <= 12288, R <= 4096, n < 2^31, n_ref < 2^31, fewer than 2^31 reference residues in all; beyond any of them MGTA_EINVAL
+ * names the limit and nothing is written.  n = 0: MGTA_OK, stats all zero.  n_ref = 0: every contig unaligned.
+ * It is not FrameBot's rule: shifts of one nucleotide only, a long codon always drops its first letter, and no metric pre-filter.
+ * ------------------------------------------------------------------------------------------------ */
+typedef struct mgta_frameshift_rec { int32_t status, ref, score, ref_from, ref_to, n_match, n_ident, n_insert, n_delete, n_short, n_long; } mgta_frameshift_rec;
+typedef struct mgta_frameshift_stats {
+    int64_t n_seqs, n_refs, n_pairs, n_unaligned;
+    int64_t n_cells;                       /* sum of L * R over all pairs, L in nucleotide rows (INT64_MAX when it does not fit) */
+    int64_t n_trace_cells;                 /* sum of L * R over the (contig, nearest reference) pairs */
+    int64_t n_batches;                     /* batches of the trace pass */
+    int64_t n_segments;                    /* runs of whole references the score pass cut the concatenation into */
+    int64_t blocks_per_cu;                 /* what the runtime answered for the score kernel with its LDS */
+    int64_t waves_per_block;               /* contigs in flight per workgroup: 4, 2 or 1 by the longest contig */
+    int64_t grid_blocks;                   /* workgroups of the score pass */
+    int64_t lds_bytes;                     /* LDS of a workgroup */
+    int64_t peak_bytes;                    /* most device memory the call held at once */
+    double ms_score, ms_trace;             /* HIP events: the score pass; fill and walk of the trace pass, summed over the batches */
+    int64_t n_shifted;                     /* aligned contigs with at least one short or long codon */
+} mgta_frameshift_stats;
+int mgta_seqs_frameshift(mgta_ctx *, const char *nucl, const uint64_t *offsets /* [n + 1] */, int64_t n,
+                         const char *refs, const uint64_t *ref_offsets /* [n_ref + 1] */, int64_t n_ref,
+                         const int8_t *sub /* [27 * 27] */, int32_t gap_open, int32_t gap_extend, int32_t frameshift,
+                         mgta_frameshift_rec *recs /* [n] */, int32_t *scores /* [n * n_ref] or NULL; INT32_MIN = no score */,
+                         char *path /* [offsets[n] + n * 4096] or NULL */, int32_t *path_len /* [n] or NULL */,
+                         mgta_frameshift_stats *stats /* may be NULL */);
+
+/* ------------------------------------------------------------------------------------------------
  * Contigs that two references explain better than one (the place of the chimera removal in the reference's bin/post_proc.sh:89-95,
  * which runs `uchime` on the representatives; that tool is not part of the reference, and the rule below is this library's own: it is
  * not uchime's and is not checked against it).  Needs no graph.  Contigs, references, residue classes, sub, gap_open and gap_extend

@@ -191,6 +191,13 @@ class NearestStats(C.Structure):
         return {n: getattr(self, n) for n, _ in self._fields_}
 
 
+class FrameshiftStats(C.Structure):
+    _fields_ = NearestStats._fields_ + [("n_shifted", C.c_int64)]
+
+    def as_dict(self):
+        return {n: getattr(self, n) for n, _ in self._fields_}
+
+
 class ChimeraRec(C.Structure):
     _fields_ = [("status", C.c_int32), ("ref", C.c_int32), ("score", C.c_int32), ("brk", C.c_int32), ("left_ref", C.c_int32), ("left_score", C.c_int32),
                 ("right_ref", C.c_int32), ("right_score", C.c_int32), ("two", C.c_int32), ("one", C.c_int32), ("gain", C.c_int32)]
@@ -341,6 +348,8 @@ SYMBOLS = {
     "mgta_seqs_nearest": (C.c_int, [C.c_void_p, C.c_char_p, C.c_void_p, C.c_int64, C.c_char_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_int32, C.c_int32,
                                     C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "mgta_ctx_set_nearest_batch": (C.c_int, [C.c_void_p, C.c_int64]),
+    "mgta_seqs_frameshift": (C.c_int, [C.c_void_p, C.c_char_p, C.c_void_p, C.c_int64, C.c_char_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_int32, C.c_int32,
+                                       C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "mgta_seqs_chimera": (C.c_int, [C.c_void_p, C.c_char_p, C.c_void_p, C.c_int64, C.c_char_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_int32, C.c_int32,
                                     C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p]),
     "mgta_ctx_set_chimera_segment": (C.c_int, [C.c_void_p, C.c_int64]),

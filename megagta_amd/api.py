@@ -16,6 +16,7 @@ import numpy as np
 
 from . import _lib
 from .chimera import REC as _chimera_rec
+from .frameshift import REC as _frameshift_rec
 from ._lib import MegaGtaError, check
 
 NUM_BUCKETS = 65536
@@ -398,6 +399,39 @@ class Context:
         check(self._L.mgta_seqs_nearest(self.h, b"".join(raw), offsets.ctypes.data, n, b"".join(rraw), roffsets.ctypes.data, n_ref, table.ctypes.data,
                                         int(gap_open), int(gap_extend), recs.ctypes.data, sc.ctypes.data if scores and sc.size else None,
                                         p.ctypes.data if paths else None, plen.ctypes.data if paths else None, C.byref(st)), "mgta_seqs_nearest")
+        out = dict(recs=recs[:n], stats=st.as_dict())
+        if scores:
+            out["scores"] = sc
+        if paths:
+            out["paths"] = [p[int(offsets[i]) + i * 4096:int(offsets[i]) + i * 4096 + int(plen[i])].tobytes().decode() for i in range(n)]
+        return out
+
+    def frameshift(self, nucl, refs, sub, gap_open: int, gap_extend: int, frameshift: int, scores: bool = False, paths: bool = False) -> dict:
+        """mgta_seqs_frameshift: for every NUCLEOTIDE contig of `nucl` (str or bytes) the closest protein of `refs`, with shifts of the
+        reading frame by one nucleotide at the cost `frameshift` (the rule: include/megagta_hip.h); sub, gap_open, gap_extend as for
+        `nearest` -> dict(recs = structured array [n] (frameshift.REC) with status, ref, score, ref_from, ref_to, n_match, n_ident,
+        n_insert, n_delete, n_short, n_long; scores = int32[n, n_ref] when asked for, INT32_MIN where a pair has no score; paths =
+        list of str over M / < / > / I / D when asked for; stats).  `set_nearest_batch` sets this call's trace batch too.  Needs no
+        graph."""
+        raw = [s if isinstance(s, (bytes, bytearray)) else str(s).encode("latin-1") for s in nucl]
+        rraw = [s if isinstance(s, (bytes, bytearray)) else str(s).encode("latin-1") for s in refs]
+        n, n_ref = len(raw), len(rraw)
+        table = np.ascontiguousarray(sub, dtype=np.int8)
+        if table.shape != (27, 27):
+            raise ValueError("sub must be int8[27, 27]")
+        offsets, roffsets = np.zeros(n + 1, dtype=np.uint64), np.zeros(n_ref + 1, dtype=np.uint64)
+        if n:
+            np.cumsum([len(s) for s in raw], out=offsets[1:])
+        if n_ref:
+            np.cumsum([len(s) for s in rraw], out=roffsets[1:])
+        recs = np.zeros(max(1, n), dtype=FRAMESHIFT_REC)
+        sc = np.zeros((n, n_ref), dtype=np.int32) if scores else None
+        p = np.zeros(int(offsets[n]) + n * 4096 + 1, dtype=np.uint8) if paths else None
+        plen = np.zeros(max(1, n), dtype=np.int32) if paths else None
+        st = _lib.FrameshiftStats()
+        check(self._L.mgta_seqs_frameshift(self.h, b"".join(raw), offsets.ctypes.data, n, b"".join(rraw), roffsets.ctypes.data, n_ref, table.ctypes.data,
+                                           int(gap_open), int(gap_extend), int(frameshift), recs.ctypes.data, sc.ctypes.data if scores and sc.size else None,
+                                           p.ctypes.data if paths else None, plen.ctypes.data if paths else None, C.byref(st)), "mgta_seqs_frameshift")
         out = dict(recs=recs[:n], stats=st.as_dict())
         if scores:
             out["scores"] = sc
@@ -852,6 +886,10 @@ NEAREST_REC = np.dtype([("status", np.int32), ("ref", np.int32), ("score", np.in
 
 # mgta_chimera_rec (defined once, beside the readers of the step's files)
 CHIMERA_REC = _chimera_rec
+
+
+# mgta_frameshift_rec (defined once, beside the readers of the step's files)
+FRAMESHIFT_REC = _frameshift_rec
 
 
 def link_pairs(pairs, n_residues, lens) -> dict:

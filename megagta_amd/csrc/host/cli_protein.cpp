@@ -5,6 +5,7 @@
 #include <cmath>
 #include <cstring>
 #include "cli.hpp"
+#include "../frameshift_seq.hpp"
 
 namespace mgta_cli {
 // a device call has refused its input: the [ERROR] line of the command, and its exit code
@@ -426,7 +427,76 @@ static std::string parse_scoring(const std::string &spec, int8_t *sub) {
         for (size_t k = 0; k < cols.size(); ++k) sub[row_cls[r] * 27 + cols[k]] = (int8_t)rows[r][k];
     return "";
 }
+// `nearest --frameshift`: the same place for the NUCLEOTIDE contigs, with shifts of the reading frame (the rule is mgta_seqs_frameshift's
+// own).  Writes <out_prefix>_frameshift.txt, _corr_prot.fasta and _corr_nucl.fasta.  Formats: INTEGRATION.md 2l'.
+static int nearest_frameshift(int argc, char **argv) {
+    if (argc != 9) {
+        fprintf(stderr, "Usage: megagta nearest --frameshift <cost> <ref.faa> <nucl.fasta> <out_prefix> <gap_open> <gap_extend> <scoring>\n");
+        return 1;
+    }
+    RssLine rss;
+    const std::string ref_fasta = argv[3], fasta = argv[4], out_prefix = argv[5];
+    long long cost = 0, gap_open = 0, gap_extend = 0;
+    if (!int_arg("nearest", "frameshift cost", argv[2], &cost)) return 1;
+    if (cost < 0 || cost > 1024) { fprintf(stderr, "    [ERROR] nearest: frameshift cost = %lld: 0 <= cost <= 1024 is needed: nothing written\n", cost); return 1; }
+    if (!int_arg("nearest", "gap_open", argv[6], &gap_open) || !int_arg("nearest", "gap_extend", argv[7], &gap_extend)) return 1;
+    if (gap_extend < 0 || gap_extend > gap_open || gap_open > 1024) {
+        fprintf(stderr, "    [ERROR] nearest: gap_open = %lld, gap_extend = %lld: 0 <= gap_extend <= gap_open <= 1024 is needed: nothing written\n", gap_open, gap_extend);
+        return 1;
+    }
+    int8_t sub[27 * 27];
+    const std::string bad = parse_scoring(argv[8], sub);
+    if (!bad.empty()) { fprintf(stderr, "    [ERROR] nearest: scoring: %s: nothing written\n", bad.c_str()); return 1; }
+    const FastaRecords in = read_fasta(fasta), ref = read_fasta(ref_fasta);
+    const int64_t n = in.n(), n_ref = ref.n();
+    const auto [refs, roffsets] = clean_references(ref);
+    const double t0 = now_s();
+    mgta_ctx *ctx = ctx_get();
+    std::vector<mgta_frameshift_rec> recs((size_t)n + 1);
+    std::vector<char> path((size_t)in.seqs.size() + (size_t)n * 4096 + 1);
+    std::vector<int32_t> path_len((size_t)n + 1);
+    mgta_frameshift_stats st;
+    if (mgta_seqs_frameshift(ctx, in.seqs.data(), in.offsets.data(), n, refs.data(), roffsets.data(), n_ref, sub, (int32_t)gap_open, (int32_t)gap_extend, (int32_t)cost,
+                             recs.data(), nullptr, path.data(), path_len.data(), &st) != MGTA_OK)
+        return nothing_written("nearest", ctx);
+    logf("nearest with frameshifts of %lld records among %lld references: %lld unaligned, %lld shifted; %lld cells in %lld segments, %lld workgroups of %lld waves, "
+         "%lld per CU, %lld B of LDS; %lld trace cells in %lld batches; peak %lld B; score %.1f ms, trace %.1f ms; wall %.3f s", (long long)st.n_seqs, (long long)st.n_refs,
+         (long long)st.n_unaligned, (long long)st.n_shifted, (long long)st.n_cells, (long long)st.n_segments, (long long)st.grid_blocks, (long long)st.waves_per_block,
+         (long long)st.blocks_per_cu, (long long)st.lds_bytes, (long long)st.n_trace_cells, (long long)st.n_batches, (long long)st.peak_bytes, st.ms_score, st.ms_trace,
+         now_s() - t0);
+    std::string table = "#contig\tstatus\tref\tscore\tidentity\tlen\tref_len\tref_from\tref_to\tmatch\tident\tinsert\tdelete\tshort\tlong\tshifts\n", prot, nucl;
+    char num[64];
+    mgta::Corrected corr;
+    for (size_t u = 0; u < (size_t)n; ++u) {
+        const mgta_frameshift_rec &r = recs[u];
+        const bool un = r.status != 0;
+        const int64_t cols = (int64_t)r.n_match + r.n_short + r.n_long + r.n_insert + r.n_delete;
+        snprintf(num, sizeof num, "%.4f", cols ? (double)r.n_ident / (double)cols : 0.0);
+        const size_t L = (size_t)(in.offsets[u + 1] - in.offsets[u]);
+        std::string shifts = ".";
+        if (!un) {
+            if (!mgta::corrected_of(in.seqs.data() + in.offsets[u], L, path.data() + in.offsets[u] + u * 4096, (size_t)path_len[u], &corr)) {
+                fprintf(stderr, "    [ERROR] nearest: record %s: its path does not consume its %zu nucleotides: nothing written\n", in.names[u].c_str(), L);
+                ctx_put(ctx);
+                return 1;
+            }
+            shifts = corr.shifts;
+            prot += ">" + in.names[u] + "\n" + corr.prot + "\n";
+            nucl += ">" + in.names[u] + "\n" + corr.nucl + "\n";
+        }
+        table += in.names[u] + "\t" + (un ? "unaligned" : "aligned") + "\t" + (un ? std::string("-") : ref.names[(size_t)r.ref]) + "\t" + std::to_string(r.score) + "\t" + num +
+                 "\t" + std::to_string(L) + "\t" + std::to_string(un ? 0 : roffsets[(size_t)r.ref + 1] - roffsets[(size_t)r.ref]) + "\t" + std::to_string(r.ref_from) + "\t" +
+                 std::to_string(r.ref_to) + "\t" + std::to_string(r.n_match) + "\t" + std::to_string(r.n_ident) + "\t" + std::to_string(r.n_insert) + "\t" +
+                 std::to_string(r.n_delete) + "\t" + std::to_string(r.n_short) + "\t" + std::to_string(r.n_long) + "\t" + shifts + "\n";
+    }
+    write_or_die(out_prefix + "_frameshift.txt", table);
+    write_or_die(out_prefix + "_corr_prot.fasta", prot);
+    write_or_die(out_prefix + "_corr_nucl.fasta", nucl);
+    ctx_put(ctx);
+    return 0;
+}
 int main_nearest(int argc, char **argv) {
+    if (argc >= 2 && !strcmp(argv[1], "--frameshift")) return nearest_frameshift(argc, argv);
     if (argc != 7) { fprintf(stderr, "Usage: megagta nearest <ref.faa> <prot.fasta> <out_prefix> <gap_open> <gap_extend> <scoring>\n"); return 1; }
     RssLine rss;
     const std::string ref_fasta = argv[1], fasta = argv[2], out_prefix = argv[3];

@@ -69,6 +69,11 @@ USAGE = """Usage:
     --nearest-scoring S       MATCH,MISMATCH or a substitution matrix file in NCBI format [5,-4: this driver's own default]
     --nearest-gap-open N      cost of a gap's first residue [10: this driver's own default]
     --nearest-gap-extend N    cost of every further residue of a gap [1: this driver's own default]
+    --frameshift     behind --nearest where that runs: per gene the closest reference protein (column 4 of the gene list) of every NUCLEOTIDE
+                     contig, nucl_merged[_rmdup][_rep_seqs].fasta, with shifts of the reading frame by one nucleotide found and repaired:
+                     contigs/<gene>/nucl_merged[_rmdup][_rep_seqs]_frameshift.txt, ..._corr_prot.fasta and ..._corr_nucl.fasta; scoring and
+                     gap costs are the --nearest-* options; the rule is this project's own, not FrameBot's (GPU 0)
+    --frameshift-cost N       cost of a shift of one nucleotide, 0 .. 1024 [10: this driver's own default]
     --chimera        after every other step: per gene the protein contigs that two of the gene's reference proteins (column 4 of the gene
                      list) explain better than one: contigs/<gene>/prot_merged[_rmdup][_rep_seqs]_chimera.txt (every contig, its break and
                      its two parents) and prot_..._nochim.fasta, nucl_..._nochim.fasta (the contigs that are not chimeric); scoring and gap
@@ -147,6 +152,8 @@ class Opt:
         self.nearest_scoring = "5,-4"
         self.nearest_gap_open = 10
         self.nearest_gap_extend = 1
+        self.frameshift = False
+        self.frameshift_cost = 10
         self.chimera = False
         self.chimera_min_seg = 10
         self.chimera_min_gain = 15
@@ -167,6 +174,7 @@ LONG = ["help", "read=", "12=", "out-dir=", "memory=", "gpu-mem=", "min-contig-l
         "min-count=", "max-tip-len=", "no-mercy", "keep-tmp-files", "mem-flag=", "version", "verbose", "continue", "gene-list=",
         "prune-len=", "low-cov-penalty=", "bin=", "one-process-per-step", "gpus=", "coverage", "match-reads", "derep", "align", "posterior", "cluster",
         "cluster-dist=", "cluster-min-overlap=", "cluster-dists=", "nearest", "nearest-scoring=", "nearest-gap-open=", "nearest-gap-extend=",
+        "frameshift", "frameshift-cost=",
         "chimera", "chimera-min-seg=", "chimera-min-gain=", "taxon-abund", "sample-abund", "pileup", "min-anchors=", "min-overlap=",
         "max-mismatch-permille=", "min-depth=", "min-alt-permille=", "phase", "max-span=", "min-link=", "min-hap-permille=",
         "gapped", "max-gap=", "gap-open=", "gap-extend="]
@@ -228,6 +236,8 @@ def parse_opt(argv):
         elif o == "--nearest-scoring": opt.nearest_scoring = v
         elif o == "--nearest-gap-open": opt.nearest_gap_open = int(v)
         elif o == "--nearest-gap-extend": opt.nearest_gap_extend = int(v)
+        elif o == "--frameshift": opt.frameshift = True
+        elif o == "--frameshift-cost": opt.frameshift_cost = int(v)
         elif o == "--chimera": opt.chimera = True
         elif o == "--chimera-min-seg": opt.chimera_min_seg = int(v)
         elif o == "--chimera-min-gain": opt.chimera_min_gain = int(v)
@@ -334,6 +344,8 @@ def check_opt():
         raise Usage("--cluster-min-overlap should be >= 1")
     if not 0 <= opt.nearest_gap_extend <= opt.nearest_gap_open <= 1024:
         raise Usage("--nearest-gap-open and --nearest-gap-extend should satisfy 0 <= extend <= open <= 1024")
+    if not 0 <= opt.frameshift_cost <= 1024:
+        raise Usage("--frameshift-cost should be between [0, 1024]")
     if not 1 <= opt.chimera_min_seg <= 4096:
         raise Usage("--chimera-min-seg should be between [1, 4096]")
     if not 1 <= opt.chimera_min_gain <= 1 << 20:
@@ -798,6 +810,21 @@ def nearest(k):
         write_cp()
 
 
+def frameshift(k):
+    """--frameshift: per gene the closest reference protein of every NUCLEOTIDE contig, with shifts of the reading frame by one
+    nucleotide found and repaired (`megagta nearest --frameshift`, GPU 0; no graph is needed, k only names the step).  The contigs are
+    the nucleotide companion of what --nearest reads: the representatives when --cluster runs too, else what --derep kept when that flag
+    runs, else all; references, scoring and gap costs are those of --nearest, which need not run.  Its checkpoints follow those of
+    --nearest, so `--continue` works under any combination."""
+    stem = "/nucl_merged" + ("_rmdup" if opt.derep else "") + ("_rep_seqs" if opt.cluster else "")
+    for gene in opt.gene_info:
+        prefix = opt.out_dir + "contigs/" + gene + stem
+        if should_run():
+            run_step([opt.bin, "nearest", "--frameshift", str(opt.frameshift_cost), opt.gene_info[gene][2], prefix + ".fasta", prefix, str(opt.nearest_gap_open),
+                      str(opt.nearest_gap_extend), opt.nearest_scoring], "Placing the nucleotide contigs of %s on the references with frameshifts" % gene)
+        write_cp()
+
+
 def chimera(k):
     """--chimera: per gene the protein contigs that two reference proteins explain better than one, and the contigs without them
     (`megagta chimera`, GPU 0; no graph is needed, k only names the step).  Contigs, references, scoring and gap costs are those of
@@ -939,6 +966,8 @@ def after_search(k):
         cluster(k)
     if opt.nearest:
         nearest(k)
+    if opt.frameshift:
+        frameshift(k)
     if opt.chimera:
         chimera(k)
     if opt.taxon_abund:
