@@ -637,6 +637,57 @@ int mgta_reads_phase(const mgta_reads *reads, int reads_reversed, const mgta_rea
 int mgta_ctx_set_phase_chunk(mgta_ctx *, uint32_t slots);   /* fragment slots per queue grab, 0 = the library's; a switch for tests, moves no output */
 
 /* ------------------------------------------------------------------------------------------------
+ * Read recruitment by the gene's model: which reads of the library the profile HMM places in one of six frames.  The rule is this
+ * library's own; it is not HMMER's and nothing here is checked against it.  Needs no graph.
+ *   Input.     The reads [0, n_short_reads) of an uploaded library (reads_reversed as in mgta_reads_match_contigs) and a model of
+ *              mgta_hmm_load, both of this context.
+ *   Frames.    For a read of n bases: frame f in {0, 1, 2} is the read as sequenced from base f, frame f in {3, 4, 5} its reverse
+ *              complement from base f - 3.  Frame f has floor((n - f mod 3) / 3) codons (none when n < f mod 3), translated by the
+ *              standard code into the upper-case letters KNKNTTTTRSRSIIMIQHQHPPPPRRRRLLLLEDEDAAAAGGGGVVVV*Y*YSSSS*CWCLFLF (codon =
+ *              16 b0 + 4 b1 + b2, A C G T = 0 .. 3).  The library holds A, C, G, T only: there is no X.
+ *   Stretch.   A frame's stretch is its longest run of residues without a stop; among equally long runs the first (lowest aa_from,
+ *              0-based in the frame's translation).  A stretch shorter than min_aa (>= 1) is not scored, nor is an empty one.
+ *   Score.     Exactly what mgta_seqs_align returns for the stretch as a protein sequence (the block of mgta_seqs_align below: global
+ *              in the stretch, local in the model, fp64, every + one IEEE add, the maximum first and then + e, the first candidate
+ *              wins a tie): score bit for bit, model_to the lowest end column that reaches it, model_from the column of the first
+ *              match state of the path its traceback walks.  No traceback is made here: every candidate of the recurrence carries
+ *              the column it entered the model at, and the candidate that wins a maximum hands its column on, under the same tie
+ *              order.  A stretch whose score is -inf is scored and unaligned.
+ *   Best.      The scored frame with the highest score, the lowest frame number on equality.  status 0: aa_from, aa_len, frame,
+ *              score, model_from, model_to of that frame.  status 1 (every scored frame is -inf): score -inf, frame, aa_from and
+ *              aa_len of the lowest scored frame, model_from = model_to = 0.  status 2 (no scored frame): score -inf, zeros.
+ *   Recruited. status == 0 and score >= min_score.  min_score is in nats; -inf, +inf and an exact score are legal thresholds.  The
+ *              default, 20 bits = 20 * 0.6931471805599453 nats, is a knob, not a calibrated value: no E-values are computed.
+ * Outputs: bit r of hit_bits[r / 64] = read r is recruited (reads at and behind n_short_reads have no bit and no record);
+ * recs[r] when given; col_depth[j - 1], j = 1 .. M, when given = the number of recruited reads with model_from <= j <= model_to.
+ * stats: n_reads scanned, n_frames_scored, n_cells = the sum of aa_len * M over the scored frames, n_unaligned (status 1),
+ * n_unscored (status 2), n_recruited and n_recruited_frame[f] by best frame.  Everything but ms_*, blocks_per_cu, waves_per_block,
+ * grid_blocks, lds_bytes, msc_in_lds, rows_per_wave and chunk is a function of (tables, reads, params) alone, the same to the last
+ * bit for every chunk and across runs: integer atomics only, one writer per record.
+ * It is global in the stretch: a read that runs over an end of the gene has to place its flank and scores low.  One stretch per
+ * frame, no flanking states, no Forward score, no prefilter, one device; the reverse model is not used.
+ * Limits: a read of more than 3 * 4096 + 2 bases among the scanned ones is MGTA_EINVAL naming the first such read, with nothing
+ * written.  MGTA_EINVAL also: NULL context / model / reads / hit_bits (n_short_reads > 0), n_short_reads above the upload, a model
+ * or reads of another context, min_aa < 1, a NaN min_score.  n_short_reads = 0: col_depth and stats all zero.
+ * ------------------------------------------------------------------------------------------------ */
+typedef struct mgta_recruit_params { int32_t min_aa; int32_t pad; double min_score; } mgta_recruit_params;
+typedef struct mgta_recruit_rec { double score; int32_t model_from, model_to; uint16_t aa_from, aa_len; uint8_t frame, status; uint8_t pad[2]; } mgta_recruit_rec;
+typedef struct mgta_recruit_stats {
+    int64_t n_reads, n_frames_scored, n_cells;
+    int64_t n_unaligned, n_unscored, n_recruited;
+    int64_t n_recruited_frame[6];
+    int64_t blocks_per_cu, waves_per_block, grid_blocks, lds_bytes, msc_in_lds;   /* as in mgta_align_stats */
+    int64_t rows_per_wave;                 /* residues a wave sweeps back to back: 256, or what the longest read needs */
+    int64_t chunk;                         /* reads per queue grab of this call */
+    double ms_scan, ms_fill;               /* HIP events: the length scan; translation, fill and records */
+} mgta_recruit_stats;
+int mgta_reads_recruit(mgta_ctx *, const mgta_hmm *, const mgta_reads *, int reads_reversed, uint64_t n_short_reads,
+                       const mgta_recruit_params * /* NULL = defaults: min_aa 20, min_score 20 bits in nats */,
+                       uint64_t *hit_bits /* [ceil(n_short_reads / 64)] */, mgta_recruit_rec *recs /* [n_short_reads] or NULL */,
+                       uint64_t *col_depth /* [M] or NULL */, mgta_recruit_stats *stats /* or NULL */);
+int mgta_ctx_set_recruit_chunk(mgta_ctx *, uint32_t reads);   /* reads per queue grab (at most 64 are taken), 0 = the library's; a switch for tests, moves no output */
+
+/* ------------------------------------------------------------------------------------------------
  * De-replication ("get the unique merged contigs", the first step of the reference's bin/post_proc.sh:50-55: `Clustering.jar derep`,
  * then `ReadSeq.jar rm-dupseq -d`, both from a submodule the reference does not ship).  Needs no graph.  Sequence i =
  * seqs[offsets[i] .. offsets[i + 1]), a byte string compared byte for byte: no case folding, no reverse complement (a gene's contigs

@@ -256,6 +256,27 @@ class PhaseStats(C.Structure):
         return {n: getattr(self, n) for n, _ in self._fields_}
 
 
+class RecruitParams(C.Structure):
+    _fields_ = [("min_aa", C.c_int32), ("pad", C.c_int32), ("min_score", C.c_double)]
+
+
+class RecruitRec(C.Structure):
+    _fields_ = [("score", C.c_double), ("model_from", C.c_int32), ("model_to", C.c_int32), ("aa_from", C.c_uint16), ("aa_len", C.c_uint16),
+                ("frame", C.c_uint8), ("status", C.c_uint8), ("pad", C.c_uint8 * 2)]
+
+
+class RecruitStats(C.Structure):
+    _fields_ = [("n_reads", C.c_int64), ("n_frames_scored", C.c_int64), ("n_cells", C.c_int64), ("n_unaligned", C.c_int64), ("n_unscored", C.c_int64),
+                ("n_recruited", C.c_int64), ("n_recruited_frame", C.c_int64 * 6), ("blocks_per_cu", C.c_int64), ("waves_per_block", C.c_int64),
+                ("grid_blocks", C.c_int64), ("lds_bytes", C.c_int64), ("msc_in_lds", C.c_int64), ("rows_per_wave", C.c_int64), ("chunk", C.c_int64),
+                ("ms_scan", C.c_double), ("ms_fill", C.c_double)]
+
+    def as_dict(self):
+        d = {n: getattr(self, n) for n, _ in self._fields_}
+        d["n_recruited_frame"] = list(self.n_recruited_frame)
+        return d
+
+
 EDGE_SINK = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_int32, C.c_int32, C.POINTER(C.c_int64), C.POINTER(C.c_uint16), C.c_int64,
                         C.POINTER(C.c_uint16), C.c_int64, C.POINTER(C.c_uint32), C.c_int64)
 CONTIG_SINK = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_void_p, C.c_int64,
@@ -328,6 +349,8 @@ SYMBOLS = {
     "mgta_reads_phase": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p,
                                   C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p]),
     "mgta_ctx_set_phase_chunk": (C.c_int, [C.c_void_p, C.c_uint32]),
+    "mgta_reads_recruit": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_uint64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "mgta_ctx_set_recruit_chunk": (C.c_int, [C.c_void_p, C.c_uint32]),
     "mgta_seqs_derep": (C.c_int, [C.c_void_p, C.c_char_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "mgta_ctx_set_derep_hash_bits": (C.c_int, [C.c_void_p, C.c_int]),
     "mgta_seqs_align": (C.c_int, [C.c_void_p, C.c_void_p, C.c_char_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),

@@ -191,6 +191,37 @@ class Context:
                                        joint.ctypes.data if joint.size else None, int(joint_cap), C.byref(st)), "mgta_reads_phase")
         return dict(site_counts=counts, pair_off=pair_off, joint=joint[:int(pair_off[-1])], site_off=off.astype(np.int64), site_pos=pos, stats=st.as_dict())
 
+    def set_recruit_chunk(self, reads: int = 0):
+        """reads a wave of Context.recruit takes per visit to the queue head (0 = the library's choice, at most 64 are taken); moves
+        no output -- a switch for tests"""
+        check(self._L.mgta_ctx_set_recruit_chunk(self.h, int(reads)), "mgta_ctx_set_recruit_chunk")
+
+    def recruit(self, hmm: "DeviceHmm", reads: "Reads", n_short_reads: int | None = None, params: dict | None = None, recs: bool = True, cols: bool = True,
+                reads_reversed: bool = True) -> dict:
+        """mgta_reads_recruit: which of the first n_short_reads reads (default: all of `reads`) the model places in one of six frames,
+        by the rule of include/megagta_hip.h.  params = dict(min_aa=, min_score= in nats, or min_bits=); missing = 20 residues and 20
+        bits.  -> dict(hit_bits = uint64[ceil(n / 64)], bits = bool[n], recs = recruit.REC[n] or None, col_depth = uint64[M] or None,
+        stats).  Needs no graph."""
+        from .recruit import LN2, REC
+        unknown = set(params or {}) - {"min_aa", "min_score", "min_bits"}
+        if unknown:
+            raise ValueError(f"unknown recruit parameters: {sorted(unknown)}")
+        p = dict(params or {})
+        if "min_score" in p and "min_bits" in p:
+            raise ValueError("recruit parameters: min_score (nats) or min_bits, not both")
+        par = _lib.RecruitParams()
+        par.min_aa = int(p.get("min_aa", 20))
+        par.min_score = float(p["min_score"]) if "min_score" in p else float(p.get("min_bits", 20.0)) * LN2
+        ns = reads.n_reads if n_short_reads is None else int(n_short_reads)
+        words = np.zeros(max(1, (ns + 63) // 64), dtype=np.uint64)          # (never an empty buffer: NULL is an error of its own)
+        r = np.zeros(max(1, ns), dtype=REC) if recs else None
+        depth = np.zeros(max(1, hmm.M), dtype=np.uint64) if cols else None
+        st = _lib.RecruitStats()
+        check(self._L.mgta_reads_recruit(self.h, hmm.h, reads.h, int(bool(reads_reversed)), ns, C.byref(par), words.ctypes.data, r.ctypes.data if recs else None,
+                                         depth.ctypes.data if cols else None, C.byref(st)), "mgta_reads_recruit")
+        bits = np.unpackbits(words.view(np.uint8), bitorder="little")[:ns].astype(bool)
+        return dict(hit_bits=words[:(ns + 63) // 64], bits=bits, recs=r[:ns] if recs else None, col_depth=depth[:hmm.M] if cols else None, stats=st.as_dict())
+
     def set_derep_hash_bits(self, bits: int = 64):
         """bits of both hashes `derep` keeps (1 .. 64, the default): with a few bits nearly every key collides.  The result does not
         depend on it; only stats["n_compares"] does."""

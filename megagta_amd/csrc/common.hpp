@@ -152,6 +152,7 @@ struct mgta_ctx {
     int share_hash_bits = 64;    // mgta_ctx_set_share_hash_bits: bits of the hash the count table of mgta_contig_share_coverage keeps (fewer = more collisions, same answers)
     uint32_t pileup_chunk = 0;   // mgta_ctx_set_pileup_chunk: reads a group takes per visit to the queue head of mgta_reads_pileup (0 = the library's choice)
     uint32_t phase_chunk = 0;    // mgta_ctx_set_phase_chunk: fragment slots a group takes per visit to the queue head of mgta_reads_phase (0 = the library's choice)
+    uint32_t recruit_chunk = 0;  // mgta_ctx_set_recruit_chunk: reads a wave takes per visit to the queue head of mgta_reads_recruit (0 = the library's choice)
     const void *last_large = nullptr;
     uint64_t last_n_large = 0;
     mgta::DevBuf acc_large;

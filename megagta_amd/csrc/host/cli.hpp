@@ -45,7 +45,7 @@ int writer_join();                                   // the graph files of the l
 int contigs_join(bool free_text);                    // the same for the contigs file of the last denovo
 PackedReads &lib_get(const std::string &bin_path, const std::string &lib_prefix, const std::string &extra, bool extra_is_assist, PackedReads &local,
                      PackedReads::Mark &mk);
-// the library alone, as matchreads, samplecov and pileup take it, and a library's copy on the device (freed with mgta_reads_free)
+// the library alone, as matchreads, samplecov, pileup and recruit take it, and a library's copy on the device (freed with mgta_reads_free)
 PackedReads &reads_open(const std::string &lib, PackedReads &local, uint64_t *n_reads);
 mgta_reads *reads_upload(mgta_ctx *ctx, const PackedReads &pr);
 // the three ways to a graph (the rule is written once, above them in session.cpp), and the end of a step's use of one
@@ -177,7 +177,7 @@ void search_plan(size_t ns, int *window, int *rate, long long *knee, int *rate2)
 // ---- the sub-commands ------------------------------------------------------------------------------------------------------------------
 typedef int SubCommand(int argc, char **argv);
 SubCommand main_buildgraph, main_denovo, main_search, main_findstart, main_filterbylen, main_translate, main_buildlib;     // cli_graph.cpp
-SubCommand main_coverage, main_sharecov, main_matchreads, main_samplecov, main_pileup;                                      // cli_reads.cpp
+SubCommand main_coverage, main_sharecov, main_matchreads, main_samplecov, main_pileup, main_recruit;                            // cli_reads.cpp
 SubCommand main_derep, main_align, main_posterior, main_cluster, main_clustertree, main_nearest, main_chimera;              // cli_protein.cpp
 SubCommand main_libdump, main_sdbgcopy, main_sdbgmerge, main_hmmdump, main_searchplan, main_dumpversion;                    // cli_dev.cpp
 

@@ -1,5 +1,6 @@
 // cli_reads.cpp — coverage, sharecov (graph_counted), matchreads, samplecov and pileup (graph_any + the read library): the contigs of a
-// FASTA set against the graph and the reads it was built from.  File formats: INTEGRATION.md; megagta_amd/*.py print the same bytes.
+// FASTA set against the graph and the reads it was built from; recruit: the read library against a gene's model, without a graph.
+// File formats: INTEGRATION.md; megagta_amd/*.py print the same bytes.
 #include <algorithm>
 #include <cstring>
 #include "cli.hpp"
@@ -123,6 +124,83 @@ int main_matchreads(int argc, char **argv) {
     }
     if (fclose(f) != 0) die("short write to %s", path.c_str());
     graph_done(g);
+    ctx_put(ctx);
+    return 0;
+}
+
+// ---- recruit: the reads of the library that a gene's profile HMM places in one of six frames (mgta_reads_recruit).  No graph is loaded
+// and a worker's resident graphs and library stay as they are.  The rule and the file formats are this project's own: INTEGRATION.md
+// 2h'; megagta_amd/recruit.py prints the same bytes.
+int main_recruit(int argc, char **argv) {
+    const char *usage = "Usage: megagta recruit <model.hmm> <read.lib> <out_prefix> [--min-bits B] [--min-aa N]\n";
+    if (argc < 4) { fputs(usage, stderr); return 1; }
+    double min_bits = 20.0;
+    long long min_aa = 20;
+    for (int i = 4; i < argc; ++i) {
+        const std::string a = argv[i];
+        if ((a != "--min-bits" && a != "--min-aa") || i + 1 >= argc) { fputs(usage, stderr); return 1; }
+        const char *text = argv[++i];
+        if (a == "--min-aa") {
+            if (!parse_ll(text, &min_aa) || min_aa < 1 || min_aa > 4096) { fprintf(stderr, "megagta recruit: --min-aa %s is not a count of 1 .. 4096 residues\n%s", text, usage); return 1; }
+        } else {
+            char *end = nullptr;
+            min_bits = strtod(text, &end);
+            if (end == text || *end || min_bits != min_bits) { fprintf(stderr, "megagta recruit: --min-bits %s is not a number\n%s", text, usage); return 1; }
+        }
+    }
+    RssLine rss;
+    const std::string model = argv[1], lib = argv[2], out_prefix = argv[3];
+    const std::vector<LibRow> libs = read_lib_table(lib);
+    double t0 = now_s();
+    PackedReads local;
+    uint64_t n_reads = 0;
+    const PackedReads &pr = reads_open(lib, local, &n_reads);
+    if (!libs.empty() && (uint64_t)(libs.back().to + 1) != n_reads)
+        die("recruit: %s.lib_info names %lld reads, %s.bin holds %llu", lib.c_str(), libs.back().to + 1, lib.c_str(), (unsigned long long)n_reads);
+    logf("%llu reads, %llu total bases (load %.3f s)", (unsigned long long)n_reads, (unsigned long long)pr.start.back(), now_s() - t0);
+    t0 = now_s();
+    mgta_ctx *ctx = ctx_get();
+    int M = 0;
+    mgta_hmm *hmm = upload_hmm(ctx, model, &M);
+    mgta_reads *rd = reads_upload(ctx, pr);
+    std::vector<uint64_t> bits((size_t)((n_reads + 63) / 64) + 1), depth((size_t)M + 1);
+    std::vector<mgta_recruit_rec> recs((size_t)n_reads + 1);
+    const mgta_recruit_params par{(int32_t)min_aa, 0, min_bits * 0.6931471805599453};
+    mgta_recruit_stats st;
+    if (mgta_reads_recruit(ctx, hmm, rd, 1, n_reads, &par, bits.data(), recs.data(), depth.data(), &st) != MGTA_OK) die("mgta_reads_recruit: %s", mgta_last_error());
+    mgta_reads_free(rd);
+    mgta_hmm_free(hmm);
+    logf("recruited reads of %s (%d columns, >= %g bits, stretches >= %lld residues): %lld of %lld reads, %lld frames scored, %lld cells, %lld reads unaligned, %lld "
+         "unscored; %lld rows per wave, %lld reads per grab, %lld waves per workgroup, %lld per CU, LDS %lld (scan %.1f ms, fill %.1f ms); wall %.3f s", model.c_str(), M,
+         min_bits, min_aa, (long long)st.n_recruited, (long long)st.n_reads, (long long)st.n_frames_scored, (long long)st.n_cells, (long long)st.n_unaligned,
+         (long long)st.n_unscored, (long long)st.rows_per_wave, (long long)st.chunk, (long long)st.waves_per_block, (long long)st.blocks_per_cu, (long long)st.lds_bytes,
+         st.ms_scan, st.ms_fill, now_s() - t0);
+    std::string fa, table = "#read\tframe\taa_from\taa_len\tbits\tmodel_from\tmodel_to\n", cols = "#column\tdepth\n", summary;
+    std::vector<long long> per_lib(libs.size(), 0);
+    size_t s = 0;
+    for (uint64_t r = 0; r < n_reads; ++r) {
+        if (!((bits[(size_t)(r >> 6)] >> (r & 63)) & 1)) continue;
+        const uint64_t s0 = pr.start[(size_t)r], len = pr.start[(size_t)r + 1] - s0;
+        fa += ">r" + std::to_string((unsigned long long)r) + "\n";
+        for (uint64_t j = 0; j < len; ++j) {                            // reversed storage -> the read as sequenced
+            const uint64_t q = s0 + (len - 1 - j);
+            fa.push_back("ACGT"[(pr.words[(size_t)(q >> 4)] >> (30 - 2 * (q & 15))) & 3]);
+        }
+        fa.push_back('\n');
+        const mgta_recruit_rec &c = recs[(size_t)r];
+        appendf(table, "%llu\t%u\t%u\t%u\t%.4f\t%d\t%d\n", (unsigned long long)r, (unsigned)c.frame, (unsigned)c.aa_from, (unsigned)c.aa_len, c.score / 0.6931471805599453,
+                c.model_from, c.model_to);
+        while (s < libs.size() && (long long)r > libs[s].to) ++s;
+        if (s < libs.size()) ++per_lib[s];
+    }
+    for (int j = 0; j < M; ++j) appendf(cols, "%d\t%llu\n", j + 1, (unsigned long long)depth[(size_t)j]);
+    appendf(summary, "reads_scanned\t%lld\nreads_scored\t%lld\nreads_recruited\t%lld\n", (long long)st.n_reads, (long long)(st.n_reads - st.n_unscored), (long long)st.n_recruited);
+    for (int f = 0; f < 6; ++f) appendf(summary, "recruited_frame%d\t%lld\n", f, (long long)st.n_recruited_frame[f]);
+    for (size_t l = 0; l < libs.size(); ++l) appendf(summary, "recruited_lib%zu\t%lld\n", l, per_lib[l]);
+    write_or_die(out_prefix + "_reads.fa", fa);
+    write_or_die(out_prefix + ".txt", table);
+    write_or_die(out_prefix + "_cols.txt", cols);
+    write_or_die(out_prefix + "_summary.txt", summary);
     ctx_put(ctx);
     return 0;
 }

@@ -256,6 +256,7 @@ static const Command kCommands[] = {
     {"sdbgmerge", main_sdbgmerge, nullptr},
     {"hmmdump", main_hmmdump, nullptr},
     {"searchplan", main_searchplan, nullptr},
+    {"recruit", main_recruit, nullptr},                                  // (the usage text and the "built here" list are pinned as recorded: tests/golden/cli_errors)
 };
 static int dispatch(int argc, char **argv) {
     if (argc < 2) {

@@ -108,7 +108,14 @@ USAGE = """Usage:
                      placements, and nucl_merged[_rmdup]_pileup_indels.txt lists the insertions and deletions the reads show
     --max-gap N               needs --gapped: most letters of an insertion or deletion [32, at most 255]
     --gap-open N              needs --gapped: what a gap costs a placement's score [4]
-    --gap-extend N            needs --gapped: what every letter of the gap costs on top [1]"""
+    --gap-extend N            needs --gapped: what every letter of the gap costs on top [1]
+    --recruit        after every other step: per gene the reads of the library that the gene's forward model places in one of six
+                     reading frames, whether or not they were assembled: contigs/<gene>/recruit_reads.fa (`>r<index in the library>`
+                     records), recruit.txt (frame, stretch, bits and model columns per read), recruit_cols.txt (recruited reads per model
+                     column) and recruit_summary.txt (reads scanned, scored and recruited, per frame and per library; with --match-reads
+                     also recruited_and_matched and assembled_fraction); the rule is this project's own, not HMMER's (GPU 0)
+    --recruit-bits B          needs --recruit: lowest score of a recruited read, in bits [20: a knob, not a calibrated value]
+    --recruit-min-aa N        needs --recruit: shortest stop-free stretch of a frame that is scored, in residues [20]"""
 
 
 class Usage(Exception):
@@ -165,6 +172,8 @@ class Opt:
         self.phase_opts = {}             # the numeric options of --phase that were given: flag -> value
         self.gapped = False
         self.gapped_opts = {}            # the numeric options of --gapped that were given: flag -> value
+        self.recruit = False
+        self.recruit_opts = {}           # the options of --recruit that were given: flag -> text
 
 
 opt = Opt()
@@ -177,7 +186,7 @@ LONG = ["help", "read=", "12=", "out-dir=", "memory=", "gpu-mem=", "min-contig-l
         "frameshift", "frameshift-cost=",
         "chimera", "chimera-min-seg=", "chimera-min-gain=", "taxon-abund", "sample-abund", "pileup", "min-anchors=", "min-overlap=",
         "max-mismatch-permille=", "min-depth=", "min-alt-permille=", "phase", "max-span=", "min-link=", "min-hap-permille=",
-        "gapped", "max-gap=", "gap-open=", "gap-extend="]
+        "gapped", "max-gap=", "gap-open=", "gap-extend=", "recruit", "recruit-bits=", "recruit-min-aa="]
 
 
 def parse_opt(argv):
@@ -258,6 +267,18 @@ def parse_opt(argv):
             if not v.isdigit():
                 raise Usage("%s %s: a count is expected" % (o, v))
             opt.gapped_opts[o] = int(v)
+        elif o == "--recruit": opt.recruit = True
+        elif o == "--recruit-bits":
+            try:
+                if float(v) != float(v):
+                    raise ValueError
+            except ValueError:
+                raise Usage("%s %s: a number of bits is expected" % (o, v))
+            opt.recruit_opts[o] = v
+        elif o == "--recruit-min-aa":
+            if not v.isdigit() or not 1 <= int(v) <= 4096:
+                raise Usage("%s %s: a count of 1 .. 4096 residues is expected" % (o, v))
+            opt.recruit_opts[o] = v
         else:
             raise Usage("Invalid option " + o)
     opt.temp_dir = opt.out_dir + "tmp/"
@@ -323,6 +344,8 @@ def check_opt():
         raise Usage("%s needs --phase: it is an option of that step" % sorted(opt.phase_opts)[0])
     if opt.phase and not opt.pileup:
         raise Usage("--phase needs --pileup: it is an option of that step")
+    if opt.recruit_opts and not opt.recruit:
+        raise Usage("%s needs --recruit: it is an option of that step" % sorted(opt.recruit_opts)[0])
     if opt.gapped_opts and not opt.gapped:
         raise Usage("%s needs --gapped: it is an option of that step" % sorted(opt.gapped_opts)[0])
     if opt.gapped and not opt.pileup:
@@ -913,6 +936,36 @@ def pileup(k):
         write_cp()
 
 
+def recruit(k):
+    """--recruit: per gene the reads of the run's library that the gene's forward model places in one of six frames (`megagta recruit`,
+    GPU 0; no graph is needed or loaded, k only names the step), and, when --match-reads ran, the share of them that lies under a
+    contig, from the two read files (megagta_amd/recruit.py, host only).  One checkpoint per gene, after every other checkpoint, so
+    `--continue` works under any combination."""
+    extra = []
+    if "--recruit-bits" in opt.recruit_opts:
+        extra += ["--min-bits", opt.recruit_opts["--recruit-bits"]]
+    if "--recruit-min-aa" in opt.recruit_opts:
+        extra += ["--min-aa", opt.recruit_opts["--recruit-min-aa"]]
+    for gene in opt.gene_info:
+        d = opt.out_dir + "contigs/" + gene
+        if should_run():
+            run_step([opt.bin, "recruit", opt.gene_info[gene][0], opt.lib, d + "/recruit"] + extra, "Recruiting the reads of %s by its model" % gene)
+            if opt.match_reads:
+                what = "Counting the recruited reads of %s under a contig" % gene
+                logging.info("--- [%s] %s ---" % (datetime.now().strftime("%c"), what))
+                root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+                if root not in sys.path:
+                    sys.path.insert(0, root)
+                from megagta_amd import recruit as rc
+                try:
+                    both, frac = rc.append_assembled(d + "/recruit_summary.txt", d + "/recruit_reads.fa", d + "/nucl_merged_match_reads.fa")
+                except (ValueError, OSError) as e:
+                    logging.error(str(e))
+                    fail_step("running \"%s\"" % what, 1)
+                logging.debug("%d recruited reads under a contig, assembled fraction %.4f" % (both, frac))
+        write_cp()
+
+
 def cluster_cutoff_tags(text):
     """the tags of --cluster-dists LIST (megagta_amd/cluster.py parse_cutoff_list; ValueError says what is wrong with an item)"""
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -978,6 +1031,8 @@ def after_search(k):
         cluster_dists(k)
     if opt.pileup:
         pileup(k)
+    if opt.recruit:
+        recruit(k)
 
 
 def main(argv=None):
