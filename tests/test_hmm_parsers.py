@@ -16,6 +16,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 BIN = os.path.join(ROOT, "megagta_amd", "bin", "megagta")
 
 CASES = [("toy/for_enone.hmm", "toy/hmm_for.txt.gz"), ("toy/rev_enone.hmm", "toy/hmm_rev.txt.gz"), ("bigm/star.hmm", "bigm/star_tables.txt.gz")]
+CASES += [(f"richm/{c}_{d}_enone.hmm", f"richm/{c}_{d}_tables.txt.gz") for c in ("r75", "r130") for d in ("for", "rev")]   # position-specific (tests/rich_models.py)
 
 
 def _same(a, b):
