@@ -15,10 +15,11 @@ from __future__ import annotations
 
 import numpy as np
 
+from . import _lib
+
 STATUS = ("aligned", "unaligned")
 TABLE_HEADER = "#contig\tlen\tstatus\tscore\tmodel_from\tmodel_to\tmatch\tinsert\tdelete\n"
-REC = np.dtype([("score", np.float64), ("status", np.int32), ("model_from", np.int32), ("model_to", np.int32), ("n_match", np.int32),
-                ("n_insert", np.int32), ("n_delete", np.int32)], align=True)
+REC = _lib.RECORDS[_lib.AlignRec]                                     # mgta_align_rec
 
 
 def record_name(header: str) -> str:

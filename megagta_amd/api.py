@@ -15,11 +15,19 @@ from dataclasses import dataclass, field
 import numpy as np
 
 from . import _lib
-from .chimera import REC as _chimera_rec
-from .frameshift import REC as _frameshift_rec
 from ._lib import MegaGtaError, check
+from .recruit import LN2
 
 NUM_BUCKETS = 65536
+
+# the record dtypes of the C ABI (one object each, derived in _lib from the struct's mirror; the stage modules name the same objects:
+# align.REC, nearest.REC, chimera.REC, frameshift.REC, recruit.REC, pileup.CONTIG_DTYPE / READ_DTYPE, gapped.PLACE_DTYPE / GAP_DTYPE)
+COV_DTYPE, SHARE_DTYPE = _lib.RECORDS[_lib.ContigCov], _lib.RECORDS[_lib.ContigShare]
+ALIGN_REC, POST_REC = _lib.RECORDS[_lib.AlignRec], _lib.RECORDS[_lib.PostRec]
+ROW_PAIR, TREE_MERGE = _lib.RECORDS[_lib.RowPair], _lib.RECORDS[_lib.TreeMerge]
+NEAREST_REC, FRAMESHIFT_REC, CHIMERA_REC = _lib.RECORDS[_lib.NearestRec], _lib.RECORDS[_lib.FrameshiftRec], _lib.RECORDS[_lib.ChimeraRec]
+_RECRUIT_REC, _CONTIG_PILEUP = _lib.RECORDS[_lib.RecruitRec], _lib.RECORDS[_lib.ContigPileup]
+_READ_PLACE, _GAP_PLACE, _GAP_REC = _lib.RECORDS[_lib.ReadPlace], _lib.RECORDS[_lib.GapPlace], _lib.RECORDS[_lib.GapRec]
 
 
 @dataclass
@@ -43,6 +51,87 @@ class EdgeStream:
         h.update(self.large.astype("<u2").tobytes())
         h.update(self.tips.astype("<u4").tobytes())
         return h.hexdigest()
+
+
+# ---- how the wrappers below marshal a call ------------------------------------------------------------------------------------
+def _pack(seqs, encoding: str = "utf-8") -> tuple[bytes, np.ndarray, int]:
+    """a list of sequences (bytes as they are, anything else by the encoding of its str) -> (the letters back to back, offsets
+    uint64[n + 1], n).  The encoding is the call's: the graph and model stages take UTF-8, `nearest`, `frameshift` and `chimera` latin-1."""
+    raw = [s if isinstance(s, (bytes, bytearray)) else str(s).encode(encoding) for s in seqs]
+    offsets = np.zeros(len(raw) + 1, dtype=np.uint64)
+    if raw:
+        np.cumsum([len(s) for s in raw], out=offsets[1:])
+    return b"".join(raw), offsets, len(raw)
+
+
+def _window_offsets(offsets: np.ndarray, k: int) -> np.ndarray:
+    """int64[n + 1]: the windows in front of every contig, len - k of them per contig and none for a contig of k letters or fewer"""
+    woff = np.zeros(len(offsets), dtype=np.int64)
+    np.cumsum(np.maximum(0, np.diff(offsets.astype(np.int64)) - k), out=woff[1:])
+    return woff
+
+
+def _known(params: dict | None, names, what: str) -> dict:
+    """the call's parameters as a dict; a name the call does not know is an error"""
+    unknown = set(params or {}) - set(names)
+    if unknown:
+        raise ValueError(f"unknown {what} parameters: {sorted(unknown)}")
+    return dict(params or {})
+
+
+def _int_params(cls, params: dict | None, what: str):
+    """a *Params struct of integer members from a dict of them; a member that is not named stays 0, the library's word for its default"""
+    par = cls()
+    for name, v in _known(params, [name for name, _ in cls._fields_], what).items():
+        setattr(par, name, int(v))
+    return par
+
+
+def _sub_table(sub) -> np.ndarray:
+    table = np.ascontiguousarray(sub, dtype=np.int8)
+    if table.shape != (27, 27):
+        raise ValueError("sub must be int8[27, 27]")
+    return table
+
+
+def _path_buffers(offsets: np.ndarray, n: int, stride: int) -> tuple[np.ndarray, np.ndarray]:
+    """the path letters of n sequences (sequence i writes from offsets[i] + i * stride) and their lengths"""
+    return np.zeros(int(offsets[n]) + n * stride + 1, dtype=np.uint8), np.zeros(max(1, n), dtype=np.int32)
+
+
+def _paths(p: np.ndarray, plen: np.ndarray, offsets: np.ndarray, n: int, stride: int) -> list[str]:
+    return [p[int(offsets[i]) + i * stride:int(offsets[i]) + i * stride + int(plen[i])].tobytes().decode() for i in range(n)]
+
+
+def _one_per_row(lens, n: int) -> np.ndarray:
+    ln = np.ascontiguousarray(lens, dtype=np.int64)
+    if ln.shape != (n,):
+        raise ValueError("lens must hold one length per row")
+    return ln
+
+
+def _residues_and_lens(n_residues, lens) -> tuple[np.ndarray, np.ndarray, int]:
+    nr, ln = np.ascontiguousarray(n_residues, dtype=np.int32), np.ascontiguousarray(lens, dtype=np.int64)
+    if ln.shape != (nr.size,) or nr.ndim != 1:
+        raise ValueError("n_residues and lens must hold one value per row")
+    return nr, ln, nr.size
+
+
+def _linkage_outputs(shape) -> tuple[np.ndarray, np.ndarray, np.ndarray, np.ndarray]:
+    """cluster int32, rep int64, rep_diff and rep_overlap uint16 of a linkage"""
+    return np.zeros(shape, dtype=np.int32), np.zeros(shape, dtype=np.int64), np.zeros(shape, dtype=np.uint16), np.zeros(shape, dtype=np.uint16)
+
+
+def _linkage_result(cl, rep, rd, ro, st, **more) -> dict:
+    return dict(cluster=cl, rep=rep, rep_diff=rd, rep_overlap=ro, **more, stats=st.as_dict())
+
+
+def _pair_array(pairs) -> np.ndarray:
+    return np.ascontiguousarray(pairs, dtype=ROW_PAIR) if isinstance(pairs, np.ndarray) else np.array([tuple(x) for x in pairs], dtype=ROW_PAIR)
+
+
+def _hit_bits(words: np.ndarray, ns: int) -> np.ndarray:
+    return np.unpackbits(words.view(np.uint8), bitorder="little")[:ns].astype(bool)
 
 
 class Context:
@@ -157,7 +246,6 @@ class Context:
         lens_or_seqs = per contig its length or its letters; sites = per contig a list of ascending 0-based positions; params =
         dict(max_span=), 0 or missing = 1000.  joint_cap (pairs) defaults to what the sites need.  -> dict(site_counts = uint32[S, 4],
         pair_off = uint64[S + 1], joint = uint32[n_pairs, 16], site_off = int64[n + 1], site_pos = uint32[S], stats)."""
-        from .pileup import READ_DTYPE
         if reads.ctx is not self:
             raise MegaGtaError("mgta_reads_phase: the reads belong to another context")
         lens = [int(x) if isinstance(x, (int, np.integer)) else len(x) for x in lens_or_seqs]
@@ -168,14 +256,10 @@ class Context:
         off, pos = self._site_lists(sites)
         if len(off) - 1 != n:
             raise ValueError("sites and contigs differ in number")
-        unknown = set(params or {}) - {"max_span"}
-        if unknown:
-            raise ValueError(f"unknown phase parameters: {sorted(unknown)}")
-        par = _lib.PhaseParams()
-        par.max_span = int((params or {}).get("max_span", 0))
+        par = _int_params(_lib.PhaseParams, params, "phase")
         ends = np.ascontiguousarray([int(e) for e, _ in libs], dtype=np.uint64)
         paired = np.ascontiguousarray([1 if p else 0 for _, p in libs], dtype=np.uint8)
-        pl = np.ascontiguousarray(place, dtype=READ_DTYPE)
+        pl = np.ascontiguousarray(place, dtype=_READ_PLACE)
         if ends.size and pl.size < int(ends[-1]):
             raise ValueError(f"{pl.size} placement records for {int(ends[-1])} reads")
         S = int(off[-1])
@@ -202,11 +286,7 @@ class Context:
         by the rule of include/megagta_hip.h.  params = dict(min_aa=, min_score= in nats, or min_bits=); missing = 20 residues and 20
         bits.  -> dict(hit_bits = uint64[ceil(n / 64)], bits = bool[n], recs = recruit.REC[n] or None, col_depth = uint64[M] or None,
         stats).  Needs no graph."""
-        from .recruit import LN2, REC
-        unknown = set(params or {}) - {"min_aa", "min_score", "min_bits"}
-        if unknown:
-            raise ValueError(f"unknown recruit parameters: {sorted(unknown)}")
-        p = dict(params or {})
+        p = _known(params, ("min_aa", "min_score", "min_bits"), "recruit")
         if "min_score" in p and "min_bits" in p:
             raise ValueError("recruit parameters: min_score (nats) or min_bits, not both")
         par = _lib.RecruitParams()
@@ -214,13 +294,12 @@ class Context:
         par.min_score = float(p["min_score"]) if "min_score" in p else float(p.get("min_bits", 20.0)) * LN2
         ns = reads.n_reads if n_short_reads is None else int(n_short_reads)
         words = np.zeros(max(1, (ns + 63) // 64), dtype=np.uint64)          # (never an empty buffer: NULL is an error of its own)
-        r = np.zeros(max(1, ns), dtype=REC) if recs else None
+        r = np.zeros(max(1, ns), dtype=_RECRUIT_REC) if recs else None
         depth = np.zeros(max(1, hmm.M), dtype=np.uint64) if cols else None
         st = _lib.RecruitStats()
         check(self._L.mgta_reads_recruit(self.h, hmm.h, reads.h, int(bool(reads_reversed)), ns, C.byref(par), words.ctypes.data, r.ctypes.data if recs else None,
                                          depth.ctypes.data if cols else None, C.byref(st)), "mgta_reads_recruit")
-        bits = np.unpackbits(words.view(np.uint8), bitorder="little")[:ns].astype(bool)
-        return dict(hit_bits=words[:(ns + 63) // 64], bits=bits, recs=r[:ns] if recs else None, col_depth=depth[:hmm.M] if cols else None, stats=st.as_dict())
+        return dict(hit_bits=words[:(ns + 63) // 64], bits=_hit_bits(words, ns), recs=r[:ns] if recs else None, col_depth=depth[:hmm.M] if cols else None, stats=st.as_dict())
 
     def set_derep_hash_bits(self, bits: int = 64):
         """bits of both hashes `derep` keeps (1 .. 64, the default): with a few bits nearly every key collides.  The result does not
@@ -232,14 +311,10 @@ class Context:
         uint8[n]: 0 kept, 1 duplicate of an earlier sequence, 2 contained in a longer one; rep = int64[n]: the first occurrence of a
         duplicate, -1 for a contained sequence, itself for a kept one; copies = uint32[n]: inputs equal to a first occurrence, 0 for a
         duplicate; stats).  Needs no graph."""
-        raw = [s if isinstance(s, (bytes, bytearray)) else str(s).encode() for s in seqs]
-        n = len(raw)
-        offsets = np.zeros(n + 1, dtype=np.uint64)
-        if n:
-            np.cumsum([len(s) for s in raw], out=offsets[1:])
+        buf, offsets, n = _pack(seqs)
         status, rep, copies = np.zeros(max(1, n), dtype=np.uint8), np.zeros(max(1, n), dtype=np.int64), np.zeros(max(1, n), dtype=np.uint32)
         st = _lib.DerepStats()
-        check(self._L.mgta_seqs_derep(self.h, b"".join(raw), offsets.ctypes.data, n, status.ctypes.data, rep.ctypes.data, copies.ctypes.data, C.byref(st)),
+        check(self._L.mgta_seqs_derep(self.h, buf, offsets.ctypes.data, n, status.ctypes.data, rep.ctypes.data, copies.ctypes.data, C.byref(st)),
               "mgta_seqs_derep")
         return dict(status=status[:n], rep=rep[:n], copies=copies[:n], stats=st.as_dict())
 
@@ -253,23 +328,18 @@ class Context:
         dict(recs = structured array [n] with score, status (0 aligned, 1 unaligned), model_from, model_to, n_match, n_insert, n_delete;
         cols = uint8[n, M] when asked for: the upper-cased residue where a match state emitted it, `-` elsewhere; paths = list of str
         over M / I / D when asked for; stats).  Needs no graph."""
-        raw = [s if isinstance(s, (bytes, bytearray)) else str(s).encode() for s in seqs]
-        n, M = len(raw), hmm.M
-        offsets = np.zeros(n + 1, dtype=np.uint64)
-        if n:
-            np.cumsum([len(s) for s in raw], out=offsets[1:])
+        (buf, offsets, n), M = _pack(seqs), hmm.M
         recs = np.zeros(max(1, n), dtype=ALIGN_REC)
         c = np.zeros((max(1, n), M), dtype=np.uint8) if cols else None
-        p = np.zeros(int(offsets[n]) + n * M + 1, dtype=np.uint8) if paths else None
-        plen = np.zeros(max(1, n), dtype=np.int32) if paths else None
+        p, plen = _path_buffers(offsets, n, M) if paths else (None, None)
         st = _lib.AlignStats()
-        check(self._L.mgta_seqs_align(self.h, hmm.h, b"".join(raw), offsets.ctypes.data, n, recs.ctypes.data, c.ctypes.data if cols else None,
+        check(self._L.mgta_seqs_align(self.h, hmm.h, buf, offsets.ctypes.data, n, recs.ctypes.data, c.ctypes.data if cols else None,
                                       p.ctypes.data if paths else None, plen.ctypes.data if paths else None, C.byref(st)), "mgta_seqs_align")
         out = dict(recs=recs[:n], stats=st.as_dict())
         if cols:
             out["cols"] = c[:n]
         if paths:
-            out["paths"] = [p[int(offsets[i]) + i * M:int(offsets[i]) + i * M + int(plen[i])].tobytes().decode() for i in range(n)]
+            out["paths"] = _paths(p, plen, offsets, n, M)
         return out
 
     def set_posterior_batch(self, cells: int = 0):
@@ -284,15 +354,11 @@ class Context:
         state its label names (+j the match state of node j, -j its insert state, 0 none), `labels` being one sequence of ints per
         sequence (posterior.labels_from_path makes Viterbi's); col_match, col_insert = float64[n, M] when `cols`: the posteriors of
         every match / insert state summed over the residues; stats).  Needs no graph."""
-        raw = [s if isinstance(s, (bytes, bytearray)) else str(s).encode() for s in seqs]
-        n, M = len(raw), hmm.M
-        offsets = np.zeros(n + 1, dtype=np.uint64)
-        if n:
-            np.cumsum([len(s) for s in raw], out=offsets[1:])
+        (buf, offsets, n), M = _pack(seqs), hmm.M
         total = int(offsets[n])
         lab = pp = None
         if labels is not None:
-            if len(labels) != n or any(len(l) != len(s) for l, s in zip(labels, raw)):
+            if len(labels) != n or any(len(l) != int(m) for l, m in zip(labels, np.diff(offsets))):
                 raise ValueError("posterior: one label per residue of every sequence")
             lab = np.zeros(total + 1, dtype=np.int32)
             if total:
@@ -302,7 +368,7 @@ class Context:
         cm = np.zeros((max(1, n), M), dtype=np.float64) if cols else None
         ci = np.zeros((max(1, n), M), dtype=np.float64) if cols else None
         st = _lib.PostStats()
-        check(self._L.mgta_seqs_posterior(self.h, hmm.h, b"".join(raw), offsets.ctypes.data, n, lab.ctypes.data if lab is not None else None, recs.ctypes.data,
+        check(self._L.mgta_seqs_posterior(self.h, hmm.h, buf, offsets.ctypes.data, n, lab.ctypes.data if lab is not None else None, recs.ctypes.data,
                                           pp.ctypes.data if pp is not None else None, cm.ctypes.data if cols else None, ci.ctypes.data if cols else None,
                                           C.byref(st)), "mgta_seqs_posterior")
         out = dict(recs=recs[:n], stats=st.as_dict())
@@ -355,15 +421,12 @@ class Context:
         uint16[n], the counts of a row against its representative; stats).  Needs no graph."""
         r = self._rows(rows)
         n, M = r.shape
-        ln = np.ascontiguousarray(lens, dtype=np.int64)
-        if ln.shape != (n,):
-            raise ValueError("lens must hold one length per row")
-        cl, rep = np.zeros(max(1, n), dtype=np.int32), np.zeros(max(1, n), dtype=np.int64)
-        rd, ro = np.zeros(max(1, n), dtype=np.uint16), np.zeros(max(1, n), dtype=np.uint16)
+        ln = _one_per_row(lens, n)
+        cl, rep, rd, ro = _linkage_outputs(max(1, n))
         st = _lib.ClusterStats()
         check(self._L.mgta_rows_cluster(self.h, r.ctypes.data, ln.ctypes.data, n, M, int(min_overlap), float(cutoff), cl.ctypes.data, rep.ctypes.data,
                                         rd.ctypes.data, ro.ctypes.data, C.byref(st)), "mgta_rows_cluster")
-        return dict(cluster=cl[:n], rep=rep[:n], rep_diff=rd[:n], rep_overlap=ro[:n], stats=st.as_dict())
+        return _linkage_result(cl[:n], rep[:n], rd[:n], ro[:n], st)
 
     def pairs_tree(self, pairs, n_residues) -> dict:
         """mgta_pairs_tree: the complete-linkage merge tree of the kept pairs of n rows (a ROW_PAIR array ascending by (i, j), or tuples),
@@ -385,20 +448,17 @@ class Context:
         uint16[n_cutoffs, n]: row k is what `cluster` gives at cutoffs[k]; merges = the tree (TREE_MERGE array); stats)."""
         r = self._rows(rows)
         n, M = r.shape
-        ln = np.ascontiguousarray(lens, dtype=np.int64)
-        if ln.shape != (n,):
-            raise ValueError("lens must hold one length per row")
+        ln = _one_per_row(lens, n)
         cut = np.ascontiguousarray(cutoffs, dtype=np.float64)
         if cut.ndim != 1:
             raise ValueError("cutoffs must be a list of numbers")
         k = cut.size
-        cl, rep = np.zeros((k, n), dtype=np.int32), np.zeros((k, n), dtype=np.int64)                  # cut-off j at [j * n, (j + 1) * n)
-        rd, ro = np.zeros((k, n), dtype=np.uint16), np.zeros((k, n), dtype=np.uint16)
+        cl, rep, rd, ro = _linkage_outputs((k, n))                                                    # cut-off j at [j * n, (j + 1) * n)
         merges = np.zeros(max(1, n), dtype=TREE_MERGE)
         cnt, st = C.c_int64(0), _lib.TreeStats()
         check(self._L.mgta_rows_clusters(self.h, r.ctypes.data, ln.ctypes.data, n, M, int(min_overlap), cut.ctypes.data if k else None, k, cl.ctypes.data,
                                          rep.ctypes.data, rd.ctypes.data, ro.ctypes.data, merges.ctypes.data, C.byref(cnt), C.byref(st)), "mgta_rows_clusters")
-        return dict(cluster=cl, rep=rep, rep_diff=rd, rep_overlap=ro, merges=merges[:cnt.value], stats=st.as_dict())
+        return _linkage_result(cl, rep, rd, ro, st, merges=merges[:cnt.value])
 
     def set_nearest_batch(self, cells: int = 0):
         """cells (L * R) of one trace batch of `nearest` (0 = the default: by the context's free memory); a batch holds at least one
@@ -411,31 +471,7 @@ class Context:
         (0 aligned, 1 unaligned), ref (-1 unaligned), score, ref_from, ref_to, n_match, n_ident, n_insert, n_delete; scores =
         int32[n, n_ref] of every pair when asked for, INT32_MIN where a pair has no score; paths = list of str over M / I / D when
         asked for; stats).  Needs no graph."""
-        raw = [s if isinstance(s, (bytes, bytearray)) else str(s).encode("latin-1") for s in seqs]
-        rraw = [s if isinstance(s, (bytes, bytearray)) else str(s).encode("latin-1") for s in refs]
-        n, n_ref = len(raw), len(rraw)
-        table = np.ascontiguousarray(sub, dtype=np.int8)
-        if table.shape != (27, 27):
-            raise ValueError("sub must be int8[27, 27]")
-        offsets, roffsets = np.zeros(n + 1, dtype=np.uint64), np.zeros(n_ref + 1, dtype=np.uint64)
-        if n:
-            np.cumsum([len(s) for s in raw], out=offsets[1:])
-        if n_ref:
-            np.cumsum([len(s) for s in rraw], out=roffsets[1:])
-        recs = np.zeros(max(1, n), dtype=NEAREST_REC)
-        sc = np.zeros((n, n_ref), dtype=np.int32) if scores else None
-        p = np.zeros(int(offsets[n]) + n * 4096 + 1, dtype=np.uint8) if paths else None
-        plen = np.zeros(max(1, n), dtype=np.int32) if paths else None
-        st = _lib.NearestStats()
-        check(self._L.mgta_seqs_nearest(self.h, b"".join(raw), offsets.ctypes.data, n, b"".join(rraw), roffsets.ctypes.data, n_ref, table.ctypes.data,
-                                        int(gap_open), int(gap_extend), recs.ctypes.data, sc.ctypes.data if scores and sc.size else None,
-                                        p.ctypes.data if paths else None, plen.ctypes.data if paths else None, C.byref(st)), "mgta_seqs_nearest")
-        out = dict(recs=recs[:n], stats=st.as_dict())
-        if scores:
-            out["scores"] = sc
-        if paths:
-            out["paths"] = [p[int(offsets[i]) + i * 4096:int(offsets[i]) + i * 4096 + int(plen[i])].tobytes().decode() for i in range(n)]
-        return out
+        return self._closest("mgta_seqs_nearest", NEAREST_REC, _lib.NearestStats, seqs, refs, sub, (gap_open, gap_extend), scores, paths)
 
     def frameshift(self, nucl, refs, sub, gap_open: int, gap_extend: int, frameshift: int, scores: bool = False, paths: bool = False) -> dict:
         """mgta_seqs_frameshift: for every NUCLEOTIDE contig of `nucl` (str or bytes) the closest protein of `refs`, with shifts of the
@@ -444,30 +480,26 @@ class Context:
         n_insert, n_delete, n_short, n_long; scores = int32[n, n_ref] when asked for, INT32_MIN where a pair has no score; paths =
         list of str over M / < / > / I / D when asked for; stats).  `set_nearest_batch` sets this call's trace batch too.  Needs no
         graph."""
-        raw = [s if isinstance(s, (bytes, bytearray)) else str(s).encode("latin-1") for s in nucl]
-        rraw = [s if isinstance(s, (bytes, bytearray)) else str(s).encode("latin-1") for s in refs]
-        n, n_ref = len(raw), len(rraw)
-        table = np.ascontiguousarray(sub, dtype=np.int8)
-        if table.shape != (27, 27):
-            raise ValueError("sub must be int8[27, 27]")
-        offsets, roffsets = np.zeros(n + 1, dtype=np.uint64), np.zeros(n_ref + 1, dtype=np.uint64)
-        if n:
-            np.cumsum([len(s) for s in raw], out=offsets[1:])
-        if n_ref:
-            np.cumsum([len(s) for s in rraw], out=roffsets[1:])
-        recs = np.zeros(max(1, n), dtype=FRAMESHIFT_REC)
+        return self._closest("mgta_seqs_frameshift", FRAMESHIFT_REC, _lib.FrameshiftStats, nucl, refs, sub, (gap_open, gap_extend, frameshift), scores, paths)
+
+    def _closest(self, entry: str, rec: np.dtype, stats, seqs, refs, sub, costs: tuple, scores: bool, paths: bool) -> dict:
+        """`nearest` and `frameshift`: the two C entries take the same arguments but for the costs (two, or three with the frame shift)
+        and their own record and stats structs"""
+        buf, offsets, n = _pack(seqs, "latin-1")
+        rbuf, roffsets, n_ref = _pack(refs, "latin-1")
+        table = _sub_table(sub)
+        recs = np.zeros(max(1, n), dtype=rec)
         sc = np.zeros((n, n_ref), dtype=np.int32) if scores else None
-        p = np.zeros(int(offsets[n]) + n * 4096 + 1, dtype=np.uint8) if paths else None
-        plen = np.zeros(max(1, n), dtype=np.int32) if paths else None
-        st = _lib.FrameshiftStats()
-        check(self._L.mgta_seqs_frameshift(self.h, b"".join(raw), offsets.ctypes.data, n, b"".join(rraw), roffsets.ctypes.data, n_ref, table.ctypes.data,
-                                           int(gap_open), int(gap_extend), int(frameshift), recs.ctypes.data, sc.ctypes.data if scores and sc.size else None,
-                                           p.ctypes.data if paths else None, plen.ctypes.data if paths else None, C.byref(st)), "mgta_seqs_frameshift")
+        p, plen = _path_buffers(offsets, n, 4096) if paths else (None, None)
+        st = stats()
+        check(getattr(self._L, entry)(self.h, buf, offsets.ctypes.data, n, rbuf, roffsets.ctypes.data, n_ref, table.ctypes.data, *(int(c) for c in costs),
+                                      recs.ctypes.data, sc.ctypes.data if scores and sc.size else None, p.ctypes.data if paths else None,
+                                      plen.ctypes.data if paths else None, C.byref(st)), entry)
         out = dict(recs=recs[:n], stats=st.as_dict())
         if scores:
             out["scores"] = sc
         if paths:
-            out["paths"] = [p[int(offsets[i]) + i * 4096:int(offsets[i]) + i * 4096 + int(plen[i])].tobytes().decode() for i in range(n)]
+            out["paths"] = _paths(p, plen, offsets, n, 4096)
         return out
 
     def set_chimera_segment(self, columns: int = 0):
@@ -487,21 +519,13 @@ class Context:
         clean, 1 chimeric, 2 unchecked), ref, score, brk, left_ref, left_score, right_ref, right_score, two, one, gain; tops = a list
         of int32[L, 8] per contig when asked for: P1.score, P1.ref, P2.score, P2.ref, S1.score, S1.ref, S2.score, S2.ref of every row,
         INT32_MIN, -1 where absent; stats).  Needs no graph."""
-        raw = [s if isinstance(s, (bytes, bytearray)) else str(s).encode("latin-1") for s in seqs]
-        rraw = [s if isinstance(s, (bytes, bytearray)) else str(s).encode("latin-1") for s in refs]
-        n, n_ref = len(raw), len(rraw)
-        table = np.ascontiguousarray(sub, dtype=np.int8)
-        if table.shape != (27, 27):
-            raise ValueError("sub must be int8[27, 27]")
-        offsets, roffsets = np.zeros(n + 1, dtype=np.uint64), np.zeros(n_ref + 1, dtype=np.uint64)
-        if n:
-            np.cumsum([len(s) for s in raw], out=offsets[1:])
-        if n_ref:
-            np.cumsum([len(s) for s in rraw], out=roffsets[1:])
+        buf, offsets, n = _pack(seqs, "latin-1")
+        rbuf, roffsets, n_ref = _pack(refs, "latin-1")
+        table = _sub_table(sub)
         recs = np.zeros(max(1, n), dtype=CHIMERA_REC)
         tp = np.zeros((int(offsets[n]) + 1, 8), dtype=np.int32) if tops else None
         st = _lib.ChimeraStats()
-        check(self._L.mgta_seqs_chimera(self.h, b"".join(raw), offsets.ctypes.data, n, b"".join(rraw), roffsets.ctypes.data, n_ref, table.ctypes.data,
+        check(self._L.mgta_seqs_chimera(self.h, buf, offsets.ctypes.data, n, rbuf, roffsets.ctypes.data, n_ref, table.ctypes.data,
                                         int(gap_open), int(gap_extend), int(min_seg), int(min_gain), recs.ctypes.data, tp.ctypes.data if tops else None,
                                         C.byref(st)), "mgta_seqs_chimera")
         out = dict(recs=recs[:n], stats=st.as_dict())
@@ -580,12 +604,6 @@ def export_records_to_torch(ctx: "Context"):
     t = torch.empty(max(1, n.value * 2), dtype=torch.uint8, device="cuda")
     check(ctx._L.mgta_sdbg_export_records_device(ctx.h, t.data_ptr(), t.numel(), C.byref(n)), "mgta_sdbg_export_records_device")
     return t[: n.value * 2]
-
-
-# mgta_contig_cov
-SHARE_DTYPE = np.dtype([("mass", "<u8"), ("len", "<u4"), ("n_windows", "<u4"), ("n_covered", "<u4"), ("n_unique", "<u4"), ("max_share", "<u4"),
-                        ("reserved_", "<u4")])
-COV_DTYPE = np.dtype([("sum", "<u8"), ("len", "<u4"), ("n_windows", "<u4"), ("n_covered", "<u4"), ("min", "<u4"), ("max", "<u4"), ("median", "<u4")])
 
 
 class _multiplicity:
@@ -712,16 +730,9 @@ class Graph:
         median: the lower median over all windows), abundance = int64[65536] distinct edges per multiplicity over THIS call,
         stats, and with per_window=True per_window = uint16 coverages back to back + window_offsets int64[n + 1]).
         One call = one set of contigs (abundance marks live for one call): pass a gene's contigs together."""
-        raw = [s if isinstance(s, (bytes, bytearray)) else str(s).encode() for s in seqs]
-        n = len(raw)
-        offsets = np.zeros(n + 1, dtype=np.uint64)
-        if n:
-            np.cumsum([len(s) for s in raw], out=offsets[1:])
-        buf = b"".join(raw)
+        buf, offsets, n = _pack(seqs)
         cov = np.zeros(n, dtype=COV_DTYPE)
-        nw = np.maximum(0, np.diff(offsets.astype(np.int64)) - self.ctx._L.mgta_sdbg_k(self.h))      # (the graph's own k sizes the buffer)
-        woff = np.zeros(n + 1, dtype=np.int64)
-        np.cumsum(nw, out=woff[1:])
+        woff = _window_offsets(offsets, self.ctx._L.mgta_sdbg_k(self.h))                               # (the graph's own k sizes the buffers)
         pw = np.zeros(int(woff[-1]), dtype=np.uint16) if per_window else None
         ab = np.zeros(65536, dtype=np.int64) if abundance else None
         st = _lib.CoverageStats()
@@ -738,19 +749,13 @@ class Graph:
         of THIS call that land on it, so that the masses add up over any set of contigs.  -> dict(contigs = structured array (mass: Q16,
         len, n_windows, n_covered, n_unique, max_share), stats, and with per_window=True per_window_share = uint32 shares back to back
         (0 = no edge), per_window = uint16 multiplicities + window_offsets int64[n + 1]).  One call = one set of contigs."""
-        raw = [s if isinstance(s, (bytes, bytearray)) else str(s).encode() for s in seqs]
-        n = len(raw)
-        offsets = np.zeros(n + 1, dtype=np.uint64)
-        if n:
-            np.cumsum([len(s) for s in raw], out=offsets[1:])
+        buf, offsets, n = _pack(seqs)
         rec = np.zeros(n, dtype=SHARE_DTYPE)
-        nw = np.maximum(0, np.diff(offsets.astype(np.int64)) - self.ctx._L.mgta_sdbg_k(self.h))      # (the graph's own k sizes the buffers)
-        woff = np.zeros(n + 1, dtype=np.int64)
-        np.cumsum(nw, out=woff[1:])
+        woff = _window_offsets(offsets, self.ctx._L.mgta_sdbg_k(self.h))                               # (the graph's own k sizes the buffers)
         pws = np.zeros(int(woff[-1]), dtype=np.uint32) if per_window else None
         pw = np.zeros(int(woff[-1]), dtype=np.uint16) if per_window else None
         st = _lib.ShareStats()
-        check(self.ctx._L.mgta_contig_share_coverage(self.h, b"".join(raw), offsets.ctypes.data, n, rec.ctypes.data if n else None,
+        check(self.ctx._L.mgta_contig_share_coverage(self.h, buf, offsets.ctypes.data, n, rec.ctypes.data if n else None,
                                                      pws.ctypes.data if per_window and pws.size else None, pw.ctypes.data if per_window and pw.size else None,
                                                      C.byref(st)), "mgta_contig_share_coverage")
         out = dict(contigs=rec, stats=st.as_dict(), per_window_share=pws, per_window=pw)
@@ -763,19 +768,14 @@ class Graph:
         `seqs` (str or bytes, any case), on either strand.  -> dict(bits = bool[n_short_reads], hit_windows = None, or with counts=True
         uint32[n_short_reads] hitting windows per read, stats).  Without counts the walk of a read ends at its first hit.  Any loaded
         graph will do (no multiplicities needed); one call = one set of contigs."""
-        raw = [s if isinstance(s, (bytes, bytearray)) else str(s).encode() for s in seqs]
-        n = len(raw)
-        offsets = np.zeros(n + 1, dtype=np.uint64)
-        if n:
-            np.cumsum([len(s) for s in raw], out=offsets[1:])
+        buf, offsets, n = _pack(seqs)
         ns = reads.n_reads if n_short_reads is None else int(n_short_reads)
         words = np.zeros(max(1, (ns + 63) // 64), dtype=np.uint64)          # (never an empty buffer: NULL is an error of its own)
         hits = np.zeros(ns, dtype=np.uint32) if counts else None
         st = _lib.MatchStats()
-        check(self.ctx._L.mgta_reads_match_contigs(self.h, reads.h, int(bool(reads_reversed)), ns, b"".join(raw), offsets.ctypes.data, n, words.ctypes.data,
+        check(self.ctx._L.mgta_reads_match_contigs(self.h, reads.h, int(bool(reads_reversed)), ns, buf, offsets.ctypes.data, n, words.ctypes.data,
                                                    hits.ctypes.data if counts and ns else None, C.byref(st)), "mgta_reads_match_contigs")
-        bits = np.unpackbits(words.view(np.uint8), bitorder="little")[:ns].astype(bool)
-        return dict(bits=bits, hit_windows=hits, stats=st.as_dict())
+        return dict(bits=_hit_bits(words, ns), hit_windows=hits, stats=st.as_dict())
 
     def contig_sample_coverage(self, reads: "Reads", lib_end, seqs, per_window: bool = False, reads_reversed: bool = True) -> dict:
         """mgta_contig_sample_coverage: the read windows of every library on the windows of the contigs `seqs` (str or bytes, any case),
@@ -784,26 +784,20 @@ class Graph:
         contigs = structured array as of contig_share_coverage (mass = the sum over the libraries), lib_hit_windows = uint64[n_libs],
         stats, and with per_window=True per_window_count = uint64[windows, n_libs], per_window_share = uint32[windows] (0 = no edge) +
         window_offsets int64[n + 1]).  Any loaded graph will do; one call = one set of contigs."""
-        raw = [s if isinstance(s, (bytes, bytearray)) else str(s).encode() for s in seqs]
-        n = len(raw)
-        offsets = np.zeros(n + 1, dtype=np.uint64)
-        if n:
-            np.cumsum([len(s) for s in raw], out=offsets[1:])
+        buf, offsets, n = _pack(seqs)
         ends = np.ascontiguousarray(lib_end, dtype=np.uint64)
         if ends.ndim != 1:
             raise ValueError("lib_end is a list of read numbers")
         nl = int(ends.size)
         rec = np.zeros(n, dtype=SHARE_DTYPE)
-        nw = np.maximum(0, np.diff(offsets.astype(np.int64)) - self.ctx._L.mgta_sdbg_k(self.h))      # (the graph's own k sizes the buffers)
-        woff = np.zeros(n + 1, dtype=np.int64)
-        np.cumsum(nw, out=woff[1:])
+        woff = _window_offsets(offsets, self.ctx._L.mgta_sdbg_k(self.h))                               # (the graph's own k sizes the buffers)
         mass = np.zeros((n, nl), dtype=np.uint64)
         hits = np.zeros(max(1, nl), dtype=np.uint64)
         pwc = np.zeros((int(woff[-1]), nl), dtype=np.uint64) if per_window else None
         pws = np.zeros(int(woff[-1]), dtype=np.uint32) if per_window else None
         keep = np.zeros(1, dtype=np.uint64)                                    # (never a NULL mass for n = 0: NULL is an error of its own)
         st = _lib.SampleCovStats()
-        check(self.ctx._L.mgta_contig_sample_coverage(self.h, reads.h, int(bool(reads_reversed)), ends.ctypes.data if nl else None, nl, b"".join(raw),
+        check(self.ctx._L.mgta_contig_sample_coverage(self.h, reads.h, int(bool(reads_reversed)), ends.ctypes.data if nl else None, nl, buf,
                                                       offsets.ctypes.data, n, mass.ctypes.data if mass.size else keep.ctypes.data, rec.ctypes.data if n else None,
                                                       pwc.ctypes.data if per_window and pwc.size else None, pws.ctypes.data if per_window and pws.size else None,
                                                       hits.ctypes.data, C.byref(st)), "mgta_contig_sample_coverage")
@@ -819,26 +813,16 @@ class Graph:
         the default of each.  -> dict(counts = uint32[letters, 4] (A C G T, in the contig's strand), uniq = uint32[letters], contigs =
         structured array (pileup.CONTIG_DTYPE), offsets = int64[n + 1], stats, and with per_read=True reads = structured array
         (pileup.READ_DTYPE) of n_short_reads records).  Any loaded graph will do; one call = one set of contigs."""
-        from .pileup import CONTIG_DTYPE, READ_DTYPE
-        raw = [s if isinstance(s, (bytes, bytearray)) else str(s).encode() for s in seqs]
-        n = len(raw)
-        offsets = np.zeros(n + 1, dtype=np.uint64)
-        if n:
-            np.cumsum([len(s) for s in raw], out=offsets[1:])
+        buf, offsets, n = _pack(seqs)
         ns = reads.n_reads if n_short_reads is None else int(n_short_reads)
         total = int(offsets[-1])
         counts = np.zeros((total, 4), dtype=np.uint32)
         uniq = np.zeros(total, dtype=np.uint32)
-        rec = np.zeros(n, dtype=CONTIG_DTYPE)
-        pr = np.zeros(ns, dtype=READ_DTYPE) if per_read else None
-        par = _lib.PileupParams()
-        unknown = set(params or {}) - {"min_anchors", "min_overlap", "max_mismatch_permille"}
-        if unknown:
-            raise ValueError(f"unknown pileup parameters: {sorted(unknown)}")
-        for name, v in (params or {}).items():
-            setattr(par, name, int(v))
+        rec = np.zeros(n, dtype=_CONTIG_PILEUP)
+        pr = np.zeros(ns, dtype=_READ_PLACE) if per_read else None
+        par = _int_params(_lib.PileupParams, params, "pileup")
         st = _lib.PileupStats()
-        check(self.ctx._L.mgta_reads_pileup(self.h, reads.h, int(bool(reads_reversed)), ns, b"".join(raw), offsets.ctypes.data, n, C.byref(par) if params else None,
+        check(self.ctx._L.mgta_reads_pileup(self.h, reads.h, int(bool(reads_reversed)), ns, buf, offsets.ctypes.data, n, C.byref(par) if params else None,
                                             counts.ctypes.data if total else None, uniq.ctypes.data if total else None, rec.ctypes.data if n else None,
                                             pr.ctypes.data if per_read and ns else None, C.byref(st)), "mgta_reads_pileup")
         return dict(counts=counts, uniq=uniq, contigs=rec, offsets=offsets.astype(np.int64), stats=st.as_dict(), reads=pr)
@@ -849,30 +833,19 @@ class Graph:
         params = the three of pileup and max_gap=, gap_open=, gap_extend=, 0 or missing = the default of each.  -> the dict of
         Graph.pileup with reads = gapped.PLACE_DTYPE records and gaps = gapped.GAP_DTYPE records, sorted by the library.  The buffer
         of the gap records is sized from the reads scanned and the call repeated once with the count the library names."""
-        from .gapped import GAP_DTYPE, PLACE_DTYPE
-        from .pileup import CONTIG_DTYPE
-        raw = [s if isinstance(s, (bytes, bytearray)) else str(s).encode() for s in seqs]
-        n = len(raw)
-        offsets = np.zeros(n + 1, dtype=np.uint64)
-        if n:
-            np.cumsum([len(s) for s in raw], out=offsets[1:])
+        buf, offsets, n = _pack(seqs)
         ns = reads.n_reads if n_short_reads is None else int(n_short_reads)
         total = int(offsets[-1])
         counts = np.zeros((total, 4), dtype=np.uint32)
         uniq = np.zeros(total, dtype=np.uint32)
-        rec = np.zeros(n, dtype=CONTIG_DTYPE)
-        pr = np.zeros(ns, dtype=PLACE_DTYPE) if per_read else None
-        par = _lib.GappedParams()
-        unknown = set(params or {}) - {name for name, _ in _lib.GappedParams._fields_}
-        if unknown:
-            raise ValueError(f"unknown gapped pileup parameters: {sorted(unknown)}")
-        for name, v in (params or {}).items():
-            setattr(par, name, int(v))
+        rec = np.zeros(n, dtype=_CONTIG_PILEUP)
+        pr = np.zeros(ns, dtype=_GAP_PLACE) if per_read else None
+        par = _int_params(_lib.GappedParams, params, "gapped pileup")
         st = _lib.GappedStats()
         cap = max(16, ns // 8) if gap_cap is None else int(gap_cap)
         for attempt in (0, 1):
-            gaps = np.zeros(cap, dtype=GAP_DTYPE)
-            rc = self.ctx._L.mgta_reads_pileup_gapped(self.h, reads.h, int(bool(reads_reversed)), ns, b"".join(raw), offsets.ctypes.data, n,
+            gaps = np.zeros(cap, dtype=_GAP_REC)
+            rc = self.ctx._L.mgta_reads_pileup_gapped(self.h, reads.h, int(bool(reads_reversed)), ns, buf, offsets.ctypes.data, n,
                                                       C.byref(par) if params else None, counts.ctypes.data if total else None, uniq.ctypes.data if total else None,
                                                       rec.ctypes.data if n else None, pr.ctypes.data if per_read and ns else None, gaps.ctypes.data if cap else None,
                                                       cap, C.byref(st))
@@ -886,8 +859,7 @@ class Graph:
     def denovo(self, max_tip_len: int = 150, no_bubble: bool = False, min_contig: int = 0) -> tuple[str, dict]:
         """`megagta denovo` (main_assemble, assembler.cpp:98-167): tips, bubbles, unitigs -> (text of PREFIX.contigs.fa, stats).
         The result is the reference's one-thread output.  CONSUMES the validity bits of this graph."""
-        from ._lib import DenovoStats
-        text, n, st = C.c_void_p(), C.c_uint64(), DenovoStats()
+        text, n, st = C.c_void_p(), C.c_uint64(), _lib.DenovoStats()
         check(self.ctx._L.mgta_denovo(self.h, max_tip_len, int(no_bubble), min_contig, C.byref(text), C.byref(n), C.byref(st)), "mgta_denovo")
         try:      # (ctypes.string_at takes a C int: a 100 M-read graph gives > 2^31 characters)
             fasta = bytes(memoryview((C.c_char * n.value).from_address(text.value))).decode() if n.value else ""
@@ -903,45 +875,17 @@ class Graph:
     __del__ = free
 
 
-# mgta_post_rec
-POST_REC = np.dtype([("fwd", np.float64), ("bwd", np.float64), ("status", np.int32), ("pad", np.int32)], align=True)
-# mgta_align_rec
-ALIGN_REC = np.dtype([("score", np.float64), ("status", np.int32), ("model_from", np.int32), ("model_to", np.int32), ("n_match", np.int32),
-                      ("n_insert", np.int32), ("n_delete", np.int32)], align=True)
-
-
-# mgta_nearest_rec
-NEAREST_REC = np.dtype([("status", np.int32), ("ref", np.int32), ("score", np.int32), ("ref_from", np.int32), ("ref_to", np.int32), ("n_match", np.int32),
-                        ("n_ident", np.int32), ("n_insert", np.int32), ("n_delete", np.int32)], align=True)
-
-
-# mgta_chimera_rec (defined once, beside the readers of the step's files)
-CHIMERA_REC = _chimera_rec
-
-
-# mgta_frameshift_rec (defined once, beside the readers of the step's files)
-FRAMESHIFT_REC = _frameshift_rec
-
-
 def link_pairs(pairs, n_residues, lens) -> dict:
     """mgta_pairs_link: the linkage of `Context.cluster` alone, on the host, no context and no device: pairs = the kept pairs of n rows
     ascending by (i, j) (a ROW_PAIR array, or tuples (i, j, n_diff, n_overlap)), n_residues = the residue columns of every row
     (0 = unaligned), lens -> dict(cluster, rep, rep_diff, rep_overlap, stats)."""
-    p = np.ascontiguousarray(pairs, dtype=ROW_PAIR) if isinstance(pairs, np.ndarray) else np.array([tuple(x) for x in pairs], dtype=ROW_PAIR)
-    nr, ln = np.ascontiguousarray(n_residues, dtype=np.int32), np.ascontiguousarray(lens, dtype=np.int64)
-    n = nr.size
-    if ln.shape != (n,) or nr.ndim != 1:
-        raise ValueError("n_residues and lens must hold one value per row")
-    cl, rep = np.zeros(max(1, n), dtype=np.int32), np.zeros(max(1, n), dtype=np.int64)
-    rd, ro = np.zeros(max(1, n), dtype=np.uint16), np.zeros(max(1, n), dtype=np.uint16)
+    p = _pair_array(pairs)
+    nr, ln, n = _residues_and_lens(n_residues, lens)
+    cl, rep, rd, ro = _linkage_outputs(max(1, n))
     st = _lib.ClusterStats()
     check(_lib.load().mgta_pairs_link(p.ctypes.data if p.size else None, p.size, nr.ctypes.data, ln.ctypes.data, n, cl.ctypes.data, rep.ctypes.data, rd.ctypes.data,
                                       ro.ctypes.data, C.byref(st)), "mgta_pairs_link")
-    return dict(cluster=cl[:n], rep=rep[:n], rep_diff=rd[:n], rep_overlap=ro[:n], stats=st.as_dict())
-
-
-def _pair_array(pairs) -> np.ndarray:
-    return np.ascontiguousarray(pairs, dtype=ROW_PAIR) if isinstance(pairs, np.ndarray) else np.array([tuple(x) for x in pairs], dtype=ROW_PAIR)
+    return _linkage_result(cl[:n], rep[:n], rd[:n], ro[:n], st)
 
 
 def tree_cut(pairs, merges, n_residues, lens, cutoff: float) -> dict:
@@ -950,22 +894,12 @@ def tree_cut(pairs, merges, n_residues, lens, cutoff: float) -> dict:
     stats["n_cut_fallbacks"] = 1 when the kept rule split equal fractions and the host linkage ran instead."""
     p = _pair_array(pairs)
     m = np.ascontiguousarray(merges, dtype=TREE_MERGE) if isinstance(merges, np.ndarray) else np.array([tuple(x) for x in merges], dtype=TREE_MERGE)
-    nr, ln = np.ascontiguousarray(n_residues, dtype=np.int32), np.ascontiguousarray(lens, dtype=np.int64)
-    n = nr.size
-    if ln.shape != (n,) or nr.ndim != 1:
-        raise ValueError("n_residues and lens must hold one value per row")
-    cl, rep = np.zeros(max(1, n), dtype=np.int32), np.zeros(max(1, n), dtype=np.int64)
-    rd, ro = np.zeros(max(1, n), dtype=np.uint16), np.zeros(max(1, n), dtype=np.uint16)
+    nr, ln, n = _residues_and_lens(n_residues, lens)
+    cl, rep, rd, ro = _linkage_outputs(max(1, n))
     st = _lib.TreeStats()
     check(_lib.load().mgta_tree_cut(p.ctypes.data if p.size else None, p.size, m.ctypes.data if m.size else None, m.size, nr.ctypes.data, ln.ctypes.data, n,
                                     float(cutoff), cl.ctypes.data, rep.ctypes.data, rd.ctypes.data, ro.ctypes.data, C.byref(st)), "mgta_tree_cut")
-    return dict(cluster=cl[:n], rep=rep[:n], rep_diff=rd[:n], rep_overlap=ro[:n], stats=st.as_dict())
-
-
-# mgta_row_pair
-ROW_PAIR = np.dtype([("i", np.int32), ("j", np.int32), ("n_diff", np.uint16), ("n_overlap", np.uint16)], align=True)
-# mgta_tree_merge
-TREE_MERGE = np.dtype([("a", np.int32), ("b", np.int32), ("n_diff", np.uint16), ("n_overlap", np.uint16)], align=True)
+    return _linkage_result(cl[:n], rep[:n], rd[:n], ro[:n], st)
 
 
 class DeviceHmm:
@@ -1014,6 +948,16 @@ def _set_cost(ctx: "Context", cost_rate) -> None:
     check(ctx._L.mgta_ctx_set_search_cost_rate(ctx.h, int(cost_rate)), "mgta_ctx_set_search_cost_rate")
 
 
+def _seeds(graph: "Graph", kmers: list[str], start_states, cost_rate) -> tuple[bytes, np.ndarray, int]:
+    """what both searches do first: the cost rate set, then (the first k + 1 letters of every seed k-mer back to back, the start states
+    as int32, the number of seeds)"""
+    _set_cost(graph.ctx, cost_rate)
+    klen = graph.k + 1
+    if any(len(s) < klen for s in kmers):
+        raise MegaGtaError(f"seed k-mer shorter than k+1={klen}")
+    return "".join(s[:klen] for s in kmers).encode(), np.ascontiguousarray(start_states, dtype=np.int32), len(kmers)
+
+
 def astar_search(graph: "Graph", fwd: DeviceHmm, rev: DeviceHmm, kmers: list[str], start_states, prune_len: int = 20,
                  low_cov_penalty: float = 0.5, cache_mode: int = 0, cost_rate=0) -> tuple[list[SeedResult], dict]:
     """Batched HMM-guided A* (mgta_astar_batch).  start_states[i] = model position - 1 (search.cpp:157).
@@ -1021,15 +965,7 @@ def astar_search(graph: "Graph", fwd: DeviceHmm, rev: DeviceHmm, kmers: list[str
     (cost_rate 0: no cost term; B = 1 then is the reference's sequential run; cost_rate < 0: j + B + c_j * |cost_rate|;
     cost_rate = (rate, knee, rate2): c_j // rate up to `knee` expansions, knee // rate + (c_j - knee) // rate2 beyond).
     cache_mode = -1: no ordering at all (timing-dependent, the reference's multi-thread behaviour)."""
-    ctx = graph.ctx
-    _set_cost(ctx, cost_rate)
-    klen = graph.k + 1
-    n = len(kmers)
-    for s in kmers:
-        if len(s) < klen:
-            raise MegaGtaError(f"seed k-mer shorter than k+1={klen}")
-    buf = "".join(s[:klen] for s in kmers).encode()
-    ss = np.ascontiguousarray(start_states, dtype=np.int32)
+    buf, ss, n = _seeds(graph, kmers, start_states, cost_rate)
     results: list[SeedResult] = [None] * n
 
     def side(p):
@@ -1043,8 +979,8 @@ def astar_search(graph: "Graph", fwd: DeviceHmm, rev: DeviceHmm, kmers: list[str
         return 0
 
     st = _lib.AstarStats()
-    check(ctx._L.mgta_astar_batch(graph.h, fwd.h, rev.h, buf, ss.ctypes.data, n, prune_len, low_cov_penalty, cache_mode,
-                                  _lib.CONTIG_SINK(sink), None, C.byref(st)), "mgta_astar_batch")
+    check(graph.ctx._L.mgta_astar_batch(graph.h, fwd.h, rev.h, buf, ss.ctypes.data, n, prune_len, low_cov_penalty, cache_mode,
+                                        _lib.CONTIG_SINK(sink), None, C.byref(st)), "mgta_astar_batch")
     return results, st.as_dict()
 
 
@@ -1053,13 +989,7 @@ def astar_search_packed(graph: "Graph", fwd: DeviceHmm, rev: DeviceHmm, kmers: l
     """astar_search with the results in flat arrays (mgta_astar_batch_packed): -> (contigs uint8[total], offsets int64[n + 1], stats[, sides]);
     contig i = contigs[offsets[i]:offsets[i + 1]] = left + lower-cased k-mer + right.  No Python work per seed."""
     ctx = graph.ctx
-    _set_cost(ctx, cost_rate)
-    klen = graph.k + 1
-    n = len(kmers)
-    if any(len(s) < klen for s in kmers):
-        raise MegaGtaError(f"seed k-mer shorter than k+1={klen}")
-    buf = "".join(s[:klen] for s in kmers).encode()
-    ss = np.ascontiguousarray(start_states, dtype=np.int32)
+    buf, ss, n = _seeds(graph, kmers, start_states, cost_rate)
     offsets = np.zeros(n + 1, dtype=np.uint64)
     sides = (_lib.AstarSide * (2 * n))() if want_sides else None
     text, st = C.c_void_p(), _lib.AstarStats()

@@ -15,12 +15,12 @@ from __future__ import annotations
 
 import numpy as np
 
+from . import _lib
 from .align import record_name
 
 STATUS = ("clean", "chimeric", "unchecked")
 CHIMERA_HEADER = "#contig\tstatus\tref\tscore\tlen\tbreak\tleft_ref\tleft_score\tright_ref\tright_score\ttwo\tone\tgain\n"
-REC = np.dtype([("status", np.int32), ("ref", np.int32), ("score", np.int32), ("brk", np.int32), ("left_ref", np.int32), ("left_score", np.int32),
-                ("right_ref", np.int32), ("right_score", np.int32), ("two", np.int32), ("one", np.int32), ("gain", np.int32)], align=True)
+REC = _lib.RECORDS[_lib.ChimeraRec]                                   # mgta_chimera_rec
 UNCHECKED = (2, -1, 0, 0, -1, 0, -1, 0, 0, 0, 0)
 MIN_SEG_RANGE, MIN_GAIN_RANGE = (1, 4096), (1, 1 << 20)
 

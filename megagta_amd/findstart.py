@@ -19,8 +19,7 @@ _CODE = {c: i for i, c in enumerate(AA)}
 _DECODE = AA.lower() + "*"                        # ProtKmer::intToChar: lower case (prot_kmer.h:36-37,43)
 
 
-class SeedHit(C.Structure):
-    _fields_ = [("read", C.c_uint64), ("pos_strand", C.c_uint32), ("ref", C.c_int32)]
+SeedHit = _lib.SeedHit                            # mgta_seed_hit
 
 
 def read_fasta(path: str):
@@ -83,7 +82,7 @@ def find_hits(ctx, reads, reads_reversed: bool, k: int, packed_words: np.ndarray
         check(ctx._L.mgta_findstart(ctx.h, reads.h, int(reads_reversed), k, pw.ctypes.data, pw.shape[0], hits, cap, C.byref(n), C.byref(ms)),
               "mgta_findstart")
         if n.value <= cap:
-            arr = np.frombuffer(hits, dtype=[("read", "<u8"), ("pos_strand", "<u4"), ("ref", "<i4")], count=n.value).copy()
+            arr = np.frombuffer(hits, dtype=_lib.RECORDS[SeedHit], count=n.value).copy()
             return arr, ms.value
         cap = int(n.value) + 1024
 

@@ -18,12 +18,12 @@ from __future__ import annotations
 
 import numpy as np
 
+from . import _lib
 from .align import record_name
 
 STATUS = ("aligned", "unaligned")
 FRAMESHIFT_HEADER = "#contig\tstatus\tref\tscore\tidentity\tlen\tref_len\tref_from\tref_to\tmatch\tident\tinsert\tdelete\tshort\tlong\tshifts\n"
-REC = np.dtype([("status", np.int32), ("ref", np.int32), ("score", np.int32), ("ref_from", np.int32), ("ref_to", np.int32), ("n_match", np.int32),
-                ("n_ident", np.int32), ("n_insert", np.int32), ("n_delete", np.int32), ("n_short", np.int32), ("n_long", np.int32)], align=True)
+REC = _lib.RECORDS[_lib.FrameshiftRec]                                # mgta_frameshift_rec
 CODON_AA = "KNKNTTTTRSRSIIMIQHQHPPPPRRRRLLLLEDEDAAAAGGGGVVVV*Y*YSSSS*CWCLFLF"
 _NT = {"A": 0, "C": 1, "G": 2, "T": 3, "a": 0, "c": 1, "g": 2, "t": 3}
 _TAKES = {"M": 3, "I": 3, "<": 2, ">": 4, "D": 0}

@@ -19,11 +19,11 @@ import sys
 
 import numpy as np
 
+from . import _lib
 from .pileup import MIN_ALT_PERMILLE, MIN_DEPTH, READ_DTYPE, _text, format_pileup
 
-PLACE_DTYPE = np.dtype([("score", "<i4"), ("contig", "<i4"), ("diag", "<i4"), ("orient", "<i4"), ("n_placed", "<u4"), ("n_mismatch", "<u4"),
-                        ("diag2", "<i4"), ("brk", "<u4")])                                            # mgta_gap_place
-GAP_DTYPE = np.dtype([("read", "<u8"), ("contig", "<i4"), ("pos", "<u4"), ("len", "<i4"), ("brk", "<u4"), ("orient", "<i4"), ("unique", "<i4")])   # mgta_gap_rec
+PLACE_DTYPE = _lib.RECORDS[_lib.GapPlace]                             # mgta_gap_place
+GAP_DTYPE = _lib.RECORDS[_lib.GapRec]                                 # mgta_gap_rec
 INDEL_HEADER = "#contig\tpos\ttype\tlen\tseq\treads\tunique\tdepth\n"
 _BASES = "ACGT"
 _COMP = str.maketrans("ACGT", "TGCA")

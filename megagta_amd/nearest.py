@@ -19,13 +19,13 @@ import os
 
 import numpy as np
 
+from . import _lib
 from .align import record_name
 
 STATUS = ("aligned", "unaligned")
 NEAREST_HEADER = "#contig\tstatus\tref\tscore\tidentity\tlen\tref_len\tref_from\tref_to\tmatch\tident\tinsert\tdelete\n"
 REFS_HEADER = "#ref\tref_len\tcontigs\tmean_identity\n"
-REC = np.dtype([("status", np.int32), ("ref", np.int32), ("score", np.int32), ("ref_from", np.int32), ("ref_to", np.int32), ("n_match", np.int32),
-                ("n_ident", np.int32), ("n_insert", np.int32), ("n_delete", np.int32)], align=True)
+REC = _lib.RECORDS[_lib.NearestRec]                                   # mgta_nearest_rec
 _LETTERS = "ABCDEFGHIJKLMNOPQRSTUVWXYZ"
 
 

@@ -15,9 +15,10 @@ from __future__ import annotations
 
 import numpy as np
 
-CONTIG_DTYPE = np.dtype([("len", "<u4"), ("n_covered", "<u4"), ("min_depth", "<u4"), ("max_depth", "<u4"), ("n_placed", "<u8"), ("n_unique", "<u8"),
-                         ("depth_sum", "<u8"), ("mismatch_sum", "<u8")])                               # mgta_contig_pileup
-READ_DTYPE = np.dtype([("score", "<i4"), ("contig", "<i4"), ("diag", "<i4"), ("orient", "<i4"), ("n_placed", "<u4"), ("n_mismatch", "<u4")])   # mgta_read_place
+from . import _lib
+
+CONTIG_DTYPE = _lib.RECORDS[_lib.ContigPileup]                        # mgta_contig_pileup
+READ_DTYPE = _lib.RECORDS[_lib.ReadPlace]                             # mgta_read_place
 SUMMARY_HEADER = "#contig\tlen\treads\tunique\tcovered\tmin\tmax\tmean\tmismatches\tvariants\n"
 BASE_HEADER = "#contig\tpos\tref\tdepth\tA\tC\tG\tT\tunique\n"
 MIN_DEPTH, MIN_ALT_PERMILLE = 8, 100

@@ -15,12 +15,12 @@ import math
 
 import numpy as np
 
+from . import _lib
 from .matchreads import match_reads_text, parse_match_reads
 
 LN2 = 0.6931471805599453          # the one constant bits are turned into nats with: nats = bits * LN2
 
-REC = np.dtype([("score", np.float64), ("model_from", np.int32), ("model_to", np.int32), ("aa_from", np.uint16), ("aa_len", np.uint16),
-                ("frame", np.uint8), ("status", np.uint8), ("pad", np.uint8, (2,))])
+REC = _lib.RECORDS[_lib.RecruitRec]                                   # mgta_recruit_rec
 assert REC.itemsize == 24
 
 HEADER = "#read\tframe\taa_from\taa_len\tbits\tmodel_from\tmodel_to"

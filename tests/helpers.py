@@ -307,3 +307,35 @@ def reads_behind_marks(payload_reads, fill_len: int, mode: str, seed: int):
     decoy = np.setdiff1d(np.concatenate([own % (m >> 4) for m in MARKS]), own)
     packed[decoy] = rng.integers(1, 1 << 32, decoy.size, dtype=np.uint64).astype(np.uint32)
     return packed, start, ids
+
+
+# ---- include/megagta_hip.h: the structs of the C ABI
+HEADER = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "include", "megagta_hip.h")
+
+
+def header_text() -> str:
+    return open(HEADER).read()
+
+
+def header_structs(hdr: str | None = None) -> dict:
+    """every `typedef struct mgta_X { ... } mgta_X;` of the header, in its order -> {"mgta_X": [(C type, member, array length or None), ...]}
+    with the members in their order: comments dropped, `int32_t a, b;` gives two members, `uint8_t pad[2];` one of length 2"""
+    import re
+    hdr = re.sub(r"/\*.*?\*/|//[^\n]*", " ", header_text() if hdr is None else hdr, flags=re.S)
+    out = {}
+    for name, body in re.findall(r"typedef\s+struct\s+(mgta_\w+)\s*\{(.*?)\}\s*\1\s*;", hdr, re.S):
+        members = []
+        for decl in filter(None, (d.strip() for d in body.split(";"))):
+            m = re.fullmatch(r"((?:unsigned\s+)?\w+)\s+(.+)", decl, re.S)
+            assert m, f"{name}: cannot read `{decl}`"
+            for item in m.group(2).split(","):
+                d = re.fullmatch(r"(\w+)\s*(?:\[\s*(\d+)\s*\])?", item.strip())
+                assert d, f"{name}: cannot read `{decl}`"
+                members.append((m.group(1), d.group(1), int(d.group(2)) if d.group(2) else None))
+        out[name] = members
+    return out
+
+
+def header_fields(struct: str, hdr: str | None = None) -> list[str]:
+    """the member names of one struct of the header, in order"""
+    return [name for _, name, _ in header_structs(hdr)[struct]]

@@ -10,6 +10,7 @@ import pytest
 
 from megagta_amd import _lib
 from megagta_amd import align as al
+from tests import helpers as H
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 BIN = os.path.join(ROOT, "megagta_amd", "bin", "megagta")
@@ -78,9 +79,7 @@ def test_new_symbols_are_declared():
     assert re.search(r"\bmgta_seqs_align\s*\(", hdr) and re.search(r"\bmgta_ctx_set_align_batch\s*\(", hdr)
     for struct, mirror in (("mgta_align_stats", _lib.AlignStats), ("mgta_align_rec", _lib.AlignRec)):
         fields = [n for n, _ in mirror._fields_]
-        body = re.search(r"typedef struct %s \{(.*?)\} %s;" % (struct, struct), hdr, re.S).group(1)
-        body = re.sub(r"/\*.*?\*/", "", body, flags=re.S)
-        names = [n for decl in body.split(";") for n in re.findall(r"\b([a-z_]+)\b\s*(?:,|$)", decl.strip())]
+        names = H.header_fields(struct, hdr)
         assert names == fields, struct                                    # the ctypes mirror has the header's order
     assert [n for n, _ in _lib.AlignRec._fields_] == list(al.REC.names)
     import ctypes

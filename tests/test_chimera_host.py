@@ -15,6 +15,7 @@ import pytest
 from megagta_amd import _lib, api
 from megagta_amd import chimera as ch
 from megagta_amd import nearest as nr
+from tests import helpers as H
 from tests.test_chimera_gpu import (cls, prefix_scores, random_seq, restate_chimera, row_maxima, score, suffix_scores_by_reversal, suffix_scores_literal, top_two,
                                     variant)
 
@@ -81,9 +82,7 @@ def test_new_symbols_are_declared():
         assert re.search(r"\b%s\s*\(" % name, hdr), name
     for struct, mirror in (("mgta_chimera_stats", _lib.ChimeraStats), ("mgta_chimera_rec", _lib.ChimeraRec)):
         fields = [n for n, _ in mirror._fields_]
-        body = re.search(r"typedef struct %s \{(.*?)\} %s;" % (struct, struct), hdr, re.S).group(1)
-        body = re.sub(r"/\*.*?\*/", "", body, flags=re.S)
-        names = [n for decl in body.split(";") for n in re.findall(r"\b([a-z_]+)\b\s*(?:,|$)", decl.strip())]
+        names = H.header_fields(struct, hdr)
         assert names == fields, struct                                    # the ctypes mirror has the header's order
     assert [n for n, _ in _lib.ChimeraRec._fields_] == list(api.CHIMERA_REC.names) == list(ch.REC.names)
     assert [n for n, _ in _lib.ChimeraRec._fields_] == ["status", "ref", "score", "brk", "left_ref", "left_score", "right_ref", "right_score", "two", "one", "gain"]

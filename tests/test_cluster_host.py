@@ -13,6 +13,7 @@ import pytest
 
 from megagta_amd import _lib, api
 from megagta_amd import cluster as cl
+from tests import helpers as H
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 BIN = os.path.join(ROOT, "megagta_amd", "bin", "megagta")
@@ -80,9 +81,7 @@ def test_new_symbols_are_declared():
         assert re.search(r"\b%s\s*\(" % name, hdr), name
     for struct, mirror in (("mgta_cluster_stats", _lib.ClusterStats), ("mgta_row_pair", _lib.RowPair)):
         fields = [n for n, _ in mirror._fields_]
-        body = re.search(r"typedef struct %s \{(.*?)\} %s;" % (struct, struct), hdr, re.S).group(1)
-        body = re.sub(r"/\*.*?\*/", "", body, flags=re.S)
-        names = [n for decl in body.split(";") for n in re.findall(r"\b([a-z_]+)\b\s*(?:,|$)", decl.strip())]
+        names = H.header_fields(struct, hdr)
         assert names == fields, struct                                    # the ctypes mirror has the header's order
     assert [n for n, _ in _lib.RowPair._fields_] == list(api.ROW_PAIR.names)
     assert ctypes.sizeof(_lib.RowPair) == api.ROW_PAIR.itemsize == 12

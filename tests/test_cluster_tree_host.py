@@ -13,6 +13,7 @@ import pytest
 
 from megagta_amd import _lib, api
 from megagta_amd import cluster as cl
+from tests import helpers as H
 from tests.test_cluster_gpu import GAP, is_kept, restate_link
 from tests.test_cluster_host import _fresh_driver
 from tests.test_cluster_tree_gpu import restate_tree
@@ -136,8 +137,7 @@ def test_new_symbols_are_declared():
     for name in new:
         assert f"int {name}(" in hdr
     # the structures of _lib are those of the header, field for field
-    body = hdr[hdr.index("typedef struct mgta_tree_stats {"):hdr.index("} mgta_tree_stats;")]
-    fields = [w.strip() for line in body.splitlines()[1:] for w in line.split("/*")[0].replace("int64_t", "").replace("double", "").replace(";", "").split(",") if w.strip()]
+    fields = H.header_fields("mgta_tree_stats", hdr)
     assert fields == [n for n, _ in _lib.TreeStats._fields_]
     assert C.sizeof(_lib.TreeStats) == 8 * len(fields) and api.TREE_MERGE.itemsize == 12 and api.TREE_MERGE.names == ("a", "b", "n_diff", "n_overlap")
 

@@ -8,6 +8,7 @@ import numpy as np
 import pytest
 
 from megagta_amd import _lib, gapped as gp, pileup as pl
+from tests import helpers as H
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
@@ -90,9 +91,7 @@ def test_header_declares_the_entry_and_the_structures_match():
     assert "mgta_reads_pileup_gapped" in _lib.SYMBOLS and len(_lib.SYMBOLS["mgta_reads_pileup_gapped"][1]) == 15
 
     def fields(name):
-        body = re.search(r"typedef struct %s \{(.*?)\} %s;" % (name, name), hdr, re.S).group(1)
-        body = re.sub(r"/\*.*?\*/", "", body, flags=re.S)
-        return [(decl.split(None, 1)[0], n.strip()) for decl in body.split(";") if decl.strip() for n in decl.split(None, 1)[1].split(",")]
+        return [(ctype, member) for ctype, member, _ in H.header_structs(hdr)[name]]
     size = {"int32_t": 4, "uint32_t": 4, "int64_t": 8, "uint64_t": 8, "double": 8}
     assert [n for _, n in fields("mgta_gapped_params")] == [n for n, _ in _lib.GappedParams._fields_] and C.sizeof(_lib.GappedParams) == 24
     assert [n for _, n in fields("mgta_gapped_stats")] == [n for n, _ in _lib.GappedStats._fields_]

@@ -13,6 +13,7 @@ import pytest
 
 from megagta_amd import _lib, api
 from megagta_amd import nearest as nr
+from tests import helpers as H
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 BIN = os.path.join(ROOT, "megagta_amd", "bin", "megagta")
@@ -133,9 +134,7 @@ def test_new_symbols_are_declared():
         assert re.search(r"\b%s\s*\(" % name, hdr), name
     for struct, mirror in (("mgta_nearest_stats", _lib.NearestStats), ("mgta_nearest_rec", _lib.NearestRec)):
         fields = [n for n, _ in mirror._fields_]
-        body = re.search(r"typedef struct %s \{(.*?)\} %s;" % (struct, struct), hdr, re.S).group(1)
-        body = re.sub(r"/\*.*?\*/", "", body, flags=re.S)
-        names = [n for decl in body.split(";") for n in re.findall(r"\b([a-z_]+)\b\s*(?:,|$)", decl.strip())]
+        names = H.header_fields(struct, hdr)
         assert names == fields, struct                                    # the ctypes mirror has the header's order
     assert [n for n, _ in _lib.NearestRec._fields_] == list(api.NEAREST_REC.names) == list(nr.REC.names)
     assert ctypes.sizeof(_lib.NearestRec) == api.NEAREST_REC.itemsize == nr.REC.itemsize == 36

@@ -9,6 +9,7 @@ import pytest
 
 from megagta_amd import _lib
 from megagta_amd import phase as ph
+from tests import helpers as H
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
@@ -178,9 +179,7 @@ def test_header_declares_the_entries_and_the_structures_match():
     for name, n_args in (("mgta_phase_pairs", 5), ("mgta_reads_phase", 16), ("mgta_ctx_set_phase_chunk", 2)):
         assert name in _lib.SYMBOLS and len(_lib.SYMBOLS[name][1]) == n_args, name
         assert hasattr(_lib.load(), name)
-    body = re.search(r"typedef struct mgta_phase_stats \{(.*?)\} mgta_phase_stats;", hdr, re.S).group(1)
-    body = re.sub(r"/\*.*?\*/", "", body, flags=re.S)
-    fields = [n.strip() for decl in body.split(";") if decl.strip() for n in decl.split(None, 1)[1].split(",")]
+    fields = H.header_fields("mgta_phase_stats", hdr)
     assert fields == [n for n, _ in _lib.PhaseStats._fields_]
     assert "PREFIX_phase_links.txt" in ph.__doc__ and ph.LINK_DTYPE.names == ("contig", "u", "v", "fragments", "phased")
 

@@ -8,6 +8,7 @@ import pytest
 
 from megagta_amd import _lib
 from megagta_amd import pileup as pl
+from tests import helpers as H
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 NAMES = ["c1", "empty", "c3"]
@@ -125,7 +126,5 @@ def test_header_declares_the_entry_and_the_structures_match():
     assert "typedef struct mgta_pileup_params { int32_t min_anchors, min_overlap, max_mismatch_permille; } mgta_pileup_params;" in hdr
     assert "mgta_reads_pileup" in _lib.SYMBOLS and "mgta_ctx_set_pileup_chunk" in _lib.SYMBOLS and len(_lib.SYMBOLS["mgta_reads_pileup"][1]) == 13
     assert pl.CONTIG_DTYPE.itemsize == 48 and pl.READ_DTYPE.itemsize == 24
-    body = re.search(r"typedef struct mgta_pileup_stats \{(.*?)\} mgta_pileup_stats;", hdr, re.S).group(1)
-    body = re.sub(r"/\*.*?\*/", "", body, flags=re.S)
-    fields = [n.strip() for decl in body.split(";") if decl.strip() for n in decl.split(None, 1)[1].split(",")]
+    fields = H.header_fields("mgta_pileup_stats", hdr)
     assert fields == [n for n, _ in _lib.PileupStats._fields_]

@@ -15,6 +15,7 @@ from megagta_amd import _lib
 from megagta_amd import hmm as H
 from megagta_amd import readlib, synth
 from megagta_amd import recruit as rc
+from tests import helpers
 from tests import recruit_ref as ref
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -200,9 +201,7 @@ def test_header_declares_the_entry_and_the_structures_match():
     assert "mgta_reads_recruit" in _lib.SYMBOLS and "mgta_ctx_set_recruit_chunk" in _lib.SYMBOLS and len(_lib.SYMBOLS["mgta_reads_recruit"][1]) == 10
     assert rc.REC.itemsize == ctypes.sizeof(_lib.RecruitRec) == 24 and ctypes.sizeof(_lib.RecruitParams) == 16
     assert [rc.REC.fields[n][1] for n in ("score", "model_from", "model_to", "aa_from", "aa_len", "frame", "status")] == [0, 8, 12, 16, 18, 20, 21]
-    body = re.search(r"typedef struct mgta_recruit_stats \{(.*?)\} mgta_recruit_stats;", hdr, re.S).group(1)
-    body = re.sub(r"/\*.*?\*/", "", body, flags=re.S)
-    fields = [re.sub(r"\[\d+\]", "", n).strip() for decl in body.split(";") if decl.strip() for n in decl.split(None, 1)[1].split(",")]
+    fields = helpers.header_fields("mgta_recruit_stats", hdr)
     assert fields == [n for n, _ in _lib.RecruitStats._fields_]
     assert os.path.exists(_lib.LIB_PATH), "libmegagta_hip.so missing: run __graft_entry__.build()"
     L = ctypes.CDLL(_lib.LIB_PATH)

@@ -14,6 +14,7 @@ import pytest
 from megagta_amd import _lib, readlib
 from megagta_amd import cluster as clustlib
 from megagta_amd import samplecov as sc
+from tests import helpers as H
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 DRIVER = os.path.join(ROOT, "megagta_amd", "megagta.py")
@@ -222,8 +223,7 @@ def test_library_and_header_have_the_symbol():
     header = open(os.path.join(ROOT, "include", "megagta_hip.h")).read()
     assert "int mgta_contig_sample_coverage(mgta_sdbg *, const mgta_reads *reads, int reads_reversed, const uint64_t *lib_end" in header
     assert "typedef struct mgta_sample_cov_stats {" in header
-    body = header[header.index("typedef struct mgta_sample_cov_stats {"):header.index("} mgta_sample_cov_stats;")]
-    fields = re.findall(r"\b(n_\w+|total_mass|table_slots|table_bytes|window_bytes|count_bytes|groups_per_cu|ms_\w+)\b(?=[,;])", body)
+    fields = H.header_fields("mgta_sample_cov_stats", header)
     assert fields == [n for n, _ in _lib.SampleCovStats._fields_] and ctypes.sizeof(_lib.SampleCovStats) == 8 * len(fields)
     if not os.path.exists(_lib.LIB_PATH):
         import __graft_entry__

@@ -4,6 +4,8 @@ and undefined-behaviour sanitizers.  No device."""
 import os
 import subprocess
 
+from tests import helpers as H
+
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 CSRC = os.path.join(ROOT, "megagta_amd", "csrc")
 
@@ -18,11 +20,8 @@ def test_packer_and_list_capacities_under_sanitizers(tmp_path):
 
 def test_stats_struct_mirrors_the_header():
     """n_split_levels is the last field of mgta_build_stats, in the header and in the ctypes mirror"""
-    import re
     from megagta_amd import _lib
     hdr = open(os.path.join(ROOT, "include", "megagta_hip.h")).read()
-    body = re.search(r"typedef struct mgta_build_stats \{(.*?)\} mgta_build_stats;", hdr, re.S).group(1)
-    body = re.sub(r"/\*.*?\*/", "", body, flags=re.S)
-    names = [n.strip() for decl in body.split(";") if decl.strip() for n in decl.strip().split(None, 1)[1].split(",")]
+    names = H.header_fields("mgta_build_stats", hdr)
     assert names == [n for n, _ in _lib.BuildStats._fields_]
     assert names[-1] == "n_split_levels"
