@@ -145,14 +145,14 @@ __device__ __forceinline__ uint32_t chain_ticket(uint32_t *ticket, uint32_t *s_s
     return wave_uniform(*s_slot);
 }
 
-// one full wave calls with the same (tile, agg); returns the sum of the aggregates of the tiles before `tile`
-__device__ __forceinline__ uint64_t chain_exclusive(unsigned long long *state, uint32_t tile, uint64_t agg, uint32_t *error) {
+// The two halves of chain_exclusive, for a wave that has work of its own to do between them: chain_publish as soon as the tile's
+// aggregate is known, chain_look_back (same wave, same arguments) when the prefix is needed.
+__device__ __forceinline__ void chain_publish(unsigned long long *state, uint32_t tile, uint64_t agg) {
+    if (lane_id() == 0) __hip_atomic_store(&state[tile], (tile == 0 ? kChainInclusive : kChainAggregate) | agg, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+}
+__device__ __forceinline__ uint64_t chain_look_back(unsigned long long *state, uint32_t tile, uint64_t agg, uint32_t *error) {
     const int lane = lane_id();
-    if (tile == 0) {
-        if (lane == 0) __hip_atomic_store(&state[0], kChainInclusive | agg, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        return 0;
-    }
-    if (lane == 0) __hip_atomic_store(&state[tile], kChainAggregate | agg, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    if (tile == 0) return 0;
     uint64_t excl = 0;
     long long base = (long long)tile - 1;                             // the nearest predecessor not summed yet
     uint32_t spins = 0;
@@ -178,6 +178,11 @@ __device__ __forceinline__ uint64_t chain_exclusive(unsigned long long *state, u
     }
     if (lane == 0) __hip_atomic_store(&state[tile], kChainInclusive | ((excl + agg) & kChainValue), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
     return excl;
+}
+// one full wave calls with the same (tile, agg); returns the sum of the aggregates of the tiles before `tile`
+__device__ __forceinline__ uint64_t chain_exclusive(unsigned long long *state, uint32_t tile, uint64_t agg, uint32_t *error) {
+    chain_publish(state, tile, agg);
+    return chain_look_back(state, tile, agg, error);
 }
 
 }  // namespace mgta

@@ -1944,7 +1944,18 @@ struct EmitChain {
     uint32_t *ticket;            // zeroed
     uint32_t *error;
     unsigned long long *total;   // number of runs, written by the last tile
+    unsigned long long *dollar;  // [kDollarSlots], zeroed: the runs whose a is $ (an upper bound of the tips), summed by the host
 };
+constexpr int kDollarSlots = 64; // one atomic per workgroup, spread over this many addresses
+// all threads of the workgroup call once (two barriers): mine = the heads with a = $ this thread saw
+__device__ __forceinline__ void count_dollar_heads(const EmitChain &chain, uint32_t tile, uint32_t mine, uint32_t *s_sum) {
+    if (threadIdx.x == 0) *s_sum = 0;
+    __syncthreads();
+    mine = wave_sum(mine);
+    if (lane_id() == 0 && mine) atomicAdd(s_sum, mine);
+    __syncthreads();
+    if (threadIdx.x == 0 && *s_sum) atomicAdd(&chain.dollar[tile % kDollarSlots], (unsigned long long)*s_sum);
+}
 
 // TICKET = false numbers the tiles by blockIdx (workgroups are dispatched in that order on this hardware, which nothing guarantees):
 // if a tile ever waits in vain the bounded walk raises chain.error and the host repeats the launch with TICKET = true.
@@ -1953,12 +1964,12 @@ __global__ __launch_bounds__(kEmitThreads) void emit_compact_kernel(const Key<W>
                                                                      RunStarts sub_start, uint8_t *sub_info) {
     __shared__ uint32_t s_cnt[kEmitPerThread * (kEmitThreads / 64)];
     __shared__ uint32_t s_scr[kEmitThreads / 64 + 1];
-    __shared__ uint32_t s_tile;
+    __shared__ uint32_t s_tile, s_dollar;
     __shared__ unsigned long long s_base;
     const uint32_t tile = TICKET ? chain_ticket(chain.ticket, &s_tile) : blockIdx.x;
     uint64_t base = (uint64_t)tile * kEmitTile;
     const int lane = lane_id(), wv = wave_id();
-    uint32_t headbits = 0;
+    uint32_t headbits = 0, n_dollar = 0;
     uint32_t rank_in_wave[kEmitPerThread];
     uint8_t info[kEmitPerThread];
 #pragma unroll
@@ -2002,8 +2013,10 @@ __global__ __launch_bounds__(kEmitThreads) void emit_compact_kernel(const Key<W>
             sub_start.lo[s] = (uint32_t)idx;
             if ((s & ((1u << kRunBaseStepLog) - 1)) == 0) sub_start.base[s >> kRunBaseStepLog] = idx;
             sub_info[s] = info[it];
+            n_dollar += (info[it] & 7) == kDollar;
         }
     }
+    count_dollar_heads(chain, tile, n_dollar, &s_dollar);
 }
 
 // The same compaction from the info array the sort left behind (one byte per key position, kInfoNoHead where no run starts): the
@@ -2020,7 +2033,7 @@ __global__ __launch_bounds__(kEmitThreads) void emit_compact_info_kernel(const u
     static_assert(kEmitPerThread == 16, "one 16-byte load per lane and round");
     static_assert(kInfoRounds == 8 && kEmitTile <= 65535, "round counts are scanned as 2 x 4 fields of 16 bits");
     __shared__ uint64_t s_scr[kEmitThreads / 64 + 1];
-    __shared__ uint32_t s_tile;
+    __shared__ uint32_t s_tile, s_dollar;
     __shared__ unsigned long long s_base;
     __shared__ uint16_t s_off[kEmitTile];                  // the descriptors of a round: position inside the round, info byte
     __shared__ uint8_t s_inf[kEmitTile];
@@ -2065,6 +2078,7 @@ __global__ __launch_bounds__(kEmitThreads) void emit_compact_info_kernel(const u
         }
     }
     uint64_t tb = 0;
+    uint32_t n_dollar = 0;
 #pragma unroll
     for (int r = 0; r < kInfoRounds; ++r) {
         if (round_total[r] == 0) continue;                 // (workgroup-uniform)
@@ -2085,10 +2099,13 @@ __global__ __launch_bounds__(kEmitThreads) void emit_compact_info_kernel(const u
             const uint64_t s = out0 + i, idx = pos0 + s_off[i];
             sub_start.lo[s] = (uint32_t)idx;
             if ((s & ((1u << kRunBaseStepLog) - 1)) == 0) sub_start.base[s >> kRunBaseStepLog] = idx;
-            sub_info[s] = s_inf[i];
+            const uint8_t inf = s_inf[i];
+            sub_info[s] = inf;
+            n_dollar += (inf & 7) == kDollar;
         }
         __syncthreads();                                   // the stage is free again
     }
+    count_dollar_heads(chain, tile, n_dollar, &s_dollar);
 }
 
 // MGTA_EMIT_FUSED=2: the m run descriptors of emit_compact_info_kernel against those of emit_compact_kernel (bad[0]: starts, bad[1]: info bytes)
@@ -2222,8 +2239,11 @@ __global__ __launch_bounds__(kDecideThreads) void emit_write_kernel(const Key<W>
         if (s < m) {
             r[q] = rec[s];
             if (r[q] != 0xFFFF) {
-                uint64_t run = run_length(sub_start, s, m, n_items);
-                cnts[q] = run > 65535 ? 65535u : (uint32_t)run;
+                cnts[q] = r[q] >> 8;                               // (the run starts are read for the runs above 254 only)
+                if (cnts[q] == 255) {
+                    uint64_t run = run_length(sub_start, s, m, n_items);
+                    cnts[q] = run > 65535 ? 65535u : (uint32_t)run;
+                }
                 packed += 1ull + ((uint64_t)(cnts[q] > 254) << 20) + ((uint64_t)((r[q] >> 5) & 1) << 40);
             }
         }
@@ -2251,6 +2271,267 @@ __global__ __launch_bounds__(kDecideThreads) void emit_write_kernel(const Key<W>
             }
         }
     }
+}
+
+// E3-E5 in one kernel (MGTA_EMIT_CHAIN): emit_decide_kernel's decision and emit_write_kernel's compaction behind two chained scans
+// across the workgroups, so that no record of a run, no per-tile count and no base ever goes through device memory.  A workgroup
+// takes kChainRounds rounds of kDecideTile runs (lane <-> run as in emit_decide_kernel) and issues the loads of the descriptors
+// -- the info bytes of the tile and a halo, 16 at a time, and both run starts of every run, half the rounds at a time -- before it
+// uses one.  The decision (one byte: w | last << 4 | tip << 5, 0xFF suppressed) and the capped count of every run stay in
+// registers; the counts per (round, q, wave) are scanned in LDS, wave 0 publishes the tile's emitted records to one chain and wave 1
+// its large << kChainTipBits | tips to the other, every wave collects its records in LDS in stream order, and only then do the two
+// waves look back.  The records leave as one run of 16-byte stores.  Runs above 254, tips and bucket heads are rare; they leave
+// lane by lane.  sub_info is 16-byte aligned and readable up to the next multiple of 16 behind m.
+constexpr int kChainRounds = 8;
+constexpr int kChainTile = kDecideTile * kChainRounds;     // 8192 runs per workgroup
+constexpr int kChainSlots = kChainRounds * kDecidePerThread * (kDecideThreads / 64);
+constexpr int kChainTipBits = 34;                          // host: tips <= m < 2^34, large <= n_items / 255 < 2^(62 - 34)
+static_assert(kChainTipBits < 62 && kChainTile < (1 << 20), "the second chain's value, the packed tile counts");
+struct DecideChain {
+    unsigned long long *state_e, *state_lt;   // [n_tiles] each, zeroed
+    uint32_t *ticket, *error;                  // zeroed
+    uint64_t *totals;                          // [3] emitted, large, tips: written by the last tile
+};
+
+template <int W, bool TICKET>
+__global__ __launch_bounds__(kDecideThreads, 6) void emit_decide_write_kernel(const Key<W> *keys, RunStarts sub_start, const uint8_t *sub_info, uint64_t m,
+                                                                            uint64_t n_items, DecideChain chain, uint32_t n_tiles, int words_per_tip,
+                                                                            uint32_t b_lo, uint16_t *out_rec, uint16_t *out_large, uint32_t *out_tips,
+                                                                            int64_t *bucket_first /* [nb][3] */) {
+    constexpr int NW = kDecideThreads / 64, NQ = kDecidePerThread;
+    constexpr int kChunks = (kChainTile + 2 * kDecideHalo) / 16, kChunkIters = (kChunks + kDecideThreads - 1) / kDecideThreads;
+    static_assert(NQ == 4 && kDecideHalo % 16 == 0 && kChainSlots <= kDecideThreads, "four decisions per word; 16-byte loads; one scan");
+    __shared__ uint4 s_info4[kChunks];
+    __shared__ uint16_t s_out[kChainTile];
+    __shared__ uint64_t s_cnt[kChainSlots];                // emitted | large << 20 | tips << 40 per (round, q, wave), then their prefix
+    __shared__ uint64_t s_scr[NW + 1];
+    __shared__ uint32_t s_tile;
+    __shared__ unsigned long long s_base[2];
+    const uint8_t *s_info = reinterpret_cast<const uint8_t *>(s_info4);    // s_info[x - t0 + kDecideHalo]
+    const uint32_t tile = TICKET ? chain_ticket(chain.ticket, &s_tile) : blockIdx.x;
+    const uint64_t t0 = (uint64_t)tile * kChainTile;
+    const uint32_t tid = threadIdx.x;
+    const int lane = lane_id(), wv = wave_id();
+    // positions inside the tile are 32-bit offsets from t0 (a walk stays within a group's 24 runs): j < m_l <=> t0 + j < m
+    const uint8_t *info_t = sub_info + t0;
+    const uint32_t *lo_t = sub_start.lo + t0;
+    const int m_l = (int)(m - t0 < (1ull << 30) ? m - t0 : (1ull << 30));
+    const uint32_t n_t = (uint32_t)(m_l < kChainTile + 1 ? m_l : kChainTile + 1);      // the runs of the tile, and the one behind it
+    const int w_lo = tile ? -kDecideHalo : 0, w_hi = m_l < kChainTile + kDecideHalo ? m_l : kChainTile + kDecideHalo;   // what LDS holds
+
+    // ---- every load first
+    uint4 iv[kChunkIters];
+#pragma unroll
+    for (int j = 0; j < kChunkIters; ++j) {
+        const uint32_t c = (uint32_t)j * kDecideThreads + tid;
+        const int at = 16 * (int)c - kDecideHalo;
+        iv[j] = make_uint4(0, 0, 0, 0);
+        if (c < (uint32_t)kChunks && at >= w_lo && at < m_l) iv[j] = *reinterpret_cast<const uint4 *>(info_t + at);
+    }
+    // the count of every run, capped at 65535 (kMaxMulti_t), two per word: both starts of the runs of half the rounds are in flight at
+    // a time (all of them at once need more registers than six waves per SIMD leave)
+    uint32_t cnt2[kChainRounds][NQ / 2];
+    const bool owns_last = n_t <= (uint32_t)kChainTile && ((n_t - 1) & (kDecideThreads - 1)) == tid;   // the last run of all ends with the keys
+    uint32_t last_len = 0;
+#pragma unroll
+    for (int half = 0; half < 2; ++half) {
+        uint32_t lo0[kChainRounds / 2][NQ], lo1[kChainRounds / 2][NQ];
+#pragma unroll
+        for (int r = 0; r < kChainRounds / 2; ++r)
+#pragma unroll
+            for (int q = 0; q < NQ; ++q) {                 // (clamped, not skipped: no branch between the loads)
+                const uint32_t idx = (uint32_t)(((half * (kChainRounds / 2) + r) * NQ + q) * kDecideThreads) + tid;
+                lo0[r][q] = lo_t[idx < n_t - 1 ? idx : n_t - 1];
+                lo1[r][q] = lo_t[idx + 1 < n_t - 1 ? idx + 1 : n_t - 1];
+            }
+        if (half == 0) {
+#pragma unroll
+            for (int j = 0; j < kChunkIters; ++j) {
+                const uint32_t c = (uint32_t)j * kDecideThreads + tid;
+                if (c < (uint32_t)kChunks) s_info4[c] = iv[j];
+            }
+            if (owns_last) {
+                const uint64_t rest = n_items - run_full_start(sub_start, t0 + n_t - 1);
+                last_len = rest > 65535 ? 65535u : (uint32_t)rest;
+            }
+        }
+        __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+        for (int r = 0; r < kChainRounds / 2; ++r) {
+            const int rr = half * (kChainRounds / 2) + r;
+            cnt2[rr][0] = cnt2[rr][1] = 0;
+#pragma unroll
+            for (int q = 0; q < NQ; ++q) {
+                uint32_t len = lo1[r][q] - lo0[r][q];
+                if (owns_last && (uint32_t)(rr * NQ + q) == (n_t - 1) / kDecideThreads) len = last_len;
+                cnt2[rr][q >> 1] |= (len > 65535u ? 65535u : len) << (16 * (q & 1));
+            }
+            // (the compiler must not see through the packing, or it keeps all the counts in a register each)
+            asm volatile("" : "+v"(cnt2[rr][0]), "+v"(cnt2[rr][1]));
+        }
+        __builtin_amdgcn_sched_barrier(0);
+    }
+    __syncthreads();
+
+    // ---- the decision of every run: emit_decide_kernel's, on the LDS copy of the descriptors
+    auto info_at = [&](int j) -> int { return (j >= w_lo && j < w_hi) ? (int)s_info[j + kDecideHalo] : (int)info_t[j]; };
+    uint32_t dec[kChainRounds];
+#pragma unroll
+    for (int r = 0; r < kChainRounds; ++r) dec[r] = ~0u;
+#pragma unroll 1
+    for (int r = 0; r < kChainRounds; ++r) {               // (one copy of the walks; the round's registers are picked by compares)
+        uint32_t c01 = 0, c23 = 0, dr = 0;
+#pragma unroll
+        for (int rr = 0; rr < kChainRounds; ++rr)
+            if (rr == r) { c01 = cnt2[rr][0]; c23 = cnt2[rr][1]; }
+#pragma unroll
+        for (int q = 0; q < NQ; ++q) {
+            const int s = (r * NQ + q) * kDecideThreads + (int)tid;
+            const uint32_t count = ((q & 2 ? c23 : c01) >> (16 * (q & 1))) & 0xFFFFu;
+            uint32_t d = 0xFFu;
+            if (s < m_l) {
+                const int inf = info_at(s);
+                const int a = inf & 7, b = (inf >> 3) & 7;
+                // group extent [gs, ge): the characters its solid runs carry are collected on the way, and the walk back also answers
+                // outputed_b (s2.cpp:822-824): a run in front with the same b is not suppressed if its a != $, or if its a == $ and no
+                // solid run of the group carries b
+                int has_a = 0, has_b = 0;
+                auto collect = [&](int xi) {
+                    const int xa = xi & 7, xb = (xi >> 3) & 7;
+                    if (xa != kDollar && xb != kDollar) { has_a |= 1 << xa; has_b |= 1 << xb; }
+                };
+                collect(inf);
+                bool front_b_solid = false, front_b_dollar = false;
+                int gs = s;
+                for (int gi = inf; !(gi & 64);) {
+                    --gs; gi = info_at(gs); collect(gi);
+                    if (((gi >> 3) & 7) == b) { if ((gi & 7) != kDollar) front_b_solid = true; else front_b_dollar = true; }
+                }
+                int ge = s + 1;
+                while (ge < m_l) {
+                    const int xi = info_at(ge);
+                    if (xi & 64) break;
+                    collect(xi);
+                    ++ge;
+                }
+                if (!run_suppressed(a, b, has_a, has_b)) {
+                    const bool seen_b = front_b_solid || (front_b_dollar && !((has_b >> b) & 1));
+                    const int w = (b == kDollar) ? 0 : (seen_b ? b + 5 : b + 1);
+                    int last = 0;
+                    if (a != kDollar) {                    // last_a[], s2.cpp:776-779,823
+                        bool later = false;
+                        for (int x = s + 1; x < ge; ++x) {
+                            const int xi = info_at(x), xa = xi & 7, xb = (xi >> 3) & 7;
+                            if (xa == a && (xb != kDollar || !((has_a >> a) & 1))) later = true;
+                        }
+                        last = later ? 0 : 1;
+                    }
+                    d = (uint32_t)(w | (last << 4) | ((a == kDollar) << 5));
+                }
+            }
+            dr |= d << (8 * q);
+            const bool em = d != 0xFFu;
+            const uint64_t bal_e = __ballot(em), bal_l = __ballot(em && count > 254u), bal_t = __ballot(em && (d & 32u));   // > 254: kMaxMulti2_t
+            if (lane == 0)
+                s_cnt[(r * NQ + q) * NW + wv] = (uint64_t)__popcll(bal_e) | (uint64_t)__popcll(bal_l) << 20 | (uint64_t)__popcll(bal_t) << 40;
+        }
+#pragma unroll
+        for (int rr = 0; rr < kChainRounds; ++rr)
+            if (rr == r) dec[rr] = dr;
+    }
+    __syncthreads();
+
+    // ---- the tile's three counts, their prefix inside the tile, and the aggregates out to the chains
+    uint64_t tot = 0;
+    const uint64_t ex = block_excl_scan64<kDecideThreads>(tid < (uint32_t)kChainSlots ? s_cnt[tid] : 0ull, s_scr, &tot);
+    if (tid < (uint32_t)kChainSlots) s_cnt[tid] = ex;
+    const uint32_t te = (uint32_t)tot & 0xFFFFFu, tl = (uint32_t)(tot >> 20) & 0xFFFFFu, tt = (uint32_t)(tot >> 40);
+    const uint64_t agg_lt = (uint64_t)tl << kChainTipBits | tt;
+    if (wv == 0) chain_publish(chain.state_e, tile, te);
+    if (wv == 1) chain_publish(chain.state_lt, tile, agg_lt);
+    __syncthreads();
+
+    // ---- the records in stream order, in LDS (order of the runs: round, q, wave, lane)
+#pragma unroll
+    for (int r = 0; r < kChainRounds; ++r)
+#pragma unroll
+        for (int q = 0; q < NQ; ++q) {
+            const uint32_t d = (dec[r] >> (8 * q)) & 0xFFu, count = (cnt2[r][q >> 1] >> (16 * (q & 1))) & 0xFFFFu;
+            const bool em = d != 0xFFu;
+            const uint64_t bal_e = __ballot(em);
+            if (em) {
+                const uint32_t at = ((uint32_t)s_cnt[(r * NQ + q) * NW + wv] & 0xFFFFFu) + (uint32_t)__popcll(bal_e & lanemask_lt());
+                s_out[at] = (uint16_t)(d | (count > 255u ? 255u : count) << 8);
+            }
+        }
+    if (wv == 0) {
+        const uint64_t before = chain_look_back(chain.state_e, tile, te, chain.error);
+        if (lane == 0) {
+            s_base[0] = before;
+            if (tile + 1 == n_tiles) chain.totals[0] = before + te;
+        }
+    }
+    if (wv == 1) {
+        const uint64_t before = chain_look_back(chain.state_lt, tile, agg_lt, chain.error);
+        if (lane == 0) {
+            s_base[1] = before;
+            if (tile + 1 == n_tiles) { chain.totals[1] = (before >> kChainTipBits) + tl; chain.totals[2] = (before & ((1ull << kChainTipBits) - 1ull)) + tt; }
+        }
+    }
+    __syncthreads();
+    const uint64_t be = s_base[0], bl = s_base[1] >> kChainTipBits, bt = s_base[1] & ((1ull << kChainTipBits) - 1ull);
+
+    // ---- the records out: single ones up to the first 16-byte boundary of the stream, eight per store, single ones again
+    {
+        uint32_t head = (uint32_t)((8u - (uint32_t)(be & 7u)) & 7u);
+        if (head > te) head = te;
+        const uint32_t n8 = (te - head) >> 3, tail0 = head + (n8 << 3);
+        if (tid < head) out_rec[be + tid] = s_out[tid];
+        for (uint32_t c = tid; c < n8; c += kDecideThreads) {
+            const uint32_t i = head + (c << 3);
+            uint4 v;
+            v.x = (uint32_t)s_out[i] | (uint32_t)s_out[i + 1] << 16; v.y = (uint32_t)s_out[i + 2] | (uint32_t)s_out[i + 3] << 16;
+            v.z = (uint32_t)s_out[i + 4] | (uint32_t)s_out[i + 5] << 16; v.w = (uint32_t)s_out[i + 6] | (uint32_t)s_out[i + 7] << 16;
+            *reinterpret_cast<uint4 *>(out_rec + be + i) = v;
+        }
+        if (tail0 + tid < te) out_rec[be + tail0 + tid] = s_out[tail0 + tid];
+    }
+
+    // ---- the runs above 254, the tips and the bucket heads: the only ones with a second output, the last two the only ones that
+    // look at a key
+#pragma unroll
+    for (int r = 0; r < kChainRounds; ++r)
+#pragma unroll
+        for (int q = 0; q < NQ; ++q) {
+            const int k0 = (r * NQ + q) * kDecideThreads;                               // the run is t0 + k0 + tid
+            const uint32_t d = (dec[r] >> (8 * q)) & 0xFFu, count = (cnt2[r][q >> 1] >> (16 * (q & 1))) & 0xFFFFu;
+            const bool em = d != 0xFFu, large = em && count > 254u, tip = em && (d & 32u);
+            const bool bucket_head = (int)tid < m_l - k0 && (s_info[kDecideHalo + k0 + tid] & 128) != 0;
+            if (__ballot(large || tip || bucket_head) == 0) continue;                  // (wave-uniform)
+            const uint64_t bal_e = __ballot(em), bal_l = __ballot(large), bal_t = __ballot(tip), lt = lanemask_lt();
+            const uint64_t x = s_cnt[(r * NQ + q) * NW + wv];
+            const uint64_t ie = be + ((uint32_t)x & 0xFFFFFu) + (uint32_t)__popcll(bal_e & lt);
+            const uint64_t il = bl + ((uint32_t)(x >> 20) & 0xFFFFFu) + (uint32_t)__popcll(bal_l & lt);
+            const uint64_t it = bt + (uint32_t)(x >> 40) + (uint32_t)__popcll(bal_t & lt);
+            if (large) out_large[il] = (uint16_t)count;
+            if (tip || bucket_head) {
+                const uint64_t first_item = run_full_start(sub_start, t0 + k0 + tid);
+                if (bucket_head) {                                                     // number of records/large/tips before this bucket
+                    const uint32_t bucket = keys[first_item].w[0] >> 16;
+                    int64_t *bf = bucket_first + (uint64_t)(bucket - b_lo) * 3;
+                    bf[0] = (int64_t)ie; bf[1] = (int64_t)il; bf[2] = (int64_t)it;
+                }
+                if (tip)
+                    for (int j = 0; j < words_per_tip; ++j) out_tips[it * words_per_tip + j] = keys[first_item].w[j];   // s2.cpp:826-830
+            }
+        }
+}
+
+// MGTA_EMIT_CHAIN=2: an output of emit_decide_write_kernel against that of the three-step route
+template <class T>
+__global__ __launch_bounds__(256) void emit_equal_kernel(const T *a, const T *b, uint64_t n, uint32_t *bad) {
+    for (uint64_t i = (uint64_t)blockIdx.x * 256 + threadIdx.x; i < n; i += (uint64_t)gridDim.x * 256)
+        if (a[i] != b[i]) atomicAdd(bad, 1u);
 }
 
 }  // namespace mgta
@@ -2298,12 +2579,16 @@ static uint64_t pool_bytes(const mgta_ctx *ctx) {
 // MGTA_EMIT_FUSED: the segment-local finish leaves the emitter's info byte of every key position behind, and the emitter compacts
 // those bytes instead of reading the keys again (see lds_finish) 0 never, 1 (default) wherever the sorted prefix lies inside the
 // (k-1)-mer, 2 the same and the run descriptors checked on the device against those of emit_compact_kernel (tests).
+// MGTA_EMIT_CHAIN: the runs are decided and their records written by one kernel behind two chained scans (emit_decide_write_kernel)
+// 0 never: emit_decide_kernel, three scans, a host round trip and emit_write_kernel, 1 (default) always, 2 both and every output
+// of the one kernel checked on the device against the three steps' (tests).
 struct SortModes {
-    int bias = 1, side = 1, fused = 1, wide = 1, emit_fused = 1;
+    int bias = 1, side = 1, fused = 1, wide = 1, emit_fused = 1, emit_chain = 1;
     static SortModes from_env() {
         const char *bias = getenv("MGTA_SORT_BIAS"), *side = getenv("MGTA_SORT_SIDE"), *fused = getenv("MGTA_SORT_FUSED"), *wide = getenv("MGTA_SORT_WIDE");
-        const char *emit_fused = getenv("MGTA_EMIT_FUSED");
-        return SortModes{bias ? atoi(bias) : 1, side ? atoi(side) : 1, fused ? atoi(fused) : 1, wide ? atoi(wide) : 1, emit_fused ? atoi(emit_fused) : 1};
+        const char *emit_fused = getenv("MGTA_EMIT_FUSED"), *emit_chain = getenv("MGTA_EMIT_CHAIN");
+        return SortModes{bias ? atoi(bias) : 1, side ? atoi(side) : 1, fused ? atoi(fused) : 1, wide ? atoi(wide) : 1, emit_fused ? atoi(emit_fused) : 1,
+                         emit_chain ? atoi(emit_chain) : 1};
     }
 };
 
@@ -3175,23 +3460,29 @@ struct Build {                                 // a build of keys of W words: wh
         uint64_t e_tiles = (n_items + kEmitTile - 1) / kEmitTile;
         uint64_t *d_scan_tmp = pool_get<uint64_t>(ctx, S_SCAN_TMP, scan_tmp_elems(std::max<uint64_t>(std::max(n_blocks, e_tiles), n_items / kDecideTile + 1)) * 8);
         // run descriptors, compacted in key order in one read of the keys (chained scan over the tiles).  Scratch layout for up to
-        // n_items runs (<= 7.01 bytes per key of a >= 12-byte-per-key buffer): start u32 | rec u16 | info u8 | full start u64 per 1024 runs
+        // n_items runs (<= 7.01 bytes per key of a >= 12-byte-per-key buffer): start u32 | rec u16 (three-step route) | info u8, on a
+        // 16-byte boundary | full start u64 per 1024 runs
         if (e_tiles > 0xFFFFFFFFull) { set_error("too many emit tiles"); return MGTA_EUNSUPPORTED; }
         unsigned long long *d_chain = pool_get<unsigned long long>(ctx, S_TILE_BASE, (e_tiles + 4) * 8);
         RunStarts sub_start;
         sub_start.lo = reinterpret_cast<uint32_t *>(scratch);
         uint16_t *rec = reinterpret_cast<uint16_t *>(scratch + n_items * 4);
-        uint8_t *info = reinterpret_cast<uint8_t *>(scratch + n_items * 6);
-        sub_start.base = reinterpret_cast<uint64_t *>(scratch + ((n_items * 7 + 7) & ~7ull));
-        // from the info bytes the sort left behind where it did (MGTA_EMIT_FUSED), else from the keys; returns the number of runs
-        auto compact = [&](const uint8_t *key_info, RunStarts st, uint8_t *st_info, uint64_t *m_out) {
+        const uint64_t info_at = (n_items * 6 + 15) & ~15ull;
+        uint8_t *info = reinterpret_cast<uint8_t *>(scratch + info_at);
+        sub_start.base = reinterpret_cast<uint64_t *>(scratch + ((info_at + n_items + 15) & ~15ull));
+        unsigned long long *d_dollar = reinterpret_cast<unsigned long long *>(pool_get<uint64_t>(ctx, S_SMALL, 4096) + 64);   // [kDollarSlots]
+        // from the info bytes the sort left behind where it did (MGTA_EMIT_FUSED), else from the keys; returns the number of runs and
+        // how many of them have a = $
+        auto compact = [&](const uint8_t *key_info, RunStarts st, uint8_t *st_info, uint64_t *m_out, uint64_t *n_dollar_out) {
             unsigned long long chain_out[3] = {0, 0, 0};           // total, ticket, error
+            unsigned long long dollar[kDollarSlots];
             const uint64_t tiles = key_info ? (n_items + kInfoTile - 1) / kInfoTile : e_tiles;   // (<= e_tiles: the chain's buffer holds either)
             EmitChain chain;
-            chain.state = d_chain; chain.total = d_chain + tiles;
+            chain.state = d_chain; chain.total = d_chain + tiles; chain.dollar = d_dollar;
             chain.ticket = reinterpret_cast<uint32_t *>(d_chain + tiles + 1); chain.error = reinterpret_cast<uint32_t *>(d_chain + tiles + 2);
             for (int attempt = 0; attempt < 2; ++attempt) {
                 MGTA_HIP_CHECK(hipMemsetAsync(d_chain, 0, (tiles + 4) * 8, stream));
+                MGTA_HIP_CHECK(hipMemsetAsync(d_dollar, 0, sizeof(dollar), stream));
                 const bool ticket = !(attempt == 0 && !ctx->force_full_lsd);
                 const dim3 grid((unsigned)tiles), block(kEmitThreads);
                 if (key_info && !ticket)
@@ -3203,15 +3494,18 @@ struct Build {                                 // a build of keys of W words: wh
                 else
                     hipLaunchKernelGGL((emit_compact_kernel<W, true>), grid, block, 0, stream, sorted, n_items, k, chain, (uint32_t)tiles, st, st_info);
                 MGTA_HIP_CHECK(hipMemcpyAsync(chain_out, d_chain + tiles, 24, hipMemcpyDeviceToHost, stream));
+                MGTA_HIP_CHECK(hipMemcpyAsync(dollar, d_dollar, sizeof(dollar), hipMemcpyDeviceToHost, stream));
                 MGTA_HIP_CHECK(hipStreamSynchronize(stream));
                 if ((uint32_t)chain_out[2] == 0) break;
             }
             if ((uint32_t)chain_out[2] != 0) { set_error("internal: chained scan of the emitter timed out"); return MGTA_EINTERNAL; }
             *m_out = chain_out[0];
+            *n_dollar_out = 0;
+            for (unsigned long long d : dollar) *n_dollar_out += d;
             return MGTA_OK;
         };
-        uint64_t m = 0;
-        if (int rc = compact(sorted_info, sub_start, info, &m)) return rc;
+        uint64_t m = 0, n_dollar = 0;
+        if (int rc = compact(sorted_info, sub_start, info, &m, &n_dollar)) return rc;
         if (sorted_info) {
             ctx->emit_fused_passes++;
             if (modes.emit_fused >= 2) {       // (test aid) the same from the keys, into the part of the scratch that is still idle
@@ -3224,8 +3518,10 @@ struct Build {                                 // a build of keys of W words: wh
                     set_error("internal: no room to check the emitter's info bytes");
                     return MGTA_EINTERNAL;
                 }
-                uint64_t m_ref = 0;
-                if (int rc = compact(nullptr, ref, ref_info, &m_ref)) return rc;
+                uint64_t m_ref = 0, n_dollar_ref = 0;
+                if (int rc = compact(nullptr, ref, ref_info, &m_ref, &n_dollar_ref)) return rc;
+                if (n_dollar_ref != n_dollar) { set_error("internal: the info bytes of the sort give %llu runs with a = $, the keys %llu",
+                                                          (unsigned long long)n_dollar, (unsigned long long)n_dollar_ref); return MGTA_EINTERNAL; }
                 uint32_t *d_bad = reinterpret_cast<uint32_t *>(pool_get<uint64_t>(ctx, S_SMALL, 4096) + 320);
                 uint32_t bad[2] = {0, 0};
                 MGTA_HIP_CHECK(hipMemsetAsync(d_bad, 0, 8, stream));
@@ -3243,25 +3539,108 @@ struct Build {                                 // a build of keys of W words: wh
                 }
             }
         }
-        uint64_t d_tiles = (m + kDecideTile - 1) / kDecideTile;
-        uint32_t *ce = pool_get<uint32_t>(ctx, S_CNT, d_tiles * 4 * 3), *cl = ce + d_tiles, *ct = cl + d_tiles;
-        uint64_t *be = pool_get<uint64_t>(ctx, S_BASE, d_tiles * 8 * 3), *bl = be + d_tiles, *bt = bl + d_tiles;
-        p.first = pool_get<int64_t>(ctx, S_FIRST, (uint64_t)MGTA_NUM_BUCKETS * 3 * 8);
-        MGTA_HIP_CHECK(hipMemsetAsync(p.first, 0xFF, (uint64_t)p.nb() * 3 * 8, stream));
-        hipLaunchKernelGGL(emit_decide_kernel, dim3((unsigned)d_tiles), dim3(kDecideThreads), 0, stream, sub_start, info, m, n_items,
-                           rec, ce, cl, ct);
-        exclusive_scan_u32(stream, ce, d_tiles, be, d_scan_tmp, d_tot3);
-        exclusive_scan_u32(stream, cl, d_tiles, bl, d_scan_tmp, d_tot3 + 1);
-        exclusive_scan_u32(stream, ct, d_tiles, bt, d_scan_tmp, d_tot3 + 2);
-        uint64_t tot3[3];
-        MGTA_HIP_CHECK(hipMemcpyAsync(tot3, d_tot3, 24, hipMemcpyDeviceToHost, stream));
-        MGTA_HIP_CHECK(hipStreamSynchronize(stream));
-        p.n_edges = tot3[0]; p.n_large = tot3[1]; p.n_tips = tot3[2];
-        p.rec = pool_get<uint16_t>(ctx, S_OUT_REC, p.n_edges * 2);
-        p.large = pool_get<uint16_t>(ctx, S_OUT_LARGE, p.n_large * 2);
-        p.tips = pool_get<uint32_t>(ctx, S_OUT_TIPS, p.n_tips * words_per_tip * 4);
-        hipLaunchKernelGGL((emit_write_kernel<W>), dim3((unsigned)d_tiles), dim3(kDecideThreads), 0, stream, sorted, sub_start, info, rec, m,
-                           n_items, be, bl, bt, words_per_tip, p.b_lo, p.rec, p.large, p.tips, p.first);
+        // the runs decided and their records written: by one kernel, by the three steps, or by both (MGTA_EMIT_CHAIN)
+        struct Out { uint16_t *rec = nullptr, *large = nullptr; uint32_t *tips = nullptr; int64_t *first = nullptr; uint64_t tot[3] = {0, 0, 0}; };
+        DevBuf t_rec, t_large, t_tips, t_first;                    // MGTA_EMIT_CHAIN=2: what the three steps write, next to the pass's own output
+        auto room = [&](bool pooled, int slot, DevBuf &tmp, uint64_t bytes) -> void * {
+            if (pooled) return pool_get<char>(ctx, slot, bytes);
+            tmp.alloc(bytes, &ctx->live_bytes, &ctx->peak_bytes);
+            return tmp.p;
+        };
+        const uint64_t first_b = (uint64_t)MGTA_NUM_BUCKETS * 3 * 8;
+        // E3 per-tile counts, three scans, the totals to the host to size the outputs, E5
+        auto three_steps = [&](bool pooled, Out &o) -> int {
+            const uint64_t d_tiles = (m + kDecideTile - 1) / kDecideTile;
+            uint32_t *ce = pool_get<uint32_t>(ctx, S_CNT, d_tiles * 4 * 3), *cl = ce + d_tiles, *ct = cl + d_tiles;
+            uint64_t *be = pool_get<uint64_t>(ctx, S_BASE, d_tiles * 8 * 3), *bl = be + d_tiles, *bt = bl + d_tiles;
+            o.first = static_cast<int64_t *>(room(pooled, S_FIRST, t_first, first_b));
+            MGTA_HIP_CHECK(hipMemsetAsync(o.first, 0xFF, (uint64_t)p.nb() * 3 * 8, stream));
+            hipLaunchKernelGGL(emit_decide_kernel, dim3((unsigned)d_tiles), dim3(kDecideThreads), 0, stream, sub_start, info, m, n_items,
+                               rec, ce, cl, ct);
+            exclusive_scan_u32(stream, ce, d_tiles, be, d_scan_tmp, d_tot3);
+            exclusive_scan_u32(stream, cl, d_tiles, bl, d_scan_tmp, d_tot3 + 1);
+            exclusive_scan_u32(stream, ct, d_tiles, bt, d_scan_tmp, d_tot3 + 2);
+            MGTA_HIP_CHECK(hipMemcpyAsync(o.tot, d_tot3, 24, hipMemcpyDeviceToHost, stream));
+            MGTA_HIP_CHECK(hipStreamSynchronize(stream));
+            o.rec = static_cast<uint16_t *>(room(pooled, S_OUT_REC, t_rec, o.tot[0] * 2));
+            o.large = static_cast<uint16_t *>(room(pooled, S_OUT_LARGE, t_large, o.tot[1] * 2));
+            o.tips = static_cast<uint32_t *>(room(pooled, S_OUT_TIPS, t_tips, o.tot[2] * words_per_tip * 4));
+            hipLaunchKernelGGL((emit_write_kernel<W>), dim3((unsigned)d_tiles), dim3(kDecideThreads), 0, stream, sorted, sub_start, info, rec, m,
+                               n_items, be, bl, bt, words_per_tip, p.b_lo, o.rec, o.large, o.tips, o.first);
+            return MGTA_OK;
+        };
+        // One kernel.  The outputs are sized before the totals are known: at most m records (the planner's n_items * 2 bytes of output
+        // cover them), a run above 254 holds at least 255 keys, and a tip is a run whose a is $.
+        auto chained = [&](Out &o) -> int {
+            if ((m >> kChainTipBits) != 0 || ((n_items / 255) >> (62 - kChainTipBits)) != 0) {
+                set_error("too many runs (%llu) or keys (%llu) for the emitter's chained scan", (unsigned long long)m, (unsigned long long)n_items);
+                return MGTA_EUNSUPPORTED;
+            }
+            const uint64_t tiles = (m + kChainTile - 1) / kChainTile;                  // (2 tiles + 2 <= e_tiles + 4 words of d_chain)
+            DecideChain dc;
+            dc.state_e = d_chain; dc.state_lt = d_chain + tiles; dc.totals = d_tot3;
+            dc.ticket = reinterpret_cast<uint32_t *>(d_chain + 2 * tiles); dc.error = reinterpret_cast<uint32_t *>(d_chain + 2 * tiles + 1);
+            o.rec = pool_get<uint16_t>(ctx, S_OUT_REC, m * 2);
+            o.large = pool_get<uint16_t>(ctx, S_OUT_LARGE, (n_items / 255 + 1) * 2);
+            o.tips = pool_get<uint32_t>(ctx, S_OUT_TIPS, n_dollar * words_per_tip * 4);
+            o.first = pool_get<int64_t>(ctx, S_FIRST, first_b);
+            unsigned long long err = 0;
+            for (int attempt = 0; attempt < 2; ++attempt) {
+                MGTA_HIP_CHECK(hipMemsetAsync(d_chain, 0, (2 * tiles + 2) * 8, stream));
+                MGTA_HIP_CHECK(hipMemsetAsync(d_tot3, 0, 24, stream));
+                MGTA_HIP_CHECK(hipMemsetAsync(o.first, 0xFF, (uint64_t)p.nb() * 3 * 8, stream));
+                const dim3 grid((unsigned)tiles), block(kDecideThreads);
+                if (attempt == 0 && !ctx->force_full_lsd)
+                    hipLaunchKernelGGL((emit_decide_write_kernel<W, false>), grid, block, 0, stream, sorted, sub_start, info, m, n_items, dc, (uint32_t)tiles,
+                                       words_per_tip, p.b_lo, o.rec, o.large, o.tips, o.first);
+                else
+                    hipLaunchKernelGGL((emit_decide_write_kernel<W, true>), grid, block, 0, stream, sorted, sub_start, info, m, n_items, dc, (uint32_t)tiles,
+                                       words_per_tip, p.b_lo, o.rec, o.large, o.tips, o.first);
+                MGTA_HIP_CHECK(hipMemcpyAsync(o.tot, d_tot3, 24, hipMemcpyDeviceToHost, stream));
+                MGTA_HIP_CHECK(hipMemcpyAsync(&err, d_chain + 2 * tiles + 1, 8, hipMemcpyDeviceToHost, stream));
+                MGTA_HIP_CHECK(hipStreamSynchronize(stream));
+                if ((uint32_t)err == 0) break;
+            }
+            if ((uint32_t)err != 0) { set_error("internal: chained scan of the emitter's records timed out"); return MGTA_EINTERNAL; }
+            if (o.tot[0] > m || o.tot[1] > n_items / 255 + 1 || o.tot[2] > n_dollar) {
+                set_error("internal: the emitter wrote %llu records, %llu large counts and %llu tips into room for %llu, %llu and %llu", (unsigned long long)o.tot[0],
+                          (unsigned long long)o.tot[1], (unsigned long long)o.tot[2], (unsigned long long)m, (unsigned long long)(n_items / 255 + 1), (unsigned long long)n_dollar);
+                return MGTA_EINTERNAL;
+            }
+            return MGTA_OK;
+        };
+        Out out, ref;
+        if (modes.emit_chain <= 0) {
+            if (int rc = three_steps(true, out)) return rc;
+        } else {
+            if (modes.emit_chain >= 2)
+                if (int rc = three_steps(false, ref)) return rc;
+            if (int rc = chained(out)) return rc;
+        }
+        if (modes.emit_chain >= 2) {           // (test aid) every output of the one kernel against the three steps'
+            uint32_t *d_bad = reinterpret_cast<uint32_t *>(pool_get<uint64_t>(ctx, S_SMALL, 4096) + 320);
+            uint32_t bad[4] = {0, 0, 0, 0};
+            MGTA_HIP_CHECK(hipMemsetAsync(d_bad, 0, 16, stream));
+            const bool same_totals = out.tot[0] == ref.tot[0] && out.tot[1] == ref.tot[1] && out.tot[2] == ref.tot[2];
+            auto grid_of = [&](uint64_t n) { return dim3((unsigned)std::min<uint64_t>((n + 255) / 256, (uint64_t)ctx->num_cus * 16)); };
+            if (same_totals) {
+                const uint64_t n_tw = out.tot[2] * words_per_tip, n_f = (uint64_t)p.nb() * 3;
+                if (out.tot[0]) hipLaunchKernelGGL((emit_equal_kernel<uint16_t>), grid_of(out.tot[0]), dim3(256), 0, stream, out.rec, ref.rec, out.tot[0], d_bad);
+                if (out.tot[1]) hipLaunchKernelGGL((emit_equal_kernel<uint16_t>), grid_of(out.tot[1]), dim3(256), 0, stream, out.large, ref.large, out.tot[1], d_bad + 1);
+                if (n_tw) hipLaunchKernelGGL((emit_equal_kernel<uint32_t>), grid_of(n_tw), dim3(256), 0, stream, out.tips, ref.tips, n_tw, d_bad + 2);
+                hipLaunchKernelGGL((emit_equal_kernel<int64_t>), grid_of(n_f), dim3(256), 0, stream, out.first, ref.first, n_f, d_bad + 3);
+            }
+            MGTA_HIP_CHECK(hipMemcpyAsync(bad, d_bad, 16, hipMemcpyDeviceToHost, stream));
+            MGTA_HIP_CHECK(hipStreamSynchronize(stream));
+            if (!same_totals || bad[0] || bad[1] || bad[2] || bad[3]) {
+                set_error("internal: one emit kernel gives %llu records, %llu large, %llu tips, the three steps %llu, %llu, %llu; %u records, %u large counts, "
+                          "%u tip words and %u bucket entries differ", (unsigned long long)out.tot[0], (unsigned long long)out.tot[1], (unsigned long long)out.tot[2],
+                          (unsigned long long)ref.tot[0], (unsigned long long)ref.tot[1], (unsigned long long)ref.tot[2], bad[0], bad[1], bad[2], bad[3]);
+                return MGTA_EINTERNAL;
+            }
+        }
+        p.rec = out.rec; p.large = out.large; p.tips = out.tips; p.first = out.first;
+        p.n_edges = out.tot[0]; p.n_large = out.tot[1]; p.n_tips = out.tot[2];
         S.ms_emit += t_ph.stop();
         return MGTA_OK;
     }
