@@ -547,6 +547,11 @@ class Context:
         side (mgta_astar_stats.n_over_limit): 1 .. 1024, 0 = the library's 1024.  Small values exercise that limit on small inputs."""
         check(self._L.mgta_ctx_set_search_page_limit(self.h, int(pages)), "mgta_ctx_set_search_page_limit")
 
+    def set_search_share(self, num: int = 1, den: int = 1):
+        """the search batches that run on this context (astar_search(..., run=this)) take num / den of the CUs, 1 <= num <= den (1 / 1 =
+        all of them): what two contexts that search one graph side by side set to 1 / 2 each.  The result does not depend on it."""
+        check(self._L.mgta_ctx_set_search_share(self.h, int(num), int(den)), "mgta_ctx_set_search_share")
+
     # ---- SdBG build ---------------------------------------------------------------------------
     def upload_reads(self, packed: np.ndarray, start_idx: np.ndarray) -> "Reads":
         packed = np.ascontiguousarray(packed, dtype=np.uint32)
@@ -948,10 +953,10 @@ def _set_cost(ctx: "Context", cost_rate) -> None:
     check(ctx._L.mgta_ctx_set_search_cost_rate(ctx.h, int(cost_rate)), "mgta_ctx_set_search_cost_rate")
 
 
-def _seeds(graph: "Graph", kmers: list[str], start_states, cost_rate) -> tuple[bytes, np.ndarray, int]:
-    """what both searches do first: the cost rate set, then (the first k + 1 letters of every seed k-mer back to back, the start states
-    as int32, the number of seeds)"""
-    _set_cost(graph.ctx, cost_rate)
+def _seeds(graph: "Graph", kmers: list[str], start_states, cost_rate, run: "Context | None" = None) -> tuple[bytes, np.ndarray, int]:
+    """what both searches do first: the cost rate set (on the context the batch runs on: the graph's own unless `run` names another), then
+    (the first k + 1 letters of every seed k-mer back to back, the start states as int32, the number of seeds)"""
+    _set_cost(graph.ctx if run is None else run, cost_rate)
     klen = graph.k + 1
     if any(len(s) < klen for s in kmers):
         raise MegaGtaError(f"seed k-mer shorter than k+1={klen}")
@@ -959,13 +964,15 @@ def _seeds(graph: "Graph", kmers: list[str], start_states, cost_rate) -> tuple[b
 
 
 def astar_search(graph: "Graph", fwd: DeviceHmm, rev: DeviceHmm, kmers: list[str], start_states, prune_len: int = 20,
-                 low_cov_penalty: float = 0.5, cache_mode: int = 0, cost_rate=0) -> tuple[list[SeedResult], dict]:
+                 low_cov_penalty: float = 0.5, cache_mode: int = 0, cost_rate=0, run: "Context | None" = None) -> tuple[list[SeedResult], dict]:
     """Batched HMM-guided A* (mgta_astar_batch).  start_states[i] = model position - 1 (search.cpp:157).
     cache_mode = B >= 1 shares paths between seeds: seed j's path (c_j expansions) is seen by the seeds >= j + B + c_j // cost_rate
     (cost_rate 0: no cost term; B = 1 then is the reference's sequential run; cost_rate < 0: j + B + c_j * |cost_rate|;
     cost_rate = (rate, knee, rate2): c_j // rate up to `knee` expansions, knee // rate + (c_j - knee) // rate2 beyond).
-    cache_mode = -1: no ordering at all (timing-dependent, the reference's multi-thread behaviour)."""
-    buf, ss, n = _seeds(graph, kmers, start_states, cost_rate)
+    cache_mode = -1: no ordering at all (timing-dependent, the reference's multi-thread behaviour).
+    run = a context of the graph's device other than the graph's own: the batch takes that context's stream, work memory, cost rate and
+    share of the CUs (mgta_astar_batch_on; Context.set_search_share), so that two threads can search one graph side by side."""
+    buf, ss, n = _seeds(graph, kmers, start_states, cost_rate, run)
     results: list[SeedResult] = [None] * n
 
     def side(p):
@@ -979,6 +986,10 @@ def astar_search(graph: "Graph", fwd: DeviceHmm, rev: DeviceHmm, kmers: list[str
         return 0
 
     st = _lib.AstarStats()
+    if run is not None:
+        check(run._L.mgta_astar_batch_on(run.h, graph.h, fwd.h, rev.h, buf, ss.ctypes.data, n, prune_len, low_cov_penalty, cache_mode,
+                                         _lib.CONTIG_SINK(sink), None, C.byref(st)), "mgta_astar_batch_on")
+        return results, st.as_dict()
     check(graph.ctx._L.mgta_astar_batch(graph.h, fwd.h, rev.h, buf, ss.ctypes.data, n, prune_len, low_cov_penalty, cache_mode,
                                         _lib.CONTIG_SINK(sink), None, C.byref(st)), "mgta_astar_batch")
     return results, st.as_dict()

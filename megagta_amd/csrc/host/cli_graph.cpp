@@ -201,6 +201,15 @@ void search_plan(size_t ns, int *window, int *rate, long long *knee, int *rate2)
     if (*rate < 1 || *knee <= 0 || *rate2 <= *rate) { *knee = 0; *rate2 = 0; }           // (one rate throughout)
 }
 
+// a progress line of one gene's search.  With MEGAGTA_SEARCH_LANES=2 two threads log side by side, and logf writes a line in three pieces:
+// the lines of two genes that ended together came out torn ("[megagta_amd]     [megagta_amd] Done rplB: ...\nDone nirK: ...").  The stream's
+// own lock (recursive: the fprintf calls inside take it again) keeps the pieces of one line together.
+template <class... A> static void gene_logf(const char *fmt, A... a) {
+    flockfile(stderr);
+    logf(fmt, a...);
+    funlockfile(stderr);
+}
+
 int main_search(int argc, char **argv) {
     RssLine rss;
     if (argc < 7) {
@@ -225,7 +234,7 @@ int main_search(int argc, char **argv) {
     const size_t klen = (size_t)gk + 1;
     auto run_gene = [&](const GeneEntry &gene, mgta_ctx *ctx) {
         double tg = now_s();
-        logf("START %s", gene.name.c_str());
+        gene_logf("START %s", gene.name.c_str());
         mgta_hmm *fw = upload_hmm(ctx, gene.fwd_hmm), *rv = upload_hmm(ctx, gene.rev_hmm);
         std::vector<std::string> kmers;
         std::vector<int32_t> start;
@@ -239,7 +248,7 @@ int main_search(int argc, char **argv) {
             mgta_hmm_free(fw); mgta_hmm_free(rv);
             return;
         }
-        logf("Searching from %zu starting kmers", kmers.size());
+        gene_logf("Searching from %zu starting kmers", kmers.size());
         std::string flat;
         flat.reserve(kmers.size() * klen);
         for (const std::string &km : kmers) {
@@ -264,18 +273,18 @@ int main_search(int argc, char **argv) {
         search_plan(ns, &window, &rate, &knee, &rate2);
         if ((knee ? mgta_ctx_set_search_cost_curve(ctx, rate, (uint64_t)knee, rate2) : mgta_ctx_set_search_cost_rate(ctx, rate)) != MGTA_OK)
             die("MEGAGTA_CACHE_COST_RATE must be >= -64 (%s)", mgta_last_error());
-        logf("sharing rule: window %d, cost term %d expansions per seed%s", window, rate,
-             knee ? (" up to " + std::to_string(knee) + " expansions, " + std::to_string(rate2) + " beyond").c_str() : "");
+        gene_logf("sharing rule: window %d, cost term %d expansions per seed%s", window, rate,
+                  knee ? (" up to " + std::to_string(knee) + " expansions, " + std::to_string(rate2) + " beyond").c_str() : "");
         if (mgta_astar_batch_on(ctx, g, fw, rv, flat.data(), start.data(), (int64_t)kmers.size(), prune, pen, window, sink_contig, &fo, &st) != MGTA_OK)
             die("mgta_astar_batch: %s", mgta_last_error());
         fclose(out);
         mgta_hmm_free(fw); mgta_hmm_free(rv);
-        logf("Done %s: time %.4lf (%lld expansions, %.1f ms on device; %lld searches grew in place, %lld run again, %lld resumed passes, pool %.1f of %.1f GB, "
-             "reserve %.2f of %.1f GB; largest search %lld nodes / %lld expansions, %lld sides over the page limit%s)",
-             gene.name.c_str(), now_s() - tg, (long long)st.n_expansions, st.ms_total, (long long)st.n_grown, (long long)st.n_retries, (long long)st.n_resumes,
-             st.pool_used / 1e9, st.pool_bytes / 1e9, st.reserve_used / 1e9, st.reserve_bytes / 1e9, (long long)st.max_search_nodes,
-             (long long)st.max_search_expansions, (long long)st.n_over_limit,
-             st.order_abandoned ? "; the searches outgrew the pool: paths shared WITHOUT an order from there on" : "");
+        gene_logf("Done %s: time %.4lf (%lld expansions, %.1f ms on device; %lld searches grew in place, %lld run again, %lld resumed passes, pool %.1f of %.1f GB, "
+                  "reserve %.2f of %.1f GB; largest search %lld nodes / %lld expansions, %lld sides over the page limit%s)",
+                  gene.name.c_str(), now_s() - tg, (long long)st.n_expansions, st.ms_total, (long long)st.n_grown, (long long)st.n_retries, (long long)st.n_resumes,
+                  st.pool_used / 1e9, st.pool_bytes / 1e9, st.reserve_used / 1e9, st.reserve_bytes / 1e9, (long long)st.max_search_nodes,
+                  (long long)st.max_search_expansions, (long long)st.n_over_limit,
+                  st.order_abandoned ? "; the searches outgrew the pool: paths shared WITHOUT an order from there on" : "");
     };
     // the genes of the list one after the other (search.cpp:124).  MEGAGTA_SEARCH_LANES=2 searches two genes side by side on one
     // graph, each batch on its own context (stream + work memory) and half of the CUs (mgta_astar_batch_on): measured and NOT the

@@ -122,7 +122,7 @@ def describe(fn: str, i: int, a, argtype):
     if a is None:
         return "null", None
     if isinstance(a, Handle):
-        return dict(handle=a.name), None
+        return dict(handle=a.name), a                            # (a script may ask WHICH handle of that name it was given)
     if isinstance(a, (bytes, bytearray)):
         return dict(bytes=len(a), sha=sha(a)), None
     if isinstance(a, C._CFuncPtr):
@@ -272,10 +272,12 @@ each("switch", [
     ("set_chimera_groups", lambda w: w.ctx.set_chimera_groups(2)), ("release_scratch", lambda w: w.ctx.release_scratch()),
     ("set_search_arena", lambda w: w.ctx.set_search_arena(10, 1 << 20)), ("set_search_arena default", lambda w: w.ctx.set_search_arena()),
     ("set_search_page_limit", lambda w: w.ctx.set_search_page_limit(3)), ("last_counting", lambda w: w.ctx.last_counting()),
+    ("set_search_share", lambda w: w.ctx.set_search_share(1, 2)), ("set_search_share default", lambda w: w.ctx.set_search_share()),
     ("close", lambda w: (w.ctx.close(), w.ctx.h, w.ctx.close())), ("graph free", lambda w: (w.graph.free(), w.graph.h, w.graph.free())),
     ("reads free", lambda w: (w.reads.free(), w.reads.h, w.reads.free())),
 ])
 each("switch fails", [("set_mem_limit", lambda w: w.ctx.set_mem_limit(1))], script={"mgta_ctx_set_mem_limit": -2})
+each("switch fails", [("set_search_share", lambda w: w.ctx.set_search_share(2, 1))], script={"mgta_ctx_set_search_share": -2})
 
 
 @case("context create", script={"mgta_ctx_create": Handle("ctx")})
@@ -595,6 +597,36 @@ for name, fn in (("astar_search", api.astar_search), ("astar_search_packed", api
                 ("cost curve", lambda w, fn=fn: search(fn, w, KMERS, [3, 7], cost_rate=(1000, 5000, 100))), ("cost curve without knee", lambda w, fn=fn: search(fn, w, KMERS, [3, 7], cost_rate=[1000, 0, 100])),
                 ("short k-mer", lambda w, fn=fn: search(fn, w, ["ACGTA", "ACGT"], [3, 7])), ("non-ascii k-mer", lambda w, fn=fn: search(fn, w, ["ACGéA"], [3]))])
 each("astar_search", [("sink called", lambda w: search(api.astar_search, w, KMERS, [3, 7]))], script={"mgta_astar_batch": astar_sink})
+
+
+def search_on(w, kmers, states, *a, own=False, answer=None, **kw):
+    """astar_search(..., run=): on a second context of the world's library (own: on the graph's own, named).  Its handle is another object
+    of the same name, so the records cannot tell the two contexts apart; the stand-in does: it answers MGTA_EINVAL (-2) unless the cost
+    rate is set on the run context and the batch is given the run context's handle first and the graph's second."""
+    run = w.ctx
+    if not own:
+        run = api.Context.__new__(api.Context)
+        run._L, run.h = w.lib, Handle("ctx")
+
+    def cost(objs, nth):
+        return 0 if objs[0] is run.h else -2
+
+    def batch(objs, nth):
+        if objs[0] is not run.h or objs[1] is not w.graph.h:
+            return -2
+        return answer(objs[1:], nth) if answer else 0
+
+    w.lib.script.update(mgta_ctx_set_search_cost_rate=cost, mgta_ctx_set_search_cost_curve=cost, mgta_astar_batch_on=batch)
+    return api.astar_search(w.graph, w.hmm, w.rev, kmers, states, *a, run=run, **kw)
+
+
+each("astar_search on", [("none", lambda w: search_on(w, [], [])), ("two", lambda w: search_on(w, KMERS, [3, 7])),
+                         ("arguments", lambda w: search_on(w, KMERS, np.array([3, 7]), 25, 0.25, 4, 1000)),
+                         ("cost curve", lambda w: search_on(w, KMERS, [3, 7], cost_rate=(1000, 5000, 100))),
+                         ("the graph's own context", lambda w: search_on(w, KMERS, [3, 7], cache_mode=1, own=True)),
+                         ("short k-mer", lambda w: search_on(w, ["ACGTA", "ACGT"], [3, 7])),
+                         ("sink called", lambda w: search_on(w, KMERS, [3, 7], answer=astar_sink)),
+                         ("fails", lambda w: search_on(w, KMERS, [3, 7], answer=lambda objs, nth: -6))])
 PACKED_TEXT = C.create_string_buffer(b"ACacgtaGTT", 10)
 
 
