@@ -638,7 +638,8 @@ int mgta_ctx_set_phase_chunk(mgta_ctx *, uint32_t slots);   /* fragment slots pe
 
 /* ------------------------------------------------------------------------------------------------
  * Read recruitment by the gene's model: which reads of the library the profile HMM places in one of six frames.  The rule is this
- * library's own; it is not HMMER's and nothing here is checked against it.  Needs no graph.
+ * library's own; it is not HMMER's and nothing here is checked against it.  Needs no graph.  Two modes (mgta_recruit_params.mode):
+ * the blocks Stretch .. Best below state mode 0, global in the stretch; mode 1, local, follows them.
  *   Input.     The reads [0, n_short_reads) of an uploaded library (reads_reversed as in mgta_reads_match_contigs) and a model of
  *              mgta_hmm_load, both of this context.
  *   Frames.    For a read of n bases: frame f in {0, 1, 2} is the read as sequenced from base f, frame f in {3, 4, 5} its reverse
@@ -664,13 +665,41 @@ int mgta_ctx_set_phase_chunk(mgta_ctx *, uint32_t slots);   /* fragment slots pe
  * n_unscored (status 2), n_recruited and n_recruited_frame[f] by best frame.  Everything but ms_*, blocks_per_cu, waves_per_block,
  * grid_blocks, lds_bytes, msc_in_lds, rows_per_wave and chunk is a function of (tables, reads, params) alone, the same to the last
  * bit for every chunk and across runs: integer atomics only, one writer per record.
- * It is global in the stretch: a read that runs over an end of the gene has to place its flank and scores low.  One stretch per
- * frame, no flanking states, no Forward score, no prefilter, one device; the reverse model is not used.
+ * The rule above is mode 0 = MGTA_RECRUIT_GLOBAL, the default (params NULL, or mode 0: the same bytes).  It is global in the stretch:
+ * a read that runs over an end of the gene has to place its flank as inserts and scores low, and where the gene's own stop cuts a
+ * frame in two only the longer run is looked at.
+ *
+ * mode 1 = MGTA_RECRUIT_LOCAL places reads locally.  Frames, translation, letters, tables and e(j, x) are as above.
+ *   Stretches. Every maximal run of residues without a stop that has at least min_aa residues is scored, in every frame, in ascending
+ *              position.
+ *   Score.     The maximum, over all non-empty substrings x_a .. x_b of the stretch, of what mgta_seqs_align returns for that substring
+ *              as a protein: the same recurrence and the same adds, bit for bit.  As one sweep over the stretch it is the recurrence
+ *              of mgta_seqs_align with three changes.  (1) The match state of every row takes B = 0 as its first candidate, entering
+ *              at column j and row i; on equality B wins over M, I, D.  (2) The delete state VD[i][j + 1] is fed by the value
+ *              VM[i][j] would have WITHOUT its B candidate: a path does not delete straight after its first match, exactly as row 1
+ *              of mgta_seqs_align has no delete state.  (3) The alignment may end in the match state of any row: score = max over
+ *              i, j of VM[i][j].
+ *   Ties.      In every maximum the candidate written first wins: B, M, I, D.  The end cell is the cell of the lowest column that
+ *              reaches the score, and in that column the lowest row.
+ *   Record.    model_to = the end column; model_from = the column of the match state the winning path entered at, carried through
+ *              the recurrence with the winner of each maximum; aa_from, aa_len = the ALIGNED SPAN, first to last residue the path
+ *              emits, 0-based in the frame's translation -- not the whole stretch as in mode 0.
+ *   Best.      The stretch with the highest score; on equality the lower frame, then the lower aa_from.  status 0: as above.
+ *              status 1 (every scored stretch is -inf): score -inf, the frame and the whole first scored stretch, model_from =
+ *              model_to = 0.  status 2: no stretch of min_aa residues exists.  Recruited as above.
+ *   Outputs.   col_depth as above; n_frames_scored counts the scored stretches, n_cells = the sum of stretch length * M over them.
+ * Per read the local score is >= the global score, so at one threshold the local set contains the global set.  Local scores of
+ * unrelated sequence are always positive: on a synthetic model of 120 columns, 300 stop-free 50-mers at random had a median of 12.0
+ * bits and a maximum of 17.6 bits, so in local mode the default of 20 bits sits close to noise.  It remains a knob.
+ * In both modes: no flanking states with a cost, no Forward score, no E-values, no prefilter, one device; the reverse model is not used.
  * Limits: a read of more than 3 * 4096 + 2 bases among the scanned ones is MGTA_EINVAL naming the first such read, with nothing
- * written.  MGTA_EINVAL also: NULL context / model / reads / hit_bits (n_short_reads > 0), n_short_reads above the upload, a model
- * or reads of another context, min_aa < 1, a NaN min_score.  n_short_reads = 0: col_depth and stats all zero.
+ * written.  MGTA_EINVAL also, before anything is written: NULL context / model / reads / hit_bits (n_short_reads > 0), n_short_reads
+ * above the upload, a model or reads of another context, min_aa < 1, a NaN min_score, a mode other than 0 and 1, mode 1 with a model
+ * of more than 1 048 575 columns (entry column and row share a register).  n_short_reads = 0: col_depth and stats all zero.
  * ------------------------------------------------------------------------------------------------ */
-typedef struct mgta_recruit_params { int32_t min_aa; int32_t pad; double min_score; } mgta_recruit_params;
+#define MGTA_RECRUIT_GLOBAL 0
+#define MGTA_RECRUIT_LOCAL 1
+typedef struct mgta_recruit_params { int32_t min_aa; int32_t mode /* MGTA_RECRUIT_GLOBAL (0, the default) or MGTA_RECRUIT_LOCAL */; double min_score; } mgta_recruit_params;
 typedef struct mgta_recruit_rec { double score; int32_t model_from, model_to; uint16_t aa_from, aa_len; uint8_t frame, status; uint8_t pad[2]; } mgta_recruit_rec;
 typedef struct mgta_recruit_stats {
     int64_t n_reads, n_frames_scored, n_cells;

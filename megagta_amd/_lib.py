@@ -240,7 +240,7 @@ class PhaseStats(Struct):
 
 
 class RecruitParams(Struct):
-    _fields_ = [("min_aa", C.c_int32), ("pad", C.c_int32), ("min_score", C.c_double)]
+    _fields_ = [("min_aa", C.c_int32), ("mode", C.c_int32), ("min_score", C.c_double)]
 
 
 class RecruitRec(Struct):

@@ -284,13 +284,18 @@ class Context:
                 reads_reversed: bool = True) -> dict:
         """mgta_reads_recruit: which of the first n_short_reads reads (default: all of `reads`) the model places in one of six frames,
         by the rule of include/megagta_hip.h.  params = dict(min_aa=, min_score= in nats, or min_bits=); missing = 20 residues and 20
-        bits.  -> dict(hit_bits = uint64[ceil(n / 64)], bits = bool[n], recs = recruit.REC[n] or None, col_depth = uint64[M] or None,
+        bits.  local=True (or mode=1, MGTA_RECRUIT_LOCAL) scores every stop-free stretch of a frame and in it the best placement of
+        any substring; aa_from and aa_len of a record are then the aligned span.  The default is the global rule (mode 0).
+        -> dict(hit_bits = uint64[ceil(n / 64)], bits = bool[n], recs = recruit.REC[n] or None, col_depth = uint64[M] or None,
         stats).  Needs no graph."""
-        p = _known(params, ("min_aa", "min_score", "min_bits"), "recruit")
+        p = _known(params, ("min_aa", "min_score", "min_bits", "local", "mode"), "recruit")
         if "min_score" in p and "min_bits" in p:
             raise ValueError("recruit parameters: min_score (nats) or min_bits, not both")
+        if "local" in p and "mode" in p:
+            raise ValueError("recruit parameters: local or mode, not both")
         par = _lib.RecruitParams()
         par.min_aa = int(p.get("min_aa", 20))
+        par.mode = int(p["mode"]) if "mode" in p else int(bool(p.get("local", False)))
         par.min_score = float(p["min_score"]) if "min_score" in p else float(p.get("min_bits", 20.0)) * LN2
         ns = reads.n_reads if n_short_reads is None else int(n_short_reads)
         words = np.zeros(max(1, (ns + 63) // 64), dtype=np.uint64)          # (never an empty buffer: NULL is an error of its own)

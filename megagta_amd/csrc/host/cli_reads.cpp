@@ -132,12 +132,14 @@ int main_matchreads(int argc, char **argv) {
 // and a worker's resident graphs and library stay as they are.  The rule and the file formats are this project's own: INTEGRATION.md
 // 2h'; megagta_amd/recruit.py prints the same bytes.
 int main_recruit(int argc, char **argv) {
-    const char *usage = "Usage: megagta recruit <model.hmm> <read.lib> <out_prefix> [--min-bits B] [--min-aa N]\n";
+    const char *usage = "Usage: megagta recruit <model.hmm> <read.lib> <out_prefix> [--min-bits B] [--min-aa N] [--local]\n";
     if (argc < 4) { fputs(usage, stderr); return 1; }
     double min_bits = 20.0;
     long long min_aa = 20;
+    bool local_mode = false;
     for (int i = 4; i < argc; ++i) {
         const std::string a = argv[i];
+        if (a == "--local") { local_mode = true; continue; }
         if ((a != "--min-bits" && a != "--min-aa") || i + 1 >= argc) { fputs(usage, stderr); return 1; }
         const char *text = argv[++i];
         if (a == "--min-aa") {
@@ -165,14 +167,14 @@ int main_recruit(int argc, char **argv) {
     mgta_reads *rd = reads_upload(ctx, pr);
     std::vector<uint64_t> bits((size_t)((n_reads + 63) / 64) + 1), depth((size_t)M + 1);
     std::vector<mgta_recruit_rec> recs((size_t)n_reads + 1);
-    const mgta_recruit_params par{(int32_t)min_aa, 0, min_bits * 0.6931471805599453};
+    const mgta_recruit_params par{(int32_t)min_aa, local_mode ? MGTA_RECRUIT_LOCAL : MGTA_RECRUIT_GLOBAL, min_bits * 0.6931471805599453};
     mgta_recruit_stats st;
     if (mgta_reads_recruit(ctx, hmm, rd, 1, n_reads, &par, bits.data(), recs.data(), depth.data(), &st) != MGTA_OK) die("mgta_reads_recruit: %s", mgta_last_error());
     mgta_reads_free(rd);
     mgta_hmm_free(hmm);
-    logf("recruited reads of %s (%d columns, >= %g bits, stretches >= %lld residues): %lld of %lld reads, %lld frames scored, %lld cells, %lld reads unaligned, %lld "
+    logf("recruited reads of %s (%d columns, %s, >= %g bits, stretches >= %lld residues): %lld of %lld reads, %lld frames scored, %lld cells, %lld reads unaligned, %lld "
          "unscored; %lld rows per wave, %lld reads per grab, %lld waves per workgroup, %lld per CU, LDS %lld (scan %.1f ms, fill %.1f ms); wall %.3f s", model.c_str(), M,
-         min_bits, min_aa, (long long)st.n_recruited, (long long)st.n_reads, (long long)st.n_frames_scored, (long long)st.n_cells, (long long)st.n_unaligned,
+         local_mode ? "local" : "global", min_bits, min_aa, (long long)st.n_recruited, (long long)st.n_reads, (long long)st.n_frames_scored, (long long)st.n_cells, (long long)st.n_unaligned,
          (long long)st.n_unscored, (long long)st.rows_per_wave, (long long)st.chunk, (long long)st.waves_per_block, (long long)st.blocks_per_cu, (long long)st.lds_bytes,
          st.ms_scan, st.ms_fill, now_s() - t0);
     std::string fa, table = "#read\tframe\taa_from\taa_len\tbits\tmodel_from\tmodel_to\n", cols = "#column\tdepth\n", summary;
@@ -197,6 +199,7 @@ int main_recruit(int argc, char **argv) {
     appendf(summary, "reads_scanned\t%lld\nreads_scored\t%lld\nreads_recruited\t%lld\n", (long long)st.n_reads, (long long)(st.n_reads - st.n_unscored), (long long)st.n_recruited);
     for (int f = 0; f < 6; ++f) appendf(summary, "recruited_frame%d\t%lld\n", f, (long long)st.n_recruited_frame[f]);
     for (size_t l = 0; l < libs.size(); ++l) appendf(summary, "recruited_lib%zu\t%lld\n", l, per_lib[l]);
+    if (local_mode) summary += "recruit_mode\tlocal\n";
     write_or_die(out_prefix + "_reads.fa", fa);
     write_or_die(out_prefix + ".txt", table);
     write_or_die(out_prefix + "_cols.txt", cols);

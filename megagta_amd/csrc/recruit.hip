@@ -17,6 +17,16 @@
 // traceback of mgta_seqs_align would reach.  (3) A last residue offers its match value to its stretch's slot in LDS; columns are
 // offered in ascending order (strips ascend, and within a strip lane l is a step behind lane l - 1), so a strict > keeps the lowest.
 // The rows at a strip's edge are 24 bytes per residue: X, Y and their two columns.
+//
+// Local mode (MGTA_RECRUIT_LOCAL, the kernel's second template parameter; the global instantiation is the code above, unchanged).
+// The first pass gives every run of at least min_aa residues between two stops its rows and its slot, not only the longest, so the
+// rows are swept whenever 64 slots are full.  In the sweep the match state of every row takes B = 0 as its first candidate, the delete
+// state is fed by the match value without that candidate (one more add), and what is carried with X, Y and I is the entry column in
+// the low 20 bits and the entry row (of the wave's rows) in the 12 above them: still one register per value, six cross-lane moves a
+// step and 24 bytes per edge row.  A lane keeps the best match value of its column over the rows of the stretch it is in (strict >:
+// the lowest row) and offers it to the stretch's slot when it passes the stretch's last residue; a lane passes that residue a step
+// behind its left neighbour and strips ascend, so the slot's strict > still keeps the lowest column.  The slot holds the end row
+// above the end column in the same packing, and the stretch's first row beside the read and the frame.
 #include <algorithm>
 #include <cmath>
 #include <vector>
@@ -38,6 +48,8 @@ constexpr uint32_t kRecruitMaxChunk = 64;              // reads per queue grab: 
 constexpr size_t kRecruitLdsBudget = 80 * 1024;        // of a workgroup while the longest read allows it: two fit a CU
 constexpr size_t kRecruitLdsMax = 160 * 1024;          // of a workgroup at all
 constexpr uint32_t kFirstResidue = 0x80u, kLastResidue = 0x20u;
+constexpr int kLocalColBits = 20;                      // local mode: a column below, a row of the wave (< 4096) above, in one register
+constexpr int kLocalColMask = (1 << kLocalColBits) - 1;
 
 __constant__ char kRecruitCodon[65] = "KNKNTTTTRSRSIIMIQHQHPPPPRRRRLLLLEDEDAAAAGGGGVVVV*Y*YSSSS*CWCLFLF";   // codon = 16 b0 + 4 b1 + b2, A C G T = 0 .. 3
 
@@ -63,9 +75,9 @@ struct RecruitArgs {
 
 struct StretchSlot {                 // 24 bytes
     double score;
-    int32_t jend, entry;
-    uint32_t read_frame;             // read of the chunk | frame << 8
-    uint32_t aa;                     // aa_from | aa_len << 16
+    int32_t jend, entry;             // local mode: | end row << 20, | entry row << 20
+    uint32_t read_frame;             // read of the chunk | frame << 8; local mode: | the stretch's first row << 12
+    uint32_t aa;                     // aa_from | aa_len << 16, of the stretch
 };
 
 // what a wave has in LDS beside the profile's
@@ -87,7 +99,9 @@ __device__ __forceinline__ char frame_residue(const RecruitArgs &a, const char *
     return codon[16u * b0 + 4u * b1 + b2];
 }
 
-// All T residues of the wave's rows over the M nodes: the slots' score, end column and entry column.
+// All T residues of the wave's rows over the M nodes: the slots' score, end column and entry column (LOCAL: the best cell of any row,
+// end and entry as column | row << 20).
+template <bool LOCAL>
 __device__ __forceinline__ void recruit_sweep(const RecruitLds &w, int T, int M, int A, const double *tsc, const ProfileLds &lds) {
     const size_t M1 = (size_t)M + 1;
     const int lane = lane_id();
@@ -102,6 +116,8 @@ __device__ __forceinline__ void recruit_sweep(const RecruitLds &w, int T, int M,
         double x_out = NINF, y_out = NINF, x_held = NINF, v_i = NINF;
         int ex_out = 0, ey_out = 0, ex_held = 0, e_i = 0;
         int q = 0;                                                        // the stretch of this lane's row
+        double run = NINF;                                                // LOCAL: the best match value of this column in stretch q,
+        int run_row = 0, run_ent = 0;                                     // its row (the lowest) and its entry
         const int n_steps = T + wd - 1;
         for (int t = 0; t < n_steps; ++t) {
             const int i = t - lane;                                       // this lane's row, from 0
@@ -125,14 +141,20 @@ __device__ __forceinline__ void recruit_sweep(const RecruitLds &w, int T, int M,
             const uint32_t c = w.res[r];
             const bool first = (c & kFirstResidue) != 0;                  // (row 0 is always one: the rows before it reset too)
             const double e = emission(lds.alpha, nd.mrow, c & 0x5Fu);
-            if (first) { x_use = 0.0; e_m = j; v_i = NINF; v_d = NINF; }  // row 1 of a stretch: B, no insert and no delete state
+            double v_c = NINF;                                            // LOCAL: the match value without its B candidate
+            int e_c = 0;
+            if (LOCAL) {
+                if (first) { x_use = NINF; v_i = NINF; v_d = NINF; }      // row 1 of a stretch: nothing continues into it
+                v_c = x_use + e; e_c = e_m;
+                if (!(x_use > 0.0)) { x_use = 0.0; e_m = (int)((uint32_t)j | (uint32_t)r << kLocalColBits); }   // B first: it wins an equality
+            } else if (first) { x_use = 0.0; e_m = j; v_i = NINF; v_d = NINF; }        // row 1 of a stretch: B, no insert and no delete state
             const double v_m = x_use + e;
             const double c0 = v_m + nd.mm, c1 = v_i + nd.im, c2 = v_d + nd.dm;
             double X = c0; int eX = e_m;
             if (c1 > X) { X = c1; eX = e_i; }
             if (c2 > X) { X = c2; eX = e_d; }
-            const double d0 = v_m + nd.md, d1 = v_d + nd.dd;
-            double Y = d0; int eY = e_m;
+            const double d0 = (LOCAL ? v_c : v_m) + nd.md, d1 = v_d + nd.dd;    // (LOCAL: no delete straight after the first match)
+            double Y = d0; int eY = LOCAL ? e_c : e_m;
             if (d1 > Y) { Y = d1; eY = e_d; }
             if (first) Y = NINF;                                          // row 1 has no delete state
             const double i0 = v_m + nd.mi, i1 = v_i + nd.ii;
@@ -146,8 +168,12 @@ __device__ __forceinline__ void recruit_sweep(const RecruitLds &w, int T, int M,
                     w.bxy[2 * i + 1] = Y; w.bent[2 * i + 1] = eY;         // the delete state of (i, j + 1)
                     if (i + 1 < T) { w.bxy[2 * i + 2] = X; w.bent[2 * i + 2] = eX; }   // the candidate of the match state of (i + 1, j + 1)
                 }
+                if (LOCAL && v_m > run) { run = v_m; run_row = i; run_ent = e_m; }
                 if (c & kLastResidue) {
-                    if (v_m > w.slot[q].score) { w.slot[q].score = v_m; w.slot[q].jend = j; w.slot[q].entry = e_m; }
+                    if (LOCAL) {
+                        if (run > w.slot[q].score) { w.slot[q].score = run; w.slot[q].jend = (int)((uint32_t)j | (uint32_t)run_row << kLocalColBits); w.slot[q].entry = run_ent; }
+                        run = NINF;
+                    } else if (v_m > w.slot[q].score) { w.slot[q].score = v_m; w.slot[q].jend = j; w.slot[q].entry = e_m; }
                     ++q;
                 }
             }
@@ -177,7 +203,7 @@ __global__ __launch_bounds__(256) void recruit_lengths_kernel(const uint64_t *st
     if (first != ~0ull) atomicMin(&out[1], first);
 }
 
-template <bool MSC_LDS>
+template <bool MSC_LDS, bool LOCAL>
 __global__ __launch_bounds__(256) void recruit_kernel(RecruitArgs a) {
     extern __shared__ __align__(16) unsigned char lds_raw[];
     const size_t n_msc = ((size_t)a.M + 1) * a.A;
@@ -204,15 +230,24 @@ __global__ __launch_bounds__(256) void recruit_kernel(RecruitArgs a) {
         const auto flush = [&]() {
             if (ns == 0) return;
             wave_lds_fence();
-            recruit_sweep(w, (int)T, a.M, a.A, tsc, lds);
+            recruit_sweep<LOCAL>(w, (int)T, a.M, a.A, tsc, lds);
             for (uint32_t q = 0; q < ns; ++q) {
                 const uint32_t rf = w.slot[q].read_frame, aa = w.slot[q].aa;
                 const double sc = w.slot[q].score;
                 if ((uint32_t)lane == (rf & 0xFFu)) {
-                    if (best.n_scored == 0) { best.frame = rf >> 8; best.aa = aa; }
+                    const uint32_t frame = LOCAL ? (rf >> 8) & 7u : rf >> 8;
+                    if (best.n_scored == 0) { best.frame = frame; best.aa = aa; }
                     ++best.n_scored;
                     best.residues += aa >> 16;
-                    if (sc > best.score) { best.score = sc; best.from = w.slot[q].entry; best.to = w.slot[q].jend; best.frame = rf >> 8; best.aa = aa; }
+                    if (sc > best.score) {                                // stretches ascend by frame and position: the earlier keeps an equal score
+                        const int32_t entry = w.slot[q].entry, jend = w.slot[q].jend;
+                        best.score = sc; best.frame = frame;
+                        if (LOCAL) {                                      // the aligned span: entry row .. end row of the stretch's rows
+                            const uint32_t row_in = (uint32_t)entry >> kLocalColBits, row_out = (uint32_t)jend >> kLocalColBits;
+                            best.from = entry & kLocalColMask; best.to = jend & kLocalColMask;
+                            best.aa = ((aa & 0xFFFFu) + (row_in - (rf >> 12))) | ((row_out - row_in + 1u) << 16);
+                        } else { best.from = entry; best.to = jend; best.aa = aa; }
+                    }
                 }
             }
             wave_lds_fence();
@@ -226,32 +261,40 @@ __global__ __launch_bounds__(256) void recruit_kernel(RecruitArgs a) {
                 const int o = f >= 3 ? 1 : 0, same = o == a.reversed;     // the stored order, complemented when reversed, is orientation `reversed`
                 const uint32_t comp = o ? 3u : 0u, off = f % 3;
                 const uint32_t ncod = len >= off ? (len - off) / 3 : 0;
-                // the longest run without a stop, the first of equally long ones
+                // the residues [aa_from, aa_from + aa_len) of the frame into the rows, and their slot
+                const auto take = [&](uint32_t aa_from, uint32_t aa_len) {
+                    if (T + aa_len > a.rows || ns == kRecruitSlots) flush();
+                    for (uint32_t c = (uint32_t)lane; c < aa_len; c += 64) {
+                        const uint32_t ch = (uint32_t)(uint8_t)frame_residue(a, w.codon, s0, len, same, comp, off, aa_from + c);
+                        w.res[T + c] = (uint8_t)(ch | (c == 0 ? kFirstResidue : 0u) | (c == aa_len - 1 ? kLastResidue : 0u));
+                    }
+                    if (lane == 0) {
+                        w.slot[ns].score = NINF; w.slot[ns].jend = 0x7FFFFFFF; w.slot[ns].entry = 0;
+                        w.slot[ns].read_frame = rl | (f << 8) | (LOCAL ? T << 12 : 0u); w.slot[ns].aa = aa_from | (aa_len << 16);
+                    }
+                    T += aa_len; ++ns;
+                };
+                // the longest run without a stop, the first of equally long ones; LOCAL: every run of min_aa residues, as it is found
                 uint32_t run_start = 0, aa_len = 0, aa_from = 0;
-                for (uint32_t c0 = 0; c0 < ncod; c0 += 64) {
+                const uint32_t n_look = LOCAL ? ncod + 1 : ncod;           // (LOCAL: the frame's end closes its last run like a stop)
+                for (uint32_t c0 = 0; c0 < n_look; c0 += 64) {
                     const uint32_t c = c0 + (uint32_t)lane;
-                    bool stop = false;
+                    bool stop = LOCAL && c == ncod;
                     if (c < ncod) stop = frame_residue(a, w.codon, s0, len, same, comp, off, c) == '*';
                     uint64_t m = __ballot(stop);
                     while (m) {
                         const uint32_t p = c0 + (uint32_t)__builtin_ctzll(m);
-                        if (p - run_start > aa_len) { aa_len = p - run_start; aa_from = run_start; }
+                        if (LOCAL) {
+                            if (p - run_start >= a.min_aa) take(run_start, p - run_start);
+                        } else if (p - run_start > aa_len) { aa_len = p - run_start; aa_from = run_start; }
                         run_start = p + 1;
                         m &= m - 1;
                     }
                 }
+                if (LOCAL) continue;
                 if (ncod - run_start > aa_len) { aa_len = ncod - run_start; aa_from = run_start; }
                 if (aa_len == 0 || aa_len < a.min_aa) continue;
-                if (T + aa_len > a.rows || ns == kRecruitSlots) flush();
-                for (uint32_t c = (uint32_t)lane; c < aa_len; c += 64) {
-                    const uint32_t ch = (uint32_t)(uint8_t)frame_residue(a, w.codon, s0, len, same, comp, off, aa_from + c);
-                    w.res[T + c] = (uint8_t)(ch | (c == 0 ? kFirstResidue : 0u) | (c == aa_len - 1 ? kLastResidue : 0u));
-                }
-                if (lane == 0) {
-                    w.slot[ns].score = NINF; w.slot[ns].jend = 0x7FFFFFFF; w.slot[ns].entry = 0;
-                    w.slot[ns].read_frame = rl | (f << 8); w.slot[ns].aa = aa_from | (aa_len << 16);
-                }
-                T += aa_len; ++ns;
+                take(aa_from, aa_len);
             }
         }
         flush();
@@ -324,7 +367,16 @@ int mgta_reads_recruit(mgta_ctx *ctx, const mgta_hmm *hmm, const mgta_reads *rea
     if (params) par = *params;
     if (par.min_aa < 1) { set_error("mgta_reads_recruit: min_aa = %d (>= 1 is required)", (int)par.min_aa); return MGTA_EINVAL; }
     if (std::isnan(par.min_score)) { set_error("mgta_reads_recruit: min_score must not be NaN"); return MGTA_EINVAL; }
+    if (par.mode != MGTA_RECRUIT_GLOBAL && par.mode != MGTA_RECRUIT_LOCAL) {
+        set_error("mgta_reads_recruit: mode = %d (0 = MGTA_RECRUIT_GLOBAL or 1 = MGTA_RECRUIT_LOCAL is required)", (int)par.mode);
+        return MGTA_EINVAL;
+    }
     const int M = hmm->M, A = hmm->A;
+    const bool local = par.mode == MGTA_RECRUIT_LOCAL;
+    if (local && M > kLocalColMask) {
+        set_error("mgta_reads_recruit: local mode takes a model of at most %d columns, this one has %d", kLocalColMask, M);
+        return MGTA_EINVAL;
+    }
     if (n_short_reads == 0) {
         if (col_depth) memset(col_depth, 0, (size_t)M * 8);
         if (stats) memset(stats, 0, sizeof(*stats));
@@ -363,7 +415,7 @@ int mgta_reads_recruit(mgta_ctx *ctx, const mgta_hmm *hmm, const mgta_reads *rea
         size_t lds = fixed + (size_t)waves * per_wave;
         const bool msc_lds = lds + msc_bytes <= budget;
         if (msc_lds) lds += msc_bytes;
-        const auto kernel = msc_lds ? recruit_kernel<true> : recruit_kernel<false>;
+        const auto kernel = local ? (msc_lds ? recruit_kernel<true, true> : recruit_kernel<false, true>) : (msc_lds ? recruit_kernel<true, false> : recruit_kernel<false, false>);
         const int blocks_per_cu = blocks_per_cu_of(kernel, waves, lds);
         // reads per grab: the switch, else 4 where every wave in flight still gets several grabs (400 k reads of 150 bases, M = 300:
         // 97.2 ms at 1, 94.4 at 4, 95.7 at 16, 112.6 at 64, where the last grabs leave waves idle; profiles/recruit/README.md)

@@ -3,11 +3,13 @@ no device.  The definitions are those of mgta_reads_recruit (include/megagta_hip
 
   recruit_reads.fa     `>r<i>` records of the recruited reads, exactly as matchreads.py writes a matched-reads file
   recruit.txt          #read<TAB>frame<TAB>aa_from<TAB>aa_len<TAB>bits<TAB>model_from<TAB>model_to, one line per recruited read,
-                       ascending i; bits = score / ln 2 as %.4f
+                       ascending i; bits = score / ln 2 as %.4f; aa_from and aa_len as the record holds them: the scored stretch in
+                       global mode, the aligned span in local mode
   recruit_cols.txt     #column<TAB>depth, one line per model column 1 .. M
   recruit_summary.txt  key<TAB>value lines: reads_scanned, reads_scored, reads_recruited, recruited_frame<f> (f = 0 .. 5),
-                       recruited_lib<s> per library, and, when the matched reads are known, recruited_and_matched and
-                       assembled_fraction (%.4f; 0.0000 when nothing is recruited)
+                       recruited_lib<s> per library, in local mode (MGTA_RECRUIT_LOCAL) the line recruit_mode<TAB>local, and, when
+                       the matched reads are known, recruited_and_matched and assembled_fraction (%.4f; 0.0000 when nothing is
+                       recruited)
 """
 from __future__ import annotations
 
@@ -87,13 +89,15 @@ def assembled_fraction(recruited, matched) -> tuple[int, float]:
     return both, (both / rec.size if rec.size else 0.0)
 
 
-def summary_text(stats: dict, per_lib=None, recruited=None, matched=None) -> str:
+def summary_text(stats: dict, per_lib=None, recruited=None, matched=None, local: bool = False) -> str:
     """the text of recruit_summary.txt from the stats of Context.recruit; per_lib = lib_counts(...) of a run with libraries;
-    recruited and matched = the two index sets when --match-reads was part of the run"""
+    recruited and matched = the two index sets when --match-reads was part of the run; local = the run was made in local mode"""
     lines = ["reads_scanned\t%d" % stats["n_reads"], "reads_scored\t%d" % (stats["n_reads"] - stats["n_unscored"]), "reads_recruited\t%d" % stats["n_recruited"]]
     lines += ["recruited_frame%d\t%d" % (f, int(c)) for f, c in enumerate(stats["n_recruited_frame"])]
     if per_lib is not None:
         lines += ["recruited_lib%d\t%d" % (s, int(c)) for s, c in enumerate(per_lib)]
+    if local:
+        lines.append("recruit_mode\tlocal")
     if matched is not None:
         both, frac = assembled_fraction(recruited, matched)
         lines += ["recruited_and_matched\t%d" % both, "assembled_fraction\t%.4f" % frac]
@@ -106,7 +110,7 @@ def parse_summary(text: str) -> dict:
         key, _, val = ln.partition("\t")
         if not key or not val:
             raise ValueError(f"recruit summary text: bad line {ln!r}")
-        out[key] = float(val) if key == "assembled_fraction" else int(val)
+        out[key] = val if key == "recruit_mode" else float(val) if key == "assembled_fraction" else int(val)
     return out
 
 
@@ -125,15 +129,17 @@ def append_assembled(summary_path: str, recruit_fa: str, match_fa: str) -> tuple
     return both, frac
 
 
-def write_files(out_dir: str, res: dict, packed: np.ndarray, start: np.ndarray, lib_end=None, matched=None, reversed_storage: bool = True) -> dict:
-    """the four files of a gene under out_dir from res = Context.recruit(..., recs=True, cols=True); -> their paths"""
+def write_files(out_dir: str, res: dict, packed: np.ndarray, start: np.ndarray, lib_end=None, matched=None, reversed_storage: bool = True,
+                local: bool = False) -> dict:
+    """the four files of a gene under out_dir from res = Context.recruit(..., recs=True, cols=True); local = it ran in local mode;
+    -> their paths"""
     import os
     n = int(res["stats"]["n_reads"])
     idx = hit_indices(res["hit_bits"], n)
     paths = {name: os.path.join(out_dir, name) for name in ("recruit_reads.fa", "recruit.txt", "recruit_cols.txt", "recruit_summary.txt")}
     texts = {"recruit_reads.fa": match_reads_text(idx, packed, start, reversed_storage), "recruit.txt": recruit_text(res["recs"], idx),
              "recruit_cols.txt": cols_text(res["col_depth"]),
-             "recruit_summary.txt": summary_text(res["stats"], lib_counts(res["hit_bits"], lib_end) if lib_end is not None else None, idx, matched)}
+             "recruit_summary.txt": summary_text(res["stats"], lib_counts(res["hit_bits"], lib_end) if lib_end is not None else None, idx, matched, local)}
     for name, text in texts.items():
         with open(paths[name], "w") as fh:
             fh.write(text)
