@@ -1,6 +1,8 @@
 """The layout of helpers.reads_behind_marks, checked on its numbers: a broken layout must not be able to hide a failure of the device
-stages that tests/test_far_offsets_gpu.py runs on it.  About 2 GB of host memory per mode."""
+stages that tests/test_far_offsets_gpu.py runs on it.  About 2 GB of host memory per mode.  And the list of those stages, held against
+the entry points of include/megagta_hip.h that take the reads."""
 import os
+import re
 
 import numpy as np
 import pytest
@@ -75,6 +77,37 @@ def test_layout_on_the_numbers(payload, mode):
     assert np.isin(nz, np.concatenate([own, decoy])).all()
     assert not np.isin(decoy, own).any() and decoy.max() < own.min()      # the decoys lie in the first filler run
     assert np.unique(packed[decoy]).size > 0.99 * decoy.size               # random bits, not one pattern
+
+
+def entry_points_taking_reads(hdr):
+    """the functions of the header text that take a `const mgta_reads *`: comments dropped as helpers.header_structs drops them, a
+    declaration = a name, its parameters up to the closing parenthesis (over any number of lines) and a semicolon"""
+    hdr = re.sub(r"/\*.*?\*/|//[^\n]*", " ", hdr, flags=re.S)
+    decls = re.findall(r"\b(mgta_\w+)\s*\(([^()]*)\)\s*;", hdr)
+    return {name for name, params in decls if re.search(r"\bconst\s+mgta_reads\s*\*", params)}
+
+
+def test_every_entry_point_that_takes_reads_is_covered_or_excused():
+    """a new read-consuming entry point fails here until tests/test_far_offsets_gpu.py names the tests that run it behind the marks (or
+    says why it never indexes bases by start[r])"""
+    from tests import test_far_offsets_gpu as FG
+    found = entry_points_taking_reads(H.header_text())
+    assert {"mgta_sdbg_build_resident", "mgta_findstart", "mgta_reads_recruit", "mgta_reads_pileup_gapped"} <= found       # the parser finds them, over line breaks too
+    assert "mgta_reads_free" not in found and "mgta_reads_upload" not in found
+    assert entry_points_taking_reads(H.header_text() + "\nint mgta_x(const mgta_reads *);\n") == found | {"mgta_x"}
+    assert entry_points_taking_reads(H.header_text() + "\nint mgta_y(mgta_ctx *,\n    const   mgta_reads\n*reads, int k);\n") == found | {"mgta_y"}
+    assert set(FG.COVERED) | set(FG.NOT_READ) == found
+    assert not set(FG.COVERED) & set(FG.NOT_READ)
+    assert all(isinstance(why, str) and why.strip() for why in FG.NOT_READ.values())
+    marks = FG.pytestmark if isinstance(FG.pytestmark, (list, tuple)) else [FG.pytestmark]
+    assert any(m.name == "gpu" for m in marks)                            # the module's mark: every test of it carries it
+    for entry, names in FG.COVERED.items():
+        assert names, entry
+        for name in names:
+            assert name.startswith("test_") and callable(getattr(FG, name, None)), (entry, name)
+    # and no test of the module is left out of the table
+    tests = {name for name, f in vars(FG).items() if name.startswith("test_") and callable(f) and getattr(f, "__module__", None) == FG.__name__}
+    assert tests == {name for names in FG.COVERED.values() for name in names}
 
 
 def test_the_helper_refuses_what_it_cannot_lay_out(payload):
